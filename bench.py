@@ -16,12 +16,21 @@ waited for ONCE, inside the timed region.  N GPUs: one process per GPU,
 each with its own 1024 scans (weak scaling).
 
 Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events on the
-context's stream; `cpu_baseline` times the REFERENCE'S OWN CODE (kind "reference":
+context's stream.  A plain run sets up, warms up, times the steps, writes the outputs
+(--dump-outputs) and prints the line; everything else is measured with --full only:
+the live PMC counter passes and the device-copy ceiling of `roofline`, the exchange
+step alone (N > 1), `cpu_baseline`, `parity_checked` and the extra blocks.
+`cpu_baseline` times the REFERENCE'S OWN CODE (kind "reference":
 oracle/_ref = StateEstimator.hpp compiled verbatim against stand-in third-party
 headers, built where /root/reference exists and shipped with the snapshot) on a
 bounded sample of the same scans on this box's cores — or the oracle (kind "port")
 when that library did not travel; `parity_checked` compares the GPU results of the
 timed batch with that sample.
+
+--dump-outputs DIR writes what the last timed step computed, as the caller of
+lins_batch_run receives it (ctx.download(): per scan state, covariance, norms, flags),
+to DIR/<name>.npy in float64.  The inputs are seeded: the same arguments give the same
+inputs in every run, so two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -407,6 +416,30 @@ def e2e_rates(pkg, ieskf, host, pairs, args):
     return out
 
 
+def ensure_built(g):
+    """g.build() only when the libraries on disk were not built from these sources (the content digest build() stamps):
+    a tree that is already built, perhaps by another user, is benchmarked as it is, without write access to it."""
+    try:
+        with open(g.STAMP) as f:
+            current = all(os.path.exists(p) for p in g.LIBS) and f.read().strip() == g._source_digest()
+    except OSError:
+        current = False
+    if not current:
+        g.build()
+
+
+def dump_outputs(out_dir, res):
+    """The per-scan results of the last timed step (rank 0's shard), one float64 array per field, scan-major."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"state": np.stack([r.state for r in res]), "cov": np.stack([r.cov for r in res])}
+    for f in ("residual_norm", "update_norm", "iters", "converged", "diverged", "m_surf", "m_corner"):
+        arrays[f] = np.array([getattr(r, f) for r in res], dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` with no launcher around it: re-exec under torch.distributed.run, one rank per
     GPU on this node (the driver's own N > 1 command line does the same from outside and is honoured as is)."""
@@ -473,8 +506,11 @@ def main():
     ap.add_argument("--iters", type=int, default=10, help="IESKF iterations per scan")
     ap.add_argument("--search", default=os.environ.get("LINS_SEARCH", "auto"))
     ap.add_argument("--cpu-sample", type=int, default=192, help="scans timed on the CPU oracle (0 = skip)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the reference-stop-rule and single-scan blocks")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip cpu_baseline and parity_checked")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the reference-stop-rule, single-scan and other extra blocks")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: live PMC passes, copy ceiling, gather alone, CPU leg, extra blocks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's results to DIR/<name>.npy")
     ap.add_argument("--dry-run", action="store_true", help="launcher + pose gather only, gloo, no GPU (test aid)")
     args = ap.parse_args()
 
@@ -493,7 +529,7 @@ def main():
 
     import __graft_entry__ as g
 
-    g.build()
+    ensure_built(g)
     pkg = importlib.import_module(PKG)
     host = importlib.import_module(PKG + ".host")
     ieskf = importlib.import_module(PKG + ".ieskf")
@@ -591,12 +627,15 @@ def main():
     # timed steps took on the device is the span of all of them, not the sum of per-launch durations.
     span_ms = ctx.runs_span_ms(min(args.steps, 64))
     launches = ctx.launch_ms_history(min(args.steps, 64))
-    # N > 1: what a scaling curve needs to explain itself — every rank's own kernel time and step time, and the cost of the
-    # exchange step alone (the same flat all-gather, back to back with one wait, outside the timed region)
+    res = ctx.download() if rank == 0 else None  # what the last timed step computed (before anything else runs on the context)
+    if res is not None and args.dump_outputs:
+        dump_outputs(args.dump_outputs, res)
+    # N > 1: what a scaling curve needs to explain itself — every rank's own kernel time and step time, and (--full) the
+    # cost of the exchange step alone (the same flat all-gather, back to back with one wait, outside the timed region)
     per_rank = None
     if use_dist:
         gather_us = None
-        if c_abi_gather:
+        if c_abi_gather and args.full:
             reps = 20
             ctx.sync()
             tg = time.perf_counter()
@@ -613,10 +652,10 @@ def main():
                     "note": "kernel_ms: HIP events of the update kernel on each rank's stream (mean of the timed steps); gather_us: the "
                             "all-gather of the pose records alone, 20 back to back, one wait"}
 
-    # device-copy ceiling of this box: a streaming float4 copy inside the context's arenas,
+    # device-copy ceiling of this box (--full): a streaming float4 copy inside the context's arenas,
     # measured after the timed region (it overwrites the uploaded clouds)
     copy_gbs = None
-    if rank == 0:
+    if rank == 0 and args.full:
         import ctypes as C
 
         L = ieskf.lib()
@@ -645,14 +684,14 @@ def main():
             ctx.rccl_destroy()
 
     if rank == 0:
-        res = ctx.download()
         n_div = sum(1 for r in res if r.diverged)
         value = iters_all * args.steps / elapsed_max
         k_ms = span_ms / min(args.steps, 64)  # device time per step over the timed region (launches of successive steps overlap)
         # algorithmic bytes per launch = sum_scans B_iter(scan) * iterations(scan); with the
         # fixed-iteration mode every non-diverged scan runs args.iters iterations
         alg_bytes = bytes_iter_local / len(pairs) * iters_local
-        traffic = traffic_from_profiles(args.search, live=(world == 1))  # (single-GPU runs only: the counter passes are runs of their own)
+        # live counter passes: --full single-GPU runs only (they are runs of their own); otherwise the committed record
+        traffic = traffic_from_profiles(args.search, live=(world == 1 and args.full))
         achieved = alg_bytes / (k_ms * 1e-3) / 1e9
         out = {
             "metric": "ESKF iterations/sec (16x1800 VLP-16, ~2k feat)",
@@ -741,9 +780,9 @@ def main():
                 "kernel": "grid_index_kernel", "kernel_ms": index_ms,
                 "with_build_each_step": {"ms_per_step": step_ms + index_ms, "value": iters_all / ((step_ms + index_ms) * 1e-3),
                                          "frac": alg_bytes / ((k_ms + index_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS}}
-        if not args.no_cpu and args.cpu_sample > 0 and world == 1:  # (the CPU leg: single-GPU runs only)
+        if args.full and not args.no_cpu and args.cpu_sample > 0 and world == 1:  # (the CPU leg: single-GPU runs only)
             out.update(cpu_leg(pkg, args, prm, pairs, res))
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             out["reference_stop_rule"] = reference_stop_rule_rate(pkg, ieskf, pairs, args, max_targets)
             out["single_scan"] = single_scan_latency(pkg, ieskf, pairs[0])
             out["two_batches_in_flight"] = two_batches_in_flight(pkg, ieskf, pairs, args, max_targets)

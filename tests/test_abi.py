@@ -50,10 +50,14 @@ def test_device_entries_of_the_host_header_are_in_the_hip_library(ieskf):
 
 def test_no_compute_without_a_device(pkg, ieskf):
     """Creating a context without a GPU fails loudly (there is no CPU fallback)."""
-    import pytest
-    import torch
+    import sys
 
-    if torch.cuda.is_available():
+    import pytest
+
+    # (asked in a child process: torch brings a HIP runtime of its own, and this process must not initialise a second one
+    # next to the library's — the GPU tests that follow in the same session would find no device)
+    gpu = subprocess.run([sys.executable, "-c", "import torch; print(int(torch.cuda.is_available()))"], stdout=subprocess.PIPE, check=True)
+    if gpu.stdout.strip() == b"1":
         pytest.skip("a GPU is present")
     with pytest.raises(ieskf.LinsError, match="-5|-2"):
         ieskf.IeskfContext(pkg.default_params())

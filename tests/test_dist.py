@@ -210,10 +210,47 @@ def test_bench_honours_an_external_launcher_and_rejects_a_mismatch():
     assert p.returncode != 0 and b"WORLD_SIZE=1" in p.stderr
 
 
-def test_bench_says_in_one_line_when_the_node_has_too_few_gpus():
-    import torch
+def test_bench_builds_only_a_tree_that_is_not_built(monkeypatch, tmp_path):
+    """bench.py calls build() only when the libraries are missing or were built from other sources (the digest build()
+    stamps): a tree built earlier, perhaps by another user, is benchmarked without write access to it (build() takes a
+    lock file in the package directory)."""
+    import importlib.util
 
-    n = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    import __graft_entry__ as g
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    so, stamp = tmp_path / "lib.so", tmp_path / "stamp"
+    so.write_bytes(b"")
+    stamp.write_text(g._source_digest() + "\n")
+    calls = []
+    monkeypatch.setattr(g, "build", lambda: calls.append(1))
+    monkeypatch.setattr(g, "LIBS", [str(so)])
+    monkeypatch.setattr(g, "STAMP", str(stamp))
+    bench.ensure_built(g)
+    assert calls == []  # built from these sources: nothing to do, nothing written
+    stamp.write_text("0" * 64 + "\n")
+    bench.ensure_built(g)
+    assert calls == [1]  # other sources
+    stamp.write_text(g._source_digest() + "\n")
+    monkeypatch.setattr(g, "LIBS", [str(so), str(tmp_path / "missing.so")])
+    bench.ensure_built(g)
+    assert calls == [1, 1]  # a library missing
+    monkeypatch.setattr(g, "STAMP", str(tmp_path / "no_stamp"))
+    monkeypatch.setattr(g, "LIBS", [str(so)])
+    bench.ensure_built(g)
+    assert calls == [1, 1, 1]  # never stamped
+
+
+def test_bench_says_in_one_line_when_the_node_has_too_few_gpus():
+    import subprocess
+    import sys
+
+    # (counted in a child process: no second HIP runtime initialised in this one, see tests/test_abi.py)
+    n = int(subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count() if torch.cuda.is_available() else 0)"],
+                           stdout=subprocess.PIPE, check=True).stdout)
     p = _bench("--gpus", str(n + 2), "--steps", "1")
     assert p.returncode != 0
     assert f"needs {n + 2} GPUs on this node, found {n}".encode() in p.stderr

@@ -11,10 +11,11 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(extra_env, port):
+def _run(extra_env, port, extra_args=()):
     env = dict(os.environ, **extra_env)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu", "--steps", "3", "--warmup", "1", "--batch", "320"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu", "--steps", "3", "--warmup", "1", "--batch", "320",
+                        *extra_args],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
@@ -31,12 +32,12 @@ def test_bench_prints_one_json_line_last():
 
 
 def test_bench_checks_its_own_results_and_times_the_reference():
-    """The default command's CPU leg on a small sample: parity_checked compares the timed batch's GPU results with the
+    """The --full command's CPU leg on a small sample: parity_checked compares the timed batch's GPU results with the
     oracle on the same scans; cpu_baseline is the reference's own code when oracle/_ref travelled."""
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "300", "--cpu-sample",
-                        "16", "--no-extras"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+                        "16", "--no-extras", "--full"], cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     d = json.loads([l for l in p.stdout.decode().splitlines() if l.strip()][-1])
     pc = d["parity_checked"]
@@ -45,6 +46,32 @@ def test_bench_checks_its_own_results_and_times_the_reference():
     assert cb["value"] > 0 and cb["kind"] in ("reference", "port")
     if os.path.exists(os.path.join(ROOT, "oracle", "_ref", "liblins_ref.so")):
         assert cb["kind"] == "reference" and cb["port"]["reduced_all_cores"]["value"] > 0
+
+
+def test_bench_dumps_what_the_timed_steps_computed(tmp_path, pkg, host):
+    """--dump-outputs: the last timed step's per-scan results as float64 .npy files, the same for the same arguments, and
+    equal to the oracle on the first scans of the batch (the same fixed-iteration update)."""
+    import numpy as np
+    from oracle import oracle
+
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        r = _run({}, 0, ("--dump-outputs", str(d)))
+        assert r["steps"] == 3 and "cpu_baseline" not in r and "single_scan" not in r  # (a plain run: the headline only)
+    a = {f.stem: np.load(f) for f in sorted(dirs[0].glob("*.npy"))}
+    b = {f.stem: np.load(f) for f in sorted(dirs[1].glob("*.npy"))}
+    assert a.keys() == b.keys() and {"state", "cov", "iters", "converged", "diverged", "m_surf", "m_corner"} <= a.keys()
+    assert all(v.dtype == np.float64 and v.shape[0] == 320 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["state"].shape == (320, 19) and a["cov"].shape == (320, 18, 18)
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    prm = pkg.default_params(num_iter=10, fixed_iters=1)
+    for i, p in enumerate(host.synth_pair(i) for i in range(4)):
+        w = oracle.ieskf(prm, p, oracle.FORM_DENSE, oracle.NN_KDTREE)
+        assert (a["iters"][i], a["diverged"][i], a["m_surf"][i], a["m_corner"][i]) == (w.iters, w.diverged, w.m_surf, w.m_corner)
+        assert np.abs(a["state"][i, :3] - w.state[:3]).max() <= 1e-6
+        assert np.abs(a["cov"][i] - w.cov).max() <= 1e-9 * np.abs(w.cov).max()
 
 
 def test_bench_with_the_rccl_gather_forced_on_one_gpu():

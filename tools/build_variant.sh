@@ -4,5 +4,5 @@
 # SLP vectoriser: the canary of tests/test_gpu_canaries.py)
 name=$1; shift
 cd "$(dirname "$0")/../lins---lidar-inertial-slam_amd/csrc" && mkdir -p ../../ab/$name &&
-  make -j32 BUILD=build_$name OUT=../../ab/$name EXTRA="$*" $VARIANT_MAKE ../../ab/$name/liblins_ieskf.so > /tmp/build_$name.log 2>&1 &&
+  make -j16 BUILD=build_$name OUT=../../ab/$name EXTRA="$*" $VARIANT_MAKE ../../ab/$name/liblins_ieskf.so > ../../ab/build_$name.log 2>&1 &&
   mv ../../ab/$name/liblins_ieskf.so ../../ab/$name.so && rmdir ../../ab/$name && rm -rf build_$name && echo "built ab/$name.so ($*)"

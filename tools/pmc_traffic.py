@@ -20,17 +20,17 @@ import os
 import sqlite3
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-OUT = os.path.join(ROOT, "gpurun_out")
 
 
 def counters(cmd, counter, tag):
     """One rocprofv3 pass (PMC + kernel trace only).  counter: a name -> {kernel: (sum, dispatches)};
     a list of names -> {kernel: {name: sum / dispatches}}."""
     names = [counter] if isinstance(counter, str) else list(counter)
-    d = os.path.join(OUT, f"_pmc_{tag}_{names[0]}")
+    d = tempfile.mkdtemp(prefix=f"pmc_{tag}_{names[0]}_")  # (outside the tree: bench.py --full may run where it cannot write)
     subprocess.run(["rm", "-rf", d])
     # (counters are summed per LAUNCH: the runs under the counters pin the one-launch form of a step — lins_set_launch_queues 1 —
     # so that "per launch" is "per step of the whole batch", as in every earlier round's record)

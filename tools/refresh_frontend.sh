@@ -12,7 +12,7 @@ timeout 900 python -m pytest tests -q -m gpu > $out/${tag}_pytest_gpu.log 2>&1; 
 cat $out/canaries.log >> $out/${tag}_pytest_gpu.log 2>/dev/null
 timeout 600 python tools/pmc_traffic.py $tag > $out/${tag}_pmc_traffic.log 2>&1; tail -3 $out/${tag}_pmc_traffic.log
 cp $out/${tag}_pmc_traffic.json profiles/ 2>/dev/null   # (bench.py reads the record from profiles/, stamp-checked)
-timeout 600 python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+timeout 600 python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 tail -1 $out/${tag}_bench.json | cut -c1-300
 {
   timeout 300 python tools/e2e_rate.py 2>&1 | tail -2
