@@ -25,6 +25,7 @@
 #define LINS_HOST_H_
 
 #include "lins_ieskf.h"
+#include "lins_map.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -195,6 +196,16 @@ int lins_synth_seq_truth(uint32_t seed, double tau, double* xyyaw, double* speed
 int lins_host_perform_ieskf(lins_ctx* ctx, const lins_params* prm,
                             const lins_scan_pair* in, lins_result* out,
                             int32_t* used_icp_fallback);
+
+/* ---- the mapping node's local map on the CPU (host/local_map.cpp) ------------
+ * The restatement lins_local_map_build is checked against, bit for bit: the last min(window, n_frames) of `frames`
+ * (oldest first) moved into the map frame and VoxelGrid-filtered, and the scan's four VoxelGrid passes
+ * (LM:1201-1349; include/lins_map.h).  out[c] holds at least as many points as cloud c reads: the window's corner
+ * points / surf + outlier points, the scan's corner / surf / outlier / surf + outlier points.  sizes: as
+ * lins_local_map_build reports them.  Returns LINS_E_INPUT for a scan / frame / pose outside the input contract
+ * (nothing written), else LINS_OK (the entry's own status in sizes->status). */
+int lins_host_local_map(const lins_keyframe* frames, int n_frames, int window, const lins_local_scan* scan,
+                        lins_point* const* out, lins_local_map_sizes* sizes);
 
 #ifdef __cplusplus
 }

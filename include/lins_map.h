@@ -29,7 +29,7 @@ typedef struct lins_map_problem {
   const lins_point* scan_surf;   /* laserCloudSurfTotalLastDS */
   int32_t n_map_corner, n_map_surf, n_scan_corner, n_scan_surf;
   float transform[6]; /* transformTobeMapped: rx, ry, rz, tx, ty, tz */
-  int32_t reserved[2]; /* [0]: flags (LINS_MAP_REUSE), [1]: 0 */
+  int32_t reserved[2]; /* [0]: flags (LINS_MAP_REUSE or LINS_MAP_LOCAL), [1]: 0 */
 } lins_map_problem;
 
 /* reserved[0] flag: the two map clouds of this problem are the ones of the previous call at the same batch index
@@ -37,6 +37,11 @@ typedef struct lins_map_problem {
  * sizes match, the maps already resident on the device — uploaded and bucketed into 1 m cells by the last call —
  * are used as they are; map_corner / map_surf are not read.                                                     */
 #define LINS_MAP_REUSE 1
+/* reserved[0] flag: problem k is entry k of the last lins_local_map_build — maps and queries are the clouds that call
+ * built on the device (laserCloudCornerFromMapDS / SurfFromMapDS, laserCloudCornerLastDS / SurfTotalLastDS) and are
+ * read where they lie; map_* / scan_* / n_* are not read.  Every problem of the batch carries it (else LINS_E_ARG), it
+ * is not combined with LINS_MAP_REUSE (LINS_E_ARG), and the batch has the size of the last build (else LINS_E_STATE). */
+#define LINS_MAP_LOCAL 2
 
 /* one query of cornerOptimization / surfOptimization */
 typedef struct lins_map_corr {
@@ -65,6 +70,71 @@ int lins_scan2map_batch(lins_ctx* ctx, int n, const lins_map_problem* in, lins_m
 /* HIP-event time (ms) of the device sequence of the last call (the rounds' kernels; lins_map_correspondences: its
  * one pass) and the number of query evaluations it did */
 int lins_last_map_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* queries);
+
+/* ---- the mapping node's local map on the device (LM:1201-1349, 1752-1763) ------------------------------------------
+ * Key frames live on the device in per-slot rings, in the sensor frame, with the trigonometry of their pose formed on
+ * the host once (std::cos / std::sin of float, as updateTransformPointCloudSinCos does, LM:612-624).  A build moves the
+ * last min(window, K) frames of a slot into the map frame (transformPointCloud, LM:627-650, f32 as written),
+ * concatenates them oldest first — corner map: corner_i; surf map: surf_i then outlier_i — and VoxelGrid-filters them
+ * (corner 0.2 m, surf 0.4 m, LM:1316-1323); it filters the raw scan as downsampleCurrentScan does (LM:1326-1349).
+ * VoxelGrid is the project's contract: f32 box, stable order by PCL's linear voxel index, centroid
+ * = sequential f32 sums in input order / (float)count, output in ascending voxel order, no minimum count.           */
+typedef struct lins_key_pose {
+  float x, y, z, roll, pitch, yaw; /* PointTypePose (LM:1721-1732: t[3], t[4], t[5], t[0], t[1], t[2] of transformAftMapped) */
+} lins_key_pose;
+
+typedef struct lins_keyframe { /* one key frame: cornerCloudKeyFrames / surf / outlier (sensor frame) + its pose */
+  const lins_point* corner;
+  const lins_point* surf;
+  const lins_point* outlier;
+  int32_t n_corner, n_surf, n_outlier, reserved;
+  lins_key_pose pose;
+} lins_keyframe;
+
+typedef struct lins_local_scan { /* laserCloudCornerLast, laserCloudSurfLast, laserCloudOutlierLast of one build entry */
+  const lins_point* corner;
+  const lins_point* surf;
+  const lins_point* outlier;
+  int32_t n_corner, n_surf, n_outlier, reserved;
+} lins_local_scan;
+
+/* the six clouds of a build entry */
+#define LINS_LOCAL_MAP_CORNER 0   /* laserCloudCornerFromMapDS  = VG0.2(corner_i ...)               */
+#define LINS_LOCAL_MAP_SURF 1     /* laserCloudSurfFromMapDS    = VG0.4(surf_i, outlier_i ...)      */
+#define LINS_LOCAL_SCAN_CORNER 2  /* laserCloudCornerLastDS     = VG0.2(corner)                     */
+#define LINS_LOCAL_SCAN_SURF 3    /* laserCloudSurfLastDS       = VG0.4(surf)                       */
+#define LINS_LOCAL_SCAN_OUTLIER 4 /* laserCloudOutlierLastDS    = VG0.4(outlier)                    */
+#define LINS_LOCAL_SCAN_TOTAL 5   /* laserCloudSurfTotalLastDS  = VG0.4(surfDS ++ outlierDS)        */
+
+typedef struct lins_local_map_sizes {
+  int32_t n[6];          /* points of the six clouds (LINS_LOCAL_* order)                                          */
+  int32_t box_min[2][3]; /* the 1 m cell box scan-to-map grids the corner / surf map into (floor of the coordinates; */
+  int32_t box_dim[2][3]; /* an empty map: min 0, dim 1)                                                             */
+  int32_t frames;        /* key frames in the window                                                               */
+  int32_t status;        /* LINS_OK; LINS_E_CAPACITY: a VoxelGrid box of more than 2^31 cells; LINS_E_INPUT: a map
+                            point beyond |coord| <= 1e6 — the entry's clouds are then empty                        */
+} lins_local_map_sizes;
+
+/* n_slots rings of `window` key frames (surroundingKeyframeSearchNum = 50), each frame up to max_points_per_frame
+ * points over its three clouds.  Sized once; a second call drops every ring and sizes anew. */
+int lins_local_map_init(lins_ctx* ctx, int n_slots, int window, int max_points_per_frame);
+/* saveKeyFramesAndFactor's cloud copies (LM:1752-1763): one key frame onto the ring of `slot`; a full ring drops its
+ * oldest frame (LM:1226-1240).  Clouds: finite, |coord| <= 1e6 (LINS_E_INPUT); pose finite, |x|,|y|,|z| <= 1e6. */
+int lins_local_map_push(lins_ctx* ctx, int slot, const lins_keyframe* frame);
+/* extractSurroundingKeyFrames + downsampleCurrentScan for n entries: entry k uses the ring of slots[k] and filters
+ * scans[k]; everything runs on the context's stream with one synchronisation at the end; out[k] (may be NULL) gets
+ * the sizes, the 1 m boxes and the entry's status.  An empty ring gives empty maps.  Scans: finite, |coord| <= 1e6. */
+int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_local_scan* scans, lins_local_map_sizes* out);
+/* the cornerDS, surfDS and outlierDS of the chosen entries of the last build become new key frames of their slots,
+ * device to device, in the order given (the caller's key-frame rule, LM:1655-1669, decides which) */
+int lins_local_map_push_scans(lins_ctx* ctx, int n, const int32_t* entries, const lins_key_pose* poses);
+/* correctPoses (LM:1767-1795): the pose of the frame `age` frames before the newest (0: the newest) of `slot` */
+int lins_local_map_set_pose(lins_ctx* ctx, int slot, int age, const lins_key_pose* pose);
+/* cloud `which` (LINS_LOCAL_*) of entry `entry` of the last build; returns the point count (>= 0), LINS_E_CAPACITY
+ * when it is larger than cap */
+int lins_local_map_download(lins_ctx* ctx, int entry, int which, lins_point* out, int cap);
+/* HIP-event time (ms) of the device sequence of the last build and the points it read (window frames + raw scans) */
+int lins_last_local_map_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* points_in);
 
 #ifdef __cplusplus
 }

@@ -193,6 +193,9 @@ class Result:
 
 
 # ---- scan-to-map row (include/lins_map.h) -------------------------------------------------
+LINS_MAP_REUSE, LINS_MAP_LOCAL = 1, 2
+
+
 class MapProblemC(C.Structure):
     _fields_ = [("map_corner", C.POINTER(Point)), ("map_surf", C.POINTER(Point)), ("scan_corner", C.POINTER(Point)),
                 ("scan_surf", C.POINTER(Point)), ("n_map_corner", C.c_int32), ("n_map_surf", C.c_int32),
@@ -217,13 +220,74 @@ class MapProblem:
         self.map_corner, self.map_surf, self.scan_corner, self.scan_surf = f(map_corner), f(map_surf), f(scan_corner), f(scan_surf)
         self.transform = np.asarray(transform, dtype=np.float32).copy()
         self.reuse_resident_map = False  # LINS_MAP_REUSE: the maps are the previous call's (lins_map.h)
+        self.use_local_map = False  # LINS_MAP_LOCAL: maps and queries are entry k of the last local-map build
+
+    @classmethod
+    def local(cls, transform):
+        """problem k of a LINS_MAP_LOCAL batch: the clouds are those of entry k of the last lins_local_map_build"""
+        e = np.zeros((0, 4), np.float32)
+        p = cls(e, e, e, e, transform)
+        p.use_local_map = True
+        return p
 
     def as_c(self):
         c = MapProblemC()
-        c.reserved[0] = 1 if self.reuse_resident_map else 0
+        c.reserved[0] = (LINS_MAP_REUSE if self.reuse_resident_map else 0) | (LINS_MAP_LOCAL if self.use_local_map else 0)
         pp = lambda a: a.ctypes.data_as(C.POINTER(Point))
         c.map_corner, c.map_surf, c.scan_corner, c.scan_surf = pp(self.map_corner), pp(self.map_surf), pp(self.scan_corner), pp(self.scan_surf)
         c.n_map_corner, c.n_map_surf = len(self.map_corner), len(self.map_surf)
         c.n_scan_corner, c.n_scan_surf = len(self.scan_corner), len(self.scan_surf)
         c.transform[:] = [float(v) for v in self.transform]
         return c
+
+
+# ---- the mapping node's local map (include/lins_map.h lins_local_map_*) -------------------
+LOCAL_MAP_CORNER, LOCAL_MAP_SURF, LOCAL_SCAN_CORNER, LOCAL_SCAN_SURF, LOCAL_SCAN_OUTLIER, LOCAL_SCAN_TOTAL = range(6)
+
+
+class KeyPoseC(C.Structure):
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float), ("roll", C.c_float), ("pitch", C.c_float), ("yaw", C.c_float)]
+
+
+def key_pose(p):
+    """(x, y, z, roll, pitch, yaw) -> lins_key_pose"""
+    return KeyPoseC(*[float(v) for v in np.asarray(p, dtype=np.float32)])
+
+
+class KeyframeC(C.Structure):
+    _fields_ = [("corner", C.POINTER(Point)), ("surf", C.POINTER(Point)), ("outlier", C.POINTER(Point)),
+                ("n_corner", C.c_int32), ("n_surf", C.c_int32), ("n_outlier", C.c_int32), ("reserved", C.c_int32),
+                ("pose", KeyPoseC)]
+
+
+class LocalScanC(C.Structure):
+    _fields_ = [("corner", C.POINTER(Point)), ("surf", C.POINTER(Point)), ("outlier", C.POINTER(Point)),
+                ("n_corner", C.c_int32), ("n_surf", C.c_int32), ("n_outlier", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LocalMapSizesC(C.Structure):
+    _fields_ = [("n", C.c_int32 * 6), ("box_min", (C.c_int32 * 3) * 2), ("box_dim", (C.c_int32 * 3) * 2),
+                ("frames", C.c_int32), ("status", C.c_int32)]
+
+    def as_dict(self):
+        return dict(n=[int(v) for v in self.n], box_min=[list(r) for r in self.box_min], box_dim=[list(r) for r in self.box_dim],
+                    frames=int(self.frames), status=int(self.status))
+
+
+def cloud(a):
+    """an (n, 4) f32 C-contiguous array (x, y, z, intensity)"""
+    return np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 4)
+
+
+def keyframe_c(corner, surf, outlier, pose):
+    """lins_keyframe over numpy clouds; returns (struct, the arrays it points into)"""
+    keep = [cloud(corner), cloud(surf), cloud(outlier)]
+    pp = lambda a: a.ctypes.data_as(C.POINTER(Point))
+    f = KeyframeC(pp(keep[0]), pp(keep[1]), pp(keep[2]), len(keep[0]), len(keep[1]), len(keep[2]), 0, key_pose(pose))
+    return f, keep
+
+
+def local_scan_c(corner, surf, outlier):
+    keep = [cloud(corner), cloud(surf), cloud(outlier)]
+    pp = lambda a: a.ctypes.data_as(C.POINTER(Point))
+    return LocalScanC(pp(keep[0]), pp(keep[1]), pp(keep[2]), len(keep[0]), len(keep[1]), len(keep[2]), 0), keep

@@ -1,0 +1,445 @@
+// lins_local_map_capi.hip — C ABI of the mapping node's local map on the device (include/lins_map.h lins_local_map_*):
+// the key-frame rings, the packing of a build into the VoxelGrid jobs of local_map_kernels.hip, and the view scan-to-map
+// reads the built clouds through (LINS_MAP_LOCAL).  The rings hold the key frames in the sensor frame; the host keeps
+// their counts, poses and trigonometry (std::cos / std::sin of float, once per pose, LM:612-624).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/lins_map.h"
+#include "lins_ctx_priv.h"
+#include "local_map.h"
+
+namespace lins {
+void launch_lm_transform(hipStream_t, int, const void*, const int2*, const float4*, float4*, void*);
+void launch_lm_stage(hipStream_t, int, int, int, const int2*, const void*, void*, float4*, unsigned*, unsigned*, int*, int*,
+                     int*, int*, int*, float4*);
+}  // namespace lins
+using namespace lins;
+
+namespace {
+
+struct KeyFrame {
+  int n[3];  // corner, surf, outlier (stored one after the other in the frame's block of the ring)
+  lins_key_pose pose;
+  float t[9];  // ctRoll, stRoll, ctPitch, stPitch, ctYaw, stYaw, tInX, tInY, tInZ
+};
+
+struct LocalMap {
+  int n_slots = 0, window = 0, max_pts = 0;
+  float4* d_frames = nullptr;  // [slot][window][max_pts]
+  std::vector<KeyFrame> meta;  // [slot][window]
+  std::vector<int> head, count;
+  // build arenas (grown, never shrunk)
+  float4 *d_stage = nullptr, *d_out = nullptr;
+  unsigned *d_ka = nullptr, *d_kb = nullptr;
+  int *d_va = nullptr, *d_vb = nullptr, *d_starts = nullptr, *d_hist = nullptr, *d_tilecnt = nullptr;
+  char* d_tab = nullptr;
+  float4* h_raw = nullptr;
+  char *h_tab = nullptr, *h_states = nullptr;
+  size_t cap_stage = 0, cap_out = 0, cap_tiles = 0, cap_tab = 0, cap_raw = 0, cap_htab = 0, cap_hstates = 0;
+  // the last build
+  bool built = false;
+  std::vector<int> slots;
+  std::vector<long long> off;  // 6 per entry
+  std::vector<lins_local_map_sizes> sizes;
+  float ms = 0.f;
+  uint64_t points_in = 0;
+};
+
+void local_free(void* p) {
+  LocalMap* m = (LocalMap*)p;
+  (void)hipFree(m->d_frames), (void)hipFree(m->d_stage), (void)hipFree(m->d_out), (void)hipFree(m->d_ka), (void)hipFree(m->d_kb);
+  (void)hipFree(m->d_va), (void)hipFree(m->d_vb), (void)hipFree(m->d_starts), (void)hipFree(m->d_hist), (void)hipFree(m->d_tilecnt);
+  (void)hipFree(m->d_tab), (void)hipHostFree(m->h_raw), (void)hipHostFree(m->h_tab), (void)hipHostFree(m->h_states);
+  delete m;
+}
+
+LocalMap* local_of(lins_ctx* ctx) {
+  void** slot = map_local_slot(ctx, local_free);
+  if (!*slot) *slot = new LocalMap();
+  return (LocalMap*)*slot;
+}
+
+#define LM_TRY(ctx, expr)                                        \
+  do {                                                           \
+    hipError_t e__ = (expr);                                     \
+    if (e__ != hipSuccess) return ctx_fail_hip(ctx, e__, #expr); \
+  } while (0)
+
+template <class T>
+int grow(lins_ctx* ctx, T** p, size_t* cap, size_t need) {
+  need = std::max<size_t>(need, 1);
+  if (*cap >= need) return LINS_OK;
+  (void)hipFree(*p);
+  *p = nullptr, *cap = 0;
+  LM_TRY(ctx, hipMalloc((void**)p, need * sizeof(T)));
+  *cap = need;
+  return LINS_OK;
+}
+template <class T>
+int grow_pinned(lins_ctx* ctx, T** p, size_t* cap, size_t need) {
+  need = std::max<size_t>(need, 1);
+  if (*cap >= need) return LINS_OK;
+  (void)hipHostFree(*p);
+  *p = nullptr, *cap = 0;
+  LM_TRY(ctx, hipHostMalloc((void**)p, need * sizeof(T)));
+  *cap = need;
+  return LINS_OK;
+}
+
+bool point_ok(const lins_point& p) {
+  return std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z) && std::fabs(p.x) <= 1e6f && std::fabs(p.y) <= 1e6f &&
+         std::fabs(p.z) <= 1e6f;
+}
+int cloud_check(const lins_point* p, int n) {
+  if (n < 0 || (n && !p)) return LINS_E_ARG;
+  for (int i = 0; i < n; ++i)
+    if (!point_ok(p[i])) return LINS_E_INPUT;
+  return LINS_OK;
+}
+bool pose_ok(const lins_key_pose& p) {
+  const float v[6] = {p.x, p.y, p.z, p.roll, p.pitch, p.yaw};
+  for (float x : v)
+    if (!std::isfinite(x)) return false;
+  return std::fabs(p.x) <= 1e6f && std::fabs(p.y) <= 1e6f && std::fabs(p.z) <= 1e6f;
+}
+void set_pose(KeyFrame& f, const lins_key_pose& p) {  // updateTransformPointCloudSinCos (LM:612-624)
+  f.pose = p;
+  const float t[9] = {std::cos(p.roll), std::sin(p.roll), std::cos(p.pitch), std::sin(p.pitch), std::cos(p.yaw), std::sin(p.yaw), p.x, p.y, p.z};
+  std::memcpy(f.t, t, sizeof t);
+}
+
+// the ring position a new key frame of `slot` goes to (a full ring drops its oldest, LM:1226-1240)
+int ring_push(LocalMap* m, int slot) {
+  int& h = m->head[slot];
+  int& c = m->count[slot];
+  if (c < m->window) return (h + c++) % m->window;
+  const int idx = h;
+  h = (h + 1) % m->window;
+  return idx;
+}
+float4* frame_ptr(LocalMap* m, int slot, int idx) { return m->d_frames + ((size_t)slot * m->window + idx) * m->max_pts; }
+
+size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
+
+}  // namespace
+
+namespace lins {
+int local_map_view(lins_ctx* ctx, LocalMapView* v) {
+  LocalMap* m = local_of(ctx);
+  if (!m->built) return LINS_E_STATE;
+  v->d_out = m->d_out, v->n = (int)m->slots.size(), v->off = m->off.data(), v->sizes = m->sizes.data();
+  return LINS_OK;
+}
+}  // namespace lins
+
+extern "C" {
+
+int lins_local_map_init(lins_ctx* ctx, int n_slots, int window, int max_points_per_frame) {
+  if (!ctx || n_slots < 1 || window < 1 || window > 4096 || max_points_per_frame < 1) return LINS_E_ARG;
+  LM_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  LocalMap* m = local_of(ctx);
+  LM_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));  // (a push_scans copy may still read the old rings)
+  (void)hipFree(m->d_frames);
+  m->d_frames = nullptr, m->n_slots = 0, m->built = false;
+  LM_TRY(ctx, hipMalloc((void**)&m->d_frames, (size_t)n_slots * window * max_points_per_frame * sizeof(float4)));
+  m->n_slots = n_slots, m->window = window, m->max_pts = max_points_per_frame;
+  m->meta.assign((size_t)n_slots * window, KeyFrame{});
+  m->head.assign(n_slots, 0), m->count.assign(n_slots, 0);
+  return LINS_OK;
+}
+
+int lins_local_map_push(lins_ctx* ctx, int slot, const lins_keyframe* f) {
+  if (!ctx || !f) return LINS_E_ARG;
+  LocalMap* m = local_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (slot < 0 || slot >= m->n_slots) return LINS_E_ARG;
+  const lins_point* c[3] = {f->corner, f->surf, f->outlier};
+  const int n[3] = {f->n_corner, f->n_surf, f->n_outlier};
+  for (int k = 0; k < 3; ++k)
+    if (int rc = cloud_check(c[k], n[k])) return rc;
+  if (!pose_ok(f->pose)) return LINS_E_INPUT;
+  if ((long long)n[0] + n[1] + n[2] > m->max_pts) return LINS_E_CAPACITY;
+  LM_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  hipStream_t st = ctx_stream(ctx);
+  const int idx = ring_push(m, slot);
+  KeyFrame& kf = m->meta[(size_t)slot * m->window + idx];
+  float4* dst = frame_ptr(m, slot, idx);
+  for (int k = 0; k < 3; ++k) {
+    kf.n[k] = n[k];
+    if (n[k]) LM_TRY(ctx, hipMemcpyAsync(dst, c[k], (size_t)n[k] * sizeof(float4), hipMemcpyHostToDevice, st));
+    dst += n[k];
+  }
+  set_pose(kf, f->pose);
+  LM_TRY(ctx, hipStreamSynchronize(st));  // (the caller's clouds may go once this returns)
+  return LINS_OK;
+}
+
+int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_local_scan* scans, lins_local_map_sizes* out) {
+  if (!ctx || n < 0 || (n && (!slots || !scans))) return LINS_E_ARG;
+  LocalMap* m = local_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  for (int k = 0; k < n; ++k) {
+    if (slots[k] < 0 || slots[k] >= m->n_slots) return LINS_E_ARG;
+    const lins_local_scan& s = scans[k];
+    if (s.n_corner < 0 || s.n_surf < 0 || s.n_outlier < 0 || (s.n_corner && !s.corner) || (s.n_surf && !s.surf) ||
+        (s.n_outlier && !s.outlier))
+      return LINS_E_ARG;
+  }
+  LM_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  m->built = false;
+  const int NJ = 6 * n;  // jobs: stage A 5 per entry (5k + cloud), stage B one per entry (5n + k)
+  std::vector<LmJob> jobs(NJ);
+  std::vector<LmState> states(NJ);
+  std::vector<long long> cap(NJ, 0);
+  std::vector<int> frames_of(n);
+  for (int k = 0; k < n; ++k) {
+    const int s = slots[k];
+    frames_of[k] = m->count[s];
+    for (int i = 0; i < m->count[s]; ++i) {
+      const KeyFrame& f = m->meta[(size_t)s * m->window + (m->head[s] + i) % m->window];
+      cap[5 * k] += f.n[0], cap[5 * k + 1] += f.n[1] + f.n[2];
+    }
+    cap[5 * k + 2] = scans[k].n_corner, cap[5 * k + 3] = scans[k].n_surf, cap[5 * k + 4] = scans[k].n_outlier;
+    cap[5 * n + k] = (long long)scans[k].n_surf + scans[k].n_outlier;
+  }
+  for (int j = 0; j < NJ; ++j)
+    if (cap[j] > INT_MAX / 2) return LINS_E_CAPACITY;
+  // staging: the raw scans of all entries first (one upload), then the maps, then stage B
+  std::vector<int> order;
+  for (int k = 0; k < n; ++k)
+    for (int c = 2; c < 5; ++c) order.push_back(5 * k + c);
+  size_t raw_total = 0;
+  for (int j : order) raw_total += (size_t)cap[j];
+  for (int k = 0; k < n; ++k) order.push_back(5 * k), order.push_back(5 * k + 1);
+  for (int k = 0; k < n; ++k) order.push_back(5 * n + k);
+  size_t stage_total = 0, tiles_total = 0, out_total = 0;
+  for (int j : order) jobs[j].off_in = (long long)stage_total, stage_total += (size_t)cap[j];
+  for (int j = 0; j < NJ; ++j) {
+    LmJob& jb = jobs[j];
+    jb.cap = (int)cap[j];
+    jb.ntiles = (int)((cap[j] + kLmTile - 1) / kLmTile);
+    jb.tile0 = (int)tiles_total, tiles_total += (size_t)jb.ntiles;
+    jb.out_after = jb.src_a = jb.src_b = jb.feed = jb.feed_after = -1, jb.map = 0, jb.pad = 0;
+    LmState& st = states[j];
+    std::memset(&st, 0, sizeof st);
+    for (int a = 0; a < 3; ++a)
+      st.mn[a] = lm_enc(INFINITY), st.mx[a] = lm_enc(-INFINITY), st.bmin[a] = INT_MAX, st.bmax[a] = INT_MIN;
+    st.n = j < 5 * n ? jb.cap : 0;
+  }
+  if (tiles_total > (size_t)INT_MAX / 256) return LINS_E_CAPACITY;
+  for (int k = 0; k < n; ++k) {
+    const long long c2 = cap[5 * k + 2] + cap[5 * n + k];  // cornerDS, then surfTotalDS right behind it (the query layout)
+    const long long ocap[5] = {cap[5 * k], cap[5 * k + 1], c2, cap[5 * k + 3], cap[5 * k + 4]};
+    for (int c = 0; c < 5; ++c) {
+      LmJob& jb = jobs[5 * k + c];
+      jb.off_out = (long long)out_total, out_total += (size_t)ocap[c];
+      jb.inv = 1.0f / (c == 0 || c == 2 ? 0.2f : 0.4f);
+    }
+    jobs[5 * k].map = jobs[5 * k + 1].map = 1;
+    LmJob& b = jobs[5 * n + k];
+    b.inv = 1.0f / 0.4f;
+    b.off_out = jobs[5 * k + 2].off_out, b.out_after = 5 * k + 2;
+    b.src_a = 5 * k + 3, b.src_b = 5 * k + 4;
+    jobs[5 * k + 3].feed = jobs[5 * k + 4].feed = 5 * n + k;
+    jobs[5 * k + 4].feed_after = 5 * k + 3;
+  }
+  int rc;
+  if ((rc = grow_pinned(ctx, &m->h_raw, &m->cap_raw, raw_total))) return rc;
+  // raw scans: input contract, f32 box (the min / max the device would fold), packed for one upload
+  for (int k = 0; k < n; ++k) {
+    const lins_point* c[3] = {scans[k].corner, scans[k].surf, scans[k].outlier};
+    const int cn[3] = {scans[k].n_corner, scans[k].n_surf, scans[k].n_outlier};
+    for (int q = 0; q < 3; ++q) {
+      if ((rc = cloud_check(c[q], cn[q]))) return rc;
+      const int j = 5 * k + 2 + q;
+      float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+      for (int i = 0; i < cn[q]; ++i) {
+        const lins_point& p = c[q][i];
+        mn[0] = std::min(mn[0], p.x), mn[1] = std::min(mn[1], p.y), mn[2] = std::min(mn[2], p.z);
+        mx[0] = std::max(mx[0], p.x), mx[1] = std::max(mx[1], p.y), mx[2] = std::max(mx[2], p.z);
+      }
+      for (int a = 0; a < 3; ++a) states[j].mn[a] = lm_enc(mn[a]), states[j].mx[a] = lm_enc(mx[a]);
+      if (cn[q]) std::memcpy(m->h_raw + jobs[j].off_in, c[q], (size_t)cn[q] * sizeof(float4));
+    }
+  }
+  // the window's clouds: one segment per (frame, cloud), blocks of kLmTile points
+  std::vector<LmSeg> segs;
+  std::vector<int2> blocks;
+  uint64_t pts_in = raw_total;
+  for (int k = 0; k < n; ++k) {
+    const int s = slots[k];
+    long long at[2] = {jobs[5 * k].off_in, jobs[5 * k + 1].off_in};
+    for (int i = 0; i < m->count[s]; ++i) {
+      const int idx = (m->head[s] + i) % m->window;
+      const KeyFrame& f = m->meta[(size_t)s * m->window + idx];
+      long long src = (long long)(frame_ptr(m, s, idx) - m->d_frames);
+      for (int q = 0; q < 3; ++q) {  // LM:1242-1246: corner_i -> corner map; surf_i, outlier_i -> surf map
+        const int w = q == 0 ? 0 : 1;
+        if (f.n[q]) {
+          LmSeg g{};
+          g.src = src, g.dst = at[w], g.n = f.n[q], g.job = 5 * k + w;
+          std::memcpy(g.t, f.t, sizeof g.t);
+          for (int b = 0; b < (f.n[q] + kLmTile - 1) / kLmTile; ++b) blocks.push_back(make_int2((int)segs.size(), b));
+          segs.push_back(g);
+        }
+        src += f.n[q], at[w] += f.n[q], pts_in += (uint64_t)f.n[q];
+      }
+    }
+  }
+  std::vector<int2> tiles;
+  tiles.reserve(tiles_total);
+  for (int j = 0; j < NJ; ++j)
+    for (int t = 0; t < jobs[j].ntiles; ++t) tiles.push_back(make_int2(j, t));
+  const int tiles_a = n ? jobs[5 * n].tile0 : 0;  // stage A's tiles come first
+  const int tiles_b = (int)tiles_total - tiles_a;
+  // one table upload: jobs | states | segments | blocks | tiles
+  const size_t o_jobs = 0, o_states = align64(o_jobs + NJ * sizeof(LmJob)), o_segs = align64(o_states + NJ * sizeof(LmState)),
+               o_blocks = align64(o_segs + segs.size() * sizeof(LmSeg)), o_tiles = align64(o_blocks + blocks.size() * sizeof(int2)),
+               tab_bytes = align64(o_tiles + tiles.size() * sizeof(int2));
+  if ((rc = grow_pinned(ctx, &m->h_tab, &m->cap_htab, tab_bytes))) return rc;
+  if ((rc = grow_pinned(ctx, &m->h_states, &m->cap_hstates, NJ * sizeof(LmState)))) return rc;
+  std::memcpy(m->h_tab + o_jobs, jobs.data(), NJ * sizeof(LmJob));
+  std::memcpy(m->h_tab + o_states, states.data(), NJ * sizeof(LmState));
+  if (!segs.empty()) std::memcpy(m->h_tab + o_segs, segs.data(), segs.size() * sizeof(LmSeg));
+  if (!blocks.empty()) std::memcpy(m->h_tab + o_blocks, blocks.data(), blocks.size() * sizeof(int2));
+  if (!tiles.empty()) std::memcpy(m->h_tab + o_tiles, tiles.data(), tiles.size() * sizeof(int2));
+  if ((rc = grow(ctx, &m->d_tab, &m->cap_tab, tab_bytes))) return rc;
+  if (m->cap_stage < std::max<size_t>(stage_total, 1)) {  // the staging arena and the sort's scratch: same extent
+    size_t c[7] = {0, 0, 0, 0, 0, 0, 0};
+    (void)hipFree(m->d_stage), (void)hipFree(m->d_ka), (void)hipFree(m->d_kb), (void)hipFree(m->d_va), (void)hipFree(m->d_vb);
+    (void)hipFree(m->d_starts);
+    m->d_stage = nullptr, m->d_ka = m->d_kb = nullptr, m->d_va = m->d_vb = m->d_starts = nullptr, m->cap_stage = 0;
+    if ((rc = grow(ctx, &m->d_stage, &c[0], stage_total)) || (rc = grow(ctx, &m->d_ka, &c[1], stage_total)) ||
+        (rc = grow(ctx, &m->d_kb, &c[2], stage_total)) || (rc = grow(ctx, &m->d_va, &c[3], stage_total)) ||
+        (rc = grow(ctx, &m->d_vb, &c[4], stage_total)) || (rc = grow(ctx, &m->d_starts, &c[5], stage_total)))
+      return rc;
+    m->cap_stage = c[0];
+  }
+  if (m->cap_tiles < std::max<size_t>(tiles_total, 1)) {
+    size_t c[2] = {0, 0};
+    (void)hipFree(m->d_hist), (void)hipFree(m->d_tilecnt);
+    m->d_hist = m->d_tilecnt = nullptr, m->cap_tiles = 0;
+    if ((rc = grow(ctx, &m->d_hist, &c[0], tiles_total * 256)) || (rc = grow(ctx, &m->d_tilecnt, &c[1], tiles_total))) return rc;
+    m->cap_tiles = c[1];
+  }
+  if ((rc = grow(ctx, &m->d_out, &m->cap_out, out_total))) return rc;
+  hipStream_t st = ctx_stream(ctx);
+  hipEvent_t e0, e1;
+  ctx_events(ctx, &e0, &e1);
+  if (raw_total) LM_TRY(ctx, hipMemcpyAsync(m->d_stage, m->h_raw, raw_total * sizeof(float4), hipMemcpyHostToDevice, st));
+  if (tab_bytes) LM_TRY(ctx, hipMemcpyAsync(m->d_tab, m->h_tab, tab_bytes, hipMemcpyHostToDevice, st));
+  LM_TRY(ctx, hipEventRecord(e0, st));
+  void* d_jobs = m->d_tab + o_jobs;
+  void* d_states = m->d_tab + o_states;
+  const int2* d_tiles = (const int2*)(m->d_tab + o_tiles);
+  launch_lm_transform(st, (int)blocks.size(), m->d_tab + o_segs, (const int2*)(m->d_tab + o_blocks), m->d_frames, m->d_stage, d_states);
+  launch_lm_stage(st, 0, 5 * n, tiles_a, d_tiles, d_jobs, d_states, m->d_stage, m->d_ka, m->d_kb, m->d_va, m->d_vb, m->d_hist,
+                  m->d_tilecnt, m->d_starts, m->d_out);
+  launch_lm_stage(st, 5 * n, n, tiles_b, d_tiles + tiles_a, d_jobs, d_states, m->d_stage, m->d_ka, m->d_kb, m->d_va, m->d_vb,
+                  m->d_hist, m->d_tilecnt, m->d_starts, m->d_out);
+  LM_TRY(ctx, hipGetLastError());
+  LM_TRY(ctx, hipEventRecord(e1, st));
+  if (NJ) LM_TRY(ctx, hipMemcpyAsync(m->h_states, d_states, NJ * sizeof(LmState), hipMemcpyDeviceToHost, st));
+  LM_TRY(ctx, hipStreamSynchronize(st));
+  LM_TRY(ctx, hipEventElapsedTime(&m->ms, e0, e1));
+  m->points_in = pts_in;
+  const LmState* S = (const LmState*)m->h_states;
+  m->slots.assign(slots, slots + n);
+  m->off.assign((size_t)6 * n, 0);
+  m->sizes.assign(n, lins_local_map_sizes{});
+  for (int k = 0; k < n; ++k) {
+    lins_local_map_sizes& z = m->sizes[k];
+    const int js[6] = {5 * k, 5 * k + 1, 5 * k + 2, 5 * k + 3, 5 * k + 4, 5 * n + k};
+    int status = LINS_OK;
+    for (int j : js)
+      if (S[j].status == LINS_E_INPUT || (S[j].status && !status)) status = S[j].status;
+    z.status = status, z.frames = frames_of[k];
+    for (int c = 0; c < 6; ++c) {
+      z.n[c] = status ? 0 : S[js[c]].nvox;
+      m->off[6 * k + c] = c < 5 ? jobs[js[c]].off_out : jobs[5 * k + 2].off_out + S[5 * k + 2].nvox;
+    }
+    for (int w = 0; w < 2; ++w)
+      for (int a = 0; a < 3; ++a) {
+        const bool any = z.n[w] > 0;
+        z.box_min[w][a] = any ? S[js[w]].bmin[a] : 0;
+        z.box_dim[w][a] = any ? S[js[w]].bmax[a] - S[js[w]].bmin[a] + 1 : 1;
+      }
+    if (out) out[k] = z;
+  }
+  m->built = true;
+  return LINS_OK;
+}
+
+int lins_local_map_push_scans(lins_ctx* ctx, int n, const int32_t* entries, const lins_key_pose* poses) {
+  if (!ctx || n < 0 || (n && (!entries || !poses))) return LINS_E_ARG;
+  LocalMap* m = local_of(ctx);
+  if (!m->built) return LINS_E_STATE;
+  for (int i = 0; i < n; ++i) {
+    const int e = entries[i];
+    if (e < 0 || e >= (int)m->slots.size()) return LINS_E_ARG;
+    const lins_local_map_sizes& z = m->sizes[e];
+    if (z.status) return LINS_E_STATE;
+    if (!pose_ok(poses[i])) return LINS_E_INPUT;
+    if ((long long)z.n[LINS_LOCAL_SCAN_CORNER] + z.n[LINS_LOCAL_SCAN_SURF] + z.n[LINS_LOCAL_SCAN_OUTLIER] > m->max_pts)
+      return LINS_E_CAPACITY;
+  }
+  LM_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  hipStream_t st = ctx_stream(ctx);
+  for (int i = 0; i < n; ++i) {  // saveKeyFramesAndFactor (LM:1758-1763): cornerDS, surfDS, outlierDS
+    const int e = entries[i], s = m->slots[e];
+    const int idx = ring_push(m, s);
+    KeyFrame& kf = m->meta[(size_t)s * m->window + idx];
+    float4* dst = frame_ptr(m, s, idx);
+    for (int q = 0; q < 3; ++q) {
+      const int c = LINS_LOCAL_SCAN_CORNER + q, cnt = m->sizes[e].n[c];
+      kf.n[q] = cnt;
+      if (cnt) LM_TRY(ctx, hipMemcpyAsync(dst, m->d_out + m->off[6 * e + c], (size_t)cnt * sizeof(float4), hipMemcpyDeviceToDevice, st));
+      dst += cnt;
+    }
+    set_pose(kf, poses[i]);
+  }
+  return LINS_OK;
+}
+
+int lins_local_map_set_pose(lins_ctx* ctx, int slot, int age, const lins_key_pose* pose) {
+  if (!ctx || !pose) return LINS_E_ARG;
+  LocalMap* m = local_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (slot < 0 || slot >= m->n_slots || age < 0 || age >= m->count[slot]) return LINS_E_ARG;
+  if (!pose_ok(*pose)) return LINS_E_INPUT;
+  const int idx = (m->head[slot] + m->count[slot] - 1 - age) % m->window;
+  set_pose(m->meta[(size_t)slot * m->window + idx], *pose);
+  return LINS_OK;
+}
+
+int lins_local_map_download(lins_ctx* ctx, int entry, int which, lins_point* out, int cap) {
+  if (!ctx) return LINS_E_ARG;
+  LocalMap* m = local_of(ctx);
+  if (!m->built) return LINS_E_STATE;
+  if (entry < 0 || entry >= (int)m->slots.size() || which < 0 || which > 5) return LINS_E_ARG;
+  const int cnt = m->sizes[entry].n[which];
+  if (cnt > cap) return LINS_E_CAPACITY;
+  if (cnt && !out) return LINS_E_ARG;
+  if (!cnt) return 0;
+  LM_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  hipStream_t st = ctx_stream(ctx);
+  LM_TRY(ctx, hipMemcpyAsync(out, m->d_out + m->off[6 * entry + which], (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost, st));
+  LM_TRY(ctx, hipStreamSynchronize(st));
+  return cnt;
+}
+
+int lins_last_local_map_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* points_in) {
+  if (!ctx) return LINS_E_ARG;
+  LocalMap* m = local_of(ctx);
+  if (kernel_ms) *kernel_ms = m->ms;
+  if (points_in) *points_in = m->points_in;
+  return LINS_OK;
+}
+
+}  // extern "C"

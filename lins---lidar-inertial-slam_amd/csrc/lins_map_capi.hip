@@ -15,6 +15,7 @@
 
 #include "../../include/lins_map.h"
 #include "lins_ctx_priv.h"
+#include "local_map.h"
 #include "lm_math.h"
 #include "map_math.h"
 
@@ -67,6 +68,9 @@ struct MapState {
   float ms = 0.f;
   uint64_t queries = 0;
   bool selfcheck_done = false;
+  // the local-map state of lins_local_map_* (lins_local_map_capi.hip), freed with this one
+  void* local = nullptr;
+  void (*local_free)(void*) = nullptr;
 };
 
 void map_state_free(void* p) {
@@ -74,6 +78,7 @@ void map_state_free(void* p) {
   (void)hipFree(m->d_raw), (void)hipFree(m->d_pts), (void)hipFree(m->d_q), (void)hipFree(m->d_cells), (void)hipFree(m->d_rec);
   (void)hipFree(m->d_partials), (void)hipFree(m->d_probs), (void)hipFree(m->d_rounds), (void)hipFree(m->d_jobs);
   (void)hipFree(m->d_carry), (void)hipFree(m->d_results), (void)hipHostFree(m->h_q);
+  if (m->local) m->local_free(m->local);
   delete m;
 }
 
@@ -229,6 +234,66 @@ int map_upload(lins_ctx* ctx, MapState* m, int n, const lins_map_problem* in, st
   return LINS_OK;
 }
 
+// LINS_MAP_LOCAL: the maps and queries are the clouds of the last local-map build, read where they lie — the maps are
+// gridded from the build's cloud arena (its 1 m boxes came back with the build), the queries are its cornerDS with
+// surfTotalDS right behind (lins_local_map_capi.hip lays them out so).  No host cloud is read or uploaded.
+int map_upload_local(lins_ctx* ctx, MapState* m, const LocalMapView& lv, std::vector<MapDevHost>& dev, int* max_q) {
+  const int n = lv.n;
+  std::vector<MapGridJobHost> jobs((size_t)n * 2);
+  size_t tot_pts = 0, tot_cells = 0, tot_q = 0;
+  dev.assign(n, MapDevHost{});
+  *max_q = 0;
+  for (int k = 0; k < n; ++k) {
+    const lins_local_map_sizes& z = lv.sizes[k];
+    for (int w = 0; w < 2; ++w) {
+      MapGridJobHost& jb = jobs[(size_t)k * 2 + w];
+      long long ncell = 1;
+      for (int a = 0; a < 3; ++a) jb.cmin[a] = z.box_min[w][a], jb.cdim[a] = z.box_dim[w][a], ncell *= jb.cdim[a];
+      if (ncell > (1ll << 26)) return LINS_E_CAPACITY;  // (cloud_box's limit)
+      jb.n = z.n[w], jb.ncell = (int)ncell;
+      jb.off_raw = lv.off[6 * k + w], jb.off_pts = (long long)tot_pts, jb.off_cells = (long long)tot_cells;
+      dev[k].g[w].off_pts = jb.off_pts, dev[k].g[w].off_cells = jb.off_cells;
+      for (int a = 0; a < 3; ++a) dev[k].g[w].cmin[a] = jb.cmin[a], dev[k].g[w].cdim[a] = jb.cdim[a];
+      tot_pts += (size_t)jb.n, tot_cells += 2 * ((size_t)jb.ncell + 1);
+    }
+    dev[k].off_q = lv.off[6 * k + LINS_LOCAL_SCAN_CORNER], dev[k].off_rec = (long long)tot_q;
+    dev[k].n_q[0] = z.n[LINS_LOCAL_SCAN_CORNER], dev[k].n_q[1] = z.n[LINS_LOCAL_SCAN_TOTAL];
+    dev[k].active = z.n[0] > 10 && z.n[1] > 100;  // LM:1636
+    tot_q += (size_t)dev[k].n_q[0] + dev[k].n_q[1];
+    *max_q = std::max(*max_q, dev[k].n_q[0] + dev[k].n_q[1]);
+  }
+  int rc;
+  if ((rc = grow(ctx, &m->d_pts, &m->cap_pts, std::max<size_t>(tot_pts, 1)))) return rc;
+  if ((rc = grow(ctx, &m->d_cells, &m->cap_cells, std::max<size_t>(tot_cells, 1)))) return rc;
+  if (m->cap_probs < n) {
+    (void)hipFree(m->d_probs), (void)hipFree(m->d_rounds), (void)hipFree(m->d_jobs), (void)hipFree(m->d_carry), (void)hipFree(m->d_results);
+    m->d_probs = m->d_rounds = m->d_jobs = m->d_carry = nullptr, m->d_results = nullptr, m->cap_probs = 0;
+    MAP_TRY(ctx, hipMalloc(&m->d_probs, (size_t)n * sizeof(MapDevHost)));
+    MAP_TRY(ctx, hipMalloc(&m->d_rounds, (size_t)n * map_round_size()));
+    MAP_TRY(ctx, hipMalloc(&m->d_jobs, (size_t)n * 2 * sizeof(MapGridJobHost)));
+    MAP_TRY(ctx, hipMalloc(&m->d_carry, (size_t)n * map_carry_size()));
+    MAP_TRY(ctx, hipMalloc((void**)&m->d_results, (size_t)n * sizeof(lins_map_result)));
+    m->cap_probs = n;
+  }
+  if (m->cap_q < std::max<size_t>(tot_q, 1)) {
+    (void)hipFree(m->d_q), (void)hipFree(m->d_rec);
+    m->d_q = nullptr, m->d_rec = nullptr, m->cap_q = 0;
+    MAP_TRY(ctx, hipMalloc((void**)&m->d_q, std::max<size_t>(tot_q, 1) * sizeof(float4)));
+    MAP_TRY(ctx, hipMalloc((void**)&m->d_rec, std::max<size_t>(tot_q, 1) * sizeof(lins_map_corr)));
+    m->cap_q = std::max<size_t>(tot_q, 1);
+  }
+  hipStream_t st = ctx_stream(ctx);
+  MAP_TRY(ctx, hipMemcpyAsync(m->d_jobs, jobs.data(), jobs.size() * sizeof(MapGridJobHost), hipMemcpyHostToDevice, st));
+  launch_map_grid(st, 2 * n, m->d_jobs, lv.d_out, m->d_pts, m->d_cells);
+  MAP_TRY(ctx, hipGetLastError());
+  MAP_TRY(ctx, hipStreamSynchronize(st));  // (jobs goes out of scope)
+  // the gridded maps are resident as after an explicit upload: a later LINS_MAP_REUSE call may use them
+  m->resident_sizes.clear();
+  for (int k = 0; k < n; ++k) m->resident_sizes.push_back(lv.sizes[k].n[0]), m->resident_sizes.push_back(lv.sizes[k].n[1]);
+  m->resident_dev = dev;
+  return LINS_OK;
+}
+
 MapState* state_of(lins_ctx* ctx) {
   void** slot = ctx_map_slot(ctx, map_state_free);
   if (!*slot) *slot = new MapState();
@@ -255,6 +320,14 @@ int map_selfcheck(lins_ctx* ctx, MapState* m) {
 
 }  // namespace
 
+namespace lins {
+void** map_local_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
+  MapState* m = state_of(ctx);
+  m->local_free = free_fn;
+  return &m->local;
+}
+}  // namespace lins
+
 extern "C" {
 
 int lins_scan2map_batch(lins_ctx* ctx, int n, const lins_map_problem* in, lins_map_result* out) {
@@ -268,13 +341,23 @@ int lins_scan2map_batch(lins_ctx* ctx, int n, const lins_map_problem* in, lins_m
   MapState* m = state_of(ctx);
   int rc = map_selfcheck(ctx, m);
   if (rc) return rc;
+  int n_local = 0;
+  for (int k = 0; k < n; ++k) {
+    const int fl = in[k].reserved[0];
+    if ((fl & LINS_MAP_LOCAL) && (fl & LINS_MAP_REUSE)) return LINS_E_ARG;
+    n_local += (fl & LINS_MAP_LOCAL) != 0;
+  }
+  if (n_local && n_local != n) return LINS_E_ARG;  // a batch is local or explicit, not both
+  LocalMapView lv{};
+  if (n_local && (local_map_view(ctx, &lv) || lv.n != n)) return LINS_E_STATE;
   std::vector<MapDevHost> dev;
   int max_q = 0;
-  rc = map_upload(ctx, m, n, in, dev, &max_q);
+  rc = n_local ? map_upload_local(ctx, m, lv, dev, &max_q) : map_upload(ctx, m, n, in, dev, &max_q);
   if (rc) {
     m->resident_dev.clear(), m->resident_sizes.clear();
     return rc;
   }
+  const float4* d_q = n_local ? lv.d_out : m->d_q;
   const int bpp = std::max(1, (max_q + map_block() - 1) / map_block());
   if ((rc = grow(ctx, &m->d_partials, &m->cap_partials, (size_t)n * bpp * 28))) return rc;
   hipStream_t st = ctx_stream(ctx);
@@ -291,7 +374,7 @@ int lins_scan2map_batch(lins_ctx* ctx, int n, const lins_map_problem* in, lins_m
   MAP_TRY(ctx, hipEventRecord(e0, st));
   launch_map_lm(st, n, -1, bpp, m->d_probs, m->d_rounds, m->d_partials, m->d_results, m->d_carry);
   for (int iter = 0; iter < 10; ++iter) {
-    launch_map_corr(st, n, bpp, m->d_probs, m->d_rounds, m->d_pts, m->d_cells, m->d_q, m->d_rec, m->d_partials);
+    launch_map_corr(st, n, bpp, m->d_probs, m->d_rounds, m->d_pts, m->d_cells, d_q, m->d_rec, m->d_partials);
     launch_map_lm(st, n, iter, bpp, m->d_probs, m->d_rounds, m->d_partials, m->d_results, m->d_carry);
   }
   MAP_TRY(ctx, hipGetLastError());
@@ -306,6 +389,7 @@ int lins_scan2map_batch(lins_ctx* ctx, int n, const lins_map_problem* in, lins_m
 
 int lins_map_correspondences(lins_ctx* ctx, const lins_map_problem* in, lins_map_corr* corner, lins_map_corr* surf) {
   if (!ctx || !in || (in->n_scan_corner && !corner) || (in->n_scan_surf && !surf)) return LINS_E_ARG;
+  if (in->reserved[0] & LINS_MAP_LOCAL) return LINS_E_ARG;  // (explicit clouds only)
   if (map_dev_size() != sizeof(MapDevHost) || map_round_size() != sizeof(MapRoundParams)) return LINS_E_STATE;
   MAP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
   MapState* m = state_of(ctx);

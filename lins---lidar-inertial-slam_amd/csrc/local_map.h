@@ -1,0 +1,77 @@
+// local_map.h — the device records of the local-map build (local_map_kernels.hip, lins_local_map_capi.hip).
+//
+// A build runs VoxelGrid "jobs": per entry five in stage A (corner map, surf map, cornerDS, surfDS, outlierDS) and one
+// in stage B (surfTotalDS over surfDS ++ outlierDS).  Job j owns [off_in, off_in + cap) of the staging arena (input
+// points) and of the sort's key / value / run-start scratch, and [tile0, tile0 + ntiles) of its stage's tile grid.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/lins_map.h"
+
+namespace lins {
+
+constexpr int kLmTile = 512;   // points per tile = threads per workgroup of the tile kernels
+constexpr int kLmDigit = 8;    // radix bits per pass
+constexpr int kLmPasses = 4;   // keys < 2^31 need at most four 8-bit passes
+
+struct LmJob {
+  long long off_in;   // staging offset of the input points (and of the key / value / start scratch)
+  long long off_out;  // output offset in the cloud arena
+  int cap;            // upper bound of the input count (host-known)
+  int tile0, ntiles;  // tiles of this job in its stage's grid (ntiles = ceil(cap / kLmTile))
+  float inv;          // 1.0f / leaf, formed on the host as the restatement forms it
+  int out_after;      // job whose voxel count is added to off_out (surfTotalDS behind cornerDS), -1: none
+  int src_a, src_b;   // stage B: the jobs whose centroids are its input, -1: none
+  int feed;           // stage A: the stage-B job this job's centroids also feed, -1: none
+  int feed_after;     // ... written behind the centroids of this job, -1: at 0
+  int map;            // 1: a map cloud — the 1 m box of its output is folded
+  int pad;
+};
+static_assert(sizeof(LmJob) == 64, "LmJob layout");
+
+struct LmState {      // written by the kernels, read back once per build
+  unsigned mn[3], mx[3];  // f32 box of the input, order-preserving unsigned encoding (atomic min / max)
+  int n;                  // input points
+  int flags;              // bit 0: a transformed map point outside the input contract
+  int minb[3];
+  unsigned d0, d01;       // div0, div0 * div1
+  int passes;             // radix passes this job needs
+  int nvox;               // output points
+  int status;             // 0, LINS_E_INPUT or LINS_E_CAPACITY
+  int bmin[3], bmax[3];   // 1 m box of the output (map jobs)
+};
+static_assert(sizeof(LmState) == 88, "LmState layout");
+
+struct LmSeg {  // one cloud of one window frame moved into the map frame
+  long long src, dst;  // frame store offset, staging offset
+  int n, job;
+  float t[9];          // ctRoll, stRoll, ctPitch, stPitch, ctYaw, stYaw, tInX, tInY, tInZ
+  int pad;
+};
+static_assert(sizeof(LmSeg) == 64, "LmSeg layout");
+
+inline __host__ __device__ unsigned lm_enc(float f) {  // order-preserving float -> unsigned
+  unsigned u;
+  __builtin_memcpy(&u, &f, 4);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+inline __host__ __device__ float lm_dec(unsigned u) {
+  u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+  float f;
+  __builtin_memcpy(&f, &u, 4);
+  return f;
+}
+
+// (host side) the clouds of the last build where scan-to-map reads them: cloud c of entry k starts at
+// d_out + off[6 k + c] and holds sizes[k].n[c] points; cloud LINS_LOCAL_SCAN_TOTAL follows cloud LINS_LOCAL_SCAN_CORNER
+// directly — the query layout of map_upload.  LINS_E_STATE when there was no build.
+struct LocalMapView {
+  const float4* d_out;
+  int n;
+  const long long* off;
+  const lins_local_map_sizes* sizes;
+};
+int local_map_view(lins_ctx* ctx, LocalMapView* v);
+void** map_local_slot(lins_ctx* ctx, void (*free_fn)(void*));  // lins_map_capi.hip: held by the scan-to-map state
+
+}  // namespace lins

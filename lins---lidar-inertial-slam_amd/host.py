@@ -183,6 +183,35 @@ def lib():
     return _LIB
 
 
+def local_map(frames, scan, window=50):
+    """lins_host_local_map: the CPU restatement of lins_local_map_build for one entry.  frames: [(corner, surf, outlier,
+    pose (x, y, z, roll, pitch, yaw))] oldest first (the last `window` are used); scan: (corner, surf, outlier) raw.
+    Returns (the six clouds in LOCAL_* order, sizes dict)."""
+    from ._ctypes_defs import KeyframeC, LocalMapSizesC, keyframe_c, local_scan_c
+
+    L = lib()
+    fr, keep = (KeyframeC * max(len(frames), 1))(), []
+    for k, f in enumerate(frames):
+        fr[k], kk = keyframe_c(*f)
+        keep.append(kk)
+    sc, skeep = local_scan_c(*scan)
+    used = frames[max(0, len(frames) - window):]
+    ncorner = sum(len(f[0]) for f in used)
+    nsurf = sum(len(f[1]) + len(f[2]) for f in used)
+    caps = [ncorner, nsurf, len(skeep[0]), len(skeep[1]), len(skeep[2]), len(skeep[1]) + len(skeep[2])]
+    outs = [np.zeros((max(c, 1), 4), np.float32) for c in caps]
+    ptrs = (C.POINTER(Point) * 6)(*[o.ctypes.data_as(C.POINTER(Point)) for o in outs])
+    sizes = LocalMapSizesC()
+    L.lins_host_local_map.argtypes = [C.POINTER(KeyframeC), C.c_int, C.c_int, C.POINTER(type(sc)), C.POINTER(C.POINTER(Point)),
+                                      C.POINTER(LocalMapSizesC)]
+    L.lins_host_local_map.restype = C.c_int
+    rc = L.lins_host_local_map(fr, len(frames), int(window), C.byref(sc), ptrs, C.byref(sizes))
+    if rc != 0:
+        raise RuntimeError(f"lins_host_local_map: {rc}")
+    d = sizes.as_dict()
+    return [o[:n].copy() for o, n in zip(outs, d["n"])], d
+
+
 def _buf(n):
     a = np.zeros((n, 4), dtype=np.float32)
     return a, a.ctypes.data_as(C.POINTER(Point))

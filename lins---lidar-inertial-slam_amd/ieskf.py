@@ -25,7 +25,8 @@ EXPORTS = [
     "lins_last_segment_ms", "lins_streams_step_raw", "lins_map_correspondences", "lins_scan2map_batch",
     "lins_last_map_stats", "lins_last_search", "lins_kernel_ms_history", "lins_set_pipelined", "lins_set_launch_queues", "lins_runs_span_ms", "lins_launch_ms_history",
     "lins_rccl_unique_id", "lins_rccl_init", "lins_pose_allgather", "lins_rccl_destroy", "lins_last_index_ms", "lins_last_cut",
-    "lins_batch_map",
+    "lins_batch_map", "lins_local_map_init", "lins_local_map_push", "lins_local_map_build", "lins_local_map_push_scans",
+    "lins_local_map_set_pose", "lins_local_map_download", "lins_last_local_map_stats",
 ]
 
 
@@ -205,6 +206,76 @@ class IeskfContext:
         L.lins_last_map_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
         self._check(L.lins_last_map_stats(self._h, C.byref(ms), C.byref(q)))
         return ms.value, q.value
+
+    # -- the mapping node's local map on the device (include/lins_map.h lins_local_map_*) ------------
+    def local_map_init(self, n_slots, window=50, max_points_per_frame=16384):
+        self._check(lib().lins_local_map_init(self._h, int(n_slots), int(window), int(max_points_per_frame)))
+
+    def local_map_push(self, slot, corner, surf, outlier, pose):
+        """one key frame (sensor-frame clouds, pose (x, y, z, roll, pitch, yaw)) onto the ring of `slot`"""
+        from ._ctypes_defs import KeyframeC, keyframe_c
+
+        f, _keep = keyframe_c(corner, surf, outlier, pose)
+        L = lib()
+        L.lins_local_map_push.argtypes = [C.c_void_p, C.c_int, C.POINTER(KeyframeC)]
+        self._check(L.lins_local_map_push(self._h, int(slot), C.byref(f)))
+
+    def local_map_build(self, slots, scans):
+        """extractSurroundingKeyFrames + downsampleCurrentScan for len(slots) entries; scans: (corner, surf, outlier)
+        raw clouds per entry.  Returns the per-entry sizes dicts (n, box_min, box_dim, frames, status)."""
+        from ._ctypes_defs import LocalMapSizesC, LocalScanC, local_scan_c
+
+        n = len(slots)
+        keep, arr = [], (LocalScanC * max(n, 1))()
+        for k, sc in enumerate(scans):
+            arr[k], kk = local_scan_c(*sc)
+            keep.append(kk)
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        out = (LocalMapSizesC * max(n, 1))()
+        L = lib()
+        L.lins_local_map_build.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(LocalScanC), C.POINTER(LocalMapSizesC)]
+        self._local_sizes = []
+        self._check(L.lins_local_map_build(self._h, n, sl.ctypes.data, arr, out))
+        self._local_sizes = [out[k].as_dict() for k in range(n)]
+        return self._local_sizes
+
+    def local_map_push_scans(self, entries, poses):
+        """the cornerDS / surfDS / outlierDS of the chosen entries of the last build become key frames of their slots"""
+        from ._ctypes_defs import KeyPoseC, key_pose
+
+        n = len(entries)
+        e = np.ascontiguousarray(entries, dtype=np.int32)
+        ps = (KeyPoseC * max(n, 1))(*[key_pose(p) for p in poses])
+        L = lib()
+        L.lins_local_map_push_scans.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(KeyPoseC)]
+        self._check(L.lins_local_map_push_scans(self._h, n, e.ctypes.data, ps))
+
+    def local_map_set_pose(self, slot, age, pose):
+        from ._ctypes_defs import KeyPoseC, key_pose
+
+        p = key_pose(pose)
+        L = lib()
+        L.lins_local_map_set_pose.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(KeyPoseC)]
+        self._check(L.lins_local_map_set_pose(self._h, int(slot), int(age), C.byref(p)))
+
+    def local_map_download(self, entry, which):
+        """cloud `which` (LOCAL_*) of entry `entry` of the last build, (n, 4) f32"""
+        sizes = getattr(self, "_local_sizes", [])
+        cap = sizes[entry]["n"][which] if 0 <= entry < len(sizes) and 0 <= which < 6 else 0
+        out = np.zeros((max(cap, 1), 4), np.float32)
+        L = lib()
+        L.lins_local_map_download.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        rc = L.lins_local_map_download(self._h, int(entry), int(which), out.ctypes.data, int(cap))
+        if rc < 0:
+            self._check(rc)
+        return out[:rc].copy()
+
+    def local_map_stats(self):
+        ms, pts = C.c_float(0), C.c_uint64(0)
+        L = lib()
+        L.lins_last_local_map_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+        self._check(L.lins_last_local_map_stats(self._h, C.byref(ms), C.byref(pts)))
+        return ms.value, pts.value
 
     # -- image_projection_node on the device: raw clouds -> segmented scans --------------------
     def segment_batch(self, raws):
