@@ -225,7 +225,10 @@
           need_walk = !ok23 || verify;
         }
       }
-      warm2 = a2, warm3 = a3;
+      // (a query without a nearest neighbour last iteration has no walk part of its own: planes 2-3 then hold whatever an
+      // earlier iteration, update or scan left in the slot — positions that may name the other cloud — never warm candidates)
+      const bool own_set = sel_old >= 0 || dirty;
+      warm2 = own_set ? a2 : -1, warm3 = own_set ? a3 : -1;
       if (need_walk && warm_iter) reseed2 = drift_from(__uint_as_float(w1.x), __uint_as_float(w1.y), __uint_as_float(w1.z)) > prm.reseed_drift;
       if (active && p1 >= 0 && !need_walk) {  // finished: predictions taken, record written when it changed
         p2 = pred2, p3 = pred3;

@@ -835,6 +835,7 @@ int lins_create(const lins_params* params, int device, int max_batch, int max_ta
       if (const char* e = std::getenv("LINS_RELAY_SPINS")) ctx->relay_spins = std::max(0, std::atoi(e));
       if (const char* e = std::getenv("LINS_QUEUE_GRID")) ctx->queue_grid = std::max(1, std::atoi(e));  // (batches beyond this many scans are cut)
       if (const char* e = std::getenv("LINS_STREAMS_FUSE")) ctx->streams_fuse = e[0] != '0';  // (0: re-projection and index build as two kernels)
+      if (const char* e = std::getenv("LINS_RUN_GEN0")) ctx->run_gen = std::atoi(e);  // (test aid: the walk cache's 16-bit wrap on a chosen launch)
     }
   ctx->max_batch = max_batch;
   ctx->max_targets = max_targets;
@@ -885,6 +886,7 @@ int lins_create(const lins_params* params, int device, int max_batch, int max_ta
   // the carry records of the batch kernel's queries (ieskf_lds_lean.h: tracked candidates and certificates between the
   // iterations of an update; 32 KB per scan): every launch of that kernel uses them, cut into parts or not
   CREATE_TRY(hipMalloc((void**)&ctx->d_relay_lane, (size_t)ctx->max_batch * kLaneIntsPerScan * sizeof(int)));
+  CREATE_TRY(hipMemset(ctx->d_relay_lane, 0xFF, (size_t)ctx->max_batch * kLaneIntsPerScan * sizeof(int)));  // (empty records)
   if (ctx->max_batch > ctx->queue_grid && lds_mr_has_parts()) {  // (only batches beyond the device's workgroup slots are cut into parts)
     CREATE_TRY(hipMalloc((void**)&ctx->d_relay_hdr, (size_t)ctx->max_batch * 64 * sizeof(double)));
     CREATE_TRY(hipHostMalloc((void**)&ctx->h_relay_err, sizeof(int)));
@@ -1104,12 +1106,20 @@ int lins_batch_run(lins_ctx* ctx, void* d_poses, int32_t scan_id_base) {
     if (int rcs = split_join(ctx)) return rcs;
   if (split) {
     if (int rcq = split_prepare(ctx)) return rcq;
+    const int n = ctx->n_uploaded, n_launch = (n + ctx->queue_grid - 1) / ctx->queue_grid, per = (n + n_launch - 1) / n_launch;
+    if (ctx->d_walk_cache && (ctx->run_gen & 0xFFFF) + n_launch > 0xFFFF) {
+      // the launch numbers of this run would come round in their low 16 bits (the walk cache's tags): next_run_gen's clear on
+      // the context's stream would not be ordered against the second queue's launches — the cache is cleared HERE instead,
+      // behind both queues and ahead of every launch of the run (the fork below), and the run starts the new round of numbers
+      if (int rcs = split_join(ctx)) return rcs;
+      HIP_TRY(ctx, hipMemsetAsync(ctx->d_walk_cache, 0xFF, ctx->slot_cap * 32, ctx->stream));
+      ctx->run_gen = (ctx->run_gen | 0xFFFF) + 1;
+    }
     if (ctx->split_dirty) {  // (uploads, index builds, downloads since the last fork: the second queue starts behind them)
       HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
       HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
       ctx->split_dirty = false;
     }
-    const int n = ctx->n_uploaded, n_launch = (n + ctx->queue_grid - 1) / ctx->queue_grid, per = (n + n_launch - 1) / n_launch;
     RangeFlags fl;
     fl.lds_ok = ctx->lds_ok, fl.mr_ok = ctx->mr_ok, fl.lds3_ok = ctx->lds3_ok;
     if (wait_comm) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, q.ev_comm[set], 0));  // (the second queue writes that pose buffer too)
@@ -1399,6 +1409,25 @@ int lins_debug_math(lins_ctx* ctx, int op, int n, const double* in, int n_in, do
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   (void)hipFree(d_in), (void)hipFree(d_out), (void)hipFree(d_lm);
   if (e != hipSuccess) return fail_hip(ctx, e, "lins_debug_math");
+  return LINS_OK;
+}
+
+/* Debug aid (not part of the drop-in surface; tests/test_gpu_context_state.py): read (write = 0) or write (write = 1)
+ * `bytes` bytes at `offset_bytes` of the context's scratch state that outlives a run — which = 0: the carry records of
+ * the batch kernel (ieskf_lds_lean.h, kLaneIntsPerScan ints per scan), 1: the walk cache (32 B per query slot).
+ * Synchronous, ordered behind both launch queues and the gather stream. */
+int lins_debug_scratch(lins_ctx* ctx, int which, int write, size_t offset_bytes, size_t bytes, void* host) {
+  if (!ctx || !host || (which != 0 && which != 1)) return LINS_E_ARG;
+  char* const base = which == 0 ? reinterpret_cast<char*>(ctx->d_relay_lane) : reinterpret_cast<char*>(ctx->d_walk_cache);
+  const size_t cap = which == 0 ? (size_t)ctx->max_batch * kLaneIntsPerScan * sizeof(int) : ctx->slot_cap * 32;
+  if (!base || offset_bytes > cap || bytes > cap - offset_bytes) return LINS_E_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = pipe_join(ctx)) return rc;
+  if (write)
+    HIP_TRY(ctx, hipMemcpyAsync(base + offset_bytes, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+  else
+    HIP_TRY(ctx, hipMemcpyAsync(host, base + offset_bytes, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return LINS_OK;
 }
 
@@ -2290,6 +2319,7 @@ int lins_ieskf_update_batch(lins_ctx* ctx, int n, const lins_scan_pair* in, lins
   // (the history entry of this call spans the whole pipelined region: the kernels of all chunks AND the copy waits
   // between them — lins_last_kernel_ms() after lins_ieskf_update_batch() is an upper bound of the kernel time)
   HIP_TRY(ctx, hipEventRecord(ctx->hist1[ctx->hist_n % lins_ctx::kHist], ctx->stream));
+  ctx->hist_split[ctx->hist_n % lins_ctx::kHist] = false;  // (one queue: the slot's second-queue events are another run's)
   ctx->hist_n++;
   // the batch stays resident (inputs, search index): a later lins_batch_run finds its launch order too
   launch_order(ctx, n);
