@@ -35,7 +35,9 @@ typedef struct lins_map_problem {
 /* reserved[0] flag: the two map clouds of this problem are the ones of the previous call at the same batch index
  * (the mapping node's local map only changes with its key frames): when EVERY problem of a batch says so and the
  * sizes match, the maps already resident on the device — uploaded and bucketed into 1 m cells by the last call —
- * are used as they are; map_corner / map_surf are not read.                                                     */
+ * are used as they are; map_corner / map_surf are not read.  "The previous call" is the last one that succeeded AND
+ * no call failed since: a call that returns an error other than LINS_E_ARG / LINS_E_STATE leaves nothing resident, so
+ * a LINS_MAP_REUSE call behind it uploads its own maps.                                                            */
 #define LINS_MAP_REUSE 1
 /* reserved[0] flag: problem k is entry k of the last lins_local_map_build — maps and queries are the clouds that call
  * built on the device (laserCloudCornerFromMapDS / SurfFromMapDS, laserCloudCornerLastDS / SurfTotalLastDS) and are
@@ -60,6 +62,13 @@ typedef struct lins_map_result {
   int32_t n_sel;      /* rows selected in the last round */
 } lins_map_result;
 
+/* Input contract of the two calls below.  Map points: finite, |coord| <= 1e6 (LINS_E_INPUT), at most 2^26 cells of
+ * 1 m in a cloud's box (LINS_E_CAPACITY).  Scan points: finite (LINS_E_INPUT), of any magnitude.  transform: finite
+ * (LINS_E_INPUT).  A call that fails this way changes no result, leaves no map resident and the context usable.  Where a query's
+ * associated point lands is NOT part of the contract: far from the map, beyond the range of an int, or non-finite (the
+ * transform of a later round is the optimisation's own), it has no fifth neighbour within 1 m and gets ind = -1,
+ * accepted = 0, sq5 = inf — the device clamps the point to +-2^30 in float before it takes its cell, so the cell
+ * arithmetic is defined for every float and the other queries of the batch are not affected.                      */
 /* one correspondence pass at in->transform: n_scan_corner + n_scan_surf records */
 int lins_map_correspondences(lins_ctx* ctx, const lins_map_problem* in, lins_map_corr* corner, lins_map_corr* surf);
 /* scan2MapOptimization for n independent problems, entirely on the device: the maps are bucketed into 1 m cells by

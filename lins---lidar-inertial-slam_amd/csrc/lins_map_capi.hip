@@ -68,6 +68,7 @@ struct MapState {
   float ms = 0.f;
   uint64_t queries = 0;
   bool selfcheck_done = false;
+  int max_rounds = 10;  // lins_debug_map_rounds (test aid): the rounds lins_scan2map_batch runs at most
   // the local-map state of lins_local_map_* (lins_local_map_capi.hip), freed with this one
   void* local = nullptr;
   void (*local_free)(void*) = nullptr;
@@ -294,6 +295,12 @@ int map_upload_local(lins_ctx* ctx, MapState* m, const LocalMapView& lv, std::ve
   return LINS_OK;
 }
 
+bool transform_finite(const float* t) {
+  for (int i = 0; i < 6; ++i)
+    if (!std::isfinite(t[i])) return false;
+  return true;
+}
+
 MapState* state_of(lins_ctx* ctx) {
   void** slot = ctx_map_slot(ctx, map_state_free);
   if (!*slot) *slot = new MapState();
@@ -348,6 +355,11 @@ int lins_scan2map_batch(lins_ctx* ctx, int n, const lins_map_problem* in, lins_m
     n_local += (fl & LINS_MAP_LOCAL) != 0;
   }
   if (n_local && n_local != n) return LINS_E_ARG;  // a batch is local or explicit, not both
+  for (int k = 0; k < n; ++k)
+    if (!transform_finite(in[k].transform)) {  // (input contract, lins_map.h: like every LINS_E_INPUT, nothing stays resident)
+      m->resident_dev.clear(), m->resident_sizes.clear();
+      return LINS_E_INPUT;
+    }
   LocalMapView lv{};
   if (n_local && (local_map_view(ctx, &lv) || lv.n != n)) return LINS_E_STATE;
   std::vector<MapDevHost> dev;
@@ -373,7 +385,7 @@ int lins_scan2map_batch(lins_ctx* ctx, int n, const lins_map_problem* in, lins_m
   MAP_TRY(ctx, hipMemcpyAsync(m->d_results, out, (size_t)n * sizeof(lins_map_result), hipMemcpyHostToDevice, st));
   MAP_TRY(ctx, hipEventRecord(e0, st));
   launch_map_lm(st, n, -1, bpp, m->d_probs, m->d_rounds, m->d_partials, m->d_results, m->d_carry);
-  for (int iter = 0; iter < 10; ++iter) {
+  for (int iter = 0; iter < m->max_rounds; ++iter) {
     launch_map_corr(st, n, bpp, m->d_probs, m->d_rounds, m->d_pts, m->d_cells, d_q, m->d_rec, m->d_partials);
     launch_map_lm(st, n, iter, bpp, m->d_probs, m->d_rounds, m->d_partials, m->d_results, m->d_carry);
   }
@@ -397,7 +409,7 @@ int lins_map_correspondences(lins_ctx* ctx, const lins_map_problem* in, lins_map
   if (rc) return rc;
   std::vector<MapDevHost> dev;
   int max_q = 0;
-  rc = map_upload(ctx, m, 1, in, dev, &max_q);
+  rc = transform_finite(in->transform) ? map_upload(ctx, m, 1, in, dev, &max_q) : (int)LINS_E_INPUT;
   if (rc) {
     m->resident_dev.clear(), m->resident_sizes.clear();
     return rc;
@@ -416,6 +428,15 @@ int lins_map_correspondences(lins_ctx* ctx, const lins_map_problem* in, lins_map
   if (in->n_scan_surf)
     MAP_TRY(ctx, hipMemcpyAsync(surf, m->d_rec + in->n_scan_corner, (size_t)in->n_scan_surf * sizeof(lins_map_corr), hipMemcpyDeviceToHost, st));
   MAP_TRY(ctx, hipStreamSynchronize(st));
+  return LINS_OK;
+}
+
+/* Debug aid (not part of the drop-in surface; tests/test_gpu_map_rounds.py): lins_scan2map_batch of this context stops
+ * after `rounds` rounds (0 .. 10; 10 is the behaviour without the call) — results are those of the last round run, so
+ * that every round of the device's own loop can be held against the oracle's trace.  Declared by its users. */
+int lins_debug_map_rounds(lins_ctx* ctx, int rounds) {
+  if (!ctx || rounds < 0 || rounds > 10) return LINS_E_ARG;
+  state_of(ctx)->max_rounds = rounds;
   return LINS_OK;
 }
 

@@ -76,7 +76,14 @@ __global__ __launch_bounds__(kMapBlock) void map_corr_kernel(const MapDev* __res
     const unsigned long long kNoKey = ((unsigned long long)0x7F800000u << 32) | 0xFFFFFFFFull;
     unsigned long long key[5] = {kNoKey, kNoKey, kNoKey, kNoKey, kNoKey};
     int pos[5] = {-1, -1, -1, -1, -1};
-    const int cx = (int)floorf(sx) - g.cmin[0], cy = (int)floorf(sy) - g.cmin[1], cz = (int)floorf(sz) - g.cmin[2];
+    // The query's cell, defined for EVERY float: the associated point is clamped to +-2^30 before the conversion (the
+    // transform of a later round is the device's own and may be anything, NaN included).  Map boxes lie within
+    // +-1e6 (cloud_box), so a clamped point's cell is more than one cell outside every box and meets no point — what
+    // the exhaustive search gives for it too (no fifth neighbour within 1 m); fmaxf / fminf return the other operand
+    // for a NaN, which lands there as well.  Below 2^30 floorf and the conversion are exact and nothing overflows.
+    const float kFar = 1073741824.f;
+    const int cx = (int)floorf(fminf(fmaxf(sx, -kFar), kFar)) - g.cmin[0], cy = (int)floorf(fminf(fmaxf(sy, -kFar), kFar)) - g.cmin[1],
+              cz = (int)floorf(fminf(fmaxf(sz, -kFar), kFar)) - g.cmin[2];
     const float4* gp = pts + g.off_pts;
     const int* gc = cells + g.off_cells;
     for (int dz = -1; dz <= 1; ++dz)

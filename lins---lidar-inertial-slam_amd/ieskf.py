@@ -200,6 +200,13 @@ class IeskfContext:
         return [dict(transform=np.array(r.transform[:], dtype=np.float32), iters=r.iters, converged=r.converged,
                      degenerate=r.degenerate, n_sel=r.n_sel) for r in res]
 
+    def debug_map_rounds(self, rounds):
+        """test aid (lins_debug_map_rounds): scan2map_batch of this context stops after `rounds` rounds (10: as shipped)"""
+        L = lib()
+        L.lins_debug_map_rounds.argtypes = [C.c_void_p, C.c_int]
+        L.lins_debug_map_rounds.restype = C.c_int
+        self._check(L.lins_debug_map_rounds(self._h, int(rounds)))
+
     def map_stats(self):
         ms, q = C.c_float(0), C.c_uint64(0)
         L = lib()

@@ -82,7 +82,8 @@ void qr_solve(float* a, float* b, float* x) {
 void inv6(const float* A, float* inv) { lins_cvr::inv(A, 6, inv); }
 
 // cornerOptimization's body for one point (LM:1354-1452)
-void corner_one(const Assoc& as, const lins_point* map, int n_map, const lins_point& ori, lins_map_corr& out) {
+// (fq, the traced form only: the quantities the accept / reject branches decide on — see oracle_map_fit_quantities)
+void corner_one(const Assoc& as, const lins_point* map, int n_map, const lins_point& ori, lins_map_corr& out, double* fq = nullptr) {
   const P3 sel = associate(as, ori);
   out.sel[0] = sel.x, out.sel[1] = sel.y, out.sel[2] = sel.z;
   float sq[5];
@@ -106,6 +107,7 @@ void corner_one(const Assoc& as, const lins_point* map, int n_map, const lins_po
   a11 /= 5, a12 /= 5, a13 /= 5, a22 /= 5, a23 /= 5, a33 /= 5;
   float A[9] = {a11, a12, a13, a12, a22, a23, a13, a23, a33}, D[3], V[9];
   jacobi_eig<3>(A, D, V);
+  if (fq) fq[0] = 1, fq[1] = D[0], fq[2] = D[1];
   if (!(D[0] > 3 * D[1])) return;
   float x0 = sel.x, y0 = sel.y, z0 = sel.z;
   float x1 = cx + 0.1 * V[0], y1 = cy + 0.1 * V[1], z1 = cz + 0.1 * V[2];
@@ -125,12 +127,13 @@ void corner_one(const Assoc& as, const lins_point* map, int n_map, const lins_po
              a012 / l12;
   float ld2 = a012 / l12;
   float s = 1 - 0.9 * std::fabs(ld2);
+  if (fq) fq[0] = 2, fq[3] = s;
   out.coeff[0] = s * la, out.coeff[1] = s * lb, out.coeff[2] = s * lc, out.coeff[3] = s * ld2;
   if (s > 0.1) out.accepted = 1;
 }
 
 // surfOptimization's body for one point (LM:1458-1519)
-void surf_one(const Assoc& as, const lins_point* map, int n_map, const lins_point& ori, lins_map_corr& out) {
+void surf_one(const Assoc& as, const lins_point* map, int n_map, const lins_point& ori, lins_map_corr& out, double* fq = nullptr) {
   const P3 sel = associate(as, ori);
   out.sel[0] = sel.x, out.sel[1] = sel.y, out.sel[2] = sel.z;
   float sq[5];
@@ -149,6 +152,13 @@ void surf_one(const Assoc& as, const lins_point* map, int n_map, const lins_poin
   float pa = X[0], pb = X[1], pc = X[2], pd = 1;
   float ps = std::sqrt(pa * pa + pb * pb + pc * pc);
   pa /= ps, pb /= ps, pc /= ps, pd /= ps;
+  if (fq) {  // (the largest of the five plane distances: the loop below stops at the first one beyond 0.2)
+    fq[0] = 1, fq[1] = 0;
+    for (int j = 0; j < 5; j++) {
+      const float d = std::fabs(pa * map[out.ind[j]].x + pb * map[out.ind[j]].y + pc * map[out.ind[j]].z + pd);
+      if (d > fq[1]) fq[1] = d;
+    }
+  }
   bool planeValid = true;
   for (int j = 0; j < 5; j++)
     if (std::fabs(pa * map[out.ind[j]].x + pb * map[out.ind[j]].y + pc * map[out.ind[j]].z + pd) > 0.2) {
@@ -158,6 +168,7 @@ void surf_one(const Assoc& as, const lins_point* map, int n_map, const lins_poin
   if (!planeValid) return;
   float pd2 = pa * sel.x + pb * sel.y + pc * sel.z + pd;
   float s = 1 - 0.9 * std::fabs(pd2) / std::sqrt(std::sqrt(sel.x * sel.x + sel.y * sel.y + sel.z * sel.z));
+  if (fq) fq[0] = 2, fq[3] = s;
   out.coeff[0] = s * pa, out.coeff[1] = s * pb, out.coeff[2] = s * pc, out.coeff[3] = s * pd2;
   if (s > 0.1) out.accepted = 1;
 }
@@ -168,11 +179,13 @@ struct LmState {
 };
 
 // LMOptimization (LM:1523-1633) on the selected rows; true = converged
-bool lm_step(float* T, const std::vector<lins_point>& ori, const std::vector<lins_map_corr>& sel, int iter, LmState& st) {
+// (sums27, the traced form only: the upper triangle of A^T A row by row, then A^T b — also of a round that returns early)
+bool lm_step(float* T, const std::vector<lins_point>& ori, const std::vector<lins_map_corr>& sel, int iter, LmState& st,
+             double* sums27 = nullptr) {
   float srx = std::sin(T[0]), crx = std::cos(T[0]), sry = std::sin(T[1]), cry = std::cos(T[1]);
   float srz = std::sin(T[2]), crz = std::cos(T[2]);
   const int n = (int)ori.size();
-  if (n < 50) return false;
+  if (n < 50 && !sums27) return false;
   double AtA[36] = {0}, AtB[6] = {0};
   for (int i = 0; i < n; i++) {
     const lins_point& pointOri = ori[i];
@@ -194,6 +207,13 @@ bool lm_step(float* T, const std::vector<lins_point>& ori, const std::vector<lin
       AtB[a] += (double)row[a] * (double)b;
     }
   }
+  if (sums27) {
+    int t = 0;
+    for (int a = 0; a < 6; ++a)
+      for (int e = a; e < 6; ++e) sums27[t++] = AtA[a * 6 + e];
+    for (int a = 0; a < 6; ++a) sums27[21 + a] = AtB[a];
+  }
+  if (n < 50) return false;  // LM:1530-1532
   float A[36], B[6], X[6], Aq[36], Bq[6];
   for (int i = 0; i < 36; ++i) A[i] = (float)AtA[i];
   for (int i = 0; i < 6; ++i) B[i] = (float)AtB[i];
@@ -240,7 +260,11 @@ int oracle_map_correspondences(const lins_map_problem* in, lins_map_corr* corner
   return LINS_OK;
 }
 
-int oracle_scan2map(const lins_map_problem* in, lins_map_result* out) {
+// scan2MapOptimization; trace (may be NULL) gets 42 doubles per executed round, at most
+// cap_rounds rounds of them: [0..5] the transform entering the round, [6] n_sel, [7..27] the upper triangle of A^T A row
+// by row, [28..33] A^T b (both f64, rows in selection order: corner then surf), [34..39] the transform leaving the
+// round, [40] isDegenerate after it, [41] LMOptimization's return value.
+static int scan2map_impl(const lins_map_problem* in, lins_map_result* out, double* trace, int cap_rounds) {
   if (!in || !out) return LINS_E_ARG;
   std::memcpy(out->transform, in->transform, sizeof out->transform);
   out->iters = 0, out->converged = 0, out->degenerate = 0, out->n_sel = 0;
@@ -259,12 +283,70 @@ int oracle_scan2map(const lins_map_problem* in, lins_map_result* out) {
       if (s[i].accepted) ori.push_back(in->scan_surf[i]), sel.push_back(s[i]);
     out->n_sel = (int)ori.size();
     out->iters = iter + 1;
-    if (lm_step(out->transform, ori, sel, iter, st)) {
+    double* tr = trace && iter < cap_rounds ? trace + (size_t)iter * 42 : nullptr;
+    if (tr) {
+      for (int i = 0; i < 6; ++i) tr[i] = out->transform[i];
+      tr[6] = out->n_sel;
+    }
+    const bool conv = lm_step(out->transform, ori, sel, iter, st, tr ? tr + 7 : nullptr);
+    if (tr) {
+      for (int i = 0; i < 6; ++i) tr[34 + i] = out->transform[i];
+      tr[40] = st.degenerate ? 1 : 0, tr[41] = conv ? 1 : 0;
+    }
+    if (conv) {
       out->converged = 1;
       break;
     }
   }
   out->degenerate = st.degenerate ? 1 : 0;
+  return LINS_OK;
+}
+
+int oracle_scan2map(const lins_map_problem* in, lins_map_result* out) { return scan2map_impl(in, out, nullptr, 0); }
+
+int oracle_scan2map_trace(const lins_map_problem* in, lins_map_result* out, double* trace, int cap_rounds) {
+  if (!trace || cap_rounds < 0) return LINS_E_ARG;
+  return scan2map_impl(in, out, trace, cap_rounds);
+}
+
+// LMOptimization's 21 + 6 sums (the layout of the trace) of GIVEN correspondence records — the device's, say — at
+// in->transform: the oracle's row formula and its summation order over the accepted records, corner then surf.
+int oracle_map_sums(const lins_map_problem* in, const lins_map_corr* corner, const lins_map_corr* surf, double* sums27, int* n_sel) {
+  if (!in || !sums27) return LINS_E_ARG;
+  std::vector<lins_point> ori;
+  std::vector<lins_map_corr> sel;
+  for (int i = 0; i < in->n_scan_corner; ++i)
+    if (corner[i].accepted) ori.push_back(in->scan_corner[i]), sel.push_back(corner[i]);
+  for (int i = 0; i < in->n_scan_surf; ++i)
+    if (surf[i].accepted) ori.push_back(in->scan_surf[i]), sel.push_back(surf[i]);
+  float T[6];
+  std::memcpy(T, in->transform, sizeof T);
+  LmState st;
+  // (the sums are written before anything moves; the step itself runs on a copy and is dropped.  Round 1: no eigen-test.)
+  lm_step(T, ori, sel, 1, st, sums27);
+  if (n_sel) *n_sel = (int)ori.size();
+  return LINS_OK;
+}
+
+// The quantities the two fits decide on, four doubles per query (corner queries, then surf queries), at in->transform:
+//   [0] how far the query got: 0 fewer than five neighbours within 1 m, 1 stopped at the shape test (corner: largest
+//       eigenvalue > 3 x the second; surf: every neighbour within 0.2 of the plane), 2 reached the weight test (s > 0.1)
+//   [1] corner: largest eigenvalue; surf: the largest |distance| of the five neighbours to the fitted plane
+//   [2] corner: second eigenvalue; surf: 0        [3] the weight s (stage 2 only)
+int oracle_map_fit_quantities(const lins_map_problem* in, double* corner4, double* surf4) {
+  if (!in) return LINS_E_ARG;
+  const Assoc as = make_assoc(in->transform);
+  lins_map_corr r;
+  for (int i = 0; i < in->n_scan_corner; ++i) {
+    double* q = corner4 + 4 * (size_t)i;
+    q[0] = q[1] = q[2] = q[3] = 0;
+    corner_one(as, in->map_corner, in->n_map_corner, in->scan_corner[i], r, q);
+  }
+  for (int i = 0; i < in->n_scan_surf; ++i) {
+    double* q = surf4 + 4 * (size_t)i;
+    q[0] = q[1] = q[2] = q[3] = 0;
+    surf_one(as, in->map_surf, in->n_map_surf, in->scan_surf[i], r, q);
+  }
   return LINS_OK;
 }
 

@@ -206,6 +206,54 @@ def scan2map(problem):
                 degenerate=r.degenerate, n_sel=r.n_sel)
 
 
+def scan2map_trace(problem):
+    """scan2map() with its rounds: (result dict, list of per-round dicts) — per executed round the transform entering
+    it (t_in), n_sel, the 21 + 6 f64 sums of LMOptimization (sums: upper triangle of A^T A row by row, then A^T b;
+    also of a round that returns early for fewer than 50 rows), the transform leaving it (t_out), isDegenerate after it
+    and LMOptimization's return value (converged)."""
+    c = problem.as_c()
+    r = _defs.MapResultC()
+    tr = np.zeros((10, 42), np.float64)
+    L = lib()
+    L.oracle_scan2map_trace.argtypes = [C.POINTER(_defs.MapProblemC), C.POINTER(_defs.MapResultC), C.c_void_p, C.c_int]
+    rc = L.oracle_scan2map_trace(C.byref(c), C.byref(r), tr.ctypes.data, 10)
+    assert rc == 0, rc
+    res = dict(transform=np.array(r.transform[:], dtype=np.float32), iters=r.iters, converged=r.converged,
+               degenerate=r.degenerate, n_sel=r.n_sel)
+    rounds = [dict(t_in=t[0:6].astype(np.float32), n_sel=int(t[6]), sums=t[7:34].copy(), t_out=t[34:40].astype(np.float32),
+                   degenerate=int(t[40]), converged=int(t[41])) for t in tr[:r.iters]]
+    return res, rounds
+
+
+def map_sums(problem, corner, surf):
+    """LMOptimization's 21 + 6 f64 sums (scan2map_trace's layout) of given correspondence records at problem.transform,
+    by the oracle's row formula in the oracle's order -> (sums[27], n_sel)"""
+    c = problem.as_c()
+    corner, surf = np.ascontiguousarray(corner), np.ascontiguousarray(surf)
+    assert corner.dtype == _defs.MAP_CORR_DTYPE and surf.dtype == _defs.MAP_CORR_DTYPE
+    assert len(corner) == len(problem.scan_corner) and len(surf) == len(problem.scan_surf)
+    sums, n = np.zeros(27, np.float64), C.c_int(0)
+    L = lib()
+    L.oracle_map_sums.argtypes = [C.POINTER(_defs.MapProblemC), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+    rc = L.oracle_map_sums(C.byref(c), corner.ctypes.data, surf.ctypes.data, sums.ctypes.data, C.byref(n))
+    assert rc == 0, rc
+    return sums, n.value
+
+
+def map_fit_quantities(problem):
+    """what the accept / reject branches of the two fits decide on, per query: (corner (n, 4), surf (n, 4)) float64 —
+    [0] stage reached (0: fewer than five neighbours within 1 m, 1: stopped at the shape test, 2: reached the weight
+    test), [1] corner: largest eigenvalue / surf: largest neighbour-to-plane distance, [2] corner: second eigenvalue,
+    [3] the weight s (stage 2)"""
+    c = problem.as_c()
+    qc, qs = np.zeros((len(problem.scan_corner), 4)), np.zeros((len(problem.scan_surf), 4))
+    L = lib()
+    L.oracle_map_fit_quantities.argtypes = [C.POINTER(_defs.MapProblemC), C.c_void_p, C.c_void_p]
+    rc = L.oracle_map_fit_quantities(C.byref(c), qc.ctypes.data, qs.ctypes.data)
+    assert rc == 0, rc
+    return qc, qs
+
+
 # ---- stages either side of the update (oracle/frontend_oracle.cpp: independent of csrc/, libm angles) ----------
 CLOUD_MAX = 16 * 1800
 

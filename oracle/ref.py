@@ -290,6 +290,19 @@ def scan2map(problem):
                 degenerate=r.degenerate, n_sel=r.n_sel)
 
 
+def scan2map_rounds(problem):
+    """scan2map() and transformTobeMapped after every round it ran: (result dict, (iters, 6) float32)"""
+    c = problem.as_c()
+    r = _defs.MapResultC()
+    t = np.zeros((10, 6), np.float32)
+    L = lib()
+    L.ref_scan2map_rounds.argtypes = [C.POINTER(_defs.MapProblemC), C.POINTER(_defs.MapResultC), C.c_void_p]
+    rc = L.ref_scan2map_rounds(C.byref(c), C.byref(r), t.ctypes.data)
+    assert rc == 0, rc
+    return dict(transform=np.array(r.transform[:], dtype=np.float32), iters=r.iters, converged=r.converged,
+                degenerate=r.degenerate, n_sel=r.n_sel), t[:r.iters].copy()
+
+
 def filter_run(fprm, vn, ba, bw, imu, reset1=False):
     """StatePredictor: initialization(0, 0, vn, ba, bw) -> predict() per row of imu (dt, acc, gyr) -> optional reset(1).
     fprm: host.FilterParams.  Returns (state19, cov 18x18)."""

@@ -79,7 +79,7 @@ int ref_map_rows(const lins_map_problem* in, lins_point* ori, float* coeff4, int
 // scan2MapOptimization.  The transform comes from the node's own scan2MapOptimization(); the counters (rounds run,
 // converged, rows of the last round, degenerate) from a second object driven round by round through the same three
 // member functions — whose transform must equal the first's (-9 otherwise).
-int ref_scan2map(const lins_map_problem* in, lins_map_result* out) {
+static int scan2map_rounds(const lins_map_problem* in, lins_map_result* out, float* t_after) {
   if (!in || !out) return -1;
   parameter::LINE_NUM = 16, parameter::SCAN_NUM = 1800;
   ros::NodeHandle nh, pnh("~");
@@ -96,7 +96,10 @@ int ref_scan2map(const lins_map_problem* in, lins_map_result* out) {
       steps.surfOptimization(iter);
       out->n_sel = (int)steps.laserCloudOri->points.size();
       out->iters = iter + 1;
-      if (steps.LMOptimization(iter)) {
+      const bool conv = steps.LMOptimization(iter);
+      if (t_after)
+        for (int i = 0; i < 6; ++i) t_after[6 * iter + i] = steps.transformTobeMapped[i];
+      if (conv) {
         out->converged = 1;
         break;
       }
@@ -107,6 +110,14 @@ int ref_scan2map(const lins_map_problem* in, lins_map_result* out) {
   for (int i = 0; i < 6; ++i)
     if (std::memcmp(&whole.transformTobeMapped[i], &steps.transformTobeMapped[i], sizeof(float)) != 0) return -9;
   return 0;
+}
+
+int ref_scan2map(const lins_map_problem* in, lins_map_result* out) { return scan2map_rounds(in, out, nullptr); }
+
+// ref_scan2map + transformTobeMapped after every round run (t_after: 10 x 6 floats, the first out->iters rows written)
+int ref_scan2map_rounds(const lins_map_problem* in, lins_map_result* out, float* t_after) {
+  if (!t_after) return -1;
+  return scan2map_rounds(in, out, t_after);
 }
 
 }  // extern "C"
