@@ -22,6 +22,7 @@
 #include "ieskf_device.h"
 #include "ieskf_rowsum.h"
 #include "icp_wave.h"
+#include "lins_launch.h"
 
 namespace lins {
 

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/lins_host.h"
+#include "lins_launch.h"
 #include "lins_math.h"
 
 namespace lins {
@@ -35,15 +36,6 @@ constexpr int kFeBlock = 1024;
 constexpr int kSectorCap = 512;          // >= points of one sector (a ring has <= 1800 -> <= 300 + margins)
 constexpr int kRingCap = 2048;           // >= less-flat points of one ring
 constexpr int kPickStride = 32;          // per sector: [0..1] sharp, [2..21] less sharp (incl. sharp), [22..25] flat, [26..28] counts
-
-struct FeScan {  // device view of one lins_segmented_scan + its outputs
-  long long off;     // first point in the point / range / col / ground arenas
-  int n;
-  int start_ring[kFeRows], end_ring[kFeRows];
-  float start_ori, end_ori, ori_diff;
-  int pad;
-  long long o_sharp, o_less_sharp, o_flat, o_less_flat;  // where the four feature clouds go (points from `out`)
-};
 
 struct FeLds {
   union {
@@ -928,13 +920,12 @@ __global__ __launch_bounds__(kFeBlock) void frontend_kernel(
 #endif
 }
 
-void launch_frontend(hipStream_t stream, int n_scans, const void* scans, const float4* cloud, const float* range,
+void launch_frontend(hipStream_t stream, int n_scans, const FeScan* scans, const float4* cloud, const float* range,
                      const unsigned* col, const unsigned char* ground, double scan_period, int* picks, float4* out,
                      int* out_counts) {
-  hipLaunchKernelGGL(frontend_kernel, dim3(n_scans), dim3(kFeBlock), 0, stream, (const FeScan*)scans, cloud, range, col,
+  hipLaunchKernelGGL(frontend_kernel, dim3(n_scans), dim3(kFeBlock), 0, stream, scans, cloud, range, col,
                      ground, scan_period, picks, out, out_counts);
 }
-size_t fe_scan_size() { return sizeof(FeScan); }
 int fe_pick_stride() { return kFeRows * 6 * kPickStride; }
 
 }  // namespace lins

@@ -6,6 +6,7 @@
 
 #include "ieskf_grid.h"
 #include "ieskf_rowsum.h"
+#include "lins_launch.h"
 
 #ifndef LINS_GRID_PF
 #define LINS_GRID_PF 8  // steps of the grid build whose point reads are in flight together, in the histogram pass (measured

@@ -30,13 +30,9 @@
 #include "ieskf_binned.h"
 #include "ieskf_device.h"
 #include "ieskf_joseph.h"
+#include "lins_launch.h"
 
 namespace lins {
-
-struct OutRec {
-  double residual_norm, update_norm;
-  int iters, converged, diverged, m_surf, m_corner, pad[3];
-};
 
 // row vector v = (c0 c1 c2 a0 a1 a2 r); sum k accumulates v[A[k]] * v[B[k]]:
 // [0..20] upper triangle of H^T H (row-major), [21..26] H^T r, [27] r^T r
@@ -498,21 +494,15 @@ __global__ __launch_bounds__(kBlock) void ieskf_pass_kernel(
 // ---------------------------------------------------------------------------
 void launch_persistent(hipStream_t stream, int n, const DevParams& prm, const ScanDesc* descs,
                        const float4* arena, const double* state_in, const double* cov_in, double* state_out,
-                       double* cov_out, double* a6, void* out, int4* idx_store, lins_pose_record* poses,
+                       double* cov_out, double* a6, OutRec* out, int4* idx_store, lins_pose_record* poses,
                        int scan_id_base, float4* binned, long long* prof) {
   if (prm.search == SEARCH_BINNED)
     hipLaunchKernelGGL(ieskf_persistent_kernel<SEARCH_BINNED>, dim3(n), dim3(kBlock), 0, stream, prm, descs, arena,
-                       state_in, cov_in, state_out, a6, (OutRec*)out, idx_store, poses, scan_id_base, binned, prof);
+                       state_in, cov_in, state_out, a6, out, idx_store, poses, scan_id_base, binned, prof);
   else
     hipLaunchKernelGGL(ieskf_persistent_kernel<SEARCH_BRUTE>, dim3(n), dim3(kBlock), 0, stream, prm, descs, arena,
-                       state_in, cov_in, state_out, a6, (OutRec*)out, idx_store, poses, scan_id_base, binned, prof);
-  hipLaunchKernelGGL(ieskf_joseph_kernel, dim3(n), dim3(kJosephBlock), 0, stream, prm, cov_in, a6, (const OutRec*)out,
-                     cov_out);
-}
-
-void launch_joseph(hipStream_t stream, int n, const DevParams& prm, const double* cov_in, const double* a6,
-                   const void* out, double* cov_out) {
-  hipLaunchKernelGGL(ieskf_joseph_kernel, dim3(n), dim3(kJosephBlock), 0, stream, prm, cov_in, a6, (const OutRec*)out,
+                       state_in, cov_in, state_out, a6, out, idx_store, poses, scan_id_base, binned, prof);
+  hipLaunchKernelGGL(ieskf_joseph_kernel, dim3(n), dim3(kJosephBlock), 0, stream, prm, cov_in, a6, out,
                      cov_out);
 }
 
@@ -532,13 +522,6 @@ void launch_pass(hipStream_t stream, int n, const DevParams& prm, const ScanDesc
 // One thread per point, blockIdx.y = cloud; pure streaming (16 B in, 16 or 32 B out per point)
 // with ~300 f64 flops of de-skew per point in between.
 // ---------------------------------------------------------------------------
-struct ReprojectJob {
-  long long off;  // first point of the cloud in the in / out arenas
-  int n, has_yzx;
-  double t[3], q[4];
-  double inv_period;
-};
-
 constexpr int kToEndPts = 8;
 __global__ __launch_bounds__(256) void transform_to_end_kernel(const ReprojectJob* __restrict__ jobs,
                                                                const float4* __restrict__ in,
@@ -567,22 +550,17 @@ __global__ __launch_bounds__(256) void transform_to_end_kernel(const ReprojectJo
   }
 }
 
-void launch_transform_to_end(hipStream_t stream, int n_jobs, int max_n, const void* jobs, const float4* in,
+void launch_transform_to_end(hipStream_t stream, int n_jobs, int max_n, const ReprojectJob* jobs, const float4* in,
                              float4* out_xyz, float4* out_yzx) {
   int gx = (max_n + 256 * kToEndPts - 1) / (256 * kToEndPts);
   if (gx < 1) gx = 1;
   if (gx > 64) gx = 64;
-  hipLaunchKernelGGL(transform_to_end_kernel, dim3(gx, n_jobs), dim3(256), 0, stream, (const ReprojectJob*)jobs, in,
+  hipLaunchKernelGGL(transform_to_end_kernel, dim3(gx, n_jobs), dim3(256), 0, stream, jobs, in,
                      out_xyz, out_yzx);
 }
-size_t reproject_job_size() { return sizeof(ReprojectJob); }
 
 // updatePointCloud's re-projection for device-resident streams (lins_streams_step): the pose is read
 // from the update's output states on the device, the clouds are rewritten in place (SE:1122-1131)
-struct StreamCloud {
-  long long off;  // first point in the stream arena
-  int n, stream;  // points, index of the state to use
-};
 __global__ __launch_bounds__(256) void reproject_in_place_kernel(const StreamCloud* __restrict__ jobs,
                                                                  const double* __restrict__ states, float4* __restrict__ arena,
                                                                  double inv_period) {
@@ -605,14 +583,13 @@ __global__ __launch_bounds__(256) void reproject_in_place_kernel(const StreamClo
     }
   }
 }
-void launch_reproject_in_place(hipStream_t stream, int n_jobs, int max_n, const void* jobs, const double* states,
+void launch_reproject_in_place(hipStream_t stream, int n_jobs, int max_n, const StreamCloud* jobs, const double* states,
                                float4* arena, double inv_period) {
   int gx = (max_n + 256 * kToEndPts - 1) / (256 * kToEndPts);
   gx = gx < 1 ? 1 : (gx > 64 ? 64 : gx);
-  hipLaunchKernelGGL(reproject_in_place_kernel, dim3(gx, n_jobs), dim3(256), 0, stream, (const StreamCloud*)jobs, states,
+  hipLaunchKernelGGL(reproject_in_place_kernel, dim3(gx, n_jobs), dim3(256), 0, stream, jobs, states,
                      arena, inv_period);
 }
-size_t stream_cloud_size() { return sizeof(StreamCloud); }
 
 // device-copy ceiling probe (lins_debug_stream_copy): what a pure streaming kernel reaches on this box
 __global__ __launch_bounds__(256) void stream_copy_kernel(const float4* __restrict__ in, float4* __restrict__ out, size_t n) {
@@ -621,7 +598,5 @@ __global__ __launch_bounds__(256) void stream_copy_kernel(const float4* __restri
 void launch_stream_copy(hipStream_t stream, const float4* in, float4* out, size_t n) {
   hipLaunchKernelGGL(stream_copy_kernel, dim3(256 * 16), dim3(256), 0, stream, in, out, n);
 }
-
-size_t out_rec_size() { return sizeof(OutRec); }
 
 }  // namespace lins

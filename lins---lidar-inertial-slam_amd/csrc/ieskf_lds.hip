@@ -42,12 +42,12 @@ int lds_np_cap() { return lds_full::kNpMax; }
 // (one workgroup per CU: nothing to order; the batch shape's several-part updates do not exist here)
 void launch_lds(hipStream_t stream, int n, const DevParams& prm, int lanes, const ScanDesc* descs,
                 const float4* arena, const float4* sorted, const GridTables* tabs, const double* state_in, const double* cov_in, double* state_out, double* a6,
-                double* cov_out, void* out, int4* idx_store, lins_pose_record* poses, int scan_id_base, long long* prof, int* carry) {
+                double* cov_out, OutRec* out, int4* idx_store, lins_pose_record* poses, int scan_id_base, long long* prof, int* carry) {
   lds_full::KernelArgs ka{};
   ka.relay_lane = carry;  // (the carry records of these n scans: the one-lane shape's per-query state, ieskf_lds_lean.h)
   ka.prm = prm, ka.descs = descs, ka.tabs = tabs;
   ka.state_in = state_in, ka.cov_in = cov_in, ka.state_out = state_out, ka.a6_out = a6, ka.cov_out = cov_out;
-  ka.out = (lds_full::OutRec*)out, ka.poses = poses, ka.scan_id_base = scan_id_base, ka.prof_buf = prof;
+  ka.out = out, ka.poses = poses, ka.scan_id_base = scan_id_base, ka.prof_buf = prof;
   if (lanes == 3) {
     if (prof)
       launch_args(lds_full::ieskf_lds_kernel<1024, 3, false, true>, n, 1024, stream, ka, arena, sorted, idx_store);

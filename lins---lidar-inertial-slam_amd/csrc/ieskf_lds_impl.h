@@ -63,6 +63,7 @@
 #include "icp_math.h"
 #include "icp_wave.h"
 #include "ieskf_rowsum.h"
+#include "lins_launch.h"
 
 #ifndef LINS_PERSIST
 #define LINS_PERSIST 0
@@ -86,11 +87,6 @@
 
 namespace lins {
 namespace LINS_LDS_NS {
-
-struct OutRec {
-  double residual_norm, update_norm;
-  int iters, converged, diverged, m_surf, m_corner, pad[3];
-};
 
 // The kernel's ONE parameter (by value: it lies at offset 0 of the kernarg segment).  Round 3 passed these as 28
 // separate arguments; the compiler loads every argument at the kernel's entry and keeps it in scalar registers to the
@@ -791,9 +787,7 @@ __device__ __forceinline__ WalkOut coop_walk(const LdsStore& L, const LCloud& c,
   return r;
 }
 // ---- the register-lean search core of the batch kernel (round 6): Top2, nn_lean, walk_lean, the carry records ----------
-constexpr int kRelayLanes = 512;                    // query slots of a scan's carry records
-constexpr int kRelayRegionInts = 4 * kRelayLanes * 4;  // ints per scan in KernelArgs::relay_lane: [4][512] 16-byte words, by QUERY slot
-constexpr int kRelayLaneInts = kRelayRegionInts;
+// (kRelayLanes, kRelayRegionInts, kRelayLaneInts — the size of a scan's carry records: lins_records.h, shared with the host)
 #ifdef LINS_LDS_LEAN
 #include "ieskf_lds_lean.h"
 constexpr bool kLeanBuild = true;

@@ -76,14 +76,14 @@ int lds_mr_resident_workgroups(int n_cu) {
 // per-scan flags are never reset: a flag of an earlier launch is smaller)
 void launch_lds_mr(hipStream_t stream, int n, const DevParams& prm, const ScanDesc* descs, const int* order, const float4* arena,
                    const float4* sorted, const GridTables* tabs, const double* state_in, const double* cov_in, double* state_out, double* a6,
-                   double* cov_out, void* out, int4* idx_store, lins_pose_record* poses, int scan_id_base, long long* prof,
+                   double* cov_out, OutRec* out, int4* idx_store, lins_pose_record* poses, int scan_id_base, long long* prof,
                    const RelayArgs* relay, unsigned* walk_cache, int run_gen, int* carry) {
   // (carry: the carry records of these n scans — 4 x 512 16-byte words each, ieskf_lds_lean.h; every launch needs them)
   lds_mr::KernelArgs ka{};
   ka.relay_lane = carry;
   ka.prm = prm, ka.descs = descs, ka.order = order, ka.tabs = tabs;
   ka.state_in = state_in, ka.cov_in = cov_in, ka.state_out = state_out, ka.a6_out = a6, ka.cov_out = cov_out;
-  ka.out = (lds_mr::OutRec*)out, ka.poses = poses, ka.scan_id_base = scan_id_base, ka.prof_buf = prof;
+  ka.out = out, ka.poses = poses, ka.scan_id_base = scan_id_base, ka.prof_buf = prof;
   int grid = n;
   ka.walk_cache = walk_cache, ka.run_gen = run_gen;
   if (relay) {
@@ -109,11 +109,11 @@ void launch_lds_mr(hipStream_t stream, int n, const DevParams& prm, const ScanDe
 // ICP / Gauss-Newton fallback (estimateTransform, SE:1163-1320) on the same grid and searches:
 // state_in = the pose to start from (the filter's), state_out = that state with rn_, qbn_ replaced
 void launch_lds_mr_icp(hipStream_t stream, int n, const DevParams& prm, const ScanDesc* descs, const float4* arena,
-                       const float4* sorted, const GridTables* tabs, const double* state_in, double* state_out, void* out, int4* idx_store) {
+                       const float4* sorted, const GridTables* tabs, const double* state_in, double* state_out, OutRec* out, int4* idx_store) {
   lds_mr::KernelArgs ka{};
   ka.prm = prm, ka.descs = descs, ka.tabs = tabs;
   ka.state_in = state_in, ka.cov_in = state_in /*unused: no covariance on this path*/, ka.state_out = state_out;
-  ka.out = (lds_mr::OutRec*)out;
+  ka.out = out;
   launch_args(lds_mr::ieskf_lds_kernel<LINS_MR_BLOCK, 1, false, false, true>, n, LINS_MR_BLOCK, stream, ka, arena, sorted, idx_store);
 }
 

@@ -1,0 +1,206 @@
+// lins_capi_debug.hip — every lins_debug_* entry point of the C ABI (include/lins_ieskf.h): test and measurement aids,
+// not part of the drop-in surface.
+#include "lins_ctx.h"
+#include "lm_math.h"
+
+using namespace lins;
+
+extern "C" {
+
+/* Debug aid (unit tests of the device math against the oracle; see debug_kernels.hip for the op codes):
+ * evaluates op on n items of n_in doubles each, n_out doubles out per item. */
+int lins_debug_math(lins_ctx* ctx, int op, int n, const double* in, int n_in, double* out, int n_out) {
+  if (ctx && in && out && op >= 100 && op <= 111 && n >= 1 && n_in >= 9 && n_out == 2) {  // cycle microbenchmarks, n blocks
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    double *d_in = nullptr, *d_out = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&d_in, 9 * 8));
+    HIP_TRY(ctx, hipMalloc((void**)&d_out, (size_t)n * 2 * 8));
+    HIP_TRY(ctx, hipMemcpy(d_in, in, 9 * 8, hipMemcpyHostToDevice));
+    launch_debug_cycles(ctx->stream, op, n, d_in, d_out);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(out, d_out, (size_t)n * 2 * 8, hipMemcpyDeviceToHost));
+    (void)hipFree(d_in), (void)hipFree(d_out);
+    return LINS_OK;
+  }
+  static const int kIn[20] = {4, 3, 3, 37, 38, 4, 24, 42, 42, 448, 448, 42, 42, 3, 4, 4, 43, 43, 72, 72};
+  static const int kOut[20] = {3, 4, 9, 19, 18, 12, 3, 6, 6, 28, 28, 6, 6, 4, 3, 12, 6, 6, 44, 44};
+  if (!ctx || !in || !out || op < 0 || op > 19 || n < 0 || n_in != kIn[op] || n_out != kOut[op]) return LINS_E_ARG;
+  if (n == 0) return LINS_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  double *d_in = nullptr, *d_out = nullptr;
+  LmCarry* d_lm = nullptr;
+  HIP_TRY(ctx, hipMalloc((void**)&d_in, (size_t)n * n_in * 8));
+  hipError_t e = hipMalloc((void**)&d_out, (size_t)n * n_out * 8);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, (size_t)n * n_in * 8, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    if (op == 9 || op == 10)
+      launch_debug_reduce_rows(ctx->stream, op, n, d_in, d_out);
+    else if (op == 8 || op == 12)
+      launch_debug_wave_solve(ctx->stream, n, op == 12, d_in, d_out);
+    else if (op == 16 || op == 17)
+      launch_debug_icp_gn(ctx->stream, n, op == 17, d_in, d_out);
+    else if (op == 18 || op == 19) {  // lm_step_from_sums: one thread (lm_math.h) / over a wave (lm_wave.h); 72 in, 44 out
+      e = hipMalloc(&d_lm, (size_t)n * sizeof(LmCarry));
+      if (e == hipSuccess) launch_debug_lm_step(ctx->stream, n, op == 19, d_in, d_out, d_lm);
+    }
+    else
+      launch_debug_math(ctx->stream, op, n, n_in, n_out, d_in, d_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * n_out * 8, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(d_in), (void)hipFree(d_out), (void)hipFree(d_lm);
+  if (e != hipSuccess) return ctx_fail_hip(ctx, e, "lins_debug_math");
+  return LINS_OK;
+}
+
+/* Debug aid (not part of the drop-in surface; tests/test_gpu_context_state.py): read (write = 0) or write (write = 1)
+ * `bytes` bytes at `offset_bytes` of the context's scratch state that outlives a run — which = 0: the carry records of
+ * the batch kernel (ieskf_lds_lean.h, kRelayLaneInts ints per scan), 1: the walk cache (32 B per query slot).
+ * Synchronous, ordered behind both launch queues and the gather stream. */
+int lins_debug_scratch(lins_ctx* ctx, int which, int write, size_t offset_bytes, size_t bytes, void* host) {
+  if (!ctx || !host || (which != 0 && which != 1)) return LINS_E_ARG;
+  char* const base = which == 0 ? reinterpret_cast<char*>(ctx->d_relay_lane) : reinterpret_cast<char*>(ctx->d_walk_cache);
+  const size_t cap = which == 0 ? (size_t)ctx->max_batch * kRelayLaneInts * sizeof(int) : ctx->slot_cap * 32;
+  if (!base || offset_bytes > cap || bytes > cap - offset_bytes) return LINS_E_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = pipe_join(ctx)) return rc;
+  if (write)
+    HIP_TRY(ctx, hipMemcpyAsync(base + offset_bytes, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+  else
+    HIP_TRY(ctx, hipMemcpyAsync(host, base + offset_bytes, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return LINS_OK;
+}
+
+
+/* Debug aid (not part of the drop-in surface): enable / read the per-workgroup phase
+ * profile of the persistent kernel: 16 int64 shader-clock ticks per scan
+ * ([0] setup [1] correspondence [2] reduction [3] solve [4] update [5] total [6..10] per wave). */
+int lins_debug_phase_profile(lins_ctx* ctx, int enable, long long* out, int n_scans) {
+  if (!ctx) return LINS_E_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rcs = split_join(ctx)) return rcs;
+  if (enable && !ctx->d_prof) {
+    // (16 words per scan, then — behind the records of the launch — 32 words per scan of per-wave phase ticks, written by
+    // libraries built with -DLINS_PROF2=k: lins_debug_wave_phases)
+    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_prof, (size_t)ctx->max_batch * 80 * sizeof(long long)));
+    HIP_TRY(ctx, hipMemset(ctx->d_prof, 0, (size_t)ctx->max_batch * 80 * sizeof(long long)));
+  }
+  if (out && ctx->d_prof) {
+    if (n_scans > ctx->max_batch) return LINS_E_CAPACITY;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(out, ctx->d_prof, (size_t)n_scans * 16 * sizeof(long long), hipMemcpyDeviceToHost));
+  }
+  if (!enable && ctx->d_prof) {
+    (void)hipFree(ctx->d_prof);
+    ctx->d_prof = nullptr;
+  }
+  return LINS_OK;
+}
+
+/* Debug aid (libraries built with -DLINS_QUEUE_TRACE=1, a several-part run): per workgroup of the last launch, in
+ * workgroup-index order, four words: start, item in hand, end (100 MHz wall clock) and the item (scan | part << 27, -1 =
+ * none: the later part of an update that had ended).                                                                  */
+int lins_debug_queue_trace(lins_ctx* ctx, long long* out, int n_wg) {
+  if (!ctx || !out || n_wg < 0) return LINS_E_ARG;
+  if (!ctx->d_queue || n_wg > 15 * ctx->max_batch) return LINS_E_STATE;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(out, ctx->d_queue + lds_mr_queue_flags_offset() + (size_t)ctx->max_batch, (size_t)n_wg * 32, hipMemcpyDeviceToHost));
+  return LINS_OK;
+}
+
+/* Debug aid (libraries built with -DLINS_PROF2=k, profile enabled, whole updates of the batch kernel): per scan 8 waves x
+ * 8 phases of 32-bit shader-clock ticks summed over the iterations >= k — [0] query load + de-skew [1] nearest
+ * neighbour: certificates + searches [2] second / third point [3] rows [4] row reduction [5] wait at the barrier behind
+ * it [6] fold + barrier [7] solve / update (the waves that do not solve wait here).  n_scans = the scans of the last run. */
+int lins_debug_wave_phases(lins_ctx* ctx, int* out, int n_scans) {
+  if (!ctx || !out) return LINS_E_ARG;
+  if (!ctx->d_prof || n_scans != ctx->n_uploaded) return LINS_E_STATE;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(out, ctx->d_prof + (size_t)n_scans * 16, (size_t)n_scans * 64 * sizeof(int), hipMemcpyDeviceToHost));
+  return LINS_OK;
+}
+
+/* Debug aid (LINS_PROF2 builds): per scan 8 waves x 8 counts over the iterations >= k — nearest-neighbour phase: max over
+ * the lanes of the window scans (scan_spans calls) and of the grid positions they cover, the sums of both over the lanes;
+ * then the same four for the walk phase. */
+int lins_debug_wave_counts(lins_ctx* ctx, int* out, int n_scans) {
+  if (!ctx || !out) return LINS_E_ARG;
+  if (!ctx->d_prof || n_scans != ctx->n_uploaded) return LINS_E_STATE;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(out, ctx->d_prof + (size_t)n_scans * 48, (size_t)n_scans * 64 * sizeof(int), hipMemcpyDeviceToHost));
+  return LINS_OK;
+}
+
+/* Debug aid (LINS_PROF2 builds): the per-query slots of the uploaded batch (int4 each), where the profiled batch kernel
+ * leaves (searches, walks, walk mask by iteration, ring) of every query. */
+int lins_debug_query_slots(lins_ctx* ctx, int* out, int n_slots) {
+  if (!ctx || !out || n_slots < 0 || (size_t)n_slots > ctx->slot_cap) return LINS_E_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  HIP_TRY(ctx, hipMemcpy(out, ctx->d_idx, (size_t)n_slots * sizeof(int4), hipMemcpyDeviceToHost));
+  return LINS_OK;
+}
+
+/* Measurement aid ("measure a device-copy ceiling with a stream kernel and report
+ * against both"): a grid-stride float4 copy of `bytes` bytes inside the context's point arenas,
+ * timed with HIP events on the context's stream; *gbs = (read + written bytes) / time of the best
+ * of `reps` launches.  An uploaded batch stays valid (only the scratch arena is written).       */
+int lins_debug_stream_copy(lins_ctx* ctx, uint64_t bytes, int reps, double* gbs) {
+  if (!ctx || !gbs || reps < 1) return LINS_E_ARG;
+  const size_t cap = ctx->arena_cap * sizeof(float4);
+  if (bytes > cap) bytes = cap;
+  const size_t n4 = bytes / sizeof(float4);
+  if (!n4) return LINS_E_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  float best = 1e30f;  // (source = the cloud arena, untouched; destination = the sorted-copy arena, scratch)
+  for (int r = 0; r < reps + 1; ++r) {  // (first launch: warm-up)
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    launch_stream_copy(ctx->stream, ctx->d_arena, ctx->d_binned, n4);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev2));
+    float ms = 0;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev2));
+    if (r && ms < best) best = ms;
+  }
+  *gbs = 2.0 * (double)(n4 * sizeof(float4)) / ((double)best * 1e-3) / 1e9;
+  return LINS_OK;
+}
+
+/* measurement aid (tools/pull_copy_rate.py): `bytes` of the pinned staging arena to the device arena — mode 0: hipMemcpyAsync
+ * (what the uploads do), mode 1: a copy KERNEL reading the host memory over PCIe (launch_stream_copy on the mapped pointer) —
+ * best of `reps`, GB/s one way. */
+int lins_debug_pull_copy(lins_ctx* ctx, uint64_t bytes, int reps, int mode, double* gbs) {
+  if (!ctx || !gbs || reps < 1) return LINS_E_ARG;
+  const size_t cap = ctx->arena_cap * sizeof(float4);
+  if (bytes > cap) bytes = cap;
+  const size_t n4 = bytes / sizeof(float4);
+  if (!n4) return LINS_E_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = pipe_join(ctx)) return rc;
+  float4* mapped = nullptr;
+  HIP_TRY(ctx, hipHostGetDevicePointer((void**)&mapped, ctx->h_arena, 0));
+  float best = 1e30f;
+  for (int r = 0; r < reps + 1; ++r) {
+    HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+    if (mode == 0)
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->d_binned, ctx->h_arena, n4 * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
+    else
+      launch_stream_copy(ctx->stream, mapped, ctx->d_binned, n4);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
+    HIP_TRY(ctx, hipEventSynchronize(ctx->ev2));
+    float ms = 0;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev2));
+    if (r && ms < best) best = ms;
+  }
+  *gbs = (double)(n4 * sizeof(float4)) / ((double)best * 1e-3) / 1e9;
+  return LINS_OK;
+}
+
+}  // extern "C"

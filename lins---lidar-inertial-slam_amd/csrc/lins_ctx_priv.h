@@ -1,6 +1,6 @@
-// lins_ctx_priv.h — what other translation units of liblins_ieskf.so may use of a lins_ctx (the struct itself
-// is private to lins_capi.hip): its stream / device, the error-string slot, and one attachment slot for the
-// state of the scan-to-map row (freed by lins_destroy through the registered function).
+// lins_ctx_priv.h — what the scan-to-map files of liblins_ieskf.so may use of a lins_ctx (the struct itself is
+// lins_ctx.h, shared by the lins_capi*.hip files only): its stream / device, the error-string slot, and one attachment
+// slot for the state of the scan-to-map row (freed by lins_destroy through the registered function).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,3 +15,10 @@ void** ctx_map_slot(lins_ctx* ctx, void (*free_fn)(void*));       // attachment 
 void ctx_events(lins_ctx* ctx, hipEvent_t* a, hipEvent_t* b);
 const lins_params* ctx_params(const lins_ctx* ctx);  // the parameters the context was created with
 }  // namespace lins
+
+// every HIP call of the C API files: on failure the message goes to the context and the function returns LINS_E_HIP
+#define HIP_TRY(ctx, expr)                          \
+  do {                                              \
+    hipError_t e__ = (expr);                        \
+    if (e__ != hipSuccess) return ctx_fail_hip(ctx, e__, #expr); \
+  } while (0)

@@ -1,0 +1,89 @@
+// lins_launch.h — every host-callable launcher and capacity query of the kernel files, declared ONCE with parameter
+// names.  The kernel file that defines a launcher includes this header (a changed signature is a compile error there),
+// and so does every C API file that calls one.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/lins_ieskf.h"
+#include "../../include/lins_map.h"
+#include "lins_records.h"
+
+namespace lins {
+
+struct DevParams;   // ieskf_device.h
+struct ScanDesc;
+struct RelayArgs;
+struct GridTables;  // ieskf_grid.h
+struct LmCarry;     // lm_math.h
+struct MapRoundParams;
+struct LmSeg;       // local_map.h
+struct LmJob;
+struct LmState;
+
+// ---- ieskf_kernels.hip: the any-size update kernel (global-memory grid or exhaustive search), re-projection, copy probe
+void launch_persistent(hipStream_t stream, int n, const DevParams& prm, const ScanDesc* descs, const float4* arena, const double* state_in, const double* cov_in, double* state_out, double* cov_out,
+                       double* a6, OutRec* out, int4* idx_store, lins_pose_record* poses, int scan_id_base, float4* binned, long long* prof);
+void launch_pass(hipStream_t stream, int n, const DevParams& prm, const ScanDesc* descs, const float4* arena, const double* lin_state, const double* filt_state, int iter, int4* idx_store,
+                 lins_corr* dump, double* sums_out, int* counts_out, float4* binned);
+void launch_transform_to_end(hipStream_t stream, int n_jobs, int max_n, const ReprojectJob* jobs, const float4* in, float4* out_xyz, float4* out_yzx);
+void launch_reproject_in_place(hipStream_t stream, int n_jobs, int max_n, const StreamCloud* jobs, const double* states, float4* arena, double inv_period);
+void launch_stream_copy(hipStream_t stream, const float4* in, float4* out, size_t n);
+
+// ---- ieskf_grid.hip: the search index of scans [0, n) of `descs` — sorted copy into gsorted (same offsets as the targets
+// in the arena: positions 0 .. n_all - 1 at off_surf_t), tables into tab[scan]
+void launch_grid_index(hipStream_t stream, int n, const ScanDesc* descs, const float4* arena, float4* gsorted, GridTables* tab);
+// updatePointCloud in one kernel: the clouds `descs` name as targets are re-projected in place with states[scan] (19
+// doubles each: t at 0, q at 6) and indexed as re-projected (grid_index_kernel<true>)
+void launch_reproject_and_index(hipStream_t stream, int n, const ScanDesc* descs, float4* arena, float4* gsorted, GridTables* tab, const double* states, double inv_period);
+
+// ---- ieskf_lds.hip: the full-residency LDS kernel (lanes = 3: 1024 threads, lanes = 1: 384 threads)
+int lds_np_cap();  // target points of a scan the kernel takes
+void launch_lds(hipStream_t stream, int n, const DevParams& prm, int lanes, const ScanDesc* descs, const float4* arena, const float4* sorted, const GridTables* tabs, const double* state_in,
+                const double* cov_in, double* state_out, double* a6, double* cov_out, OutRec* out, int4* idx_store, lins_pose_record* poses, int scan_id_base, long long* prof, int* carry);
+void launch_lds_pass(hipStream_t stream, int n, const DevParams& prm, int lanes, const ScanDesc* descs, const float4* arena, const float4* sorted, const GridTables* tabs, const double* lin_state,
+                     const double* filt_state, int iter, int4* idx_store, lins_corr* dump, double* sums_out, int* counts_out);
+
+// ---- ieskf_lds_mr.hip: the multi-resident (batch) LDS kernel
+int lds_mr_np_cap();
+bool lds_mr_has_parts();                   // the build has the several-part updates
+int lds_mr_queue_flags_offset();           // ints of ticket counters in front of the per-scan flags of RelayArgs::queue
+int lds_mr_resident_workgroups(int n_cu);  // workgroups resident at once on the current device
+void launch_lds_mr(hipStream_t stream, int n, const DevParams& prm, const ScanDesc* descs, const int* order, const float4* arena, const float4* sorted, const GridTables* tabs, const double* state_in,
+                   const double* cov_in, double* state_out, double* a6, double* cov_out, OutRec* out, int4* idx_store, lins_pose_record* poses, int scan_id_base, long long* prof,
+                   const RelayArgs* relay, unsigned* walk_cache, int run_gen, int* carry);
+void launch_lds_mr_icp(hipStream_t stream, int n, const DevParams& prm, const ScanDesc* descs, const float4* arena, const float4* sorted, const GridTables* tabs, const double* state_in,
+                       double* state_out, OutRec* out, int4* idx_store);
+void launch_lds_mr_pass(hipStream_t stream, int n, const DevParams& prm, const ScanDesc* descs, const float4* arena, const float4* sorted, const GridTables* tabs, const double* lin_state,
+                        const double* filt_state, int iter, int4* idx_store, lins_corr* dump, double* sums_out, int* counts_out);
+
+// ---- frontend_kernels.hip / segment_kernels.hip
+int fe_pick_stride();  // ints of pick scratch per scan
+void launch_frontend(hipStream_t stream, int n_scans, const FeScan* scans, const float4* cloud, const float* range, const unsigned* col, const unsigned char* ground, double scan_period, int* picks,
+                     float4* out, int* out_counts);
+void launch_segment(hipStream_t stream, int n_scans, const SgRaw* raws, const float4* raw, float sin_ax, float cos_ax, float sin_ay, float cos_ay, float theta, unsigned* cellidx, int* seg_rows,
+                    FeScan* fe_scans, float4* out_cloud, float* out_range, unsigned* out_col, unsigned char* out_ground, int* out_outliers);
+
+// ---- debug_kernels.hip (lins_debug_math; op codes there)
+void launch_debug_math(hipStream_t stream, int op, int n, int n_in, int n_out, const double* in, double* out);
+void launch_debug_cycles(hipStream_t stream, int op, int blocks, const double* in, double* out);
+void launch_debug_wave_solve(hipStream_t stream, int n, int gj, const double* in, double* out);
+void launch_debug_icp_gn(hipStream_t stream, int n, int wave_version, const double* in, double* out);
+void launch_debug_reduce_rows(hipStream_t stream, int op, int n, const double* in, double* out);
+
+// ---- map_kernels.hip: scan-to-map
+int map_block();  // queries per block of map_corr_kernel
+void launch_map_selfcheck(hipStream_t stream, float* out);
+void launch_map_grid(hipStream_t stream, int n_jobs, const MapGridJob* jobs, const float4* raw, float4* pts, int* cells);
+void launch_map_corr(hipStream_t stream, int n_problems, int blocks_per_problem, const MapDev* probs, const MapRoundParams* rounds, const float4* pts, const int* cells, const float4* queries,
+                     lins_map_corr* recs, double* partials);
+void launch_map_lm(hipStream_t stream, int n, int iter, int blocks_per_problem, MapDev* probs, MapRoundParams* rounds, const double* partials, lins_map_result* results, LmCarry* carry);
+void launch_debug_lm_step(hipStream_t stream, int n, int wave_version, const double* in, double* out, LmCarry* scratch);
+
+// ---- local_map_kernels.hip: the mapping node's local map
+void launch_lm_transform(hipStream_t s, int n_blocks, const LmSeg* segs, const int2* blocks, const float4* frames, float4* stage, LmState* states);
+// one stage: jobs [j0, j0 + n_jobs), tiles [0, n_tiles) of `tiles`
+void launch_lm_stage(hipStream_t s, int j0, int n_jobs, int n_tiles, const int2* tiles, const LmJob* jobs, LmState* states, float4* stage, unsigned* keys_a, unsigned* keys_b, int* vals_a, int* vals_b,
+                     int* hist, int* tilecnt, int* starts, float4* out);
+
+}  // namespace lins

@@ -12,13 +12,9 @@
 
 #include "../../include/lins_map.h"
 #include "lins_ctx_priv.h"
+#include "lins_launch.h"
 #include "local_map.h"
 
-namespace lins {
-void launch_lm_transform(hipStream_t, int, const void*, const int2*, const float4*, float4*, void*);
-void launch_lm_stage(hipStream_t, int, int, int, const int2*, const void*, void*, float4*, unsigned*, unsigned*, int*, int*,
-                     int*, int*, int*, float4*);
-}  // namespace lins
 using namespace lins;
 
 namespace {
@@ -65,19 +61,13 @@ LocalMap* local_of(lins_ctx* ctx) {
   return (LocalMap*)*slot;
 }
 
-#define LM_TRY(ctx, expr)                                        \
-  do {                                                           \
-    hipError_t e__ = (expr);                                     \
-    if (e__ != hipSuccess) return ctx_fail_hip(ctx, e__, #expr); \
-  } while (0)
-
 template <class T>
 int grow(lins_ctx* ctx, T** p, size_t* cap, size_t need) {
   need = std::max<size_t>(need, 1);
   if (*cap >= need) return LINS_OK;
   (void)hipFree(*p);
   *p = nullptr, *cap = 0;
-  LM_TRY(ctx, hipMalloc((void**)p, need * sizeof(T)));
+  HIP_TRY(ctx, hipMalloc((void**)p, need * sizeof(T)));
   *cap = need;
   return LINS_OK;
 }
@@ -87,7 +77,7 @@ int grow_pinned(lins_ctx* ctx, T** p, size_t* cap, size_t need) {
   if (*cap >= need) return LINS_OK;
   (void)hipHostFree(*p);
   *p = nullptr, *cap = 0;
-  LM_TRY(ctx, hipHostMalloc((void**)p, need * sizeof(T)));
+  HIP_TRY(ctx, hipHostMalloc((void**)p, need * sizeof(T)));
   *cap = need;
   return LINS_OK;
 }
@@ -142,12 +132,12 @@ extern "C" {
 
 int lins_local_map_init(lins_ctx* ctx, int n_slots, int window, int max_points_per_frame) {
   if (!ctx || n_slots < 1 || window < 1 || window > 4096 || max_points_per_frame < 1) return LINS_E_ARG;
-  LM_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
   LocalMap* m = local_of(ctx);
-  LM_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));  // (a push_scans copy may still read the old rings)
+  HIP_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));  // (a push_scans copy may still read the old rings)
   (void)hipFree(m->d_frames);
   m->d_frames = nullptr, m->n_slots = 0, m->built = false;
-  LM_TRY(ctx, hipMalloc((void**)&m->d_frames, (size_t)n_slots * window * max_points_per_frame * sizeof(float4)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_frames, (size_t)n_slots * window * max_points_per_frame * sizeof(float4)));
   m->n_slots = n_slots, m->window = window, m->max_pts = max_points_per_frame;
   m->meta.assign((size_t)n_slots * window, KeyFrame{});
   m->head.assign(n_slots, 0), m->count.assign(n_slots, 0);
@@ -165,18 +155,18 @@ int lins_local_map_push(lins_ctx* ctx, int slot, const lins_keyframe* f) {
     if (int rc = cloud_check(c[k], n[k])) return rc;
   if (!pose_ok(f->pose)) return LINS_E_INPUT;
   if ((long long)n[0] + n[1] + n[2] > m->max_pts) return LINS_E_CAPACITY;
-  LM_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
   hipStream_t st = ctx_stream(ctx);
   const int idx = ring_push(m, slot);
   KeyFrame& kf = m->meta[(size_t)slot * m->window + idx];
   float4* dst = frame_ptr(m, slot, idx);
   for (int k = 0; k < 3; ++k) {
     kf.n[k] = n[k];
-    if (n[k]) LM_TRY(ctx, hipMemcpyAsync(dst, c[k], (size_t)n[k] * sizeof(float4), hipMemcpyHostToDevice, st));
+    if (n[k]) HIP_TRY(ctx, hipMemcpyAsync(dst, c[k], (size_t)n[k] * sizeof(float4), hipMemcpyHostToDevice, st));
     dst += n[k];
   }
   set_pose(kf, f->pose);
-  LM_TRY(ctx, hipStreamSynchronize(st));  // (the caller's clouds may go once this returns)
+  HIP_TRY(ctx, hipStreamSynchronize(st));  // (the caller's clouds may go once this returns)
   return LINS_OK;
 }
 
@@ -191,7 +181,7 @@ int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_
         (s.n_outlier && !s.outlier))
       return LINS_E_ARG;
   }
-  LM_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
   m->built = false;
   const int NJ = 6 * n;  // jobs: stage A 5 per entry (5k + cloud), stage B one per entry (5n + k)
   std::vector<LmJob> jobs(NJ);
@@ -332,22 +322,22 @@ int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_
   hipStream_t st = ctx_stream(ctx);
   hipEvent_t e0, e1;
   ctx_events(ctx, &e0, &e1);
-  if (raw_total) LM_TRY(ctx, hipMemcpyAsync(m->d_stage, m->h_raw, raw_total * sizeof(float4), hipMemcpyHostToDevice, st));
-  if (tab_bytes) LM_TRY(ctx, hipMemcpyAsync(m->d_tab, m->h_tab, tab_bytes, hipMemcpyHostToDevice, st));
-  LM_TRY(ctx, hipEventRecord(e0, st));
-  void* d_jobs = m->d_tab + o_jobs;
-  void* d_states = m->d_tab + o_states;
+  if (raw_total) HIP_TRY(ctx, hipMemcpyAsync(m->d_stage, m->h_raw, raw_total * sizeof(float4), hipMemcpyHostToDevice, st));
+  if (tab_bytes) HIP_TRY(ctx, hipMemcpyAsync(m->d_tab, m->h_tab, tab_bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipEventRecord(e0, st));
+  const LmJob* d_jobs = (const LmJob*)(m->d_tab + o_jobs);
+  LmState* d_states = (LmState*)(m->d_tab + o_states);
   const int2* d_tiles = (const int2*)(m->d_tab + o_tiles);
-  launch_lm_transform(st, (int)blocks.size(), m->d_tab + o_segs, (const int2*)(m->d_tab + o_blocks), m->d_frames, m->d_stage, d_states);
+  launch_lm_transform(st, (int)blocks.size(), (const LmSeg*)(m->d_tab + o_segs), (const int2*)(m->d_tab + o_blocks), m->d_frames, m->d_stage, d_states);
   launch_lm_stage(st, 0, 5 * n, tiles_a, d_tiles, d_jobs, d_states, m->d_stage, m->d_ka, m->d_kb, m->d_va, m->d_vb, m->d_hist,
                   m->d_tilecnt, m->d_starts, m->d_out);
   launch_lm_stage(st, 5 * n, n, tiles_b, d_tiles + tiles_a, d_jobs, d_states, m->d_stage, m->d_ka, m->d_kb, m->d_va, m->d_vb,
                   m->d_hist, m->d_tilecnt, m->d_starts, m->d_out);
-  LM_TRY(ctx, hipGetLastError());
-  LM_TRY(ctx, hipEventRecord(e1, st));
-  if (NJ) LM_TRY(ctx, hipMemcpyAsync(m->h_states, d_states, NJ * sizeof(LmState), hipMemcpyDeviceToHost, st));
-  LM_TRY(ctx, hipStreamSynchronize(st));
-  LM_TRY(ctx, hipEventElapsedTime(&m->ms, e0, e1));
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(e1, st));
+  if (NJ) HIP_TRY(ctx, hipMemcpyAsync(m->h_states, d_states, NJ * sizeof(LmState), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  HIP_TRY(ctx, hipEventElapsedTime(&m->ms, e0, e1));
   m->points_in = pts_in;
   const LmState* S = (const LmState*)m->h_states;
   m->slots.assign(slots, slots + n);
@@ -389,7 +379,7 @@ int lins_local_map_push_scans(lins_ctx* ctx, int n, const int32_t* entries, cons
     if ((long long)z.n[LINS_LOCAL_SCAN_CORNER] + z.n[LINS_LOCAL_SCAN_SURF] + z.n[LINS_LOCAL_SCAN_OUTLIER] > m->max_pts)
       return LINS_E_CAPACITY;
   }
-  LM_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
   hipStream_t st = ctx_stream(ctx);
   for (int i = 0; i < n; ++i) {  // saveKeyFramesAndFactor (LM:1758-1763): cornerDS, surfDS, outlierDS
     const int e = entries[i], s = m->slots[e];
@@ -399,7 +389,7 @@ int lins_local_map_push_scans(lins_ctx* ctx, int n, const int32_t* entries, cons
     for (int q = 0; q < 3; ++q) {
       const int c = LINS_LOCAL_SCAN_CORNER + q, cnt = m->sizes[e].n[c];
       kf.n[q] = cnt;
-      if (cnt) LM_TRY(ctx, hipMemcpyAsync(dst, m->d_out + m->off[6 * e + c], (size_t)cnt * sizeof(float4), hipMemcpyDeviceToDevice, st));
+      if (cnt) HIP_TRY(ctx, hipMemcpyAsync(dst, m->d_out + m->off[6 * e + c], (size_t)cnt * sizeof(float4), hipMemcpyDeviceToDevice, st));
       dst += cnt;
     }
     set_pose(kf, poses[i]);
@@ -427,10 +417,10 @@ int lins_local_map_download(lins_ctx* ctx, int entry, int which, lins_point* out
   if (cnt > cap) return LINS_E_CAPACITY;
   if (cnt && !out) return LINS_E_ARG;
   if (!cnt) return 0;
-  LM_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
   hipStream_t st = ctx_stream(ctx);
-  LM_TRY(ctx, hipMemcpyAsync(out, m->d_out + m->off[6 * entry + which], (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost, st));
-  LM_TRY(ctx, hipStreamSynchronize(st));
+  HIP_TRY(ctx, hipMemcpyAsync(out, m->d_out + m->off[6 * entry + which], (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
   return cnt;
 }
 

@@ -15,41 +15,14 @@
 
 #include "../../include/lins_map.h"
 #include "lins_ctx_priv.h"
+#include "lins_launch.h"
 #include "local_map.h"
 #include "lm_math.h"
 #include "map_math.h"
 
-namespace lins {
-void launch_map_selfcheck(hipStream_t, float*);
-void launch_map_corr(hipStream_t, int, int, const void*, const void*, const float4*, const int*, const float4*,
-                     lins_map_corr*, double*);
-void launch_map_grid(hipStream_t, int, const void*, const float4*, float4*, int*);
-void launch_map_lm(hipStream_t, int, int, int, void*, void*, const double*, lins_map_result*, void*);
-size_t map_dev_size();
-size_t map_round_size();
-size_t map_grid_job_size();
-size_t map_carry_size();
-int map_block();
-}  // namespace lins
 using namespace lins;
 
 namespace {
-
-struct MapGridHost {
-  long long off_pts, off_cells;
-  int cmin[3], cdim[3];
-};
-struct MapDevHost {
-  MapGridHost g[2];
-  long long off_q, off_rec;
-  int n_q[2];
-  int active, pad;
-};
-struct MapGridJobHost {  // (map_kernels.hip's MapGridJob)
-  long long off_raw, off_pts, off_cells;
-  int n, ncell;
-  int cmin[3], cdim[3];
-};
 
 struct MapState {
   float4 *d_raw = nullptr, *d_pts = nullptr, *d_q = nullptr;
@@ -58,13 +31,16 @@ struct MapState {
   int* d_cells = nullptr;
   lins_map_corr* d_rec = nullptr;
   double* d_partials = nullptr;
-  void *d_probs = nullptr, *d_rounds = nullptr, *d_jobs = nullptr, *d_carry = nullptr;
+  MapDev* d_probs = nullptr;
+  MapRoundParams* d_rounds = nullptr;
+  MapGridJob* d_jobs = nullptr;
+  LmCarry* d_carry = nullptr;
   lins_map_result* d_results = nullptr;
   size_t cap_raw = 0, cap_pts = 0, cap_q = 0, cap_cells = 0, cap_partials = 0;
   int cap_probs = 0;
   // the maps resident on the device (gridded): sizes per problem of the last upload, for LINS_MAP_REUSE
   std::vector<int> resident_sizes;
-  std::vector<MapDevHost> resident_dev;
+  std::vector<MapDev> resident_dev;
   float ms = 0.f;
   uint64_t queries = 0;
   bool selfcheck_done = false;
@@ -83,18 +59,12 @@ void map_state_free(void* p) {
   delete m;
 }
 
-#define MAP_TRY(ctx, expr)                                  \
-  do {                                                      \
-    hipError_t e__ = (expr);                                \
-    if (e__ != hipSuccess) return ctx_fail_hip(ctx, e__, #expr); \
-  } while (0)
-
 template <class T>
 int grow(lins_ctx* ctx, T** p, size_t* cap, size_t need) {
   if (*cap >= need) return LINS_OK;
   (void)hipFree(*p);
   *p = nullptr, *cap = 0;
-  MAP_TRY(ctx, hipMalloc((void**)p, need * sizeof(T)));
+  HIP_TRY(ctx, hipMalloc((void**)p, need * sizeof(T)));
   *cap = need;
   return LINS_OK;
 }
@@ -134,7 +104,7 @@ int cloud_box(const lins_point* p, int n, int* cmin, int* cdim, long long* ncell
 // Brings n problems onto the device: queries always; the maps (raw upload + device gridding) unless every problem
 // carries LINS_MAP_REUSE and the resident maps have the same sizes — the local map of the mapping node only changes
 // with its key frames.  Fills the device descriptors; active[k] = precondition of LM:1636.
-int map_upload(lins_ctx* ctx, MapState* m, int n, const lins_map_problem* in, std::vector<MapDevHost>& dev, int* max_q) {
+int map_upload(lins_ctx* ctx, MapState* m, int n, const lins_map_problem* in, std::vector<MapDev>& dev, int* max_q) {
   bool reuse = (int)m->resident_dev.size() == n && n > 0;
   for (int k = 0; k < n; ++k) {
     const lins_map_problem& p = in[k];
@@ -150,10 +120,10 @@ int map_upload(lins_ctx* ctx, MapState* m, int n, const lins_map_problem* in, st
   int rc;
   if (!reuse) {
     m->resident_dev.clear(), m->resident_sizes.clear();
-    std::vector<MapGridJobHost> jobs((size_t)n * 2);
+    std::vector<MapGridJob> jobs((size_t)n * 2);
     rc = parallel_for(2 * n, [&](int j) {
       const lins_map_problem& p = in[j / 2];
-      MapGridJobHost& jb = jobs[j];
+      MapGridJob& jb = jobs[j];
       jb.n = (j & 1) ? p.n_map_surf : p.n_map_corner;
       long long ncell = 1;
       const int r = cloud_box((j & 1) ? p.map_surf : p.map_corner, jb.n, jb.cmin, jb.cdim, &ncell);
@@ -162,10 +132,10 @@ int map_upload(lins_ctx* ctx, MapState* m, int n, const lins_map_problem* in, st
     });
     if (rc) return rc;
     size_t tot_pts = 0, tot_cells = 0;
-    dev.assign(n, MapDevHost{});
+    dev.assign(n, MapDev{});
     for (int k = 0; k < n; ++k)
       for (int w = 0; w < 2; ++w) {
-        MapGridJobHost& jb = jobs[(size_t)k * 2 + w];
+        MapGridJob& jb = jobs[(size_t)k * 2 + w];
         jb.off_raw = jb.off_pts = (long long)tot_pts, jb.off_cells = (long long)tot_cells;
         dev[k].g[w].off_pts = jb.off_pts, dev[k].g[w].off_cells = jb.off_cells;
         for (int a = 0; a < 3; ++a) dev[k].g[w].cmin[a] = jb.cmin[a], dev[k].g[w].cdim[a] = jb.cdim[a];
@@ -176,24 +146,24 @@ int map_upload(lins_ctx* ctx, MapState* m, int n, const lins_map_problem* in, st
     if ((rc = grow(ctx, &m->d_cells, &m->cap_cells, std::max<size_t>(tot_cells, 1)))) return rc;
     if (m->cap_probs < n) {
       (void)hipFree(m->d_probs), (void)hipFree(m->d_rounds), (void)hipFree(m->d_jobs), (void)hipFree(m->d_carry), (void)hipFree(m->d_results);
-      m->d_probs = m->d_rounds = m->d_jobs = m->d_carry = nullptr, m->d_results = nullptr, m->cap_probs = 0;
-      MAP_TRY(ctx, hipMalloc(&m->d_probs, (size_t)n * sizeof(MapDevHost)));
-      MAP_TRY(ctx, hipMalloc(&m->d_rounds, (size_t)n * map_round_size()));
-      MAP_TRY(ctx, hipMalloc(&m->d_jobs, (size_t)n * 2 * sizeof(MapGridJobHost)));
-      MAP_TRY(ctx, hipMalloc(&m->d_carry, (size_t)n * map_carry_size()));
-      MAP_TRY(ctx, hipMalloc((void**)&m->d_results, (size_t)n * sizeof(lins_map_result)));
+      m->d_probs = nullptr, m->d_rounds = nullptr, m->d_jobs = nullptr, m->d_carry = nullptr, m->d_results = nullptr, m->cap_probs = 0;
+      HIP_TRY(ctx, hipMalloc(&m->d_probs, (size_t)n * sizeof(MapDev)));
+      HIP_TRY(ctx, hipMalloc(&m->d_rounds, (size_t)n * sizeof(MapRoundParams)));
+      HIP_TRY(ctx, hipMalloc(&m->d_jobs, (size_t)n * 2 * sizeof(MapGridJob)));
+      HIP_TRY(ctx, hipMalloc(&m->d_carry, (size_t)n * sizeof(LmCarry)));
+      HIP_TRY(ctx, hipMalloc((void**)&m->d_results, (size_t)n * sizeof(lins_map_result)));
       m->cap_probs = n;
     }
     for (int k = 0; k < n; ++k) {
       if (in[k].n_map_corner)
-        MAP_TRY(ctx, hipMemcpyAsync(m->d_raw + jobs[(size_t)k * 2].off_raw, in[k].map_corner, (size_t)in[k].n_map_corner * sizeof(float4), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(m->d_raw + jobs[(size_t)k * 2].off_raw, in[k].map_corner, (size_t)in[k].n_map_corner * sizeof(float4), hipMemcpyHostToDevice, st));
       if (in[k].n_map_surf)
-        MAP_TRY(ctx, hipMemcpyAsync(m->d_raw + jobs[(size_t)k * 2 + 1].off_raw, in[k].map_surf, (size_t)in[k].n_map_surf * sizeof(float4), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(m->d_raw + jobs[(size_t)k * 2 + 1].off_raw, in[k].map_surf, (size_t)in[k].n_map_surf * sizeof(float4), hipMemcpyHostToDevice, st));
     }
-    MAP_TRY(ctx, hipMemcpyAsync(m->d_jobs, jobs.data(), jobs.size() * sizeof(MapGridJobHost), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(m->d_jobs, jobs.data(), jobs.size() * sizeof(MapGridJob), hipMemcpyHostToDevice, st));
     launch_map_grid(st, 2 * n, m->d_jobs, m->d_raw, m->d_pts, m->d_cells);
-    MAP_TRY(ctx, hipGetLastError());
-    MAP_TRY(ctx, hipStreamSynchronize(st));  // (jobs goes out of scope)
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st));  // (jobs goes out of scope)
     for (int k = 0; k < n; ++k) m->resident_sizes.push_back(in[k].n_map_corner), m->resident_sizes.push_back(in[k].n_map_surf);
   } else {
     dev = m->resident_dev;
@@ -210,7 +180,7 @@ int map_upload(lins_ctx* ctx, MapState* m, int n, const lins_map_problem* in, st
   if (m->cap_hq < std::max<size_t>(tot_q, 1)) {
     (void)hipHostFree(m->h_q);
     m->h_q = nullptr, m->cap_hq = 0;
-    MAP_TRY(ctx, hipHostMalloc((void**)&m->h_q, std::max<size_t>(tot_q, 1) * sizeof(float4)));
+    HIP_TRY(ctx, hipHostMalloc((void**)&m->h_q, std::max<size_t>(tot_q, 1) * sizeof(float4)));
     m->cap_hq = std::max<size_t>(tot_q, 1);
   }
   rc = parallel_for(n, [&](int k) {  // input contract + packing into the pinned staging buffer
@@ -226,11 +196,11 @@ int map_upload(lins_ctx* ctx, MapState* m, int n, const lins_map_problem* in, st
   if (m->cap_q < std::max<size_t>(tot_q, 1)) {
     (void)hipFree(m->d_q), (void)hipFree(m->d_rec);
     m->d_q = nullptr, m->d_rec = nullptr, m->cap_q = 0;
-    MAP_TRY(ctx, hipMalloc((void**)&m->d_q, std::max<size_t>(tot_q, 1) * sizeof(float4)));
-    MAP_TRY(ctx, hipMalloc((void**)&m->d_rec, std::max<size_t>(tot_q, 1) * sizeof(lins_map_corr)));
+    HIP_TRY(ctx, hipMalloc((void**)&m->d_q, std::max<size_t>(tot_q, 1) * sizeof(float4)));
+    HIP_TRY(ctx, hipMalloc((void**)&m->d_rec, std::max<size_t>(tot_q, 1) * sizeof(lins_map_corr)));
     m->cap_q = std::max<size_t>(tot_q, 1);
   }
-  if (tot_q) MAP_TRY(ctx, hipMemcpyAsync(m->d_q, m->h_q, tot_q * sizeof(float4), hipMemcpyHostToDevice, st));
+  if (tot_q) HIP_TRY(ctx, hipMemcpyAsync(m->d_q, m->h_q, tot_q * sizeof(float4), hipMemcpyHostToDevice, st));
   m->resident_dev = dev;
   return LINS_OK;
 }
@@ -238,16 +208,16 @@ int map_upload(lins_ctx* ctx, MapState* m, int n, const lins_map_problem* in, st
 // LINS_MAP_LOCAL: the maps and queries are the clouds of the last local-map build, read where they lie — the maps are
 // gridded from the build's cloud arena (its 1 m boxes came back with the build), the queries are its cornerDS with
 // surfTotalDS right behind (lins_local_map_capi.hip lays them out so).  No host cloud is read or uploaded.
-int map_upload_local(lins_ctx* ctx, MapState* m, const LocalMapView& lv, std::vector<MapDevHost>& dev, int* max_q) {
+int map_upload_local(lins_ctx* ctx, MapState* m, const LocalMapView& lv, std::vector<MapDev>& dev, int* max_q) {
   const int n = lv.n;
-  std::vector<MapGridJobHost> jobs((size_t)n * 2);
+  std::vector<MapGridJob> jobs((size_t)n * 2);
   size_t tot_pts = 0, tot_cells = 0, tot_q = 0;
-  dev.assign(n, MapDevHost{});
+  dev.assign(n, MapDev{});
   *max_q = 0;
   for (int k = 0; k < n; ++k) {
     const lins_local_map_sizes& z = lv.sizes[k];
     for (int w = 0; w < 2; ++w) {
-      MapGridJobHost& jb = jobs[(size_t)k * 2 + w];
+      MapGridJob& jb = jobs[(size_t)k * 2 + w];
       long long ncell = 1;
       for (int a = 0; a < 3; ++a) jb.cmin[a] = z.box_min[w][a], jb.cdim[a] = z.box_dim[w][a], ncell *= jb.cdim[a];
       if (ncell > (1ll << 26)) return LINS_E_CAPACITY;  // (cloud_box's limit)
@@ -268,26 +238,26 @@ int map_upload_local(lins_ctx* ctx, MapState* m, const LocalMapView& lv, std::ve
   if ((rc = grow(ctx, &m->d_cells, &m->cap_cells, std::max<size_t>(tot_cells, 1)))) return rc;
   if (m->cap_probs < n) {
     (void)hipFree(m->d_probs), (void)hipFree(m->d_rounds), (void)hipFree(m->d_jobs), (void)hipFree(m->d_carry), (void)hipFree(m->d_results);
-    m->d_probs = m->d_rounds = m->d_jobs = m->d_carry = nullptr, m->d_results = nullptr, m->cap_probs = 0;
-    MAP_TRY(ctx, hipMalloc(&m->d_probs, (size_t)n * sizeof(MapDevHost)));
-    MAP_TRY(ctx, hipMalloc(&m->d_rounds, (size_t)n * map_round_size()));
-    MAP_TRY(ctx, hipMalloc(&m->d_jobs, (size_t)n * 2 * sizeof(MapGridJobHost)));
-    MAP_TRY(ctx, hipMalloc(&m->d_carry, (size_t)n * map_carry_size()));
-    MAP_TRY(ctx, hipMalloc((void**)&m->d_results, (size_t)n * sizeof(lins_map_result)));
+    m->d_probs = nullptr, m->d_rounds = nullptr, m->d_jobs = nullptr, m->d_carry = nullptr, m->d_results = nullptr, m->cap_probs = 0;
+    HIP_TRY(ctx, hipMalloc(&m->d_probs, (size_t)n * sizeof(MapDev)));
+    HIP_TRY(ctx, hipMalloc(&m->d_rounds, (size_t)n * sizeof(MapRoundParams)));
+    HIP_TRY(ctx, hipMalloc(&m->d_jobs, (size_t)n * 2 * sizeof(MapGridJob)));
+    HIP_TRY(ctx, hipMalloc(&m->d_carry, (size_t)n * sizeof(LmCarry)));
+    HIP_TRY(ctx, hipMalloc((void**)&m->d_results, (size_t)n * sizeof(lins_map_result)));
     m->cap_probs = n;
   }
   if (m->cap_q < std::max<size_t>(tot_q, 1)) {
     (void)hipFree(m->d_q), (void)hipFree(m->d_rec);
     m->d_q = nullptr, m->d_rec = nullptr, m->cap_q = 0;
-    MAP_TRY(ctx, hipMalloc((void**)&m->d_q, std::max<size_t>(tot_q, 1) * sizeof(float4)));
-    MAP_TRY(ctx, hipMalloc((void**)&m->d_rec, std::max<size_t>(tot_q, 1) * sizeof(lins_map_corr)));
+    HIP_TRY(ctx, hipMalloc((void**)&m->d_q, std::max<size_t>(tot_q, 1) * sizeof(float4)));
+    HIP_TRY(ctx, hipMalloc((void**)&m->d_rec, std::max<size_t>(tot_q, 1) * sizeof(lins_map_corr)));
     m->cap_q = std::max<size_t>(tot_q, 1);
   }
   hipStream_t st = ctx_stream(ctx);
-  MAP_TRY(ctx, hipMemcpyAsync(m->d_jobs, jobs.data(), jobs.size() * sizeof(MapGridJobHost), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(m->d_jobs, jobs.data(), jobs.size() * sizeof(MapGridJob), hipMemcpyHostToDevice, st));
   launch_map_grid(st, 2 * n, m->d_jobs, lv.d_out, m->d_pts, m->d_cells);
-  MAP_TRY(ctx, hipGetLastError());
-  MAP_TRY(ctx, hipStreamSynchronize(st));  // (jobs goes out of scope)
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(st));  // (jobs goes out of scope)
   // the gridded maps are resident as after an explicit upload: a later LINS_MAP_REUSE call may use them
   m->resident_sizes.clear();
   for (int k = 0; k < n; ++k) m->resident_sizes.push_back(lv.sizes[k].n[0]), m->resident_sizes.push_back(lv.sizes[k].n[1]);
@@ -312,7 +282,7 @@ int map_selfcheck(lins_ctx* ctx, MapState* m) {
   if (m->selfcheck_done) return LINS_OK;
   float* d = nullptr;
   float h[5] = {0, 0, 0, 0, 0};
-  MAP_TRY(ctx, hipMalloc((void**)&d, sizeof h));
+  HIP_TRY(ctx, hipMalloc((void**)&d, sizeof h));
   launch_map_selfcheck(ctx_stream(ctx), d);
   hipError_t e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, ctx_stream(ctx));
   if (e == hipSuccess) e = hipStreamSynchronize(ctx_stream(ctx));
@@ -340,11 +310,8 @@ extern "C" {
 int lins_scan2map_batch(lins_ctx* ctx, int n, const lins_map_problem* in, lins_map_result* out) {
   if (!ctx || n < 0 || (n && (!in || !out))) return LINS_E_ARG;
   if (n == 0) return LINS_OK;
-  static_assert(sizeof(MapDevHost) == 112 && sizeof(MapRoundParams) == 64 && sizeof(lins_map_corr) == 56, "layouts");
-  if (map_dev_size() != sizeof(MapDevHost) || map_round_size() != sizeof(MapRoundParams) ||
-      map_grid_job_size() != sizeof(MapGridJobHost))
-    return LINS_E_STATE;
-  MAP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  static_assert(sizeof(MapRoundParams) == 64 && sizeof(lins_map_corr) == 56, "layouts");
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
   MapState* m = state_of(ctx);
   int rc = map_selfcheck(ctx, m);
   if (rc) return rc;
@@ -362,7 +329,7 @@ int lins_scan2map_batch(lins_ctx* ctx, int n, const lins_map_problem* in, lins_m
     }
   LocalMapView lv{};
   if (n_local && (local_map_view(ctx, &lv) || lv.n != n)) return LINS_E_STATE;
-  std::vector<MapDevHost> dev;
+  std::vector<MapDev> dev;
   int max_q = 0;
   rc = n_local ? map_upload_local(ctx, m, lv, dev, &max_q) : map_upload(ctx, m, n, in, dev, &max_q);
   if (rc) {
@@ -381,19 +348,19 @@ int lins_scan2map_batch(lins_ctx* ctx, int n, const lins_map_problem* in, lins_m
   }
   // the ten rounds of scan2MapOptimization (LM:1640-1647) back to back on the device: correspondences + rows + sums,
   // then the 6x6 step, which also writes the next round's rotation terms and retires converged problems
-  MAP_TRY(ctx, hipMemcpyAsync(m->d_probs, dev.data(), (size_t)n * sizeof(MapDevHost), hipMemcpyHostToDevice, st));
-  MAP_TRY(ctx, hipMemcpyAsync(m->d_results, out, (size_t)n * sizeof(lins_map_result), hipMemcpyHostToDevice, st));
-  MAP_TRY(ctx, hipEventRecord(e0, st));
+  HIP_TRY(ctx, hipMemcpyAsync(m->d_probs, dev.data(), (size_t)n * sizeof(MapDev), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(m->d_results, out, (size_t)n * sizeof(lins_map_result), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipEventRecord(e0, st));
   launch_map_lm(st, n, -1, bpp, m->d_probs, m->d_rounds, m->d_partials, m->d_results, m->d_carry);
   for (int iter = 0; iter < m->max_rounds; ++iter) {
     launch_map_corr(st, n, bpp, m->d_probs, m->d_rounds, m->d_pts, m->d_cells, d_q, m->d_rec, m->d_partials);
     launch_map_lm(st, n, iter, bpp, m->d_probs, m->d_rounds, m->d_partials, m->d_results, m->d_carry);
   }
-  MAP_TRY(ctx, hipGetLastError());
-  MAP_TRY(ctx, hipEventRecord(e1, st));
-  MAP_TRY(ctx, hipMemcpyAsync(out, m->d_results, (size_t)n * sizeof(lins_map_result), hipMemcpyDeviceToHost, st));
-  MAP_TRY(ctx, hipStreamSynchronize(st));
-  MAP_TRY(ctx, hipEventElapsedTime(&m->ms, e0, e1));
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(e1, st));
+  HIP_TRY(ctx, hipMemcpyAsync(out, m->d_results, (size_t)n * sizeof(lins_map_result), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  HIP_TRY(ctx, hipEventElapsedTime(&m->ms, e0, e1));
   m->queries = 0;
   for (int k = 0; k < n; ++k) m->queries += (uint64_t)out[k].iters * ((uint64_t)dev[k].n_q[0] + dev[k].n_q[1]);
   return LINS_OK;
@@ -402,12 +369,11 @@ int lins_scan2map_batch(lins_ctx* ctx, int n, const lins_map_problem* in, lins_m
 int lins_map_correspondences(lins_ctx* ctx, const lins_map_problem* in, lins_map_corr* corner, lins_map_corr* surf) {
   if (!ctx || !in || (in->n_scan_corner && !corner) || (in->n_scan_surf && !surf)) return LINS_E_ARG;
   if (in->reserved[0] & LINS_MAP_LOCAL) return LINS_E_ARG;  // (explicit clouds only)
-  if (map_dev_size() != sizeof(MapDevHost) || map_round_size() != sizeof(MapRoundParams)) return LINS_E_STATE;
-  MAP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
   MapState* m = state_of(ctx);
   int rc = map_selfcheck(ctx, m);
   if (rc) return rc;
-  std::vector<MapDevHost> dev;
+  std::vector<MapDev> dev;
   int max_q = 0;
   rc = transform_finite(in->transform) ? map_upload(ctx, m, 1, in, dev, &max_q) : (int)LINS_E_INPUT;
   if (rc) {
@@ -419,15 +385,15 @@ int lins_map_correspondences(lins_ctx* ctx, const lins_map_problem* in, lins_map
   if ((rc = grow(ctx, &m->d_partials, &m->cap_partials, (size_t)bpp * 28))) return rc;
   hipStream_t st = ctx_stream(ctx);
   const MapRoundParams rd = lm_make_round(in->transform);
-  MAP_TRY(ctx, hipMemcpyAsync(m->d_probs, dev.data(), sizeof(MapDevHost), hipMemcpyHostToDevice, st));
-  MAP_TRY(ctx, hipMemcpyAsync(m->d_rounds, &rd, sizeof rd, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(m->d_probs, dev.data(), sizeof(MapDev), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(m->d_rounds, &rd, sizeof rd, hipMemcpyHostToDevice, st));
   launch_map_corr(st, 1, bpp, m->d_probs, m->d_rounds, m->d_pts, m->d_cells, m->d_q, m->d_rec, m->d_partials);
-  MAP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipGetLastError());
   if (in->n_scan_corner)
-    MAP_TRY(ctx, hipMemcpyAsync(corner, m->d_rec, (size_t)in->n_scan_corner * sizeof(lins_map_corr), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(corner, m->d_rec, (size_t)in->n_scan_corner * sizeof(lins_map_corr), hipMemcpyDeviceToHost, st));
   if (in->n_scan_surf)
-    MAP_TRY(ctx, hipMemcpyAsync(surf, m->d_rec + in->n_scan_corner, (size_t)in->n_scan_surf * sizeof(lins_map_corr), hipMemcpyDeviceToHost, st));
-  MAP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipMemcpyAsync(surf, m->d_rec + in->n_scan_corner, (size_t)in->n_scan_surf * sizeof(lins_map_corr), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
   return LINS_OK;
 }
 

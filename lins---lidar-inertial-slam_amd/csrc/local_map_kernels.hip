@@ -16,6 +16,7 @@
 #include <climits>
 
 #include "../../include/lins_ieskf.h"
+#include "lins_launch.h"
 #include "local_map.h"
 
 namespace lins {
@@ -288,18 +289,16 @@ __global__ __launch_bounds__(kLmTile) void lm_sum_kernel(const int2* __restrict_
 
 }  // namespace
 
-void launch_lm_transform(hipStream_t s, int n_blocks, const void* segs, const int2* blocks, const float4* frames, float4* stage, void* states) {
+void launch_lm_transform(hipStream_t s, int n_blocks, const LmSeg* segs, const int2* blocks, const float4* frames, float4* stage, LmState* states) {
   if (n_blocks)
-    hipLaunchKernelGGL(lm_transform_kernel, dim3(n_blocks), dim3(kLmTile), 0, s, (const LmSeg*)segs, blocks, frames, stage, (LmState*)states);
+    hipLaunchKernelGGL(lm_transform_kernel, dim3(n_blocks), dim3(kLmTile), 0, s, segs, blocks, frames, stage, states);
 }
 
 // one stage: jobs [j0, j0 + n_jobs), tiles [0, n_tiles) of `tiles`
-void launch_lm_stage(hipStream_t s, int j0, int n_jobs, int n_tiles, const int2* tiles, const void* jobs_v, void* states_v,
+void launch_lm_stage(hipStream_t s, int j0, int n_jobs, int n_tiles, const int2* tiles, const LmJob* jobs, LmState* states,
                      float4* stage, unsigned* keys_a, unsigned* keys_b, int* vals_a, int* vals_b, int* hist, int* tilecnt,
                      int* starts, float4* out) {
   if (!n_jobs) return;
-  const LmJob* jobs = (const LmJob*)jobs_v;
-  LmState* states = (LmState*)states_v;
   hipLaunchKernelGGL(lm_setup_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, s, j0, n_jobs, jobs, states);
   if (!n_tiles) return;
   hipLaunchKernelGGL(lm_keys_kernel, dim3(n_tiles), dim3(kLmTile), 0, s, tiles, jobs, states, stage, keys_a, vals_a);

@@ -11,30 +11,14 @@
 // of A^T A, A^T b (f64, fixed-shape tree per block; the host adds the per-block partials in order).
 #include <hip/hip_runtime.h>
 
+#include "lins_launch.h"
 #include "lm_math.h"
 #include "lm_wave.h"
 #include "map_math.h"
 
 namespace lins {
 
-struct MapGrid {  // one cloud of one problem
-  long long off_pts;    // first sorted point (x, y, z, original index bits) in the point arena
-  long long off_cells;  // first of (ncell + 1) cell starts in the cell arena (positions relative to off_pts)
-  int cmin[3], cdim[3];
-};
-struct MapDev {  // one problem
-  MapGrid g[2];      // 0 corner map, 1 surf map
-  long long off_q;   // queries: corner scan points, then surf scan points
-  long long off_rec; // lins_map_corr records, same order
-  int n_q[2];
-  int active;        // 0: finished / precondition not met — its blocks return at once
-  int pad;
-};
-struct MapRound {
-  MapAssoc as;
-  MapTrig tg;
-  float pad;
-};
+using MapRound = MapRoundParams;  // (lm_math.h; MapGrid, MapDev, MapGridJob: lins_records.h)
 
 constexpr int kMapBlock = 256;
 constexpr int kMapLanes = 8;  // lanes per query: they share the scan of its 27 cells, then merge their five-best lists
@@ -201,13 +185,6 @@ __global__ __launch_bounds__(kMapBlock) void map_corr_kernel(const MapDev* __res
 // the cursors, histogram (L2 atomics), exclusive scan, scatter.  The order inside a cell is whatever the atomics
 // give: the 5-NN is decided on (distance, index) keys, so it does not matter.
 // ---------------------------------------------------------------------------
-struct MapGridJob {
-  long long off_raw;   // raw points of this cloud in the staging arena
-  long long off_pts;   // sorted points
-  long long off_cells; // ncell + 1 starts (relative to off_pts), followed by ncell + 1 scratch cursors
-  int n, ncell;
-  int cmin[3], cdim[3];
-};
 constexpr int kGridBlock = 1024;
 
 __global__ __launch_bounds__(kGridBlock) void map_grid_kernel(const MapGridJob* __restrict__ jobs, const float4* __restrict__ raw,
@@ -338,26 +315,24 @@ __global__ __launch_bounds__(64) void debug_lm_step_kernel(int wave_version, con
     for (int t = 0; t < 36; ++t) o[8 + t] = (double)c->P[t];
   }
 }
-void launch_debug_lm_step(hipStream_t stream, int n, int wave_version, const double* in, double* out, void* scratch) {
-  hipLaunchKernelGGL(debug_lm_step_kernel, dim3(n), dim3(64), 0, stream, wave_version, in, out, (LmCarry*)scratch);
+void launch_debug_lm_step(hipStream_t stream, int n, int wave_version, const double* in, double* out, LmCarry* scratch) {
+  hipLaunchKernelGGL(debug_lm_step_kernel, dim3(n), dim3(64), 0, stream, wave_version, in, out, scratch);
 }
 
-void launch_map_grid(hipStream_t stream, int n_jobs, const void* jobs, const float4* raw, float4* pts, int* cells) {
-  hipLaunchKernelGGL(map_grid_kernel, dim3(n_jobs), dim3(kGridBlock), 0, stream, (const MapGridJob*)jobs, raw, pts, cells);
+void launch_map_grid(hipStream_t stream, int n_jobs, const MapGridJob* jobs, const float4* raw, float4* pts, int* cells) {
+  hipLaunchKernelGGL(map_grid_kernel, dim3(n_jobs), dim3(kGridBlock), 0, stream, jobs, raw, pts, cells);
 }
-void launch_map_lm(hipStream_t stream, int n, int iter, int blocks_per_problem, void* probs, void* rounds, const double* partials,
-                   lins_map_result* results, void* carry) {
-  hipLaunchKernelGGL(map_lm_kernel, dim3(n), dim3(64), 0, stream, n, iter, blocks_per_problem, (MapDev*)probs,
-                     (MapRound*)rounds, partials, results, (LmCarry*)carry);
+void launch_map_lm(hipStream_t stream, int n, int iter, int blocks_per_problem, MapDev* probs, MapRoundParams* rounds, const double* partials,
+                   lins_map_result* results, LmCarry* carry) {
+  hipLaunchKernelGGL(map_lm_kernel, dim3(n), dim3(64), 0, stream, n, iter, blocks_per_problem, probs,
+                     rounds, partials, results, carry);
 }
-size_t map_grid_job_size() { return sizeof(MapGridJob); }
-size_t map_carry_size() { return sizeof(LmCarry); }
 
-void launch_map_corr(hipStream_t stream, int n_problems, int blocks_per_problem, const void* probs, const void* rounds,
+void launch_map_corr(hipStream_t stream, int n_problems, int blocks_per_problem, const MapDev* probs, const MapRoundParams* rounds,
                      const float4* pts, const int* cells, const float4* queries, lins_map_corr* recs, double* partials) {
   // (one-dimensional grid: 8 x blocks_per_problem x ceil(n_problems / 8) — the XCD-aware mapping of the kernel)
-  hipLaunchKernelGGL(map_corr_kernel, dim3(8 * blocks_per_problem * ((n_problems + 7) / 8)), dim3(kMapBlock), 0, stream, (const MapDev*)probs,
-                     (const MapRound*)rounds, pts, cells, queries, recs, partials, blocks_per_problem, n_problems);
+  hipLaunchKernelGGL(map_corr_kernel, dim3(8 * blocks_per_problem * ((n_problems + 7) / 8)), dim3(kMapBlock), 0, stream, probs,
+                     rounds, pts, cells, queries, recs, partials, blocks_per_problem, n_problems);
 }
 // Start-up self-check of the plane fit: five points of the wall y = 2 and a query 5 cm in front of it must give a
 // normal along y.  (ROCm 7.2's SLP vectoriser loses the y column of the unrolled 5 x 3 QR at -O2 and above — this file
@@ -369,8 +344,6 @@ __global__ void map_selfcheck_kernel(float* __restrict__ out) {
   out[0] = c[0], out[1] = c[1], out[2] = c[2], out[3] = c[3], out[4] = (float)acc;
 }
 void launch_map_selfcheck(hipStream_t stream, float* out) { hipLaunchKernelGGL(map_selfcheck_kernel, dim3(1), dim3(1), 0, stream, out); }
-size_t map_dev_size() { return sizeof(MapDev); }
-size_t map_round_size() { return sizeof(MapRound); }
 int map_block() { return kMapQPerBlock; }  // queries per block
 
 }  // namespace lins

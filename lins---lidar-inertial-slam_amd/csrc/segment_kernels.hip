@@ -21,6 +21,7 @@
 #include <cfloat>
 
 #include "../../include/lins_host.h"
+#include "lins_launch.h"
 #include "lins_math.h"
 
 namespace lins {
@@ -35,13 +36,7 @@ struct FeScanOut {  // the head of FeScan (frontend_kernels.hip): what this kern
   int start_ring[kSgRows], end_ring[kSgRows];
   float start_ori, end_ori, ori_diff;
 };
-constexpr size_t kFeScanStride = 192;  // sizeof(FeScan)
-
-struct SgRaw {
-  long long off;  // first raw point of the scan
-  int n;
-  int pad;
-};
+constexpr size_t kFeScanStride = sizeof(FeScan);
 
 struct SgConsts {
   float sin_ax, cos_ax, sin_ay, cos_ay;  // sin / cos of segmentAlphaX / Y as the host computes them
@@ -412,13 +407,12 @@ __global__ __launch_bounds__(kSgBlock) void segment_kernel(const SgRaw* __restri
   }
 }
 
-void launch_segment(hipStream_t stream, int n_scans, const void* raws, const float4* raw, float sin_ax, float cos_ax,
-                    float sin_ay, float cos_ay, float theta, unsigned* cellidx, int* seg_rows, void* fe_scans, float4* out_cloud,
+void launch_segment(hipStream_t stream, int n_scans, const SgRaw* raws, const float4* raw, float sin_ax, float cos_ax,
+                    float sin_ay, float cos_ay, float theta, unsigned* cellidx, int* seg_rows, FeScan* fe_scans, float4* out_cloud,
                     float* out_range, unsigned* out_col, unsigned char* out_ground, int* out_outliers) {
   SgConsts k{sin_ax, cos_ax, sin_ay, cos_ay, theta};
-  hipLaunchKernelGGL(segment_kernel, dim3(n_scans), dim3(kSgBlock), 0, stream, (const SgRaw*)raws, raw, k, cellidx, seg_rows,
+  hipLaunchKernelGGL(segment_kernel, dim3(n_scans), dim3(kSgBlock), 0, stream, raws, raw, k, cellidx, seg_rows,
                      (unsigned char*)fe_scans, out_cloud, out_range, out_col, out_ground, out_outliers);
 }
-size_t sg_raw_size() { return sizeof(SgRaw); }
 
 }  // namespace lins
