@@ -207,6 +207,21 @@ int lins_host_perform_ieskf(lins_ctx* ctx, const lins_params* prm,
 int lins_host_local_map(const lins_keyframe* frames, int n_frames, int window, const lins_local_scan* scan,
                         lins_point* const* out, lins_local_map_sizes* sizes);
 
+/* ---- the key-frame archive on the CPU (host/keyframe_archive.cpp) ------------
+ * The restatements lins_archive_select_radius / _find_loop / _assemble are checked against, bit for bit
+ * (include/lins_map.h; the selection is the same inline code in both libraries, host/keyframe_select.h).  poses / times:
+ * the key poses of one slot by frame id.  Both return LINS_E_INPUT for a pose outside the local map's input contract. */
+/* returns the count of selected frame ids (LINS_E_CAPACITY beyond cap) */
+int lins_host_select_radius(const lins_key_pose* poses, int n, const float centre[3], float radius, float pose_leaf,
+                            int32_t* ids, int cap);
+int lins_host_find_loop(const lins_key_pose* poses, const double* times, int n, const float centre[3], float radius,
+                        double now, double min_gap_s, int32_t* closest);
+/* one lins_submap_spec over `frames` (frame id = index): out holds at least the points the spec reads (the chosen clouds
+ * of the chosen frames, repeats counted).  LINS_E_ARG for a bad id / mask / flag as lins_archive_assemble, LINS_E_INPUT
+ * for a chosen frame outside the input contract (nothing written), else LINS_OK (the cloud's own status in info->status). */
+int lins_host_submap(const lins_keyframe* frames, int n_frames, const int32_t* ids, int n_ids, int clouds, float leaf,
+                     int flags, lins_point* out, lins_submap_info* info);
+
 #ifdef __cplusplus
 }
 #endif

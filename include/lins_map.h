@@ -145,6 +145,83 @@ int lins_local_map_download(lins_ctx* ctx, int entry, int which, lins_point* out
 /* HIP-event time (ms) of the device sequence of the last build and the points it read (window frames + raw scans) */
 int lins_last_local_map_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* points_in);
 
+/* ---- the key-frame archive: global map and loop-closure submaps (LM:984-1031, 1043-1112, 1767-1795) ------------------
+ * Every key frame of a slot stays on the device, in the sensor frame, in one bump-allocated point arena per context
+ * (nothing is ever deleted); the host keeps per frame its offset, counts, pose, the pose's trigonometry as the local
+ * map forms it, and a time.  Frame ids are 0, 1, 2 ... per slot in push order — the index cloudKeyPoses3D carries in
+ * `intensity`.  The archive is independent of the local map's rings: a caller that wants both pushes to both.
+ *
+ * An assembly moves the chosen clouds of the chosen frames into the map frame (the two-argument transformPointCloud,
+ * LM:654-686: the same f32 sequence as LM:627-650, and its cos / sin act on the same float members of PointTypePose in
+ * the same translation unit as updateTransformPointCloudSinCos, so they are the same overloads — forming the six values
+ * once per frame on the host is value-identical), concatenates them in the order given — within a frame always corner,
+ * surf, outlier — and either VoxelGrid-filters the result (leaf > 0; DESIGN.md §5.3's contract, as the local map) or
+ * hands it out as it is (leaf == 0), optionally without the points of (int)intensity < 0.  That predicate is C's cast as
+ * x86 evaluates it for EVERY float: kept are exactly -1 < intensity < 2^31 (-0.5 is kept, -1.0 dropped; NaN, +-inf and
+ * anything the cast cannot represent give INT_MIN there and are dropped), so intensity needs no input contract.
+ *
+ * The reference's three clouds are compositions (H = historyKeyframeSearchNum = 25, latest = count - 1):
+ *   globalMapKeyFramesDS            ids = select_radius(centre, 500, 1.0)   clouds = corner | surf | outlier  leaf 0.4
+ *   nearHistorySurfKeyFrameCloudDS  ids = max(0, closest - H) .. min(latest, closest + H)   corner | surf     leaf 0.4
+ *   latestSurfKeyFrameCloud         ids = { latest }                        corner | surf   leaf 0, DROP_NEGATIVE      */
+#define LINS_SUBMAP_CORNER 1
+#define LINS_SUBMAP_SURF 2
+#define LINS_SUBMAP_OUTLIER 4
+#define LINS_SUBMAP_DROP_NEGATIVE 1 /* flags: drop (int)intensity < 0, order kept; only with leaf == 0 (else LINS_E_ARG) */
+
+typedef struct lins_submap_spec {
+  const int32_t* ids; /* frames of `slot`, concatenated in this order (an id may repeat) */
+  int32_t n_ids;
+  int32_t slot;
+  int32_t clouds;     /* mask of LINS_SUBMAP_CORNER | _SURF | _OUTLIER, at least one */
+  int32_t flags;      /* 0 or LINS_SUBMAP_DROP_NEGATIVE */
+  float leaf;         /* 0: the bare concatenation; > 0: VoxelGrid of this leaf */
+  int32_t reserved;
+} lins_submap_spec;
+
+typedef struct lins_submap_info {
+  int32_t n;          /* points of the assembled cloud */
+  int32_t frames;     /* n_ids */
+  uint64_t points_in; /* points read from the archive */
+  int32_t box_min[3]; /* the 1 m cell box of a filtered (leaf > 0) output, as lins_local_map_sizes has it; */
+  int32_t box_dim[3]; /* an empty or unfiltered cloud: min 0, dim 1 */
+  int32_t status;     /* LINS_OK; LINS_E_CAPACITY: a VoxelGrid box of more than 2^31 cells; LINS_E_INPUT: a
+                         transformed point beyond |coord| <= 1e6 — the cloud is then empty */
+  int32_t reserved;
+} lins_submap_info;
+
+/* Errors of every call below: LINS_E_STATE before lins_archive_init, LINS_E_ARG for a bad slot / id / mask / flag,
+ * LINS_E_CAPACITY when the arena or a slot's frame list is full.  A refused call changes nothing.                */
+/* n_slots frame lists of up to max_frames_per_slot frames over one arena of max_points_total points.  Sized once; a
+ * second call drops every frame and sizes anew. */
+int lins_archive_init(lins_ctx* ctx, int n_slots, int max_frames_per_slot, long long max_points_total);
+/* one key frame behind the frames of `slot`; returns its id (>= 0) or an error.  Input contract of lins_local_map_push. */
+int lins_archive_push(lins_ctx* ctx, int slot, const lins_keyframe* frame, double time);
+/* cornerDS / surfDS / outlierDS of entries of the last lins_local_map_build become frames of their slots, device to
+ * device, in the order given (as lins_local_map_push_scans); ids_out (may be NULL) gets the new ids */
+int lins_archive_push_scans(lins_ctx* ctx, int n, const int32_t* entries, const lins_key_pose* poses, const double* times, int32_t* ids_out);
+/* correctPoses over the whole history: frames first_id .. first_id + n - 1 of slot */
+int lins_archive_set_poses(lins_ctx* ctx, int slot, int first_id, int n, const lins_key_pose* poses);
+/* frames of slot (>= 0) */
+int lins_archive_count(lins_ctx* ctx, int slot);
+/* publishGlobalMap's choice of frames (LM:989-1007): radius search around centre, VoxelGrid(pose_leaf) of the hits as
+ * points (x, y, z, (float)id), frame = (int) of each voxel's averaged intensity, in ascending voxel order (the
+ * selection's contract: DESIGN.md §5.3, csrc/host/keyframe_select.h).  Returns the count; LINS_E_CAPACITY beyond cap. */
+int lins_archive_select_radius(lins_ctx* ctx, int slot, const float centre[3], float radius, float pose_leaf, int32_t* ids, int cap);
+/* detectLoopClosure's candidate (LM:1050-1067): the first hit of the radius search with |time - now| > min_gap_s;
+ * *closest = its id or -1 */
+int lins_archive_find_loop(lins_ctx* ctx, int slot, const float centre[3], float radius, double now, double min_gap_s, int32_t* closest);
+/* n assemblies in one sequence of launches on the context's stream with one synchronisation; out[k] (may be NULL) */
+int lins_archive_assemble(lins_ctx* ctx, int n, const lins_submap_spec* specs, lins_submap_info* out);
+/* the cloud of entry `entry` of the last assembly; returns the point count, LINS_E_CAPACITY when larger than cap */
+int lins_archive_download(lins_ctx* ctx, int entry, lins_point* out, int cap);
+/* HIP-event time (ms) of the device sequence of the last assembly and the points it read */
+int lins_last_archive_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* points_in);
+/* test hook: the scans over a job's (256 digits x tiles) histogram and over its per-tile counts run in one workgroup
+ * for a job of at most chunk_tiles tiles (of 512 points) and are split into chunks of chunk_tiles tiles over many
+ * workgroups above it.  0: the default; INT_MAX: never split.  Results are the same bits for every value. */
+int lins_archive_set_scan_chunk(lins_ctx* ctx, int chunk_tiles);
+
 #ifdef __cplusplus
 }
 #endif

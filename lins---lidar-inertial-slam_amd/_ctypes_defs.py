@@ -291,3 +291,22 @@ def local_scan_c(corner, surf, outlier):
     keep = [cloud(corner), cloud(surf), cloud(outlier)]
     pp = lambda a: a.ctypes.data_as(C.POINTER(Point))
     return LocalScanC(pp(keep[0]), pp(keep[1]), pp(keep[2]), len(keep[0]), len(keep[1]), len(keep[2]), 0), keep
+
+
+# ---- the key-frame archive (include/lins_map.h lins_archive_*) ------------------------------
+SUBMAP_CORNER, SUBMAP_SURF, SUBMAP_OUTLIER = 1, 2, 4
+SUBMAP_DROP_NEGATIVE = 1
+
+
+class SubmapSpecC(C.Structure):
+    _fields_ = [("ids", C.POINTER(C.c_int32)), ("n_ids", C.c_int32), ("slot", C.c_int32), ("clouds", C.c_int32),
+                ("flags", C.c_int32), ("leaf", C.c_float), ("reserved", C.c_int32)]
+
+
+class SubmapInfoC(C.Structure):
+    _fields_ = [("n", C.c_int32), ("frames", C.c_int32), ("points_in", C.c_uint64), ("box_min", C.c_int32 * 3),
+                ("box_dim", C.c_int32 * 3), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return dict(n=int(self.n), frames=int(self.frames), points_in=int(self.points_in), box_min=list(self.box_min),
+                    box_dim=list(self.box_dim), status=int(self.status))

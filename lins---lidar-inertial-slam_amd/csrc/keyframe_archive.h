@@ -1,0 +1,31 @@
+// keyframe_archive.h — the device records of the key-frame archive's assembly (archive_kernels.hip,
+// lins_archive_capi.hip).  An assembly is one VoxelGrid job (leaf > 0) or one compaction job (leaf == 0) per spec, in
+// the records of the local-map build (local_map.h LmJob / LmState / LmSeg and its (job, tile) table): the VoxelGrid
+// arithmetic is that build's kernels.  What is the archive's own is the gather from its arena, the compaction, and the
+// scan of a large job's counts over many workgroups:
+//   a job of more than `chunk` tiles has its digit-major row of (rows x tiles) counts cut into chunks of rows * chunk
+//   elements; chunk sums (one workgroup per chunk) -> exclusive scan of the job's chunk sums (one workgroup per job) ->
+//   each chunk re-scanned from its offset (one workgroup per chunk).  Integer sums: the same bits whatever the split.
+#pragma once
+#include "local_map.h"
+
+namespace lins {
+
+constexpr int kArScanChunk = 16;  // default chunk (tiles): a job of at most this many tiles is scanned in one workgroup
+
+struct ArChunk {  // one chunk of one split job
+  int job;
+  int k;       // chunk index within the job
+  int c0;      // the job's first chunk sum in the chunk-sum arena
+  int pad;
+};
+static_assert(sizeof(ArChunk) == 16, "ArChunk layout");
+
+struct ArSplit {  // one split job
+  int job;
+  int c0, nc;  // its chunk sums
+  int pad;
+};
+static_assert(sizeof(ArSplit) == 16, "ArSplit layout");
+
+}  // namespace lins

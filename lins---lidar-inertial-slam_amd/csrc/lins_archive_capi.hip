@@ -1,0 +1,450 @@
+// lins_archive_capi.hip — C ABI of the key-frame archive (include/lins_map.h lins_archive_*): every key frame of a slot
+// in one bump-allocated device arena, the host's list of frames (offset, counts, pose, trigonometry, time), the
+// selection of frames (host/keyframe_select.h — the same inline code liblins_host.so exports), and the packing of an
+// assembly into the jobs of archive_kernels.hip / local_map_kernels.hip.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/lins_map.h"
+#include "host/keyframe_select.h"
+#include "keyframe_archive.h"
+#include "lins_ctx_priv.h"
+#include "lins_launch.h"
+#include "local_map.h"
+
+using namespace lins;
+using lins_hostmap::cloud_ok;
+using lins_hostmap::pose_ok;
+
+namespace {
+
+struct ArFrame {
+  long long off;  // of the frame's block in the arena: corner, surf, outlier one after the other
+  int n[3];
+  lins_key_pose pose;
+  float t[9];  // ctRoll, stRoll, ctPitch, stPitch, ctYaw, stYaw, tInX, tInY, tInZ
+  double time;
+};
+
+struct Archive {
+  int n_slots = 0, max_frames = 0, chunk = kArScanChunk;
+  long long max_points = 0, used = 0;
+  float4* d_arena = nullptr;
+  std::vector<std::vector<ArFrame>> frames;  // [slot][id]
+  // assembly arenas (grown, never shrunk)
+  float4 *d_stage = nullptr, *d_out = nullptr;
+  unsigned *d_ka = nullptr, *d_kb = nullptr;
+  int *d_va = nullptr, *d_vb = nullptr, *d_starts = nullptr, *d_hist = nullptr, *d_tilecnt = nullptr, *d_csum = nullptr;
+  char *d_tab = nullptr, *h_tab = nullptr, *h_states = nullptr;
+  size_t cap_stage = 0, cap_sort = 0, cap_out = 0, cap_hist = 0, cap_tilecnt = 0, cap_csum = 0, cap_tab = 0, cap_htab = 0, cap_hstates = 0;
+  // the last assembly
+  bool built = false;
+  std::vector<long long> off;
+  std::vector<lins_submap_info> info;
+  float ms = 0.f;
+  uint64_t points_in = 0;
+};
+
+void archive_free(void* p) {
+  Archive* m = (Archive*)p;
+  (void)hipFree(m->d_arena), (void)hipFree(m->d_stage), (void)hipFree(m->d_out), (void)hipFree(m->d_ka), (void)hipFree(m->d_kb);
+  (void)hipFree(m->d_va), (void)hipFree(m->d_vb), (void)hipFree(m->d_starts), (void)hipFree(m->d_hist), (void)hipFree(m->d_tilecnt);
+  (void)hipFree(m->d_csum), (void)hipFree(m->d_tab), (void)hipHostFree(m->h_tab), (void)hipHostFree(m->h_states);
+  delete m;
+}
+
+Archive* archive_of(lins_ctx* ctx) {
+  void** slot = map_archive_slot(ctx, archive_free);
+  if (!*slot) *slot = new Archive();
+  return (Archive*)*slot;
+}
+
+template <class T>
+int grow(lins_ctx* ctx, T** p, size_t* cap, size_t need) {
+  need = std::max<size_t>(need, 1);
+  if (*cap >= need) return LINS_OK;
+  (void)hipFree(*p);
+  *p = nullptr, *cap = 0;
+  HIP_TRY(ctx, hipMalloc((void**)p, need * sizeof(T)));
+  *cap = need;
+  return LINS_OK;
+}
+template <class T>
+int grow_pinned(lins_ctx* ctx, T** p, size_t* cap, size_t need) {
+  need = std::max<size_t>(need, 1);
+  if (*cap >= need) return LINS_OK;
+  (void)hipHostFree(*p);
+  *p = nullptr, *cap = 0;
+  HIP_TRY(ctx, hipHostMalloc((void**)p, need * sizeof(T)));
+  *cap = need;
+  return LINS_OK;
+}
+
+void set_pose(ArFrame& f, const lins_key_pose& p) {  // updateTransformPointCloudSinCos (LM:612-624), as the local map's set_pose
+  f.pose = p;
+  const float t[9] = {std::cos(p.roll), std::sin(p.roll), std::cos(p.pitch), std::sin(p.pitch), std::cos(p.yaw), std::sin(p.yaw), p.x, p.y, p.z};
+  std::memcpy(f.t, t, sizeof t);
+}
+
+size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
+
+std::vector<lins_key_pose> poses_of(const std::vector<ArFrame>& fr) {
+  std::vector<lins_key_pose> p(fr.size());
+  for (size_t i = 0; i < fr.size(); ++i) p[i] = fr[i].pose;
+  return p;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lins_archive_init(lins_ctx* ctx, int n_slots, int max_frames_per_slot, long long max_points_total) {
+  if (!ctx || n_slots < 1 || max_frames_per_slot < 1 || max_points_total < 1 || max_points_total > (1ll << 40)) return LINS_E_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  Archive* m = archive_of(ctx);
+  HIP_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));  // (a push_scans copy may still write the old arena)
+  (void)hipFree(m->d_arena);
+  m->d_arena = nullptr, m->n_slots = 0, m->built = false, m->used = 0;
+  m->frames.clear();
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_arena, (size_t)max_points_total * sizeof(float4)));
+  m->n_slots = n_slots, m->max_frames = max_frames_per_slot, m->max_points = max_points_total;
+  m->frames.assign(n_slots, {});
+  return LINS_OK;
+}
+
+int lins_archive_push(lins_ctx* ctx, int slot, const lins_keyframe* f, double time) {
+  if (!ctx || !f) return LINS_E_ARG;
+  Archive* m = archive_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (slot < 0 || slot >= m->n_slots) return LINS_E_ARG;
+  const lins_point* c[3] = {f->corner, f->surf, f->outlier};
+  const int n[3] = {f->n_corner, f->n_surf, f->n_outlier};
+  for (int k = 0; k < 3; ++k) {
+    if (n[k] < 0 || (n[k] && !c[k])) return LINS_E_ARG;
+    if (!cloud_ok(c[k], n[k])) return LINS_E_INPUT;
+  }
+  if (!pose_ok(f->pose) || !std::isfinite(time)) return LINS_E_INPUT;
+  const long long total = (long long)n[0] + n[1] + n[2];
+  if (m->used + total > m->max_points || (int)m->frames[slot].size() >= m->max_frames) return LINS_E_CAPACITY;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  hipStream_t st = ctx_stream(ctx);
+  ArFrame fr{};
+  fr.off = m->used, fr.time = time;
+  float4* dst = m->d_arena + fr.off;
+  for (int k = 0; k < 3; ++k) {
+    fr.n[k] = n[k];
+    if (n[k]) HIP_TRY(ctx, hipMemcpyAsync(dst, c[k], (size_t)n[k] * sizeof(float4), hipMemcpyHostToDevice, st));
+    dst += n[k];
+  }
+  set_pose(fr, f->pose);
+  HIP_TRY(ctx, hipStreamSynchronize(st));  // (the caller's clouds may go once this returns)
+  m->used += total;
+  m->frames[slot].push_back(fr);
+  return (int)m->frames[slot].size() - 1;
+}
+
+int lins_archive_push_scans(lins_ctx* ctx, int n, const int32_t* entries, const lins_key_pose* poses, const double* times, int32_t* ids_out) {
+  if (!ctx || n < 0 || (n && (!entries || !poses || !times))) return LINS_E_ARG;
+  Archive* m = archive_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  LocalMapView v;
+  if (int rc = local_map_view(ctx, &v)) return rc;
+  long long total = 0;
+  std::vector<int> added(m->n_slots, 0);
+  for (int i = 0; i < n; ++i) {
+    const int e = entries[i];
+    if (e < 0 || e >= v.n || v.slots[e] >= m->n_slots) return LINS_E_ARG;
+    const lins_local_map_sizes& z = v.sizes[e];
+    if (z.status) return LINS_E_STATE;
+    if (!pose_ok(poses[i]) || !std::isfinite(times[i])) return LINS_E_INPUT;
+    total += (long long)z.n[LINS_LOCAL_SCAN_CORNER] + z.n[LINS_LOCAL_SCAN_SURF] + z.n[LINS_LOCAL_SCAN_OUTLIER];
+    if ((int)m->frames[v.slots[e]].size() + ++added[v.slots[e]] > m->max_frames) return LINS_E_CAPACITY;
+  }
+  if (m->used + total > m->max_points) return LINS_E_CAPACITY;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  hipStream_t st = ctx_stream(ctx);
+  for (int i = 0; i < n; ++i) {  // saveKeyFramesAndFactor (LM:1758-1763): cornerDS, surfDS, outlierDS
+    const int e = entries[i], s = v.slots[e];
+    ArFrame fr{};
+    fr.off = m->used, fr.time = times[i];
+    float4* dst = m->d_arena + fr.off;
+    for (int q = 0; q < 3; ++q) {
+      const int c = LINS_LOCAL_SCAN_CORNER + q, cnt = v.sizes[e].n[c];
+      fr.n[q] = cnt;
+      if (cnt) HIP_TRY(ctx, hipMemcpyAsync(dst, v.d_out + v.off[6 * e + c], (size_t)cnt * sizeof(float4), hipMemcpyDeviceToDevice, st));
+      dst += cnt;
+    }
+    set_pose(fr, poses[i]);
+    m->used += (long long)fr.n[0] + fr.n[1] + fr.n[2];
+    m->frames[s].push_back(fr);
+    if (ids_out) ids_out[i] = (int32_t)m->frames[s].size() - 1;
+  }
+  return LINS_OK;
+}
+
+int lins_archive_set_poses(lins_ctx* ctx, int slot, int first_id, int n, const lins_key_pose* poses) {
+  if (!ctx || n < 0 || (n && !poses)) return LINS_E_ARG;
+  Archive* m = archive_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (slot < 0 || slot >= m->n_slots || first_id < 0 || (long long)first_id + n > (long long)m->frames[slot].size()) return LINS_E_ARG;
+  for (int i = 0; i < n; ++i)
+    if (!pose_ok(poses[i])) return LINS_E_INPUT;
+  for (int i = 0; i < n; ++i) set_pose(m->frames[slot][first_id + i], poses[i]);
+  return LINS_OK;
+}
+
+int lins_archive_count(lins_ctx* ctx, int slot) {
+  if (!ctx) return LINS_E_ARG;
+  Archive* m = archive_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (slot < 0 || slot >= m->n_slots) return LINS_E_ARG;
+  return (int)m->frames[slot].size();
+}
+
+int lins_archive_select_radius(lins_ctx* ctx, int slot, const float centre[3], float radius, float pose_leaf, int32_t* ids, int cap) {
+  if (!ctx) return LINS_E_ARG;
+  Archive* m = archive_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (slot < 0 || slot >= m->n_slots || cap < 0 || !lins_select::query_ok(centre, radius) || !(pose_leaf > 0.f)) return LINS_E_ARG;
+  const std::vector<lins_key_pose> poses = poses_of(m->frames[slot]);
+  std::vector<int> sel;
+  if (!lins_select::select_radius(poses.data(), (int)poses.size(), centre, radius, pose_leaf, sel)) return LINS_E_CAPACITY;
+  if ((int)sel.size() > cap) return LINS_E_CAPACITY;
+  if (!sel.empty() && !ids) return LINS_E_ARG;
+  for (size_t i = 0; i < sel.size(); ++i) ids[i] = sel[i];
+  return (int)sel.size();
+}
+
+int lins_archive_find_loop(lins_ctx* ctx, int slot, const float centre[3], float radius, double now, double min_gap_s, int32_t* closest) {
+  if (!ctx || !closest) return LINS_E_ARG;
+  Archive* m = archive_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (slot < 0 || slot >= m->n_slots || !lins_select::query_ok(centre, radius)) return LINS_E_ARG;
+  const std::vector<lins_key_pose> poses = poses_of(m->frames[slot]);
+  std::vector<double> times(poses.size());
+  for (size_t i = 0; i < times.size(); ++i) times[i] = m->frames[slot][i].time;
+  *closest = lins_select::find_loop(poses.data(), times.data(), (int)poses.size(), centre, radius, now, min_gap_s);
+  return LINS_OK;
+}
+
+int lins_archive_set_scan_chunk(lins_ctx* ctx, int chunk_tiles) {
+  if (!ctx || chunk_tiles < 0) return LINS_E_ARG;
+  archive_of(ctx)->chunk = chunk_tiles ? chunk_tiles : kArScanChunk;
+  return LINS_OK;
+}
+
+int lins_archive_assemble(lins_ctx* ctx, int n, const lins_submap_spec* specs, lins_submap_info* out) {
+  if (!ctx || n < 0 || (n && !specs)) return LINS_E_ARG;
+  Archive* m = archive_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  const int all = LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF | LINS_SUBMAP_OUTLIER;
+  std::vector<long long> cap(n, 0);
+  for (int k = 0; k < n; ++k) {
+    const lins_submap_spec& sp = specs[k];
+    if (sp.slot < 0 || sp.slot >= m->n_slots || sp.n_ids < 0 || (sp.n_ids && !sp.ids) || sp.clouds <= 0 || (sp.clouds & ~all) ||
+        (sp.flags & ~LINS_SUBMAP_DROP_NEGATIVE) || !(sp.leaf >= 0.f) || !std::isfinite(sp.leaf) ||
+        ((sp.flags & LINS_SUBMAP_DROP_NEGATIVE) && sp.leaf != 0.f))
+      return LINS_E_ARG;
+    const std::vector<ArFrame>& fr = m->frames[sp.slot];
+    for (int i = 0; i < sp.n_ids; ++i) {
+      if (sp.ids[i] < 0 || sp.ids[i] >= (int)fr.size()) return LINS_E_ARG;
+      for (int q = 0; q < 3; ++q)
+        if (sp.clouds & (1 << q)) cap[k] += fr[sp.ids[i]].n[q];
+    }
+  }
+  for (int k = 0; k < n; ++k)
+    if (cap[k] > INT_MAX / 2) return LINS_E_CAPACITY;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  m->built = false;
+  // jobs: VoxelGrid jobs first — those whose scans are split, then the others — then the leaf == 0 jobs, the split ones last
+  const int chunk = m->chunk;
+  auto tiles_of = [&](int k) { return (cap[k] + kLmTile - 1) / kLmTile; };
+  auto cls = [&](int k) {
+    const bool vg = specs[k].leaf > 0.f, split = tiles_of(k) > chunk;
+    return vg ? (split ? 0 : 1) : (split ? 3 : 2);
+  };
+  std::vector<int> spec_of, job_of(n);
+  int bound[5] = {0, 0, 0, 0, 0};  // jobs of class c: [bound[c], bound[c + 1])
+  for (int c = 0; c < 4; ++c) {
+    for (int k = 0; k < n; ++k)
+      if (cls(k) == c) job_of[k] = (int)spec_of.size(), spec_of.push_back(k);
+    bound[c + 1] = (int)spec_of.size();
+  }
+  const int nv = bound[2];
+  std::vector<LmJob> jobs(n);
+  std::vector<LmState> states(n);
+  std::vector<int> jflags(n, 0);
+  std::vector<int2> tiles;
+  std::vector<ArChunk> chunks;
+  std::vector<ArSplit> splits;
+  size_t stage_total = 0, sort_total = 0, tiles_total = 0, vg_tiles = 0, out_total = 0;
+  int n_hist_chunks = 0;
+  for (int j = 0; j < n; ++j) {
+    const int k = spec_of[j];
+    LmJob& jb = jobs[j];
+    jb.off_in = (long long)stage_total, stage_total += (size_t)cap[k];
+    jb.off_out = (long long)out_total, out_total += (size_t)cap[k];
+    jb.cap = (int)cap[k];
+    jb.ntiles = (int)tiles_of(k);
+    jb.tile0 = (int)tiles_total, tiles_total += (size_t)jb.ntiles;
+    jb.inv = specs[k].leaf > 0.f ? 1.0f / specs[k].leaf : 0.f;
+    jb.out_after = jb.src_a = jb.src_b = jb.feed = jb.feed_after = -1, jb.map = j < nv ? 1 : 0, jb.pad = 0;
+    jflags[j] = specs[k].flags;
+    if (j < nv) sort_total = stage_total, vg_tiles = tiles_total;
+    for (int t = 0; t < jb.ntiles; ++t) tiles.push_back(make_int2(j, t));
+    LmState& st = states[j];
+    std::memset(&st, 0, sizeof st);
+    for (int a = 0; a < 3; ++a)
+      st.mn[a] = lm_enc(INFINITY), st.mx[a] = lm_enc(-INFINITY), st.bmin[a] = INT_MAX, st.bmax[a] = INT_MIN;
+    st.n = jb.cap;
+  }
+  if (tiles_total > (size_t)INT_MAX / 256) return LINS_E_CAPACITY;
+  for (int pass = 0; pass < 2; ++pass) {  // the split jobs' chunks: the VoxelGrid jobs' first (the histogram scans use those alone)
+    for (int j = pass ? bound[3] : 0; j < (pass ? bound[4] : bound[1]); ++j) {
+      ArSplit s{j, (int)chunks.size(), (jobs[j].ntiles + chunk - 1) / chunk, 0};
+      for (int c = 0; c < s.nc; ++c) chunks.push_back(ArChunk{j, c, s.c0, 0});
+      splits.push_back(s);
+    }
+    if (!pass) n_hist_chunks = (int)chunks.size();
+  }
+  // the chosen clouds: one segment per run of chosen clouds of a frame (they lie one after the other in the arena and
+  // share the frame's pose), blocks of kLmTile points
+  std::vector<LmSeg> segs;
+  std::vector<int2> blocks;
+  uint64_t pts_in = 0;
+  for (int j = 0; j < n; ++j) {
+    const lins_submap_spec& sp = specs[spec_of[j]];
+    long long at = jobs[j].off_in;
+    for (int i = 0; i < sp.n_ids; ++i) {
+      const ArFrame& f = m->frames[sp.slot][sp.ids[i]];
+      long long src = f.off;
+      for (int q = 0; q < 3;) {
+        if (!(sp.clouds & (1 << q))) {
+          src += f.n[q++];
+          continue;
+        }
+        LmSeg g{};
+        g.src = src, g.dst = at, g.job = j;
+        for (; q < 3 && (sp.clouds & (1 << q)); ++q) g.n += f.n[q];
+        std::memcpy(g.t, f.t, sizeof g.t);
+        if (g.n) {
+          for (int b = 0; b < (g.n + kLmTile - 1) / kLmTile; ++b) blocks.push_back(make_int2((int)segs.size(), b));
+          segs.push_back(g);
+        }
+        src += g.n, at += g.n, pts_in += (uint64_t)g.n;
+      }
+    }
+  }
+  // one table upload: jobs | states | segments | blocks | tiles | job flags | chunks | splits
+  const size_t o_jobs = 0, o_states = align64(o_jobs + n * sizeof(LmJob)), o_segs = align64(o_states + n * sizeof(LmState)),
+               o_blocks = align64(o_segs + segs.size() * sizeof(LmSeg)), o_tiles = align64(o_blocks + blocks.size() * sizeof(int2)),
+               o_flags = align64(o_tiles + tiles.size() * sizeof(int2)), o_chunks = align64(o_flags + n * sizeof(int)),
+               o_splits = align64(o_chunks + chunks.size() * sizeof(ArChunk)), tab_bytes = align64(o_splits + splits.size() * sizeof(ArSplit));
+  int rc;
+  if ((rc = grow_pinned(ctx, &m->h_tab, &m->cap_htab, tab_bytes))) return rc;
+  if ((rc = grow_pinned(ctx, &m->h_states, &m->cap_hstates, n * sizeof(LmState)))) return rc;
+  auto put = [&](size_t o, const void* p, size_t bytes) {
+    if (bytes) std::memcpy(m->h_tab + o, p, bytes);
+  };
+  put(o_jobs, jobs.data(), n * sizeof(LmJob)), put(o_states, states.data(), n * sizeof(LmState));
+  put(o_segs, segs.data(), segs.size() * sizeof(LmSeg)), put(o_blocks, blocks.data(), blocks.size() * sizeof(int2));
+  put(o_tiles, tiles.data(), tiles.size() * sizeof(int2)), put(o_flags, jflags.data(), n * sizeof(int));
+  put(o_chunks, chunks.data(), chunks.size() * sizeof(ArChunk)), put(o_splits, splits.data(), splits.size() * sizeof(ArSplit));
+  if ((rc = grow(ctx, &m->d_tab, &m->cap_tab, tab_bytes)) || (rc = grow(ctx, &m->d_stage, &m->cap_stage, stage_total)) ||
+      (rc = grow(ctx, &m->d_out, &m->cap_out, out_total)) || (rc = grow(ctx, &m->d_hist, &m->cap_hist, vg_tiles * 256)) ||
+      (rc = grow(ctx, &m->d_tilecnt, &m->cap_tilecnt, tiles_total)) || (rc = grow(ctx, &m->d_csum, &m->cap_csum, chunks.size())))
+    return rc;
+  if (m->cap_sort < std::max<size_t>(sort_total, 1)) {  // the sort's scratch: the extent of the VoxelGrid jobs' staging
+    size_t c[5] = {0, 0, 0, 0, 0};
+    (void)hipFree(m->d_ka), (void)hipFree(m->d_kb), (void)hipFree(m->d_va), (void)hipFree(m->d_vb), (void)hipFree(m->d_starts);
+    m->d_ka = m->d_kb = nullptr, m->d_va = m->d_vb = m->d_starts = nullptr, m->cap_sort = 0;
+    if ((rc = grow(ctx, &m->d_ka, &c[0], sort_total)) || (rc = grow(ctx, &m->d_kb, &c[1], sort_total)) || (rc = grow(ctx, &m->d_va, &c[2], sort_total)) ||
+        (rc = grow(ctx, &m->d_vb, &c[3], sort_total)) || (rc = grow(ctx, &m->d_starts, &c[4], sort_total)))
+      return rc;
+    m->cap_sort = c[0];
+  }
+  hipStream_t st = ctx_stream(ctx);
+  hipEvent_t e0, e1;
+  ctx_events(ctx, &e0, &e1);
+  if (tab_bytes) HIP_TRY(ctx, hipMemcpyAsync(m->d_tab, m->h_tab, tab_bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipEventRecord(e0, st));
+  const LmJob* d_jobs = (const LmJob*)(m->d_tab + o_jobs);
+  LmState* d_states = (LmState*)(m->d_tab + o_states);
+  const int2* d_tiles = (const int2*)(m->d_tab + o_tiles);
+  const int* d_flags = (const int*)(m->d_tab + o_flags);
+  const ArChunk* d_chunks = (const ArChunk*)(m->d_tab + o_chunks);
+  const ArSplit* d_splits = (const ArSplit*)(m->d_tab + o_splits);
+  const int vt = (int)vg_tiles, ct = (int)(tiles_total - vg_tiles);
+  launch_ar_gather(st, (int)blocks.size(), (const LmSeg*)(m->d_tab + o_segs), (const int2*)(m->d_tab + o_blocks), m->d_arena, m->d_stage, d_states);
+  // the VoxelGrid jobs: the local-map build's kernels; the scans of the jobs [0, bound[1]) over many workgroups
+  launch_lm_setup(st, 0, nv, d_jobs, d_states);
+  launch_lm_keys(st, vt, d_tiles, d_jobs, d_states, m->d_stage, m->d_ka, m->d_va);
+  for (int p = 0; p < kLmPasses && vt; ++p) {
+    unsigned *kin = (p & 1) ? m->d_kb : m->d_ka, *kout = (p & 1) ? m->d_ka : m->d_kb;
+    int *vin = (p & 1) ? m->d_vb : m->d_va, *vout = (p & 1) ? m->d_va : m->d_vb;
+    launch_lm_hist(st, p, vt, d_tiles, d_jobs, d_states, kin, m->d_hist);
+    launch_lm_scan(st, p, bound[1], nv - bound[1], d_jobs, d_states, m->d_hist);
+    launch_ar_scan(st, 256, p, chunk, n_hist_chunks, d_chunks, bound[1], d_splits, d_jobs, d_states, m->d_hist, m->d_csum);
+    launch_lm_scatter(st, p, vt, d_tiles, d_jobs, d_states, m->d_hist, kin, vin, kout, vout);
+  }
+  launch_lm_heads(st, vt, d_tiles, d_jobs, d_states, m->d_ka, m->d_kb, m->d_tilecnt);
+  // the leaf == 0 jobs: keep counts per tile; then one scan of the per-tile counts for both kinds
+  launch_ar_keep(st, nv, n - nv, ct, d_tiles + vt, d_jobs, d_states, d_flags, m->d_stage, m->d_tilecnt);
+  launch_lm_heads_scan(st, bound[1], bound[3] - bound[1], d_jobs, d_states, m->d_tilecnt);
+  launch_ar_scan(st, 1, -1, chunk, (int)chunks.size(), d_chunks, (int)splits.size(), d_splits, d_jobs, d_states, m->d_tilecnt, m->d_csum);
+  launch_lm_starts(st, vt, d_tiles, d_jobs, d_states, m->d_ka, m->d_kb, m->d_tilecnt, m->d_starts);
+  launch_lm_sum(st, vt, d_tiles, d_jobs, d_states, m->d_va, m->d_vb, m->d_starts, m->d_stage, m->d_out);
+  launch_ar_compact(st, ct, d_tiles + vt, d_jobs, d_states, d_flags, m->d_stage, m->d_tilecnt, m->d_out);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(e1, st));
+  if (n) HIP_TRY(ctx, hipMemcpyAsync(m->h_states, d_states, n * sizeof(LmState), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  HIP_TRY(ctx, hipEventElapsedTime(&m->ms, e0, e1));
+  m->points_in = pts_in;
+  const LmState* S = (const LmState*)m->h_states;
+  m->off.assign(n, 0);
+  m->info.assign(n, lins_submap_info{});
+  for (int k = 0; k < n; ++k) {
+    const int j = job_of[k];
+    lins_submap_info& z = m->info[k];
+    z.status = S[j].status, z.frames = specs[k].n_ids, z.points_in = (uint64_t)cap[k];
+    z.n = z.status ? 0 : S[j].nvox;
+    m->off[k] = jobs[j].off_out;
+    const bool box = j < nv && z.n > 0;
+    for (int a = 0; a < 3; ++a) z.box_min[a] = box ? S[j].bmin[a] : 0, z.box_dim[a] = box ? S[j].bmax[a] - S[j].bmin[a] + 1 : 1;
+    if (out) out[k] = z;
+  }
+  m->built = true;
+  return LINS_OK;
+}
+
+int lins_archive_download(lins_ctx* ctx, int entry, lins_point* out, int cap) {
+  if (!ctx) return LINS_E_ARG;
+  Archive* m = archive_of(ctx);
+  if (!m->built) return LINS_E_STATE;
+  if (entry < 0 || entry >= (int)m->info.size()) return LINS_E_ARG;
+  const int cnt = m->info[entry].n;
+  if (cnt > cap) return LINS_E_CAPACITY;
+  if (cnt && !out) return LINS_E_ARG;
+  if (!cnt) return 0;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  hipStream_t st = ctx_stream(ctx);
+  HIP_TRY(ctx, hipMemcpyAsync(out, m->d_out + m->off[entry], (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return cnt;
+}
+
+int lins_last_archive_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* points_in) {
+  if (!ctx) return LINS_E_ARG;
+  Archive* m = archive_of(ctx);
+  if (kernel_ms) *kernel_ms = m->ms;
+  if (points_in) *points_in = m->points_in;
+  return LINS_OK;
+}
+
+}  // extern "C"

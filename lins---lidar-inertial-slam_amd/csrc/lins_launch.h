@@ -20,6 +20,8 @@ struct MapRoundParams;
 struct LmSeg;       // local_map.h
 struct LmJob;
 struct LmState;
+struct ArChunk;    // keyframe_archive.h
+struct ArSplit;
 
 // ---- ieskf_kernels.hip: the any-size update kernel (global-memory grid or exhaustive search), re-projection, copy probe
 void launch_persistent(hipStream_t stream, int n, const DevParams& prm, const ScanDesc* descs, const float4* arena, const double* state_in, const double* cov_in, double* state_out, double* cov_out,
@@ -85,5 +87,34 @@ void launch_lm_transform(hipStream_t s, int n_blocks, const LmSeg* segs, const i
 // one stage: jobs [j0, j0 + n_jobs), tiles [0, n_tiles) of `tiles`
 void launch_lm_stage(hipStream_t s, int j0, int n_jobs, int n_tiles, const int2* tiles, const LmJob* jobs, LmState* states, float4* stage, unsigned* keys_a, unsigned* keys_b, int* vals_a, int* vals_b,
                      int* hist, int* tilecnt, int* starts, float4* out);
+// the same kernels one by one (job kernels: jobs [j0, j0 + n_jobs); tile kernels: tiles [0, n_tiles) of `tiles`)
+void launch_lm_setup(hipStream_t s, int j0, int n_jobs, const LmJob* jobs, LmState* states);
+void launch_lm_keys(hipStream_t s, int n_tiles, const int2* tiles, const LmJob* jobs, const LmState* states, const float4* stage, unsigned* keys, int* vals);
+void launch_lm_hist(hipStream_t s, int pass, int n_tiles, const int2* tiles, const LmJob* jobs, const LmState* states, const unsigned* kin, int* hist);
+void launch_lm_scan(hipStream_t s, int pass, int j0, int n_jobs, const LmJob* jobs, const LmState* states, int* hist);
+void launch_lm_scatter(hipStream_t s, int pass, int n_tiles, const int2* tiles, const LmJob* jobs, const LmState* states, const int* hist, const unsigned* kin,
+                       const int* vin, unsigned* kout, int* vout);
+void launch_lm_heads(hipStream_t s, int n_tiles, const int2* tiles, const LmJob* jobs, const LmState* states, const unsigned* keys_a, const unsigned* keys_b,
+                     int* tilecnt);
+void launch_lm_heads_scan(hipStream_t s, int j0, int n_jobs, const LmJob* jobs, LmState* states, int* tilecnt);
+void launch_lm_starts(hipStream_t s, int n_tiles, const int2* tiles, const LmJob* jobs, const LmState* states, const unsigned* keys_a, const unsigned* keys_b,
+                      const int* tilecnt, int* starts);
+void launch_lm_sum(hipStream_t s, int n_tiles, const int2* tiles, const LmJob* jobs, LmState* states, const int* vals_a, const int* vals_b, const int* starts,
+                   float4* stage, float4* out);
+
+// ---- archive_kernels.hip: the key-frame archive's assembly (keyframe_archive.h)
+// gather-transform from the archive arena into the staging arena, f32 box folded once per workgroup
+void launch_ar_gather(hipStream_t s, int n_blocks, const LmSeg* segs, const int2* blocks, const float4* arena, float4* stage, LmState* states);
+// the scan of lm_scan_kernel / lm_heads_scan_kernel over many workgroups, for the jobs the chunk tables name: `rows` x
+// tiles counts per job at data + tile0 * rows (256: a radix pass's histogram, pass < the job's passes; 1: the per-tile
+// counts, pass = -1, the total goes to the job's nvox), in chunks of rows * chunk_tiles elements of the digit-major row
+void launch_ar_scan(hipStream_t s, int rows, int pass, int chunk_tiles, int n_chunks, const ArChunk* chunks, int n_splits, const ArSplit* splits,
+                    const LmJob* jobs, LmState* states, int* data, int* csum);
+// leaf == 0 jobs [j0, j0 + n_jobs), their tiles [0, n_tiles) of `tiles`: status, per-tile keep counts; then (behind the
+// scan of the counts) the stable scatter of the kept points to out.  jflags[job] & 1: keep only (int)intensity >= 0
+void launch_ar_keep(hipStream_t s, int j0, int n_jobs, int n_tiles, const int2* tiles, const LmJob* jobs, LmState* states, const int* jflags,
+                    const float4* stage, int* tilecnt);
+void launch_ar_compact(hipStream_t s, int n_tiles, const int2* tiles, const LmJob* jobs, const LmState* states, const int* jflags, const float4* stage,
+                       const int* tilecnt, float4* out);
 
 }  // namespace lins

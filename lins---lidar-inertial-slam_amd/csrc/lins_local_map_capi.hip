@@ -123,7 +123,7 @@ namespace lins {
 int local_map_view(lins_ctx* ctx, LocalMapView* v) {
   LocalMap* m = local_of(ctx);
   if (!m->built) return LINS_E_STATE;
-  v->d_out = m->d_out, v->n = (int)m->slots.size(), v->off = m->off.data(), v->sizes = m->sizes.data();
+  v->d_out = m->d_out, v->n = (int)m->slots.size(), v->off = m->off.data(), v->sizes = m->sizes.data(), v->slots = m->slots.data();
   return LINS_OK;
 }
 }  // namespace lins

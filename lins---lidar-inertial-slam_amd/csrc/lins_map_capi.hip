@@ -48,6 +48,9 @@ struct MapState {
   // the local-map state of lins_local_map_* (lins_local_map_capi.hip), freed with this one
   void* local = nullptr;
   void (*local_free)(void*) = nullptr;
+  // the key-frame archive of lins_archive_* (lins_archive_capi.hip), likewise
+  void* archive = nullptr;
+  void (*archive_free)(void*) = nullptr;
 };
 
 void map_state_free(void* p) {
@@ -56,6 +59,7 @@ void map_state_free(void* p) {
   (void)hipFree(m->d_partials), (void)hipFree(m->d_probs), (void)hipFree(m->d_rounds), (void)hipFree(m->d_jobs);
   (void)hipFree(m->d_carry), (void)hipFree(m->d_results), (void)hipHostFree(m->h_q);
   if (m->local) m->local_free(m->local);
+  if (m->archive) m->archive_free(m->archive);
   delete m;
 }
 
@@ -302,6 +306,11 @@ void** map_local_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
   MapState* m = state_of(ctx);
   m->local_free = free_fn;
   return &m->local;
+}
+void** map_archive_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
+  MapState* m = state_of(ctx);
+  m->archive_free = free_fn;
+  return &m->archive;
 }
 }  // namespace lins
 

@@ -70,8 +70,10 @@ struct LocalMapView {
   int n;
   const long long* off;
   const lins_local_map_sizes* sizes;
+  const int* slots;  // the slot of entry k
 };
 int local_map_view(lins_ctx* ctx, LocalMapView* v);
 void** map_local_slot(lins_ctx* ctx, void (*free_fn)(void*));  // lins_map_capi.hip: held by the scan-to-map state
+void** map_archive_slot(lins_ctx* ctx, void (*free_fn)(void*));  // ... and the key-frame archive's (lins_archive_capi.hip)
 
 }  // namespace lins

@@ -294,25 +294,59 @@ void launch_lm_transform(hipStream_t s, int n_blocks, const LmSeg* segs, const i
     hipLaunchKernelGGL(lm_transform_kernel, dim3(n_blocks), dim3(kLmTile), 0, s, segs, blocks, frames, stage, states);
 }
 
+// the kernels of a stage one by one (what launch_lm_stage runs; the key-frame archive runs the same kernels around its
+// own scans, lins_archive_capi.hip): the job kernels over jobs [j0, j0 + n_jobs), the tile kernels over tiles [0, n_tiles)
+void launch_lm_setup(hipStream_t s, int j0, int n_jobs, const LmJob* jobs, LmState* states) {
+  if (n_jobs) hipLaunchKernelGGL(lm_setup_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, s, j0, n_jobs, jobs, states);
+}
+void launch_lm_keys(hipStream_t s, int n_tiles, const int2* tiles, const LmJob* jobs, const LmState* states, const float4* stage, unsigned* keys, int* vals) {
+  if (n_tiles) hipLaunchKernelGGL(lm_keys_kernel, dim3(n_tiles), dim3(kLmTile), 0, s, tiles, jobs, states, stage, keys, vals);
+}
+void launch_lm_hist(hipStream_t s, int pass, int n_tiles, const int2* tiles, const LmJob* jobs, const LmState* states, const unsigned* kin, int* hist) {
+  if (n_tiles) hipLaunchKernelGGL(lm_hist_kernel, dim3(n_tiles), dim3(kLmTile), 0, s, pass, tiles, jobs, states, kin, hist);
+}
+void launch_lm_scan(hipStream_t s, int pass, int j0, int n_jobs, const LmJob* jobs, const LmState* states, int* hist) {
+  if (n_jobs) hipLaunchKernelGGL(lm_scan_kernel, dim3(n_jobs), dim3(kLmTile), 0, s, pass, j0, jobs, states, hist);
+}
+void launch_lm_scatter(hipStream_t s, int pass, int n_tiles, const int2* tiles, const LmJob* jobs, const LmState* states, const int* hist, const unsigned* kin,
+                       const int* vin, unsigned* kout, int* vout) {
+  if (n_tiles) hipLaunchKernelGGL(lm_scatter_kernel, dim3(n_tiles), dim3(kLmTile), 0, s, pass, tiles, jobs, states, hist, kin, vin, kout, vout);
+}
+void launch_lm_heads(hipStream_t s, int n_tiles, const int2* tiles, const LmJob* jobs, const LmState* states, const unsigned* keys_a, const unsigned* keys_b,
+                     int* tilecnt) {
+  if (n_tiles) hipLaunchKernelGGL(lm_heads_kernel, dim3(n_tiles), dim3(kLmTile), 0, s, tiles, jobs, states, keys_a, keys_b, tilecnt);
+}
+void launch_lm_heads_scan(hipStream_t s, int j0, int n_jobs, const LmJob* jobs, LmState* states, int* tilecnt) {
+  if (n_jobs) hipLaunchKernelGGL(lm_heads_scan_kernel, dim3(n_jobs), dim3(kLmTile), 0, s, j0, jobs, states, tilecnt);
+}
+void launch_lm_starts(hipStream_t s, int n_tiles, const int2* tiles, const LmJob* jobs, const LmState* states, const unsigned* keys_a, const unsigned* keys_b,
+                      const int* tilecnt, int* starts) {
+  if (n_tiles) hipLaunchKernelGGL(lm_starts_kernel, dim3(n_tiles), dim3(kLmTile), 0, s, tiles, jobs, states, keys_a, keys_b, tilecnt, starts);
+}
+void launch_lm_sum(hipStream_t s, int n_tiles, const int2* tiles, const LmJob* jobs, LmState* states, const int* vals_a, const int* vals_b, const int* starts,
+                   float4* stage, float4* out) {
+  if (n_tiles) hipLaunchKernelGGL(lm_sum_kernel, dim3(n_tiles), dim3(kLmTile), 0, s, tiles, jobs, states, vals_a, vals_b, starts, stage, out);
+}
+
 // one stage: jobs [j0, j0 + n_jobs), tiles [0, n_tiles) of `tiles`
 void launch_lm_stage(hipStream_t s, int j0, int n_jobs, int n_tiles, const int2* tiles, const LmJob* jobs, LmState* states,
                      float4* stage, unsigned* keys_a, unsigned* keys_b, int* vals_a, int* vals_b, int* hist, int* tilecnt,
                      int* starts, float4* out) {
   if (!n_jobs) return;
-  hipLaunchKernelGGL(lm_setup_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, s, j0, n_jobs, jobs, states);
+  launch_lm_setup(s, j0, n_jobs, jobs, states);
   if (!n_tiles) return;
-  hipLaunchKernelGGL(lm_keys_kernel, dim3(n_tiles), dim3(kLmTile), 0, s, tiles, jobs, states, stage, keys_a, vals_a);
+  launch_lm_keys(s, n_tiles, tiles, jobs, states, stage, keys_a, vals_a);
   for (int p = 0; p < kLmPasses; ++p) {
     unsigned *kin = (p & 1) ? keys_b : keys_a, *kout = (p & 1) ? keys_a : keys_b;
     int *vin = (p & 1) ? vals_b : vals_a, *vout = (p & 1) ? vals_a : vals_b;
-    hipLaunchKernelGGL(lm_hist_kernel, dim3(n_tiles), dim3(kLmTile), 0, s, p, tiles, jobs, states, kin, hist);
-    hipLaunchKernelGGL(lm_scan_kernel, dim3(n_jobs), dim3(kLmTile), 0, s, p, j0, jobs, states, hist);
-    hipLaunchKernelGGL(lm_scatter_kernel, dim3(n_tiles), dim3(kLmTile), 0, s, p, tiles, jobs, states, hist, kin, vin, kout, vout);
+    launch_lm_hist(s, p, n_tiles, tiles, jobs, states, kin, hist);
+    launch_lm_scan(s, p, j0, n_jobs, jobs, states, hist);
+    launch_lm_scatter(s, p, n_tiles, tiles, jobs, states, hist, kin, vin, kout, vout);
   }
-  hipLaunchKernelGGL(lm_heads_kernel, dim3(n_tiles), dim3(kLmTile), 0, s, tiles, jobs, states, keys_a, keys_b, tilecnt);
-  hipLaunchKernelGGL(lm_heads_scan_kernel, dim3(n_jobs), dim3(kLmTile), 0, s, j0, jobs, states, tilecnt);
-  hipLaunchKernelGGL(lm_starts_kernel, dim3(n_tiles), dim3(kLmTile), 0, s, tiles, jobs, states, keys_a, keys_b, tilecnt, starts);
-  hipLaunchKernelGGL(lm_sum_kernel, dim3(n_tiles), dim3(kLmTile), 0, s, tiles, jobs, states, vals_a, vals_b, starts, stage, out);
+  launch_lm_heads(s, n_tiles, tiles, jobs, states, keys_a, keys_b, tilecnt);
+  launch_lm_heads_scan(s, j0, n_jobs, jobs, states, tilecnt);
+  launch_lm_starts(s, n_tiles, tiles, jobs, states, keys_a, keys_b, tilecnt, starts);
+  launch_lm_sum(s, n_tiles, tiles, jobs, states, vals_a, vals_b, starts, stage, out);
 }
 
 }  // namespace lins

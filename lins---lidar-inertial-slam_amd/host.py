@@ -212,6 +212,69 @@ def local_map(frames, scan, window=50):
     return [o[:n].copy() for o, n in zip(outs, d["n"])], d
 
 
+def _key_poses(poses):
+    from ._ctypes_defs import KeyPoseC, key_pose
+
+    return (KeyPoseC * max(len(poses), 1))(*[key_pose(p) for p in poses])
+
+
+def select_radius(poses, centre, radius, pose_leaf):
+    """lins_host_select_radius: publishGlobalMap's choice of frames (LM:989-1007) among key poses (x, y, z, roll, pitch,
+    yaw) by frame id -> the selected ids in the order the frames are visited"""
+    from ._ctypes_defs import KeyPoseC
+
+    L = lib()
+    ids = np.zeros(max(len(poses), 1), np.int32)
+    c = (C.c_float * 3)(*[float(v) for v in centre])
+    L.lins_host_select_radius.argtypes = [C.POINTER(KeyPoseC), C.c_int, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_void_p, C.c_int]
+    L.lins_host_select_radius.restype = C.c_int
+    rc = L.lins_host_select_radius(_key_poses(poses), len(poses), c, float(radius), float(pose_leaf), ids.ctypes.data, len(poses))
+    if rc < 0:
+        raise RuntimeError(f"lins_host_select_radius: {rc}")
+    return ids[:rc].copy()
+
+
+def find_loop(poses, times, centre, radius, now, min_gap_s):
+    """lins_host_find_loop: detectLoopClosure's candidate (LM:1050-1067) -> frame id or -1"""
+    from ._ctypes_defs import KeyPoseC
+
+    L = lib()
+    t = np.ascontiguousarray(times, np.float64)
+    c = (C.c_float * 3)(*[float(v) for v in centre])
+    out = C.c_int32(-2)
+    L.lins_host_find_loop.argtypes = [C.POINTER(KeyPoseC), C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_double, C.c_double,
+                                      C.POINTER(C.c_int32)]
+    L.lins_host_find_loop.restype = C.c_int
+    rc = L.lins_host_find_loop(_key_poses(poses), t.ctypes.data, len(poses), c, float(radius), float(now), float(min_gap_s), C.byref(out))
+    if rc != 0:
+        raise RuntimeError(f"lins_host_find_loop: {rc}")
+    return int(out.value)
+
+
+def submap(frames, ids, clouds, leaf, flags=0):
+    """lins_host_submap: the CPU restatement of one lins_archive_assemble spec.  frames: [(corner, surf, outlier, pose)]
+    by frame id.  Returns (cloud (n, 4) f32, info dict)."""
+    from ._ctypes_defs import KeyframeC, SubmapInfoC, keyframe_c
+
+    L = lib()
+    fr, keep = (KeyframeC * max(len(frames), 1))(), []
+    for k, f in enumerate(frames):
+        fr[k], kk = keyframe_c(*f)
+        keep.append(kk)
+    idv = np.ascontiguousarray(ids, np.int32)
+    cap = sum(len(frames[i][q]) for i in idv if 0 <= i < len(frames) for q in range(3) if clouds & (1 << q) and clouds > 0)
+    out = np.zeros((max(cap, 1), 4), np.float32)
+    info = SubmapInfoC()
+    L.lins_host_submap.argtypes = [C.POINTER(KeyframeC), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p,
+                                   C.POINTER(SubmapInfoC)]
+    L.lins_host_submap.restype = C.c_int
+    rc = L.lins_host_submap(fr, len(frames), idv.ctypes.data, len(idv), int(clouds), float(leaf), int(flags), out.ctypes.data, C.byref(info))
+    if rc != 0:
+        raise RuntimeError(f"lins_host_submap: {rc}")
+    d = info.as_dict()
+    return out[:d["n"]].copy(), d
+
+
 def _buf(n):
     a = np.zeros((n, 4), dtype=np.float32)
     return a, a.ctypes.data_as(C.POINTER(Point))

@@ -27,6 +27,9 @@ EXPORTS = [
     "lins_rccl_unique_id", "lins_rccl_init", "lins_pose_allgather", "lins_rccl_destroy", "lins_last_index_ms", "lins_last_cut",
     "lins_batch_map", "lins_local_map_init", "lins_local_map_push", "lins_local_map_build", "lins_local_map_push_scans",
     "lins_local_map_set_pose", "lins_local_map_download", "lins_last_local_map_stats",
+    "lins_archive_init", "lins_archive_push", "lins_archive_push_scans", "lins_archive_set_poses", "lins_archive_count",
+    "lins_archive_select_radius", "lins_archive_find_loop", "lins_archive_assemble", "lins_archive_download",
+    "lins_last_archive_stats", "lins_archive_set_scan_chunk",
 ]
 
 
@@ -283,6 +286,117 @@ class IeskfContext:
         L.lins_last_local_map_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
         self._check(L.lins_last_local_map_stats(self._h, C.byref(ms), C.byref(pts)))
         return ms.value, pts.value
+
+    # -- the key-frame archive on the device (include/lins_map.h lins_archive_*) --------------------
+    def _rc(self, rc):
+        """a call that returns a count / id (>= 0) or an error"""
+        if rc < 0:
+            self._check(rc)
+        return rc
+
+    def archive_init(self, n_slots, max_frames_per_slot, max_points_total):
+        L = lib()
+        L.lins_archive_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_longlong]
+        self._check(L.lins_archive_init(self._h, int(n_slots), int(max_frames_per_slot), int(max_points_total)))
+
+    def archive_push(self, slot, corner, surf, outlier, pose, time=0.0):
+        """one key frame behind the frames of `slot`; returns its id"""
+        from ._ctypes_defs import KeyframeC, keyframe_c
+
+        f, _keep = keyframe_c(corner, surf, outlier, pose)
+        L = lib()
+        L.lins_archive_push.argtypes = [C.c_void_p, C.c_int, C.POINTER(KeyframeC), C.c_double]
+        return self._rc(L.lins_archive_push(self._h, int(slot), C.byref(f), float(time)))
+
+    def archive_push_scans(self, entries, poses, times):
+        """cornerDS / surfDS / outlierDS of entries of the last local_map_build become frames of their slots; returns the ids"""
+        from ._ctypes_defs import KeyPoseC, key_pose
+
+        n = len(entries)
+        e = np.ascontiguousarray(entries, dtype=np.int32)
+        t = np.ascontiguousarray(times, dtype=np.float64)
+        ps = (KeyPoseC * max(n, 1))(*[key_pose(p) for p in poses])
+        ids = np.full(max(n, 1), -1, np.int32)
+        L = lib()
+        L.lins_archive_push_scans.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(KeyPoseC), C.c_void_p, C.c_void_p]
+        self._check(L.lins_archive_push_scans(self._h, n, e.ctypes.data, ps, t.ctypes.data, ids.ctypes.data))
+        return ids[:n].tolist()
+
+    def archive_set_poses(self, slot, first_id, poses):
+        """correctPoses: the poses of frames first_id .. first_id + len(poses) - 1 of `slot`"""
+        from ._ctypes_defs import KeyPoseC, key_pose
+
+        ps = (KeyPoseC * max(len(poses), 1))(*[key_pose(p) for p in poses])
+        L = lib()
+        L.lins_archive_set_poses.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(KeyPoseC)]
+        self._check(L.lins_archive_set_poses(self._h, int(slot), int(first_id), len(poses), ps))
+
+    def archive_count(self, slot):
+        L = lib()
+        L.lins_archive_count.argtypes = [C.c_void_p, C.c_int]
+        return self._rc(L.lins_archive_count(self._h, int(slot)))
+
+    def archive_select_radius(self, slot, centre, radius, pose_leaf):
+        """publishGlobalMap's choice of frames (LM:989-1007): ids in the order the frames are visited"""
+        L = lib()
+        cap = max(self.archive_count(slot), 1)
+        ids = np.zeros(cap, np.int32)
+        c = (C.c_float * 3)(*[float(v) for v in centre])
+        L.lins_archive_select_radius.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_void_p, C.c_int]
+        n = self._rc(L.lins_archive_select_radius(self._h, int(slot), c, float(radius), float(pose_leaf), ids.ctypes.data, cap))
+        return ids[:n].copy()
+
+    def archive_find_loop(self, slot, centre, radius, now, min_gap_s):
+        """detectLoopClosure's candidate (LM:1050-1067): frame id or -1"""
+        L = lib()
+        c = (C.c_float * 3)(*[float(v) for v in centre])
+        out = C.c_int32(-2)
+        L.lins_archive_find_loop.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_double, C.c_double, C.POINTER(C.c_int32)]
+        self._check(L.lins_archive_find_loop(self._h, int(slot), c, float(radius), float(now), float(min_gap_s), C.byref(out)))
+        return int(out.value)
+
+    def archive_assemble(self, specs):
+        """specs: dicts / tuples (slot, ids, clouds, leaf, flags).  Returns the per-spec info dicts (n, frames, points_in,
+        box_min, box_dim, status); the clouds stay on the device (archive_download)."""
+        from ._ctypes_defs import SubmapInfoC, SubmapSpecC
+
+        n = len(specs)
+        arr, keep = (SubmapSpecC * max(n, 1))(), []
+        for k, sp in enumerate(specs):
+            slot, ids, clouds, leaf, flags = (sp["slot"], sp["ids"], sp["clouds"], sp["leaf"], sp.get("flags", 0)) if isinstance(sp, dict) else sp
+            idv = np.ascontiguousarray(ids, dtype=np.int32)
+            keep.append(idv)
+            arr[k] = SubmapSpecC(idv.ctypes.data_as(C.POINTER(C.c_int32)), len(idv), int(slot), int(clouds), int(flags), float(leaf), 0)
+        out = (SubmapInfoC * max(n, 1))()
+        L = lib()
+        L.lins_archive_assemble.argtypes = [C.c_void_p, C.c_int, C.POINTER(SubmapSpecC), C.POINTER(SubmapInfoC)]
+        self._archive_info = []
+        self._check(L.lins_archive_assemble(self._h, n, arr, out))
+        self._archive_info = [out[k].as_dict() for k in range(n)]
+        return self._archive_info
+
+    def archive_download(self, entry):
+        """the cloud of entry `entry` of the last assembly, (n, 4) f32"""
+        info = getattr(self, "_archive_info", [])
+        cap = info[entry]["n"] if 0 <= entry < len(info) else 0
+        out = np.zeros((max(cap, 1), 4), np.float32)
+        L = lib()
+        L.lins_archive_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        n = self._rc(L.lins_archive_download(self._h, int(entry), out.ctypes.data, int(cap)))
+        return out[:n].copy()
+
+    def archive_stats(self):
+        ms, pts = C.c_float(0), C.c_uint64(0)
+        L = lib()
+        L.lins_last_archive_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+        self._check(L.lins_last_archive_stats(self._h, C.byref(ms), C.byref(pts)))
+        return ms.value, pts.value
+
+    def archive_set_scan_chunk(self, chunk_tiles):
+        """test hook: jobs above chunk_tiles tiles have their scans split over workgroups (0: default, 2**31 - 1: never)"""
+        L = lib()
+        L.lins_archive_set_scan_chunk.argtypes = [C.c_void_p, C.c_int]
+        self._check(L.lins_archive_set_scan_chunk(self._h, int(chunk_tiles)))
 
     # -- image_projection_node on the device: raw clouds -> segmented scans --------------------
     def segment_batch(self, raws):
