@@ -222,6 +222,35 @@ int lins_host_find_loop(const lins_key_pose* poses, const double* times, int n, 
 int lins_host_submap(const lins_keyframe* frames, int n_frames, const int32_t* ids, int n_ids, int clouds, float leaf,
                      int flags, lins_point* out, lins_submap_info* info);
 
+/* ---- the loop-closure ICP on the CPU (host/loop_icp.cpp) ---------------------
+ * The restatement lins_loop_icp_batch / lins_loop_icp_correspondences are checked against (include/lins_map.h has the
+ * contract; the arithmetic is csrc/loop_icp_math.h in both libraries, the search here is the exhaustive one).  Clouds:
+ * finite, |coord| <= 1e6 (LINS_E_INPUT).  lins_loop_icp_default_params is exported by this library too. */
+typedef struct lins_loop_icp_round { /* one round of the loop, for the trace */
+  double T_in[16];  /* T entering the round */
+  double delta[16]; /* the round's fit (identity when it stopped for too few correspondences) */
+  double T_out[16]; /* T leaving it */
+  double mse;
+  double stop[4];   /* 0.5 (trace R_delta - 1), |t_delta|^2, |mse - mse_prev|, |mse - mse_prev| / mse_prev */
+  int32_t n_corr;
+  int32_t reason;   /* LINS_ICP_NONE: the loop went on */
+} lins_loop_icp_round;
+/* max_rounds: 0, or the loop stops after that many rounds as under lins_debug_loop_icp_rounds */
+int lins_host_loop_icp(const lins_point* source, int n_source, const lins_point* target, int n_target, const lins_loop_icp_params* prm,
+                       int max_rounds, lins_loop_icp_result* out);
+/* the same with every round recorded (the first cap_rounds of them); returns the number of rounds run or an error */
+int lins_host_loop_icp_trace(const lins_point* source, int n_source, const lins_point* target, int n_target, const lins_loop_icp_params* prm,
+                             lins_loop_icp_round* rounds, int cap_rounds, lins_loop_icp_result* out);
+/* steps 1-2 at T by exhaustive search (cap <= 0: none): index (-1: none) and d (0 where none) per source point */
+int lins_host_loop_icp_correspondences(const lins_point* source, int n_source, const lins_point* target, int n_target, const double T[16],
+                                       float cap, int32_t* idx, float* sqdist);
+/* LM:1156-1166, all f32: T -> (x, y, z, roll, pitch, yaw) by roll = atan2(T21, T22), pitch = asin(-T20), yaw =
+ * atan2(T10, T00); correctionLidar = getTransformation(z, x, y, yaw, roll, pitch); tWrong = getTransformation(wrong.z,
+ * wrong.x, wrong.y, wrong.yaw, wrong.roll, wrong.pitch); pose_from = the same extraction of correctionLidar * tWrong.
+ * getTransformation(x, y, z, roll, pitch, yaw) = Rz(yaw) Ry(pitch) Rx(roll) with translation (x, y, z).  The factor
+ * graph stays with the caller. */
+int lins_host_loop_pose_from(const double T[16], const lins_key_pose* wrong, lins_key_pose* pose_from);
+
 #ifdef __cplusplus
 }
 #endif

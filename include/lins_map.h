@@ -222,6 +222,76 @@ int lins_last_archive_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* points_in
  * workgroups above it.  0: the default; INT_MAX: never split.  Results are the same bits for every value. */
 int lins_archive_set_scan_chunk(lins_ctx* ctx, int chunk_tiles);
 
+/* ---- loop-closure alignment: ICP over the archive's submaps (performLoopClosure, LM:1114-1186) ----------------------
+ * pcl::IterativeClosestPoint as the mapping node sets it up (LM:1128-1132), restated with a fixed operation sequence:
+ * the project's contract ("Loop-closure ICP"), one scalar definition in csrc/loop_icp_math.h compiled
+ * into both libraries.  Source S (ns points), target G (ng points, index = position in the cloud as
+ * lins_archive_download returns it).  T_0 = identity (row-major 4 x 4, f64), mse_prev = DBL_MAX.  Round k:
+ *   1 move       M = T_k rounded entry by entry to f32; x' = ((m00 x + m01 y) + m02 z) + m03 (f32, uncontracted; y', z'
+ *                alike), from the ORIGINAL source point every round
+ *   2 correspond the target of smallest (d, index), d = (dx dx + dy dy) + dz dz in f32; it counts iff
+ *                d <= max_corr_dist * max_corr_dist (f32).  Exact: the exhaustive search's answer, ties by index
+ *   3 too few    fewer than min_correspondences: stop, converged = 0, LINS_ICP_NO_CORRESPONDENCES, T kept
+ *   4 fit        Kabsch in f64 from the sums n, S x', S g, S x' g^T (tiles of 32 source points: the tree
+ *                ((q0+q4)+(q2+q6))+((q1+q5)+(q3+q7)) over each 8 consecutive points, the four eights in order, the tiles
+ *                in order); 3 x 3 SVD by one-sided cyclic Jacobi, fixed sweep count
+ *   5 compose    T_{k+1} = Delta T_k in f64
+ *   6 stop       (a) k + 1 >= max_iterations  (b) 0.5 (trace R_Delta - 1) >= rotation_threshold and |t_Delta|^2 <=
+ *                transformation_epsilon  (c) |mse - mse_prev| < fitness_epsilon  (d) |mse - mse_prev| / mse_prev < rel_mse;
+ *                the first that holds stops (converged = 1); then mse_prev = mse.  mse: f64 mean of the counted d
+ * After the loop one more pass of 1-2 at the final T without the distance cap: fitness = f64 mean of d over the source
+ * points that found a target (n_fitness of them; DBL_MAX when none).  The caller applies converged && fitness <= 0.3
+ * (LM:1140-1141).  */
+#define LINS_ICP_NONE 0               /* still running (only seen with lins_debug_loop_icp_rounds) */
+#define LINS_ICP_ITERATIONS 1
+#define LINS_ICP_TRANSFORM 2
+#define LINS_ICP_ABS_MSE 3
+#define LINS_ICP_REL_MSE 4
+#define LINS_ICP_NO_CORRESPONDENCES 5
+
+typedef struct lins_loop_icp_params {
+  double transformation_epsilon; /* 1e-6 (LM:1130) */
+  double fitness_epsilon;        /* 1e-6 (LM:1131) */
+  double rel_mse;                /* 1e-5: DefaultConvergenceCriteria's relative bound */
+  double rotation_threshold;     /* 0.99999 */
+  float max_corr_dist;           /* 100 (LM:1128) */
+  int32_t max_iterations;        /* 100 (LM:1129) */
+  int32_t min_correspondences;   /* 3 */
+  int32_t reserved;
+} lins_loop_icp_params;
+void lins_loop_icp_default_params(lins_loop_icp_params* p);
+
+typedef struct lins_loop_icp_problem { /* clouds: entries of the LAST lins_archive_assemble, read where they lie ... */
+  int32_t source_entry, target_entry;  /* ... or -1: the host clouds below are uploaded */
+  const lins_point* source;
+  const lins_point* target;
+  int32_t n_source, n_target;
+} lins_loop_icp_problem;
+
+typedef struct lins_loop_icp_result {
+  double transform[16]; /* T, row-major */
+  double fitness;       /* the fitness score (DBL_MAX: no source point found a target) */
+  double mse;           /* the last round's mse */
+  int32_t iterations, converged, reason, n_corr, n_fitness;
+  uint32_t far_searches; /* queries, over every round and the fitness pass, that were finished by the whole-target scan */
+  int32_t status;        /* LINS_OK; LINS_E_CAPACITY: a target box of more than 2^26 one-metre cells (nothing was run) */
+  int32_t reserved;
+} lins_loop_icp_result;
+
+/* Input contract: host clouds finite, |coord| <= 1e6 (LINS_E_INPUT: nothing is run, the context stays usable).  Entry
+ * problems: LINS_E_STATE without a prior assembly, LINS_E_ARG for a bad entry; an entry whose assembly failed (its
+ * status) is an empty cloud.  An empty source or target gives LINS_ICP_NO_CORRESPONDENCES at iteration 0.  A problem's
+ * result bits do not depend on the batch it is in.
+ * Device sequence: every target is gridded once into 1 m cells; per round one search + sums kernel and one step kernel
+ * (one wave per problem: sums in tile order, fit, compose, stop rule, the next round's M), queued back to back in
+ * groups with one word "problems still running" read between the groups; then the fitness pass. */
+int lins_loop_icp_batch(lins_ctx* ctx, int n, const lins_loop_icp_problem* in, const lins_loop_icp_params* prm, lins_loop_icp_result* out);
+/* one pass of steps 1-2 at a given T (cap as max_corr_dist; cap <= 0: none): index (-1: none) and d per source point */
+int lins_loop_icp_correspondences(lins_ctx* ctx, const lins_loop_icp_problem* in, const double T[16], float cap, int32_t* idx, float* sqdist);
+/* HIP-event time (ms) of the device sequence of the last of the two calls above (gridding excluded) and the query
+ * evaluations it did */
+int lins_last_loop_icp_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* searches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -310,3 +310,68 @@ class SubmapInfoC(C.Structure):
     def as_dict(self):
         return dict(n=int(self.n), frames=int(self.frames), points_in=int(self.points_in), box_min=list(self.box_min),
                     box_dim=list(self.box_dim), status=int(self.status))
+
+
+# ---- the loop-closure ICP (include/lins_map.h lins_loop_icp_*, include/lins_host.h lins_host_loop_icp*) --------
+ICP_NONE, ICP_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE, ICP_NO_CORRESPONDENCES = range(6)
+
+
+class LoopIcpParamsC(C.Structure):
+    _fields_ = [("transformation_epsilon", C.c_double), ("fitness_epsilon", C.c_double), ("rel_mse", C.c_double),
+                ("rotation_threshold", C.c_double), ("max_corr_dist", C.c_float), ("max_iterations", C.c_int32),
+                ("min_correspondences", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LoopIcpProblemC(C.Structure):
+    _fields_ = [("source_entry", C.c_int32), ("target_entry", C.c_int32), ("source", C.POINTER(Point)), ("target", C.POINTER(Point)),
+                ("n_source", C.c_int32), ("n_target", C.c_int32)]
+
+
+class LoopIcpResultC(C.Structure):
+    _fields_ = [("transform", C.c_double * 16), ("fitness", C.c_double), ("mse", C.c_double), ("iterations", C.c_int32),
+                ("converged", C.c_int32), ("reason", C.c_int32), ("n_corr", C.c_int32), ("n_fitness", C.c_int32),
+                ("far_searches", C.c_uint32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return dict(transform=np.array(self.transform[:], np.float64).reshape(4, 4), fitness=float(self.fitness), mse=float(self.mse),
+                    iterations=int(self.iterations), converged=int(self.converged), reason=int(self.reason), n_corr=int(self.n_corr),
+                    n_fitness=int(self.n_fitness), far_searches=int(self.far_searches), status=int(self.status))
+
+
+class LoopIcpRoundC(C.Structure):
+    _fields_ = [("T_in", C.c_double * 16), ("delta", C.c_double * 16), ("T_out", C.c_double * 16), ("mse", C.c_double),
+                ("stop", C.c_double * 4), ("n_corr", C.c_int32), ("reason", C.c_int32)]
+
+    def as_dict(self):
+        m = lambda a: np.array(a[:], np.float64).reshape(4, 4)
+        return dict(T_in=m(self.T_in), delta=m(self.delta), T_out=m(self.T_out), mse=float(self.mse),
+                    stop=np.array(self.stop[:], np.float64), n_corr=int(self.n_corr), reason=int(self.reason))
+
+
+def loop_icp_params(lib, **kw):
+    """lins_loop_icp_default_params of `lib` (both libraries export it) with fields overridden by keyword"""
+    p = LoopIcpParamsC()
+    lib.lins_loop_icp_default_params.argtypes = [C.POINTER(LoopIcpParamsC)]
+    lib.lins_loop_icp_default_params.restype = None
+    lib.lins_loop_icp_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def loop_icp_problem_c(source, target):
+    """lins_loop_icp_problem: each cloud an int (entry of the last archive assembly) or an (n, 4) array; returns
+    (struct, the arrays it points into)"""
+    c, keep = LoopIcpProblemC(), []
+    c.source_entry = c.target_entry = -1
+    for name, v in (("source", source), ("target", target)):
+        if isinstance(v, (int, np.integer)):
+            setattr(c, name + "_entry", int(v))
+        else:
+            a = cloud(v)
+            keep.append(a)
+            setattr(c, name, a.ctypes.data_as(C.POINTER(Point)))
+            setattr(c, "n_" + name, len(a))
+    return c, keep

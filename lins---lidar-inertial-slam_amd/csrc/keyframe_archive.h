@@ -28,4 +28,16 @@ struct ArSplit {  // one split job
 };
 static_assert(sizeof(ArSplit) == 16, "ArSplit layout");
 
+// (host side) the clouds of the last assembly where the loop-closure ICP reads them: cloud k starts at d_out + off[k]
+// and holds info[k].n points; filtered[k]: it went through VoxelGrid, so info[k] carries its 1 m box.  LINS_E_STATE
+// when there was no assembly.
+struct ArchiveView {
+  const float4* d_out;
+  int n;
+  const long long* off;
+  const lins_submap_info* info;
+  const char* filtered;
+};
+int archive_view(lins_ctx* ctx, ArchiveView* v);  // lins_archive_capi.hip
+
 }  // namespace lins

@@ -46,6 +46,7 @@ struct Archive {
   bool built = false;
   std::vector<long long> off;
   std::vector<lins_submap_info> info;
+  std::vector<char> filtered;  // per entry: a VoxelGrid output (its info carries the 1 m box)
   float ms = 0.f;
   uint64_t points_in = 0;
 };
@@ -100,6 +101,15 @@ std::vector<lins_key_pose> poses_of(const std::vector<ArFrame>& fr) {
 }
 
 }  // namespace
+
+namespace lins {
+int archive_view(lins_ctx* ctx, ArchiveView* v) {
+  Archive* m = archive_of(ctx);
+  if (!m->built) return LINS_E_STATE;
+  v->d_out = m->d_out, v->n = (int)m->info.size(), v->off = m->off.data(), v->info = m->info.data(), v->filtered = m->filtered.data();
+  return LINS_OK;
+}
+}  // namespace lins
 
 extern "C" {
 
@@ -409,12 +419,14 @@ int lins_archive_assemble(lins_ctx* ctx, int n, const lins_submap_spec* specs, l
   const LmState* S = (const LmState*)m->h_states;
   m->off.assign(n, 0);
   m->info.assign(n, lins_submap_info{});
+  m->filtered.assign(n, 0);
   for (int k = 0; k < n; ++k) {
     const int j = job_of[k];
     lins_submap_info& z = m->info[k];
     z.status = S[j].status, z.frames = specs[k].n_ids, z.points_in = (uint64_t)cap[k];
     z.n = z.status ? 0 : S[j].nvox;
     m->off[k] = jobs[j].off_out;
+    m->filtered[k] = j < nv;
     const bool box = j < nv && z.n > 0;
     for (int a = 0; a < 3; ++a) z.box_min[a] = box ? S[j].bmin[a] : 0, z.box_dim[a] = box ? S[j].bmax[a] - S[j].bmin[a] + 1 : 1;
     if (out) out[k] = z;

@@ -2,6 +2,7 @@
 // not part of the drop-in surface.
 #include "lins_ctx.h"
 #include "lm_math.h"
+#include "loop_icp.h"
 
 using namespace lins;
 
@@ -200,6 +201,23 @@ int lins_debug_pull_copy(lins_ctx* ctx, uint64_t bytes, int reps, int mode, doub
     if (r && ms < best) best = ms;
   }
   *gbs = (double)(n4 * sizeof(float4)) / ((double)best * 1e-3) / 1e9;
+  return LINS_OK;
+}
+
+/* Debug aids of the loop-closure ICP (not part of the drop-in surface; tests/test_gpu_loop_icp.py; declared by their users).
+ * rounds: lins_loop_icp_batch of this context stops every problem after `rounds` rounds (0: off) — a problem still running
+ * then reports converged = 0, reason = LINS_ICP_NONE and the T, mse, n_corr of its last round, so that every round of the
+ * device's own loop can be held against the restatement's trace.
+ * shells: the search scans at most `shells` shells per query (1: its own cell only) before the query is finished by the
+ * whole-target scan; 0 sends every query that way; negative: the default.  Results are the same bits for every value.
+ * group: rounds queued between two reads of the "still running" word (0: the default); a speed knob, same bits.
+ * last_far: the queries the last lins_loop_icp_batch / lins_loop_icp_correspondences finished by the whole-target scan. */
+int lins_debug_loop_icp_rounds(lins_ctx* ctx, int rounds) { return loop_icp_debug_set(ctx, 0, rounds); }
+int lins_debug_loop_icp_shells(lins_ctx* ctx, int shells) { return loop_icp_debug_set(ctx, 1, shells < 0 ? loop_icp_debug_shells_default() : shells); }
+int lins_debug_loop_icp_group(lins_ctx* ctx, int group) { return loop_icp_debug_set(ctx, 2, group); }
+int lins_debug_loop_icp_last_far(lins_ctx* ctx, uint32_t* far_searches) {
+  if (!ctx || !far_searches) return LINS_E_ARG;
+  *far_searches = loop_icp_last_far(ctx);
   return LINS_OK;
 }
 

@@ -51,6 +51,9 @@ struct MapState {
   // the key-frame archive of lins_archive_* (lins_archive_capi.hip), likewise
   void* archive = nullptr;
   void (*archive_free)(void*) = nullptr;
+  // the loop-closure ICP's of lins_loop_icp_* (lins_loop_icp_capi.hip), likewise
+  void* loop = nullptr;
+  void (*loop_free)(void*) = nullptr;
 };
 
 void map_state_free(void* p) {
@@ -60,6 +63,7 @@ void map_state_free(void* p) {
   (void)hipFree(m->d_carry), (void)hipFree(m->d_results), (void)hipHostFree(m->h_q);
   if (m->local) m->local_free(m->local);
   if (m->archive) m->archive_free(m->archive);
+  if (m->loop) m->loop_free(m->loop);
   delete m;
 }
 
@@ -311,6 +315,11 @@ void** map_archive_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
   MapState* m = state_of(ctx);
   m->archive_free = free_fn;
   return &m->archive;
+}
+void** map_loop_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
+  MapState* m = state_of(ctx);
+  m->loop_free = free_fn;
+  return &m->loop;
 }
 }  // namespace lins
 

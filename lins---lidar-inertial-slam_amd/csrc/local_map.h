@@ -75,5 +75,6 @@ struct LocalMapView {
 int local_map_view(lins_ctx* ctx, LocalMapView* v);
 void** map_local_slot(lins_ctx* ctx, void (*free_fn)(void*));  // lins_map_capi.hip: held by the scan-to-map state
 void** map_archive_slot(lins_ctx* ctx, void (*free_fn)(void*));  // ... and the key-frame archive's (lins_archive_capi.hip)
+void** map_loop_slot(lins_ctx* ctx, void (*free_fn)(void*));     // ... and the loop-closure ICP's (lins_loop_icp_capi.hip)
 
 }  // namespace lins

@@ -275,6 +275,85 @@ def submap(frames, ids, clouds, leaf, flags=0):
     return out[:d["n"]].copy(), d
 
 
+def loop_icp_params(**kw):
+    """lins_loop_icp_default_params with fields overridden by keyword (max_iterations=3, ...)"""
+    from ._ctypes_defs import loop_icp_params as f
+
+    return f(lib(), **kw)
+
+
+def _loop_clouds(source, target):
+    from ._ctypes_defs import cloud
+
+    s, t = cloud(source), cloud(target)
+    return s, t, s.ctypes.data_as(C.POINTER(Point)), t.ctypes.data_as(C.POINTER(Point))
+
+
+def loop_icp(source, target, params=None, max_rounds=0):
+    """lins_host_loop_icp: the CPU restatement of one lins_loop_icp_batch problem (max_rounds: as
+    lins_debug_loop_icp_rounds) -> result dict"""
+    from ._ctypes_defs import LoopIcpParamsC, LoopIcpResultC
+
+    L = lib()
+    s, t, ps, pt = _loop_clouds(source, target)
+    prm = params if params is not None else loop_icp_params()
+    out = LoopIcpResultC()
+    L.lins_host_loop_icp.argtypes = [C.POINTER(Point), C.c_int, C.POINTER(Point), C.c_int, C.POINTER(LoopIcpParamsC), C.c_int, C.POINTER(LoopIcpResultC)]
+    L.lins_host_loop_icp.restype = C.c_int
+    rc = L.lins_host_loop_icp(ps, len(s), pt, len(t), C.byref(prm), int(max_rounds), C.byref(out))
+    if rc != 0:
+        raise RuntimeError(f"lins_host_loop_icp: {rc}")
+    return out.as_dict()
+
+
+def loop_icp_trace(source, target, params=None):
+    """lins_host_loop_icp_trace -> (rounds: list of dicts (T_in, n_corr, mse, delta, T_out, stop, reason), result dict)"""
+    from ._ctypes_defs import LoopIcpParamsC, LoopIcpResultC, LoopIcpRoundC
+
+    L = lib()
+    s, t, ps, pt = _loop_clouds(source, target)
+    prm = params if params is not None else loop_icp_params()
+    cap = max(int(prm.max_iterations), 1)
+    rounds, out = (LoopIcpRoundC * cap)(), LoopIcpResultC()
+    L.lins_host_loop_icp_trace.argtypes = [C.POINTER(Point), C.c_int, C.POINTER(Point), C.c_int, C.POINTER(LoopIcpParamsC), C.POINTER(LoopIcpRoundC),
+                                           C.c_int, C.POINTER(LoopIcpResultC)]
+    L.lins_host_loop_icp_trace.restype = C.c_int
+    n = L.lins_host_loop_icp_trace(ps, len(s), pt, len(t), C.byref(prm), rounds, cap, C.byref(out))
+    if n < 0:
+        raise RuntimeError(f"lins_host_loop_icp_trace: {n}")
+    return [rounds[k].as_dict() for k in range(n)], out.as_dict()
+
+
+def loop_icp_correspondences(source, target, T, cap=0.0):
+    """lins_host_loop_icp_correspondences: the move + EXHAUSTIVE search at T -> (idx (-1: none), d)"""
+    L = lib()
+    s, t, ps, pt = _loop_clouds(source, target)
+    idx, d = np.full(max(len(s), 1), -2, np.int32), np.zeros(max(len(s), 1), np.float32)
+    Tm = np.ascontiguousarray(T, np.float64).reshape(16)
+    L.lins_host_loop_icp_correspondences.argtypes = [C.POINTER(Point), C.c_int, C.POINTER(Point), C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+    L.lins_host_loop_icp_correspondences.restype = C.c_int
+    rc = L.lins_host_loop_icp_correspondences(ps, len(s), pt, len(t), Tm.ctypes.data, float(cap), idx.ctypes.data, d.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"lins_host_loop_icp_correspondences: {rc}")
+    return idx[:len(s)].copy(), d[:len(s)].copy()
+
+
+def loop_pose_from(T, wrong):
+    """lins_host_loop_pose_from (LM:1156-1166, f32): the ICP's T and the latest key pose (x, y, z, roll, pitch, yaw) ->
+    the corrected pose the factor graph's BetweenFactor starts from, same field order"""
+    from ._ctypes_defs import KeyPoseC, key_pose
+
+    L = lib()
+    Tm = np.ascontiguousarray(T, np.float64).reshape(16)
+    w, out = key_pose(wrong), KeyPoseC()
+    L.lins_host_loop_pose_from.argtypes = [C.c_void_p, C.POINTER(KeyPoseC), C.POINTER(KeyPoseC)]
+    L.lins_host_loop_pose_from.restype = C.c_int
+    rc = L.lins_host_loop_pose_from(Tm.ctypes.data, C.byref(w), C.byref(out))
+    if rc != 0:
+        raise RuntimeError(f"lins_host_loop_pose_from: {rc}")
+    return np.array([out.x, out.y, out.z, out.roll, out.pitch, out.yaw], np.float32)
+
+
 def _buf(n):
     a = np.zeros((n, 4), dtype=np.float32)
     return a, a.ctypes.data_as(C.POINTER(Point))

@@ -30,6 +30,7 @@ EXPORTS = [
     "lins_archive_init", "lins_archive_push", "lins_archive_push_scans", "lins_archive_set_poses", "lins_archive_count",
     "lins_archive_select_radius", "lins_archive_find_loop", "lins_archive_assemble", "lins_archive_download",
     "lins_last_archive_stats", "lins_archive_set_scan_chunk",
+    "lins_loop_icp_default_params", "lins_loop_icp_batch", "lins_loop_icp_correspondences", "lins_last_loop_icp_stats",
 ]
 
 
@@ -92,7 +93,7 @@ def lib():
         L.lins_transform_to_end_batch.argtypes = [vp, C.c_int, C.POINTER(ReprojectJob)]
         L.lins_last_reproject_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
         for name in EXPORTS:
-            if name not in ("lins_destroy", "lins_strerror", "lins_last_hip_error", "lins_last_search"):
+            if name not in ("lins_destroy", "lins_strerror", "lins_last_hip_error", "lins_last_search", "lins_loop_icp_default_params"):
                 if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                     continue  # (an older build under A/B timing)
                 getattr(L, name).restype = C.c_int
@@ -397,6 +398,76 @@ class IeskfContext:
         L = lib()
         L.lins_archive_set_scan_chunk.argtypes = [C.c_void_p, C.c_int]
         self._check(L.lins_archive_set_scan_chunk(self._h, int(chunk_tiles)))
+
+    # -- the loop-closure ICP on the device (include/lins_map.h lins_loop_icp_*) ---------------------
+    def loop_icp(self, problems, params=None):
+        """performLoopClosure's alignment for a batch.  problems: (source, target) pairs, each cloud an int — that entry
+        of the last archive_assemble, read on the device where it lies — or an (n, 4) array, uploaded.  params: a
+        LoopIcpParamsC (default: lins_loop_icp_default_params).  Returns the per-problem result dicts."""
+        from ._ctypes_defs import LoopIcpParamsC, LoopIcpProblemC, LoopIcpResultC, loop_icp_params, loop_icp_problem_c
+
+        L = lib()
+        prm = params if params is not None else loop_icp_params(L)
+        n = len(problems)
+        arr, keep = (LoopIcpProblemC * max(n, 1))(), []
+        for k, (s, t) in enumerate(problems):
+            arr[k], kk = loop_icp_problem_c(s, t)
+            keep.append(kk)
+        out = (LoopIcpResultC * max(n, 1))()
+        L.lins_loop_icp_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(LoopIcpProblemC), C.POINTER(LoopIcpParamsC), C.POINTER(LoopIcpResultC)]
+        self._check(L.lins_loop_icp_batch(self._h, n, arr, C.byref(prm), out))
+        return [out[k].as_dict() for k in range(n)]
+
+    def loop_icp_correspondences(self, source, target, T, cap=0.0):
+        """one pass of the move + search at T (4 x 4): (idx (-1: none), d) per source point; cap <= 0: no distance cap"""
+        from ._ctypes_defs import LoopIcpProblemC, loop_icp_problem_c
+
+        L = lib()
+        c, _keep = loop_icp_problem_c(source, target)
+        if c.source_entry >= 0:
+            info = getattr(self, "_archive_info", [])
+            ns = info[c.source_entry]["n"] if c.source_entry < len(info) else 0
+        else:
+            ns = c.n_source
+        idx, d = np.full(max(ns, 1), -2, np.int32), np.zeros(max(ns, 1), np.float32)
+        Tm = np.ascontiguousarray(T, np.float64).reshape(16)
+        L.lins_loop_icp_correspondences.argtypes = [C.c_void_p, C.POINTER(LoopIcpProblemC), C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+        self._check(L.lins_loop_icp_correspondences(self._h, C.byref(c), Tm.ctypes.data, float(cap), idx.ctypes.data, d.ctypes.data))
+        return idx[:ns].copy(), d[:ns].copy()
+
+    def loop_icp_stats(self):
+        """(HIP-event ms of the last loop_icp / loop_icp_correspondences, query evaluations it did)"""
+        ms, q = C.c_float(0), C.c_uint64(0)
+        L = lib()
+        L.lins_last_loop_icp_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+        self._check(L.lins_last_loop_icp_stats(self._h, C.byref(ms), C.byref(q)))
+        return ms.value, q.value
+
+    def _debug_loop_icp(self, name, value):
+        f = getattr(lib(), name)
+        f.argtypes, f.restype = [C.c_void_p, C.c_int], C.c_int
+        self._check(f(self._h, int(value)))
+
+    def debug_loop_icp_rounds(self, rounds):
+        """test aid: loop_icp of this context stops every problem after `rounds` rounds (0: off)"""
+        self._debug_loop_icp("lins_debug_loop_icp_rounds", rounds)
+
+    def debug_loop_icp_shells(self, shells):
+        """test aid: shells a query scans before it is finished by the whole-target scan (0: every query goes that
+        way; None: the default).  Same result bits for every value."""
+        self._debug_loop_icp("lins_debug_loop_icp_shells", -1 if shells is None else shells)
+
+    def debug_loop_icp_group(self, group):
+        """measurement aid: rounds queued between two reads of the "still running" word (0: the default)"""
+        self._debug_loop_icp("lins_debug_loop_icp_group", group)
+
+    def debug_loop_icp_last_far(self):
+        """queries the last loop_icp / loop_icp_correspondences finished by the whole-target scan"""
+        v = C.c_uint32(0)
+        L = lib()
+        L.lins_debug_loop_icp_last_far.argtypes, L.lins_debug_loop_icp_last_far.restype = [C.c_void_p, C.POINTER(C.c_uint32)], C.c_int
+        self._check(L.lins_debug_loop_icp_last_far(self._h, C.byref(v)))
+        return int(v.value)
 
     # -- image_projection_node on the device: raw clouds -> segmented scans --------------------
     def segment_batch(self, raws):
