@@ -93,7 +93,11 @@ typedef struct lins_segmented_scan {
 } lins_segmented_scan;
 
 /* image_projection_node (IP:191-415) on the host: caller-allocated arrays of LINS_CLOUD_MAX
- * entries, `out` is pointed at them.                                                          */
+ * entries, `out` is pointed at them.
+ * Non-finite returns (here, lins_segment_batch, lins_streams_step_raw): a point with a non-finite x, y or z behaves
+ * exactly as if it were not in the cloud (removeNaNFromPointCloud, IP:176) — not projected, not read for the start /
+ * end orientation.  Fewer than two finite points: LINS_E_INPUT.  The device entry points accept NaN only: an
+ * infinite coordinate is LINS_E_INPUT there (nothing is run).                                                      */
 int lins_frontend_segment(const lins_point* raw, int n_raw, lins_point* cloud, float* range, uint32_t* col,
                           uint8_t* ground, lins_segmented_scan* out);
 /* The same stage on the device (csrc/segment_kernels.hip): n raw clouds in firing order; out[k]'s four array

@@ -51,6 +51,9 @@ extern "C" {
 #define LINS_E_HIP (-2)       /* HIP runtime error; see lins_last_hip_error()      */
 #define LINS_E_CAPACITY (-3)  /* batch / cloud larger than the context was sized   */
 #define LINS_E_INPUT (-4)     /* cloud violates the input contract (NaN, ring id)  */
+/* (Raw clouds — lins_frontend_segment, lins_segment_batch, lins_streams_step_raw in lins_host.h — are the exception
+ * for NaN: a point with a NaN x, y or z is a no-return and is dropped, see there; LINS_E_INPUT is what such a call
+ * returns for an infinite coordinate or for a cloud with fewer than two finite points.)                           */
 #define LINS_E_NODEVICE (-5)  /* no usable gfx950 device                           */
 #define LINS_E_STATE (-6)     /* call sequence error (run before upload, ...)      */
 #define LINS_E_UNSUPPORTED (-7) /* this input cannot take the requested device path (nothing was run) */

@@ -47,7 +47,22 @@ struct Segmented {
   int n_outlier = 0;
 };
 
-void project_and_segment(const lins_point* raw, int n, Segmented& seg) {
+// -> false when fewer than two points of the cloud are finite (findStartEndAngle has nothing to read)
+bool project_and_segment(const lins_point* raw, int n, Segmented& seg) {
+  // copyPointCloud: removeNaNFromPointCloud (IP:176) first — a point with a non-finite x, y or z is not part of
+  // the cloud, neither for the projection nor for the first / last points findStartEndAngle reads.  (Without this an
+  // all-NaN point would project: lins_atan2f is built from comparisons and answers 0 for NaN arguments.)
+  std::vector<lins_point> kept;
+  auto finite = [](const lins_point& p) { return std::isfinite(p.x) && std::isfinite(p.y) && std::isfinite(p.z); };
+  for (int i = 0; i < n; ++i)
+    if (!finite(raw[i])) {  // (a NaN-free cloud is read where it lies)
+      kept.assign(raw, raw + i);
+      for (int j = i + 1; j < n; ++j)
+        if (finite(raw[j])) kept.push_back(raw[j]);
+      raw = kept.data(), n = (int)kept.size();
+      break;
+    }
+  if (n < 2) return false;
   std::vector<lins_point> full(kCells, lins_point{NAN, NAN, NAN, -1.f});
   std::vector<float> range(kCells, FLT_MAX);
   std::vector<int8_t> ground(kCells, 0);
@@ -67,7 +82,7 @@ void project_and_segment(const lins_point* raw, int n, Segmented& seg) {
     lins_point p = raw[i];
     float vert = lins_atan2f(p.z, std::sqrt(p.x * p.x + p.y * p.y)) * 180 / M_PI;
     float rowf = (vert + kAngBottom) / kAngResY;
-    // size_t rowIdn = rowf (IP:207, 220-221): truncation towards zero, so (-1, 0) is row 0; <= -1 or NaN turns
+    // size_t rowIdn = rowf (IP:207, 220-221): truncation towards zero, so (-1, 0) is row 0; <= -1 turns
     // into a huge index on x86-64 and is dropped by the `>= LINE_NUM` test
     if (!(rowf > -1.0f) || rowf >= kRows) continue;
     int row = (int)rowf;
@@ -170,6 +185,7 @@ void project_and_segment(const lins_point* raw, int n, Segmented& seg) {
     }
     seg.end_ring[i] = count - 1 - 5;
   }
+  return true;
 }
 
 // pcl::VoxelGrid with leaf 0.2 and all-field averaging; output ordered by voxel index
@@ -350,7 +366,7 @@ int lins_frontend_extract(const lins_point* raw, int n_raw, double scan_period, 
   if (!out->corner_sharp || !out->corner_less_sharp || !out->surf_flat || !out->surf_less_flat)
     return LINS_E_ARG;
   Segmented seg;
-  project_and_segment(raw, n_raw, seg);
+  if (!project_and_segment(raw, n_raw, seg)) return LINS_E_INPUT;
   extract(seg, scan_period, out);
   return LINS_OK;
 }
@@ -359,7 +375,7 @@ int lins_frontend_segment(const lins_point* raw, int n_raw, lins_point* cloud, f
                           uint8_t* ground, lins_segmented_scan* out) {
   if (!raw || !cloud || !range || !col || !ground || !out || n_raw < 2) return LINS_E_ARG;
   Segmented seg;
-  project_and_segment(raw, n_raw, seg);
+  if (!project_and_segment(raw, n_raw, seg)) return LINS_E_INPUT;
   const int n = (int)seg.cloud.size();
   if (n > LINS_CLOUD_MAX) return LINS_E_CAPACITY;
   for (int i = 0; i < n; ++i) cloud[i] = seg.cloud[i], range[i] = seg.range[i], col[i] = seg.col[i], ground[i] = seg.ground[i];

@@ -183,10 +183,26 @@ static int sg_run(lins_ctx* ctx, int n, const lins_point* const* raw, const int3
   const int rcv = pack_pipelined(
       n, 64,
       [&](int k) -> int {
+        // A real driver's cloud carries its no-returns as NaN points.  The reference drops them before anything else
+        // (removeNaNFromPointCloud, IP:176) — also from the first / last points findStartEndAngle reads — so they are
+        // dropped here, while the cloud is packed: the kernel never sees one (its lins_atan2f answers 0 for NaN
+        // arguments: an all-NaN point WOULD project, to row 7 / column 1350).  Infinities stay an input error.
         const lins_point* p = raw[k];
-        for (int i = 0; i < n_raw[k]; ++i)  // (no-return points may be NaN in a real driver's cloud: they never project)
+        bool all_finite = true;
+        for (int i = 0; i < n_raw[k]; ++i) {
           if (std::isinf(p[i].x) || std::isinf(p[i].y) || std::isinf(p[i].z)) return LINS_E_INPUT;
-        std::memcpy(f.h_raw + hr[k].off, p, (size_t)n_raw[k] * sizeof(float4));
+          all_finite = all_finite && !(std::isnan(p[i].x) || std::isnan(p[i].y) || std::isnan(p[i].z));
+        }
+        if (all_finite) {
+          std::memcpy(f.h_raw + hr[k].off, p, (size_t)n_raw[k] * sizeof(float4));
+          return 0;
+        }
+        float4* dst = f.h_raw + hr[k].off;  // (the slot was sized for n_raw[k] points: the kept ones fit)
+        int m = 0;
+        for (int i = 0; i < n_raw[k]; ++i)
+          if (!(std::isnan(p[i].x) || std::isnan(p[i].y) || std::isnan(p[i].z))) std::memcpy(dst + m++, p + i, sizeof(float4));
+        if (m < 2) return LINS_E_INPUT;  // fewer than two finite points: no start / end orientation
+        hr[k].n = m;                     // (uploaded after the packing; one writer per scan)
         return 0;
       },
       [&](int lo, int hi) -> int {  // a complete chunk of clouds travels while the next ones are packed

@@ -130,7 +130,9 @@ __global__ __launch_bounds__(kSgBlock) void segment_kernel(const SgRaw* __restri
     const float vert = (float)((double)(lins_atan2f(p.z, sqrtf(p.x * p.x + p.y * p.y)) * 180) / kPi);
     const float rowf = (vert + (15.0f + 0.1f)) / 2.0f;
     // size_t rowIdn = rowf (IP:207, 220-221): the conversion truncates towards zero, so (-1, 0) is row 0; anything
-    // <= -1 (or NaN) becomes a huge index on x86-64 and fails the `>= LINE_NUM` test
+    // <= -1 becomes a huge index on x86-64 and fails the `>= LINE_NUM` test.  (No NaN gets here: the host drops the
+    // points with a non-finite coordinate while it packs the cloud, as removeNaNFromPointCloud does at IP:176 —
+    // lins_atan2f answers 0 for NaN arguments, so this test would NOT drop them.)
     if (!(rowf > -1.0f) || rowf >= kSgRows) return -1;
     const int row = (int)rowf;
     const float horizon = (float)((double)(lins_atan2f(p.x, p.y) * 180) / kPi);
@@ -266,6 +268,16 @@ __global__ __launch_bounds__(kSgBlock) void segment_kernel(const SgRaw* __restri
   constexpr int kRun = (kSgCells + kSgBlock - 1) / kSgBlock;  // 29 cells per thread
   const int c_lo = tid * kRun < kSgCells ? tid * kRun : kSgCells;
   const int c_hi = c_lo + kRun < kSgCells ? c_lo + kRun : kSgCells;
+  // Why the cap of 4096 sweeps is never reached.  Every cell on a path from a root to a cell of its segment ends with
+  // that root's label.  A sweep starts behind a barrier, so along an edge u -> v of such a path a u that holds the label
+  // when the sweep starts leaves v with it when the sweep ends (labels only fall, and v's owner reads u in that sweep);
+  // a right edge inside one thread's run costs nothing, its source is rewritten earlier in the same pass.  So a cell is
+  // final after 1 + (the edges that leave a run) sweeps along ANY path from its root, and one more sweep sees no
+  // change.  A path never returns to a row (edges go right or down) and visits a cell once; inside a row its
+  // column rises except for one return to column 0 (the only target of a wrap), i.e. at most two rising passes, each
+  // over at most 63 run boundaries (1800 / 29 cells) plus at most 8 "+255" jumps (8 * 255 > 1800).  That is at most
+  // 2 * 71 run-leaving edges per row and one down edge: 16 * 143 = 2288 < 4096.  (tests/seg_cases.py `serpentine`
+  // builds a segment whose farthest cell lies many hundreds of such edges from its root.)
   for (int sweep = 0; sweep < 4096; ++sweep) {
     if (tid == 0) L.changed = 0;
     __syncthreads();
