@@ -61,6 +61,12 @@ void lins_filter_init(lins_filter* f, const lins_filter_params* p, const double*
 void lins_filter_predict(lins_filter* f, double dt, const double* acc,
                          const double* gyr);                      /* KF:125-186  */
 void lins_filter_reset1(lins_filter* f);                          /* KF:320-352  */
+/* What processScan does after performIESKF (SE:443-453), on the filter and on globalState_ (19 doubles, the layout of a
+ * state): filter_->update(posterior) — with used_prior_cov the state only: a diverged update hands over the ICP pose
+ * with Pk_ un-updated (SE:585-592), which is the covariance the filter holds —, integrateTransformation (SE:608-617),
+ * reset(1), calculateRPfromGravity + correctRollPitch (SE:602-605, 427-431).  The CPU restatement of the streams'
+ * finish kernel (csrc/filter_math.h is the arithmetic of both).                                                     */
+void lins_filter_finish(lins_filter* f, double* global_state, const lins_result* posterior, int used_prior_cov);
 
 /* ---- front-end ------------------------------------------------------------ */
 typedef struct lins_features {
@@ -147,6 +153,9 @@ int lins_streams_stats(lins_ctx* ctx, float* frontend_ms, float* update_ms, floa
 /* test aid: a resident cloud of the last scan back to the host (which: 0 less sharp, 1 less flat);
  * returns the point count                                                                            */
 int lins_streams_peek(lins_ctx* ctx, int stream, int which, lins_point* out, int cap);
+
+/* The streams' filter on the device — IMU propagation, update from the resident prior, reset, global pose per stream
+ * (lins_streams_filter_*, lins_streams_step_imu*) — is declared in lins_streams_filter.h.                            */
 
 /* the front-end's atan2 (csrc/lins_math.h: a fixed f32 operation sequence shared bit for bit by the host
  * restatement and the device kernels; within 2 ulp(pi/4) of the true value).

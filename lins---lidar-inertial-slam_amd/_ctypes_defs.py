@@ -13,6 +13,8 @@ MAX_QUERY = 1024
 CLOUD_MAX = 16 * 1800
 
 LINS_OK = 0
+STREAMS_IMU_MAX = 64  # LINS_STREAMS_IMU_MAX: IMU rows per stream and call of the streams' device filter
+STREAMS_GATED = 1     # LINS_STREAMS_GATED: Result.reserved[0] of a scan the reference's feature gate (SE:436-440) stopped
 
 
 class Point(C.Structure):

@@ -3,8 +3,11 @@
 //
 // Behavioural mirror of filter::StatePredictor, /root/reference/lins/include/
 // KalmanFilter.hpp: predict 125-186, initializeCovariance 247-311, reset(1)
-// 320-352; unit constants parameters.h:63-71.  400 Hz x 18x18 serial algebra —
-// stays on the host by design.
+// 320-352; unit constants parameters.h:63-71.  400 Hz x 18x18 serial algebra: for
+// ONE filter it stays on the host by design.  The streams
+// path, with up to 1024 filters per scan period, runs the same operation sequence
+// on the device (csrc/filter_kernels.hip, bit-equal to this file on the seeded
+// cases of tests/test_gpu_filter.py); this mirror is what that kernel is held to.
 
 #include <cmath>
 #include <cstring>

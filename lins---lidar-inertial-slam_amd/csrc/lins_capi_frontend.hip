@@ -10,6 +10,7 @@ void streams_free(lins_ctx* ctx) {
   auto& t = ctx->st;
   (void)hipFree(t.d_arena), (void)hipFree(t.d_sorted), (void)hipFree(t.d_desc), (void)hipFree(t.d_jobs), (void)hipFree(t.d_desc_next);
   t.d_desc_next = nullptr, t.index_ready = false;
+  streams_filter_free(ctx);
   (void)hipFree(t.d_gsorted), (void)hipFree(t.d_gridtab);
   t = lins_ctx::Streams{};
 }
@@ -334,14 +335,35 @@ int lins_streams_init(lins_ctx* ctx, int n_streams) {
   HIP_TRY(ctx, hipMalloc((void**)&t.d_desc_next, (size_t)n_streams * sizeof(ScanDesc)));
   t.index_ready = false;
   HIP_TRY(ctx, hipMalloc(&t.d_jobs, (size_t)n_streams * 2 * sizeof(StreamCloud)));
-  t.n = n_streams, t.cur = 0;
+  t.n = n_streams, t.cur.assign((size_t)n_streams, 0);
   t.last_counts.assign((size_t)n_streams * 2, -1);
   return LINS_OK;
 }
 
+// imu != nullptr: the prior comes from the streams' device filter (lins_streams_step_imu*)
+struct StepImu {
+  const int32_t* n_imu;
+  const double* const* rows;
+  double* global_state_out;
+};
 static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, const lins_point* const* raw,
                              const int32_t* n_raw, const double* prior_state, const double* prior_cov, double scan_period,
-                             lins_result* out, int32_t* feature_counts);
+                             lins_result* out, int32_t* feature_counts, const StepImu* imu = nullptr);
+
+int lins_streams_step_imu(lins_ctx* ctx, const lins_segmented_scan* scans, const int32_t* n_imu, const double* const* imu,
+                          double scan_period, lins_result* out, int32_t* feature_counts, double* global_state_out) {
+  if (!scans) return LINS_E_ARG;
+  const StepImu si{n_imu, imu, global_state_out};
+  return streams_step_impl(ctx, scans, nullptr, nullptr, nullptr, nullptr, scan_period, out, feature_counts, &si);
+}
+
+int lins_streams_step_imu_raw(lins_ctx* ctx, const lins_point* const* raw, const int32_t* n_raw, const int32_t* n_imu,
+                              const double* const* imu, double scan_period, lins_result* out, int32_t* feature_counts,
+                              double* global_state_out) {
+  if (!raw || !n_raw) return LINS_E_ARG;
+  const StepImu si{n_imu, imu, global_state_out};
+  return streams_step_impl(ctx, nullptr, raw, n_raw, nullptr, nullptr, scan_period, out, feature_counts, &si);
+}
 
 int lins_streams_step(lins_ctx* ctx, const lins_segmented_scan* scans, const double* prior_state, const double* prior_cov,
                       double scan_period, lins_result* out, int32_t* feature_counts) {
@@ -357,10 +379,15 @@ int lins_streams_step_raw(lins_ctx* ctx, const lins_point* const* raw, const int
 
 static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, const lins_point* const* raw,
                              const int32_t* n_raw, const double* prior_state, const double* prior_cov, double scan_period,
-                             lins_result* out, int32_t* feature_counts) {
-  if (!ctx || !prior_state || !prior_cov || !out) return LINS_E_ARG;
+                             lins_result* out, int32_t* feature_counts, const StepImu* imu) {
+  if (!ctx || !out || (!imu && (!prior_state || !prior_cov))) return LINS_E_ARG;
   auto& t = ctx->st;
   if (t.n <= 0 || t.failed) return LINS_E_STATE;  // (after a failed step: lins_streams_init again)
+  if (imu) {  // every stream runs from its device filter against its resident last scan, or nothing is run
+    if (int rc = streams_filter_check(ctx, imu->n_imu, imu->rows)) return rc;
+    for (int k = 0; k < t.n; ++k)
+      if (t.last_counts[(size_t)k * 2] < 0) return LINS_E_STATE;
+  }
   // A step either completes for every stream — slots flipped, resident clouds re-projected — or marks the streams
   // context failed: no half-advanced state survives an early return.
   struct Guard {
@@ -373,13 +400,14 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
   const CallTrace trace;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (int rcs = split_join(ctx)) return rcs;
-  const int n = t.n, cur = t.cur, last = cur ^ 1;
+  const int n = t.n;
+  const std::vector<int>& cur = t.cur;
   ctx->n_uploaded = 0, ctx->ran = false;  // the batch buffers are reused below
   // 1. feature front-end, straight into this scan's slots
   std::vector<long long> offs((size_t)n * 4);
   for (int k = 0; k < n; ++k) {
     long long* o = &offs[(size_t)k * 4];
-    const long long b = slot_base(k, cur);
+    const long long b = slot_base(k, cur[k]);
     o[0] = b + kSlotSharp, o[1] = b + kSlotLessSharp, o[2] = b + kSlotFlat, o[3] = b + kSlotLessFlat;
   }
   std::vector<int> counts;
@@ -404,12 +432,27 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
   trace.mark("front-end done (synced)");
   // 2. IESKF update of every stream against its resident last scan (a stream's first scan: an update
   //    with no rows, which leaves the given state — the bootstrap pose — untouched)
+  //    On the filter path the prior is first propagated over the stream's IMU rows (behind the front-end, so that a
+  //    rejected input has advanced nothing), and a scan with too few features is gated (SE:436-440): no update, the
+  //    stream's resident clouds and slot stay the old scan's.
+  std::vector<char> gated((size_t)n, 0);
+  bool any_gated = false;
+  if (imu) {
+    if (int rcp = streams_filter_predict_queue(ctx, imu->n_imu, imu->rows)) return rcp;
+    for (int k = 0; k < n; ++k) {
+      const int* c = &counts[(size_t)k * 4];
+      gated[k] = c[1] <= 5 || c[3] <= 10;
+      any_gated = any_gated || gated[k];
+    }
+  }
+  const double* d_prior_state = imu ? t.f.d_state : ctx->d_state_in;
+  const double* d_prior_cov = imu ? t.f.d_cov : ctx->d_cov_in;
   bool lds_ok = true, mr_ok = true, lds3_ok = true;
   for (int k = 0; k < n; ++k) {
     const int* c = &counts[(size_t)k * 4];  // sharp, less sharp, flat, less flat
-    const bool has_last = t.last_counts[(size_t)k * 2] >= 0;
+    const bool has_last = t.last_counts[(size_t)k * 2] >= 0 && !gated[k];
     ScanDesc& d = ctx->h_desc[k];
-    const long long bq = slot_base(k, cur), bt = slot_base(k, last);
+    const long long bq = slot_base(k, cur[k]), bt = slot_base(k, cur[k] ^ 1);
     d.off_surf_q = (int)(bq + kSlotFlat), d.n_surf_q = has_last ? c[2] : 0;
     d.off_corner_q = (int)(bq + kSlotSharp), d.n_corner_q = has_last ? c[0] : 0;
     d.off_surf_t = (int)(bt + kSlotLessFlat), d.n_surf_t = has_last ? t.last_counts[(size_t)k * 2 + 1] : 0;
@@ -422,11 +465,13 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
     if (d.n_surf_q + d.n_corner_q > 336) lds3_ok = false;
   }
   ctx->lds_ok = lds_ok, ctx->mr_ok = mr_ok, ctx->lds3_ok = lds3_ok;
-  std::memcpy(ctx->h_state, prior_state, (size_t)n * 19 * 8);
-  std::memcpy(ctx->h_cov, prior_cov, (size_t)n * 324 * 8);
   HIP_TRY(ctx, hipMemcpyAsync(t.d_desc, ctx->h_desc, (size_t)n * sizeof(ScanDesc), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_state_in, ctx->h_state, (size_t)n * 19 * 8, hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cov_in, ctx->h_cov, (size_t)n * 324 * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (!imu) {
+    std::memcpy(ctx->h_state, prior_state, (size_t)n * 19 * 8);
+    std::memcpy(ctx->h_cov, prior_cov, (size_t)n * 324 * 8);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_state_in, ctx->h_state, (size_t)n * 19 * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_cov_in, ctx->h_cov, (size_t)n * 324 * 8, hipMemcpyHostToDevice, ctx->stream));
+  }
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   bool idx_ready = false;
   {
@@ -443,8 +488,8 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
         RelayArgs ra;
         const bool relay = n > ctx->queue_grid && ctx->prm.icp_freq == 1 && ctx->d_relay_hdr && ctx->relay_at != 0 && relay_max_parts(ctx->prm.num_iter, ctx->relay_at, ctx->relay_cuts) > 1;
         // launch order as in the batch calls: longest-expected-first by the prior's translation (launch_order above;
-        // h_state holds this step's priors)
-        const bool ordered = ctx->use_order && n > ctx->queue_grid;
+        // h_state holds this step's priors; the filter path's priors are on the device: natural order, same results)
+        const bool ordered = ctx->use_order && n > ctx->queue_grid && !imu;
         if (ordered) {
           launch_order(ctx, n);
           HIP_TRY(ctx, hipMemcpyAsync(ctx->d_order, ctx->h_order, (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
@@ -453,16 +498,16 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
           const int rcq = relay_prepare(ctx, n, ordered, ra);
           if (rcq) return rcq;
         }
-        launch_lds_mr(ctx->stream, n, ctx->dprm, t.d_desc, relay ? ctx->d_order + ctx->max_batch : (ordered ? ctx->d_order : nullptr), t.d_arena, t.d_gsorted, t.d_gridtab, ctx->d_state_in,
-                      ctx->d_cov_in, ctx->d_state_out, ctx->d_a6, ctx->d_cov_out, ctx->d_out, ctx->d_idx, nullptr, 0, nullptr, relay ? &ra : nullptr,
+        launch_lds_mr(ctx->stream, n, ctx->dprm, t.d_desc, relay ? ctx->d_order + ctx->max_batch : (ordered ? ctx->d_order : nullptr), t.d_arena, t.d_gsorted, t.d_gridtab, d_prior_state,
+                      d_prior_cov, ctx->d_state_out, ctx->d_a6, ctx->d_cov_out, ctx->d_out, ctx->d_idx, nullptr, 0, nullptr, relay ? &ra : nullptr,
                       ctx->d_walk_cache, next_run_gen(ctx), ctx->d_relay_lane);
       } else
-        launch_lds(ctx->stream, n, ctx->dprm, search == SEARCH_LDS3 ? 3 : 1, t.d_desc, t.d_arena, t.d_gsorted, t.d_gridtab, ctx->d_state_in,
-                   ctx->d_cov_in, ctx->d_state_out, ctx->d_a6, ctx->d_cov_out, ctx->d_out, ctx->d_idx, nullptr, 0, nullptr, ctx->d_relay_lane);
+        launch_lds(ctx->stream, n, ctx->dprm, search == SEARCH_LDS3 ? 3 : 1, t.d_desc, t.d_arena, t.d_gsorted, t.d_gridtab, d_prior_state,
+                   d_prior_cov, ctx->d_state_out, ctx->d_a6, ctx->d_cov_out, ctx->d_out, ctx->d_idx, nullptr, 0, nullptr, ctx->d_relay_lane);
     } else {
       DevParams dp = ctx->dprm;
       dp.search = want_lds ? (int)SEARCH_BINNED : search;
-      launch_persistent(ctx->stream, n, dp, t.d_desc, t.d_arena, ctx->d_state_in, ctx->d_cov_in, ctx->d_state_out,
+      launch_persistent(ctx->stream, n, dp, t.d_desc, t.d_arena, d_prior_state, d_prior_cov, ctx->d_state_out,
                         ctx->d_cov_out, ctx->d_a6, ctx->d_out, ctx->d_idx, nullptr, 0, t.d_sorted, nullptr);
     }
   }
@@ -481,17 +526,23 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
     std::memcpy(r.state, ctx->h_state + (size_t)k * 19, sizeof r.state);
     std::memcpy(r.cov, ctx->h_cov + (size_t)k * 324, sizeof r.cov);
     const OutRec& o = ctx->h_out[k];
-    const bool has_last = t.last_counts[(size_t)k * 2] >= 0;
+    const bool has_last = t.last_counts[(size_t)k * 2] >= 0 && !gated[k];
     r.residual_norm = o.residual_norm, r.update_norm = o.update_norm;
     r.iters = has_last ? o.iters : 0, r.converged = has_last ? o.converged : 0, r.diverged = has_last ? o.diverged : 0;
     r.m_surf = o.m_surf, r.m_corner = o.m_corner;
-    if (!has_last) {  // a stream's first scan: the given state and covariance, bit for bit (also as re-projection pose)
+    if (!has_last && !imu) {  // a stream's first scan: the given state and covariance, bit for bit (also as re-projection pose)
       std::memcpy(r.state, prior_state + (size_t)k * 19, sizeof r.state);
       std::memcpy(r.cov, prior_cov + (size_t)k * 324, sizeof r.cov);
       HIP_TRY(ctx, hipMemcpyAsync(ctx->d_state_out + (size_t)k * 19, ctx->d_state_in + (size_t)k * 19, 19 * 8,
                                   hipMemcpyDeviceToDevice, ctx->stream));
     }
+    if (!has_last && imu) {  // a gated scan: the filter as predicted
+      r.reserved[0] = LINS_STREAMS_GATED;
+      HIP_TRY(ctx, hipMemcpyAsync(r.state, t.f.d_state + (size_t)k * 19, 19 * 8, hipMemcpyDeviceToHost, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(r.cov, t.f.d_cov + (size_t)k * 324, 324 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
   }
+  if (any_gated) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   // 2b. diverged filters: the ICP fallback (SE:585-592) on the same resident clouds, pose into the state row
   for (int k = 0; k < n; ++k) {
     if (!out[k].diverged) continue;
@@ -505,12 +556,23 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
       launch_grid_index(ctx->stream, n, t.d_desc, t.d_arena, t.d_gsorted, t.d_gridtab);
       idx_ready = true;
     }
-    launch_lds_mr_icp(ctx->stream, 1, ctx->dprm, t.d_desc + k, t.d_arena, t.d_gsorted, t.d_gridtab + k, ctx->d_state_in + (size_t)k * 19,
+    launch_lds_mr_icp(ctx->stream, 1, ctx->dprm, t.d_desc + k, t.d_arena, t.d_gsorted, t.d_gridtab + k, d_prior_state + (size_t)k * 19,
                       ctx->d_state_out + (size_t)k * 19, ctx->d_out + k, ctx->d_idx);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(out[k].state, ctx->d_state_out + (size_t)k * 19, 19 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (imu) HIP_TRY(ctx, hipMemcpyAsync(out[k].cov, d_prior_cov + (size_t)k * 324, 324 * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::memcpy(out[k].cov, prior_cov + (size_t)k * 324, 324 * 8);  // Pk_ un-updated
+    if (!imu) std::memcpy(out[k].cov, prior_cov + (size_t)k * 324, 324 * 8);  // Pk_ un-updated
+  }
+  // 2c. the filter path: filter_->update, integrateTransformation, reset(1), correctRollPitch on the device
+  //     (filter_finish_kernel reads the posterior rows and leaves them: the re-projection below reads linState_ there)
+  if (imu) {
+    std::vector<int> mode((size_t)n);
+    for (int k = 0; k < n; ++k)
+      mode[k] = gated[k] || (out[k].diverged && out[k].reserved[0] == LINS_E_UNSUPPORTED) ? 0 : (out[k].diverged ? 2 : 1);
+    if (int rcf = streams_filter_finish_queue(ctx, mode.data())) return rcf;
+    if (imu->global_state_out)
+      HIP_TRY(ctx, hipMemcpyAsync(imu->global_state_out, t.f.d_gstate, (size_t)n * 19 * 8, hipMemcpyDeviceToHost, ctx->stream));
   }
   // 3. updatePointCloud: this scan's less-sharp / less-flat clouds to the scan end with the final pose
   //    (device-resident state rows), in place — they are the next step's targets
@@ -518,17 +580,23 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
   int max_n = 1;
   for (int k = 0; k < n; ++k) {
     const int* c = &counts[(size_t)k * 4];
-    const long long b = slot_base(k, cur);
+    const long long b = slot_base(k, cur[k]);
+    if (feature_counts) std::memcpy(feature_counts + (size_t)k * 4, c, 4 * sizeof(int));
+    if (gated[k]) {  // nothing of this scan becomes a target
+      jobs[(size_t)k * 2] = StreamCloud{b + kSlotLessSharp, 0, k}, jobs[(size_t)k * 2 + 1] = StreamCloud{b + kSlotLessFlat, 0, k};
+      continue;
+    }
     jobs[(size_t)k * 2] = StreamCloud{b + kSlotLessSharp, c[1], k};
     jobs[(size_t)k * 2 + 1] = StreamCloud{b + kSlotLessFlat, c[3], k};
     max_n = std::max(max_n, std::max(c[1], c[3]));
     t.last_counts[(size_t)k * 2] = c[1], t.last_counts[(size_t)k * 2 + 1] = c[3];
-    if (feature_counts) std::memcpy(feature_counts + (size_t)k * 4, c, 4 * sizeof(int));
   }
   // ... and, when the next step's update will search through the LDS grid, their search index in the same pass
   // (grid_index_kernel<true>: one read of the new clouds for the re-projected arena copy, the grid-sorted copy and the
   // tables; SURVEY f-2 "re-projection + target binning build")
-  bool fuse = ctx->streams_fuse && effective_search(ctx, n) >= SEARCH_LDS;
+  // (a gated stream keeps its old targets and their index: the step then runs the two kernels, and the next step builds
+  // the index of every stream's resident clouds anew — same bits either way, tests/test_gpu_edge_cases.py)
+  bool fuse = ctx->streams_fuse && effective_search(ctx, n) >= SEARCH_LDS && !any_gated;
   for (int k = 0; k < n && fuse; ++k) {
     const int* c = &counts[(size_t)k * 4];
     if (c[1] + c[3] > kGridNpMax || c[1] + c[3] > (effective_search(ctx, n) == SEARCH_MR ? lds_mr_np_cap() : lds_np_cap())) fuse = false;
@@ -537,7 +605,7 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
     for (int k = 0; k < n; ++k) {
       const int* c = &counts[(size_t)k * 4];
       ScanDesc& d = ctx->h_desc[k];  // (the update's descriptors have been consumed: its kernel has finished)
-      const long long b = slot_base(k, cur);
+      const long long b = slot_base(k, cur[k]);
       d.off_surf_t = (int)(b + kSlotLessFlat), d.n_surf_t = c[3];
       d.off_corner_t = (int)(b + kSlotLessSharp), d.n_corner_t = c[1];
     }
@@ -556,7 +624,8 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   HIP_TRY(ctx, hipEventElapsedTime(&t.reproject_ms, ctx->ev0, ctx->ev2));
   trace.mark("re-projection done (synced)");
-  t.cur = last;
+  for (int k = 0; k < n; ++k)
+    if (!gated[k]) t.cur[k] ^= 1;
   guard.done = true;
   return LINS_OK;
 }
@@ -576,7 +645,7 @@ int lins_streams_peek(lins_ctx* ctx, int stream, int which, lins_point* out, int
   const int cnt = t.last_counts[(size_t)stream * 2 + which];
   if (cnt < 0) return LINS_E_STATE;
   if (cnt > cap) return LINS_E_CAPACITY;
-  const long long b = slot_base(stream, t.cur ^ 1) + (which ? kSlotLessFlat : kSlotLessSharp);
+  const long long b = slot_base(stream, t.cur[stream] ^ 1) + (which ? kSlotLessFlat : kSlotLessSharp);
   HIP_TRY(ctx, hipMemcpy(out, t.d_arena + b, (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost));
   return cnt;
 }

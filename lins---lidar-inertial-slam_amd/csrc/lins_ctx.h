@@ -32,6 +32,7 @@ typedef enum { ncclInt8 = 0, ncclChar = 0 } ncclDataType_t;
 #endif
 
 #include "../../include/lins_host.h"
+#include "../../include/lins_streams_filter.h"
 #include "ieskf_device.h"
 #include "ieskf_grid.h"
 #include "lins_ctx_priv.h"
@@ -130,7 +131,8 @@ struct lins_ctx {
   // device-resident streams (lins_streams_step): per stream two feature slots (this scan's / the last
   // scan's clouds) inside one arena, so that ScanDesc offsets address both
   struct Streams {
-    int n = 0, cur = 0;           // slot the NEXT scan's features go to
+    int n = 0;
+    std::vector<int> cur;         // per stream: slot the NEXT scan's features go to (a gated scan does not flip its stream's)
     float4 *d_arena = nullptr, *d_sorted = nullptr, *d_gsorted = nullptr;
     GridTables* d_gridtab = nullptr;
     ScanDesc* d_desc = nullptr;
@@ -140,6 +142,19 @@ struct lins_ctx {
     std::vector<int> last_counts;  // per stream: less sharp, less flat of the resident last scan (-1: none yet)
     bool failed = false;           // a step stopped half way (HIP error): the resident clouds are not trustworthy any more
     float update_ms = 0.f, frontend_ms = 0.f, reproject_ms = 0.f;
+    // the streams' filter (lins_streams_filter_*, lins_streams_step_imu*; lins_capi_filter.hip): what lins_filter holds
+    // and globalState_, one row per stream in the layout of d_state_in / d_cov_in — the update kernels read the predicted
+    // prior where it lies.  Allocated by the first lins_streams_filter_set.
+    struct Filter {
+      double *d_state = nullptr, *d_cov = nullptr, *d_noise = nullptr, *d_aux = nullptr, *d_gstate = nullptr;  // n x 19 / 324 / 144 / kAux / 19
+      double *d_imu = nullptr, *h_imu = nullptr;  // this call's IMU rows, packed (n x LINS_STREAMS_IMU_MAX x 7 at most; h_: pinned)
+      int *d_ints = nullptr, *h_ints = nullptr;   // [n_imu | row offset | finish mode] x n (h_: pinned)
+      std::vector<char> set;                      // per stream: a filter has been loaded
+      std::vector<lins_filter_params> prm;        // ... and its parameters (lins_streams_filter_get returns them)
+      hipEvent_t ev[4] = {};                      // predict start / end, finish start / end
+      bool predict_timed = false, finish_timed = false;
+      float predict_ms = 0.f, finish_ms = 0.f;
+    } f;
   } st;
   void* map_state = nullptr;  // scan-to-map row (lins_map_capi.hip), freed through map_state_free
   void (*map_state_free)(void*) = nullptr;
@@ -221,6 +236,14 @@ int relay_check(lins_ctx* ctx);
 void rccl_free(lins_ctx* ctx);
 void fe_free(lins_ctx* ctx);
 void streams_free(lins_ctx* ctx);
+// ---- lins_capi_filter.hip
+void streams_filter_free(lins_ctx* ctx);
+// queue the predict kernel over this call's IMU rows on the context's stream (arguments checked by the caller:
+// streams_filter_check); no synchronisation
+int streams_filter_check(lins_ctx* ctx, const int32_t* n_imu, const double* const* imu);
+int streams_filter_predict_queue(lins_ctx* ctx, const int32_t* n_imu, const double* const* imu);
+// queue the finish kernel (mode per stream as launch_filter_finish) behind the update
+int streams_filter_finish_queue(lins_ctx* ctx, const int* mode);
 
 // Run fn(k) for k in [0, n) on up to 16 host threads (validation + packing of a batch is memory-bound
 // scalar work: 1024 scans = 8 M points); returns the smallest-index non-zero result.

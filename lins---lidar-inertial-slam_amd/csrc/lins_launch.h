@@ -66,6 +66,12 @@ void launch_frontend(hipStream_t stream, int n_scans, const FeScan* scans, const
 void launch_segment(hipStream_t stream, int n_scans, const SgRaw* raws, const float4* raw, float sin_ax, float cos_ax, float sin_ay, float cos_ay, float theta, unsigned* cellidx, int* seg_rows,
                     FeScan* fe_scans, float4* out_cloud, float* out_range, unsigned* out_col, unsigned char* out_ground, int* out_outliers);
 
+// ---- filter_kernels.hip: the streams' device-resident filter (filter_math.h).  imu: rows (dt, acc, gyr), stream k's
+// n_imu[k] rows start at row imu_off[k]; aux: lins_filt::kAux doubles per stream.  finish mode[k]: 0 leave the filter,
+// 1 posterior state + covariance, 2 posterior state with the filter's own (prior) covariance
+void launch_filter_predict(hipStream_t stream, int n, const int* n_imu, const int* imu_off, const double* imu, double* state, double* cov, const double* noise, double* aux);
+void launch_filter_finish(hipStream_t stream, int n, const int* mode, const double* post_state, const double* post_cov, double* state, double* cov, const double* aux, double* gstate);
+
 // ---- debug_kernels.hip (lins_debug_math; op codes there)
 void launch_debug_math(hipStream_t stream, int op, int n, int n_in, int n_out, const double* in, double* out);
 void launch_debug_cycles(hipStream_t stream, int op, int blocks, const double* in, double* out);

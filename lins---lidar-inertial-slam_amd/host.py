@@ -177,10 +177,26 @@ def lib():
         L.lins_filter_init.argtypes = [C.POINTER(Filter), C.POINTER(FilterParams)] + [C.POINTER(C.c_double)] * 3
         L.lins_filter_predict.argtypes = [C.POINTER(Filter), C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.lins_filter_reset1.argtypes = [C.POINTER(Filter)]
-        for f in (L.lins_filter_default_params, L.lins_filter_init, L.lins_filter_predict, L.lins_filter_reset1):
+        from ._ctypes_defs import ResultC
+
+        L.lins_filter_finish.argtypes = [C.POINTER(Filter), C.POINTER(C.c_double), C.POINTER(ResultC), C.c_int]
+        for f in (L.lins_filter_default_params, L.lins_filter_init, L.lins_filter_predict, L.lins_filter_reset1, L.lins_filter_finish):
             f.restype = None
         _LIB = L
     return _LIB
+
+
+def filter_finish(filt, global_state, state, cov, used_prior_cov=False):
+    """lins_filter_finish: filter_->update(state, cov) — the state only with used_prior_cov —, integrateTransformation,
+    reset(1), correctRollPitch on `filt` (a Filter, changed in place).  Returns the new globalState_ (19,)."""
+    from ._ctypes_defs import ResultC
+
+    r = ResultC()
+    r.state[:] = [float(v) for v in np.asarray(state, np.float64).reshape(19)]
+    r.cov[:] = [float(v) for v in np.asarray(cov, np.float64).reshape(324)]
+    g = np.array(global_state, dtype=np.float64).reshape(19).copy()
+    lib().lins_filter_finish(C.byref(filt), g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(r), int(bool(used_prior_cov)))
+    return g
 
 
 def local_map(frames, scan, window=50):

@@ -30,6 +30,8 @@ EXPORTS = [
     "lins_archive_init", "lins_archive_push", "lins_archive_push_scans", "lins_archive_set_poses", "lins_archive_count",
     "lins_archive_select_radius", "lins_archive_find_loop", "lins_archive_assemble", "lins_archive_download",
     "lins_last_archive_stats", "lins_archive_set_scan_chunk",
+    "lins_streams_filter_set", "lins_streams_filter_get", "lins_streams_filter_predict", "lins_streams_step_imu",
+    "lins_streams_step_imu_raw", "lins_streams_filter_stats",
     "lins_loop_icp_default_params", "lins_loop_icp_batch", "lins_loop_icp_correspondences", "lins_last_loop_icp_stats",
 ]
 
@@ -588,6 +590,91 @@ class IeskfContext:
                                             counts.ctypes.data_as(C.POINTER(C.c_int32))))
         self._n = 0
         return [Result(r) for r in res], counts
+
+    # -- the streams' filter on the device: IMU propagation, update from the resident prior, reset, global pose ------
+    def streams_filter_set(self, stream, filt, global_state):
+        """filt: a host.Filter; global_state: globalState_ (19,)"""
+        g = np.ascontiguousarray(global_state, dtype=np.float64).reshape(19)
+        L = lib()
+        L.lins_streams_filter_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+        self._check(L.lins_streams_filter_set(self._h, stream, C.byref(filt), g.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def streams_filter_get(self, stream):
+        """-> (host.Filter, globalState_ (19,)) of one stream (synchronises)"""
+        import importlib
+
+        host = importlib.import_module(__package__ + ".host")
+        filt, g = host.Filter(), np.zeros(19)
+        L = lib()
+        L.lins_streams_filter_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_double)]
+        self._check(L.lins_streams_filter_get(self._h, stream, C.byref(filt), g.ctypes.data_as(C.POINTER(C.c_double))))
+        return filt, g
+
+    def _imu_args(self, imu):
+        """imu: per stream an (m, 7) array of rows (dt, acc, gyr), m may be 0 -> (counts, pointers, keep-alive)"""
+        n = self._streams
+        assert len(imu) == n
+        rows = [np.ascontiguousarray(r, dtype=np.float64).reshape(-1, 7) for r in imu]
+        dp = C.POINTER(C.c_double)
+        ptrs = (dp * n)(*[r.ctypes.data_as(dp) if len(r) else dp() for r in rows])
+        return (C.c_int32 * n)(*[len(r) for r in rows]), ptrs, rows
+
+    def streams_filter_predict(self, imu):
+        """StatePredictor::predict of every stream over its own IMU rows (see _imu_args), one launch."""
+        cnt, ptrs, _keep = self._imu_args(imu)
+        L = lib()
+        L.lins_streams_filter_predict.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_double))]
+        self._check(L.lins_streams_filter_predict(self._h, cnt, ptrs))
+
+    def streams_step_imu(self, segs, imu, scan_period=0.1):
+        """streams_step with the prior from the device filter, propagated over `imu` first.
+        Returns (results, feature_counts (n, 4), global states (n, 19))."""
+        import importlib
+
+        host = importlib.import_module(__package__ + ".host")
+        n = self._streams
+        assert len(segs) == n
+        arr = (host.SegmentedScanC * n)(*[s.c for s in segs])
+        cnt, ptrs, _keep = self._imu_args(imu)
+        res = (ResultC * n)()
+        counts, g = np.zeros((n, 4), np.int32), np.zeros((n, 19))
+        L = lib()
+        L.lins_streams_step_imu.argtypes = [C.c_void_p, C.POINTER(host.SegmentedScanC), C.POINTER(C.c_int32), C.POINTER(C.POINTER(C.c_double)),
+                                            C.c_double, C.POINTER(ResultC), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+        self._check(L.lins_streams_step_imu(self._h, arr, cnt, ptrs, scan_period, res, counts.ctypes.data_as(C.POINTER(C.c_int32)),
+                                            g.ctypes.data_as(C.POINTER(C.c_double))))
+        self._n = 0
+        return [Result(r) for r in res], counts, g
+
+    def streams_step_imu_raw(self, raws, imu, scan_period=0.1):
+        """Like streams_step_imu, from raw clouds (firing order)."""
+        import importlib
+
+        host = importlib.import_module(__package__ + ".host")
+        n = self._streams
+        assert len(raws) == n
+        raws = [np.ascontiguousarray(r, dtype=np.float32).reshape(-1, 4) for r in raws]
+        rptrs = (C.POINTER(host.Point) * n)(*[r.ctypes.data_as(C.POINTER(host.Point)) for r in raws])
+        rcnt = (C.c_int32 * n)(*[len(r) for r in raws])
+        cnt, ptrs, _keep = self._imu_args(imu)
+        res = (ResultC * n)()
+        counts, g = np.zeros((n, 4), np.int32), np.zeros((n, 19))
+        L = lib()
+        L.lins_streams_step_imu_raw.argtypes = [C.c_void_p, C.POINTER(C.POINTER(host.Point)), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                C.POINTER(C.POINTER(C.c_double)), C.c_double, C.POINTER(ResultC), C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_double)]
+        self._check(L.lins_streams_step_imu_raw(self._h, rptrs, rcnt, cnt, ptrs, scan_period, res,
+                                                counts.ctypes.data_as(C.POINTER(C.c_int32)), g.ctypes.data_as(C.POINTER(C.c_double))))
+        self._n = 0
+        return [Result(r) for r in res], counts, g
+
+    def streams_filter_stats(self):
+        """HIP-event times (ms) of the last predict and finish kernels"""
+        a, b = C.c_float(0), C.c_float(0)
+        L = lib()
+        L.lins_streams_filter_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_float)] * 2
+        self._check(L.lins_streams_filter_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def streams_stats(self):
         a, b, c = C.c_float(0), C.c_float(0), C.c_float(0)
