@@ -257,6 +257,22 @@ int lins_host_loop_icp_trace(const lins_point* source, int n_source, const lins_
 /* steps 1-2 at T by exhaustive search (cap <= 0: none): index (-1: none) and d (0 where none) per source point */
 int lins_host_loop_icp_correspondences(const lins_point* source, int n_source, const lins_point* target, int n_target, const double T[16],
                                        float cap, int32_t* idx, float* sqdist);
+/* One problem between two rounds, as the step takes and leaves it (csrc/loop_icp_math.h State without its device-only words):
+ * a fresh problem has T = identity, mse_prev = DBL_MAX, mse = 0, fitness = DBL_MAX, the counts 0 and active = 1. */
+typedef struct lins_loop_icp_state {
+  double T[16];
+  double mse_prev, mse, fitness;
+  float move[12]; /* out only: the upper three rows of T rounded to f32, the next round's M */
+  int32_t iterations, converged, reason, n_corr, n_fitness, active;
+} lins_loop_icp_state;
+/* Steps 3-6 of ONE round from its 17 sums (0: count  1-3: S x'  4-6: S g  7-15: S x'_i g_j at 7 + 3 i + j  16: S d), handed
+ * over instead of found by the search — the test entry of the fit and the stop rule (tests/test_loop_fit_inputs.py; the
+ * device's is lins_debug_loop_icp_step).  mode 0: the round — a state with active = 0 is left as it is, as the device's
+ * step kernel leaves it; delta (the round's fit; identity when it stopped for too few correspondences) and stop (the four
+ * quantities of lins_loop_icp_round.stop; zeros then) are written.  mode 1: the fitness pass, n_fitness and fitness =
+ * sums[16] / sums[0] (DBL_MAX at a count of 0), whatever `active` says; delta and stop are not touched and may be null. */
+int lins_host_loop_icp_step(const double sums[17], const lins_loop_icp_params* prm, int mode, lins_loop_icp_state* state,
+                            double delta[16], double stop[4]);
 /* LM:1156-1166, all f32: T -> (x, y, z, roll, pitch, yaw) by roll = atan2(T21, T22), pitch = asin(-T20), yaw =
  * atan2(T10, T00); correctionLidar = getTransformation(z, x, y, yaw, roll, pitch); tWrong = getTransformation(wrong.z,
  * wrong.x, wrong.y, wrong.yaw, wrong.roll, wrong.pitch); pose_from = the same extraction of correctionLidar * tWrong.

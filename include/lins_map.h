@@ -234,7 +234,10 @@ int lins_archive_set_scan_chunk(lins_ctx* ctx, int chunk_tiles);
  *   3 too few    fewer than min_correspondences: stop, converged = 0, LINS_ICP_NO_CORRESPONDENCES, T kept
  *   4 fit        Kabsch in f64 from the sums n, S x', S g, S x' g^T (tiles of 32 source points: the tree
  *                ((q0+q4)+(q2+q6))+((q1+q5)+(q3+q7)) over each 8 consecutive points, the four eights in order, the tiles
- *                in order); 3 x 3 SVD by one-sided cyclic Jacobi, fixed sweep count
+ *                in order); 3 x 3 SVD by one-sided cyclic Jacobi, fixed sweep count; R = V diag(1, 1, det(V U^T)) U^T, a
+ *                proper rotation also where the unconstrained optimum is a reflection, defined for a rank-2 H (planar
+ *                points); an H of rank < 2 — sigma2 <= 2^14 x 2^-53 sigma1: collinear or coincident points, whose
+ *                second singular value is the rounding noise of the raw moments — gives R = I, t = mu_g - mu_s
  *   5 compose    T_{k+1} = Delta T_k in f64
  *   6 stop       (a) k + 1 >= max_iterations  (b) 0.5 (trace R_Delta - 1) >= rotation_threshold and |t_Delta|^2 <=
  *                transformation_epsilon  (c) |mse - mse_prev| < fitness_epsilon  (d) |mse - mse_prev| / mse_prev < rel_mse;

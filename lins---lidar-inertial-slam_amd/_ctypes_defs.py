@@ -350,6 +350,35 @@ class LoopIcpRoundC(C.Structure):
                     stop=np.array(self.stop[:], np.float64), n_corr=int(self.n_corr), reason=int(self.reason))
 
 
+class LoopIcpStateC(C.Structure):
+    _fields_ = [("T", C.c_double * 16), ("mse_prev", C.c_double), ("mse", C.c_double), ("fitness", C.c_double), ("move", C.c_float * 12),
+                ("iterations", C.c_int32), ("converged", C.c_int32), ("reason", C.c_int32), ("n_corr", C.c_int32), ("n_fitness", C.c_int32),
+                ("active", C.c_int32)]
+    COUNTS = ("iterations", "converged", "reason", "n_corr", "n_fitness", "active")
+
+    def as_dict(self):
+        d = dict(T=np.array(self.T[:], np.float64).reshape(4, 4), mse_prev=float(self.mse_prev), mse=float(self.mse), fitness=float(self.fitness),
+                 move=np.array(self.move[:], np.float32).reshape(3, 4))
+        d.update((k, int(getattr(self, k))) for k in self.COUNTS)
+        return d
+
+
+def loop_icp_state(state=None):
+    """lins_loop_icp_state: a fresh problem (T = I, mse_prev = fitness = DBL_MAX, active = 1) with the fields of the dict
+    `state` (as as_dict gives them; `move` is out only) put over it"""
+    s = LoopIcpStateC()
+    d = dict(T=np.eye(4), mse_prev=np.finfo(np.float64).max, mse=0.0, fitness=np.finfo(np.float64).max, active=1)
+    d.update(state or {})
+    for k, v in d.items():
+        if k == "T":
+            s.T[:] = [float(x) for x in np.asarray(v, np.float64).reshape(16)]
+        elif k != "move":
+            if not hasattr(s, k):
+                raise TypeError(k)
+            setattr(s, k, v)
+    return s
+
+
 def loop_icp_params(lib, **kw):
     """lins_loop_icp_default_params of `lib` (both libraries export it) with fields overridden by keyword"""
     p = LoopIcpParamsC()

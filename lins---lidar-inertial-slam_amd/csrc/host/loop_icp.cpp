@@ -139,6 +139,23 @@ int lins_host_loop_icp_correspondences(const lins_point* source, int n_source, c
   return LINS_OK;
 }
 
+int lins_host_loop_icp_step(const double sums[17], const lins_loop_icp_params* prm, int mode, lins_loop_icp_state* state, double delta[16],
+                            double stop[4]) {
+  if (!sums || !params_ok(prm) || !state || (mode != 0 && mode != 1) || (mode == 0 && (!delta || !stop))) return LINS_E_ARG;
+  State s;
+  state_from_public(*state, s);
+  if (mode == 0) {
+    if (!s.active) return LINS_OK;
+    for (int i = 0; i < 16; ++i) delta[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    for (int i = 0; i < 4; ++i) stop[i] = 0.0;
+    step_from_sums(*prm, sums, s, delta, stop);
+  } else {
+    fitness_from_sums(sums, s);
+  }
+  state_to_public(s, *state);
+  return LINS_OK;
+}
+
 int lins_host_loop_pose_from(const double T[16], const lins_key_pose* wrong, lins_key_pose* pose_from) {
   if (!T || !wrong || !pose_from) return LINS_E_ARG;
   float c[16], x, y, z, roll, pitch, yaw;

@@ -1,5 +1,7 @@
 // lins_capi_debug.hip — every lins_debug_* entry point of the C ABI (include/lins_ieskf.h): test and measurement aids,
 // not part of the drop-in surface.
+#include <vector>
+
 #include "lins_ctx.h"
 #include "lm_math.h"
 #include "loop_icp.h"
@@ -218,6 +220,52 @@ int lins_debug_loop_icp_group(lins_ctx* ctx, int group) { return loop_icp_debug_
 int lins_debug_loop_icp_last_far(lins_ctx* ctx, uint32_t* far_searches) {
   if (!ctx || !far_searches) return LINS_E_ARG;
   *far_searches = loop_icp_last_far(ctx);
+  return LINS_OK;
+}
+
+/* step: the device's step kernel (launch_loop_step: the tile loop, the fit, the composition, the stop rule) on sums the
+ * caller hands over instead of the search — the device side of lins_host_loop_icp_step (include/lins_host.h;
+ * tests/test_gpu_loop_fit.py).  n problems; problem k adds its first n_tiles[k] <= blocks_per_problem tiles of
+ * partials[(k * blocks_per_problem + tile) * 17 + sum], in order (the tiles behind them are not read); status[k] != 0: the
+ * problem is not run.  mode as launch_loop_step.  states: in and out (`move` out only); an inactive problem (mode 0) or
+ * one with a status comes back as it went in.  still_running (may be null): the problems that go on after the round. */
+int lins_debug_loop_icp_step(lins_ctx* ctx, int n, int blocks_per_problem, const int32_t* n_tiles, const int32_t* status, const double* partials,
+                             const lins_loop_icp_params* prm, int mode, lins_loop_icp_state* states, int32_t* still_running) {
+  if (!ctx || n < 1 || blocks_per_problem < 1 || !n_tiles || !status || !partials || !prm || (mode != 0 && mode != 1) || !states) return LINS_E_ARG;
+  std::vector<LoopDev> probs(n, LoopDev{});
+  std::vector<lins_licp::State> st(n);
+  for (int k = 0; k < n; ++k) {
+    if (n_tiles[k] < 0 || n_tiles[k] > blocks_per_problem) return LINS_E_ARG;
+    probs[k].n_src = n_tiles[k] * kLoopQPerBlock, probs[k].status = status[k];
+    for (int a = 0; a < 3; ++a) probs[k].g.cdim[a] = 1;
+    lins_licp::state_from_public(states[k], st[k]);
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t np = (size_t)n * blocks_per_problem * lins_licp::kSums;
+  LoopDev* d_probs = nullptr;
+  lins_licp::State* d_states = nullptr;
+  double* d_partials = nullptr;
+  int* d_running = nullptr;
+  int running = 0;
+  hipError_t e = hipMalloc((void**)&d_probs, (size_t)n * sizeof(LoopDev));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_states, (size_t)n * sizeof(lins_licp::State));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_partials, np * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_running, sizeof(int));
+  if (e == hipSuccess) e = hipMemcpyAsync(d_probs, probs.data(), (size_t)n * sizeof(LoopDev), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_states, st.data(), (size_t)n * sizeof(lins_licp::State), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_partials, partials, np * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_running, 0, sizeof(int), ctx->stream);
+  if (e == hipSuccess) {
+    launch_loop_step(ctx->stream, n, blocks_per_problem, mode, *prm, d_probs, d_states, d_partials, d_running);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(st.data(), d_states, (size_t)n * sizeof(lins_licp::State), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&running, d_running, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(d_probs), (void)hipFree(d_states), (void)hipFree(d_partials), (void)hipFree(d_running);
+  if (e != hipSuccess) return ctx_fail_hip(ctx, e, "lins_debug_loop_icp_step");
+  for (int k = 0; k < n; ++k) lins_licp::state_to_public(st[k], states[k]);  // (every problem: what the kernel left)
+  if (still_running) *still_running = running;
   return LINS_OK;
 }
 

@@ -6,7 +6,7 @@
 #include <float.h>
 #include <math.h>
 
-#include "../../include/lins_map.h"
+#include "../../include/lins_host.h"  // lins_map.h: the parameters; lins_loop_icp_state
 #include "lins_math.h"  // LINS_HD
 
 #ifdef __HIPCC__
@@ -21,6 +21,11 @@ constexpr int kTile = 32;   // source points per tile of the sums
 constexpr int kGroup = 8;   // consecutive points under one fixed-shape tree
 constexpr int kSums = 17;   // 0: count  1-3: S x'  4-6: S g  7-15: S x'_i g_j (3 i + j)  16: S d
 constexpr int kSweeps = 10; // Jacobi sweeps of the 3 x 3 SVD (f64 converges in 5-6; the count is part of the contract)
+// H counts as of rank < 2 when sigma2 <= kRankFloor sigma1, kRankFloor = c u with u = 2^-53 and c = 2^14.  Exactly collinear
+// points leave a second singular value of rounding noise in the f64 raw-moment H: over lines of at least 1 m within 100 m of
+// the origin, formed in plain f64 and decomposed by LAPACK, at most 1.7e3 u sigma1 (tests/loop_fit_cases.py
+// collinear_floor); c is 8 x that, rounded up to a power of two.  Part of the contract.
+constexpr double kRankFloor = 16384.0 * 1.1102230246251565e-16;
 
 LINS_HD void default_params(lins_loop_icp_params* p) {
   p->transformation_epsilon = 1e-6, p->fitness_epsilon = 1e-6, p->rel_mse = 1e-5, p->rotation_threshold = 0.99999;
@@ -59,7 +64,8 @@ LINS_HD double tree8(const double* q) { return ((q[0] + q[4]) + (q[2] + q[6])) +
 
 // U S V^T = H by one-sided Jacobi; returns R = V diag(1, 1, det(V U^T)) U^T.  The columns are ordered by falling
 // singular value and the third column of U is u0 x u1 — the same R as with the SVD's own third column, and defined for
-// a rank-2 H; an H of rank < 2 (collinear or coincident points: the rotation is not determined) gives the identity.
+// a rank-2 H; an H of rank < 2 (collinear or coincident points: the rotation is not determined; sigma2 <= kRankFloor sigma1)
+// gives the identity.
 LINS_HD void kabsch_rotation(const double* H, double* R) {
   double A[9], V[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   LICP_UNROLL
@@ -104,7 +110,7 @@ LINS_HD void kabsch_rotation(const double* H, double* R) {
   }
   LICP_UNROLL
   for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
-  if (!(n2[1] > 0.0)) return;
+  if (!(n2[1] > (kRankFloor * kRankFloor) * n2[0])) return;  // (n2 = sigma^2; false for 0 > 0 and for a NaN too)
   const double s0 = sqrt(n2[0]), s1 = sqrt(n2[1]);
   double U[9];  // U = [u0 u1 u0 x u1]; W = V, its columns in the same order
   const double* W = V;
@@ -196,6 +202,21 @@ LINS_HD void step_from_sums(const lins_loop_icp_params& prm, const double* sums,
 LINS_HD void fitness_from_sums(const double* sums, State& s) {
   s.n_fitness = (int)sums[0];
   s.fitness = s.n_fitness > 0 ? sums[16] / sums[0] : DBL_MAX;
+}
+
+// the state as the test entries of the step take and return it (include/lins_host.h lins_loop_icp_state)
+inline void state_from_public(const lins_loop_icp_state& p, State& s) {
+  state_init(s);
+  for (int i = 0; i < 16; ++i) s.T[i] = p.T[i];
+  make_move(s.T, s.M);
+  s.mse_prev = p.mse_prev, s.mse = p.mse, s.fitness = p.fitness;
+  s.iterations = p.iterations, s.converged = p.converged, s.reason = p.reason, s.n_corr = p.n_corr, s.n_fitness = p.n_fitness, s.active = p.active;
+}
+inline void state_to_public(const State& s, lins_loop_icp_state& p) {
+  for (int i = 0; i < 16; ++i) p.T[i] = s.T[i];
+  for (int i = 0; i < 12; ++i) p.move[i] = s.M[i];
+  p.mse_prev = s.mse_prev, p.mse = s.mse, p.fitness = s.fitness;
+  p.iterations = s.iterations, p.converged = s.converged, p.reason = s.reason, p.n_corr = s.n_corr, p.n_fitness = s.n_fitness, p.active = s.active;
 }
 
 }  // namespace lins_licp

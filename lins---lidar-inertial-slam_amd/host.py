@@ -354,6 +354,23 @@ def loop_icp_correspondences(source, target, T, cap=0.0):
     return idx[:len(s)].copy(), d[:len(s)].copy()
 
 
+def loop_icp_step(sums, params=None, mode=0, state=None):
+    """lins_host_loop_icp_step: steps 3-6 of one round (mode 0) or the fitness score (mode 1) from the 17 sums; state: a
+    dict of lins_loop_icp_state fields over a fresh problem -> (state dict, delta (4, 4), stop (4))"""
+    from ._ctypes_defs import LoopIcpParamsC, LoopIcpStateC, loop_icp_state
+
+    L = lib()
+    v = np.ascontiguousarray(sums, np.float64).reshape(17)
+    prm = params if params is not None else loop_icp_params()
+    st, D, q = loop_icp_state(state), np.full(16, np.nan), np.full(4, np.nan)
+    L.lins_host_loop_icp_step.argtypes = [C.c_void_p, C.POINTER(LoopIcpParamsC), C.c_int, C.POINTER(LoopIcpStateC), C.c_void_p, C.c_void_p]
+    L.lins_host_loop_icp_step.restype = C.c_int
+    rc = L.lins_host_loop_icp_step(v.ctypes.data, C.byref(prm), int(mode), C.byref(st), D.ctypes.data, q.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"lins_host_loop_icp_step: {rc}")
+    return st.as_dict(), D.reshape(4, 4), q
+
+
 def loop_pose_from(T, wrong):
     """lins_host_loop_pose_from (LM:1156-1166, f32): the ICP's T and the latest key pose (x, y, z, roll, pitch, yaw) ->
     the corrected pose the factor graph's BetweenFactor starts from, same field order"""

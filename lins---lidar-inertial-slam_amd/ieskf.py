@@ -471,6 +471,31 @@ class IeskfContext:
         self._check(L.lins_debug_loop_icp_last_far(self._h, C.byref(v)))
         return int(v.value)
 
+    def debug_loop_icp_step(self, partials, params=None, mode=0, states=None, n_tiles=None, status=None):
+        """test aid (lins_debug_loop_icp_step): the device's step kernel on handed-over sums.  partials: (K, tiles, 17)
+        f64; n_tiles: per problem, the tiles the kernel adds (default: all); status: per problem, != 0 is not run; states:
+        per problem a dict of lins_loop_icp_state fields over a fresh problem.  -> (state dicts, problems still running)"""
+        from ._ctypes_defs import LoopIcpParamsC, LoopIcpStateC, loop_icp_params, loop_icp_state
+
+        L = lib()
+        p = np.ascontiguousarray(partials, np.float64)
+        if p.ndim != 3 or p.shape[2] != 17:
+            raise ValueError("partials: (K, tiles, 17)")
+        n, bpp = p.shape[:2]
+        nt = np.full(n, bpp, np.int32) if n_tiles is None else np.ascontiguousarray(n_tiles, np.int32)
+        stt = np.zeros(n, np.int32) if status is None else np.ascontiguousarray(status, np.int32)
+        if nt.shape != (n,) or stt.shape != (n,) or (states is not None and len(states) != n):
+            raise ValueError("one entry per problem")
+        prm = params if params is not None else loop_icp_params(L)
+        arr = (LoopIcpStateC * max(n, 1))(*[loop_icp_state(states[k] if states is not None else None) for k in range(n)])
+        running = C.c_int32(-1)
+        f = L.lins_debug_loop_icp_step
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LoopIcpParamsC), C.c_int, C.POINTER(LoopIcpStateC),
+                      C.POINTER(C.c_int32)]
+        f.restype = C.c_int
+        self._check(f(self._h, n, bpp, nt.ctypes.data, stt.ctypes.data, p.ctypes.data, C.byref(prm), int(mode), arr, C.byref(running)))
+        return [arr[k].as_dict() for k in range(n)], int(running.value)
+
     # -- image_projection_node on the device: raw clouds -> segmented scans --------------------
     def segment_batch(self, raws):
         """raws: list of (n,4) f32 raw clouds in firing order.  Returns a list of host.Segmented."""

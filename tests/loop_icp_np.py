@@ -53,6 +53,35 @@ def kabsch(X, Y):
     return D
 
 
+def round_from_pairs(X, Y, d, T, mse_prev, iterations, **kw):
+    """steps 3-6 of one round from its correspondences — the moved points X, their targets Y, the f32 d of each — entering
+    with T, mse_prev and `iterations` fitted rounds: the round's dict (T_in, n_corr, delta, T_out, stop, reason, mse);
+    reason NONE: the loop goes on"""
+    p = dict(DEFAULTS, **kw)
+    T = np.asarray(T, np.float64).reshape(4, 4)
+    r = dict(T_in=T.copy(), n_corr=len(X), delta=np.eye(4), stop=np.zeros(4), reason=NONE, mse=0.0, T_out=T.copy())
+    if r["n_corr"] < p["min_correspondences"]:
+        r["reason"] = NO_CORRESPONDENCES
+        return r
+    D = kabsch(np.asarray(X)[:, :3], np.asarray(Y)[:, :3])
+    mse = float(np.sum(np.asarray(d).astype(np.float64)) / r["n_corr"])
+    with np.errstate(over="ignore"):
+        ad = abs(mse - mse_prev)
+        q = np.array([0.5 * (np.trace(D[:3, :3]) - 1.0), float(D[:3, 3] @ D[:3, 3]), ad, ad / mse_prev])
+    if iterations + 1 >= p["max_iterations"]:
+        reason = ITERATIONS
+    elif q[0] >= p["rotation_threshold"] and q[1] <= p["transformation_epsilon"]:
+        reason = TRANSFORM
+    elif q[2] < p["fitness_epsilon"]:
+        reason = ABS_MSE
+    elif q[3] < p["rel_mse"]:
+        reason = REL_MSE
+    else:
+        reason = NONE
+    r.update(delta=D, T_out=D @ T, stop=q, reason=reason, mse=mse)
+    return r
+
+
 def icp(S, G, max_rounds=0, **kw):
     """-> (rounds, result), the shapes of host.loop_icp_trace"""
     p = dict(DEFAULTS, **kw)
@@ -62,35 +91,17 @@ def icp(S, G, max_rounds=0, **kw):
     while res["reason"] == NONE and (max_rounds == 0 or len(rounds) < max_rounds):
         idx, d, X = correspondences(S, G, T, p["max_corr_dist"])
         ok = idx >= 0
-        r = dict(T_in=T.copy(), n_corr=int(ok.sum()), delta=np.eye(4), stop=np.zeros(4), reason=NONE, mse=0.0)
+        r = round_from_pairs(X[ok], G[idx[ok], :3], d[ok], T, mse_prev, res["iterations"], **kw)
         res["n_corr"] = r["n_corr"]
-        if r["n_corr"] < p["min_correspondences"]:
-            r["reason"] = res["reason"] = NO_CORRESPONDENCES
-            r["T_out"] = T.copy()
-            rounds.append(r)
-            break
-        D = kabsch(X[ok], G[idx[ok], :3])
-        T = D @ T
-        res["iterations"] += 1
-        mse = float(np.sum(d[ok].astype(np.float64)) / r["n_corr"])
-        with np.errstate(over="ignore"):
-            ad = abs(mse - mse_prev)
-            q = np.array([0.5 * (np.trace(D[:3, :3]) - 1.0), float(D[:3, 3] @ D[:3, 3]), ad, ad / mse_prev])
-        if res["iterations"] >= p["max_iterations"]:
-            reason = ITERATIONS
-        elif q[0] >= p["rotation_threshold"] and q[1] <= p["transformation_epsilon"]:
-            reason = TRANSFORM
-        elif q[2] < p["fitness_epsilon"]:
-            reason = ABS_MSE
-        elif q[3] < p["rel_mse"]:
-            reason = REL_MSE
-        else:
-            reason = NONE
-        mse_prev = res["mse"] = mse
-        r.update(delta=D, T_out=T.copy(), stop=q, reason=reason, mse=mse)
         rounds.append(r)
-        if reason != NONE:
-            res["reason"], res["converged"] = reason, 1
+        if r["reason"] == NO_CORRESPONDENCES:
+            res["reason"] = NO_CORRESPONDENCES
+            break
+        T = r["T_out"]
+        res["iterations"] += 1
+        mse_prev = res["mse"] = r["mse"]
+        if r["reason"] != NONE:
+            res["reason"], res["converged"] = r["reason"], 1
     idx, d, _ = correspondences(S, G, T, 0.0)
     ok = idx >= 0
     res["n_fitness"] = int(ok.sum())

@@ -1,5 +1,5 @@
 """The ctypes mirrors of the loop-closure ICP's structs (include/lins_map.h lins_loop_icp_params / _problem / _result,
-include/lins_host.h lins_loop_icp_round) have the C structs' sizes and field offsets, compiled with the host compiler as
+include/lins_host.h lins_loop_icp_round / _state) have the C structs' sizes and field offsets, compiled with the host compiler as
 tests/test_abi_archive.py does, and both libraries export their entry points."""
 import ctypes as C
 import os
@@ -24,6 +24,9 @@ int main(void) {
          offsetof(lins_loop_icp_result, status));
   printf("%zu %zu %zu %zu %zu %zu\n", sizeof(lins_loop_icp_round), offsetof(lins_loop_icp_round, delta), offsetof(lins_loop_icp_round, T_out),
          offsetof(lins_loop_icp_round, mse), offsetof(lins_loop_icp_round, stop), offsetof(lins_loop_icp_round, reason));
+  printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(lins_loop_icp_state), offsetof(lins_loop_icp_state, mse_prev), offsetof(lins_loop_icp_state, fitness),
+         offsetof(lins_loop_icp_state, move), offsetof(lins_loop_icp_state, iterations), offsetof(lins_loop_icp_state, n_corr),
+         offsetof(lins_loop_icp_state, active));
   printf("%d %d %d %d %d %d\n", LINS_ICP_NONE, LINS_ICP_ITERATIONS, LINS_ICP_TRANSFORM, LINS_ICP_ABS_MSE, LINS_ICP_REL_MSE, LINS_ICP_NO_CORRESPONDENCES);
   return 0;
 }
@@ -39,7 +42,9 @@ int main(void) {
     assert got[4:9] == [C.sizeof(Q), Q.target_entry.offset, Q.source.offset, Q.target.offset, Q.n_target.offset]
     assert got[9:16] == [C.sizeof(R), R.fitness.offset, R.mse.offset, R.iterations.offset, R.n_fitness.offset, R.far_searches.offset, R.status.offset]
     assert got[16:22] == [C.sizeof(T), T.delta.offset, T.T_out.offset, T.mse.offset, T.stop.offset, T.reason.offset]
-    assert got[22:] == [defs.ICP_NONE, defs.ICP_ITERATIONS, defs.ICP_TRANSFORM, defs.ICP_ABS_MSE, defs.ICP_REL_MSE, defs.ICP_NO_CORRESPONDENCES]
+    S = defs.LoopIcpStateC
+    assert got[22:29] == [C.sizeof(S), S.mse_prev.offset, S.fitness.offset, S.move.offset, S.iterations.offset, S.n_corr.offset, S.active.offset]
+    assert got[29:] == [defs.ICP_NONE, defs.ICP_ITERATIONS, defs.ICP_TRANSFORM, defs.ICP_ABS_MSE, defs.ICP_REL_MSE, defs.ICP_NO_CORRESPONDENCES]
 
 
 def test_default_parameters_are_the_mapping_nodes(host, ieskf, defs):
@@ -51,9 +56,10 @@ def test_default_parameters_are_the_mapping_nodes(host, ieskf, defs):
 
 def test_both_libraries_export_the_loop_icp(host, ieskf):
     for name in ("lins_host_loop_icp", "lins_host_loop_icp_correspondences", "lins_host_loop_icp_trace", "lins_host_loop_pose_from",
-                 "lins_loop_icp_default_params"):
+                 "lins_host_loop_icp_step", "lins_loop_icp_default_params"):
         assert hasattr(host.lib(), name), name
     want = {"lins_loop_icp_default_params", "lins_loop_icp_batch", "lins_loop_icp_correspondences", "lins_last_loop_icp_stats"}
     assert want <= set(ieskf.EXPORTS)
-    for name in sorted(want) + ["lins_debug_loop_icp_rounds", "lins_debug_loop_icp_shells", "lins_debug_loop_icp_group", "lins_debug_loop_icp_last_far"]:
+    for name in sorted(want) + ["lins_debug_loop_icp_rounds", "lins_debug_loop_icp_shells", "lins_debug_loop_icp_group", "lins_debug_loop_icp_last_far",
+                                "lins_debug_loop_icp_step"]:
         assert hasattr(ieskf.lib(), name), name
