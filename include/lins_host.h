@@ -34,6 +34,8 @@ extern "C" {
 #define LINS_LINE_NUM 16   /* LINE_NUM  (exp_port.yaml:9)  */
 #define LINS_SCAN_NUM 1800 /* SCAN_NUM  (exp_port.yaml:10) */
 #define LINS_CLOUD_MAX (LINS_LINE_NUM * LINS_SCAN_NUM)
+/* most points of an outlier cloud (IP:300-303): rows above groundScanInd = 5, every fifth column */
+#define LINS_OUTLIER_MAX ((LINS_LINE_NUM - 6) * (LINS_SCAN_NUM / 5))
 
 /* ---- StatePredictor ------------------------------------------------------ */
 typedef struct lins_filter_params {
@@ -112,6 +114,14 @@ int lins_frontend_segment(const lins_point* raw, int n_raw, lins_point* cloud, f
 int lins_segment_batch(lins_ctx* ctx, int n, const lins_point* const* raw, const int32_t* n_raw,
                        lins_segmented_scan* out);
 int lins_last_segment_ms(lins_ctx* ctx, float* kernel_ms);
+/* The third cloud image_projection_node publishes, /outlier_cloud (IP:300-303): the cells of the segments that fail the
+ * validity test, in rows above groundScanInd and in every fifth column, in raster order (ring-major, ascending column),
+ * as fullCloud points — x, y, z of the cell's owning point, intensity = row + col / 10000 (IP:234).  outlier: caller-
+ * allocated, LINS_OUTLIER_MAX entries.  Input contract of lins_frontend_segment.  Returns the count (what
+ * lins_frontend_segment reports as n_outlier) or an error.                                                          */
+int lins_frontend_segment_outliers(const lins_point* raw, int n_raw, lins_point* outlier);
+/* The same cloud from the device's segmentation stage (lins_segment_batch_outliers), and what the streams keep of it for
+ * the mapping node (lins_streams_put_outliers, lins_streams_map_cloud), are declared in lins_streams_map.h.            */
 /* StateEstimator's feature stage (undistortPcl .. extractFeatures, SE:619-827) on the host — the
  * CPU restatement the device version is checked against.                                      */
 int lins_frontend_extract_segmented(const lins_segmented_scan* in, double scan_period, lins_features* out);

@@ -134,6 +134,18 @@ int lins_local_map_push(lins_ctx* ctx, int slot, const lins_keyframe* frame);
  * scans[k]; everything runs on the context's stream with one synchronisation at the end; out[k] (may be NULL) gets
  * the sizes, the 1 m boxes and the entry's status.  An empty ring gives empty maps.  Scans: finite, |coord| <= 1e6. */
 int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_local_scan* scans, lins_local_map_sizes* out);
+/* lins_local_map_build with entry k's three scan clouds taken from stream streams[k] of the context's device-resident
+ * streams (lins_streams_map.h) where they lie: the clouds lins_streams_map_cloud would return — corner last, surf last, outlier
+ * last — are moved into the mapping node's axes, checked and boxed by one kernel instead of on the host; nothing is
+ * downloaded or uploaded.  Everything behind that, and every result bit, is lins_local_map_build's;
+ * lins_local_map_push_scans, lins_archive_push_scans, lins_local_map_download and LINS_MAP_LOCAL work on this build as on
+ * any other.  A stream may appear once (LINS_E_ARG); a stream that has not stepped, or a failed streams context:
+ * LINS_E_STATE.  The input contract is checked on the device: an entry with a scan point that is not finite or beyond
+ * 1e6 gets status LINS_E_INPUT and empty clouds (as a window cloud outside the contract), the call returns LINS_OK.   */
+int lins_local_map_build_streams(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* streams, lins_local_map_sizes* out);
+/* HIP-event time (ms) of the staging kernel of the last lins_local_map_build_streams (part of the build's kernel_ms;
+ * 0 after lins_local_map_build) */
+int lins_last_local_map_stage_ms(lins_ctx* ctx, float* stage_ms);
 /* the cornerDS, surfDS and outlierDS of the chosen entries of the last build become new key frames of their slots,
  * device to device, in the order given (the caller's key-frame rule, LM:1655-1669, decides which) */
 int lins_local_map_push_scans(lins_ctx* ctx, int n, const int32_t* entries, const lins_key_pose* poses);

@@ -11,6 +11,7 @@ STATE_DIM = 19
 ERR_DIM = 18
 MAX_QUERY = 1024
 CLOUD_MAX = 16 * 1800
+OUTLIER_MAX = (16 - 6) * (1800 // 5)  # LINS_OUTLIER_MAX: rows above groundScanInd, every fifth column
 
 LINS_OK = 0
 STREAMS_IMU_MAX = 64  # LINS_STREAMS_IMU_MAX: IMU rows per stream and call of the streams' device filter

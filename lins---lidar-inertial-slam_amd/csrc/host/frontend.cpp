@@ -45,6 +45,7 @@ struct Segmented {
   int start_ring[kRows], end_ring[kRows];
   float start_ori, end_ori, ori_diff;
   int n_outlier = 0;
+  std::vector<lins_point>* outlier = nullptr;  // when set: outlierCloud (IP:300-303), raster order
 };
 
 // -> false when fewer than two points of the cloud are finite (findStartEndAngle has nothing to read)
@@ -165,6 +166,7 @@ bool project_and_segment(const lins_point* raw, int n, Segmented& seg) {
   // emission (IP:292-321)
   seg.cloud.clear(), seg.ground.clear(), seg.col.clear(), seg.range.clear();
   seg.n_outlier = 0;
+  if (seg.outlier) seg.outlier->clear();
   int count = 0;
   for (int i = 0; i < kRows; ++i) {
     seg.start_ring[i] = count - 1 + 5;
@@ -172,7 +174,10 @@ bool project_and_segment(const lins_point* raw, int n, Segmented& seg) {
       int c = j + i * kCols;
       if (label[c] > 0 || ground[c] == 1) {
         if (label[c] == 999999) {
-          if (i > kGroundScanInd && j % 5 == 0) seg.n_outlier++;
+          if (i > kGroundScanInd && j % 5 == 0) {
+            seg.n_outlier++;
+            if (seg.outlier) seg.outlier->push_back(full[c]);
+          }
           continue;
         }
         if (ground[c] == 1 && j % 5 != 0 && j > 5 && j < kCols - 5) continue;
@@ -384,6 +389,17 @@ int lins_frontend_segment(const lins_point* raw, int n_raw, lins_point* cloud, f
   out->start_ori = seg.start_ori, out->end_ori = seg.end_ori, out->ori_diff = seg.ori_diff;
   out->n_outlier = seg.n_outlier;
   return LINS_OK;
+}
+
+int lins_frontend_segment_outliers(const lins_point* raw, int n_raw, lins_point* outlier) {
+  if (!raw || !outlier || n_raw < 2) return LINS_E_ARG;
+  Segmented seg;
+  std::vector<lins_point> cloud;
+  seg.outlier = &cloud;
+  if (!project_and_segment(raw, n_raw, seg)) return LINS_E_INPUT;
+  if ((int)cloud.size() > LINS_OUTLIER_MAX) return LINS_E_CAPACITY;  // (rows 6 .. 15, every fifth column: never)
+  for (size_t i = 0; i < cloud.size(); ++i) outlier[i] = cloud[i];
+  return (int)cloud.size();
 }
 
 int lins_frontend_extract_segmented(const lins_segmented_scan* in, double scan_period, lins_features* out) {

@@ -5,21 +5,42 @@
 
 using namespace lins;
 
+namespace {
+// slot layout (points): [flat 512 | sharp 256 | less flat LINS_CLOUD_MAX | less sharp 1920]; the less-sharp cloud
+// follows the less-flat one so that the multi-resident kernel's sorted copy (positions 0 .. n_all) stays in the slot
+constexpr long long kSlotFlat = 0, kSlotSharp = 512, kSlotLessFlat = 768, kSlotLessSharp = 768 + LINS_CLOUD_MAX;
+constexpr long long kSlotSize = kSlotLessSharp + 1920;
+inline long long slot_base(int stream, int slot) { return ((long long)stream * 2 + slot) * kSlotSize; }
+}  // namespace
+
 namespace lins {
 void streams_free(lins_ctx* ctx) {
   auto& t = ctx->st;
   (void)hipFree(t.d_arena), (void)hipFree(t.d_sorted), (void)hipFree(t.d_desc), (void)hipFree(t.d_jobs), (void)hipFree(t.d_desc_next);
   t.d_desc_next = nullptr, t.index_ready = false;
   streams_filter_free(ctx);
-  (void)hipFree(t.d_gsorted), (void)hipFree(t.d_gridtab);
+  (void)hipFree(t.d_gsorted), (void)hipFree(t.d_gridtab), (void)hipFree(t.d_outl);
   t = lins_ctx::Streams{};
+}
+
+int streams_map_clouds(lins_ctx* ctx, int stream, StreamMapClouds* v) {
+  auto& t = ctx->st;
+  if (t.n <= 0 || t.failed) return LINS_E_STATE;
+  if (stream < 0 || stream >= t.n) return LINS_E_ARG;
+  if (t.last_counts[(size_t)stream * 2] < 0) return LINS_E_STATE;
+  const int last = t.cur[stream] ^ 1;  // the slot of the scan taken in last
+  const long long b = ((long long)stream * 2 + last) * kSlotSize;
+  v->src[0] = t.d_arena + b + kSlotLessSharp, v->n[0] = t.last_counts[(size_t)stream * 2];
+  v->src[1] = t.d_arena + b + kSlotLessFlat, v->n[1] = t.last_counts[(size_t)stream * 2 + 1];
+  v->src[2] = t.d_outl + (size_t)(stream * 2 + last) * LINS_OUTLIER_MAX, v->n[2] = t.outl_counts[(size_t)stream * 2 + last];
+  return LINS_OK;
 }
 
 void fe_free(lins_ctx* ctx) {
   auto& f = ctx->fe;
   void* ptrs[] = {f.d_scans, f.d_cloud, f.d_out, f.d_range, f.d_col, f.d_ground, f.d_picks, f.d_counts};
   for (void* p : ptrs) (void)hipFree(p);
-  void* sg[] = {f.d_raw, f.d_raws, f.d_cellidx, f.d_segrows, f.d_outliers};
+  void* sg[] = {f.d_raw, f.d_raws, f.d_cellidx, f.d_segrows, f.d_outliers, f.d_outl};
   for (void* p : sg) (void)hipFree(p);
   (void)hipHostFree(f.h_raw);
   (void)hipHostFree(f.h_cloud), (void)hipHostFree(f.h_range), (void)hipHostFree(f.h_col), (void)hipHostFree(f.h_ground);
@@ -145,14 +166,16 @@ static int fe_launch(lins_ctx* ctx, int n, double scan_period, float4* out_base,
 
 // image_projection stage on the device: n raw clouds -> the front-end's device input buffers (f.d_cloud /
 // d_range / d_col / d_ground at k * LINS_CLOUD_MAX) and the head of each FeScan (n, ring indices, orientations);
-// offs = where the front-end will later put the four feature clouds of each scan
-static int sg_run(lins_ctx* ctx, int n, const lins_point* const* raw, const int32_t* n_raw, const long long (*offs)[4]) {
+// offs = where the front-end will later put the four feature clouds of each scan; outl / o_slots: null, or the arena the
+// outlier clouds go to and the slot of each scan in it (LINS_OUTLIER_MAX points per slot)
+static int sg_run(lins_ctx* ctx, int n, const lins_point* const* raw, const int32_t* n_raw, const long long (*offs)[4],
+                  float4* outl = nullptr, const int* o_slots = nullptr) {
   const size_t N = LINS_CLOUD_MAX;
   size_t total = 0;
   std::vector<SgRaw> hr(n);
   for (int k = 0; k < n; ++k) {
     if (!raw[k] || n_raw[k] < 2 || n_raw[k] > 65536) return LINS_E_ARG;
-    hr[k] = SgRaw{(long long)total, n_raw[k], 0};
+    hr[k] = SgRaw{(long long)total, n_raw[k], outl ? o_slots[k] : 0};
     total += align4(n_raw[k]);
   }
   int rc = fe_alloc(ctx, n);
@@ -227,23 +250,34 @@ static int sg_run(lins_ctx* ctx, int n, const lins_point* const* raw, const int3
   const float ax = (float)(0.2f / 180.0 * M_PI), ay = (float)(2.0f / 180.0 * M_PI);
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   launch_segment(ctx->stream, n, f.d_raws, f.d_raw, std::sin(ax), std::cos(ax), std::sin(ay), std::cos(ay), 1.0472f,
-                 f.d_cellidx, f.d_segrows, f.d_scans, f.d_cloud, f.d_range, f.d_col, f.d_ground, f.d_outliers);
+                 f.d_cellidx, f.d_segrows, f.d_scans, f.d_cloud, f.d_range, f.d_col, f.d_ground, f.d_outliers, outl);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream));
   return LINS_OK;
 }
 
-int lins_segment_batch(lins_ctx* ctx, int n, const lins_point* const* raw, const int32_t* n_raw, lins_segmented_scan* out) {
-  if (!ctx || n < 0 || (n && (!raw || !n_raw || !out))) return LINS_E_ARG;
-  if (n == 0) return LINS_OK;
+// lins_segment_batch (outlier == nullptr: the kernel runs without the emission) and lins_segment_batch_outliers
+static int segment_batch_impl(lins_ctx* ctx, int n, const lins_point* const* raw, const int32_t* n_raw, lins_segmented_scan* out,
+                              lins_point* const* outlier) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (int rcs = split_join(ctx)) return rcs;
   for (int k = 0; k < n; ++k)
-    if (!out[k].cloud || !out[k].range || !out[k].col || !out[k].ground) return LINS_E_ARG;
+    if (!out[k].cloud || !out[k].range || !out[k].col || !out[k].ground || (outlier && !outlier[k])) return LINS_E_ARG;
   std::vector<long long> offs((size_t)n * 4, 0);
-  int rc = sg_run(ctx, n, raw, n_raw, reinterpret_cast<const long long(*)[4]>(offs.data()));
-  if (rc) return rc;
   auto& f = ctx->fe;
+  std::vector<int> o_slots((size_t)n);
+  if (outlier) {
+    if (int rc0 = fe_alloc(ctx, n)) return rc0;  // (first: growing the front-end's buffers drops every buffer of `f`)
+    if (f.outl_cap < n) {
+      (void)hipFree(f.d_outl);
+      f.d_outl = nullptr, f.outl_cap = 0;
+      HIP_TRY(ctx, hipMalloc((void**)&f.d_outl, (size_t)n * LINS_OUTLIER_MAX * sizeof(float4)));
+      f.outl_cap = n;
+    }
+    for (int k = 0; k < n; ++k) o_slots[k] = k;
+  }
+  int rc = sg_run(ctx, n, raw, n_raw, reinterpret_cast<const long long(*)[4]>(offs.data()), outlier ? f.d_outl : nullptr, o_slots.data());
+  if (rc) return rc;
   std::vector<FeScan> hs(n);
   std::vector<int> outl(n);
   HIP_TRY(ctx, hipMemcpyAsync(hs.data(), f.d_scans, (size_t)n * sizeof(FeScan), hipMemcpyDeviceToHost, ctx->stream));
@@ -262,9 +296,25 @@ int lins_segment_batch(lins_ctx* ctx, int n, const lins_point* const* raw, const
     HIP_TRY(ctx, hipMemcpyAsync(const_cast<float*>(o.range), f.d_range + b, o.n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint32_t*>(o.col), f.d_col + b, o.n * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(const_cast<uint8_t*>(o.ground), f.d_ground + b, o.n, hipMemcpyDeviceToHost, ctx->stream));
+    if (outlier && o.n_outlier)
+      HIP_TRY(ctx, hipMemcpyAsync(outlier[k], f.d_outl + (size_t)k * LINS_OUTLIER_MAX, (size_t)o.n_outlier * sizeof(float4),
+                                  hipMemcpyDeviceToHost, ctx->stream));
   }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return LINS_OK;
+}
+
+int lins_segment_batch(lins_ctx* ctx, int n, const lins_point* const* raw, const int32_t* n_raw, lins_segmented_scan* out) {
+  if (!ctx || n < 0 || (n && (!raw || !n_raw || !out))) return LINS_E_ARG;
+  if (n == 0) return LINS_OK;
+  return segment_batch_impl(ctx, n, raw, n_raw, out, nullptr);
+}
+
+int lins_segment_batch_outliers(lins_ctx* ctx, int n, const lins_point* const* raw, const int32_t* n_raw, lins_segmented_scan* out,
+                                lins_point* const* outlier) {
+  if (!ctx || n < 0 || (n && (!raw || !n_raw || !out || !outlier))) return LINS_E_ARG;
+  if (n == 0) return LINS_OK;
+  return segment_batch_impl(ctx, n, raw, n_raw, out, outlier);
 }
 
 int lins_last_segment_ms(lins_ctx* ctx, float* kernel_ms) {
@@ -310,13 +360,6 @@ int lins_extract_features_batch(lins_ctx* ctx, int n, const lins_segmented_scan*
 }
 
 // ---- device-resident streams: front-end -> IESKF update -> re-projection without the clouds leaving HBM ----
-namespace {
-// slot layout (points): [flat 512 | sharp 256 | less flat LINS_CLOUD_MAX | less sharp 1920]; the less-sharp cloud
-// follows the less-flat one so that the multi-resident kernel's sorted copy (positions 0 .. n_all) stays in the slot
-constexpr long long kSlotFlat = 0, kSlotSharp = 512, kSlotLessFlat = 768, kSlotLessSharp = 768 + LINS_CLOUD_MAX;
-constexpr long long kSlotSize = kSlotLessSharp + 1920;
-inline long long slot_base(int stream, int slot) { return ((long long)stream * 2 + slot) * kSlotSize; }
-}  // namespace
 
 int lins_streams_init(lins_ctx* ctx, int n_streams) {
   if (!ctx || n_streams < 1) return LINS_E_ARG;
@@ -335,6 +378,8 @@ int lins_streams_init(lins_ctx* ctx, int n_streams) {
   HIP_TRY(ctx, hipMalloc((void**)&t.d_desc_next, (size_t)n_streams * sizeof(ScanDesc)));
   t.index_ready = false;
   HIP_TRY(ctx, hipMalloc(&t.d_jobs, (size_t)n_streams * 2 * sizeof(StreamCloud)));
+  HIP_TRY(ctx, hipMalloc((void**)&t.d_outl, (size_t)n_streams * 2 * LINS_OUTLIER_MAX * sizeof(float4)));
+  t.outl_counts.assign((size_t)n_streams * 2, 0), t.outl_put.assign((size_t)n_streams, 0), t.outl_pending = false;
   t.n = n_streams, t.cur.assign((size_t)n_streams, 0);
   t.last_counts.assign((size_t)n_streams * 2, -1);
   return LINS_OK;
@@ -411,15 +456,22 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
     o[0] = b + kSlotSharp, o[1] = b + kSlotLessSharp, o[2] = b + kSlotFlat, o[3] = b + kSlotLessFlat;
   }
   std::vector<int> counts;
+  // this scan's outlier cloud: slot cur of the stream, as its feature clouds (the count of a segmented step: what
+  // lins_streams_put_outliers left, else none)
+  std::vector<int> n_outl((size_t)n, 0);
   int rc;
   if (scans) {
+    if (t.outl_pending) n_outl = t.outl_put;
     rc = fe_run(ctx, n, scans, scan_period, t.d_arena, reinterpret_cast<const long long(*)[4]>(offs.data()), counts);
   } else {  // raw clouds: the image_projection stage on the device feeds the front-end where its output lies
-    rc = sg_run(ctx, n, raw, n_raw, reinterpret_cast<const long long(*)[4]>(offs.data()));
+    std::vector<int> o_slots((size_t)n);
+    for (int k = 0; k < n; ++k) o_slots[k] = k * 2 + cur[k];
+    rc = sg_run(ctx, n, raw, n_raw, reinterpret_cast<const long long(*)[4]>(offs.data()), t.d_outl, o_slots.data());
     if (rc) {
       guard.done = rc != LINS_E_HIP;  // (a rejected input has advanced nothing: only this scan's own slots were touched)
       return rc;
     }
+    HIP_TRY(ctx, hipMemcpyAsync(n_outl.data(), ctx->fe.d_outliers, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipEventElapsedTime(&ctx->fe.sg_ms, ctx->ev0, ctx->ev2));
     rc = fe_launch(ctx, n, scan_period, t.d_arena, counts, 0);
@@ -590,6 +642,7 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
     jobs[(size_t)k * 2 + 1] = StreamCloud{b + kSlotLessFlat, c[3], k};
     max_n = std::max(max_n, std::max(c[1], c[3]));
     t.last_counts[(size_t)k * 2] = c[1], t.last_counts[(size_t)k * 2 + 1] = c[3];
+    t.outl_counts[(size_t)k * 2 + cur[k]] = n_outl[k];
   }
   // ... and, when the next step's update will search through the LDS grid, their search index in the same pass
   // (grid_index_kernel<true>: one read of the new clouds for the re-projected arena copy, the grid-sorted copy and the
@@ -626,8 +679,48 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
   trace.mark("re-projection done (synced)");
   for (int k = 0; k < n; ++k)
     if (!gated[k]) t.cur[k] ^= 1;
+  t.outl_pending = false;
   guard.done = true;
   return LINS_OK;
+}
+
+int lins_streams_put_outliers(lins_ctx* ctx, const lins_point* const* outlier, const int32_t* n_outlier) {
+  if (!ctx || !outlier || !n_outlier) return LINS_E_ARG;
+  auto& t = ctx->st;
+  if (t.n <= 0 || t.failed) return LINS_E_STATE;
+  for (int k = 0; k < t.n; ++k) {
+    if (n_outlier[k] < 0 || n_outlier[k] > LINS_OUTLIER_MAX || (n_outlier[k] && !outlier[k])) return LINS_E_ARG;
+    for (int i = 0; i < n_outlier[k]; ++i) {
+      const lins_point& p = outlier[k][i];
+      if (!std::isfinite(p.x) || !std::isfinite(p.y) || !std::isfinite(p.z) || !std::isfinite(p.intensity)) return LINS_E_INPUT;
+    }
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rcs = split_join(ctx)) return rcs;
+  for (int k = 0; k < t.n; ++k)  // into the slot the next scan's clouds go to
+    if (n_outlier[k])
+      HIP_TRY(ctx, hipMemcpyAsync(t.d_outl + (size_t)(k * 2 + t.cur[k]) * LINS_OUTLIER_MAX, outlier[k], (size_t)n_outlier[k] * sizeof(float4),
+                                  hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // (the caller's clouds may go once this returns)
+  t.outl_put.assign(n_outlier, n_outlier + t.n), t.outl_pending = true;
+  return LINS_OK;
+}
+
+int lins_streams_map_cloud(lins_ctx* ctx, int stream, int which, lins_point* out, int cap) {
+  if (!ctx || which < 0 || which > 2) return LINS_E_ARG;
+  StreamMapClouds v;
+  if (int rc = streams_map_clouds(ctx, stream, &v)) return rc;
+  const int cnt = v.n[which];
+  if (cnt > cap) return LINS_E_CAPACITY;
+  if (!cnt) return 0;
+  if (!out) return LINS_E_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipMemcpy(out, v.src[which], (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost));
+  for (int i = 0; i < cnt; ++i) {  // the mapping node's axes (SE:1128-1131): (x, y, z) <- (y, z, x)
+    const lins_point p = out[i];
+    out[i] = lins_point{p.y, p.z, p.x, p.intensity};
+  }
+  return cnt;
 }
 
 int lins_streams_stats(lins_ctx* ctx, float* frontend_ms, float* update_ms, float* reproject_ms) {

@@ -33,6 +33,7 @@ typedef enum { ncclInt8 = 0, ncclChar = 0 } ncclDataType_t;
 
 #include "../../include/lins_host.h"
 #include "../../include/lins_streams_filter.h"
+#include "../../include/lins_streams_map.h"
 #include "ieskf_device.h"
 #include "ieskf_grid.h"
 #include "lins_ctx_priv.h"
@@ -126,6 +127,8 @@ struct lins_ctx {
     SgRaw* d_raws = nullptr;
     unsigned* d_cellidx = nullptr;
     int *d_segrows = nullptr, *d_outliers = nullptr;
+    float4* d_outl = nullptr;  // lins_segment_batch_outliers: the outlier clouds, LINS_OUTLIER_MAX points per scan (outl_cap scans)
+    int outl_cap = 0;
     float sg_ms = 0.f;
   } fe;
   // device-resident streams (lins_streams_step): per stream two feature slots (this scan's / the last
@@ -140,6 +143,12 @@ struct lins_ctx {
     bool index_ready = false;         // d_gsorted / d_gridtab hold the index of the resident last scans (built by the step before)
     StreamCloud* d_jobs = nullptr;
     std::vector<int> last_counts;  // per stream: less sharp, less flat of the resident last scan (-1: none yet)
+    // the outlier clouds (lins_streams_map_cloud, lins_local_map_build_streams): two slots of LINS_OUTLIER_MAX points per
+    // stream, flipped with the feature slots — a raw step's segmentation writes slot cur, lins_streams_put_outliers too
+    float4* d_outl = nullptr;
+    std::vector<int> outl_counts;  // [stream][slot]
+    std::vector<int> outl_put;     // per stream: the count lins_streams_put_outliers left for the next segmented step
+    bool outl_pending = false;
     bool failed = false;           // a step stopped half way (HIP error): the resident clouds are not trustworthy any more
     float update_ms = 0.f, frontend_ms = 0.f, reproject_ms = 0.f;
     // the streams' filter (lins_streams_filter_*, lins_streams_step_imu*; lins_capi_filter.hip): what lins_filter holds

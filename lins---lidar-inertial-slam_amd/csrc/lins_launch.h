@@ -18,6 +18,7 @@ struct GridTables;  // ieskf_grid.h
 struct LmCarry;     // lm_math.h
 struct MapRoundParams;
 struct LmSeg;       // local_map.h
+struct LmScanSeg;
 struct LmJob;
 struct LmState;
 struct ArChunk;    // keyframe_archive.h
@@ -64,7 +65,8 @@ int fe_pick_stride();  // ints of pick scratch per scan
 void launch_frontend(hipStream_t stream, int n_scans, const FeScan* scans, const float4* cloud, const float* range, const unsigned* col, const unsigned char* ground, double scan_period, int* picks,
                      float4* out, int* out_counts);
 void launch_segment(hipStream_t stream, int n_scans, const SgRaw* raws, const float4* raw, float sin_ax, float cos_ax, float sin_ay, float cos_ay, float theta, unsigned* cellidx, int* seg_rows,
-                    FeScan* fe_scans, float4* out_cloud, float* out_range, unsigned* out_col, unsigned char* out_ground, int* out_outliers);
+                    FeScan* fe_scans, float4* out_cloud, float* out_range, unsigned* out_col, unsigned char* out_ground, int* out_outliers,
+                    float4* out_outl);  // out_outl: null, or the outlier arena (LINS_OUTLIER_MAX points per slot; scan k's slot: raws[k].o_slot)
 
 // ---- filter_kernels.hip: the streams' device-resident filter (filter_math.h).  imu: rows (dt, acc, gyr), stream k's
 // n_imu[k] rows start at row imu_off[k]; aux: lins_filt::kAux doubles per stream.  finish mode[k]: 0 leave the filter,
@@ -90,6 +92,9 @@ void launch_debug_lm_step(hipStream_t stream, int n, int wave_version, const dou
 
 // ---- local_map_kernels.hip: the mapping node's local map
 void launch_lm_transform(hipStream_t s, int n_blocks, const LmSeg* segs, const int2* blocks, const float4* frames, float4* stage, LmState* states);
+// the scan clouds of a build out of the streams' arenas: (x, y, z) <- (y, z, x) into the staging arena at the segment's
+// dst, f32 box folded into its job's state, a point outside the input contract flags the job (blocks: (segment, tile))
+void launch_lm_stage_scans(hipStream_t s, int n_blocks, const LmScanSeg* segs, const int2* blocks, float4* stage, LmState* states);
 // one stage: jobs [j0, j0 + n_jobs), tiles [0, n_tiles) of `tiles`
 void launch_lm_stage(hipStream_t s, int j0, int n_jobs, int n_tiles, const int2* tiles, const LmJob* jobs, LmState* states, float4* stage, unsigned* keys_a, unsigned* keys_b, int* vals_a, int* vals_b,
                      int* hist, int* tilecnt, int* starts, float4* out);

@@ -43,7 +43,8 @@ struct LocalMap {
   std::vector<int> slots;
   std::vector<long long> off;  // 6 per entry
   std::vector<lins_local_map_sizes> sizes;
-  float ms = 0.f;
+  float ms = 0.f, stage_ms = 0.f;  // stage_ms: the staging kernel of lins_local_map_build_streams (inside ms)
+  hipEvent_t ev_stage = nullptr;
   uint64_t points_in = 0;
 };
 
@@ -52,6 +53,7 @@ void local_free(void* p) {
   (void)hipFree(m->d_frames), (void)hipFree(m->d_stage), (void)hipFree(m->d_out), (void)hipFree(m->d_ka), (void)hipFree(m->d_kb);
   (void)hipFree(m->d_va), (void)hipFree(m->d_vb), (void)hipFree(m->d_starts), (void)hipFree(m->d_hist), (void)hipFree(m->d_tilecnt);
   (void)hipFree(m->d_tab), (void)hipHostFree(m->h_raw), (void)hipHostFree(m->h_tab), (void)hipHostFree(m->h_states);
+  if (m->ev_stage) (void)hipEventDestroy(m->ev_stage);
   delete m;
 }
 
@@ -170,19 +172,14 @@ int lins_local_map_push(lins_ctx* ctx, int slot, const lins_keyframe* f) {
   return LINS_OK;
 }
 
-int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_local_scan* scans, lins_local_map_sizes* out) {
-  if (!ctx || n < 0 || (n && (!slots || !scans))) return LINS_E_ARG;
-  LocalMap* m = local_of(ctx);
-  if (!m->n_slots) return LINS_E_STATE;
-  for (int k = 0; k < n; ++k) {
-    if (slots[k] < 0 || slots[k] >= m->n_slots) return LINS_E_ARG;
-    const lins_local_scan& s = scans[k];
-    if (s.n_corner < 0 || s.n_surf < 0 || s.n_outlier < 0 || (s.n_corner && !s.corner) || (s.n_surf && !s.surf) ||
-        (s.n_outlier && !s.outlier))
-      return LINS_E_ARG;
-  }
+// The build behind lins_local_map_build (scans: the entries' scan clouds on the host — checked, boxed and packed here,
+// one upload) and lins_local_map_build_streams (from: the same clouds where they lie in the streams' arenas — one
+// kernel does that work); arguments checked by the caller.  Everything else is the same job table and the same launches.
+static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t* slots, const lins_local_scan* scans,
+                                const StreamMapClouds* from, lins_local_map_sizes* out) {
   HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
   m->built = false;
+  auto scan_n = [&](int k, int q) { return from ? from[k].n[q] : (q == 0 ? scans[k].n_corner : q == 1 ? scans[k].n_surf : scans[k].n_outlier); };
   const int NJ = 6 * n;  // jobs: stage A 5 per entry (5k + cloud), stage B one per entry (5n + k)
   std::vector<LmJob> jobs(NJ);
   std::vector<LmState> states(NJ);
@@ -195,8 +192,8 @@ int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_
       const KeyFrame& f = m->meta[(size_t)s * m->window + (m->head[s] + i) % m->window];
       cap[5 * k] += f.n[0], cap[5 * k + 1] += f.n[1] + f.n[2];
     }
-    cap[5 * k + 2] = scans[k].n_corner, cap[5 * k + 3] = scans[k].n_surf, cap[5 * k + 4] = scans[k].n_outlier;
-    cap[5 * n + k] = (long long)scans[k].n_surf + scans[k].n_outlier;
+    cap[5 * k + 2] = scan_n(k, 0), cap[5 * k + 3] = scan_n(k, 1), cap[5 * k + 4] = scan_n(k, 2);
+    cap[5 * n + k] = (long long)scan_n(k, 1) + scan_n(k, 2);
   }
   for (int j = 0; j < NJ; ++j)
     if (cap[j] > INT_MAX / 2) return LINS_E_CAPACITY;
@@ -240,9 +237,9 @@ int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_
     jobs[5 * k + 4].feed_after = 5 * k + 3;
   }
   int rc;
-  if ((rc = grow_pinned(ctx, &m->h_raw, &m->cap_raw, raw_total))) return rc;
+  if (scans && (rc = grow_pinned(ctx, &m->h_raw, &m->cap_raw, raw_total))) return rc;
   // raw scans: input contract, f32 box (the min / max the device would fold), packed for one upload
-  for (int k = 0; k < n; ++k) {
+  for (int k = 0; k < n && scans; ++k) {
     const lins_point* c[3] = {scans[k].corner, scans[k].surf, scans[k].outlier};
     const int cn[3] = {scans[k].n_corner, scans[k].n_surf, scans[k].n_outlier};
     for (int q = 0; q < 3; ++q) {
@@ -258,6 +255,16 @@ int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_
       if (cn[q]) std::memcpy(m->h_raw + jobs[j].off_in, c[q], (size_t)cn[q] * sizeof(float4));
     }
   }
+  // ... or staged on the device out of the streams' arenas: one segment per (entry, cloud), blocks of kLmTile points
+  std::vector<LmScanSeg> ssegs;
+  std::vector<int2> sblocks;
+  for (int k = 0; k < n && from; ++k)
+    for (int q = 0; q < 3; ++q) {
+      const int cnt = from[k].n[q], j = 5 * k + 2 + q;
+      if (!cnt) continue;
+      for (int b = 0; b < (cnt + kLmTile - 1) / kLmTile; ++b) sblocks.push_back(make_int2((int)ssegs.size(), b));
+      ssegs.push_back(LmScanSeg{from[k].src[q], jobs[j].off_in, cnt, j});
+    }
   // the window's clouds: one segment per (frame, cloud), blocks of kLmTile points
   std::vector<LmSeg> segs;
   std::vector<int2> blocks;
@@ -288,10 +295,11 @@ int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_
     for (int t = 0; t < jobs[j].ntiles; ++t) tiles.push_back(make_int2(j, t));
   const int tiles_a = n ? jobs[5 * n].tile0 : 0;  // stage A's tiles come first
   const int tiles_b = (int)tiles_total - tiles_a;
-  // one table upload: jobs | states | segments | blocks | tiles
+  // one table upload: jobs | states | segments | blocks | tiles | scan segments | scan blocks
   const size_t o_jobs = 0, o_states = align64(o_jobs + NJ * sizeof(LmJob)), o_segs = align64(o_states + NJ * sizeof(LmState)),
                o_blocks = align64(o_segs + segs.size() * sizeof(LmSeg)), o_tiles = align64(o_blocks + blocks.size() * sizeof(int2)),
-               tab_bytes = align64(o_tiles + tiles.size() * sizeof(int2));
+               o_ssegs = align64(o_tiles + tiles.size() * sizeof(int2)), o_sblocks = align64(o_ssegs + ssegs.size() * sizeof(LmScanSeg)),
+               tab_bytes = align64(o_sblocks + sblocks.size() * sizeof(int2));
   if ((rc = grow_pinned(ctx, &m->h_tab, &m->cap_htab, tab_bytes))) return rc;
   if ((rc = grow_pinned(ctx, &m->h_states, &m->cap_hstates, NJ * sizeof(LmState)))) return rc;
   std::memcpy(m->h_tab + o_jobs, jobs.data(), NJ * sizeof(LmJob));
@@ -299,6 +307,9 @@ int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_
   if (!segs.empty()) std::memcpy(m->h_tab + o_segs, segs.data(), segs.size() * sizeof(LmSeg));
   if (!blocks.empty()) std::memcpy(m->h_tab + o_blocks, blocks.data(), blocks.size() * sizeof(int2));
   if (!tiles.empty()) std::memcpy(m->h_tab + o_tiles, tiles.data(), tiles.size() * sizeof(int2));
+  if (!ssegs.empty()) std::memcpy(m->h_tab + o_ssegs, ssegs.data(), ssegs.size() * sizeof(LmScanSeg));
+  if (!sblocks.empty()) std::memcpy(m->h_tab + o_sblocks, sblocks.data(), sblocks.size() * sizeof(int2));
+  if (from && !m->ev_stage) HIP_TRY(ctx, hipEventCreate(&m->ev_stage));
   if ((rc = grow(ctx, &m->d_tab, &m->cap_tab, tab_bytes))) return rc;
   if (m->cap_stage < std::max<size_t>(stage_total, 1)) {  // the staging arena and the sort's scratch: same extent
     size_t c[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -322,12 +333,16 @@ int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_
   hipStream_t st = ctx_stream(ctx);
   hipEvent_t e0, e1;
   ctx_events(ctx, &e0, &e1);
-  if (raw_total) HIP_TRY(ctx, hipMemcpyAsync(m->d_stage, m->h_raw, raw_total * sizeof(float4), hipMemcpyHostToDevice, st));
+  if (raw_total && scans) HIP_TRY(ctx, hipMemcpyAsync(m->d_stage, m->h_raw, raw_total * sizeof(float4), hipMemcpyHostToDevice, st));
   if (tab_bytes) HIP_TRY(ctx, hipMemcpyAsync(m->d_tab, m->h_tab, tab_bytes, hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipEventRecord(e0, st));
   const LmJob* d_jobs = (const LmJob*)(m->d_tab + o_jobs);
   LmState* d_states = (LmState*)(m->d_tab + o_states);
   const int2* d_tiles = (const int2*)(m->d_tab + o_tiles);
+  if (from) {
+    launch_lm_stage_scans(st, (int)sblocks.size(), (const LmScanSeg*)(m->d_tab + o_ssegs), (const int2*)(m->d_tab + o_sblocks), m->d_stage, d_states);
+    HIP_TRY(ctx, hipEventRecord(m->ev_stage, st));
+  }
   launch_lm_transform(st, (int)blocks.size(), (const LmSeg*)(m->d_tab + o_segs), (const int2*)(m->d_tab + o_blocks), m->d_frames, m->d_stage, d_states);
   launch_lm_stage(st, 0, 5 * n, tiles_a, d_tiles, d_jobs, d_states, m->d_stage, m->d_ka, m->d_kb, m->d_va, m->d_vb, m->d_hist,
                   m->d_tilecnt, m->d_starts, m->d_out);
@@ -338,6 +353,8 @@ int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_
   if (NJ) HIP_TRY(ctx, hipMemcpyAsync(m->h_states, d_states, NJ * sizeof(LmState), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   HIP_TRY(ctx, hipEventElapsedTime(&m->ms, e0, e1));
+  m->stage_ms = 0.f;
+  if (from) HIP_TRY(ctx, hipEventElapsedTime(&m->stage_ms, e0, m->ev_stage));
   m->points_in = pts_in;
   const LmState* S = (const LmState*)m->h_states;
   m->slots.assign(slots, slots + n);
@@ -363,6 +380,42 @@ int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_
     if (out) out[k] = z;
   }
   m->built = true;
+  return LINS_OK;
+}
+
+int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_local_scan* scans, lins_local_map_sizes* out) {
+  if (!ctx || n < 0 || (n && (!slots || !scans))) return LINS_E_ARG;
+  LocalMap* m = local_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  for (int k = 0; k < n; ++k) {
+    if (slots[k] < 0 || slots[k] >= m->n_slots) return LINS_E_ARG;
+    const lins_local_scan& s = scans[k];
+    if (s.n_corner < 0 || s.n_surf < 0 || s.n_outlier < 0 || (s.n_corner && !s.corner) || (s.n_surf && !s.surf) ||
+        (s.n_outlier && !s.outlier))
+      return LINS_E_ARG;
+  }
+  static const lins_local_scan none{};
+  return local_map_build_impl(ctx, m, n, slots, n ? scans : &none, nullptr, out);
+}
+
+int lins_local_map_build_streams(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* streams, lins_local_map_sizes* out) {
+  if (!ctx || n < 0 || (n && (!slots || !streams))) return LINS_E_ARG;
+  LocalMap* m = local_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  std::vector<StreamMapClouds> from((size_t)std::max(n, 1));
+  for (int k = 0; k < n; ++k) {
+    if (slots[k] < 0 || slots[k] >= m->n_slots) return LINS_E_ARG;
+    for (int i = 0; i < k; ++i)
+      if (streams[i] == streams[k]) return LINS_E_ARG;  // (a stream may appear once)
+  }
+  for (int k = 0; k < n; ++k)
+    if (int rc = streams_map_clouds(ctx, streams[k], &from[k])) return rc;
+  return local_map_build_impl(ctx, m, n, slots, nullptr, from.data(), out);
+}
+
+int lins_last_local_map_stage_ms(lins_ctx* ctx, float* stage_ms) {
+  if (!ctx || !stage_ms) return LINS_E_ARG;
+  *stage_ms = local_of(ctx)->stage_ms;
   return LINS_OK;
 }
 

@@ -32,7 +32,7 @@ static_assert(sizeof(FeScan) == 192, "FeScan layout");
 struct SgRaw {  // one raw cloud of the image_projection stage (segment_kernels.hip)
   long long off;  // first raw point of the scan
   int n;
-  int pad;
+  int o_slot;     // slot of the outlier arena this scan's outlier cloud goes to (launch_segment)
 };
 static_assert(sizeof(SgRaw) == 16, "SgRaw layout");
 

@@ -50,6 +50,13 @@ struct LmSeg {  // one cloud of one window frame moved into the map frame
 };
 static_assert(sizeof(LmSeg) == 64, "LmSeg layout");
 
+struct LmScanSeg {  // one scan cloud of one entry taken from a stream where it lies (lins_local_map_build_streams)
+  const float4* src;   // the stream's cloud, sensor axes
+  long long dst;       // staging offset (the job's off_in)
+  int n, job;
+};
+static_assert(sizeof(LmScanSeg) == 24, "LmScanSeg layout");
+
 inline __host__ __device__ unsigned lm_enc(float f) {  // order-preserving float -> unsigned
   unsigned u;
   __builtin_memcpy(&u, &f, 4);

@@ -89,6 +89,44 @@ __global__ __launch_bounds__(kLmTile) void lm_transform_kernel(const LmSeg* __re
   fold_box(&states[s.job], q.x, q.y, q.z, valid);
 }
 
+// The scan clouds of lins_local_map_build_streams: what lins_local_map_build's host pass does to the clouds it is handed —
+// the input contract, the f32 box, the packing into the staging arena — for clouds that lie in the streams' arenas in
+// the sensor's axes.  The box is folded wave -> LDS -> one set of six atomics per workgroup (archive_kernels.hip's
+// gather): min / max of the order-preserving encoding, the bits the host's fold leaves.
+__global__ __launch_bounds__(kLmTile) void lm_stage_scans_kernel(const LmScanSeg* __restrict__ segs, const int2* __restrict__ blocks,
+                                                                 float4* __restrict__ stage, LmState* __restrict__ states) {
+  const int2 b = blocks[blockIdx.x];
+  const LmScanSeg s = segs[b.x];
+  const int i = b.y * kLmTile + threadIdx.x;
+  const bool valid = i < s.n;
+  float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+  bool bad = false;
+  if (valid) {
+    const float4 p = s.src[i];
+    q = make_float4(p.y, p.z, p.x, p.w);  // the mapping node's axes (SE:1128-1131)
+    stage[s.dst + i] = q;
+    bad = !(fabsf(q.x) <= 1e6f && fabsf(q.y) <= 1e6f && fabsf(q.z) <= 1e6f);  // (true for NaN and infinities)
+  }
+  if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&states[s.job].flags, 1);
+  __shared__ float wbox[kWaves][6];
+  float v[6] = {valid ? q.x : INFINITY, valid ? q.y : INFINITY, valid ? q.z : INFINITY,
+                valid ? q.x : -INFINITY, valid ? q.y : -INFINITY, valid ? q.z : -INFINITY};
+  for (int o = 32; o; o >>= 1)
+    for (int a = 0; a < 3; ++a) v[a] = fminf(v[a], __shfl_xor(v[a], o)), v[3 + a] = fmaxf(v[3 + a], __shfl_xor(v[3 + a], o));
+  if ((threadIdx.x & 63) == 0)
+    for (int a = 0; a < 6; ++a) wbox[threadIdx.x >> 6][a] = v[a];
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const int a = threadIdx.x;
+    float lo = INFINITY, hi = -INFINITY;
+    for (int w = 0; w < kWaves; ++w) lo = fminf(lo, wbox[w][a]), hi = fmaxf(hi, wbox[w][3 + a]);
+    if (lo <= hi) {  // (a tile of the table holds at least one point)
+      LmState* st = &states[s.job];
+      atomicMin(&st->mn[a], lm_enc(lo)), atomicMax(&st->mx[a], lm_enc(hi));
+    }
+  }
+}
+
 __global__ void lm_setup_kernel(int j0, int n_jobs, const LmJob* __restrict__ jobs, LmState* __restrict__ states) {
   const int j = j0 + blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= j0 + n_jobs) return;
@@ -292,6 +330,10 @@ __global__ __launch_bounds__(kLmTile) void lm_sum_kernel(const int2* __restrict_
 void launch_lm_transform(hipStream_t s, int n_blocks, const LmSeg* segs, const int2* blocks, const float4* frames, float4* stage, LmState* states) {
   if (n_blocks)
     hipLaunchKernelGGL(lm_transform_kernel, dim3(n_blocks), dim3(kLmTile), 0, s, segs, blocks, frames, stage, states);
+}
+
+void launch_lm_stage_scans(hipStream_t s, int n_blocks, const LmScanSeg* segs, const int2* blocks, float4* stage, LmState* states) {
+  if (n_blocks) hipLaunchKernelGGL(lm_stage_scans_kernel, dim3(n_blocks), dim3(kLmTile), 0, s, segs, blocks, stage, states);
 }
 
 // the kernels of a stage one by one (what launch_lm_stage runs; the key-frame archive runs the same kernels around its

@@ -44,7 +44,7 @@ struct SgConsts {
 };
 
 struct SgLds {
-  unsigned char flags[kSgCells];  // bit 0 right, bit 1 "+255", bit 2 down edge; bit 3 groundMat == 1; bit 7 eligible (labelMat == 0)
+  unsigned char flags[kSgCells];  // bit 0 right, bit 1 "+255", bit 2 down edge; bit 3 groundMat == 1; bit 4 outlier, bit 6 emitted (the emission sets them); bit 7 eligible (labelMat == 0)
   union {
     unsigned own[kSgCells];  // 1 + index of the point that owns the cell (0: no return) — during the projection
     float range[kSgCells];   // rangeMat — until the adjacency is built
@@ -53,6 +53,10 @@ struct SgLds {
       unsigned cnt2[kSgCells / 2];     // cells per label, two u16 counters per word (a count never exceeds 28 800)
     } seg;                             // — afterwards
     unsigned short emitted[kSgCells];  // the emitted cells in output order — once validity is decided
+    struct {
+      unsigned short emitted_[kSgCells];
+      unsigned short cell[LINS_OUTLIER_MAX];  // the outlier cells in output order (cell-by-cell path), behind the list
+    } outl;
   } u;
   int changed;
   int scan_tmp[20];
@@ -91,7 +95,8 @@ __global__ __launch_bounds__(kSgBlock) void segment_kernel(const SgRaw* __restri
                                                            SgConsts k, unsigned* __restrict__ cellidx, int* __restrict__ seg_rows,
                                                            unsigned char* __restrict__ fe_scans, float4* __restrict__ out_cloud,
                                                            float* __restrict__ out_range, unsigned* __restrict__ out_col,
-                                                           unsigned char* __restrict__ out_ground, int* __restrict__ out_outliers) {
+                                                           unsigned char* __restrict__ out_ground, int* __restrict__ out_outliers,
+                                                           float4* __restrict__ out_outl) {
   SgLds& L = g_sg;
 #ifdef LINS_SG_PROF
   long long sg_t0 = clock64();
@@ -343,15 +348,22 @@ __global__ __launch_bounds__(kSgBlock) void segment_kernel(const SgRaw* __restri
     const int s = label[c], np = count_of(s);
     return np >= 30 || (np >= 5 && __popc(rws[s]) >= 3);
   };
-  int mine = 0;
+  // The outlier cloud (IP:300-303: the cells of invalid segments above the ground rows, every fifth column, as
+  // fullCloud points) goes to slot rw.o_slot of out_outl — a null arena skips it (uniform over the workgroup).
+  const bool want_outl = out_outl != nullptr;
+  int mine = 0, mine_o = 0;
   unsigned emit_mask = 0;  // bit k: cell c_lo + k is emitted (kRun <= 32)
+  unsigned outl_mask = 0;  // bit k: cell c_lo + k is an outlier (disjoint from emit_mask)
   static_assert(kRun <= 32, "emit mask");
   for (int c = c_lo; c < c_hi; ++c) {
     const int i = c / kSgCols, j = c - i * kSgCols;
     bool emit = false;
     if (L.flags[c] & 0x80) {
       emit = feasible(c);
-      if (!emit && i > kSgGroundScanInd && j % 5 == 0) atomicAdd(&L.n_outlier, 1);
+      if (!emit && i > kSgGroundScanInd && j % 5 == 0) {
+        atomicAdd(&L.n_outlier, 1);
+        if (want_outl) ++mine_o, outl_mask |= 1u << (c - c_lo);
+      }
     } else if (L.flags[c] & 8) {
       emit = !(j % 5 != 0 && j > 5 && j < kSgCols - 5);
     }
@@ -359,8 +371,14 @@ __global__ __launch_bounds__(kSgBlock) void segment_kernel(const SgRaw* __restri
   }
   const int base = sg_block_scan(mine, tid, L.scan_tmp);
   const int total = L.scan_tmp[18];
+  // a thread's run is contiguous in raster order: the second scan puts the outliers in the reference's order
+  int pos_o = 0, total_o = 0;
+  if (want_outl) {
+    pos_o = sg_block_scan(mine_o, tid, L.scan_tmp);
+    total_o = L.scan_tmp[18];
+  }
   const size_t ob = (size_t)fo->off;
-  // (sg_block_scan's barriers: every thread is done with the labels and counters — their bytes take the list)
+  // (sg_block_scan's barriers: every thread is done with the labels and counters — their bytes take the lists)
   int pos = base;
   for (int c = c_lo; c < c_hi; ++c) {
     if (c % kSgCols == 0) L.ring_count[c / kSgCols] = pos;  // points emitted before ring i
@@ -369,6 +387,11 @@ __global__ __launch_bounds__(kSgBlock) void segment_kernel(const SgRaw* __restri
         L.u.emitted[c] = (unsigned short)pos++, L.flags[c] |= 0x40;  // cell -> output position, bit 6: emitted
       else
         L.u.emitted[pos++] = (unsigned short)c;                       // output position -> cell
+    } else if (outl_mask & (1u << (c - c_lo))) {  // (the same word as an emitted cell's: the two sets are disjoint)
+      if (by_point)
+        L.u.emitted[c] = (unsigned short)pos_o++, L.flags[c] |= 0x10;  // bit 4: outlier
+      else
+        L.u.outl.cell[pos_o++] = (unsigned short)c;
     }
   }
   __syncthreads();
@@ -379,18 +402,31 @@ __global__ __launch_bounds__(kSgBlock) void segment_kernel(const SgRaw* __restri
     out_cloud[ob + o] = p, out_col[ob + o] = (unsigned)j;
     out_ground[ob + o] = (L.flags[c] & 8) ? 1 : 0;
   };
+  float4* oc = out_outl + (want_outl ? (size_t)rw.o_slot * LINS_OUTLIER_MAX : 0);
+  auto put_outl = [&](int o, int c, float4 p) {
+    const int i = c / kSgCols, j = c - i * kSgCols;
+    p.w = (float)((double)(float)i + (double)(float)j / 10000.0);
+    oc[o] = p;
+  };
   if (by_point) {  // every owner of an emitted cell writes its point: coalesced reads of the raw cloud
 #pragma unroll
     for (int k = 0; k < kSgPts; ++k)
       if ((owner_mask >> k) & 1u) {
         const int c = cell_of[k];
-        if (L.flags[c] & 0x40) put((int)L.u.emitted[c], c, pts[tid + k * kSgBlock]);
+        if (L.flags[c] & 0x40)
+          put((int)L.u.emitted[c], c, pts[tid + k * kSgBlock]);
+        else if (L.flags[c] & 0x10)
+          put_outl((int)L.u.emitted[c], c, pts[tid + k * kSgBlock]);
       }
   } else {  // one thread per emitted point: coalesced stores, gathers of the owning points
 #pragma unroll 4
     for (int o = tid; o < total; o += kSgBlock) {
       const int c = L.u.emitted[o];
       put(o, c, pts[(int)ci[c] - 1]);
+    }
+    for (int o = tid; o < total_o; o += kSgBlock) {
+      const int c = L.u.outl.cell[o];
+      put_outl(o, c, pts[(int)ci[c] - 1]);
     }
   }
   if (tid == 0) L.ring_count[kSgRows] = total;
@@ -421,10 +457,10 @@ __global__ __launch_bounds__(kSgBlock) void segment_kernel(const SgRaw* __restri
 
 void launch_segment(hipStream_t stream, int n_scans, const SgRaw* raws, const float4* raw, float sin_ax, float cos_ax,
                     float sin_ay, float cos_ay, float theta, unsigned* cellidx, int* seg_rows, FeScan* fe_scans, float4* out_cloud,
-                    float* out_range, unsigned* out_col, unsigned char* out_ground, int* out_outliers) {
+                    float* out_range, unsigned* out_col, unsigned char* out_ground, int* out_outliers, float4* out_outl) {
   SgConsts k{sin_ax, cos_ax, sin_ay, cos_ay, theta};
   hipLaunchKernelGGL(segment_kernel, dim3(n_scans), dim3(kSgBlock), 0, stream, raws, raw, k, cellidx, seg_rows,
-                     (unsigned char*)fe_scans, out_cloud, out_range, out_col, out_ground, out_outliers);
+                     (unsigned char*)fe_scans, out_cloud, out_range, out_col, out_ground, out_outliers, out_outl);
 }
 
 }  // namespace lins

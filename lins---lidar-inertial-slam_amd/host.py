@@ -99,6 +99,21 @@ def frontend_segment(raw):
     return Segmented(cloud, rng, col, ground, c)
 
 
+def frontend_segment_outliers(raw):
+    """image_projection_node's /outlier_cloud on the host (lins_frontend_segment_outliers): (n, 4) f32, raster order."""
+    from ._ctypes_defs import OUTLIER_MAX
+
+    raw = np.ascontiguousarray(raw, dtype=np.float32).reshape(-1, 4)
+    out = np.zeros((OUTLIER_MAX, 4), np.float32)
+    L = lib()
+    L.lins_frontend_segment_outliers.argtypes = [C.POINTER(Point), C.c_int, C.POINTER(Point)]
+    L.lins_frontend_segment_outliers.restype = C.c_int
+    rc = L.lins_frontend_segment_outliers(raw.ctypes.data_as(C.POINTER(Point)), len(raw), out.ctypes.data_as(C.POINTER(Point)))
+    if rc < 0:
+        raise RuntimeError(f"lins_frontend_segment_outliers failed: {rc}")
+    return out[:rc].copy()
+
+
 def segmented_from_arrays(cloud, rng, col, ground, n, start_ring, end_ring, orientation, n_outlier=0):
     """A Segmented (lins_segmented_scan view) over caller-provided arrays — e.g. another implementation's output."""
     cloud = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 4)

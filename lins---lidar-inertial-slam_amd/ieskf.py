@@ -33,6 +33,8 @@ EXPORTS = [
     "lins_streams_filter_set", "lins_streams_filter_get", "lins_streams_filter_predict", "lins_streams_step_imu",
     "lins_streams_step_imu_raw", "lins_streams_filter_stats",
     "lins_loop_icp_default_params", "lins_loop_icp_batch", "lins_loop_icp_correspondences", "lins_last_loop_icp_stats",
+    "lins_segment_batch_outliers", "lins_streams_put_outliers", "lins_streams_map_cloud", "lins_local_map_build_streams",
+    "lins_last_local_map_stage_ms",
 ]
 
 
@@ -251,6 +253,31 @@ class IeskfContext:
         self._check(L.lins_local_map_build(self._h, n, sl.ctypes.data, arr, out))
         self._local_sizes = [out[k].as_dict() for k in range(n)]
         return self._local_sizes
+
+    def local_map_build_streams(self, slots, streams):
+        """local_map_build with entry k's scan clouds taken from stream streams[k] where they lie on the device
+        (lins_local_map_build_streams).  Returns the per-entry sizes dicts."""
+        from ._ctypes_defs import LocalMapSizesC
+
+        n = len(slots)
+        assert len(streams) == n
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        stv = np.ascontiguousarray(streams, dtype=np.int32)
+        out = (LocalMapSizesC * max(n, 1))()
+        L = lib()
+        L.lins_local_map_build_streams.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(LocalMapSizesC)]
+        self._local_sizes = []
+        self._check(L.lins_local_map_build_streams(self._h, n, sl.ctypes.data, stv.ctypes.data, out))
+        self._local_sizes = [out[k].as_dict() for k in range(n)]
+        return self._local_sizes
+
+    def local_map_stage_ms(self):
+        """HIP-event time (ms) of the staging kernel of the last local_map_build_streams"""
+        ms = C.c_float(0)
+        L = lib()
+        L.lins_last_local_map_stage_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self._check(L.lins_last_local_map_stage_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def local_map_push_scans(self, entries, poses):
         """the cornerDS / surfDS / outlierDS of the chosen entries of the last build become key frames of their slots"""
@@ -497,7 +524,11 @@ class IeskfContext:
         return [arr[k].as_dict() for k in range(n)], int(running.value)
 
     # -- image_projection_node on the device: raw clouds -> segmented scans --------------------
-    def segment_batch(self, raws):
+    def segment_batch_outliers(self, raws):
+        """segment_batch plus the outlier clouds: (list of host.Segmented, list of (n_outlier, 4) f32)."""
+        return self.segment_batch(raws, outliers=True)
+
+    def segment_batch(self, raws, outliers=False):
         """raws: list of (n,4) f32 raw clouds in firing order.  Returns a list of host.Segmented."""
         import importlib
 
@@ -519,14 +550,25 @@ class IeskfContext:
             out[k].ground = ground.ctypes.data_as(C.POINTER(C.c_uint8))
             keep.append((cloud, rng, col, ground))
         L = lib()
-        L.lins_segment_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(host.Point)), C.POINTER(C.c_int32),
-                                         C.POINTER(host.SegmentedScanC)]
-        self._check(L.lins_segment_batch(self._h, n, ptrs, counts, out))
+        if outliers:
+            from ._ctypes_defs import OUTLIER_MAX
+
+            obufs = [np.zeros((OUTLIER_MAX, 4), np.float32) for _ in range(n)]
+            optrs = (C.POINTER(host.Point) * n)(*[b.ctypes.data_as(C.POINTER(host.Point)) for b in obufs])
+            L.lins_segment_batch_outliers.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(host.Point)), C.POINTER(C.c_int32),
+                                                      C.POINTER(host.SegmentedScanC), C.POINTER(C.POINTER(host.Point))]
+            self._check(L.lins_segment_batch_outliers(self._h, n, ptrs, counts, out, optrs))
+        else:
+            L.lins_segment_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.POINTER(host.Point)), C.POINTER(C.c_int32),
+                                             C.POINTER(host.SegmentedScanC)]
+            self._check(L.lins_segment_batch(self._h, n, ptrs, counts, out))
         res = []
         for k in range(n):
             c = host.SegmentedScanC()
             C.memmove(C.byref(c), C.byref(out[k]), C.sizeof(c))
             res.append(host.Segmented(*keep[k], c))
+        if outliers:
+            return res, [obufs[k][: res[k].c.n_outlier].copy() for k in range(n)]
         return res
 
     def segment_ms(self):
@@ -713,6 +755,28 @@ class IeskfContext:
         L = lib()
         L.lins_streams_peek.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
         n = L.lins_streams_peek(self._h, stream, which, buf.ctypes.data, len(buf))
+        self._check(min(n, 0))
+        return buf[:n].copy()
+
+    def streams_put_outliers(self, outliers):
+        """one (m, 4) outlier cloud per stream for the NEXT segmented step (lins_streams_put_outliers)"""
+        n = self._streams
+        assert len(outliers) == n
+        cl = [np.ascontiguousarray(o, dtype=np.float32).reshape(-1, 4) for o in outliers]
+        pp = C.POINTER(Point)
+        ptrs = (pp * n)(*[c.ctypes.data_as(pp) if len(c) else pp() for c in cl])
+        cnt = (C.c_int32 * n)(*[len(c) for c in cl])
+        L = lib()
+        L.lins_streams_put_outliers.argtypes = [C.c_void_p, C.POINTER(pp), C.POINTER(C.c_int32)]
+        self._check(L.lins_streams_put_outliers(self._h, ptrs, cnt))
+
+    def streams_map_cloud(self, stream, which):
+        """what the mapping node reads of a stream's last step, in its axes (y, z, x): which = 0 corner last,
+        1 surf last, 2 outlier last (lins_streams_map_cloud)"""
+        buf = np.zeros((28800, 4), np.float32)
+        L = lib()
+        L.lins_streams_map_cloud.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        n = L.lins_streams_map_cloud(self._h, stream, which, buf.ctypes.data, len(buf))
         self._check(min(n, 0))
         return buf[:n].copy()
 
