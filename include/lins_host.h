@@ -290,6 +290,19 @@ int lins_host_loop_icp_step(const double sums[17], const lins_loop_icp_params* p
  * graph stays with the caller. */
 int lins_host_loop_pose_from(const double T[16], const lins_key_pose* wrong, lins_key_pose* pose_from);
 
+/* ---- the mapping node's own pose arithmetic (csrc/map_pose_math.h; the CPU restatement of lins_streams_map_step's two
+ * kernels, lins_streams_map.h).  Pose vectors are (rx, ry, rz, tx, ty, tz) as transformTobeMapped; all f32.
+ * transformAssociateToMap (LM:411-536): transformTobeMapped from transformBefMapped, transformAftMapped, transformSum.
+ * |rx| of the result near pi / 2 is outside the contract (the reference divides by its cosine).                      */
+void lins_host_map_associate(const float bef[6], const float aft[6], const float sum[6], float tobe[6]);
+/* the tail of transformUpdate (LM:567-576): with has_imu the blend tobe[0] <- 0.998 tobe[0] + 0.002 imu_pitch, tobe[2]
+ * <- 0.998 tobe[2] + 0.002 imu_roll (f64, rounded once to f32); then bef <- sum, aft <- tobe.  imu_roll / imu_pitch
+ * are imuHandler's interpolation (LM:539-565), the caller's.                                                        */
+void lins_host_map_transform_update(float tobe[6], int has_imu, float imu_roll, float imu_pitch, const float sum[6], float bef[6], float aft[6]);
+/* the key-frame rule (LM:1655-1671): returns 1 when the scan becomes a key frame — the f32 distance of prev
+ * (previousRobotPosPoint) to aft[3..5] is not < 0.3, or have_frames == 0 — and then sets prev to aft[3..5]          */
+int lins_host_map_key_rule(float prev[3], const float aft[6], int have_frames);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 /*
  * lins_streams_map.h — the outlier cloud on the device and the hand-over of a stream's clouds to the mapping node
  * (entry points of liblins_ieskf.so; the host restatement lins_frontend_segment_outliers and LINS_OUTLIER_MAX are in
- * lins_host.h, lins_local_map_build_streams in lins_map.h).
+ * lins_host.h, lins_local_map_build_streams in lins_map.h), and the mapping node's run() for streams: per-stream map
+ * poses resident on the device, one call per scan (lins_streams_map_step).
  */
 #ifndef LINS_STREAMS_MAP_H_
 #define LINS_STREAMS_MAP_H_
@@ -32,6 +33,72 @@ int lins_streams_put_outliers(lins_ctx* ctx, const lins_point* const* outlier, c
  * Returns the count; LINS_E_STATE before the stream's first step or on a failed streams context, LINS_E_CAPACITY when
  * cap is too small.  lins_local_map_build_streams (lins_map.h) reads the same clouds where they lie.                  */
 int lins_streams_map_cloud(lins_ctx* ctx, int stream, int which, lins_point* out, int cap);
+
+/* ---- the mapping node's run() for streams (LM:1821-1836): one call per scan ------------------------------------------
+ * Each stream's map pose lives on the device: transformBefMapped, transformAftMapped, transformTobeMapped, transformLast
+ * (rx, ry, rz, tx, ty, tz), previousRobotPosPoint and the number of key frames the stream has saved; timeLastProcessing
+ * is kept beside it on the host.  Zero at init, last_time = -1, as allocateMemory leaves them (LM:305-409).  The
+ * arithmetic is csrc/map_pose_math.h (host restatement: lins_host_map_* in lins_host.h).
+ *
+ * iSAM2 stays with the caller.  The step treats it as the identity, a departure from the node: the first key frame of a
+ * stream takes transformTobeMapped (LM:1676-1686), every later one transformAftMapped (LM:1699-1704), and for every key
+ * frame after the first transformLast = transformTobeMapped = transformAftMapped (LM:1737-1749).  GTSAM's RzRyRx /
+ * pitch() / yaw() / roll() round trip of those six numbers is not imitated.  A caller with iSAM2 writes its estimate
+ * back with lins_streams_map_set_pose (+ lins_local_map_set_pose, lins_archive_set_poses for the stored frames).     */
+typedef struct lins_map_pose_state {
+  float bef[6], aft[6], tobe[6], last[6], prev[3];
+  int32_t n_frames;  /* cloudKeyPoses3D->points.size() of this stream */
+  double last_time;  /* timeLastProcessing */
+} lins_map_pose_state;
+
+typedef struct lins_map_odom { /* laserOdometryHandler's and imuHandler's outputs for one scan of one stream */
+  float transform_sum[6];      /* transformSum (LM:711-724) */
+  float imu_roll, imu_pitch;   /* imuRollLast, imuPitchLast (LM:539-565); read with has_imu */
+  int32_t has_imu;             /* imuPointerLast >= 0 */
+  int32_t reserved;
+  double time;                 /* timeLaserOdometry */
+} lins_map_odom;
+
+#define LINS_MAP_STEP_SKIPPED 1 /* lins_map_step_result.status: the interval gate of LM:1821 stopped the entry */
+
+typedef struct lins_map_step_result {
+  float tobe_start[6]; /* transformTobeMapped as transformAssociateToMap left it */
+  float transform[6];  /* transformAftMapped after the step */
+  float key_pose[6];   /* the pose the key frame was stored with (key_frame == 1), same order */
+  int32_t iters, converged, degenerate, n_sel; /* as lins_map_result */
+  int32_t status;      /* LINS_OK | LINS_MAP_STEP_SKIPPED | LINS_E_INPUT | LINS_E_CAPACITY (the build entry's status) */
+  int32_t key_frame;   /* 1: the scan became a key frame of its stream's slot (and of the archive) */
+  int32_t ring_age;    /* the age lins_local_map_set_pose addresses the stored frame by (0: the newest); -1: none stored */
+  int32_t archive_id;  /* the id lins_archive_push_scans gave it; -1 without an archive or a key frame */
+} lins_map_step_result;
+
+/* map_associate_kernel on caller data: tobe6[6 k ..] = transformAssociateToMap of row k of bef6 / aft6 / sum6 (n x 6
+ * floats each).  A row's result bits do not depend on n or on its position.  Non-finite input: LINS_E_INPUT.          */
+int lins_map_associate_batch(lins_ctx* ctx, int n, const float* bef6, const float* aft6, const float* sum6, float* tobe6);
+/* After lins_streams_init and lins_local_map_init with n_slots >= n_streams (else LINS_E_STATE); stream k uses slot k
+ * of the local map, and of the archive if lins_archive_init has been called by then.  process_interval:
+ * mappingProcessInterval, 0.3 (LM:1821); >= 0.  A second call starts every stream anew.                              */
+int lins_streams_map_init(lins_ctx* ctx, int n_streams, double process_interval);
+int lins_streams_map_get_pose(lins_ctx* ctx, int stream, lins_map_pose_state* out);
+/* what a caller's iSAM2 writes back (LM:1737-1749), or a start pose; finite values, n_frames >= 0 (LINS_E_INPUT)      */
+int lins_streams_map_set_pose(lins_ctx* ctx, int stream, const lins_map_pose_state* in);
+/* run() for the n streams named (each at most once; n <= n_streams), in the order of LM:1821-1836:
+ *   gate        odom[k].time - last_time >= process_interval (f64), else status LINS_MAP_STEP_SKIPPED, nothing changes;
+ *               the other entries form the batch, last_time <- time
+ *   associate   transformAssociateToMap on the device from the resident pose
+ *   local map   lins_local_map_build_streams for the batch (entry <-> stream, slot = stream)
+ *   scan2map    lins_scan2map_batch's rounds with LINS_MAP_LOCAL, started where the associate kernel left the transform
+ *   finish      transformUpdate if the precondition of LM:1636 held, the key-frame rule, the key pose; one download
+ *   key frames  lins_local_map_push_scans and lins_archive_push_scans for the entries with key_frame set, with
+ *               lins_key_pose{t[3], t[4], t[5], t[0], t[1], t[2]} of key_pose and odom[k].time
+ * A build entry with a status (LINS_E_INPUT / LINS_E_CAPACITY) reports it, keeps its pose state (last_time included) and
+ * stores nothing; the others proceed.  Non-finite transform_sum / imu values / time: LINS_E_INPUT; a stream named twice,
+ * a bad index, n > n_streams: LINS_E_ARG — for the whole call, before anything is queued.  LINS_E_STATE before
+ * lins_streams_map_init.  The local map's build and the resident maps of lins_scan2map_batch are this call's afterwards,
+ * as after the explicit calls.                                                                                       */
+int lins_streams_map_step(lins_ctx* ctx, int n, const int32_t* streams, const lins_map_odom* odom, lins_map_step_result* out);
+/* HIP-event times (ms) of the associate and finish kernels of the last step (0 when the step queued none)            */
+int lins_last_streams_map_ms(lins_ctx* ctx, float* associate_ms, float* finish_ms);
 
 #ifdef __cplusplus
 }

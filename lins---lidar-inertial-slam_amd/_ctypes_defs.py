@@ -407,3 +407,49 @@ def loop_icp_problem_c(source, target):
             setattr(c, name, a.ctypes.data_as(C.POINTER(Point)))
             setattr(c, "n_" + name, len(a))
     return c, keep
+
+
+# ---- the mapping node's step for streams (include/lins_streams_map.h lins_streams_map_*, lins_map_associate_batch) ----
+MAP_STEP_SKIPPED = 1
+
+
+class MapPoseStateC(C.Structure):
+    _fields_ = [("bef", C.c_float * 6), ("aft", C.c_float * 6), ("tobe", C.c_float * 6), ("last", C.c_float * 6), ("prev", C.c_float * 3),
+                ("n_frames", C.c_int32), ("last_time", C.c_double)]
+    VECTORS = ("bef", "aft", "tobe", "last", "prev")
+
+    def as_dict(self):
+        d = {k: np.array(getattr(self, k)[:], np.float32) for k in self.VECTORS}
+        d.update(n_frames=int(self.n_frames), last_time=float(self.last_time))
+        return d
+
+
+def map_pose_state(state=None):
+    """lins_map_pose_state as lins_streams_map_init leaves it (zero, last_time = -1) with the fields of `state` over it"""
+    s = MapPoseStateC()
+    s.last_time = -1.0
+    for k, v in (state or {}).items():
+        if k in MapPoseStateC.VECTORS:
+            getattr(s, k)[:] = [float(x) for x in np.asarray(v, np.float32)]
+        elif k in ("n_frames", "last_time"):
+            setattr(s, k, v)
+        else:
+            raise TypeError(k)
+    return s
+
+
+class MapOdomC(C.Structure):
+    _fields_ = [("transform_sum", C.c_float * 6), ("imu_roll", C.c_float), ("imu_pitch", C.c_float), ("has_imu", C.c_int32),
+                ("reserved", C.c_int32), ("time", C.c_double)]
+
+
+class MapStepResultC(C.Structure):
+    _fields_ = [("tobe_start", C.c_float * 6), ("transform", C.c_float * 6), ("key_pose", C.c_float * 6), ("iters", C.c_int32),
+                ("converged", C.c_int32), ("degenerate", C.c_int32), ("n_sel", C.c_int32), ("status", C.c_int32), ("key_frame", C.c_int32),
+                ("ring_age", C.c_int32), ("archive_id", C.c_int32)]
+    COUNTS = ("iters", "converged", "degenerate", "n_sel", "status", "key_frame", "ring_age", "archive_id")
+
+    def as_dict(self):
+        d = {k: np.array(getattr(self, k)[:], np.float32) for k in ("tobe_start", "transform", "key_pose")}
+        d.update((k, int(getattr(self, k))) for k in self.COUNTS)
+        return d

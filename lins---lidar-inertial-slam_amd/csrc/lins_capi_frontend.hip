@@ -23,6 +23,8 @@ void streams_free(lins_ctx* ctx) {
   t = lins_ctx::Streams{};
 }
 
+int streams_count(lins_ctx* ctx) { return ctx->st.failed ? 0 : ctx->st.n; }
+
 int streams_map_clouds(lins_ctx* ctx, int stream, StreamMapClouds* v) {
   auto& t = ctx->st;
   if (t.n <= 0 || t.failed) return LINS_E_STATE;

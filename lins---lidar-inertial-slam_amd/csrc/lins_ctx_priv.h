@@ -22,6 +22,7 @@ struct StreamMapClouds {
   int n[3];
 };
 int streams_map_clouds(lins_ctx* ctx, int stream, StreamMapClouds* v);
+int streams_count(lins_ctx* ctx);  // streams of lins_streams_init (0: none, or a failed streams context)
 }  // namespace lins
 
 // every HIP call of the C API files: on failure the message goes to the context and the function returns LINS_E_HIP

@@ -7,6 +7,7 @@
 
 #include "../../include/lins_ieskf.h"
 #include "../../include/lins_map.h"
+#include "../../include/lins_streams_map.h"
 #include "lins_records.h"
 
 namespace lins {
@@ -89,6 +90,14 @@ void launch_map_corr(hipStream_t stream, int n_problems, int blocks_per_problem,
                      lins_map_corr* recs, double* partials);
 void launch_map_lm(hipStream_t stream, int n, int iter, int blocks_per_problem, MapDev* probs, MapRoundParams* rounds, const double* partials, lins_map_result* results, LmCarry* carry);
 void launch_debug_lm_step(hipStream_t stream, int n, int wave_version, const double* in, double* out, LmCarry* scratch);
+
+// ---- map_pose_kernels.hip: the mapping node's pose arithmetic around scan-to-map (map_pose_math.h).  One lane per entry;
+// probs[k].pad: < 0 the build entry's status, 1 the precondition of LM:1636 held, 0 it did not (associate: probs may be
+// null = 0, results may be null)
+void launch_map_associate(hipStream_t stream, int n, const MapPoseEntry* entries, const MapDev* probs, MapPoseRec* poses, lins_map_result* results,
+                          lins_map_step_result* out);
+void launch_map_pose_finish(hipStream_t stream, int n, const MapPoseEntry* entries, const MapDev* probs, MapPoseRec* poses,
+                            const lins_map_result* results, lins_map_step_result* out);
 
 // ---- local_map_kernels.hip: the mapping node's local map
 void launch_lm_transform(hipStream_t s, int n_blocks, const LmSeg* segs, const int2* blocks, const float4* frames, float4* stage, LmState* states);

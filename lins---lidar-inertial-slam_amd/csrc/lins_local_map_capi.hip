@@ -128,6 +128,7 @@ int local_map_view(lins_ctx* ctx, LocalMapView* v) {
   v->d_out = m->d_out, v->n = (int)m->slots.size(), v->off = m->off.data(), v->sizes = m->sizes.data(), v->slots = m->slots.data();
   return LINS_OK;
 }
+int local_map_slots(lins_ctx* ctx) { return local_of(ctx)->n_slots; }
 }  // namespace lins
 
 extern "C" {

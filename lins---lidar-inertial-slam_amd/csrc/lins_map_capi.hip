@@ -54,6 +54,9 @@ struct MapState {
   // the loop-closure ICP's of lins_loop_icp_* (lins_loop_icp_capi.hip), likewise
   void* loop = nullptr;
   void (*loop_free)(void*) = nullptr;
+  // the streams' map poses of lins_streams_map_* (lins_streams_map_capi.hip), likewise
+  void* pose = nullptr;
+  void (*pose_free)(void*) = nullptr;
 };
 
 void map_state_free(void* p) {
@@ -64,6 +67,7 @@ void map_state_free(void* p) {
   if (m->local) m->local_free(m->local);
   if (m->archive) m->archive_free(m->archive);
   if (m->loop) m->loop_free(m->loop);
+  if (m->pose) m->pose_free(m->pose);
   delete m;
 }
 
@@ -320,6 +324,59 @@ void** map_loop_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
   MapState* m = state_of(ctx);
   m->loop_free = free_fn;
   return &m->loop;
+}
+void** map_pose_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
+  MapState* m = state_of(ctx);
+  m->pose_free = free_fn;
+  return &m->pose;
+}
+
+// lins_scan2map_batch with LINS_MAP_LOCAL for the step of lins_streams_map_capi.hip: the same gridding, the same rounds,
+// but the start transforms are not uploaded — map_associate_kernel forms them on the device from the resident poses and
+// writes them where the first launch_map_lm reads them — and map_pose_finish_kernel runs behind the last round, so that
+// what comes down is one lins_map_step_result per entry.  d_entries is already on its way on the context's stream.
+int scan2map_local_resident(lins_ctx* ctx, int n, const MapPoseEntry* d_entries, MapPoseRec* d_poses, lins_map_step_result* d_out,
+                            lins_map_step_result* h_out, hipEvent_t* ev) {
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  MapState* m = state_of(ctx);
+  int rc = map_selfcheck(ctx, m);
+  if (rc) return rc;
+  LocalMapView lv{};
+  if (local_map_view(ctx, &lv) || lv.n != n) return LINS_E_STATE;
+  std::vector<MapDev> dev;
+  int max_q = 0;
+  if ((rc = map_upload_local(ctx, m, lv, dev, &max_q))) {
+    m->resident_dev.clear(), m->resident_sizes.clear();
+    return rc;
+  }
+  for (int k = 0; k < n; ++k) dev[k].pad = lv.sizes[k].status ? lv.sizes[k].status : dev[k].active;  // (for the two pose kernels)
+  const int bpp = std::max(1, (max_q + map_block() - 1) / map_block());
+  if ((rc = grow(ctx, &m->d_partials, &m->cap_partials, (size_t)n * bpp * 28))) return rc;
+  hipStream_t st = ctx_stream(ctx);
+  hipEvent_t e0, e1;
+  ctx_events(ctx, &e0, &e1);
+  HIP_TRY(ctx, hipMemcpyAsync(m->d_probs, dev.data(), (size_t)n * sizeof(MapDev), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipEventRecord(ev[0], st));
+  launch_map_associate(st, n, d_entries, m->d_probs, d_poses, m->d_results, d_out);
+  HIP_TRY(ctx, hipEventRecord(ev[1], st));
+  HIP_TRY(ctx, hipEventRecord(e0, st));
+  launch_map_lm(st, n, -1, bpp, m->d_probs, m->d_rounds, m->d_partials, m->d_results, m->d_carry);
+  for (int iter = 0; iter < m->max_rounds; ++iter) {
+    launch_map_corr(st, n, bpp, m->d_probs, m->d_rounds, m->d_pts, m->d_cells, lv.d_out, m->d_rec, m->d_partials);
+    launch_map_lm(st, n, iter, bpp, m->d_probs, m->d_rounds, m->d_partials, m->d_results, m->d_carry);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(e1, st));
+  HIP_TRY(ctx, hipEventRecord(ev[2], st));
+  launch_map_pose_finish(st, n, d_entries, m->d_probs, d_poses, m->d_results, d_out);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(ev[3], st));
+  HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, (size_t)n * sizeof(lins_map_step_result), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  HIP_TRY(ctx, hipEventElapsedTime(&m->ms, e0, e1));
+  m->queries = 0;
+  for (int k = 0; k < n; ++k) m->queries += (uint64_t)h_out[k].iters * ((uint64_t)dev[k].n_q[0] + dev[k].n_q[1]);
+  return LINS_OK;
 }
 }  // namespace lins
 

@@ -74,4 +74,18 @@ struct MapGridJob {
 };
 static_assert(sizeof(MapGridJob) == 56, "MapGridJob layout");
 
+// ---- the mapping node's step for streams (map_pose_kernels.hip / lins_streams_map_capi.hip) ----
+struct MapPoseRec {  // one stream's resident map pose: lins_map_pose_state without the host's last_time
+  float bef[6], aft[6], tobe[6], last[6], prev[3];
+  int n_frames;
+};
+static_assert(sizeof(MapPoseRec) == 112, "MapPoseRec layout");
+struct MapPoseEntry {  // one entry of a step's batch (uploaded per call)
+  float sum[6];
+  float imu_roll, imu_pitch;
+  int has_imu;
+  int stream;  // the MapPoseRec it works on
+};
+static_assert(sizeof(MapPoseEntry) == 40, "MapPoseEntry layout");
+
 }  // namespace lins

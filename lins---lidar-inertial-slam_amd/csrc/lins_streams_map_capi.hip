@@ -1,0 +1,239 @@
+// lins_streams_map_capi.hip — C ABI of the mapping node's run() for streams (include/lins_streams_map.h
+// lins_streams_map_*, lins_map_associate_batch): the per-stream map poses in one device block, the interval gate, and
+// the order of LM:1821-1836 around the calls that already exist — the local-map build over the streams' clouds,
+// scan-to-map between the two pose kernels (lins_map_capi.hip scan2map_local_resident), the key-frame pushes.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <vector>
+
+#include "../../include/lins_streams_map.h"
+#include "lins_ctx_priv.h"
+#include "lins_launch.h"
+#include "local_map.h"
+
+using namespace lins;
+
+namespace {
+
+struct StreamsMap {
+  int n = 0;  // streams (0: lins_streams_map_init has not run)
+  double interval = 0.3;
+  bool use_archive = false;
+  MapPoseRec* d_poses = nullptr;  // [n]
+  std::vector<double> last_time;  // timeLastProcessing per stream
+  // one step's batch: entries up, result records down (pinned staging), n entries at most
+  MapPoseEntry *d_entries = nullptr, *h_entries = nullptr;
+  lins_map_step_result *d_out = nullptr, *h_out = nullptr;
+  hipEvent_t ev[4] = {};  // associate start / end, finish start / end
+  float associate_ms = 0.f, finish_ms = 0.f;
+  // lins_map_associate_batch's own buffers (grown, never shrunk)
+  MapPoseRec* d_ab_poses = nullptr;
+  MapPoseEntry* d_ab_entries = nullptr;
+  lins_map_step_result* d_ab_out = nullptr;
+  size_t cap_ab = 0;
+};
+
+void step_buffers_free(StreamsMap* m) {
+  (void)hipFree(m->d_poses), (void)hipFree(m->d_entries), (void)hipFree(m->d_out);
+  (void)hipHostFree(m->h_entries), (void)hipHostFree(m->h_out);
+  m->d_poses = nullptr, m->d_entries = m->h_entries = nullptr, m->d_out = m->h_out = nullptr, m->n = 0;
+}
+
+void streams_map_free(void* p) {
+  StreamsMap* m = (StreamsMap*)p;
+  step_buffers_free(m);
+  (void)hipFree(m->d_ab_poses), (void)hipFree(m->d_ab_entries), (void)hipFree(m->d_ab_out);
+  for (hipEvent_t e : m->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete m;
+}
+
+StreamsMap* state_of(lins_ctx* ctx) {
+  void** slot = map_pose_slot(ctx, streams_map_free);
+  if (!*slot) *slot = new StreamsMap();
+  return (StreamsMap*)*slot;
+}
+
+bool finite6(const float* v) {
+  for (int i = 0; i < 6; ++i)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+
+lins_key_pose key_pose_of(const float* t) { return lins_key_pose{t[3], t[4], t[5], t[0], t[1], t[2]}; }  // LM:1721-1732
+
+}  // namespace
+
+extern "C" {
+
+int lins_map_associate_batch(lins_ctx* ctx, int n, const float* bef6, const float* aft6, const float* sum6, float* tobe6) {
+  if (!ctx || n < 0 || (n && (!bef6 || !aft6 || !sum6 || !tobe6))) return LINS_E_ARG;
+  if (n == 0) return LINS_OK;
+  for (int k = 0; k < n; ++k)
+    if (!finite6(bef6 + 6 * k) || !finite6(aft6 + 6 * k) || !finite6(sum6 + 6 * k)) return LINS_E_INPUT;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  StreamsMap* m = state_of(ctx);
+  if (m->cap_ab < (size_t)n) {
+    (void)hipFree(m->d_ab_poses), (void)hipFree(m->d_ab_entries), (void)hipFree(m->d_ab_out);
+    m->d_ab_poses = nullptr, m->d_ab_entries = nullptr, m->d_ab_out = nullptr, m->cap_ab = 0;
+    HIP_TRY(ctx, hipMalloc((void**)&m->d_ab_poses, (size_t)n * sizeof(MapPoseRec)));
+    HIP_TRY(ctx, hipMalloc((void**)&m->d_ab_entries, (size_t)n * sizeof(MapPoseEntry)));
+    HIP_TRY(ctx, hipMalloc((void**)&m->d_ab_out, (size_t)n * sizeof(lins_map_step_result)));
+    m->cap_ab = (size_t)n;
+  }
+  std::vector<MapPoseRec> recs((size_t)n, MapPoseRec{});
+  std::vector<MapPoseEntry> ent((size_t)n, MapPoseEntry{});
+  std::vector<lins_map_step_result> res((size_t)n);
+  for (int k = 0; k < n; ++k) {
+    std::memcpy(recs[k].bef, bef6 + 6 * k, sizeof recs[k].bef);
+    std::memcpy(recs[k].aft, aft6 + 6 * k, sizeof recs[k].aft);
+    std::memcpy(ent[k].sum, sum6 + 6 * k, sizeof ent[k].sum);
+    ent[k].stream = k;
+  }
+  hipStream_t st = ctx_stream(ctx);
+  HIP_TRY(ctx, hipMemcpyAsync(m->d_ab_poses, recs.data(), (size_t)n * sizeof(MapPoseRec), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(m->d_ab_entries, ent.data(), (size_t)n * sizeof(MapPoseEntry), hipMemcpyHostToDevice, st));
+  launch_map_associate(st, n, m->d_ab_entries, nullptr, m->d_ab_poses, nullptr, m->d_ab_out);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(res.data(), m->d_ab_out, (size_t)n * sizeof(lins_map_step_result), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  for (int k = 0; k < n; ++k) std::memcpy(tobe6 + 6 * k, res[k].tobe_start, 6 * sizeof(float));
+  return LINS_OK;
+}
+
+int lins_streams_map_init(lins_ctx* ctx, int n_streams, double process_interval) {
+  if (!ctx || n_streams < 1 || !(process_interval >= 0.0) || !std::isfinite(process_interval)) return LINS_E_ARG;
+  if (streams_count(ctx) < n_streams || local_map_slots(ctx) < n_streams) return LINS_E_STATE;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  StreamsMap* m = state_of(ctx);
+  HIP_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));
+  step_buffers_free(m);
+  for (hipEvent_t& e : m->ev)
+    if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_poses, (size_t)n_streams * sizeof(MapPoseRec)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_entries, (size_t)n_streams * sizeof(MapPoseEntry)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_out, (size_t)n_streams * sizeof(lins_map_step_result)));
+  HIP_TRY(ctx, hipHostMalloc((void**)&m->h_entries, (size_t)n_streams * sizeof(MapPoseEntry)));
+  HIP_TRY(ctx, hipHostMalloc((void**)&m->h_out, (size_t)n_streams * sizeof(lins_map_step_result)));
+  HIP_TRY(ctx, hipMemsetAsync(m->d_poses, 0, (size_t)n_streams * sizeof(MapPoseRec), ctx_stream(ctx)));  // allocateMemory (LM:305-409)
+  HIP_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));
+  m->last_time.assign((size_t)n_streams, -1.0);  // LM:356
+  m->interval = process_interval;
+  m->use_archive = lins_archive_count(ctx, 0) >= 0;
+  m->associate_ms = m->finish_ms = 0.f;
+  m->n = n_streams;
+  return LINS_OK;
+}
+
+int lins_streams_map_get_pose(lins_ctx* ctx, int stream, lins_map_pose_state* out) {
+  if (!ctx || !out) return LINS_E_ARG;
+  StreamsMap* m = state_of(ctx);
+  if (!m->n) return LINS_E_STATE;
+  if (stream < 0 || stream >= m->n) return LINS_E_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  MapPoseRec r;
+  HIP_TRY(ctx, hipMemcpyAsync(&r, m->d_poses + stream, sizeof r, hipMemcpyDeviceToHost, ctx_stream(ctx)));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));
+  static_assert(offsetof(lins_map_pose_state, n_frames) == offsetof(MapPoseRec, n_frames), "the record is the state's head");
+  std::memcpy(out, &r, sizeof r);
+  out->last_time = m->last_time[stream];
+  return LINS_OK;
+}
+
+int lins_streams_map_set_pose(lins_ctx* ctx, int stream, const lins_map_pose_state* in) {
+  if (!ctx || !in) return LINS_E_ARG;
+  StreamsMap* m = state_of(ctx);
+  if (!m->n) return LINS_E_STATE;
+  if (stream < 0 || stream >= m->n) return LINS_E_ARG;
+  if (!finite6(in->bef) || !finite6(in->aft) || !finite6(in->tobe) || !finite6(in->last) || !std::isfinite(in->prev[0]) ||
+      !std::isfinite(in->prev[1]) || !std::isfinite(in->prev[2]) || in->n_frames < 0 || !std::isfinite(in->last_time))
+    return LINS_E_INPUT;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  MapPoseRec r;
+  std::memcpy(&r, in, sizeof r);
+  HIP_TRY(ctx, hipMemcpyAsync(m->d_poses + stream, &r, sizeof r, hipMemcpyHostToDevice, ctx_stream(ctx)));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));  // (r goes out of scope)
+  m->last_time[stream] = in->last_time;
+  return LINS_OK;
+}
+
+int lins_streams_map_step(lins_ctx* ctx, int n, const int32_t* streams, const lins_map_odom* odom, lins_map_step_result* out) {
+  if (!ctx || n < 0 || (n && (!streams || !odom || !out))) return LINS_E_ARG;
+  StreamsMap* m = state_of(ctx);
+  if (!m->n) return LINS_E_STATE;
+  if (n > m->n) return LINS_E_ARG;
+  for (int k = 0; k < n; ++k) {
+    if (streams[k] < 0 || streams[k] >= m->n) return LINS_E_ARG;
+    for (int i = 0; i < k; ++i)
+      if (streams[i] == streams[k]) return LINS_E_ARG;  // (a stream may appear once)
+  }
+  for (int k = 0; k < n; ++k) {
+    const lins_map_odom& o = odom[k];
+    if (!finite6(o.transform_sum) || !std::isfinite(o.time) || !std::isfinite(o.imu_roll) || !std::isfinite(o.imu_pitch)) return LINS_E_INPUT;
+  }
+  m->associate_ms = m->finish_ms = 0.f;
+  // the interval gate (LM:1821), f64
+  std::vector<int> batch;     // positions in the call of the entries that run
+  std::vector<int32_t> which;  // ... and their streams = their slots
+  for (int k = 0; k < n; ++k) {
+    if (odom[k].time - m->last_time[streams[k]] >= m->interval) {
+      batch.push_back(k), which.push_back(streams[k]);
+    } else {
+      out[k] = lins_map_step_result{};
+      out[k].status = LINS_MAP_STEP_SKIPPED, out[k].ring_age = -1, out[k].archive_id = -1;
+    }
+  }
+  const int nb = (int)batch.size();
+  if (nb == 0) return LINS_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  hipStream_t st = ctx_stream(ctx);
+  for (int j = 0; j < nb; ++j) {
+    const lins_map_odom& o = odom[batch[j]];
+    MapPoseEntry& e = m->h_entries[j];
+    std::memcpy(e.sum, o.transform_sum, sizeof e.sum);
+    e.imu_roll = o.imu_roll, e.imu_pitch = o.imu_pitch, e.has_imu = o.has_imu != 0, e.stream = which[j];
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(m->d_entries, m->h_entries, (size_t)nb * sizeof(MapPoseEntry), hipMemcpyHostToDevice, st));
+  // extractSurroundingKeyFrames + downsampleCurrentScan over the streams' clouds where they lie
+  int rc = lins_local_map_build_streams(ctx, nb, which.data(), which.data(), nullptr);
+  if (rc) return rc;
+  // transformAssociateToMap, scan2MapOptimization, transformUpdate, the key-frame rule
+  if ((rc = scan2map_local_resident(ctx, nb, m->d_entries, m->d_poses, m->d_out, m->h_out, m->ev))) return rc;
+  HIP_TRY(ctx, hipEventElapsedTime(&m->associate_ms, m->ev[0], m->ev[1]));
+  HIP_TRY(ctx, hipEventElapsedTime(&m->finish_ms, m->ev[2], m->ev[3]));
+  std::vector<int32_t> key_entries;
+  std::vector<lins_key_pose> key_poses;
+  std::vector<double> key_times;
+  for (int j = 0; j < nb; ++j) {
+    const int k = batch[j];
+    out[k] = m->h_out[j];
+    if (out[k].status == LINS_OK) m->last_time[which[j]] = odom[k].time;  // LM:1824
+    if (out[k].key_frame) key_entries.push_back(j), key_poses.push_back(key_pose_of(out[k].key_pose)), key_times.push_back(odom[k].time);
+  }
+  // saveKeyFramesAndFactor's cloud copies (LM:1751-1764), device to device
+  const int nk = (int)key_entries.size();
+  if (nk) {
+    if ((rc = lins_local_map_push_scans(ctx, nk, key_entries.data(), key_poses.data()))) return rc;
+    std::vector<int32_t> ids((size_t)nk, -1);
+    if (m->use_archive && (rc = lins_archive_push_scans(ctx, nk, key_entries.data(), key_poses.data(), key_times.data(), ids.data()))) return rc;
+    for (int i = 0; i < nk; ++i) {
+      lins_map_step_result& r = out[batch[key_entries[i]]];
+      r.ring_age = 0, r.archive_id = ids[i];
+    }
+  }
+  return LINS_OK;
+}
+
+int lins_last_streams_map_ms(lins_ctx* ctx, float* associate_ms, float* finish_ms) {
+  if (!ctx) return LINS_E_ARG;
+  StreamsMap* m = state_of(ctx);
+  if (associate_ms) *associate_ms = m->associate_ms;
+  if (finish_ms) *finish_ms = m->finish_ms;
+  return LINS_OK;
+}
+
+}  // extern "C"

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/lins_map.h"
+#include "../../include/lins_streams_map.h"
 
 namespace lins {
 
@@ -80,8 +81,18 @@ struct LocalMapView {
   const int* slots;  // the slot of entry k
 };
 int local_map_view(lins_ctx* ctx, LocalMapView* v);
+int local_map_slots(lins_ctx* ctx);  // n_slots of lins_local_map_init (0 before it)
 void** map_local_slot(lins_ctx* ctx, void (*free_fn)(void*));  // lins_map_capi.hip: held by the scan-to-map state
 void** map_archive_slot(lins_ctx* ctx, void (*free_fn)(void*));  // ... and the key-frame archive's (lins_archive_capi.hip)
 void** map_loop_slot(lins_ctx* ctx, void (*free_fn)(void*));     // ... and the loop-closure ICP's (lins_loop_icp_capi.hip)
+void** map_pose_slot(lins_ctx* ctx, void (*free_fn)(void*));     // ... and the streams' map poses (lins_streams_map_capi.hip)
+
+// lins_map_capi.hip: scan-to-map over the last local-map build (n entries, as LINS_MAP_LOCAL) between the two pose
+// kernels of map_pose_kernels.hip — entry k works on d_poses[d_entries[k].stream]; h_out receives the n result records
+// (pinned or pageable), one synchronisation.  ev: four events, recorded around the associate and the finish kernel.
+struct MapPoseEntry;  // lins_records.h
+struct MapPoseRec;
+int scan2map_local_resident(lins_ctx* ctx, int n, const MapPoseEntry* d_entries, MapPoseRec* d_poses, lins_map_step_result* d_out,
+                            lins_map_step_result* h_out, hipEvent_t* ev);
 
 }  // namespace lins

@@ -35,6 +35,8 @@ EXPORTS = [
     "lins_loop_icp_default_params", "lins_loop_icp_batch", "lins_loop_icp_correspondences", "lins_last_loop_icp_stats",
     "lins_segment_batch_outliers", "lins_streams_put_outliers", "lins_streams_map_cloud", "lins_local_map_build_streams",
     "lins_last_local_map_stage_ms",
+    "lins_map_associate_batch", "lins_streams_map_init", "lins_streams_map_get_pose", "lins_streams_map_set_pose",
+    "lins_streams_map_step", "lins_last_streams_map_ms",
 ]
 
 
