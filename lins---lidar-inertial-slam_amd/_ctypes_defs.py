@@ -12,6 +12,9 @@ ERR_DIM = 18
 MAX_QUERY = 1024
 CLOUD_MAX = 16 * 1800
 OUTLIER_MAX = (16 - 6) * (1800 // 5)  # LINS_OUTLIER_MAX: rows above groundScanInd, every fifth column
+# `path` of lins_debug_cov_update(ctx, path, n, P, sums, r2, diverged, out) by index (csrc/lins_capi_debug.hip): the
+# covariance epilogue of the three LDS kernel families, then the any-size path's stand-alone kernel
+COV_PATHS = ("lds", "lds1", "mr", "joseph")
 
 LINS_OK = 0
 STREAMS_IMU_MAX = 64  # LINS_STREAMS_IMU_MAX: IMU rows per stream and call of the streams' device filter

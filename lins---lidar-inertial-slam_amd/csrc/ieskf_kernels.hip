@@ -502,6 +502,12 @@ void launch_persistent(hipStream_t stream, int n, const DevParams& prm, const Sc
   else
     hipLaunchKernelGGL(ieskf_persistent_kernel<SEARCH_BRUTE>, dim3(n), dim3(kBlock), 0, stream, prm, descs, arena,
                        state_in, cov_in, state_out, a6, out, idx_store, poses, scan_id_base, binned, prof);
+  launch_joseph(stream, n, prm, cov_in, a6, out, cov_out);
+}
+
+// the covariance update of n scans from their 21 sums and OutRec::diverged (launch_persistent's second kernel; on its own:
+// lins_debug_cov_update)
+void launch_joseph(hipStream_t stream, int n, const DevParams& prm, const double* cov_in, const double* a6, const OutRec* out, double* cov_out) {
   hipLaunchKernelGGL(ieskf_joseph_kernel, dim3(n), dim3(kJosephBlock), 0, stream, prm, cov_in, a6, out,
                      cov_out);
 }

@@ -63,6 +63,14 @@ void launch_lds(hipStream_t stream, int n, const DevParams& prm, int lanes, cons
   }
 }
 
+// test aid: the covariance epilogue alone, as instantiated for the shape `lanes` selects (debug_cov_update_kernel, ieskf_lds_impl.h)
+void launch_debug_cov_lds(hipStream_t stream, int n, int lanes, double r2, const double* cov_in, const double* sums, const int* diverged, double* cov_out) {
+  if (lanes == 3)
+    hipLaunchKernelGGL(lds_full::debug_cov_update_kernel<1024>, dim3(n), dim3(1024), 0, stream, r2, cov_in, sums, diverged, cov_out);
+  else
+    hipLaunchKernelGGL(lds_full::debug_cov_update_kernel<LINS_FULL_BLOCK1>, dim3(n), dim3(LINS_FULL_BLOCK1), 0, stream, r2, cov_in, sums, diverged, cov_out);
+}
+
 void launch_lds_pass(hipStream_t stream, int n, const DevParams& prm, int lanes, const ScanDesc* descs,
                      const float4* arena, const float4* sorted, const GridTables* tabs, const double* lin_state, const double* filt_state, int iter,
                      int4* idx_store, lins_corr* dump, double* sums_out, int* counts_out) {

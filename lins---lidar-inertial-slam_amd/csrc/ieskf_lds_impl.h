@@ -1852,6 +1852,27 @@ __global__ __launch_bounds__(BLOCK) void ieskf_lds_kernel(
   }
 }
 
+// Test aid (lins_debug_cov_update; tests/test_gpu_cov_update.py): the covariance epilogue of this family ALONE — one
+// workgroup per case, the prior and the 21 sums of H^T H put where the update's set-up and its last iteration leave them
+// (g_lds.P, g_lds.sums), then the update kernels' own joseph_epilogue<BLOCK>: the same out-of-line function, nothing of
+// it restated.  Workgroup shape, register bound and LDS block are the update kernel's of that shape (the attributes of a
+// kernel reach the functions it calls: a caller with others could move the epilogue's register allocation).
+template <int BLOCK>
+#if LINS_LDS_MINW > 1
+__global__ __launch_bounds__(BLOCK, LINS_LDS_MINW) void debug_cov_update_kernel(
+#else
+__global__ __launch_bounds__(BLOCK) void debug_cov_update_kernel(
+#endif
+    double r2, const double* __restrict__ cov_in, const double* __restrict__ sums_in, const int* __restrict__ diverged, double* __restrict__ cov_out) {
+  LdsStore& L = g_lds;
+  const int tid = threadIdx.x;
+  const size_t scan = blockIdx.x;
+  for (int k = tid; k < 324; k += BLOCK) L.P[k] = cov_in[scan * 324 + k];
+  if (tid < 21) L.sums[tid] = sums_in[scan * 21 + tid];
+  __syncthreads();
+  joseph_epilogue<BLOCK>(r2, diverged[scan], cov_out + scan * 324, tid);
+}
+
 #undef KP
 #undef PROF2_ADD
 }  // namespace LINS_LDS_NS

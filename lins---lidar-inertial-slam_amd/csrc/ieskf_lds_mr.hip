@@ -106,6 +106,11 @@ void launch_lds_mr(hipStream_t stream, int n, const DevParams& prm, const ScanDe
   }
 }
 
+// test aid: the batch kernel's covariance epilogue alone (debug_cov_update_kernel, ieskf_lds_impl.h)
+void launch_debug_cov_lds_mr(hipStream_t stream, int n, double r2, const double* cov_in, const double* sums, const int* diverged, double* cov_out) {
+  hipLaunchKernelGGL(lds_mr::debug_cov_update_kernel<LINS_MR_BLOCK>, dim3(n), dim3(LINS_MR_BLOCK), 0, stream, r2, cov_in, sums, diverged, cov_out);
+}
+
 // ICP / Gauss-Newton fallback (estimateTransform, SE:1163-1320) on the same grid and searches:
 // state_in = the pose to start from (the filter's), state_out = that state with rn_, qbn_ replaced
 void launch_lds_mr_icp(hipStream_t stream, int n, const DevParams& prm, const ScanDesc* descs, const float4* arena,

@@ -269,4 +269,48 @@ int lins_debug_loop_icp_step(lins_ctx* ctx, int n, int blocks_per_problem, const
   return LINS_OK;
 }
 
+/* Debug aid (not part of the drop-in surface; tests/test_gpu_cov_update.py): the covariance update of the iterated update
+ * (SE:594-598) ALONE, by the program one of the update paths runs — path 0: joseph_epilogue of the 1024-thread LDS
+ * kernel ("lds"), 1: of its one-lane shape ("lds1"), 2: of the batch kernel ("mr") (debug_cov_update_kernel of each
+ * family, ieskf_lds_impl.h: the kernels' own epilogue function on a prior and sums put into their LDS block), 3:
+ * ieskf_joseph_kernel, the any-size path's ("binned", "brute").  n cases in ONE launch, one workgroup each: P n x 324
+ * the priors, sums n x 21 the upper triangle of A = H^T H row by row (what sym6 reads), r2 = sigma^2, diverged[k] != 0:
+ * case k's prior is passed through.  out: n x 324. */
+int lins_debug_cov_update(lins_ctx* ctx, int path, int n, const double* P, const double* sums, double r2, const int32_t* diverged, double* out) {
+  if (!ctx || path < 0 || path > 3 || n < 1 || !P || !sums || !diverged || !out) return LINS_E_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<OutRec> recs(n, OutRec{});
+  for (int k = 0; k < n; ++k) recs[k].diverged = diverged[k] != 0;
+  double *d_P = nullptr, *d_sums = nullptr, *d_out = nullptr;
+  int* d_div = nullptr;
+  OutRec* d_recs = nullptr;
+  hipError_t e = hipMalloc((void**)&d_P, (size_t)n * 324 * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_sums, (size_t)n * 21 * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_out, (size_t)n * 324 * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&d_div, (size_t)n * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_recs, (size_t)n * sizeof(OutRec));
+  if (e == hipSuccess) e = hipMemcpyAsync(d_P, P, (size_t)n * 324 * 8, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_sums, sums, (size_t)n * 21 * 8, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_div, diverged, (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_recs, recs.data(), (size_t)n * sizeof(OutRec), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_out, 0xFF, (size_t)n * 324 * 8, ctx->stream);  // (NaN: an element no thread wrote is seen)
+  if (e == hipSuccess) {
+    if (path == 3) {
+      DevParams prm{};
+      prm.r2 = r2;
+      launch_joseph(ctx->stream, n, prm, d_P, d_sums, d_recs, d_out);
+    } else if (path == 2) {
+      launch_debug_cov_lds_mr(ctx->stream, n, r2, d_P, d_sums, d_div, d_out);
+    } else {
+      launch_debug_cov_lds(ctx->stream, n, path == 0 ? 3 : 1, r2, d_P, d_sums, d_div, d_out);
+    }
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * 324 * 8, hipMemcpyDeviceToHost, ctx->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  (void)hipFree(d_P), (void)hipFree(d_sums), (void)hipFree(d_out), (void)hipFree(d_div), (void)hipFree(d_recs);
+  if (e != hipSuccess) return ctx_fail_hip(ctx, e, "lins_debug_cov_update");
+  return LINS_OK;
+}
+
 }  // extern "C"

@@ -30,6 +30,7 @@ void launch_persistent(hipStream_t stream, int n, const DevParams& prm, const Sc
                        double* a6, OutRec* out, int4* idx_store, lins_pose_record* poses, int scan_id_base, float4* binned, long long* prof);
 void launch_pass(hipStream_t stream, int n, const DevParams& prm, const ScanDesc* descs, const float4* arena, const double* lin_state, const double* filt_state, int iter, int4* idx_store,
                  lins_corr* dump, double* sums_out, int* counts_out, float4* binned);
+void launch_joseph(hipStream_t stream, int n, const DevParams& prm, const double* cov_in, const double* a6, const OutRec* out, double* cov_out);  // launch_persistent's covariance kernel alone
 void launch_transform_to_end(hipStream_t stream, int n_jobs, int max_n, const ReprojectJob* jobs, const float4* in, float4* out_xyz, float4* out_yzx);
 void launch_reproject_in_place(hipStream_t stream, int n_jobs, int max_n, const StreamCloud* jobs, const double* states, float4* arena, double inv_period);
 void launch_stream_copy(hipStream_t stream, const float4* in, float4* out, size_t n);
@@ -47,6 +48,8 @@ void launch_lds(hipStream_t stream, int n, const DevParams& prm, int lanes, cons
                 const double* cov_in, double* state_out, double* a6, double* cov_out, OutRec* out, int4* idx_store, lins_pose_record* poses, int scan_id_base, long long* prof, int* carry);
 void launch_lds_pass(hipStream_t stream, int n, const DevParams& prm, int lanes, const ScanDesc* descs, const float4* arena, const float4* sorted, const GridTables* tabs, const double* lin_state,
                      const double* filt_state, int iter, int4* idx_store, lins_corr* dump, double* sums_out, int* counts_out);
+// test aid (lins_debug_cov_update): joseph_epilogue of the shape `lanes` selects on n (prior, 21 sums, diverged) cases, one workgroup each
+void launch_debug_cov_lds(hipStream_t stream, int n, int lanes, double r2, const double* cov_in, const double* sums, const int* diverged, double* cov_out);
 
 // ---- ieskf_lds_mr.hip: the multi-resident (batch) LDS kernel
 int lds_mr_np_cap();
@@ -60,6 +63,7 @@ void launch_lds_mr_icp(hipStream_t stream, int n, const DevParams& prm, const Sc
                        double* state_out, OutRec* out, int4* idx_store);
 void launch_lds_mr_pass(hipStream_t stream, int n, const DevParams& prm, const ScanDesc* descs, const float4* arena, const float4* sorted, const GridTables* tabs, const double* lin_state,
                         const double* filt_state, int iter, int4* idx_store, lins_corr* dump, double* sums_out, int* counts_out);
+void launch_debug_cov_lds_mr(hipStream_t stream, int n, double r2, const double* cov_in, const double* sums, const int* diverged, double* cov_out);  // as launch_debug_cov_lds
 
 // ---- frontend_kernels.hip / segment_kernels.hip
 int fe_pick_stride();  // ints of pick scratch per scan

@@ -525,6 +525,28 @@ class IeskfContext:
         self._check(f(self._h, n, bpp, nt.ctypes.data, stt.ctypes.data, p.ctypes.data, C.byref(prm), int(mode), arr, C.byref(running)))
         return [arr[k].as_dict() for k in range(n)], int(running.value)
 
+    def debug_cov_update(self, path, P, sums, r2, diverged=None):
+        """test aid (lins_debug_cov_update): the covariance update alone by the program of one update path — path: one of
+        _ctypes_defs.COV_PATHS ("lds", "lds1", "mr": that kernel family's joseph_epilogue; "joseph": ieskf_joseph_kernel).
+        P: (n, 18, 18) priors, sums: (n, 21) upper triangle of H^T H row by row, r2 = sigma^2, diverged: per case, != 0
+        passes the prior through.  One launch, one workgroup per case -> (n, 18, 18)"""
+        from ._ctypes_defs import COV_PATHS
+
+        P = np.ascontiguousarray(P, np.float64)
+        s = np.ascontiguousarray(sums, np.float64)
+        if P.ndim != 3 or P.shape[1:] != (18, 18) or s.shape != (len(P), 21) or len(P) < 1:
+            raise ValueError("P: (n, 18, 18), sums: (n, 21)")
+        n = len(P)
+        div = np.zeros(n, np.int32) if diverged is None else np.ascontiguousarray(diverged, np.int32)
+        if div.shape != (n,):
+            raise ValueError("one diverged flag per case")
+        out = np.zeros((n, 18, 18), np.float64)
+        f = lib().lins_debug_cov_update
+        f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+        f.restype = C.c_int
+        self._check(f(self._h, COV_PATHS.index(path), n, P.ctypes.data, s.ctypes.data, float(r2), div.ctypes.data, out.ctypes.data))
+        return out
+
     # -- image_projection_node on the device: raw clouds -> segmented scans --------------------
     def segment_batch_outliers(self, raws):
         """segment_batch plus the outlier clouds: (list of host.Segmented, list of (n_outlier, 4) f32)."""

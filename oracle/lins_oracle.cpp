@@ -1140,6 +1140,13 @@ void oracle_transform_to_start(const lins_params* prm, const double* lin_state, 
                                lins_point* out) {
   *out = transform_to_start(*prm, load_state(lin_state), *in);
 }
+void oracle_joseph_reduced(const lins_params* prm, const double* P, const double* sums21, double* Pout) {
+  double A6[36], g6[6];
+  double s[27] = {0};
+  std::memcpy(s, sums21, 21 * sizeof(double));
+  sums_to_normal(s, A6, g6);
+  joseph_reduced(*prm, P, A6, Pout);
+}
 
 int oracle_bench(const lins_params* prm, int n, const lins_scan_pair* in, int form, int nn_mode,
                  int threads, double* seconds, uint64_t* iters) {

@@ -76,6 +76,9 @@ void oracle_box_plus(const double* state19, const double* dx18, double* out19);
 void oracle_box_minus(const double* a19, const double* b19, double* out18);
 void oracle_transform_to_start(const lins_params* prm, const double* lin_state,
                                const lins_point* in, lins_point* out);
+/* joseph_reduced alone (SE:594-598 in the reduced form): P 18 x 18, sums21 the upper triangle of A = H^T H row by
+ * row, sigma = prm->lidar_std.  No divergence branch: that is performIESKF's.                                      */
+void oracle_joseph_reduced(const lins_params* prm, const double* P, const double* sums21, double* Pout);
 
 /* Timed throughput loop for bench.py's cpu_baseline: runs oracle_ieskf over
  * `n` pairs with `threads` std::threads, returns wall seconds and total

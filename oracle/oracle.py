@@ -108,6 +108,19 @@ def box_minus(a, b):
     return o
 
 
+def joseph_reduced(prm, P, sums21):
+    """joseph_reduced alone: the posterior covariance (18, 18) from the prior and the 21 sums of A = H^T H (upper
+    triangle row by row), sigma = prm.lidar_std"""
+    P = np.ascontiguousarray(P, dtype=np.float64).reshape(324)
+    s = np.ascontiguousarray(sums21, dtype=np.float64).reshape(21)
+    o = np.zeros(324)
+    L = lib()
+    L.oracle_joseph_reduced.argtypes = [C.POINTER(Params)] + [C.POINTER(C.c_double)] * 3
+    L.oracle_joseph_reduced.restype = None
+    L.oracle_joseph_reduced(C.byref(prm), _d(P), _d(s), _d(o))
+    return o.reshape(18, 18)
+
+
 def transform_to_start(prm, lin_state, pts):
     pts = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 4)
     lin_state = np.ascontiguousarray(lin_state, dtype=np.float64)

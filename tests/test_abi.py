@@ -120,3 +120,17 @@ int main(void) {
         ok, o_stride, o_state, o_cov = [int(x) for x in subprocess.check_output([exe]).split()]
     assert ok == 1
     assert (o_stride, o_state, o_cov) == (defs.ScanPairC.point_stride_bytes.offset, defs.ScanPairC.state.offset, defs.ScanPairC.cov.offset)
+
+
+def test_the_covariance_debug_entry_and_its_oracle_counterpart(ieskf, defs, oracle):
+    """lins_debug_cov_update(ctx, path, n, P, sums, r2, diverged, out) is exported, refuses a null context before it
+    touches the device, and its four paths have names; the oracle exports joseph_reduced alone"""
+    f = ieskf.lib().lins_debug_cov_update
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    f.restype = C.c_int
+    buf = (C.c_double * 324)()
+    flag = (C.c_int32 * 1)()
+    assert f(None, 0, 1, buf, buf, 1e-4, flag, buf) == -1  # LINS_E_ARG
+    assert ieskf.lib().lins_strerror(-1) == b"bad argument"
+    assert defs.COV_PATHS == ("lds", "lds1", "mr", "joseph")
+    assert hasattr(oracle.lib(), "oracle_joseph_reduced")
