@@ -70,6 +70,30 @@ void lins_filter_reset1(lins_filter* f);                          /* KF:320-352 
  * finish kernel (csrc/filter_math.h is the arithmetic of both).                                                     */
 void lins_filter_finish(lins_filter* f, double* global_state, const lins_result* posterior, int used_prior_cov);
 
+/* ---- the two-scan bootstrap (SE:331-425; on the device: lins_streams_filter.h) ---- */
+typedef struct lins_boot_params {
+  lins_filter_params filter;
+  double init_ba[3], init_bw[3]; /* INIT_BA, INIT_BW (exp_port.yaml:65-76) */
+} lins_boot_params;
+/* the IMU pre-integration between a stream's first and second scan (IB:179-187; delta_q: w x y z) */
+typedef struct lins_preintegration {
+  double sum_dt, delta_p[3], delta_q[4], delta_v[3], acc_0[3], gyr_0[3];
+} lins_preintegration;
+/* ---- CPU restatement of the bootstrap's arithmetic (liblins_host.so, csrc/host/boot.cpp; csrc/boot_math.h is the text
+ * of both sides).  The ICP itself is not restated: its pose is an input.                                            */
+void lins_host_preintegrate(lins_preintegration* pre, int n_rows, const double* rows /* n_rows x 7: dt, acc, gyr */,
+                            const double* init_ba, const double* init_bw);
+/* the pose estimateTransform starts from (SE:392-396): t[3], q[4] (w x y z) */
+void lins_host_boot_start(const lins_preintegration* pre, double* t, double* q);
+/* processFirstScan (SE:339-361): f = the zero initialisation, lin_state19 = identity, pre reset with imu_last;
+ * global_state is left as it is (the reference does not touch globalState_ here)                                   */
+void lins_host_boot_first(lins_filter* f, double* global_state, double* lin_state19, lins_preintegration* pre,
+                          const double imu_last[6], double time, const lins_boot_params* prm);
+/* processSecondScan behind estimateTransform (SE:401-415) */
+void lins_host_boot_second(lins_filter* f, double* global_state, double* lin_state19, const lins_preintegration* pre,
+                           const double icp_t[3], const double icp_q[4], const double imu_last[6], double time,
+                           const lins_boot_params* prm);
+
 /* ---- front-end ------------------------------------------------------------ */
 typedef struct lins_features {
   lins_point* corner_sharp;      int32_t n_corner_sharp;      /* cap 192  */

@@ -19,6 +19,11 @@ COV_PATHS = ("lds", "lds1", "mr", "joseph")
 LINS_OK = 0
 STREAMS_IMU_MAX = 64  # LINS_STREAMS_IMU_MAX: IMU rows per stream and call of the streams' device filter
 STREAMS_GATED = 1     # LINS_STREAMS_GATED: Result.reserved[0] of a scan the reference's feature gate (SE:436-440) stopped
+# the streams' state machine (include/lins_streams_filter.h): status_ values (SE:177-183) and Result.reserved[0] of an
+# accepted first / second scan
+STREAM_INIT, STREAM_FIRST_SCAN, STREAM_RUNNING = 0, 1, 3
+STREAMS_FIRST, STREAMS_BOOTED = 2, 3
+E_STATE, E_UNSUPPORTED = -6, -7
 
 
 class Point(C.Structure):

@@ -114,11 +114,15 @@ LINS_HD void reset1_state(St& s) {
 
 // calculateRPfromGravity (SE:602-605) on the reset filter's gravity, then correctRollPitch (SE:427-431): the yaw of
 // Q2rpy (R2rpy of toRotationMatrix, math_utils.h) kept, roll and pitch replaced; rpy2Quat does not normalise.
+LINS_HD void rp_from_gravity(V3 fbib, double& roll, double& pitch) {
+  const double sg = fbib.z >= 0.0 ? 1.0 : -1.0;
+  pitch = -sg * asin(fbib.x / kG0);
+  roll = sg * asin(fbib.y / kG0);
+}
 LINS_HD void correct_roll_pitch(St& g, V3 gn) {
   using namespace lins;
-  const double sg = gn.z >= 0.0 ? 1.0 : -1.0;
-  const double pitch = -sg * asin(gn.x / kG0);
-  const double roll = sg * asin(gn.y / kG0);
+  double roll, pitch;
+  rp_from_gravity(gn, roll, pitch);
   const M3 R = qmat(g.q);
   const double p1 = atan2(-R.m[6], sqrt(R.m[7] * R.m[7] + R.m[8] * R.m[8]));
   const double yaw = atan2(R.m[3] / cos(p1), R.m[0] / cos(p1));

@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "../../../include/lins_host.h"
+#include "../filter_init.h"
 #include "../lins_math.h"
 
 using namespace lins;
@@ -54,11 +55,7 @@ const M3 kI3{{1, 0, 0, 0, 1, 0, 0, 0, 1}};
 extern "C" {
 
 void lins_filter_default_params(lins_filter_params* p) {
-  // lins/config/exp_config/exp_port.yaml:29-62
-  p->acc_n = 70000, p->gyr_n = 0.1, p->acc_w = 500, p->gyr_w = 0.05;
-  for (int i = 0; i < 3; ++i) p->init_pos_std[i] = p->init_vel_std[i] = p->init_att_std[i] = 0.0;
-  p->init_acc_std[0] = 0.01, p->init_acc_std[1] = 0.01, p->init_acc_std[2] = 0.02;
-  p->init_gyr_std[0] = p->init_gyr_std[1] = p->init_gyr_std[2] = 0.002;
+  lins_filt_init::default_params(p);  // exp_port.yaml:29-62
 }
 
 void lins_filter_init(lins_filter* f, const lins_filter_params* p, const double* vn, const double* ba,
@@ -68,26 +65,7 @@ void lins_filter_init(lins_filter* f, const lins_filter_params* p, const double*
   St s{{0, 0, 0}, {vn[0], vn[1], vn[2]}, {1, 0, 0, 0}, {ba[0], ba[1], ba[2]}, {bw[0], bw[1], bw[2]},
        {0, 0, -kG0}};
   store(s, f->state);
-  // initializeCovariance(0), KF:247-286
-  double* C = f->cov;
-  for (int i = 0; i < 3; ++i) {
-    C[(0 + i) * 18 + 0 + i] = p->init_pos_std[i] * p->init_pos_std[i];
-    C[(3 + i) * 18 + 3 + i] = p->init_vel_std[i] * p->init_vel_std[i];
-    double a = p->init_att_std[i] * kDeg;
-    C[(6 + i) * 18 + 6 + i] = a * a;
-    C[(9 + i) * 18 + 9 + i] = p->init_acc_std[i] * p->init_acc_std[i];
-    C[(12 + i) * 18 + 12 + i] = p->init_gyr_std[i] * p->init_gyr_std[i];
-    C[(15 + i) * 18 + 15 + i] = 0.01;
-  }
-  // noise_, KF:263-266, 307-311
-  double peba = std::pow(p->acc_n * kUg, 2), pebg = std::pow(p->gyr_n * kDph, 2);
-  double pweba = std::pow(p->acc_w * kUg, 2), pwebg = std::pow(p->gyr_w * kDpsh, 2);
-  for (int i = 0; i < 3; ++i) {
-    f->noise[(0 + i) * 12 + 0 + i] = peba;
-    f->noise[(3 + i) * 12 + 3 + i] = pebg;
-    f->noise[(6 + i) * 12 + 6 + i] = pweba;
-    f->noise[(9 + i) * 12 + 9 + i] = pwebg;
-  }
+  lins_filt_init::cov_noise(p, f->cov, f->noise);  // initializeCovariance(0) and noise_, KF:247-311
 }
 
 void lins_filter_predict(lins_filter* f, double dt, const double* acc_, const double* gyr_) {

@@ -19,7 +19,7 @@ void streams_filter_free(lins_ctx* ctx) {
   f = lins_ctx::Streams::Filter{};
 }
 
-static int filter_alloc(lins_ctx* ctx) {
+int streams_filter_alloc(lins_ctx* ctx) {
   auto& t = ctx->st;
   auto& f = t.f;
   if (f.d_state) return LINS_OK;
@@ -97,7 +97,7 @@ int lins_streams_filter_set(lins_ctx* ctx, int stream, const lins_filter* filt, 
   if (t.n <= 0 || t.failed) return LINS_E_STATE;
   if (stream < 0 || stream >= t.n) return LINS_E_ARG;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (int rc = filter_alloc(ctx)) return rc;
+  if (int rc = streams_filter_alloc(ctx)) return rc;
   auto& f = t.f;
   double aux[kAux] = {};
   for (int i = 0; i < 3; ++i) {
@@ -116,6 +116,7 @@ int lins_streams_filter_set(lins_ctx* ctx, int stream, const lins_filter* filt, 
   HIP_TRY(ctx, hipMemcpyAsync(f.d_gstate + k * 19, global_state, 19 * 8, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   f.set[k] = 1, f.prm[k] = filt->prm;
+  if (t.b.on) t.b.status[k] = LINS_STREAM_RUNNING;  // (machine mode: a filter bootstrapped elsewhere)
   return LINS_OK;
 }
 
@@ -150,6 +151,19 @@ int lins_streams_filter_predict(lins_ctx* ctx, const int32_t* n_imu, const doubl
   if (!ctx) return LINS_E_ARG;
   auto& t = ctx->st;
   if (t.n <= 0 || t.failed) return LINS_E_STATE;
+  if (t.b.on) {  // machine mode, processImu by status (SE:242-257): INIT drops, FIRST_SCAN pre-integrates, RUNNING predicts
+    if (int rc = streams_boot_check(ctx, n_imu, imu)) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rcs = split_join(ctx)) return rcs;
+    std::vector<int32_t> n_run((size_t)t.n);
+    for (int k = 0; k < t.n; ++k) n_run[k] = t.b.status[k] == LINS_STREAM_RUNNING ? n_imu[k] : 0;
+    if (int rc = streams_filter_predict_queue(ctx, n_run.data(), imu)) return rc;
+    if (int rc = streams_boot_preintegrate_queue(ctx, n_imu, imu)) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < t.n; ++k)
+      if (n_imu[k]) std::memcpy(&t.b.imu_last[(size_t)k * 6], imu[k] + (size_t)(n_imu[k] - 1) * 7 + 1, 6 * 8), t.b.imu_seen[k] = 1;
+    return LINS_OK;
+  }
   if (int rc = streams_filter_check(ctx, n_imu, imu)) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (int rcs = split_join(ctx)) return rcs;

@@ -19,6 +19,7 @@ void streams_free(lins_ctx* ctx) {
   (void)hipFree(t.d_arena), (void)hipFree(t.d_sorted), (void)hipFree(t.d_desc), (void)hipFree(t.d_jobs), (void)hipFree(t.d_desc_next);
   t.d_desc_next = nullptr, t.index_ready = false;
   streams_filter_free(ctx);
+  streams_boot_free(ctx);
   (void)hipFree(t.d_gsorted), (void)hipFree(t.d_gridtab), (void)hipFree(t.d_outl);
   t = lins_ctx::Streams{};
 }
@@ -387,16 +388,6 @@ int lins_streams_init(lins_ctx* ctx, int n_streams) {
   return LINS_OK;
 }
 
-// imu != nullptr: the prior comes from the streams' device filter (lins_streams_step_imu*)
-struct StepImu {
-  const int32_t* n_imu;
-  const double* const* rows;
-  double* global_state_out;
-};
-static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, const lins_point* const* raw,
-                             const int32_t* n_raw, const double* prior_state, const double* prior_cov, double scan_period,
-                             lins_result* out, int32_t* feature_counts, const StepImu* imu = nullptr);
-
 int lins_streams_step_imu(lins_ctx* ctx, const lins_segmented_scan* scans, const int32_t* n_imu, const double* const* imu,
                           double scan_period, lins_result* out, int32_t* feature_counts, double* global_state_out) {
   if (!scans) return LINS_E_ARG;
@@ -424,17 +415,23 @@ int lins_streams_step_raw(lins_ctx* ctx, const lins_point* const* raw, const int
   return streams_step_impl(ctx, nullptr, raw, n_raw, prior_state, prior_cov, scan_period, out, feature_counts);
 }
 
-static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, const lins_point* const* raw,
-                             const int32_t* n_raw, const double* prior_state, const double* prior_cov, double scan_period,
-                             lins_result* out, int32_t* feature_counts, const StepImu* imu) {
+}  // extern "C"
+
+// imu != nullptr: the prior comes from the streams' device filter (lins_streams_step_imu*); mach != nullptr (with imu):
+// the state machine's step (lins_streams_process*, lins_capi_boot.hip) — each stream by its status, arguments checked there
+int lins::streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, const lins_point* const* raw, const int32_t* n_raw,
+                            const double* prior_state, const double* prior_cov, double scan_period, lins_result* out,
+                            int32_t* feature_counts, const StepImu* imu, const StepMachine* mach) {
   if (!ctx || !out || (!imu && (!prior_state || !prior_cov))) return LINS_E_ARG;
   auto& t = ctx->st;
   if (t.n <= 0 || t.failed) return LINS_E_STATE;  // (after a failed step: lins_streams_init again)
-  if (imu) {  // every stream runs from its device filter against its resident last scan, or nothing is run
+  if (imu && !mach) {  // every stream runs from its device filter against its resident last scan, or nothing is run
     if (int rc = streams_filter_check(ctx, imu->n_imu, imu->rows)) return rc;
     for (int k = 0; k < t.n; ++k)
-      if (t.last_counts[(size_t)k * 2] < 0) return LINS_E_STATE;
+      if (t.last_counts[(size_t)k * 2] < 0 || (t.b.on && t.b.status[k] != LINS_STREAM_RUNNING)) return LINS_E_STATE;
   }
+  // the status each stream enters the step with (machine mode; otherwise every stream is treated as running)
+  const std::vector<int> st_in = mach ? t.b.status : std::vector<int>((size_t)t.n, LINS_STREAM_RUNNING);
   // A step either completes for every stream — slots flipped, resident clouds re-projected — or marks the streams
   // context failed: no half-advanced state survives an early return.
   struct Guard {
@@ -489,13 +486,33 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
   //    On the filter path the prior is first propagated over the stream's IMU rows (behind the front-end, so that a
   //    rejected input has advanced nothing), and a scan with too few features is gated (SE:436-440): no update, the
   //    stream's resident clouds and slot stay the old scan's.
-  std::vector<char> gated((size_t)n, 0);
+  //    The state machine (mach): processImu by status — predict, pre-integrate, drop —; the bootstrap's own gate
+  //    (SE:332-333, 380-381: strict bounds); a stream that is not RUNNING gets no update (zero queries), its first or
+  //    second scan is dealt with behind the update (boot_mode: 1 / 2).  gated[k]: the scan is not kept.
+  std::vector<char> gated((size_t)n, 0), unsupported((size_t)n, 0);
+  std::vector<int> boot_mode((size_t)n, 0);
   bool any_gated = false;
   if (imu) {
-    if (int rcp = streams_filter_predict_queue(ctx, imu->n_imu, imu->rows)) return rcp;
+    if (mach) {
+      std::vector<int32_t> n_run((size_t)n);
+      for (int k = 0; k < n; ++k) n_run[k] = st_in[k] == LINS_STREAM_RUNNING ? imu->n_imu[k] : 0;
+      if (int rcp = streams_filter_predict_queue(ctx, n_run.data(), imu->rows)) return rcp;
+      if (int rcp = streams_boot_preintegrate_queue(ctx, imu->n_imu, imu->rows)) return rcp;
+    } else if (int rcp = streams_filter_predict_queue(ctx, imu->n_imu, imu->rows))
+      return rcp;
     for (int k = 0; k < n; ++k) {
       const int* c = &counts[(size_t)k * 4];
-      gated[k] = c[1] <= 5 || c[3] <= 10;
+      if (st_in[k] == LINS_STREAM_RUNNING)
+        gated[k] = c[1] <= 5 || c[3] <= 10;
+      else {
+        gated[k] = c[1] < 10 || c[3] < 100;
+        if (!gated[k]) boot_mode[k] = st_in[k] == LINS_STREAM_INIT ? 1 : 2;
+        if (boot_mode[k] == 2) {  // estimateTransform needs the device ICP: its caps, ICP_FREQ 1 (as the divergence fallback)
+          const int n_all = t.last_counts[(size_t)k * 2] + t.last_counts[(size_t)k * 2 + 1];
+          if (t.last_counts[(size_t)k * 2] < 0 || n_all > lds_mr_np_cap() || n_all > kGridNpMax || ctx->prm.icp_freq != 1)
+            boot_mode[k] = 0, gated[k] = 1, unsupported[k] = 1;
+        }
+      }
       any_gated = any_gated || gated[k];
     }
   }
@@ -504,7 +521,7 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
   bool lds_ok = true, mr_ok = true, lds3_ok = true;
   for (int k = 0; k < n; ++k) {
     const int* c = &counts[(size_t)k * 4];  // sharp, less sharp, flat, less flat
-    const bool has_last = t.last_counts[(size_t)k * 2] >= 0 && !gated[k];
+    const bool has_last = t.last_counts[(size_t)k * 2] >= 0 && !gated[k] && st_in[k] == LINS_STREAM_RUNNING;
     ScanDesc& d = ctx->h_desc[k];
     const long long bq = slot_base(k, cur[k]), bt = slot_base(k, cur[k] ^ 1);
     d.off_surf_q = (int)(bq + kSlotFlat), d.n_surf_q = has_last ? c[2] : 0;
@@ -580,7 +597,7 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
     std::memcpy(r.state, ctx->h_state + (size_t)k * 19, sizeof r.state);
     std::memcpy(r.cov, ctx->h_cov + (size_t)k * 324, sizeof r.cov);
     const OutRec& o = ctx->h_out[k];
-    const bool has_last = t.last_counts[(size_t)k * 2] >= 0 && !gated[k];
+    const bool has_last = t.last_counts[(size_t)k * 2] >= 0 && !gated[k] && st_in[k] == LINS_STREAM_RUNNING;
     r.residual_norm = o.residual_norm, r.update_norm = o.update_norm;
     r.iters = has_last ? o.iters : 0, r.converged = has_last ? o.converged : 0, r.diverged = has_last ? o.diverged : 0;
     r.m_surf = o.m_surf, r.m_corner = o.m_corner;
@@ -589,6 +606,11 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
       std::memcpy(r.cov, prior_cov + (size_t)k * 324, sizeof r.cov);
       HIP_TRY(ctx, hipMemcpyAsync(ctx->d_state_out + (size_t)k * 19, ctx->d_state_in + (size_t)k * 19, 19 * 8,
                                   hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    if (st_in[k] != LINS_STREAM_RUNNING) {  // the state machine's other streams: filled in behind the bootstrap (2d)
+      std::memset(&r, 0, sizeof r);
+      r.reserved[0] = unsupported[k] ? LINS_E_UNSUPPORTED : (gated[k] ? LINS_STREAMS_GATED : 0);
+      continue;
     }
     if (!has_last && imu) {  // a gated scan: the filter as predicted
       r.reserved[0] = LINS_STREAMS_GATED;
@@ -623,8 +645,29 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
   if (imu) {
     std::vector<int> mode((size_t)n);
     for (int k = 0; k < n; ++k)
-      mode[k] = gated[k] || (out[k].diverged && out[k].reserved[0] == LINS_E_UNSUPPORTED) ? 0 : (out[k].diverged ? 2 : 1);
+      mode[k] = gated[k] || st_in[k] != LINS_STREAM_RUNNING || (out[k].diverged && out[k].reserved[0] == LINS_E_UNSUPPORTED) ? 0 : (out[k].diverged ? 2 : 1);
     if (int rcf = streams_filter_finish_queue(ctx, mode.data())) return rcf;
+    // 2d. the state machine's first and second scans: processFirstScan / processSecondScan on the device — the ICP of all
+    //     second scans in one launch over their compact descriptor list (queries: this scan's flat / sharp clouds, targets:
+    //     the resident first scan's, as extracted), then the finish kernel, which leaves linState_ in the rows the
+    //     re-projection reads (identity for a first scan: its clouds stay as extracted)
+    if (mach) {
+      std::vector<ScanDesc> icp;
+      for (int k = 0; k < n; ++k) {
+        if (boot_mode[k] != 2) continue;
+        const int* c = &counts[(size_t)k * 4];
+        const long long bq = slot_base(k, cur[k]), bt = slot_base(k, cur[k] ^ 1);
+        ScanDesc d{};
+        d.off_surf_q = (int)(bq + kSlotFlat), d.n_surf_q = c[2];
+        d.off_corner_q = (int)(bq + kSlotSharp), d.n_corner_q = c[0];
+        d.off_surf_t = (int)(bt + kSlotLessFlat), d.n_surf_t = t.last_counts[(size_t)k * 2 + 1];
+        d.off_corner_t = (int)(bt + kSlotLessSharp), d.n_corner_t = t.last_counts[(size_t)k * 2];
+        d.surf_sorted = d.corner_sorted = 1;
+        d.slot_base = k * LINS_MAX_QUERY, d.pad = 0;
+        icp.push_back(d);
+      }
+      if (int rcb = streams_boot_finish(ctx, boot_mode.data(), icp, *mach, out)) return rcb;
+    }
     if (imu->global_state_out)
       HIP_TRY(ctx, hipMemcpyAsync(imu->global_state_out, t.f.d_gstate, (size_t)n * 19 * 8, hipMemcpyDeviceToHost, ctx->stream));
   }
@@ -682,9 +725,21 @@ static int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, co
   for (int k = 0; k < n; ++k)
     if (!gated[k]) t.cur[k] ^= 1;
   t.outl_pending = false;
+  if (mach) {  // status_ after processPCL (SE:294-307)
+    for (int k = 0; k < n; ++k) {
+      if (st_in[k] == LINS_STREAM_INIT && boot_mode[k] == 1) t.b.status[k] = LINS_STREAM_FIRST_SCAN;
+      if (st_in[k] == LINS_STREAM_FIRST_SCAN && !unsupported[k]) {
+        t.b.status[k] = boot_mode[k] == 2 ? LINS_STREAM_RUNNING : LINS_STREAM_INIT;
+        if (boot_mode[k] != 2) t.f.set[k] = 0;  // (back to INIT: the stream has no filter until its next first scan)
+      }
+      if (mach->status_out) mach->status_out[k] = t.b.status[k];
+    }
+  }
   guard.done = true;
   return LINS_OK;
 }
+
+extern "C" {
 
 int lins_streams_put_outliers(lins_ctx* ctx, const lins_point* const* outlier, const int32_t* n_outlier) {
   if (!ctx || !outlier || !n_outlier) return LINS_E_ARG;

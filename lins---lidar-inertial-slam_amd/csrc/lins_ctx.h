@@ -164,6 +164,28 @@ struct lins_ctx {
       bool predict_timed = false, finish_timed = false;
       float predict_ms = 0.f, finish_ms = 0.f;
     } f;
+    // the streams' state machine (lins_streams_machine_init, lins_streams_process*; lins_capi_boot.hip): the reference's
+    // status_ per stream and what the two-scan bootstrap keeps on the device
+    struct Boot {
+      bool on = false;
+      lins_boot_params prm{};
+      std::vector<int> status;       // LINS_STREAM_INIT / _FIRST_SCAN / _RUNNING
+      std::vector<char> imu_seen;    // the stream has been given an IMU row (or a scan_imu)
+      std::vector<double> imu_last;  // ... the newest one: n x 6 (acc, gyr)
+      std::vector<double> h_tmpl;    // host copy of the template (lins_boot::kTmpl doubles)
+      double *d_tmpl = nullptr, *d_pre = nullptr;  // the template; n x lins_boot::kPre pre-integration records
+      double *d_rows = nullptr, *h_rows = nullptr; // this call's rows of the FIRST_SCAN streams, component-major (h_: pinned)
+      double *d_scan = nullptr, *h_scan = nullptr; // n x 8: imu_last_ and time of this call's scans
+      int *d_ints = nullptr, *h_ints = nullptr;    // [rows per stream | finish mode | ICP slot | ICP list] x n
+      // the batched ICP of the second scans: compact descriptors, index tables, start / result rows, out records
+      ScanDesc* d_desc = nullptr;
+      GridTables* d_tab = nullptr;
+      double *d_icp_in = nullptr, *d_icp_out = nullptr;
+      OutRec *d_out = nullptr, *h_out = nullptr;
+      hipEvent_t ev[6] = {};  // pre-integration, ICP, finish: start / end
+      bool pre_timed = false, icp_timed = false, finish_timed = false;
+      float pre_ms = 0.f, icp_ms = 0.f, finish_ms = 0.f;
+    } b;
   } st;
   void* map_state = nullptr;  // scan-to-map row (lins_map_capi.hip), freed through map_state_free
   void (*map_state_free)(void*) = nullptr;
@@ -247,12 +269,38 @@ void fe_free(lins_ctx* ctx);
 void streams_free(lins_ctx* ctx);
 // ---- lins_capi_filter.hip
 void streams_filter_free(lins_ctx* ctx);
+int streams_filter_alloc(lins_ctx* ctx);
 // queue the predict kernel over this call's IMU rows on the context's stream (arguments checked by the caller:
 // streams_filter_check); no synchronisation
 int streams_filter_check(lins_ctx* ctx, const int32_t* n_imu, const double* const* imu);
 int streams_filter_predict_queue(lins_ctx* ctx, const int32_t* n_imu, const double* const* imu);
 // queue the finish kernel (mode per stream as launch_filter_finish) behind the update
 int streams_filter_finish_queue(lins_ctx* ctx, const int* mode);
+
+// ---- lins_capi_boot.hip: the streams' state machine around the step of lins_capi_frontend.hip
+// what lins_streams_process* adds to a step: imu_last_ (n x 6, resolved by the caller) and time of each scan
+struct StepMachine {
+  const double* scan_imu;
+  const double* scan_time;
+  const char* imu_seen;  // per stream: scan_imu[k] is valid (a RUNNING stream needs none)
+  int32_t* status_out;
+};
+struct StepImu {  // the prior comes from the streams' device filter (lins_streams_step_imu*)
+  const int32_t* n_imu;
+  const double* const* rows;
+  double* global_state_out;
+};
+int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, const lins_point* const* raw, const int32_t* n_raw,
+                      const double* prior_state, const double* prior_cov, double scan_period, lins_result* out,
+                      int32_t* feature_counts, const StepImu* imu = nullptr, const StepMachine* mach = nullptr);
+void streams_boot_free(lins_ctx* ctx);
+// argument check of a machine-mode call's IMU rows (as streams_filter_check, without the need of a loaded filter)
+int streams_boot_check(lins_ctx* ctx, const int32_t* n_imu, const double* const* imu);
+// queue the pre-integration kernel over the rows of the streams in FIRST_SCAN
+int streams_boot_preintegrate_queue(lins_ctx* ctx, const int32_t* n_imu, const double* const* imu);
+// queue start rows, index, the batched ICP and the finish kernel: mode[k] 0 / 1 first scan / 2 second scan; descs: the
+// ICP descriptor of every mode-2 stream, in stream order.  Fills out[k] of the mode 1 / 2 streams (synchronises).
+int streams_boot_finish(lins_ctx* ctx, const int* mode, const std::vector<ScanDesc>& descs, const StepMachine& mach, lins_result* out);
 
 // Run fn(k) for k in [0, n) on up to 16 host threads (validation + packing of a batch is memory-bound
 // scalar work: 1024 scans = 8 M points); returns the smallest-index non-zero result.

@@ -79,6 +79,15 @@ void launch_segment(hipStream_t stream, int n_scans, const SgRaw* raws, const fl
 void launch_filter_predict(hipStream_t stream, int n, const int* n_imu, const int* imu_off, const double* imu, double* state, double* cov, const double* noise, double* aux);
 void launch_filter_finish(hipStream_t stream, int n, const int* mode, const double* post_state, const double* post_cov, double* state, double* cov, const double* aux, double* gstate);
 
+// ---- boot_kernels.hip: the streams' two-scan bootstrap (boot_math.h).  rows: this call's IMU rows component-major,
+// element (row it, component j, stream k) at (it * 7 + j) * n + k; pre: lins_boot::kPre doubles per stream; tmpl: the
+// lins_boot::kTmpl doubles of the filter template; list / icp_slot: the compact list of second scans and its inverse;
+// scan: 8 doubles per stream (imu_last_ acc, gyr, the scan's time); finish mode[k]: 0 nothing, 1 first scan, 2 second scan
+void launch_boot_preintegrate(hipStream_t stream, int n, const int* n_rows, const double* rows, const double* tmpl, double* pre, double* aux);
+void launch_boot_start(hipStream_t stream, int m, const int* list, const double* pre, double* state_in);
+void launch_boot_finish(hipStream_t stream, int n, const int* mode, const int* icp_slot, const double* icp_state, const double* scan, const double* tmpl,
+                        double* pre, double* state, double* cov, double* noise, double* aux, double* gstate, double* lin);
+
 // ---- debug_kernels.hip (lins_debug_math; op codes there)
 void launch_debug_math(hipStream_t stream, int op, int n, int n_in, int n_out, const double* in, double* out);
 void launch_debug_cycles(hipStream_t stream, int op, int blocks, const double* in, double* out);

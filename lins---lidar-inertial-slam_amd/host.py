@@ -34,6 +34,20 @@ class Filter(C.Structure):
     ]
 
 
+class BootParams(C.Structure):
+    """lins_boot_params: the filter's parameters and INIT_BA / INIT_BW"""
+    _fields_ = [("filter", FilterParams), ("init_ba", C.c_double * 3), ("init_bw", C.c_double * 3)]
+
+
+class Preintegration(C.Structure):
+    """lins_preintegration: the IMU pre-integration between a stream's first and second scan (delta_q: w x y z)"""
+    _fields_ = [("sum_dt", C.c_double), ("delta_p", C.c_double * 3), ("delta_q", C.c_double * 4), ("delta_v", C.c_double * 3),
+                ("acc_0", C.c_double * 3), ("gyr_0", C.c_double * 3)]
+
+    def array(self):
+        return np.frombuffer(bytes(self), np.float64).copy()
+
+
 class Features(C.Structure):
     _fields_ = [
         ("corner_sharp", C.POINTER(Point)), ("n_corner_sharp", C.c_int32),
@@ -197,6 +211,14 @@ def lib():
         L.lins_filter_finish.argtypes = [C.POINTER(Filter), C.POINTER(C.c_double), C.POINTER(ResultC), C.c_int]
         for f in (L.lins_filter_default_params, L.lins_filter_init, L.lins_filter_predict, L.lins_filter_reset1, L.lins_filter_finish):
             f.restype = None
+        L.lins_boot_default_params.argtypes = [C.POINTER(BootParams)]
+        L.lins_host_preintegrate.argtypes = [C.POINTER(Preintegration), C.c_int, dp, dp, dp]
+        L.lins_host_boot_start.argtypes = [C.POINTER(Preintegration), dp, dp]
+        L.lins_host_boot_first.argtypes = [C.POINTER(Filter), dp, dp, C.POINTER(Preintegration), dp, C.c_double, C.POINTER(BootParams)]
+        L.lins_host_boot_second.argtypes = [C.POINTER(Filter), dp, dp, C.POINTER(Preintegration), dp, dp, dp, C.c_double,
+                                            C.POINTER(BootParams)]
+        for f in (L.lins_boot_default_params, L.lins_host_preintegrate, L.lins_host_boot_start, L.lins_host_boot_first, L.lins_host_boot_second):
+            f.restype = None
         _LIB = L
     return _LIB
 
@@ -212,6 +234,52 @@ def filter_finish(filt, global_state, state, cov, used_prior_cov=False):
     g = np.array(global_state, dtype=np.float64).reshape(19).copy()
     lib().lins_filter_finish(C.byref(filt), g.ctypes.data_as(C.POINTER(C.c_double)), C.byref(r), int(bool(used_prior_cov)))
     return g
+
+
+# ---- the two-scan bootstrap (lins_host_preintegrate / lins_host_boot_*: csrc/host/boot.cpp) ----
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def boot_default_params():
+    p = BootParams()
+    lib().lins_boot_default_params(C.byref(p))
+    return p
+
+
+def preintegrate(pre, rows, prm=None):
+    """IntegrationBase::push_back of `rows` ((m, 7): dt, acc, gyr) onto `pre` (a Preintegration, changed in place)"""
+    prm = prm or boot_default_params()
+    rows = np.ascontiguousarray(rows, np.float64).reshape(-1, 7)
+    ba, bw = np.array(prm.init_ba[:]), np.array(prm.init_bw[:])
+    lib().lins_host_preintegrate(C.byref(pre), len(rows), _dp(rows), _dp(ba), _dp(bw))
+    return pre
+
+
+def boot_start(pre):
+    """-> (pl (3,), ql (4,) w x y z): the pose estimateTransform starts from (SE:392-396)"""
+    t, q = np.zeros(3), np.zeros(4)
+    lib().lins_host_boot_start(C.byref(pre), _dp(t), _dp(q))
+    return t, q
+
+
+def boot_first(imu_last, time, prm=None):
+    """processFirstScan -> (Filter, linState_ (19,), Preintegration)"""
+    prm = prm or boot_default_params()
+    f, pre, lin, g = Filter(), Preintegration(), np.zeros(19), np.zeros(19)
+    il = np.ascontiguousarray(imu_last, np.float64).reshape(6)
+    lib().lins_host_boot_first(C.byref(f), _dp(g), _dp(lin), C.byref(pre), _dp(il), float(time), C.byref(prm))
+    return f, lin, pre
+
+
+def boot_second(pre, icp_t, icp_q, imu_last, time, prm=None):
+    """processSecondScan behind estimateTransform -> (Filter, globalState_ (19,), linState_ (19,))"""
+    prm = prm or boot_default_params()
+    f, g, lin = Filter(), np.zeros(19), np.zeros(19)
+    t, q = np.ascontiguousarray(icp_t, np.float64).reshape(3), np.ascontiguousarray(icp_q, np.float64).reshape(4)
+    il = np.ascontiguousarray(imu_last, np.float64).reshape(6)
+    lib().lins_host_boot_second(C.byref(f), _dp(g), _dp(lin), C.byref(pre), _dp(t), _dp(q), _dp(il), float(time), C.byref(prm))
+    return f, g, lin
 
 
 def local_map(frames, scan, window=50):

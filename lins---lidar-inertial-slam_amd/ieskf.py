@@ -32,6 +32,8 @@ EXPORTS = [
     "lins_last_archive_stats", "lins_archive_set_scan_chunk",
     "lins_streams_filter_set", "lins_streams_filter_get", "lins_streams_filter_predict", "lins_streams_step_imu",
     "lins_streams_step_imu_raw", "lins_streams_filter_stats",
+    "lins_boot_default_params", "lins_streams_machine_init", "lins_streams_process", "lins_streams_process_raw",
+    "lins_streams_status", "lins_streams_preintegration_get", "lins_streams_lin_state", "lins_streams_boot_stats",
     "lins_loop_icp_default_params", "lins_loop_icp_batch", "lins_loop_icp_correspondences", "lins_last_loop_icp_stats",
     "lins_segment_batch_outliers", "lins_streams_put_outliers", "lins_streams_map_cloud", "lins_local_map_build_streams",
     "lins_last_local_map_stage_ms",
@@ -99,7 +101,8 @@ def lib():
         L.lins_transform_to_end_batch.argtypes = [vp, C.c_int, C.POINTER(ReprojectJob)]
         L.lins_last_reproject_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
         for name in EXPORTS:
-            if name not in ("lins_destroy", "lins_strerror", "lins_last_hip_error", "lins_last_search", "lins_loop_icp_default_params"):
+            if name not in ("lins_destroy", "lins_strerror", "lins_last_hip_error", "lins_last_search", "lins_loop_icp_default_params",
+                            "lins_boot_default_params"):
                 if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                     continue  # (an older build under A/B timing)
                 getattr(L, name).restype = C.c_int
@@ -758,6 +761,95 @@ class IeskfContext:
                                                 counts.ctypes.data_as(C.POINTER(C.c_int32)), g.ctypes.data_as(C.POINTER(C.c_double))))
         self._n = 0
         return [Result(r) for r in res], counts, g
+
+    # -- the streams' state machine: INIT -> FIRST_SCAN -> RUNNING on the device (lins_streams_machine_init, _process*) ----
+    def streams_machine_init(self, boot_params=None):
+        """every stream to INIT; boot_params: a host.BootParams (default: lins_boot_default_params)"""
+        import importlib
+
+        host = importlib.import_module(__package__ + ".host")
+        L = lib()
+        if boot_params is None:
+            boot_params = host.BootParams()
+            L.lins_boot_default_params.argtypes = [C.c_void_p]
+            L.lins_boot_default_params.restype = None
+            L.lins_boot_default_params(C.byref(boot_params))
+        L.lins_streams_machine_init.argtypes = [C.c_void_p, C.c_void_p]
+        self._check(L.lins_streams_machine_init(self._h, C.byref(boot_params)))
+
+    def _process(self, fn, head_types, head, imu, scan_time, scan_imu, scan_period):
+        n = self._streams
+        cnt, ptrs, _keep = self._imu_args(imu)
+        dp = C.POINTER(C.c_double)
+        st = np.ascontiguousarray(scan_time, dtype=np.float64).reshape(n)
+        si = None if scan_imu is None else np.ascontiguousarray(scan_imu, dtype=np.float64).reshape(n, 6)
+        res = (ResultC * n)()
+        counts, g, status = np.zeros((n, 4), np.int32), np.zeros((n, 19)), np.zeros(n, np.int32)
+        fn.argtypes = [C.c_void_p] + head_types + [C.POINTER(C.c_int32), C.POINTER(dp), dp, dp, C.c_double, C.POINTER(ResultC),
+                                                   C.POINTER(C.c_int32), dp, C.POINTER(C.c_int32)]
+        self._check(fn(self._h, *head, cnt, ptrs, si.ctypes.data_as(dp) if si is not None else dp(), st.ctypes.data_as(dp), scan_period, res,
+                       counts.ctypes.data_as(C.POINTER(C.c_int32)), g.ctypes.data_as(dp), status.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._n = 0
+        return [Result(r) for r in res], counts, g, status
+
+    def streams_process(self, segs, imu, scan_time, scan_imu=None, scan_period=0.1):
+        """processImu over each stream's rows (see _imu_args), then processPCL of its segmented scan, whatever the stream's
+        status.  scan_imu: (n, 6) imu_last_ or None (the last row given).  Returns (results, feature_counts (n, 4), global
+        states (n, 19), status (n,))."""
+        import importlib
+
+        host = importlib.import_module(__package__ + ".host")
+        n = self._streams
+        assert len(segs) == n
+        arr = (host.SegmentedScanC * n)(*[s.c for s in segs])
+        return self._process(lib().lins_streams_process, [C.POINTER(host.SegmentedScanC)], [arr], imu, scan_time, scan_imu, scan_period)
+
+    def streams_process_raw(self, raws, imu, scan_time, scan_imu=None, scan_period=0.1):
+        """Like streams_process, from raw clouds (firing order)."""
+        import importlib
+
+        host = importlib.import_module(__package__ + ".host")
+        n = self._streams
+        assert len(raws) == n
+        raws = [np.ascontiguousarray(r, dtype=np.float32).reshape(-1, 4) for r in raws]
+        rptrs = (C.POINTER(host.Point) * n)(*[r.ctypes.data_as(C.POINTER(host.Point)) for r in raws])
+        rcnt = (C.c_int32 * n)(*[len(r) for r in raws])
+        return self._process(lib().lins_streams_process_raw, [C.POINTER(C.POINTER(host.Point)), C.POINTER(C.c_int32)], [rptrs, rcnt], imu,
+                             scan_time, scan_imu, scan_period)
+
+    def streams_status(self):
+        status = np.zeros(self._streams, np.int32)
+        L = lib()
+        L.lins_streams_status.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        self._check(L.lins_streams_status(self._h, status.ctypes.data_as(C.POINTER(C.c_int32))))
+        return status
+
+    def streams_preintegration_get(self, stream):
+        """-> host.Preintegration of a stream in FIRST_SCAN (synchronises)"""
+        import importlib
+
+        host = importlib.import_module(__package__ + ".host")
+        pre = host.Preintegration()
+        L = lib()
+        L.lins_streams_preintegration_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        self._check(L.lins_streams_preintegration_get(self._h, stream, C.byref(pre)))
+        return pre
+
+    def streams_lin_state(self):
+        """linState_ of every stream (n, 19) as the last step's re-projection read it"""
+        lin = np.zeros((self._streams, 19))
+        L = lib()
+        L.lins_streams_lin_state.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        self._check(L.lins_streams_lin_state(self._h, lin.ctypes.data_as(C.POINTER(C.c_double))))
+        return lin
+
+    def streams_boot_stats(self):
+        """HIP-event times (ms) of the last call's pre-integration kernel, bootstrap ICP and bootstrap finish kernel"""
+        a, b, c = C.c_float(0), C.c_float(0), C.c_float(0)
+        L = lib()
+        L.lins_streams_boot_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_float)] * 3
+        self._check(L.lins_streams_boot_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
 
     def streams_filter_stats(self):
         """HIP-event times (ms) of the last predict and finish kernels"""
