@@ -47,9 +47,11 @@
 //                       three lanes and merged with wave shuffles on (distance, key)
 //     1 lane / query    plane / line residual + Jacobian (f64 -> f32) -> H row in registers
 //     every wave        28 f64 sums by a fixed-shape register butterfly (ieskf_rowsum.h
-//                       wave_reduce_rows), then an ordered fold over the wave partials
-//     42 lanes of wave 0  6x6 Gauss-Jordan, one element per lane (ieskf_rowsum.h wave_gj_solve6), dx
-//     wave 0            NaN / divergence / convergence, boxPlus, next constants
+//                       wave_reduce_rows)
+//     wave 0            an ordered fold over the wave partials (28 lanes), 6x6 Gauss-Jordan, one element per lane
+//                       (42 lanes, ieskf_rowsum.h wave_gj_solve6), dx and the non-rotation parts of the next
+//                       iteration's constants (18 lanes), NaN / divergence, q (+) dth
+//     waves 0-2 | 3     the rotation parts of the next constants | |dx|, the stop rule, the loop's bookkeeping
 //   16 waves x 21 queries = 336 queries per round = the VLP-16 caps (144 flat + 192 sharp).
 //
 // Scans that do not fit (more than kNpCap target points, ring ids >= 16, unsorted
@@ -152,13 +154,13 @@ struct LdsStore {
   double filt[19];
   double sums[28];
   double partial[kMaxLWaves * 28 > kIcpWorkspace ? kMaxLWaves * 28 : kIcpWorkspace];  // one partial 28-vector per wave (and the ICP step's workspace)
-  double aug[3][42];  // one staging copy of [N | z] per solving wave
+  double aug[3][42];  // the tail's staging area (ieskf_lds_tail.h): [0] |r|, dx[18]; [1] the divergence flag (as int); the ICP step: JTJ, JTb
   double res_prev, res_last, upd_norm;
   int scan_tmp[kMaxLWaves + 4];
   int m_surf, m_corner, iter, conv, div, pad;
   long long prof_acc[16];  // phase profile accumulators of the PROF variant (written by thread 0)
 #ifdef LINS_PROF_TAIL
-  long long prof_tail[2];  // stamps inside solve_wave0 (system built, solved)
+  long long prof_tail[2];  // stamps inside solve_wave0 (partials folded + system built, solved)
 #endif
 #ifdef LINS_PROF2
   int prof2[64];  // per wave x phase ticks of the iterations >= LINS_PROF2 (lane 0 of each wave; lins_debug_wave_phases)
@@ -1632,13 +1634,13 @@ __device__ __forceinline__ bool ieskf_lds_update(const KernelArgs ka, const floa
     __syncthreads();
     const long long b1 = prof ? clock64() : 0;
     PROF2_ADD(5, b1 - b0);
-    if (tid < 28) {
-      double sacc = 0;
-#pragma unroll
-      for (int g = 0; g < BLOCK / 64; ++g) sacc += L.partial[g * 28 + tid];
-      L.sums[tid] = sacc;
+    // The ordered fold over the wave partials.  In an update the sums of an iteration are read by wave 0 alone, which
+    // folds them at the head of its tail (solve_wave0, ieskf_lds_tail.h) behind a wave-level fence: no second barrier on
+    // the chain.  A single pass hands them out and the ICP step has its own tail: they fold here, as ever.
+    if (PASS_ONLY || ICP) {
+      if (tid < 64) fold_partials<BLOCK / 64>(tid);
+      __syncthreads();
     }
-    __syncthreads();
     if (prof) t2 = clock64();
     PROF2_ADD(6, t2 - b1);
     if (PASS_ONLY && (pad & 4) && !L.conv) {
@@ -1659,7 +1661,7 @@ __device__ __forceinline__ bool ieskf_lds_update(const KernelArgs ka, const floa
       if (tid < 64) icp_solve_and_update(tid, iter);
       __syncthreads();
     } else
-      t3 = solve_and_update(prm.r2, prm.fixed_iters, pad, tid, iter, prof);
+      t3 = solve_and_update<BLOCK / 64>(prm.r2, prm.fixed_iters, pad, tid, iter, prof);
     if (prof) {
       long long t4 = clock64();
       PROF2_ADD(7, t4 - t2);

@@ -1,59 +1,99 @@
-// ieskf_lds_tail.h — the serial tail of one iteration of the LDS IESKF kernels and the covariance epilogue: the 6 x 6 solve +
-// boxPlus on one wave (solve_wave0), the next iteration's constants (next_iter_consts), the Gauss-Newton row and step of
-// the ICP fallback (icp_row_dev, icp_solve_and_update), the Joseph update (joseph_epilogue).  Included by ieskf_lds_impl.h
+// ieskf_lds_tail.h — the serial tail of one iteration of the LDS IESKF kernels and the covariance epilogue: the fold of the
+// wave partials, the 6 x 6 solve + boxPlus on one wave (solve_wave0), the next iteration's constants (next_iter_consts),
+// |dx| and the loop's bookkeeping on a fourth wave (tail_bookkeeping), the Gauss-Newton row and step of the ICP fallback
+// (icp_row_dev, icp_solve_and_update), the Joseph update (joseph_epilogue).  Included by ieskf_lds_impl.h
 // INSIDE its instantiation namespace, behind the definition of g_lds / LdsStore (code motion of round 6: the hot header
-// had grown past 2 200 lines; nothing here changed).  Reference: SE:542-580 (gain, increment, stop rules), SE:594-598
+// had grown past 2 200 lines).  Reference: SE:542-580 (gain, increment, stop rules), SE:594-598
 // (Joseph update), SE:1163-1320 (estimateTransform).
 #pragma once
 
 // ---------------------------------------------------------------------------
 // The serial tail of one iteration, kept out of line: its register needs (a 6x7 system in
-// registers, the 19-state) are allocated on their own instead of inflating — and spilling —
-// the search loop it would otherwise be fused with.  Called by every thread (barriers inside).
+// registers, the quaternion chain) are allocated on their own instead of inflating — and spilling —
+// the search loop it would otherwise be fused with.
 // ---------------------------------------------------------------------------
 // Round 4: the out-of-line bodies are entered by the waves that work in them only — solve_wave0 by wave 0,
-// next_iter_consts by waves 0-2 — and the barriers between them are the caller's.  As one function called by all eight
-// waves (rounds 2-3) every wave ran its prologue and epilogue, nine callee-saved registers to scratch and back per wave
-// and iteration: ~190 MB of scratch stores per launch of 1024 scans, most of the 208 MB WRITE_SIZE counted (the
-// hand-over of the several-part updates is 35 MB of it).
-__device__ __noinline__ long long solve_wave0(double prm_r2, int prm_fixed_iters, int lane, bool prof) {
+// next_iter_consts by waves 0-2, tail_bookkeeping by wave 3 — and the barriers between them are the caller's.  As one
+// function called by all eight waves (rounds 2-3) every wave ran its prologue and epilogue, nine callee-saved registers
+// to scratch and back per wave and iteration: ~190 MB of scratch stores per launch of 1024 scans, most of the 208 MB
+// WRITE_SIZE counted (the hand-over of the several-part updates is 35 MB of it).
+//
+// What the next iteration waits for is ONE chain:
+//   28 sums -> [N | z] (42 lanes) -> wave_gj_solve6 -> dx (18 lanes) -> dth = dx[6..8] -> q (+) dth -> { Rt | phi, Gt | d[6..8] }
+// and only that chain is left on wave 0 between the reduction's barrier and the barrier that publishes q:
+//   - wave 0 folds the wave partials itself (lanes 0-27) and goes straight on to [N | z]: the readers of the sums are
+//     this wave, a wave-level fence stands where the reduction's second barrier stood;
+//   - |r| and the residual-growth test do not depend on the solve and are done in front of it;
+//   - lanes 0-17 own one component of dx each: one add into their component of linState_, one subtraction for their
+//     component of x_filter (-) x_lin, both stored by the lane itself.  After the reduction's barrier nobody but this
+//     wave reads the iteration constants (every other wave is on its way to the tail's first barrier), so these go
+//     straight to L.ic — no staged copy of the 19-state, no 36 v_readlane to spread dx over the wave, no lane 0 that
+//     stores 22 values one after the other.  Only dth is broadcast (6 v_readlane), the NaN test is a ballot;
+//   - |dx|, its square root, the stop rule and the loop's bookkeeping are wave 3's (tail_bookkeeping), from the dx
+//     staged in LDS, behind the first barrier and next to the constants.
+// Arithmetic is where it was: every value is formed by the same operations in the same order (the fold g = 0 .. NW - 1,
+// |dx|^2 k = 0 .. 17, the quaternion chain), only who forms it and when has changed.
+template <int NW>
+__device__ __forceinline__ void fold_partials(int lane) {  // lanes 0-27 of wave 0: the ordered fold over the wave partials
+  LdsStore& L = g_lds;
+  if (lane < 28) {
+    double sacc = 0;
+#pragma unroll
+    for (int g = 0; g < NW; ++g) sacc += L.partial[g * 28 + lane];
+    L.sums[lane] = sacc;
+  }
+}
+constexpr int kStageRn = 0, kStageDx = 1;  // L.aug[0]: |r|, dx[18];  L.aug[1] (as int): diverged
+template <int NW>
+__device__ __noinline__ long long solve_wave0(double prm_r2, int lane, bool prof) {
   long long t3 = 0;
   LdsStore& L = g_lds;
   // ---- wave 0: (sigma^2 I + A P_SS) w = g + A d_S  (push-through form of SE:542-549) solved across the wave
-  // (wave_gj_solve6: Gauss-Jordan, one element per lane, no back-substitution), dx = d - P[:,S] w, NaN / divergence /
-  // convergence tests and boxPlus (SE:552-580).  This wave walks a chain of dependent f64 operations while the other
+  // (wave_gj_solve6: Gauss-Jordan, one element per lane, no back-substitution), dx = d - P[:,S] w, NaN / divergence
+  // tests and boxPlus (SE:552-580).  This wave walks a chain of dependent f64 operations while the other
   // seven wait at the barrier, so the chain is kept short: the rotation maps take their short-series forms
   // (lins_math.h axis2quat_fast, quat2axis_fast, phi_and_gt_small — no libm call, no square root, one division for
   // the rotations an update sees) and fall back to libm outside their range.  Round 2, measured in isolation
   // (tools/tail_cycles.py): solve 3418 -> 2487 cycles, boxPlus' axis2quat 1487 -> 582, phi + Rinvleft 2087 -> 863;
-  // in the kernel the tail's share of a late iteration fell from 12.8 to 5.4 us per launch.  The new linearisation state is STAGED in LDS — the old one may
-  // still be read by the other waves until the barrier — and after it three waves split the constants of the next
-  // iteration: wave 0 -> linState_, R^T;  wave 1 -> phi, Rinvleft(-phi)^T;  wave 2 -> x_filter (-) x_lin.
+  // in the kernel the tail's share of a late iteration fell from 12.8 to 5.4 us per launch.  After the barrier three
+  // waves split the constants of the next iteration from the new q: wave 0 -> R^T;  wave 1 -> phi, Rinvleft(-phi)^T;
+  // wave 2 -> the rotation part of x_filter (-) x_lin.
   // (Until round 2 the first three waves each ran the whole solve redundantly to save the staging: 2 x ~2.5 k
   // issued instructions per iteration for nothing.)
-  double* const stage = &L.aug[0][0];  // 22 doubles: linState_ (19), |r|, |r| kept, |dx|
-  int* const stage_flags = reinterpret_cast<int*>(&L.aug[1][0]);  // diverged, converged
+  double* const stage = &L.aug[0][0];
+  int* const stage_flags = reinterpret_cast<int*>(&L.aug[1][0]);
+  fold_partials<NW>(lane);
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   {
     double v = 0.0;
     if (lane < 42) {
+      // One pass for the 36 lanes of N and the 6 of z: the column a lane multiplies into — P[S, S_j] or d_S — and its
+      // first term are SELECTED, not branched on (as two branches the wave walked both chains one after the other).
       const int i = lane / 7, j = lane % 7;
-      if (j < 6) {
-        v = (i == j ? prm_r2 : 0.0);
+      const bool rhs = j == 6;
+      const double* const col = rhs ? &L.ic.d[0] : &L.P[sidx(j)];
+      const int stride = rhs ? 1 : 18;
+      const double z0 = L.sums[21 + i];
+      v = rhs ? z0 : (i == j ? prm_r2 : 0.0);
 #pragma unroll
-        for (int k = 0; k < 6; ++k) v += sym6(L.sums, i, k) * L.P[sidx(k) * 18 + sidx(j)];
-      } else {
-        v = L.sums[21 + i];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) v += sym6(L.sums, i, k) * L.ic.d[sidx(k)];
-      }
+      for (int k = 0; k < 6; ++k) v += sym6(L.sums, i, k) * col[sidx(k) * stride];
     }
-    // (what dx needs from LDS besides the solution is read BEFORE the solve: the reads then wait behind nothing)
-    double pls[6] = {0, 0, 0, 0, 0, 0}, dl = 0;
+    // (what dx and the lanes' own components need from LDS besides the solution is read BEFORE the solve: the reads
+    // then wait behind nothing)
+    double pls[6] = {0, 0, 0, 0, 0, 0}, dl = 0, lin_l = 0, filt_l = 0;
+    const int li = lane < 6 ? lane : lane + 1;  // p,v at 0..5; ba,bw,g at 10..18 (q occupies 6..9)
     if (lane < 18) {
 #pragma unroll
       for (int k = 0; k < 6; ++k) pls[k] = L.P[lane * 18 + sidx(k)];
       dl = L.ic.d[lane];
+      lin_l = L.ic.lin[li], filt_l = L.filt[li];
     }
+    const Q4 q{L.ic.lin[6], L.ic.lin[7], L.ic.lin[8], L.ic.lin[9]};
+    // |r| and the growth test (SE:556) are independent of the solve: their square root overlaps its lane gathers
+    const double rn = sqrt(L.sums[27]);
+    const int grew = __builtin_amdgcn_readfirstlane(rn > L.res_prev * 10 ? 1 : 0);
     double wsol[6];
 #ifdef LINS_PROF_TAIL
     if (prof && lane == 0) L.prof_tail[0] = clock64();
@@ -69,119 +109,105 @@ __device__ __noinline__ long long solve_wave0(double prm_r2, int prm_fixed_iters
 #pragma unroll
       for (int k = 0; k < 6; ++k) sacc += pls[k] * wsol[k];
       dxi = dl - sacc;
+      stage[kStageDx + lane] = dxi;
     }
     if (prof) t3 = clock64();
-    double lin[19];
-#pragma unroll
-    for (int k = 0; k < 19; ++k) lin[k] = L.ic.lin[k];
-    double dth[3] = {0, 0, 0};
-    bool has_nan = false;
-    double un = 0;
-#pragma unroll
-    for (int k = 0; k < 18; ++k) {
-      const double vk = readlane_f64(dxi, k);
-      has_nan = has_nan || isnan(vk);
-      un += vk * vk;
-      if (k >= 6 && k < 9)
-        dth[k - 6] = vk;
-      else
-        lin[k < 6 ? k : k + 1] += vk;  // p,v at 0..5; ba,bw,g at 10..18 (q occupies 6..9)
+    const bool has_nan = __ballot(lane < 18 && isnan(dxi)) != 0;
+    const int div = has_nan ? 2 : (grew ? 1 : 0);
+    if (!div) {  // (wave-uniform)
+      if (lane < 18 && !(lane >= 6 && lane < 9)) {
+        const double nl = lin_l + dxi;
+        L.ic.lin[li] = nl;
+        L.ic.d[lane] = filt_l - nl;  // boxMinus(filter, lin), KF:84-94, its vector part
+      }
+      const V3 dth{readlane_f64(dxi, 6), readlane_f64(dxi, 7), readlane_f64(dxi, 8)};
+      const Q4 qn = qnormalized(qmul(q, axis2quat_fast(dth)));
+      if (lane == 0) L.ic.lin[6] = qn.w, L.ic.lin[7] = qn.x, L.ic.lin[8] = qn.y, L.ic.lin[9] = qn.z;
     }
-    un = sqrt(un);
-    const double rn = sqrt(L.sums[27]);
-    double res_prev = L.res_prev;
-    int div = 0, conv = 0;
-    if (has_nan) {
-      div = 2, un = L.upd_norm;
-    } else if (rn > res_prev * 10) {
-      div = 1, un = L.upd_norm;
-    } else {
-      const Q4 qn = qnormalized(qmul(Q4{lin[6], lin[7], lin[8], lin[9]}, axis2quat_fast(V3{dth[0], dth[1], dth[2]})));
-      lin[6] = qn.w, lin[7] = qn.x, lin[8] = qn.y, lin[9] = qn.z;
-      if (un <= 1e-2 && !prm_fixed_iters) conv = 1;
-      res_prev = rn;
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int k = 0; k < 19; ++k) stage[k] = lin[k];
-      stage[19] = rn, stage[20] = res_prev, stage[21] = un;
-      stage_flags[0] = div, stage_flags[1] = conv;
-    }
+    if (lane == 0) stage[kStageRn] = rn, stage_flags[0] = div;
   }
   return t3;
 }
-// the constants of the next iteration from the staged linearisation state: wave 0 -> linState_, R^T; wave 1 -> phi,
-// Rinvleft(-phi)^T; wave 2 -> x_filter (-) x_lin
+// the constants of the next iteration from the new q: wave 0 -> R^T; wave 1 -> phi, Rinvleft(-phi)^T; wave 2 -> the
+// rotation part of x_filter (-) x_lin
 __device__ __noinline__ void next_iter_consts(int wave, int lane) {
   LdsStore& L = g_lds;
-  const double* const stage = &L.aug[0][0];
   {
-    const Q4 q{stage[6], stage[7], stage[8], stage[9]};
+    const Q4 q{L.ic.lin[6], L.ic.lin[7], L.ic.lin[8], L.ic.lin[9]};
     // (static indices only: a lane-indexed register array would be spilled to scratch)
     if (wave == 0) {
       const M3 Rt = mtrans(qmat(q));
-      if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 19; ++k) L.ic.lin[k] = stage[k];
-        L.ic.Rt = Rt;
-      }
+      if (lane == 0) L.ic.Rt = Rt;
     } else if (wave == 1) {
       V3 phi;
       M3 Gt;
       phi_and_Gt(q, phi, Gt);
       if (lane == 0) L.ic.phi = phi, L.ic.Gt = Gt;
     } else {
-      // boxMinus(filter, lin), KF:84-94
+      // boxMinus(filter, lin), KF:84-94, its rotation part
       const Q4 qf{L.filt[6], L.filt[7], L.filt[8], L.filt[9]};
       const V3 da = quat2axis_fast(qmul(qinverse(q), qf));
-      if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          L.ic.d[0 + k] = L.filt[0 + k] - stage[0 + k];
-          L.ic.d[3 + k] = L.filt[3 + k] - stage[3 + k];
-          L.ic.d[9 + k] = L.filt[10 + k] - stage[10 + k];
-          L.ic.d[12 + k] = L.filt[13 + k] - stage[13 + k];
-          L.ic.d[15 + k] = L.filt[16 + k] - stage[16 + k];
-        }
-        L.ic.d[6] = da.x, L.ic.d[7] = da.y, L.ic.d[8] = da.z;
-      }
+      if (lane == 0) L.ic.d[6] = da.x, L.ic.d[7] = da.y, L.ic.d[8] = da.z;
     }
+  }
+}
+// what the loop head reads, by wave 3 next to the constants: |dx| over k = 0 .. 17 from the staged dx, the stop rule
+// (SE:570-580), the residual norms, the iteration count.  A diverged update keeps the |dx| and the |r| it had.
+__device__ __noinline__ void tail_bookkeeping(int prm_fixed_iters, int iter, int lane) {
+  LdsStore& L = g_lds;
+  const double* const stage = &L.aug[0][0];
+  const int div = reinterpret_cast<const int*>(&L.aug[1][0])[0];
+  const double rn = stage[kStageRn];
+  double un = 0;
+#pragma unroll
+  for (int k = 0; k < 18; ++k) {
+    const double vk = stage[kStageDx + k];
+    un += vk * vk;
+  }
+  un = sqrt(un);
+  if (lane == 0) {
+    L.res_last = rn;
+    if (!div) L.res_prev = rn, L.upd_norm = un;
+    L.conv = (!div && un <= 1e-2 && !prm_fixed_iters) ? 1 : 0;
+    L.div = div;
+    L.iter = iter + 1;
   }
 }
 // (Scalars by value, the profile stamp returned: a reference to the kernel's parameter struct or to a local would
 // force them into scratch for the whole kernel — every later read of a parameter a scratch load.)
+template <int NW>
 __device__ __forceinline__ long long solve_and_update(double prm_r2, int prm_fixed_iters, int prm_pad, int tid, int iter, bool prof) {
+  static_assert(NW >= 4, "wave 3 keeps the loop's books");
   long long t3 = 0;
   LdsStore& L = g_lds;
   const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (prm_pad & 0x10000) {  // counting aid (LINS_DEBUG_SKIP bit 0x10000): no solve, no update — the state stands still
+    if (wave == 0) fold_partials<NW>(lane);
     if (tid == 0) L.iter = iter + 1;
     __syncthreads();
     return t3;
   }
-  const double* const stage = &L.aug[0][0];  // 22 doubles: linState_ (19), |r|, |r| kept, |dx|
-  const int* const stage_flags = reinterpret_cast<const int*>(&L.aug[1][0]);  // diverged, converged
+  const int* const stage_flags = reinterpret_cast<const int*>(&L.aug[1][0]);  // diverged
 #ifdef LINS_PROF_TAIL  // (build with -DLINS_PROF_WAVES=99 -DLINS_PROF_TAIL=1: slots 6..11 of the phase profile = the tail's sub-phases on thread 0, tools/tail_phases.py)
   const long long a0 = prof ? clock64() : 0;
 #endif
-  if (wave == 0) t3 = solve_wave0(prm_r2, prm_fixed_iters, lane, prof);
+  if (wave == 0) t3 = solve_wave0<NW>(prm_r2, lane, prof);
 #ifdef LINS_PROF_TAIL
   const long long a1 = prof ? clock64() : 0;
 #endif
-  __syncthreads();  // every reader of the old linearisation state is done; the staged one is visible
+  __syncthreads();  // the new q, the staged dx and the divergence flag are visible
 #ifdef LINS_PROF_TAIL
   const long long a2 = prof ? clock64() : 0;
 #endif
   const int div = stage_flags[0];
-  if (wave < 3 && !div) next_iter_consts(wave, lane);
+  if (wave < 3) {
+    if (!div) next_iter_consts(wave, lane);
+  } else if (wave == 3) {
+    tail_bookkeeping(prm_fixed_iters, iter, lane);
+  }
 #ifdef LINS_PROF_TAIL
   const long long a3 = prof ? clock64() : 0;
 #endif
-  if (tid == 0) {
-    L.res_last = stage[19], L.res_prev = stage[20], L.upd_norm = stage[21];
-    L.conv = stage_flags[1], L.div = div;
-    L.iter = iter + 1;
-  }
   __syncthreads();
 #ifdef LINS_PROF_TAIL
   if (prof && tid == 0) {

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Sub-phases of the serial tail of an iteration (solve_and_update, ieskf_lds_tail.h) on thread 0, shader-clock ticks per
 iteration, from a library built with -DLINS_PROF_WAVES=99 -DLINS_PROF_TAIL=1 (tools/build_variant.sh tailprof ...):
-system build, Gauss-Jordan solve, dx + boxPlus + staging, barrier, the next iteration's constants, barrier.
+fold of the wave partials + system build (behind the reduction's ONE barrier), Gauss-Jordan solve, dx + the lanes' own
+components + the quaternion update, barrier, wave 0's share of the next iteration's constants (R^T; wave 1 has phi and
+Rinvleft, wave 2 the rotation part of x_filter (-) x_lin, wave 3 |dx| and the loop's bookkeeping), barrier.
 usage: LINS_IESKF_LIB=ab/tailprof.so tools/tail_phases.py [batch = 1024] [search = mr]"""
 import ctypes as C, importlib, os, sys
 from concurrent.futures import ThreadPoolExecutor
@@ -25,7 +27,7 @@ for _ in range(2):
     ctx.run(); ctx.sync()
 prof = np.zeros((batch, 16), dtype=np.int64)
 L.lins_debug_phase_profile(ctx._h, 1, prof.ctypes.data, batch)
-names = ["system build", "Gauss-Jordan", "dx + boxPlus + staging", "barrier 1", "next constants", "barrier 2"]
+names = ["fold + system build", "Gauss-Jordan", "dx + lanes' lin / d + q", "barrier 1", "next constants (R^T)", "barrier 2"]
 m = prof[:, 6:12].mean(0) / iters
 print(f"{search}, {batch} scans x {iters} iterations, kernel {ctx.last_kernel_ms():.4f} ms; tail on thread 0, ticks per iteration (mean over the scans):")
 print("  " + ", ".join(f"{n} {v:.0f}" for n, v in zip(names, m)) + f"; sum {m.sum():.0f}")
