@@ -327,6 +327,31 @@ void lins_host_map_transform_update(float tobe[6], int has_imu, float imu_roll, 
  * (previousRobotPosPoint) to aft[3..5] is not < 0.3, or have_frames == 0 — and then sets prev to aft[3..5]          */
 int lins_host_map_key_rule(float prev[3], const float aft[6], int have_frames);
 
+/* ---- the pose graph on the CPU (host/pose_graph.cpp) ---------------------------------------------------------------
+ * The restatement lins_pose_graph_* is checked against (include/lins_map.h has the contract; the arithmetic is
+ * csrc/pose_graph_math.h and the solve csrc/pose_graph.h in both libraries: the same phases in the same order, so host
+ * and device differ only where libm does).  One graph per handle; the calls and their errors are the device's.
+ * lins_pose_graph_default_params is exported by this library too. */
+typedef struct lins_host_pose_graph lins_host_pose_graph;
+lins_host_pose_graph* lins_host_pose_graph_create(int max_frames, int max_loops);
+void lins_host_pose_graph_destroy(lins_host_pose_graph* g);
+int lins_host_pose_graph_push(lins_host_pose_graph* g, const float last6[6], const float aft6[6]);
+int lins_host_pose_graph_add_loop(lins_host_pose_graph* g, int latest_id, int closest_id, const lins_key_pose* pose_from, double fitness);
+int lins_host_pose_graph_solve(lins_host_pose_graph* g, const lins_pose_graph_params* prm, lins_pose_graph_result* out);
+int lins_host_pose_graph_poses(lins_host_pose_graph* g, int first_id, int n, lins_key_pose* out);
+int lins_host_pose_graph_count(lins_host_pose_graph* g, int32_t* n_loops);
+int lins_host_pose_graph_poses_f64(lins_host_pose_graph* g, int first_id, int n, double* out); /* n x 12: R row-major, t */
+int lins_host_pose_graph_loop_z(lins_host_pose_graph* g, int loop, double z[12]);
+/* The linearisation at given absolute poses (N x 12; NULL: the estimate), for the finite-difference test: per odometry
+ * factor k = 1 .. N - 1 the residual r_odo[6 (k - 1)], the Hessian block D[36 (k - 1)] = J^T Sigma^-1 J and the gradient
+ * g[6 (k - 1)] = J^T Sigma^-1 r with respect to the right perturbation of the increment T_{k-1}^-1 T_k; per loop l the
+ * residual r_loop[6 l] and M[36 l], the loop's rows being J_{l,k} = M_l Ad(T_k) for min(b, a) < k <= max(b, a).  Any
+ * output may be NULL. */
+int lins_host_pose_graph_linearize(lins_host_pose_graph* g, const double* poses, double* r_odo, double* D, double* gvec, double* r_loop, double* M);
+/* six floats (pitch, yaw, roll, y, z, x) <-> pose (12 doubles) */
+void lins_host_pose_from6(const float p[6], double T[12]);
+void lins_host_pose_to6(const double T[12], float p[6]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -307,6 +307,93 @@ int lins_loop_icp_correspondences(lins_ctx* ctx, const lins_loop_icp_problem* in
  * evaluations it did */
 int lins_last_loop_icp_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* searches);
 
+/* ---- the pose graph: loop closures correct the key-frame history (LM:1167-1183, 1673-1749, 1767-1795) -----------------
+ * The factor graph the mapping node hands to iSAM2, per slot, resident on the device, and a batched Levenberg-Marquardt
+ * solve of it.  The contract is the project's own (DESIGN.md §5.3 "Pose graph"; one scalar definition in
+ * csrc/pose_graph_math.h and one text of the solve in csrc/pose_graph.h, compiled into both libraries):
+ *   poses     T = (R, t) in f64 in the axes GTSAM sees.  Six floats p (pitch, yaw, roll, y, z, x — transformTobeMapped's
+ *             order) give R = Rz(p[1]) Ry(p[0]) Rx(p[2]), t = (p[5], p[3], p[4]), the floats promoted to double before
+ *             sin / cos.  Back: x = atan2(R21, R22), y = asin(-R20), z = atan2(R10, R00), translation as is, rounded once
+ *             to f32; |y| at pi / 2 is outside the contract.
+ *   factors   prior T_0 = Z_p (the first push's aft6) and odometry factor i = 1 .. N - 1 on (T_{i-1}, T_i) with
+ *             Z_i = pose(last)^-1 pose(aft), formed once in f64 at the push; both with the variances (1e-6, 1e-6, 1e-6,
+ *             1e-8, 1e-8, 1e-6), rotation first (LM:383-385).  Loop l on (T_b, T_a) = (latest, closest) with
+ *             Z_l = pose_from^-1 T_a, T_a the estimate when the loop is added, and the variance (double)(float)fitness on
+ *             all six components (LM:1171-1175).
+ *   residual  of a between-factor Z on (T_i, T_j): E = Z^-1 T_i^-1 T_j, r = (Log_SO3(R_E), t_E) — the chart form, no
+ *             SE(3) V^-1 on the translation; the retraction is (R Exp(omega), t + R v).  Cost C = 1/2 sum r^T Sigma^-1 r.
+ *   solve     a graph without loops is returned with the bits it holds, 0 iterations: iSAM2 as the identity.  With loops:
+ *             Levenberg-Marquardt on C over the increments T_{k-1}^-1 T_k (T_0 = Z_p exactly: the prior is satisfied, not
+ *             weighed), one trial an iteration — step from the damped normal equations through the 6 L x 6 L Woodbury
+ *             core, trial cost C'.  The first that holds ends the trial: |C - C'| <= rel_cost_decrease C — the cost
+ *             does not tell the trial from the estimate; this last step is taken and the solve stops (LINS_PG_REL_COST);
+ *             C' < C — the step is accepted, lambda is multiplied by lambda_down, and the solve stops if the step's
+ *             largest component is <= max_increment (LINS_PG_INCREMENT); else the step is rejected and lambda multiplied
+ *             by lambda_up.  iterations >= max_iterations stops it too (LINS_PG_ITERATIONS).
+ *   poses     T_k = T_0 D_1 ... D_k is formed in blocks of 32 consecutive increments, left to right inside a block, the
+ *             block totals left to right, T_k = (prefix of blocks) (prefix inside the block).
+ * Departures from the reference: a converged batch optimum instead of iSAM2's incremental estimate (these parameters
+ * replace relinearizeThreshold = 0.01, LM:249); GTSAM's chart flag is fixed as above; the prior is satisfied exactly; a
+ * pushed frame's increment starts at its measurement Z_i (the reference inserts pose(aft), the same pose when `last` is
+ * the previous frame's estimate).                                                                                     */
+#define LINS_PG_NONE 0       /* not run (no loops), or still running */
+#define LINS_PG_ITERATIONS 1
+#define LINS_PG_INCREMENT 2
+#define LINS_PG_REL_COST 3
+
+typedef struct lins_pose_graph_params {
+  int32_t max_iterations;    /* 50 */
+  int32_t reserved;
+  double rel_cost_decrease;  /* 1e-12 */
+  double max_increment;      /* 1e-11 (rad or m) */
+  double lambda_initial;     /* 1e-5 */
+  double lambda_up;          /* 10 */
+  double lambda_down;        /* 0.1 */
+} lins_pose_graph_params;
+void lins_pose_graph_default_params(lins_pose_graph_params* p);
+
+typedef struct lins_pose_graph_result {
+  double cost_before, cost_after; /* C at the first and at the last accepted estimate (0 for a graph without loops) */
+  double max_increment;           /* the largest step component of the last trial */
+  int32_t iterations, reason;     /* trials run; LINS_PG_* */
+  int32_t status, reserved;       /* LINS_OK */
+} lins_pose_graph_result;
+
+/* Errors of every call below: LINS_E_STATE before lins_pose_graph_init, LINS_E_ARG for a bad slot / id or latest_id ==
+ * closest_id, LINS_E_CAPACITY for a frame or loop beyond the sizes given at init, LINS_E_INPUT for non-finite input or a
+ * loop variance that is not finite and > 0.  A refused call changes nothing.                                            */
+/* n_slots graphs of up to max_frames_per_slot frames and max_loops_per_slot <= 64 loops (else LINS_E_ARG).  A second call
+ * drops every graph and sizes anew.  Device memory: 1 248 bytes a frame and slot, 288 L^2 + 640 L bytes a slot for L
+ * loops.  The loops' core is dense — a trial runs 3 L (L + 1) / 2 + 24 L barrier-separated phases on it — so the solve
+ * suits the tens of loops a slot the reference closes, not hundreds. */
+int lins_pose_graph_init(lins_ctx* ctx, int n_slots, int max_frames_per_slot, int max_loops_per_slot);
+/* saveKeyFramesAndFactor's factor (LM:1673-1705): one frame behind the frames of `slot`; the first frame takes aft6 as
+ * the prior (the caller passes transformTobeMapped, LM:1676; last6 is not read), every other the odometry factor
+ * pose(last6)^-1 pose(aft6).  Returns the frame id — the archive's, when the caller pushes to both. */
+int lins_pose_graph_push(lins_ctx* ctx, int slot, const float last6[6], const float aft6[6]);
+/* performLoopClosure's factor (LM:1167-1181): pose_from as lins_host_loop_pose_from returns it, fitness the ICP's */
+int lins_pose_graph_add_loop(lins_ctx* ctx, int slot, int latest_id, int closest_id, const lins_key_pose* pose_from, double fitness);
+/* the solve for n slots (each at most once, else LINS_E_ARG) in one sequence of launches on the context's stream: one
+ * workgroup per slot problem, the trials queued in groups with one word "problems still running" read between the
+ * groups.  A problem's result bits do not depend on the batch it is in or on what the context ran before.  Parameters
+ * outside max_iterations >= 1, finite bounds, lambda_initial > 0, lambda_up > 1, 0 < lambda_down <= 1: LINS_E_ARG. */
+int lins_pose_graph_solve(lins_ctx* ctx, int n, const int32_t* slots, const lins_pose_graph_params* prm, lins_pose_graph_result* out);
+/* the estimate of frames first_id .. first_id + n - 1 as PointTypePose, the fields as LM:1721-1733 assigns them */
+int lins_pose_graph_poses(lins_ctx* ctx, int slot, int first_id, int n, lins_key_pose* out);
+/* correctPoses (LM:1767-1795) and LM:1737-1749 in one call: every pose of `slot` goes to lins_archive_set_poses when the
+ * archive is initialised (LINS_E_ARG when it holds fewer frames of the slot), the poses of the newest frames go to the
+ * local map's ring by age when the local map is initialised — the ring's frames are taken to be the graph's newest;
+ * LINS_E_ARG when it holds fewer than min(window, N) — and for stream >= 0 aft = last = tobe = the newest pose through
+ * lins_streams_map_set_pose. */
+int lins_pose_graph_apply(lins_ctx* ctx, int slot, int stream);
+/* frames / loops of slot (>= 0) */
+int lins_pose_graph_count(lins_ctx* ctx, int slot, int32_t* n_loops);
+/* HIP-event time (ms) of the device sequence of the last solve and the trials it ran over all problems */
+int lins_last_pose_graph_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* iterations);
+/* test aids: the estimate in f64 (n x 12: R row-major, t) and loop l's measurement */
+int lins_debug_pose_graph_poses_f64(lins_ctx* ctx, int slot, int first_id, int n, double* out);
+int lins_debug_pose_graph_loop_z(lins_ctx* ctx, int slot, int loop, double z[12]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -417,6 +417,42 @@ def loop_icp_problem_c(source, target):
     return c, keep
 
 
+# ---- the pose graph (include/lins_map.h lins_pose_graph_*, include/lins_host.h lins_host_pose_graph_*) --------
+PG_NONE, PG_ITERATIONS, PG_INCREMENT, PG_REL_COST = range(4)
+
+
+class PoseGraphParamsC(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("reserved", C.c_int32), ("rel_cost_decrease", C.c_double), ("max_increment", C.c_double),
+                ("lambda_initial", C.c_double), ("lambda_up", C.c_double), ("lambda_down", C.c_double)]
+
+
+class PoseGraphResultC(C.Structure):
+    _fields_ = [("cost_before", C.c_double), ("cost_after", C.c_double), ("max_increment", C.c_double), ("iterations", C.c_int32),
+                ("reason", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return dict(cost_before=float(self.cost_before), cost_after=float(self.cost_after), max_increment=float(self.max_increment),
+                    iterations=int(self.iterations), reason=int(self.reason), status=int(self.status))
+
+
+def pose_graph_params(lib, **kw):
+    """lins_pose_graph_default_params of `lib` (both libraries export it) with fields overridden by keyword"""
+    p = PoseGraphParamsC()
+    lib.lins_pose_graph_default_params.argtypes = [C.POINTER(PoseGraphParamsC)]
+    lib.lins_pose_graph_default_params.restype = None
+    lib.lins_pose_graph_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"lins_pose_graph_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def six_floats(p):
+    """six floats (pitch, yaw, roll, y, z, x) as a C array"""
+    return (C.c_float * 6)(*[float(v) for v in np.asarray(p, dtype=np.float32)])
+
+
 # ---- the mapping node's step for streams (include/lins_streams_map.h lins_streams_map_*, lins_map_associate_batch) ----
 MAP_STEP_SKIPPED = 1
 

@@ -10,6 +10,10 @@
 #include "../../include/lins_streams_map.h"
 #include "lins_records.h"
 
+namespace lins_pg {
+struct Prob;  // pose_graph.h
+}
+
 namespace lins {
 
 struct DevParams;   // ieskf_device.h
@@ -149,5 +153,11 @@ void launch_ar_keep(hipStream_t s, int j0, int n_jobs, int n_tiles, const int2* 
                     const float4* stage, int* tilecnt);
 void launch_ar_compact(hipStream_t s, int n_tiles, const int2* tiles, const LmJob* jobs, const LmState* states, const int* jflags, const float4* stage,
                        const int* tilecnt, float4* out);
+
+// ---- pose_graph_kernels.hip: the pose graph's solve, one workgroup per problem (pose_graph.h) ----
+// the poses and the cost of every problem as it stands (the first launch of a solve)
+void launch_pose_graph_begin(hipStream_t s, int n_problems, const lins_pg::Prob* probs);
+// one Levenberg-Marquardt trial of every problem still active; still_running (may be null) += the problems that go on
+void launch_pose_graph_trial(hipStream_t s, int n_problems, const lins_pg::Prob* probs, const lins_pose_graph_params& prm, int* still_running);
 
 }  // namespace lins

@@ -129,6 +129,12 @@ int local_map_view(lins_ctx* ctx, LocalMapView* v) {
   return LINS_OK;
 }
 int local_map_slots(lins_ctx* ctx) { return local_of(ctx)->n_slots; }
+int local_map_ring(lins_ctx* ctx, int slot, int* window) {
+  LocalMap* m = local_of(ctx);
+  if (slot < 0 || slot >= m->n_slots) return -1;
+  if (window) *window = m->window;
+  return m->count[slot];
+}
 }  // namespace lins
 
 extern "C" {

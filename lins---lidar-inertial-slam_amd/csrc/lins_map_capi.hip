@@ -57,6 +57,9 @@ struct MapState {
   // the streams' map poses of lins_streams_map_* (lins_streams_map_capi.hip), likewise
   void* pose = nullptr;
   void (*pose_free)(void*) = nullptr;
+  // the pose graphs of lins_pose_graph_* (lins_pose_graph_capi.hip), likewise
+  void* graph = nullptr;
+  void (*graph_free)(void*) = nullptr;
 };
 
 void map_state_free(void* p) {
@@ -68,6 +71,7 @@ void map_state_free(void* p) {
   if (m->archive) m->archive_free(m->archive);
   if (m->loop) m->loop_free(m->loop);
   if (m->pose) m->pose_free(m->pose);
+  if (m->graph) m->graph_free(m->graph);
   delete m;
 }
 
@@ -329,6 +333,11 @@ void** map_pose_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
   MapState* m = state_of(ctx);
   m->pose_free = free_fn;
   return &m->pose;
+}
+void** map_graph_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
+  MapState* m = state_of(ctx);
+  m->graph_free = free_fn;
+  return &m->graph;
 }
 
 // lins_scan2map_batch with LINS_MAP_LOCAL for the step of lins_streams_map_capi.hip: the same gridding, the same rounds,

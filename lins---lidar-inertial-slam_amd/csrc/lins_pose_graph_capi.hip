@@ -1,0 +1,288 @@
+// lins_pose_graph_capi.hip — C ABI of the pose graph (include/lins_map.h lins_pose_graph_*): host orchestration around
+// pose_graph_kernels.hip.  The bookkeeping of a slot's graph (validation, the measurements formed in f64, the six floats
+// handed back) is lins_pg::Graph, shared with the CPU restatement; the factors and the increments live on the device in
+// arrays sized at init — a solve uploads only the frames and loops added since the last one — and the trials are queued
+// in groups with one word "problems still running" read between the groups.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/lins_map.h"
+#include "../../include/lins_streams_map.h"
+#include "lins_ctx_priv.h"
+#include "lins_launch.h"
+#include "local_map.h"
+#include "pose_graph.h"
+
+using namespace lins;
+using lins_pg::Graph;
+using lins_pg::LoopRec;
+using lins_pg::Prob;
+using lins_pg::State;
+
+namespace {
+
+// Trials queued between two reads of the "still running" word.  A trial is one launch; the solve converges
+// quadratically near the optimum, in 4-8 trials on the loop closures of the tests, so groups of 4 queue at most 3 empty
+// launches.  A reasoned default, not a measured one.
+constexpr int kPgGroup = 4;
+
+struct PgMem {
+  int n_slots = 0, F = 0, L = 0;
+  std::vector<Graph> g;
+  std::vector<int> up_frames, up_loops;  // what of each slot is on the device
+  double *d_Z = nullptr, *d_D = nullptr, *d_Dt = nullptr, *d_I = nullptr, *d_T = nullptr, *d_Tt = nullptr, *d_Q = nullptr;
+  double *d_B = nullptr, *d_c = nullptr, *d_P = nullptr, *d_q = nullptr, *d_S = nullptr, *d_y = nullptr;
+  LoopRec* d_loops = nullptr;
+  State* d_st = nullptr;
+  Prob* d_probs = nullptr;
+  int *d_running = nullptr, *h_running = nullptr;
+  float ms = 0.f;
+  uint64_t iterations = 0;
+  size_t nq() const { return (size_t)F / lins_pg::kPrefixBlock + 2; }
+};
+
+void pg_release(PgMem* m) {
+  (void)hipFree(m->d_Z), (void)hipFree(m->d_D), (void)hipFree(m->d_Dt), (void)hipFree(m->d_I), (void)hipFree(m->d_T), (void)hipFree(m->d_Tt);
+  (void)hipFree(m->d_Q), (void)hipFree(m->d_B), (void)hipFree(m->d_c), (void)hipFree(m->d_P), (void)hipFree(m->d_q), (void)hipFree(m->d_S);
+  (void)hipFree(m->d_y), (void)hipFree(m->d_loops), (void)hipFree(m->d_st), (void)hipFree(m->d_probs), (void)hipFree(m->d_running);
+  (void)hipHostFree(m->h_running);
+  *m = PgMem();
+}
+void pg_free(void* p) {
+  pg_release((PgMem*)p);
+  delete (PgMem*)p;
+}
+
+PgMem* mem_of(lins_ctx* ctx) {
+  void** slot = map_graph_slot(ctx, pg_free);
+  if (!*slot) *slot = new PgMem();
+  return (PgMem*)*slot;
+}
+
+Prob prob_of(const PgMem* m, int slot, int idx) {
+  const size_t s = (size_t)slot, F = (size_t)m->F, L = (size_t)m->L;
+  Prob p{};
+  p.n_frames = m->g[slot].n_frames(), p.n_loops = (int)m->g[slot].loops.size(), p.slot = slot;
+  p.Z = m->d_Z + s * F * 12, p.D = m->d_D + s * F * 12, p.Dt = m->d_Dt + s * F * 12, p.I = m->d_I + s * F * 12;
+  p.T = m->d_T + s * F * 12, p.Tt = m->d_Tt + s * F * 12, p.Q = m->d_Q + s * m->nq() * 12;
+  p.B = m->d_B + s * F * 36, p.c = m->d_c + s * F * 6, p.P = m->d_P + s * F * 36, p.q = m->d_q + s * F * 6;
+  p.loops = m->d_loops + s * L, p.S = m->d_S + s * 36 * L * L, p.y = m->d_y + s * 18 * L;
+  p.st = m->d_st + idx;
+  return p;
+}
+
+}  // namespace
+
+extern "C" {
+
+void lins_pose_graph_default_params(lins_pose_graph_params* p) {
+  if (p) lins_pg::default_params(p);
+}
+
+int lins_pose_graph_init(lins_ctx* ctx, int n_slots, int max_frames, int max_loops) {
+  if (!ctx || n_slots < 1 || max_frames < 1 || max_loops < 0 || max_loops > lins_pg::kMaxLoops) return LINS_E_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  PgMem* m = mem_of(ctx);
+  HIP_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));
+  pg_release(m);
+  const size_t n = (size_t)n_slots, F = (size_t)max_frames, L = (size_t)std::max(max_loops, 1);
+  m->F = max_frames, m->L = (int)L;
+  double** frames12[] = {&m->d_Z, &m->d_D, &m->d_Dt, &m->d_I, &m->d_T, &m->d_Tt};
+  for (double** p : frames12) HIP_TRY(ctx, hipMalloc((void**)p, n * F * 12 * sizeof(double)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_Q, n * m->nq() * 12 * sizeof(double)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_B, n * F * 36 * sizeof(double)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_P, n * F * 36 * sizeof(double)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_c, n * F * 6 * sizeof(double)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_q, n * F * 6 * sizeof(double)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_S, n * 36 * L * L * sizeof(double)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_y, n * 18 * L * sizeof(double)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_loops, n * L * sizeof(LoopRec)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_st, n * sizeof(State)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_probs, n * sizeof(Prob)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_running, 128 * sizeof(int)));
+  HIP_TRY(ctx, hipHostMalloc((void**)&m->h_running, sizeof(int)));
+  m->g.assign(n, Graph());
+  for (Graph& g : m->g) g.max_frames = max_frames, g.max_loops = max_loops;
+  m->up_frames.assign(n, 0), m->up_loops.assign(n, 0);
+  m->n_slots = n_slots;
+  return LINS_OK;
+}
+
+int lins_pose_graph_push(lins_ctx* ctx, int slot, const float last6[6], const float aft6[6]) {
+  if (!ctx) return LINS_E_ARG;
+  PgMem* m = mem_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (slot < 0 || slot >= m->n_slots) return LINS_E_ARG;
+  return m->g[slot].push(last6, aft6);
+}
+
+int lins_pose_graph_add_loop(lins_ctx* ctx, int slot, int latest_id, int closest_id, const lins_key_pose* pose_from, double fitness) {
+  if (!ctx) return LINS_E_ARG;
+  PgMem* m = mem_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (slot < 0 || slot >= m->n_slots) return LINS_E_ARG;
+  const int rc = m->g[slot].add_loop(latest_id, closest_id, pose_from, fitness);
+  return rc < 0 ? rc : LINS_OK;
+}
+
+int lins_pose_graph_solve(lins_ctx* ctx, int n, const int32_t* slots, const lins_pose_graph_params* prm, lins_pose_graph_result* out) {
+  if (!ctx || n < 0 || (n && (!slots || !out)) || !lins_pg::params_ok(prm)) return LINS_E_ARG;
+  PgMem* m = mem_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (n > m->n_slots) return LINS_E_ARG;
+  std::vector<char> seen(m->n_slots, 0);
+  for (int k = 0; k < n; ++k) {
+    if (slots[k] < 0 || slots[k] >= m->n_slots || seen[slots[k]]) return LINS_E_ARG;
+    seen[slots[k]] = 1;
+  }
+  m->ms = 0.f, m->iterations = 0;
+  std::vector<int> run;  // the entries with loops: the others are returned with the bits they hold
+  for (int k = 0; k < n; ++k) {
+    std::memset(out + k, 0, sizeof out[k]);
+    const Graph& g = m->g[slots[k]];
+    if (!g.loops.empty() && g.n_frames() >= 2) run.push_back(k);
+  }
+  if (run.empty()) return LINS_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  hipStream_t st = ctx_stream(ctx);
+  const int nr = (int)run.size();
+  std::vector<Prob> probs(nr);
+  std::vector<State> states(nr);
+  for (int i = 0; i < nr; ++i) {
+    const int slot = slots[run[i]];
+    const Graph& g = m->g[slot];
+    probs[i] = prob_of(m, slot, i);
+    lins_pg::state_init(states[i], *prm);
+    const int f0 = m->up_frames[slot], f1 = g.n_frames(), l0 = m->up_loops[slot], l1 = (int)g.loops.size();
+    if (f1 > f0) {  // a new frame's increment starts at its measurement
+      HIP_TRY(ctx, hipMemcpyAsync(probs[i].Z + 12 * (size_t)f0, g.Z.data() + 12 * (size_t)f0, 12 * (size_t)(f1 - f0) * sizeof(double), hipMemcpyHostToDevice, st));
+      HIP_TRY(ctx, hipMemcpyAsync(probs[i].D + 12 * (size_t)f0, g.Z.data() + 12 * (size_t)f0, 12 * (size_t)(f1 - f0) * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    if (l1 > l0) HIP_TRY(ctx, hipMemcpyAsync(probs[i].loops + l0, g.loops.data() + l0, (size_t)(l1 - l0) * sizeof(LoopRec), hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(m->d_probs, probs.data(), (size_t)nr * sizeof(Prob), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(m->d_st, states.data(), (size_t)nr * sizeof(State), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemsetAsync(m->d_running, 0, 128 * sizeof(int), st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));  // (pageable sources: the graphs' vectors may grow behind this call)
+  for (int i = 0; i < nr; ++i) m->up_frames[slots[run[i]]] = probs[i].n_frames, m->up_loops[slots[run[i]]] = probs[i].n_loops;
+  hipEvent_t e0, e1;
+  ctx_events(ctx, &e0, &e1);
+  HIP_TRY(ctx, hipEventRecord(e0, st));
+  launch_pose_graph_begin(st, nr, m->d_probs);
+  for (int done = 0, grp = 0; done < prm->max_iterations; ++grp) {
+    const int cnt = std::min(kPgGroup, prm->max_iterations - done);
+    int* word = m->d_running + (grp & 127);
+    if (grp >= 128) HIP_TRY(ctx, hipMemsetAsync(word, 0, sizeof(int), st));
+    for (int i = 0; i < cnt; ++i) launch_pose_graph_trial(st, nr, m->d_probs, *prm, i + 1 == cnt ? word : nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    done += cnt;
+    if (done >= prm->max_iterations) break;
+    HIP_TRY(ctx, hipMemcpyAsync(m->h_running, word, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (*m->h_running == 0) break;
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(e1, st));
+  std::vector<std::vector<double>> T(nr);
+  for (int i = 0; i < nr; ++i) {
+    T[i].resize(12 * (size_t)probs[i].n_frames);
+    HIP_TRY(ctx, hipMemcpyAsync(T[i].data(), probs[i].T, T[i].size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(states.data(), m->d_st, (size_t)nr * sizeof(State), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  HIP_TRY(ctx, hipEventElapsedTime(&m->ms, e0, e1));
+  for (int i = 0; i < nr; ++i) {
+    const State& s = states[i];
+    lins_pose_graph_result& r = out[run[i]];
+    r.cost_before = s.cost0, r.cost_after = s.cost, r.max_increment = s.max_inc;
+    r.iterations = s.iterations, r.reason = s.reason, r.status = LINS_OK;
+    m->iterations += (uint64_t)s.iterations;
+    m->g[slots[run[i]]].store_solution(T[i].data(), nullptr);
+  }
+  return LINS_OK;
+}
+
+int lins_pose_graph_poses(lins_ctx* ctx, int slot, int first_id, int n, lins_key_pose* out) {
+  if (!ctx) return LINS_E_ARG;
+  PgMem* m = mem_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (slot < 0 || slot >= m->n_slots || first_id < 0 || n < 0 || (long long)first_id + n > m->g[slot].n_frames() || (n && !out)) return LINS_E_ARG;
+  for (int i = 0; i < n; ++i) m->g[slot].key_pose(first_id + i, out + i);
+  return LINS_OK;
+}
+
+int lins_pose_graph_count(lins_ctx* ctx, int slot, int32_t* n_loops) {
+  if (!ctx) return LINS_E_ARG;
+  PgMem* m = mem_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (slot < 0 || slot >= m->n_slots) return LINS_E_ARG;
+  if (n_loops) *n_loops = (int32_t)m->g[slot].loops.size();
+  return m->g[slot].n_frames();
+}
+
+int lins_pose_graph_apply(lins_ctx* ctx, int slot, int stream) {
+  if (!ctx) return LINS_E_ARG;
+  PgMem* m = mem_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (slot < 0 || slot >= m->n_slots || stream < -1) return LINS_E_ARG;
+  const Graph& g = m->g[slot];
+  const int N = g.n_frames();
+  if (N == 0) return LINS_E_ARG;
+  std::vector<lins_key_pose> poses(N);
+  for (int i = 0; i < N; ++i) g.key_pose(i, &poses[i]);
+  // everything that can refuse is asked first, so that a refused call changes nothing
+  const int in_archive = lins_archive_count(ctx, slot);
+  if (in_archive != LINS_E_STATE && in_archive < N) return in_archive < 0 ? in_archive : LINS_E_ARG;
+  int window = 0;
+  const int on_ring = local_map_slots(ctx) ? local_map_ring(ctx, slot, &window) : 0;  // (0 rings: no local map)
+  if (local_map_slots(ctx) && on_ring < std::min(window, N)) return LINS_E_ARG;  // no such slot, or a ring behind the graph
+  lins_map_pose_state ps;
+  if (stream >= 0) {
+    if (int rc = lins_streams_map_get_pose(ctx, stream, &ps)) return rc;
+  }
+  if (in_archive != LINS_E_STATE) {  // correctPoses over the whole history
+    if (int rc = lins_archive_set_poses(ctx, slot, 0, N, poses.data())) return rc;
+  }
+  for (int age = 0; age < std::min(on_ring, N); ++age) {  // ... and over the ring: its frames are the newest, by age
+    if (int rc = lins_local_map_set_pose(ctx, slot, age, &poses[N - 1 - age])) return rc;
+  }
+  if (stream >= 0) {  // LM:1737-1749
+    const float* p = &g.held[6 * (size_t)(N - 1)];
+    for (int i = 0; i < 6; ++i) ps.aft[i] = ps.last[i] = ps.tobe[i] = p[i];
+    if (int rc = lins_streams_map_set_pose(ctx, stream, &ps)) return rc;
+  }
+  return LINS_OK;
+}
+
+int lins_last_pose_graph_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* iterations) {
+  if (!ctx) return LINS_E_ARG;
+  PgMem* m = mem_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (kernel_ms) *kernel_ms = m->ms;
+  if (iterations) *iterations = m->iterations;
+  return LINS_OK;
+}
+
+int lins_debug_pose_graph_poses_f64(lins_ctx* ctx, int slot, int first_id, int n, double* out) {
+  if (!ctx) return LINS_E_ARG;
+  PgMem* m = mem_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (slot < 0 || slot >= m->n_slots || first_id < 0 || n < 0 || (long long)first_id + n > m->g[slot].n_frames() || (n && !out)) return LINS_E_ARG;
+  std::memcpy(out, m->g[slot].T.data() + 12 * (size_t)first_id, 12 * (size_t)n * sizeof(double));
+  return LINS_OK;
+}
+
+int lins_debug_pose_graph_loop_z(lins_ctx* ctx, int slot, int loop, double z[12]) {
+  if (!ctx || !z) return LINS_E_ARG;
+  PgMem* m = mem_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (slot < 0 || slot >= m->n_slots || loop < 0 || loop >= (int)m->g[slot].loops.size()) return LINS_E_ARG;
+  std::memcpy(z, m->g[slot].loops[loop].Z, 12 * sizeof(double));
+  return LINS_OK;
+}
+
+}  // extern "C"

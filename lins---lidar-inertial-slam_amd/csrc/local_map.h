@@ -82,10 +82,12 @@ struct LocalMapView {
 };
 int local_map_view(lins_ctx* ctx, LocalMapView* v);
 int local_map_slots(lins_ctx* ctx);  // n_slots of lins_local_map_init (0 before it)
+int local_map_ring(lins_ctx* ctx, int slot, int* window);  // frames on the ring of slot (-1: no such slot) and the rings' window
 void** map_local_slot(lins_ctx* ctx, void (*free_fn)(void*));  // lins_map_capi.hip: held by the scan-to-map state
 void** map_archive_slot(lins_ctx* ctx, void (*free_fn)(void*));  // ... and the key-frame archive's (lins_archive_capi.hip)
 void** map_loop_slot(lins_ctx* ctx, void (*free_fn)(void*));     // ... and the loop-closure ICP's (lins_loop_icp_capi.hip)
 void** map_pose_slot(lins_ctx* ctx, void (*free_fn)(void*));     // ... and the streams' map poses (lins_streams_map_capi.hip)
+void** map_graph_slot(lins_ctx* ctx, void (*free_fn)(void*));    // ... and the pose graphs (lins_pose_graph_capi.hip)
 
 // lins_map_capi.hip: scan-to-map over the last local-map build (n entries, as LINS_MAP_LOCAL) between the two pose
 // kernels of map_pose_kernels.hip — entry k works on d_poses[d_entries[k].stream]; h_out receives the n result records

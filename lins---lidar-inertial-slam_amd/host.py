@@ -557,3 +557,137 @@ def transform_to_end(t, q, pts, scan_period=0.1):
     lib().lins_transform_to_end(t, q, scan_period, pts.ctypes.data_as(C.POINTER(Point)), len(pts),
                                 out.ctypes.data_as(C.POINTER(Point)))
     return out
+
+
+# ---- the pose graph on the CPU (include/lins_host.h lins_host_pose_graph_*) ----------------------
+def pose_graph_params(**kw):
+    """lins_pose_graph_default_params with fields overridden by keyword (max_iterations=3, ...)"""
+    from ._ctypes_defs import pose_graph_params as f
+
+    return f(lib(), **kw)
+
+
+def pose_from6(p):
+    """six floats (pitch, yaw, roll, y, z, x) -> pose (12 doubles: R row-major, t)"""
+    from ._ctypes_defs import six_floats
+
+    L, T = lib(), np.zeros(12)
+    L.lins_host_pose_from6.argtypes, L.lins_host_pose_from6.restype = [C.POINTER(C.c_float), C.c_void_p], None
+    L.lins_host_pose_from6(six_floats(p), T.ctypes.data)
+    return T
+
+
+def pose_to6(T):
+    """pose (12 doubles) -> six floats, rounded once"""
+    L, Tm, out = lib(), np.ascontiguousarray(T, dtype=np.float64).reshape(12), np.zeros(6, np.float32)
+    L.lins_host_pose_to6.argtypes, L.lins_host_pose_to6.restype = [C.c_void_p, C.c_void_p], None
+    L.lins_host_pose_to6(Tm.ctypes.data, out.ctypes.data)
+    return out
+
+
+class PoseGraph:
+    """lins_host_pose_graph: the CPU restatement of one slot's pose graph.  Calls return the C return code where it can be
+    an error the tests look at (push, add_loop); the others raise."""
+
+    def __init__(self, max_frames, max_loops):
+        L = lib()
+        L.lins_host_pose_graph_create.argtypes, L.lins_host_pose_graph_create.restype = [C.c_int, C.c_int], C.c_void_p
+        self._h = L.lins_host_pose_graph_create(int(max_frames), int(max_loops))
+        if not self._h:
+            raise RuntimeError("lins_host_pose_graph_create")
+
+    def close(self):
+        if self._h:
+            L = lib()
+            L.lins_host_pose_graph_destroy.argtypes, L.lins_host_pose_graph_destroy.restype = [C.c_void_p], None
+            L.lins_host_pose_graph_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def push(self, last6, aft6):
+        """returns the frame id (>= 0) or the error code"""
+        from ._ctypes_defs import six_floats
+
+        L = lib()
+        L.lins_host_pose_graph_push.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.lins_host_pose_graph_push.restype = C.c_int
+        return L.lins_host_pose_graph_push(self._h, six_floats(last6) if last6 is not None else None, six_floats(aft6))
+
+    def add_loop(self, latest_id, closest_id, pose_from, fitness):
+        """pose_from: (x, y, z, roll, pitch, yaw) as loop_pose_from returns it; returns the C return code"""
+        from ._ctypes_defs import KeyPoseC, key_pose
+
+        L = lib()
+        L.lins_host_pose_graph_add_loop.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(KeyPoseC), C.c_double]
+        L.lins_host_pose_graph_add_loop.restype = C.c_int
+        p = key_pose(pose_from)
+        return L.lins_host_pose_graph_add_loop(self._h, int(latest_id), int(closest_id), C.byref(p), float(fitness))
+
+    def count(self):
+        """(frames, loops)"""
+        L, nl = lib(), C.c_int32(0)
+        L.lins_host_pose_graph_count.argtypes, L.lins_host_pose_graph_count.restype = [C.c_void_p, C.POINTER(C.c_int32)], C.c_int
+        n = L.lins_host_pose_graph_count(self._h, C.byref(nl))
+        return n, int(nl.value)
+
+    def solve(self, params=None):
+        from ._ctypes_defs import PoseGraphParamsC, PoseGraphResultC
+
+        L, out = lib(), PoseGraphResultC()
+        prm = params if params is not None else pose_graph_params()
+        L.lins_host_pose_graph_solve.argtypes = [C.c_void_p, C.POINTER(PoseGraphParamsC), C.POINTER(PoseGraphResultC)]
+        L.lins_host_pose_graph_solve.restype = C.c_int
+        rc = L.lins_host_pose_graph_solve(self._h, C.byref(prm), C.byref(out))
+        if rc:
+            raise RuntimeError(f"lins_host_pose_graph_solve: {rc}")
+        return out.as_dict()
+
+    def poses(self, first_id=0, n=None):
+        """(n, 6) f32: x, y, z, roll, pitch, yaw (PointTypePose)"""
+        from ._ctypes_defs import KeyPoseC
+
+        L = lib()
+        n = self.count()[0] - first_id if n is None else n
+        out = np.zeros((max(n, 1), 6), np.float32)
+        L.lins_host_pose_graph_poses.argtypes, L.lins_host_pose_graph_poses.restype = [C.c_void_p, C.c_int, C.c_int, C.c_void_p], C.c_int
+        rc = L.lins_host_pose_graph_poses(self._h, int(first_id), int(n), out.ctypes.data)
+        if rc:
+            raise RuntimeError(f"lins_host_pose_graph_poses: {rc}")
+        return out[:n]
+
+    def poses_f64(self, first_id=0, n=None):
+        """(n, 12) f64: R row-major, t"""
+        L = lib()
+        n = self.count()[0] - first_id if n is None else n
+        out = np.zeros((max(n, 1), 12))
+        L.lins_host_pose_graph_poses_f64.argtypes, L.lins_host_pose_graph_poses_f64.restype = [C.c_void_p, C.c_int, C.c_int, C.c_void_p], C.c_int
+        rc = L.lins_host_pose_graph_poses_f64(self._h, int(first_id), int(n), out.ctypes.data)
+        if rc:
+            raise RuntimeError(f"lins_host_pose_graph_poses_f64: {rc}")
+        return out[:n]
+
+    def loop_z(self, loop):
+        L, z = lib(), np.zeros(12)
+        L.lins_host_pose_graph_loop_z.argtypes, L.lins_host_pose_graph_loop_z.restype = [C.c_void_p, C.c_int, C.c_void_p], C.c_int
+        rc = L.lins_host_pose_graph_loop_z(self._h, int(loop), z.ctypes.data)
+        if rc:
+            raise RuntimeError(f"lins_host_pose_graph_loop_z: {rc}")
+        return z
+
+    def linearize(self, poses=None):
+        """the linearisation at absolute poses (N, 12) (None: the estimate) -> dict r_odo (N-1, 6), D (N-1, 6, 6), g (N-1, 6),
+        r_loop (L, 6), M (L, 6, 6)"""
+        L = lib()
+        n, nl = self.count()
+        T = None if poses is None else np.ascontiguousarray(poses, dtype=np.float64).reshape(n, 12)
+        m = max(n - 1, 1)
+        r, D, g, rl, M = np.zeros((m, 6)), np.zeros((m, 6, 6)), np.zeros((m, 6)), np.zeros((max(nl, 1), 6)), np.zeros((max(nl, 1), 6, 6))
+        L.lins_host_pose_graph_linearize.argtypes = [C.c_void_p] * 7
+        L.lins_host_pose_graph_linearize.restype = C.c_int
+        rc = L.lins_host_pose_graph_linearize(self._h, T.ctypes.data if T is not None else None, r.ctypes.data, D.ctypes.data, g.ctypes.data,
+                                              rl.ctypes.data, M.ctypes.data)
+        if rc:
+            raise RuntimeError(f"lins_host_pose_graph_linearize: {rc}")
+        return dict(r_odo=r[:n - 1], D=D[:n - 1], g=g[:n - 1], r_loop=rl[:nl], M=M[:nl])

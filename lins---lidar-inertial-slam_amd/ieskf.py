@@ -39,6 +39,9 @@ EXPORTS = [
     "lins_last_local_map_stage_ms",
     "lins_map_associate_batch", "lins_streams_map_init", "lins_streams_map_get_pose", "lins_streams_map_set_pose",
     "lins_streams_map_step", "lins_last_streams_map_ms",
+    "lins_pose_graph_default_params", "lins_pose_graph_init", "lins_pose_graph_push", "lins_pose_graph_add_loop",
+    "lins_pose_graph_solve", "lins_pose_graph_poses", "lins_pose_graph_apply", "lins_pose_graph_count",
+    "lins_last_pose_graph_stats",
 ]
 
 
@@ -102,7 +105,7 @@ def lib():
         L.lins_last_reproject_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
         for name in EXPORTS:
             if name not in ("lins_destroy", "lins_strerror", "lins_last_hip_error", "lins_last_search", "lins_loop_icp_default_params",
-                            "lins_boot_default_params"):
+                            "lins_boot_default_params", "lins_pose_graph_default_params"):
                 if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                     continue  # (an older build under A/B timing)
                 getattr(L, name).restype = C.c_int
@@ -476,6 +479,88 @@ class IeskfContext:
         L.lins_last_loop_icp_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
         self._check(L.lins_last_loop_icp_stats(self._h, C.byref(ms), C.byref(q)))
         return ms.value, q.value
+
+    # -- the pose graph on the device (include/lins_map.h lins_pose_graph_*) -------------------------
+    def pose_graph_init(self, n_slots, max_frames_per_slot, max_loops_per_slot):
+        L = lib()
+        L.lins_pose_graph_init.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        self._check(L.lins_pose_graph_init(self._h, int(n_slots), int(max_frames_per_slot), int(max_loops_per_slot)))
+
+    def pose_graph_push(self, slot, last6, aft6):
+        """saveKeyFramesAndFactor's factor: six floats (pitch, yaw, roll, y, z, x) each; returns the frame id"""
+        from ._ctypes_defs import six_floats
+
+        L = lib()
+        L.lins_pose_graph_push.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        return self._rc(L.lins_pose_graph_push(self._h, int(slot), six_floats(last6) if last6 is not None else None, six_floats(aft6)))
+
+    def pose_graph_add_loop(self, slot, latest_id, closest_id, pose_from, fitness):
+        """performLoopClosure's factor: pose_from (x, y, z, roll, pitch, yaw) as host.loop_pose_from returns it"""
+        from ._ctypes_defs import KeyPoseC, key_pose
+
+        L, p = lib(), key_pose(pose_from)
+        L.lins_pose_graph_add_loop.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(KeyPoseC), C.c_double]
+        self._check(L.lins_pose_graph_add_loop(self._h, int(slot), int(latest_id), int(closest_id), C.byref(p), float(fitness)))
+
+    def pose_graph_solve(self, slots, params=None):
+        """the batched Levenberg-Marquardt solve of the graphs of `slots`; params: a PoseGraphParamsC (default:
+        lins_pose_graph_default_params).  Returns the per-slot result dicts."""
+        from ._ctypes_defs import PoseGraphParamsC, PoseGraphResultC, pose_graph_params
+
+        L = lib()
+        prm = params if params is not None else pose_graph_params(L)
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        n = len(sl)
+        out = (PoseGraphResultC * max(n, 1))()
+        L.lins_pose_graph_solve.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(PoseGraphParamsC), C.POINTER(PoseGraphResultC)]
+        self._check(L.lins_pose_graph_solve(self._h, n, sl.ctypes.data, C.byref(prm), out))
+        return [out[k].as_dict() for k in range(n)]
+
+    def pose_graph_count(self, slot):
+        """(frames, loops) of `slot`"""
+        L, nl = lib(), C.c_int32(0)
+        L.lins_pose_graph_count.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
+        n = self._rc(L.lins_pose_graph_count(self._h, int(slot), C.byref(nl)))
+        return n, int(nl.value)
+
+    def pose_graph_poses(self, slot, first_id=0, n=None):
+        """(n, 6) f32: x, y, z, roll, pitch, yaw (PointTypePose) of frames first_id .. first_id + n - 1"""
+        L = lib()
+        n = self.pose_graph_count(slot)[0] - first_id if n is None else n
+        out = np.zeros((max(n, 1), 6), np.float32)
+        L.lins_pose_graph_poses.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        self._check(L.lins_pose_graph_poses(self._h, int(slot), int(first_id), int(n), out.ctypes.data))
+        return out[:n]
+
+    def pose_graph_apply(self, slot, stream=-1):
+        """correctPoses + LM:1737-1749: the solved poses go to the archive, the local map's ring and (stream >= 0) the
+        stream's map pose"""
+        L = lib()
+        L.lins_pose_graph_apply.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        self._check(L.lins_pose_graph_apply(self._h, int(slot), int(stream)))
+
+    def pose_graph_stats(self):
+        """(HIP-event ms of the last pose_graph_solve, trials it ran over all problems)"""
+        L = lib()
+        ms, it = C.c_float(0), C.c_uint64(0)
+        L.lins_last_pose_graph_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+        self._check(L.lins_last_pose_graph_stats(self._h, C.byref(ms), C.byref(it)))
+        return ms.value, it.value
+
+    def debug_pose_graph_poses_f64(self, slot, first_id=0, n=None):
+        """test aid: the estimate in f64, (n, 12): R row-major, t"""
+        L = lib()
+        n = self.pose_graph_count(slot)[0] - first_id if n is None else n
+        out = np.zeros((max(n, 1), 12))
+        L.lins_debug_pose_graph_poses_f64.argtypes, L.lins_debug_pose_graph_poses_f64.restype = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p], C.c_int
+        self._check(L.lins_debug_pose_graph_poses_f64(self._h, int(slot), int(first_id), int(n), out.ctypes.data))
+        return out[:n]
+
+    def debug_pose_graph_loop_z(self, slot, loop):
+        L, z = lib(), np.zeros(12)
+        L.lins_debug_pose_graph_loop_z.argtypes, L.lins_debug_pose_graph_loop_z.restype = [C.c_void_p, C.c_int, C.c_int, C.c_void_p], C.c_int
+        self._check(L.lins_debug_pose_graph_loop_z(self._h, int(slot), int(loop), z.ctypes.data))
+        return z
 
     def _debug_loop_icp(self, name, value):
         f = getattr(lib(), name)
