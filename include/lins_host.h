@@ -313,6 +313,20 @@ int lins_host_loop_icp_step(const double sums[17], const lins_loop_icp_params* p
  * getTransformation(x, y, z, roll, pitch, yaw) = Rz(yaw) Ry(pitch) Rx(roll) with translation (x, y, z).  The factor
  * graph stays with the caller. */
 int lins_host_loop_pose_from(const double T[16], const lins_key_pose* wrong, lins_key_pose* pose_from);
+/* What the loop thread decides between its device stages (csrc/host/loop_step.h: the text lins_loop_step compiles too;
+ * DESIGN.md §5.3 "Loop thread's step").
+ * window (LM:1087-1098): the ids closest - search_num .. closest + search_num clipped to [0, latest], ascending — it may
+ * contain `latest`; returns the count (0 for latest < 0, a closest outside [0, latest] or search_num < 0), LINS_E_CAPACITY
+ * beyond cap.
+ * candidate: LINS_LOOP_NONE for closest < 0 or closest == latest (a frame is no loop with itself), LINS_LOOP_REPEAT when
+ * (latest, closest) is the pair of the slot's most recent loop factor (-1, -1: none yet), else -1: the pair is aligned.
+ * accept (LM:1140-1141): converged && !(fitness > (double)max_fitness), 1 or 0.  A NaN passes, as in the reference's
+ * expression; the variance stops it.
+ * variance (LM:1171-1175): *variance = (double)(float)fitness; returns 1 when it is finite and > 0, else 0 — a rejection. */
+int lins_host_loop_window(int latest, int closest, int search_num, int32_t* ids, int cap);
+int lins_host_loop_candidate(int latest, int closest, int last_latest, int last_closest);
+int lins_host_loop_accept(int converged, double fitness, float max_fitness);
+int lins_host_loop_variance(double fitness, double* variance);
 
 /* ---- the mapping node's own pose arithmetic (csrc/map_pose_math.h; the CPU restatement of lins_streams_map_step's two
  * kernels, lins_streams_map.h).  Pose vectors are (rx, ry, rz, tx, ty, tz) as transformTobeMapped; all f32.

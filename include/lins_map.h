@@ -386,6 +386,11 @@ int lins_pose_graph_poses(lins_ctx* ctx, int slot, int first_id, int n, lins_key
  * LINS_E_ARG when it holds fewer than min(window, N) — and for stream >= 0 aft = last = tobe = the newest pose through
  * lins_streams_map_set_pose. */
 int lins_pose_graph_apply(lins_ctx* ctx, int slot, int stream);
+/* What n calls lins_pose_graph_apply(slots[k], streams[k]) do, with every refusal asked first — a refused call changes
+ * nothing for any slot — and the streams' records written by ONE kernel (map_pose_correct_kernel: aft = last = tobe = the
+ * newest pose; bef, prev and n_frames stay) behind one upload, with one synchronisation.  streams[k] = -1: no stream.  A
+ * slot or a stream (>= 0) named twice: LINS_E_ARG. */
+int lins_pose_graph_apply_batch(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* streams);
 /* frames / loops of slot (>= 0) */
 int lins_pose_graph_count(lins_ctx* ctx, int slot, int32_t* n_loops);
 /* HIP-event time (ms) of the device sequence of the last solve and the trials it ran over all problems */
@@ -393,6 +398,80 @@ int lins_last_pose_graph_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* iterat
 /* test aids: the estimate in f64 (n x 12: R row-major, t) and loop l's measurement */
 int lins_debug_pose_graph_poses_f64(lins_ctx* ctx, int slot, int first_id, int n, double* out);
 int lins_debug_pose_graph_loop_z(lins_ctx* ctx, int slot, int loop, double z[12]);
+
+/* ---- the loop thread's step: performLoopClosure + correctPoses for n slots in one call (LM:1033-1186, 1767-1795) --------
+ * One call does, for every entry, what the chain lins_archive_find_loop -> lins_archive_assemble -> lins_loop_icp_batch ->
+ * lins_pose_graph_poses + lins_host_loop_pose_from -> lins_pose_graph_add_loop -> lins_pose_graph_solve ->
+ * lins_pose_graph_apply does for its slot, with the assembly, the alignment, the solve and the write-back each ONE batched
+ * call over the entries that reach it.  An entry's result bits, and the state it leaves in the graph, the archive, the
+ * ring and the map pose, are those of that chain: they do not depend on the batch, on its order, or on what the context
+ * ran before.  What is decided between the stages is csrc/host/loop_step.h (lins_host_loop_* in lins_host.h); its two
+ * departures from the reference — a frame is no loop with itself; a pair equal to the slot's most recent loop factor is a
+ * repeat — are stated in DESIGN.md §5.3 "Loop thread's step". */
+typedef struct lins_loop_step_params { /* lins_loop_step_default_params: the reference's values */
+  float search_radius;  /* 5  (historyKeyframeSearchRadius, parameters.h:98) */
+  float max_fitness;    /* 0.3 (historyKeyframeFitnessScore) */
+  float history_leaf;   /* 0.4: VoxelGrid leaf of the history window; >= 0 */
+  int32_t search_num;   /* 25 (historyKeyframeSearchNum); >= 0 */
+  double min_gap_s;     /* 30 */
+  lins_loop_icp_params icp;
+  lins_pose_graph_params graph;
+} lins_loop_step_params;
+void lins_loop_step_default_params(lins_loop_step_params* p);
+
+#define LINS_LOOP_CENTRE_STREAM 1 /* lins_loop_step_entry.flags: centre = currentRobotPosPoint of `stream` */
+
+typedef struct lins_loop_step_entry {
+  int32_t slot;
+  int32_t stream;   /* -1, or the stream whose map pose the correction is written to */
+  int32_t flags;    /* 0 or LINS_LOOP_CENTRE_STREAM: `centre` is not read, the search is centred on transform[3..5] of the
+                       stream's last lins_streams_map_step entry with status LINS_OK (LM:1655-1658) */
+  int32_t reserved;
+  float centre[3];  /* currentRobotPosPoint */
+  float pad;
+  double now;       /* timeLaserOdometry */
+} lins_loop_step_entry;
+
+#define LINS_LOOP_NONE 0     /* no frames, no candidate, or the candidate is the latest frame itself */
+#define LINS_LOOP_REPEAT 1   /* the candidate pair is the slot's most recent loop factor: nothing aligned or added */
+#define LINS_LOOP_REJECTED 2 /* aligned; not converged, fitness above max_fitness, or an unusable variance */
+#define LINS_LOOP_CLOSED 3   /* factor added, graph solved, history corrected */
+
+typedef struct lins_loop_step_result { /* fields of stages that did not run are zero, the ids -1 */
+  int32_t outcome;            /* LINS_LOOP_* */
+  int32_t status;             /* LINS_OK; LINS_E_CAPACITY: the slot's graph holds max_loops loops (nothing was run), or the
+                                 status of the entry's assembly / alignment / factor, behind which nothing ran for it */
+  int32_t latest_id;          /* frames of the slot - 1 (-1: none) */
+  int32_t closest_id;         /* lins_archive_find_loop's answer (-1: none) */
+  lins_submap_info latest;    /* latestSurfKeyFrameCloud: corner | surf of `latest_id`, leaf 0, DROP_NEGATIVE */
+  lins_submap_info history;   /* nearHistorySurfKeyFrameCloudDS: corner | surf of the window, history_leaf */
+  lins_loop_icp_result icp;
+  lins_key_pose pose_from;    /* lins_host_loop_pose_from of icp.transform and the graph's pose of `latest_id` */
+  lins_pose_graph_result graph;
+} lins_loop_step_result;
+
+/* The stages, in order: detect (host: lins_archive_find_loop's selection, the candidate rule, and the loop capacity of
+ * every slot with a candidate — a full slot reports LINS_E_CAPACITY with outcome NONE, the others proceed); assemble (one
+ * lins_archive_assemble of two specs per candidate); align (one lins_loop_icp_batch over the entries whose assemblies have
+ * no status); add the factor for every accepted entry (the graph's held pose of `latest`, pose_from, the variance rule);
+ * solve (one lins_pose_graph_solve over the slots that gained a loop); correct the history (one
+ * lins_pose_graph_apply_batch of those slots and their streams).
+ * For the whole call, before anything is queued, and the call changes nothing: LINS_E_STATE before lins_archive_init or
+ * lins_pose_graph_init, or for LINS_LOOP_CENTRE_STREAM on a stream that has not completed a step; LINS_E_ARG for a bad
+ * slot, stream or flag, a slot or stream named twice, a named slot whose archive and graph hold different frame counts,
+ * parameters outside the ranges of the calls they are handed to, or a write-back lins_pose_graph_apply would refuse;
+ * LINS_E_INPUT for a non-finite centre or now.  The archive's last assembly and the ICP's buffers are this call's
+ * afterwards, as after the explicit calls. */
+int lins_loop_step(lins_ctx* ctx, int n, const lins_loop_step_entry* entries, const lins_loop_step_params* prm, lins_loop_step_result* out);
+/* closed_cloud (LM:1143-1154) of entry `entry` of the last lins_loop_step, which must have been aligned (else LINS_E_ARG)
+ * with no lins_archive_assemble since (LINS_E_STATE): the ICP contract's step 1 at the final T — M = T rounded to f32,
+ * x' = ((m00 x + m01 y) + m02 z) + m03, uncontracted — over the source as assembled, intensity kept.  Returns the count;
+ * LINS_E_CAPACITY beyond cap. */
+int lins_loop_closed_cloud(lins_ctx* ctx, int entry, lins_point* out, int cap);
+/* HIP-event times (ms) of the three device sequences of the last step (0 for one that did not run) and how many entries
+ * had a candidate, were aligned, and closed a loop */
+int lins_last_loop_step_stats(lins_ctx* ctx, float* assemble_ms, float* icp_ms, float* solve_ms, int32_t* candidates, int32_t* aligned,
+                              int32_t* closed);
 
 #ifdef __cplusplus
 }

@@ -97,6 +97,18 @@ int lins_streams_map_set_pose(lins_ctx* ctx, int stream, const lins_map_pose_sta
  * lins_streams_map_init.  The local map's build and the resident maps of lins_scan2map_batch are this call's afterwards,
  * as after the explicit calls.                                                                                       */
 int lins_streams_map_step(lins_ctx* ctx, int n, const int32_t* streams, const lins_map_odom* odom, lins_map_step_result* out);
+/* on != 0: every later step also makes saveKeyFramesAndFactor's factor (LM:1673-1705) for each key frame it stores —
+ * lins_pose_graph_push(slot = stream, transformLast as the finish kernel found it, key_pose), the prior for a stream's
+ * first frame — so that lins_loop_step (lins_map.h) finds graph and archive in step; the id the graph returns is the
+ * step's archive_id (LINS_E_STATE otherwise; a graph without room for a key frame of the batch: LINS_E_CAPACITY before
+ * anything is stored).  transformLast is read from a host mirror, kept in step with the finish kernel's rule,
+ * lins_streams_map_set_pose and lins_pose_graph_apply / _apply_batch; switching on downloads it once.  After
+ * lins_streams_map_init with an archive (lins_archive_init before it) and lins_pose_graph_init, the graph with at least
+ * n_streams slots and every stream's graph and archive holding the same frame count: LINS_E_STATE otherwise.  Off — the
+ * default, and again after lins_streams_map_init — the step does not touch a graph that happens to be initialised.
+ * Either way the step remembers currentRobotPosPoint per stream: transform[3..5] of its last entry with status LINS_OK
+ * (LM:1655-1658), which LINS_LOOP_CENTRE_STREAM reads.                                                                */
+int lins_streams_map_loop(lins_ctx* ctx, int on);
 /* HIP-event times (ms) of the associate and finish kernels of the last step (0 when the step queued none)            */
 int lins_last_streams_map_ms(lins_ctx* ctx, float* associate_ms, float* finish_ms);
 

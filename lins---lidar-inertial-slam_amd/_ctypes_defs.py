@@ -448,6 +448,60 @@ def pose_graph_params(lib, **kw):
     return p
 
 
+# ---- the loop thread's step (include/lins_map.h lins_loop_step) ------------------------------------------------
+LOOP_NONE, LOOP_REPEAT, LOOP_REJECTED, LOOP_CLOSED = range(4)
+LOOP_CENTRE_STREAM = 1
+
+
+class LoopStepParamsC(C.Structure):
+    _fields_ = [("search_radius", C.c_float), ("max_fitness", C.c_float), ("history_leaf", C.c_float), ("search_num", C.c_int32),
+                ("min_gap_s", C.c_double), ("icp", LoopIcpParamsC), ("graph", PoseGraphParamsC)]
+
+
+class LoopStepEntryC(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("stream", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32), ("centre", C.c_float * 3),
+                ("pad", C.c_float), ("now", C.c_double)]
+
+
+class LoopStepResultC(C.Structure):
+    _fields_ = [("outcome", C.c_int32), ("status", C.c_int32), ("latest_id", C.c_int32), ("closest_id", C.c_int32), ("latest", SubmapInfoC),
+                ("history", SubmapInfoC), ("icp", LoopIcpResultC), ("pose_from", KeyPoseC), ("graph", PoseGraphResultC)]
+
+    def as_dict(self):
+        pf = self.pose_from
+        return dict(outcome=int(self.outcome), status=int(self.status), latest_id=int(self.latest_id), closest_id=int(self.closest_id),
+                    latest=self.latest.as_dict(), history=self.history.as_dict(), icp=self.icp.as_dict(),
+                    pose_from=np.array([pf.x, pf.y, pf.z, pf.roll, pf.pitch, pf.yaw], np.float32), graph=self.graph.as_dict())
+
+
+def loop_step_params(lib, **kw):
+    """lins_loop_step_default_params with fields overridden by keyword; icp / graph: dicts of fields of the nested structs"""
+    p = LoopStepParamsC()
+    lib.lins_loop_step_default_params.argtypes = [C.POINTER(LoopStepParamsC)]
+    lib.lins_loop_step_default_params.restype = None
+    lib.lins_loop_step_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"lins_loop_step_params has no field {k}")
+        if k in ("icp", "graph"):
+            for kk, vv in v.items():
+                if not hasattr(getattr(p, k), kk):
+                    raise TypeError(f"{k} has no field {kk}")
+                setattr(getattr(p, k), kk, vv)
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def loop_step_entry(slot, centre=None, now=0.0, stream=-1):
+    """lins_loop_step_entry; centre None: LINS_LOOP_CENTRE_STREAM (currentRobotPosPoint of `stream`)"""
+    e = LoopStepEntryC()
+    e.slot, e.stream, e.flags, e.now = int(slot), int(stream), LOOP_CENTRE_STREAM if centre is None else 0, float(now)
+    if centre is not None:
+        e.centre[:] = [float(v) for v in np.asarray(centre, np.float32)[:3]]
+    return e
+
+
 def six_floats(p):
     """six floats (pitch, yaw, roll, y, z, x) as a C array"""
     return (C.c_float * 6)(*[float(v) for v in np.asarray(p, dtype=np.float32)])

@@ -10,6 +10,7 @@
 
 #include "../../../include/lins_host.h"
 #include "../loop_icp_math.h"
+#include "loop_step.h"
 #include "voxel_map.h"
 
 using namespace lins_licp;
@@ -95,20 +96,6 @@ int run(const lins_point* S, int ns, const lins_point* G, int ng, const lins_loo
   return n_rounds;
 }
 
-// getTransformation(x, y, z, roll, pitch, yaw) = Rz(yaw) Ry(pitch) Rx(roll) with translation (x, y, z), f32
-void get_transformation(float x, float y, float z, float roll, float pitch, float yaw, float* t) {
-  const float cr = std::cos(roll), sr = std::sin(roll), cp = std::cos(pitch), sp = std::sin(pitch), cy = std::cos(yaw), sy = std::sin(yaw);
-  t[0] = cy * cp, t[1] = cy * sp * sr - sy * cr, t[2] = cy * sp * cr + sy * sr, t[3] = x;
-  t[4] = sy * cp, t[5] = sy * sp * sr + cy * cr, t[6] = sy * sp * cr - cy * sr, t[7] = y;
-  t[8] = -sp, t[9] = cp * sr, t[10] = cp * cr, t[11] = z;
-  t[12] = t[13] = t[14] = 0.f, t[15] = 1.f;
-}
-// getTranslationAndEulerAngles
-void euler_of(const float* t, float& x, float& y, float& z, float& roll, float& pitch, float& yaw) {
-  x = t[3], y = t[7], z = t[11];
-  roll = std::atan2(t[9], t[10]), pitch = std::asin(-t[8]), yaw = std::atan2(t[4], t[0]);
-}
-
 }  // namespace
 
 extern "C" {
@@ -156,17 +143,25 @@ int lins_host_loop_icp_step(const double sums[17], const lins_loop_icp_params* p
   return LINS_OK;
 }
 
+int lins_host_loop_window(int latest, int closest, int search_num, int32_t* ids, int cap) {
+  if (cap < 0) return LINS_E_ARG;
+  const int n = lins_loop::window_size(latest, closest, search_num);
+  if (n > cap) return LINS_E_CAPACITY;
+  if (n && !ids) return LINS_E_ARG;
+  return lins_loop::window(latest, closest, search_num, ids);
+}
+
+int lins_host_loop_candidate(int latest, int closest, int last_latest, int last_closest) {
+  return lins_loop::candidate(latest, closest, last_latest, last_closest);
+}
+
+int lins_host_loop_accept(int converged, double fitness, float max_fitness) { return lins_loop::accept(converged, fitness, max_fitness) ? 1 : 0; }
+
+int lins_host_loop_variance(double fitness, double* variance) { return lins_loop::variance(fitness, variance) ? 1 : 0; }
+
 int lins_host_loop_pose_from(const double T[16], const lins_key_pose* wrong, lins_key_pose* pose_from) {
   if (!T || !wrong || !pose_from) return LINS_E_ARG;
-  float c[16], x, y, z, roll, pitch, yaw;
-  for (int i = 0; i < 16; ++i) c[i] = (float)T[i];  // icp.getFinalTransformation() is a Matrix4f
-  euler_of(c, x, y, z, roll, pitch, yaw);
-  float lidar[16], tw[16], tc[16];
-  get_transformation(z, x, y, yaw, roll, pitch, lidar);
-  get_transformation(wrong->z, wrong->x, wrong->y, wrong->yaw, wrong->roll, wrong->pitch, tw);  // pclPointToAffine3fCameraToLidar
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j) tc[4 * i + j] = ((lidar[4 * i] * tw[j] + lidar[4 * i + 1] * tw[4 + j]) + lidar[4 * i + 2] * tw[8 + j]) + lidar[4 * i + 3] * tw[12 + j];
-  euler_of(tc, pose_from->x, pose_from->y, pose_from->z, pose_from->roll, pose_from->pitch, pose_from->yaw);
+  lins_loop::pose_from(T, *wrong, pose_from);
   return LINS_OK;
 }
 

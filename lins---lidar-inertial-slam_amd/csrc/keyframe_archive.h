@@ -37,6 +37,7 @@ struct ArchiveView {
   const long long* off;
   const lins_submap_info* info;
   const char* filtered;
+  unsigned long long serial;  // counts the assemblies of the context: whose clouds these are
 };
 int archive_view(lins_ctx* ctx, ArchiveView* v);  // lins_archive_capi.hip
 

@@ -44,6 +44,7 @@ struct Archive {
   size_t cap_stage = 0, cap_sort = 0, cap_out = 0, cap_hist = 0, cap_tilecnt = 0, cap_csum = 0, cap_tab = 0, cap_htab = 0, cap_hstates = 0;
   // the last assembly
   bool built = false;
+  unsigned long long serial = 0;  // assemblies started so far
   std::vector<long long> off;
   std::vector<lins_submap_info> info;
   std::vector<char> filtered;  // per entry: a VoxelGrid output (its info carries the 1 m box)
@@ -107,6 +108,7 @@ int archive_view(lins_ctx* ctx, ArchiveView* v) {
   Archive* m = archive_of(ctx);
   if (!m->built) return LINS_E_STATE;
   v->d_out = m->d_out, v->n = (int)m->info.size(), v->off = m->off.data(), v->info = m->info.data(), v->filtered = m->filtered.data();
+  v->serial = m->serial;
   return LINS_OK;
 }
 }  // namespace lins
@@ -270,7 +272,7 @@ int lins_archive_assemble(lins_ctx* ctx, int n, const lins_submap_spec* specs, l
   for (int k = 0; k < n; ++k)
     if (cap[k] > INT_MAX / 2) return LINS_E_CAPACITY;
   HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
-  m->built = false;
+  m->built = false, m->serial += 1;
   // jobs: VoxelGrid jobs first — those whose scans are split, then the others — then the leaf == 0 jobs, the split ones last
   const int chunk = m->chunk;
   auto tiles_of = [&](int k) { return (cap[k] + kLmTile - 1) / kLmTile; };

@@ -115,6 +115,8 @@ void launch_map_associate(hipStream_t stream, int n, const MapPoseEntry* entries
                           lins_map_step_result* out);
 void launch_map_pose_finish(hipStream_t stream, int n, const MapPoseEntry* entries, const MapDev* probs, MapPoseRec* poses,
                             const lins_map_result* results, lins_map_step_result* out);
+// aft = last = tobe = fixes[k].p of stream fixes[k].stream, k < n; bef, prev and n_frames stay (a stream at most once)
+void launch_map_pose_correct(hipStream_t stream, int n, const MapPoseFix* fixes, MapPoseRec* poses);
 
 // ---- local_map_kernels.hip: the mapping node's local map
 void launch_lm_transform(hipStream_t s, int n_blocks, const LmSeg* segs, const int2* blocks, const float4* frames, float4* stage, LmState* states);

@@ -1,0 +1,229 @@
+// lins_loop_step_capi.hip — C ABI of the loop thread's step (include/lins_map.h lins_loop_step, lins_loop_closed_cloud):
+// performLoopClosure + correctPoses (LM:1033-1186, 1767-1795) for n slots in one call.  Host orchestration only: every
+// device stage is the batched call that already exists — lins_archive_assemble, lins_loop_icp_batch,
+// lins_pose_graph_solve, lins_pose_graph_apply_batch — run ONCE over the entries that reach it, so an entry's bits are
+// those of the explicit chain for its slot; what is decided between the stages is host/loop_step.h, the text
+// liblins_host.so exports.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/lins_map.h"
+#include "../../include/lins_streams_map.h"
+#include "host/keyframe_select.h"
+#include "host/loop_step.h"
+#include "keyframe_archive.h"
+#include "lins_ctx_priv.h"
+#include "local_map.h"
+#include "loop_icp_math.h"
+#include "pose_graph.h"
+
+using namespace lins;
+
+namespace {
+
+struct Aligned {  // one entry of the last step
+  int source = -1;  // its source cloud in the step's assembly (-1: the entry was not aligned)
+  double T[16];
+};
+
+struct LoopStepMem {
+  std::vector<Aligned> last;
+  unsigned long long serial = 0;  // the assembly the sources are entries of
+  float assemble_ms = 0.f, icp_ms = 0.f, solve_ms = 0.f;
+  int candidates = 0, aligned = 0, closed = 0;
+};
+
+void loop_step_free(void* p) { delete (LoopStepMem*)p; }
+
+LoopStepMem* mem_of(lins_ctx* ctx) {
+  void** slot = map_loop_step_slot(ctx, loop_step_free);
+  if (!*slot) *slot = new LoopStepMem();
+  return (LoopStepMem*)*slot;
+}
+
+// the ranges of the calls the parameters are handed to: lins_archive_find_loop, lins_archive_assemble, lins_loop_icp_batch,
+// lins_pose_graph_solve
+bool params_ok(const lins_loop_step_params* p) {
+  return p && std::isfinite(p->search_radius) && p->search_radius >= 0.f && !std::isnan(p->max_fitness) && std::isfinite(p->history_leaf) &&
+         p->history_leaf >= 0.f && p->search_num >= 0 && !std::isnan(p->min_gap_s) && p->icp.max_iterations >= 1 && p->icp.min_correspondences >= 0 &&
+         std::isfinite(p->icp.max_corr_dist) && lins_pg::params_ok(&p->graph);
+}
+
+}  // namespace
+
+extern "C" {
+
+void lins_loop_step_default_params(lins_loop_step_params* p) {
+  if (!p) return;
+  p->search_radius = 5.f, p->max_fitness = 0.3f, p->history_leaf = 0.4f, p->search_num = 25, p->min_gap_s = 30.0;
+  lins_licp::default_params(&p->icp);
+  lins_pg::default_params(&p->graph);
+}
+
+int lins_loop_step(lins_ctx* ctx, int n, const lins_loop_step_entry* entries, const lins_loop_step_params* prm, lins_loop_step_result* out) {
+  if (!ctx || n < 0 || (n && (!entries || !out))) return LINS_E_ARG;
+  if (lins_archive_count(ctx, 0) == LINS_E_STATE || !pose_graph_slots(ctx)) return LINS_E_STATE;
+  if (!params_ok(prm)) return LINS_E_ARG;
+  // ---- the whole call's errors, before anything is queued ----
+  std::vector<int32_t> slots(n), streams(n);
+  std::vector<float> centre(3 * (size_t)n);
+  for (int k = 0; k < n; ++k) {
+    const lins_loop_step_entry& e = entries[k];
+    const int in_archive = lins_archive_count(ctx, e.slot);
+    if (in_archive < 0 || e.slot >= pose_graph_slots(ctx) || in_archive != lins_pose_graph_count(ctx, e.slot, nullptr)) return LINS_E_ARG;
+    if (e.stream < -1 || e.stream >= streams_map_streams(ctx) || (e.flags & ~LINS_LOOP_CENTRE_STREAM)) return LINS_E_ARG;
+    if ((e.flags & LINS_LOOP_CENTRE_STREAM) && e.stream < 0) return LINS_E_ARG;
+    for (int i = 0; i < k; ++i)
+      if (entries[i].slot == e.slot || (e.stream >= 0 && entries[i].stream == e.stream)) return LINS_E_ARG;
+    slots[k] = e.slot, streams[k] = e.stream;
+  }
+  for (int k = 0; k < n; ++k) {
+    const lins_loop_step_entry& e = entries[k];
+    if (e.flags & LINS_LOOP_CENTRE_STREAM) {
+      if (int rc = streams_map_centre(ctx, e.stream, &centre[3 * (size_t)k])) return rc;  // LINS_E_STATE: has not stepped
+    } else {
+      std::memcpy(&centre[3 * (size_t)k], e.centre, 3 * sizeof(float));
+    }
+    if (!lins_select::query_ok(&centre[3 * (size_t)k], prm->search_radius) || !std::isfinite(e.now)) return LINS_E_INPUT;
+  }
+  std::vector<int32_t> with_frames_slots, with_frames_streams;  // the write-back's refusals (a slot without frames closes nothing)
+  for (int k = 0; k < n; ++k)
+    if (lins_archive_count(ctx, slots[k]) > 0) with_frames_slots.push_back(slots[k]), with_frames_streams.push_back(streams[k]);
+  if (int rc = pose_graph_apply_check(ctx, (int)with_frames_slots.size(), with_frames_slots.data(), with_frames_streams.data())) return rc;
+
+  LoopStepMem* m = mem_of(ctx);
+  m->last.assign(n, Aligned());
+  m->assemble_ms = m->icp_ms = m->solve_ms = 0.f, m->candidates = m->aligned = m->closed = 0;
+  // ---- detect (host work: keyframe_select.h, loop_step.h) ----
+  std::vector<int> cand;  // entries that go to the assembly
+  for (int k = 0; k < n; ++k) {
+    lins_loop_step_result& r = out[k];
+    std::memset(&r, 0, sizeof r);
+    r.outcome = LINS_LOOP_NONE, r.latest_id = lins_archive_count(ctx, slots[k]) - 1, r.closest_id = -1;
+    if (r.latest_id < 0) continue;
+    if (int rc = lins_archive_find_loop(ctx, slots[k], &centre[3 * (size_t)k], prm->search_radius, entries[k].now, prm->min_gap_s, &r.closest_id)) return rc;
+    int loops_left = 0, last_latest = -1, last_closest = -1;
+    pose_graph_room(ctx, slots[k], nullptr, &loops_left, &last_latest, &last_closest);
+    const int what = lins_loop::candidate(r.latest_id, r.closest_id, last_latest, last_closest);
+    if (what != lins_loop::kAlign) {
+      r.outcome = what;
+    } else if (loops_left < 1) {
+      r.status = LINS_E_CAPACITY;
+    } else {
+      cand.push_back(k);
+    }
+  }
+  const int nc = (int)cand.size();
+  m->candidates = nc;
+  if (nc == 0) return LINS_OK;
+  // ---- assemble: per candidate the latest frame and the history window, one call ----
+  std::vector<std::vector<int32_t>> ids(2 * (size_t)nc);
+  std::vector<lins_submap_spec> specs(2 * (size_t)nc);
+  std::vector<lins_submap_info> infos(2 * (size_t)nc);
+  for (int i = 0; i < nc; ++i) {
+    const lins_loop_step_result& r = out[cand[i]];
+    ids[2 * i].assign(1, r.latest_id);
+    ids[2 * i + 1].resize(lins_loop::window_size(r.latest_id, r.closest_id, prm->search_num));
+    lins_loop::window(r.latest_id, r.closest_id, prm->search_num, ids[2 * i + 1].data());
+    specs[2 * i] = lins_submap_spec{ids[2 * i].data(), 1, slots[cand[i]], LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF, LINS_SUBMAP_DROP_NEGATIVE, 0.f, 0};
+    specs[2 * i + 1] = lins_submap_spec{ids[2 * i + 1].data(), (int32_t)ids[2 * i + 1].size(), slots[cand[i]], LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF, 0,
+                                        prm->history_leaf, 0};
+  }
+  if (int rc = lins_archive_assemble(ctx, 2 * nc, specs.data(), infos.data())) return rc;
+  (void)lins_last_archive_stats(ctx, &m->assemble_ms, nullptr);
+  ArchiveView av{};
+  if (int rc = archive_view(ctx, &av)) return rc;
+  m->serial = av.serial;
+  // ---- align: one batch over the entries whose assemblies have no status ----
+  std::vector<int> run;  // positions in cand
+  std::vector<lins_loop_icp_problem> probs;
+  for (int i = 0; i < nc; ++i) {
+    lins_loop_step_result& r = out[cand[i]];
+    r.latest = infos[2 * i], r.history = infos[2 * i + 1];
+    if (r.latest.status || r.history.status) {
+      r.status = r.latest.status ? r.latest.status : r.history.status;
+      continue;
+    }
+    run.push_back(i);
+    probs.push_back(lins_loop_icp_problem{2 * i, 2 * i + 1, nullptr, nullptr, 0, 0});
+  }
+  const int na = (int)run.size();
+  if (na == 0) return LINS_OK;
+  std::vector<lins_loop_icp_result> icp(na);
+  if (int rc = lins_loop_icp_batch(ctx, na, probs.data(), &prm->icp, icp.data())) return rc;
+  (void)lins_last_loop_icp_stats(ctx, &m->icp_ms, nullptr);
+  // ---- the factor of every accepted entry (LM:1140-1181) ----
+  std::vector<int> closed;  // entries
+  for (int j = 0; j < na; ++j) {
+    const int k = cand[run[j]];
+    lins_loop_step_result& r = out[k];
+    r.icp = icp[j];
+    if (r.icp.status) {  // (a target box beyond the gridding's limit: nothing was run)
+      r.status = r.icp.status;
+      continue;
+    }
+    m->last[k].source = 2 * run[j];
+    std::memcpy(m->last[k].T, r.icp.transform, sizeof r.icp.transform);
+    m->aligned += 1;
+    r.outcome = LINS_LOOP_REJECTED;
+    if (!lins_loop::accept(r.icp.converged, r.icp.fitness, prm->max_fitness) || !lins_loop::variance(r.icp.fitness, nullptr)) continue;
+    lins_key_pose wrong;
+    if (int rc = lins_pose_graph_poses(ctx, slots[k], r.latest_id, 1, &wrong)) return rc;
+    lins_loop::pose_from(r.icp.transform, wrong, &r.pose_from);
+    if (int rc = lins_pose_graph_add_loop(ctx, slots[k], r.latest_id, r.closest_id, &r.pose_from, r.icp.fitness)) {
+      r.status = rc;  // (a pose_from that is not finite)
+      continue;
+    }
+    closed.push_back(k);
+  }
+  const int ns = (int)closed.size();
+  if (ns == 0) return LINS_OK;
+  // ---- solve, then correct the history: one call each over the slots that gained a loop ----
+  std::vector<int32_t> s_slots(ns), s_streams(ns);
+  std::vector<lins_pose_graph_result> solved(ns);
+  for (int i = 0; i < ns; ++i) s_slots[i] = slots[closed[i]], s_streams[i] = streams[closed[i]];
+  if (int rc = lins_pose_graph_solve(ctx, ns, s_slots.data(), &prm->graph, solved.data())) return rc;
+  (void)lins_last_pose_graph_stats(ctx, &m->solve_ms, nullptr);
+  for (int i = 0; i < ns; ++i) out[closed[i]].graph = solved[i];
+  if (int rc = lins_pose_graph_apply_batch(ctx, ns, s_slots.data(), s_streams.data())) return rc;
+  for (int i = 0; i < ns; ++i) out[closed[i]].outcome = LINS_LOOP_CLOSED;
+  m->closed = ns;
+  return LINS_OK;
+}
+
+int lins_loop_closed_cloud(lins_ctx* ctx, int entry, lins_point* out, int cap) {
+  if (!ctx) return LINS_E_ARG;
+  LoopStepMem* m = mem_of(ctx);
+  if (entry < 0 || entry >= (int)m->last.size() || m->last[entry].source < 0) return LINS_E_ARG;
+  ArchiveView av{};
+  if (int rc = archive_view(ctx, &av)) return rc;
+  if (av.serial != m->serial || m->last[entry].source >= av.n) return LINS_E_STATE;  // (another assembly since the step)
+  const int cnt = lins_archive_download(ctx, m->last[entry].source, out, cap);
+  if (cnt <= 0) return cnt;
+  float M[12];
+  lins_licp::make_move(m->last[entry].T, M);
+  for (int i = 0; i < cnt; ++i) {  // step 1 of the ICP's contract at the final T; intensity stays
+    float x, y, z;
+    lins_licp::move_point(M, out[i].x, out[i].y, out[i].z, x, y, z);
+    out[i].x = x, out[i].y = y, out[i].z = z;
+  }
+  return cnt;
+}
+
+int lins_last_loop_step_stats(lins_ctx* ctx, float* assemble_ms, float* icp_ms, float* solve_ms, int32_t* candidates, int32_t* aligned,
+                              int32_t* closed) {
+  if (!ctx) return LINS_E_ARG;
+  LoopStepMem* m = mem_of(ctx);
+  if (assemble_ms) *assemble_ms = m->assemble_ms;
+  if (icp_ms) *icp_ms = m->icp_ms;
+  if (solve_ms) *solve_ms = m->solve_ms;
+  if (candidates) *candidates = m->candidates;
+  if (aligned) *aligned = m->aligned;
+  if (closed) *closed = m->closed;
+  return LINS_OK;
+}
+
+}  // extern "C"

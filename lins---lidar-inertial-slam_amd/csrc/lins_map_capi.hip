@@ -60,6 +60,9 @@ struct MapState {
   // the pose graphs of lins_pose_graph_* (lins_pose_graph_capi.hip), likewise
   void* graph = nullptr;
   void (*graph_free)(void*) = nullptr;
+  // the loop thread's step of lins_loop_step (lins_loop_step_capi.hip), likewise
+  void* loop_step = nullptr;
+  void (*loop_step_free)(void*) = nullptr;
 };
 
 void map_state_free(void* p) {
@@ -72,6 +75,7 @@ void map_state_free(void* p) {
   if (m->loop) m->loop_free(m->loop);
   if (m->pose) m->pose_free(m->pose);
   if (m->graph) m->graph_free(m->graph);
+  if (m->loop_step) m->loop_step_free(m->loop_step);
   delete m;
 }
 
@@ -338,6 +342,11 @@ void** map_graph_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
   MapState* m = state_of(ctx);
   m->graph_free = free_fn;
   return &m->graph;
+}
+void** map_loop_step_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
+  MapState* m = state_of(ctx);
+  m->loop_step_free = free_fn;
+  return &m->loop_step;
 }
 
 // lins_scan2map_batch with LINS_MAP_LOCAL for the step of lins_streams_map_capi.hip: the same gridding, the same rounds,

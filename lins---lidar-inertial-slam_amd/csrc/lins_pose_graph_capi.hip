@@ -12,6 +12,7 @@
 
 #include "../../include/lins_map.h"
 #include "../../include/lins_streams_map.h"
+#include "host/voxel_map.h"
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
 #include "local_map.h"
@@ -76,6 +77,47 @@ Prob prob_of(const PgMem* m, int slot, int idx) {
 }
 
 }  // namespace
+
+namespace lins {
+int pose_graph_slots(lins_ctx* ctx) { return mem_of(ctx)->n_slots; }
+
+void pose_graph_room(lins_ctx* ctx, int slot, int* frames_left, int* loops_left, int* last_latest, int* last_closest) {
+  const Graph& g = mem_of(ctx)->g[slot];
+  if (frames_left) *frames_left = g.max_frames - g.n_frames();
+  if (loops_left) *loops_left = g.max_loops - (int)g.loops.size();
+  if (last_latest) *last_latest = g.loops.empty() ? -1 : g.loops.back().latest;
+  if (last_closest) *last_closest = g.loops.empty() ? -1 : g.loops.back().closest;
+}
+
+int pose_graph_apply_check(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* streams) {
+  PgMem* m = mem_of(ctx);
+  for (int k = 0; k < n; ++k) {
+    const int slot = slots[k], stream = streams[k];
+    if (slot < 0 || slot >= m->n_slots || stream < -1) return LINS_E_ARG;
+    for (int i = 0; i < k; ++i)
+      if (slots[i] == slot || (stream >= 0 && streams[i] == stream)) return LINS_E_ARG;  // (a slot, a stream: once)
+    const int N = m->g[slot].n_frames();
+    if (N == 0) return LINS_E_ARG;
+    const int in_archive = lins_archive_count(ctx, slot);
+    if (in_archive != LINS_E_STATE && in_archive < N) return in_archive < 0 ? in_archive : LINS_E_ARG;
+    int window = 0;
+    const int on_ring = local_map_slots(ctx) ? local_map_ring(ctx, slot, &window) : 0;  // (0 rings: no local map)
+    if (local_map_slots(ctx) && on_ring < std::min(window, N)) return LINS_E_ARG;  // no such slot, or a ring behind the graph
+    if (stream >= 0) {
+      if (!streams_map_streams(ctx)) return LINS_E_STATE;
+      if (stream >= streams_map_streams(ctx)) return LINS_E_ARG;
+    }
+    if (in_archive != LINS_E_STATE || on_ring > 0) {  // what lins_archive_set_poses / lins_local_map_set_pose take
+      lins_key_pose p;
+      for (int i = 0; i < N; ++i) {
+        m->g[slot].key_pose(i, &p);
+        if (!lins_hostmap::pose_ok(p)) return LINS_E_INPUT;
+      }
+    }
+  }
+  return LINS_OK;
+}
+}  // namespace lins
 
 extern "C" {
 
@@ -224,38 +266,39 @@ int lins_pose_graph_count(lins_ctx* ctx, int slot, int32_t* n_loops) {
   return m->g[slot].n_frames();
 }
 
-int lins_pose_graph_apply(lins_ctx* ctx, int slot, int stream) {
-  if (!ctx) return LINS_E_ARG;
+int lins_pose_graph_apply_batch(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* streams) {
+  if (!ctx || n < 0 || (n && (!slots || !streams))) return LINS_E_ARG;
   PgMem* m = mem_of(ctx);
   if (!m->n_slots) return LINS_E_STATE;
-  if (slot < 0 || slot >= m->n_slots || stream < -1) return LINS_E_ARG;
-  const Graph& g = m->g[slot];
-  const int N = g.n_frames();
-  if (N == 0) return LINS_E_ARG;
-  std::vector<lins_key_pose> poses(N);
-  for (int i = 0; i < N; ++i) g.key_pose(i, &poses[i]);
   // everything that can refuse is asked first, so that a refused call changes nothing
-  const int in_archive = lins_archive_count(ctx, slot);
-  if (in_archive != LINS_E_STATE && in_archive < N) return in_archive < 0 ? in_archive : LINS_E_ARG;
-  int window = 0;
-  const int on_ring = local_map_slots(ctx) ? local_map_ring(ctx, slot, &window) : 0;  // (0 rings: no local map)
-  if (local_map_slots(ctx) && on_ring < std::min(window, N)) return LINS_E_ARG;  // no such slot, or a ring behind the graph
-  lins_map_pose_state ps;
-  if (stream >= 0) {
-    if (int rc = lins_streams_map_get_pose(ctx, stream, &ps)) return rc;
+  if (int rc = pose_graph_apply_check(ctx, n, slots, streams)) return rc;
+  const bool archive = lins_archive_count(ctx, 0) != LINS_E_STATE;
+  std::vector<int32_t> to;  // the streams written, and their newest poses
+  std::vector<float> six;
+  std::vector<lins_key_pose> poses;
+  for (int k = 0; k < n; ++k) {
+    const Graph& g = m->g[slots[k]];
+    const int N = g.n_frames();
+    poses.resize(N);
+    for (int i = 0; i < N; ++i) g.key_pose(i, &poses[i]);
+    if (archive) {  // correctPoses over the whole history
+      if (int rc = lins_archive_set_poses(ctx, slots[k], 0, N, poses.data())) return rc;
+    }
+    const int on_ring = local_map_slots(ctx) ? local_map_ring(ctx, slots[k], nullptr) : 0;  // (0 rings: no local map)
+    for (int age = 0; age < std::min(on_ring, N); ++age) {  // ... and over the ring: its frames are the newest, by age
+      if (int rc = lins_local_map_set_pose(ctx, slots[k], age, &poses[N - 1 - age])) return rc;
+    }
+    if (streams[k] >= 0) {
+      const float* p = &g.held[6 * (size_t)(N - 1)];
+      to.push_back(streams[k]), six.insert(six.end(), p, p + 6);
+    }
   }
-  if (in_archive != LINS_E_STATE) {  // correctPoses over the whole history
-    if (int rc = lins_archive_set_poses(ctx, slot, 0, N, poses.data())) return rc;
-  }
-  for (int age = 0; age < std::min(on_ring, N); ++age) {  // ... and over the ring: its frames are the newest, by age
-    if (int rc = lins_local_map_set_pose(ctx, slot, age, &poses[N - 1 - age])) return rc;
-  }
-  if (stream >= 0) {  // LM:1737-1749
-    const float* p = &g.held[6 * (size_t)(N - 1)];
-    for (int i = 0; i < 6; ++i) ps.aft[i] = ps.last[i] = ps.tobe[i] = p[i];
-    if (int rc = lins_streams_map_set_pose(ctx, stream, &ps)) return rc;
-  }
-  return LINS_OK;
+  return streams_map_correct(ctx, (int)to.size(), to.data(), six.data());  // LM:1737-1749
+}
+
+int lins_pose_graph_apply(lins_ctx* ctx, int slot, int stream) {
+  const int32_t s = slot, t = stream;
+  return lins_pose_graph_apply_batch(ctx, 1, &s, &t);
 }
 
 int lins_last_pose_graph_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* iterations) {

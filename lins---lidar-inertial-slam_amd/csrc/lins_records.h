@@ -87,5 +87,11 @@ struct MapPoseEntry {  // one entry of a step's batch (uploaded per call)
   int stream;  // the MapPoseRec it works on
 };
 static_assert(sizeof(MapPoseEntry) == 40, "MapPoseEntry layout");
+struct MapPoseFix {  // one entry of a write-back's batch (lins_pose_graph_apply_batch): the newest pose of a slot's graph
+  int stream;  // the MapPoseRec it goes to
+  float p[6];  // aft = last = tobe (LM:1737-1749)
+  int pad;
+};
+static_assert(sizeof(MapPoseFix) == 32, "MapPoseFix layout");
 
 }  // namespace lins

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../../include/lins_map.h"
 #include "../../include/lins_streams_map.h"
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
@@ -30,6 +31,14 @@ struct StreamsMap {
   lins_map_step_result *d_out = nullptr, *h_out = nullptr;
   hipEvent_t ev[4] = {};  // associate start / end, finish start / end
   float associate_ms = 0.f, finish_ms = 0.f;
+  // currentRobotPosPoint per stream (LM:1655-1658): transform[3..5] of its last entry with status OK
+  std::vector<float> centre;   // [n][3]
+  std::vector<char> stepped;   // [n]
+  // lins_streams_map_loop: the step feeds the pose graph; transformLast per stream mirrored on the host
+  bool loop = false;
+  std::vector<float> last6;    // [n][6]
+  // a write-back's batch (lins_pose_graph_apply_batch): n entries at most
+  MapPoseFix *d_fix = nullptr, *h_fix = nullptr;
   // lins_map_associate_batch's own buffers (grown, never shrunk)
   MapPoseRec* d_ab_poses = nullptr;
   MapPoseEntry* d_ab_entries = nullptr;
@@ -38,9 +47,10 @@ struct StreamsMap {
 };
 
 void step_buffers_free(StreamsMap* m) {
-  (void)hipFree(m->d_poses), (void)hipFree(m->d_entries), (void)hipFree(m->d_out);
-  (void)hipHostFree(m->h_entries), (void)hipHostFree(m->h_out);
-  m->d_poses = nullptr, m->d_entries = m->h_entries = nullptr, m->d_out = m->h_out = nullptr, m->n = 0;
+  (void)hipFree(m->d_poses), (void)hipFree(m->d_entries), (void)hipFree(m->d_out), (void)hipFree(m->d_fix);
+  (void)hipHostFree(m->h_entries), (void)hipHostFree(m->h_out), (void)hipHostFree(m->h_fix);
+  m->d_poses = nullptr, m->d_entries = m->h_entries = nullptr, m->d_out = m->h_out = nullptr, m->d_fix = m->h_fix = nullptr, m->n = 0;
+  m->loop = false;
 }
 
 void streams_map_free(void* p) {
@@ -67,6 +77,40 @@ bool finite6(const float* v) {
 lins_key_pose key_pose_of(const float* t) { return lins_key_pose{t[3], t[4], t[5], t[0], t[1], t[2]}; }  // LM:1721-1732
 
 }  // namespace
+
+namespace lins {
+int streams_map_streams(lins_ctx* ctx) { return state_of(ctx)->n; }
+
+int streams_map_centre(lins_ctx* ctx, int stream, float centre[3]) {
+  StreamsMap* m = state_of(ctx);
+  if (stream < 0 || stream >= m->n) return LINS_E_ARG;
+  if (!m->stepped[stream]) return LINS_E_STATE;
+  std::memcpy(centre, &m->centre[3 * (size_t)stream], 3 * sizeof(float));
+  return LINS_OK;
+}
+
+int streams_map_correct(lins_ctx* ctx, int n, const int32_t* streams, const float* six) {
+  StreamsMap* m = state_of(ctx);
+  if (n < 0 || n > m->n) return LINS_E_ARG;
+  if (n == 0) return LINS_OK;
+  for (int k = 0; k < n; ++k)
+    if (streams[k] < 0 || streams[k] >= m->n || !finite6(six + 6 * k)) return LINS_E_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  hipStream_t st = ctx_stream(ctx);
+  for (int k = 0; k < n; ++k) {
+    MapPoseFix& f = m->h_fix[k];
+    f.stream = streams[k], f.pad = 0;
+    std::memcpy(f.p, six + 6 * k, sizeof f.p);
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(m->d_fix, m->h_fix, (size_t)n * sizeof(MapPoseFix), hipMemcpyHostToDevice, st));
+  launch_map_pose_correct(st, n, m->d_fix, m->d_poses);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(st));  // (the next batch refills h_fix)
+  if (m->loop)
+    for (int k = 0; k < n; ++k) std::memcpy(&m->last6[6 * (size_t)streams[k]], six + 6 * k, 6 * sizeof(float));
+  return LINS_OK;
+}
+}  // namespace lins
 
 extern "C" {
 
@@ -119,9 +163,13 @@ int lins_streams_map_init(lins_ctx* ctx, int n_streams, double process_interval)
   HIP_TRY(ctx, hipMalloc((void**)&m->d_out, (size_t)n_streams * sizeof(lins_map_step_result)));
   HIP_TRY(ctx, hipHostMalloc((void**)&m->h_entries, (size_t)n_streams * sizeof(MapPoseEntry)));
   HIP_TRY(ctx, hipHostMalloc((void**)&m->h_out, (size_t)n_streams * sizeof(lins_map_step_result)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_fix, (size_t)n_streams * sizeof(MapPoseFix)));
+  HIP_TRY(ctx, hipHostMalloc((void**)&m->h_fix, (size_t)n_streams * sizeof(MapPoseFix)));
   HIP_TRY(ctx, hipMemsetAsync(m->d_poses, 0, (size_t)n_streams * sizeof(MapPoseRec), ctx_stream(ctx)));  // allocateMemory (LM:305-409)
   HIP_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));
   m->last_time.assign((size_t)n_streams, -1.0);  // LM:356
+  m->centre.assign(3 * (size_t)n_streams, 0.f), m->stepped.assign((size_t)n_streams, 0);
+  m->last6.assign(6 * (size_t)n_streams, 0.f);
   m->interval = process_interval;
   m->use_archive = lins_archive_count(ctx, 0) >= 0;
   m->associate_ms = m->finish_ms = 0.f;
@@ -158,6 +206,29 @@ int lins_streams_map_set_pose(lins_ctx* ctx, int stream, const lins_map_pose_sta
   HIP_TRY(ctx, hipMemcpyAsync(m->d_poses + stream, &r, sizeof r, hipMemcpyHostToDevice, ctx_stream(ctx)));
   HIP_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));  // (r goes out of scope)
   m->last_time[stream] = in->last_time;
+  if (m->loop) std::memcpy(&m->last6[6 * (size_t)stream], in->last, sizeof in->last);
+  return LINS_OK;
+}
+
+int lins_streams_map_loop(lins_ctx* ctx, int on) {
+  if (!ctx) return LINS_E_ARG;
+  StreamsMap* m = state_of(ctx);
+  if (!m->n) return LINS_E_STATE;
+  if (!on) {
+    m->loop = false;
+    return LINS_OK;
+  }
+  if (!m->use_archive || pose_graph_slots(ctx) < m->n) return LINS_E_STATE;
+  for (int s = 0; s < m->n; ++s) {
+    const int in_archive = lins_archive_count(ctx, s);  // (an archive re-sized below the streams: no such slot)
+    if (in_archive < 0 || in_archive != lins_pose_graph_count(ctx, s, nullptr)) return LINS_E_STATE;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  std::vector<MapPoseRec> recs((size_t)m->n);
+  HIP_TRY(ctx, hipMemcpyAsync(recs.data(), m->d_poses, recs.size() * sizeof(MapPoseRec), hipMemcpyDeviceToHost, ctx_stream(ctx)));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));
+  for (int s = 0; s < m->n; ++s) std::memcpy(&m->last6[6 * (size_t)s], recs[s].last, sizeof recs[s].last);
+  m->loop = true;
   return LINS_OK;
 }
 
@@ -211,11 +282,24 @@ int lins_streams_map_step(lins_ctx* ctx, int n, const int32_t* streams, const li
   for (int j = 0; j < nb; ++j) {
     const int k = batch[j];
     out[k] = m->h_out[j];
-    if (out[k].status == LINS_OK) m->last_time[which[j]] = odom[k].time;  // LM:1824
+    if (out[k].status == LINS_OK) {
+      m->last_time[which[j]] = odom[k].time;  // LM:1824
+      std::memcpy(&m->centre[3 * (size_t)which[j]], out[k].transform + 3, 3 * sizeof(float));  // LM:1655-1658
+      m->stepped[which[j]] = 1;
+    }
     if (out[k].key_frame) key_entries.push_back(j), key_poses.push_back(key_pose_of(out[k].key_pose)), key_times.push_back(odom[k].time);
   }
   // saveKeyFramesAndFactor's cloud copies (LM:1751-1764), device to device
   const int nk = (int)key_entries.size();
+  if (nk && m->loop) {  // every refusal of the graph is asked before a frame is stored anywhere
+    for (int i = 0; i < nk; ++i) {
+      const int s = which[key_entries[i]];
+      int frames_left = 0;
+      pose_graph_room(ctx, s, &frames_left, nullptr, nullptr, nullptr);
+      if (lins_pose_graph_count(ctx, s, nullptr) != lins_archive_count(ctx, s)) return LINS_E_STATE;
+      if (frames_left < 1) return LINS_E_CAPACITY;
+    }
+  }
   if (nk) {
     if ((rc = lins_local_map_push_scans(ctx, nk, key_entries.data(), key_poses.data()))) return rc;
     std::vector<int32_t> ids((size_t)nk, -1);
@@ -223,6 +307,13 @@ int lins_streams_map_step(lins_ctx* ctx, int n, const int32_t* streams, const li
     for (int i = 0; i < nk; ++i) {
       lins_map_step_result& r = out[batch[key_entries[i]]];
       r.ring_age = 0, r.archive_id = ids[i];
+      if (m->loop) {  // saveKeyFramesAndFactor's factor (LM:1673-1705): the first frame's key pose is transformTobeMapped, the prior
+        float* last = &m->last6[6 * (size_t)which[key_entries[i]]];
+        const int id = lins_pose_graph_push(ctx, which[key_entries[i]], last, r.key_pose);
+        if (id < 0) return id;
+        if (id != ids[i]) return LINS_E_STATE;
+        std::memcpy(last, r.key_pose, 6 * sizeof(float));  // mp_key_pose: transformLast = the key pose
+      }
     }
   }
   return LINS_OK;

@@ -88,6 +88,19 @@ void** map_archive_slot(lins_ctx* ctx, void (*free_fn)(void*));  // ... and the 
 void** map_loop_slot(lins_ctx* ctx, void (*free_fn)(void*));     // ... and the loop-closure ICP's (lins_loop_icp_capi.hip)
 void** map_pose_slot(lins_ctx* ctx, void (*free_fn)(void*));     // ... and the streams' map poses (lins_streams_map_capi.hip)
 void** map_graph_slot(lins_ctx* ctx, void (*free_fn)(void*));    // ... and the pose graphs (lins_pose_graph_capi.hip)
+void** map_loop_step_slot(lins_ctx* ctx, void (*free_fn)(void*));  // ... and the loop thread's step (lins_loop_step_capi.hip)
+
+// lins_streams_map_capi.hip, for the write-back of a loop closure and the loop thread's step
+int streams_map_streams(lins_ctx* ctx);  // streams of lins_streams_map_init (0 before it)
+int streams_map_centre(lins_ctx* ctx, int stream, float centre[3]);  // currentRobotPosPoint; LINS_E_STATE: the stream has not completed a step
+// aft = last = tobe = six[6 k ..] of streams[k] (each in range, at most once; n <= streams): one upload, one launch of
+// map_pose_correct_kernel, one synchronisation
+int streams_map_correct(lins_ctx* ctx, int n, const int32_t* streams, const float* six);
+// lins_pose_graph_capi.hip: n_slots (0 before lins_pose_graph_init); of a slot in range the frames and loops it still
+// takes and the pair of its most recent loop factor (-1, -1: none); every refusal of lins_pose_graph_apply_batch
+int pose_graph_slots(lins_ctx* ctx);
+void pose_graph_room(lins_ctx* ctx, int slot, int* frames_left, int* loops_left, int* last_latest, int* last_closest);
+int pose_graph_apply_check(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* streams);
 
 // lins_map_capi.hip: scan-to-map over the last local-map build (n entries, as LINS_MAP_LOCAL) between the two pose
 // kernels of map_pose_kernels.hip — entry k works on d_poses[d_entries[k].stream]; h_out receives the n result records

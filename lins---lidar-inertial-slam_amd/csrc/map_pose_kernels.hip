@@ -8,6 +8,8 @@
 // map_pose_finish_kernel   behind the last round: transformUpdate's tail (LM:567-576) where the precondition of LM:1636
 //                          held, the key-frame rule (LM:1655-1671) and the key pose with iSAM2 as the identity
 //                          (LM:1676-1686, 1699-1704, 1737-1749); one result record per entry.
+// map_pose_correct_kernel  a loop closure's write-back (LM:1737-1749): per entry, transformAftMapped = transformLast =
+//                          transformTobeMapped = the uploaded newest pose of the entry's stream; the rest of the record stays.
 // One lane per entry, no LDS, no cross-lane operation: a lane beyond n does nothing.  MapDev::pad of an entry carries
 // what the host knew when it queued the rounds: < 0 the build entry's status (nothing is touched), 1 the precondition
 // of LM:1636 held, 0 it did not (null probs: 0).  Every store is a vector store.
@@ -86,6 +88,16 @@ __global__ __launch_bounds__(kPoseThreads) void map_pose_finish_kernel(int n, co
   }
 }
 
+__global__ __launch_bounds__(kPoseThreads) void map_pose_correct_kernel(int n, const MapPoseFix* __restrict__ fixes, MapPoseRec* __restrict__ poses) {
+  const int k = blockIdx.x * kPoseThreads + threadIdx.x;
+  if (k < n) {
+    const MapPoseFix f = fixes[k];
+    MapPoseRec* rec = poses + f.stream;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) rec->aft[i] = f.p[i], rec->last[i] = f.p[i], rec->tobe[i] = f.p[i];
+  }
+}
+
 }  // namespace
 
 void launch_map_associate(hipStream_t stream, int n, const MapPoseEntry* entries, const MapDev* probs, MapPoseRec* poses, lins_map_result* results,
@@ -97,6 +109,10 @@ void launch_map_pose_finish(hipStream_t stream, int n, const MapPoseEntry* entri
                             const lins_map_result* results, lins_map_step_result* out) {
   hipLaunchKernelGGL(map_pose_finish_kernel, dim3((n + kPoseThreads - 1) / kPoseThreads), dim3(kPoseThreads), 0, stream, n, entries, probs, poses,
                      results, out);
+}
+
+void launch_map_pose_correct(hipStream_t stream, int n, const MapPoseFix* fixes, MapPoseRec* poses) {
+  hipLaunchKernelGGL(map_pose_correct_kernel, dim3((n + kPoseThreads - 1) / kPoseThreads), dim3(kPoseThreads), 0, stream, n, fixes, poses);
 }
 
 }  // namespace lins

@@ -470,6 +470,41 @@ def loop_pose_from(T, wrong):
     return np.array([out.x, out.y, out.z, out.roll, out.pitch, out.yaw], np.float32)
 
 
+def loop_window(latest, closest, search_num):
+    """lins_host_loop_window (LM:1087-1098): the ids closest - search_num .. closest + search_num clipped to [0, latest]"""
+    L = lib()
+    cap = max(int(latest) + 1, 1)
+    ids = np.zeros(cap, np.int32)
+    L.lins_host_loop_window.argtypes, L.lins_host_loop_window.restype = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int], C.c_int
+    n = L.lins_host_loop_window(int(latest), int(closest), int(search_num), ids.ctypes.data, cap)
+    if n < 0:
+        raise RuntimeError(f"lins_host_loop_window: {n}")
+    return ids[:n].tolist()
+
+
+def loop_candidate(latest, closest, last_latest=-1, last_closest=-1):
+    """lins_host_loop_candidate: LOOP_NONE (no candidate, or the latest frame itself), LOOP_REPEAT (the pair of the slot's
+    most recent loop factor), or -1: the pair is aligned"""
+    L = lib()
+    L.lins_host_loop_candidate.argtypes, L.lins_host_loop_candidate.restype = [C.c_int] * 4, C.c_int
+    return int(L.lins_host_loop_candidate(int(latest), int(closest), int(last_latest), int(last_closest)))
+
+
+def loop_accept(converged, fitness, max_fitness=0.3):
+    """lins_host_loop_accept (LM:1140-1141): converged && !(fitness > (double)(float)max_fitness)"""
+    L = lib()
+    L.lins_host_loop_accept.argtypes, L.lins_host_loop_accept.restype = [C.c_int, C.c_double, C.c_float], C.c_int
+    return bool(L.lins_host_loop_accept(int(converged), float(fitness), float(max_fitness)))
+
+
+def loop_variance(fitness):
+    """lins_host_loop_variance (LM:1171-1175) -> (usable, (double)(float)fitness)"""
+    L, v = lib(), C.c_double(0)
+    L.lins_host_loop_variance.argtypes, L.lins_host_loop_variance.restype = [C.c_double, C.POINTER(C.c_double)], C.c_int
+    ok = L.lins_host_loop_variance(float(fitness), C.byref(v))
+    return bool(ok), float(v.value)
+
+
 def _buf(n):
     a = np.zeros((n, 4), dtype=np.float32)
     return a, a.ctypes.data_as(C.POINTER(Point))

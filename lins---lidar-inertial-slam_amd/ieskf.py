@@ -41,7 +41,8 @@ EXPORTS = [
     "lins_streams_map_step", "lins_last_streams_map_ms",
     "lins_pose_graph_default_params", "lins_pose_graph_init", "lins_pose_graph_push", "lins_pose_graph_add_loop",
     "lins_pose_graph_solve", "lins_pose_graph_poses", "lins_pose_graph_apply", "lins_pose_graph_count",
-    "lins_last_pose_graph_stats",
+    "lins_last_pose_graph_stats", "lins_pose_graph_apply_batch",
+    "lins_loop_step_default_params", "lins_loop_step", "lins_loop_closed_cloud", "lins_last_loop_step_stats", "lins_streams_map_loop",
 ]
 
 
@@ -105,7 +106,7 @@ def lib():
         L.lins_last_reproject_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
         for name in EXPORTS:
             if name not in ("lins_destroy", "lins_strerror", "lins_last_hip_error", "lins_last_search", "lins_loop_icp_default_params",
-                            "lins_boot_default_params", "lins_pose_graph_default_params"):
+                            "lins_boot_default_params", "lins_pose_graph_default_params", "lins_loop_step_default_params"):
                 if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                     continue  # (an older build under A/B timing)
                 getattr(L, name).restype = C.c_int
@@ -538,6 +539,57 @@ class IeskfContext:
         L = lib()
         L.lins_pose_graph_apply.argtypes = [C.c_void_p, C.c_int, C.c_int]
         self._check(L.lins_pose_graph_apply(self._h, int(slot), int(stream)))
+
+    def pose_graph_apply_batch(self, slots, streams=None):
+        """pose_graph_apply for every (slot, stream) pair in one call: every refusal first, the streams' records by one
+        kernel behind one upload; streams None: no streams (-1)"""
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        st = np.full(len(sl), -1, np.int32) if streams is None else np.ascontiguousarray(streams, dtype=np.int32)
+        assert len(sl) == len(st)
+        L = lib()
+        L.lins_pose_graph_apply_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._check(L.lins_pose_graph_apply_batch(self._h, len(sl), sl.ctypes.data, st.ctypes.data))
+
+    # -- the loop thread's step (include/lins_map.h lins_loop_step) ------------------------------------
+    def loop_step(self, entries, params=None):
+        """performLoopClosure + correctPoses for the slots named.  entries: LoopStepEntryC (loop_step_entry) or tuples
+        (slot, centre, now[, stream]); params: a LoopStepParamsC (default: lins_loop_step_default_params).  Returns the
+        per-entry result dicts."""
+        from ._ctypes_defs import LoopStepEntryC, LoopStepParamsC, LoopStepResultC, loop_step_entry, loop_step_params
+
+        L = lib()
+        prm = params if params is not None else loop_step_params(L)
+        n = len(entries)
+        arr = (LoopStepEntryC * max(n, 1))(*[e if isinstance(e, LoopStepEntryC) else loop_step_entry(*e) for e in entries])
+        out = (LoopStepResultC * max(n, 1))()
+        L.lins_loop_step.argtypes = [C.c_void_p, C.c_int, C.POINTER(LoopStepEntryC), C.POINTER(LoopStepParamsC), C.POINTER(LoopStepResultC)]
+        self._loop_step_sizes = []
+        self._check(L.lins_loop_step(self._h, n, arr, C.byref(prm), out))
+        res = [out[k].as_dict() for k in range(n)]
+        self._loop_step_sizes = [r["latest"]["n"] for r in res]
+        # the step's assembly is the archive's last one: two clouds per entry that had a candidate, in entry order
+        self._archive_info = [r[k] for r in res if r["latest"]["frames"] for k in ("latest", "history")]
+        return res
+
+    def loop_closed_cloud(self, entry):
+        """closed_cloud (LM:1143-1154) of an aligned entry of the last loop_step, (n, 4) f32"""
+        sizes = getattr(self, "_loop_step_sizes", [])
+        cap = sizes[entry] if 0 <= entry < len(sizes) else 0
+        out = np.zeros((max(cap, 1), 4), np.float32)
+        L = lib()
+        L.lins_loop_closed_cloud.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        n = self._rc(L.lins_loop_closed_cloud(self._h, int(entry), out.ctypes.data, int(cap)))
+        return out[:n].copy()
+
+    def loop_step_stats(self):
+        """dict(assemble_ms, icp_ms, solve_ms, candidates, aligned, closed) of the last loop_step"""
+        L = lib()
+        ms = [C.c_float(0) for _ in range(3)]
+        cnt = [C.c_int32(0) for _ in range(3)]
+        L.lins_last_loop_step_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_float)] * 3 + [C.POINTER(C.c_int32)] * 3
+        self._check(L.lins_last_loop_step_stats(self._h, *[C.byref(v) for v in ms + cnt]))
+        return dict(assemble_ms=ms[0].value, icp_ms=ms[1].value, solve_ms=ms[2].value, candidates=cnt[0].value, aligned=cnt[1].value,
+                    closed=cnt[2].value)
 
     def pose_graph_stats(self):
         """(HIP-event ms of the last pose_graph_solve, trials it ran over all problems)"""

@@ -51,6 +51,14 @@ def set_pose(ctx, stream, state):
     ctx._check(L.lins_streams_map_set_pose(ctx._h, int(stream), C.byref(s)))
 
 
+def loop(ctx, on=True):
+    """lins_streams_map_loop: with it on, every step pushes the factor of each key frame it stores to the pose graph
+    (slot = stream) and lins_loop_step finds graph and archive in step"""
+    L = _ieskf.lib()
+    L.lins_streams_map_loop.argtypes = [C.c_void_p, C.c_int]
+    ctx._check(L.lins_streams_map_loop(ctx._h, int(bool(on))))
+
+
 def odom(transform_sum, time, imu_roll=0.0, imu_pitch=0.0, has_imu=False):
     o = MapOdomC()
     o.transform_sum[:] = [float(v) for v in np.asarray(transform_sum, np.float32)]
