@@ -213,7 +213,9 @@ __device__ __forceinline__ void make_iter_const_tail(const double* filt, IterCon
 // (xor 32, 16, 8, 4, 2) in which a lane pair splits the sums it still carries — one keeps the lower
 // half, the other the upper half, each adding the partner's copy — and a final xor-1 add.  29
 // shuffles instead of 28 x 6; the tree is fixed, so the sums are bit-reproducible from run to run.
-// Afterwards lane l holds sum number reduce_sum_index(l) of the whole wave.
+// Afterwards lane l holds sum number reduce_sum_index(l) of the whole wave.  The two top levels (21 of the 29
+// exchanges) swap the pair (lower half, upper half) in place (swap_halves_add below); the four lower ones select what
+// to keep and what to send and exchange the latter with xor_lane_f64.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
   const int lo = __shfl_xor(__double2loint(v), mask), hi = __shfl_xor(__double2hiint(v), mask);
@@ -247,6 +249,28 @@ template <int MASK>
 __device__ __forceinline__ double xor_lane_f64(double v, int lane) {
   return __hiloint2double(xor_lane_i32<MASK>(__double2hiint(v), lane), xor_lane_i32<MASK>(__double2loint(v), lane));
 }
+// One sum of a halving level xor MASK (32 or 16) of wave_reduce_rows: a lane without the MASK bit keeps `lo` and sends
+// `hi`, its partner lane ^ MASK keeps `hi` and sends `lo`; returns kept + received in both.  The gfx950 lane swap IS
+// that exchange when it is given the pair (lo, hi) instead of one value twice: v_permlane32_swap trades the upper 32
+// lanes of its first register for the lower 32 of its second (v_permlane16_swap: the odd rows of 16 for the even rows),
+// which leaves {lo[l], hi[l ^ MASK]} in the first and {lo[l ^ MASK], hi[l]} in the second, read at a lane l without /
+// with the bit.  Either way one register holds what the lane keeps and the other what its partner sent: no select in
+// front of the exchange and none behind it.  The upper lanes add received + kept where the select form added
+// kept + received: the same double, signed zeros and infinities included; only where BOTH are NaN may the sum carry the
+// other one's payload (profiles/rowsum_swap_exchange.md).
+template <int MASK>
+__device__ __forceinline__ double swap_halves_add(double lo, double hi) {
+  static_assert(MASK == 32 || MASK == 16, "the levels that have a lane-swap instruction");
+  const unsigned ll = (unsigned)__double2loint(lo), lh = (unsigned)__double2hiint(lo);
+  const unsigned hl = (unsigned)__double2loint(hi), hh = (unsigned)__double2hiint(hi);
+  if constexpr (MASK == 32) {
+    const auto w = __builtin_amdgcn_permlane32_swap(ll, hl, false, false), u = __builtin_amdgcn_permlane32_swap(lh, hh, false, false);
+    return __hiloint2double((int)u[0], (int)w[0]) + __hiloint2double((int)u[1], (int)w[1]);
+  } else {
+    const auto w = __builtin_amdgcn_permlane16_swap(ll, hl, false, false), u = __builtin_amdgcn_permlane16_swap(lh, hh, false, false);
+    return __hiloint2double((int)u[0], (int)w[0]) + __hiloint2double((int)u[1], (int)w[1]);
+  }
+}
 __device__ __forceinline__ int reduce_sum_index(int lane) {
   const int local = ((lane >> 3) & 1) * 4 + ((lane >> 2) & 1) * 2 + ((lane >> 1) & 1);
   return (local < 7 && !(lane & 1)) ? ((lane >> 5) & 1) * 14 + ((lane >> 4) & 1) * 7 + local : -1;
@@ -257,22 +281,10 @@ __device__ __forceinline__ double wave_reduce_rows(const double (&row)[7], int l
   double v[28];
 #pragma unroll
   for (int k = 0; k < 28; ++k) v[k] = row[A[k]] * row[B[k]];
-  {
-    const bool up = (lane & 32) != 0;
 #pragma unroll
-    for (int i = 0; i < 14; ++i) {
-      const double lo = v[i], hi = v[i + 14];
-      v[i] = (up ? hi : lo) + xor_lane_f64<32>(up ? lo : hi, lane);
-    }
-  }
-  {
-    const bool up = (lane & 16) != 0;
+  for (int i = 0; i < 14; ++i) v[i] = swap_halves_add<32>(v[i], v[i + 14]);
 #pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      const double lo = v[i], hi = v[i + 7];
-      v[i] = (up ? hi : lo) + xor_lane_f64<16>(up ? lo : hi, lane);
-    }
-  }
+  for (int i = 0; i < 7; ++i) v[i] = swap_halves_add<16>(v[i], v[i + 7]);
   v[7] = 0.0;
   {
     const bool up = (lane & 8) != 0;
