@@ -341,6 +341,26 @@ void lins_host_map_transform_update(float tobe[6], int has_imu, float imu_roll, 
  * (previousRobotPosPoint) to aft[3..5] is not < 0.3, or have_frames == 0 — and then sets prev to aft[3..5]          */
 int lins_host_map_key_rule(float prev[3], const float aft[6], int have_frames);
 
+/* ---- the seam between the filter and the mapping node on the CPU (host/odom.cpp) ------------------------------------
+ * The restatement the odometry and fusion kernels are checked against (csrc/odom_math.h in both libraries; the entry
+ * points for streams: lins_streams_slam.h).  tf's arithmetic is stated there, in f64.                                 */
+typedef struct lins_stream_odom {   /* /laser_odom_to_init of one stream + the mapping node's transformSum */
+  double position[3], orientation[4];   /* globalStateYZX_: rn_, qbn_ as (x, y, z, w) */
+  float transform_sum[6];               /* transformSum (LM:711-724) */
+  int32_t valid, reserved;              /* valid 0: the stream has no globalState_ yet, or it is not finite */
+} lins_stream_odom;
+typedef struct lins_fused_pose {    /* /integrated_to_init (TF:217-254) */
+  float transform_mapped[6];            /* transformMapped (TF:91-215) */
+  double orientation[4];                /* (x, y, z, w) as laserOdometry2 */
+} lins_fused_pose;
+/* globalState_ (19 doubles: rn_ 0-2, qbn_ 6-9 as w, x, y, z) to the record: the exact axis permutation of SE:1152-1154,
+ * then laserOdometryHandler (LM:711-724).  A non-finite rn_ / qbn_ or transformSum: valid = 0, everything else zero.  */
+void lins_host_odom_from_global(const double* gs19, lins_stream_odom* out);
+/* the orientation published with a pose (rx, ry, rz, tx, ty, tz): tf's setRPY(t[2], -t[0], -t[1]) sent as (-y, -z, x, w) */
+void lins_host_pose_quat(const float* t6, double* q4);
+/* the transform fusion node: transformMapped = lins_host_map_associate(bef, aft, sum), orientation = lins_host_pose_quat */
+void lins_host_fuse(const float* bef6, const float* aft6, const float* sum6, lins_fused_pose* out);
+
 /* ---- the pose graph on the CPU (host/pose_graph.cpp) ---------------------------------------------------------------
  * The restatement lins_pose_graph_* is checked against (include/lins_map.h has the contract; the arithmetic is
  * csrc/pose_graph_math.h and the solve csrc/pose_graph.h in both libraries: the same phases in the same order, so host

@@ -551,3 +551,24 @@ class MapStepResultC(C.Structure):
         d = {k: np.array(getattr(self, k)[:], np.float32) for k in ("tobe_start", "transform", "key_pose")}
         d.update((k, int(getattr(self, k))) for k in self.COUNTS)
         return d
+
+
+# ---- streams end to end (include/lins_streams_slam.h; lins_stream_odom / lins_fused_pose: include/lins_host.h) ----
+class StreamOdomC(C.Structure):
+    _fields_ = [("position", C.c_double * 3), ("orientation", C.c_double * 4), ("transform_sum", C.c_float * 6), ("valid", C.c_int32),
+                ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return dict(position=np.array(self.position[:], np.float64), orientation=np.array(self.orientation[:], np.float64),
+                    transform_sum=np.array(self.transform_sum[:], np.float32), valid=int(self.valid))
+
+
+class FusedPoseC(C.Structure):
+    _fields_ = [("transform_mapped", C.c_float * 6), ("orientation", C.c_double * 4)]
+
+    def as_dict(self):
+        return dict(transform_mapped=np.array(self.transform_mapped[:], np.float32), orientation=np.array(self.orientation[:], np.float64))
+
+
+class SlamImuC(C.Structure):
+    _fields_ = [("roll", C.c_float), ("pitch", C.c_float), ("has_imu", C.c_int32), ("reserved", C.c_int32)]

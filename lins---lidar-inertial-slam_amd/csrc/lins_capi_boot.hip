@@ -175,6 +175,7 @@ int lins_streams_machine_init(lins_ctx* ctx, const lins_boot_params* prm) {
   t.cur.assign(n, 0), t.last_counts.assign(n * 2, -1);
   t.outl_counts.assign(n * 2, 0), t.outl_put.assign(n, 0), t.outl_pending = false;
   t.index_ready = false;
+  streams_slam_reset(ctx);
   b.on = true;
   return LINS_OK;
 }

@@ -20,6 +20,7 @@ void streams_free(lins_ctx* ctx) {
   t.d_desc_next = nullptr, t.index_ready = false;
   streams_filter_free(ctx);
   streams_boot_free(ctx);
+  streams_slam_free(ctx);
   (void)hipFree(t.d_gsorted), (void)hipFree(t.d_gridtab), (void)hipFree(t.d_outl);
   t = lins_ctx::Streams{};
 }

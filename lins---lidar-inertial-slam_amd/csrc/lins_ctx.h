@@ -1,6 +1,7 @@
 // lins_ctx.h — the context of the C ABI (include/lins_ieskf.h) and what the C API files share: the struct itself, the
 // error macro, and the helpers more than one of lins_capi.hip / lins_capi_dist.hip / lins_capi_frontend.hip /
-// lins_capi_debug.hip needs.  (The scan-to-map files see a context through lins_ctx_priv.h only.)
+// lins_capi_debug.hip needs.  (The scan-to-map files see a context through lins_ctx_priv.h only;
+// lins_streams_slam_capi.hip, which joins the streams' filter to their mapping step, includes this header.)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -34,6 +35,7 @@ typedef enum { ncclInt8 = 0, ncclChar = 0 } ncclDataType_t;
 #include "../../include/lins_host.h"
 #include "../../include/lins_streams_filter.h"
 #include "../../include/lins_streams_map.h"
+#include "../../include/lins_streams_slam.h"
 #include "ieskf_device.h"
 #include "ieskf_grid.h"
 #include "lins_ctx_priv.h"
@@ -186,6 +188,14 @@ struct lins_ctx {
       bool pre_timed = false, icp_timed = false, finish_timed = false;
       float pre_ms = 0.f, icp_ms = 0.f, finish_ms = 0.f;
     } b;
+    // streams end to end (lins_streams_slam.h; lins_streams_slam_capi.hip): the odometry records derived from d_gstate and
+    // the staging of the fusion.  Allocated by the first call that derives the records.
+    struct Slam {
+      lins_stream_odom *d_odom = nullptr, *h_odom = nullptr;  // n records (h_: pinned)
+      int *d_ints = nullptr, *h_ints = nullptr;               // [stream has a globalState_ | fusion list] x n (h_: pinned)
+      lins_fused_pose *d_fused = nullptr, *h_fused = nullptr; // n fused poses (h_: pinned)
+      bool have = false;                                      // the records have been derived at least once
+    } s;
   } st;
   void* map_state = nullptr;  // scan-to-map row (lins_map_capi.hip), freed through map_state_free
   void (*map_state_free)(void*) = nullptr;
@@ -294,6 +304,7 @@ int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, const lin
                       const double* prior_state, const double* prior_cov, double scan_period, lins_result* out,
                       int32_t* feature_counts, const StepImu* imu = nullptr, const StepMachine* mach = nullptr);
 void streams_boot_free(lins_ctx* ctx);
+void streams_slam_free(lins_ctx* ctx);  // lins_streams_slam_capi.hip
 // argument check of a machine-mode call's IMU rows (as streams_filter_check, without the need of a loaded filter)
 int streams_boot_check(lins_ctx* ctx, const int32_t* n_imu, const double* const* imu);
 // queue the pre-integration kernel over the rows of the streams in FIRST_SCAN

@@ -22,6 +22,7 @@ struct StreamMapClouds {
   int n[3];
 };
 int streams_map_clouds(lins_ctx* ctx, int stream, StreamMapClouds* v);
+void streams_slam_reset(lins_ctx* ctx);  // lins_streams_slam_capi.hip: the resident odometry records are no longer current
 int streams_count(lins_ctx* ctx);  // streams of lins_streams_init (0: none, or a failed streams context)
 }  // namespace lins
 

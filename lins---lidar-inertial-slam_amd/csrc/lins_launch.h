@@ -110,13 +110,20 @@ void launch_debug_lm_step(hipStream_t stream, int n, int wave_version, const dou
 
 // ---- map_pose_kernels.hip: the mapping node's pose arithmetic around scan-to-map (map_pose_math.h).  One lane per entry;
 // probs[k].pad: < 0 the build entry's status, 1 the precondition of LM:1636 held, 0 it did not (associate: probs may be
-// null = 0, results may be null)
+// null = 0, results may be null).  odom null: transformSum is the entry's uploaded sum; else it is read from the resident
+// record of the entry's stream, odom[entries[k].stream].transform_sum (lins_streams_map_step_resident)
 void launch_map_associate(hipStream_t stream, int n, const MapPoseEntry* entries, const MapDev* probs, MapPoseRec* poses, lins_map_result* results,
-                          lins_map_step_result* out);
+                          lins_map_step_result* out, const lins_stream_odom* odom = nullptr);
 void launch_map_pose_finish(hipStream_t stream, int n, const MapPoseEntry* entries, const MapDev* probs, MapPoseRec* poses,
-                            const lins_map_result* results, lins_map_step_result* out);
+                            const lins_map_result* results, lins_map_step_result* out, const lins_stream_odom* odom = nullptr);
 // aft = last = tobe = fixes[k].p of stream fixes[k].stream, k < n; bef, prev and n_frames stay (a stream at most once)
 void launch_map_pose_correct(hipStream_t stream, int n, const MapPoseFix* fixes, MapPoseRec* poses);
+
+// ---- odom_kernels.hip: the seam between the streams' filter and their mapping step (odom_math.h).  One lane per stream / entry
+// recs[k] of globalState_ row k (19 doubles), k < n; has[k] == 0: the stream has no globalState_ yet (valid = 0)
+void launch_odom_records(hipStream_t stream, int n, const double* gstate, const int* has, lins_stream_odom* recs);
+// out[k] = the transform fusion node's pose of stream list[k] from poses[list[k]].bef / .aft and recs[list[k]].transform_sum
+void launch_odom_fuse(hipStream_t stream, int n, const int* list, const MapPoseRec* poses, const lins_stream_odom* recs, lins_fused_pose* out);
 
 // ---- local_map_kernels.hip: the mapping node's local map
 void launch_lm_transform(hipStream_t s, int n_blocks, const LmSeg* segs, const int2* blocks, const float4* frames, float4* stage, LmState* states);

@@ -353,8 +353,9 @@ void** map_loop_step_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
 // but the start transforms are not uploaded — map_associate_kernel forms them on the device from the resident poses and
 // writes them where the first launch_map_lm reads them — and map_pose_finish_kernel runs behind the last round, so that
 // what comes down is one lins_map_step_result per entry.  d_entries is already on its way on the context's stream.
+// d_odom (or null): the two pose kernels read transformSum from the resident record of the entry's stream.
 int scan2map_local_resident(lins_ctx* ctx, int n, const MapPoseEntry* d_entries, MapPoseRec* d_poses, lins_map_step_result* d_out,
-                            lins_map_step_result* h_out, hipEvent_t* ev) {
+                            lins_map_step_result* h_out, hipEvent_t* ev, const lins_stream_odom* d_odom) {
   HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
   MapState* m = state_of(ctx);
   int rc = map_selfcheck(ctx, m);
@@ -375,7 +376,7 @@ int scan2map_local_resident(lins_ctx* ctx, int n, const MapPoseEntry* d_entries,
   ctx_events(ctx, &e0, &e1);
   HIP_TRY(ctx, hipMemcpyAsync(m->d_probs, dev.data(), (size_t)n * sizeof(MapDev), hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipEventRecord(ev[0], st));
-  launch_map_associate(st, n, d_entries, m->d_probs, d_poses, m->d_results, d_out);
+  launch_map_associate(st, n, d_entries, m->d_probs, d_poses, m->d_results, d_out, d_odom);
   HIP_TRY(ctx, hipEventRecord(ev[1], st));
   HIP_TRY(ctx, hipEventRecord(e0, st));
   launch_map_lm(st, n, -1, bpp, m->d_probs, m->d_rounds, m->d_partials, m->d_results, m->d_carry);
@@ -386,7 +387,7 @@ int scan2map_local_resident(lins_ctx* ctx, int n, const MapPoseEntry* d_entries,
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(e1, st));
   HIP_TRY(ctx, hipEventRecord(ev[2], st));
-  launch_map_pose_finish(st, n, d_entries, m->d_probs, d_poses, m->d_results, d_out);
+  launch_map_pose_finish(st, n, d_entries, m->d_probs, d_poses, m->d_results, d_out, d_odom);
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(ev[3], st));
   HIP_TRY(ctx, hipMemcpyAsync(h_out, d_out, (size_t)n * sizeof(lins_map_step_result), hipMemcpyDeviceToHost, st));

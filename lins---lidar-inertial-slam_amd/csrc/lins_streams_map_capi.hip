@@ -80,6 +80,7 @@ lins_key_pose key_pose_of(const float* t) { return lins_key_pose{t[3], t[4], t[5
 
 namespace lins {
 int streams_map_streams(lins_ctx* ctx) { return state_of(ctx)->n; }
+const MapPoseRec* streams_map_poses(lins_ctx* ctx) { return state_of(ctx)->d_poses; }
 
 int streams_map_centre(lins_ctx* ctx, int stream, float centre[3]) {
   StreamsMap* m = state_of(ctx);
@@ -174,6 +175,7 @@ int lins_streams_map_init(lins_ctx* ctx, int n_streams, double process_interval)
   m->use_archive = lins_archive_count(ctx, 0) >= 0;
   m->associate_ms = m->finish_ms = 0.f;
   m->n = n_streams;
+  streams_slam_reset(ctx);  // (lins_streams_fuse: no records of an earlier run against the new poses)
   return LINS_OK;
 }
 
@@ -234,6 +236,14 @@ int lins_streams_map_loop(lins_ctx* ctx, int on) {
 
 int lins_streams_map_step(lins_ctx* ctx, int n, const int32_t* streams, const lins_map_odom* odom, lins_map_step_result* out) {
   if (!ctx || n < 0 || (n && (!streams || !odom || !out))) return LINS_E_ARG;
+  return streams_map_step_run(ctx, n, streams, MapStepIn{odom, nullptr, nullptr, nullptr, nullptr}, out);
+}
+
+}  // extern "C"
+
+// run() for the entries named: the body of lins_streams_map_step and lins_streams_map_step_resident (local_map.h MapStepIn)
+int lins::streams_map_step_run(lins_ctx* ctx, int n, const int32_t* streams, const MapStepIn& in, lins_map_step_result* out) {
+  const lins_map_odom* odom = in.odom;
   StreamsMap* m = state_of(ctx);
   if (!m->n) return LINS_E_STATE;
   if (n > m->n) return LINS_E_ARG;
@@ -243,19 +253,24 @@ int lins_streams_map_step(lins_ctx* ctx, int n, const int32_t* streams, const li
       if (streams[i] == streams[k]) return LINS_E_ARG;  // (a stream may appear once)
   }
   for (int k = 0; k < n; ++k) {
-    const lins_map_odom& o = odom[k];
-    if (!finite6(o.transform_sum) || !std::isfinite(o.time) || !std::isfinite(o.imu_roll) || !std::isfinite(o.imu_pitch)) return LINS_E_INPUT;
+    if (odom) {
+      const lins_map_odom& o = odom[k];
+      if (!finite6(o.transform_sum) || !std::isfinite(o.time) || !std::isfinite(o.imu_roll) || !std::isfinite(o.imu_pitch)) return LINS_E_INPUT;
+    } else if (!std::isfinite(in.time[k]) || (in.imu && (!std::isfinite(in.imu[k].roll) || !std::isfinite(in.imu[k].pitch))))
+      return LINS_E_INPUT;
   }
+  auto time_of = [&](int k) { return odom ? odom[k].time : in.time[k]; };
   m->associate_ms = m->finish_ms = 0.f;
   // the interval gate (LM:1821), f64
   std::vector<int> batch;     // positions in the call of the entries that run
   std::vector<int32_t> which;  // ... and their streams = their slots
   for (int k = 0; k < n; ++k) {
-    if (odom[k].time - m->last_time[streams[k]] >= m->interval) {
+    const bool no_record = !odom && !in.h_odom[streams[k]].valid;  // (the stream has no pose to map with: refused, entry alone)
+    if (!no_record && time_of(k) - m->last_time[streams[k]] >= m->interval) {
       batch.push_back(k), which.push_back(streams[k]);
     } else {
       out[k] = lins_map_step_result{};
-      out[k].status = LINS_MAP_STEP_SKIPPED, out[k].ring_age = -1, out[k].archive_id = -1;
+      out[k].status = no_record ? LINS_E_INPUT : LINS_MAP_STEP_SKIPPED, out[k].ring_age = -1, out[k].archive_id = -1;
     }
   }
   const int nb = (int)batch.size();
@@ -263,17 +278,25 @@ int lins_streams_map_step(lins_ctx* ctx, int n, const int32_t* streams, const li
   HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
   hipStream_t st = ctx_stream(ctx);
   for (int j = 0; j < nb; ++j) {
-    const lins_map_odom& o = odom[batch[j]];
     MapPoseEntry& e = m->h_entries[j];
-    std::memcpy(e.sum, o.transform_sum, sizeof e.sum);
-    e.imu_roll = o.imu_roll, e.imu_pitch = o.imu_pitch, e.has_imu = o.has_imu != 0, e.stream = which[j];
+    if (odom) {
+      const lins_map_odom& o = odom[batch[j]];
+      std::memcpy(e.sum, o.transform_sum, sizeof e.sum);
+      e.imu_roll = o.imu_roll, e.imu_pitch = o.imu_pitch, e.has_imu = o.has_imu != 0;
+    } else {  // (transformSum: the kernels read the resident record of the stream)
+      std::memset(e.sum, 0, sizeof e.sum);
+      const lins_slam_imu none{0.f, 0.f, 0, 0};
+      const lins_slam_imu& a = in.imu ? in.imu[batch[j]] : none;
+      e.imu_roll = a.roll, e.imu_pitch = a.pitch, e.has_imu = a.has_imu != 0;
+    }
+    e.stream = which[j];
   }
   HIP_TRY(ctx, hipMemcpyAsync(m->d_entries, m->h_entries, (size_t)nb * sizeof(MapPoseEntry), hipMemcpyHostToDevice, st));
   // extractSurroundingKeyFrames + downsampleCurrentScan over the streams' clouds where they lie
   int rc = lins_local_map_build_streams(ctx, nb, which.data(), which.data(), nullptr);
   if (rc) return rc;
   // transformAssociateToMap, scan2MapOptimization, transformUpdate, the key-frame rule
-  if ((rc = scan2map_local_resident(ctx, nb, m->d_entries, m->d_poses, m->d_out, m->h_out, m->ev))) return rc;
+  if ((rc = scan2map_local_resident(ctx, nb, m->d_entries, m->d_poses, m->d_out, m->h_out, m->ev, odom ? nullptr : in.d_odom))) return rc;
   HIP_TRY(ctx, hipEventElapsedTime(&m->associate_ms, m->ev[0], m->ev[1]));
   HIP_TRY(ctx, hipEventElapsedTime(&m->finish_ms, m->ev[2], m->ev[3]));
   std::vector<int32_t> key_entries;
@@ -283,11 +306,11 @@ int lins_streams_map_step(lins_ctx* ctx, int n, const int32_t* streams, const li
     const int k = batch[j];
     out[k] = m->h_out[j];
     if (out[k].status == LINS_OK) {
-      m->last_time[which[j]] = odom[k].time;  // LM:1824
+      m->last_time[which[j]] = time_of(k);  // LM:1824
       std::memcpy(&m->centre[3 * (size_t)which[j]], out[k].transform + 3, 3 * sizeof(float));  // LM:1655-1658
       m->stepped[which[j]] = 1;
     }
-    if (out[k].key_frame) key_entries.push_back(j), key_poses.push_back(key_pose_of(out[k].key_pose)), key_times.push_back(odom[k].time);
+    if (out[k].key_frame) key_entries.push_back(j), key_poses.push_back(key_pose_of(out[k].key_pose)), key_times.push_back(time_of(k));
   }
   // saveKeyFramesAndFactor's cloud copies (LM:1751-1764), device to device
   const int nk = (int)key_entries.size();
@@ -318,6 +341,8 @@ int lins_streams_map_step(lins_ctx* ctx, int n, const int32_t* streams, const li
   }
   return LINS_OK;
 }
+
+extern "C" {
 
 int lins_last_streams_map_ms(lins_ctx* ctx, float* associate_ms, float* finish_ms) {
   if (!ctx) return LINS_E_ARG;

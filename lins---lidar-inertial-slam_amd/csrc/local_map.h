@@ -8,6 +8,7 @@
 
 #include "../../include/lins_map.h"
 #include "../../include/lins_streams_map.h"
+#include "../../include/lins_streams_slam.h"
 
 namespace lins {
 
@@ -105,9 +106,25 @@ int pose_graph_apply_check(lins_ctx* ctx, int n, const int32_t* slots, const int
 // lins_map_capi.hip: scan-to-map over the last local-map build (n entries, as LINS_MAP_LOCAL) between the two pose
 // kernels of map_pose_kernels.hip — entry k works on d_poses[d_entries[k].stream]; h_out receives the n result records
 // (pinned or pageable), one synchronisation.  ev: four events, recorded around the associate and the finish kernel.
+// d_odom: null — transformSum is each entry's uploaded one —, or the resident records of lins_streams_odometry, indexed
+// by stream, which the two pose kernels then read it from.
 struct MapPoseEntry;  // lins_records.h
 struct MapPoseRec;
 int scan2map_local_resident(lins_ctx* ctx, int n, const MapPoseEntry* d_entries, MapPoseRec* d_poses, lins_map_step_result* d_out,
-                            lins_map_step_result* h_out, hipEvent_t* ev);
+                            lins_map_step_result* h_out, hipEvent_t* ev, const lins_stream_odom* d_odom = nullptr);
+
+// lins_streams_map_capi.hip: the body lins_streams_map_step and lins_streams_map_step_resident share.  An entry's
+// transformSum, time and IMU angles come either from the caller's rows (odom) or — odom null — from the resident records
+// (d_odom on the device, h_odom their host copy: an entry whose record is not valid gets LINS_E_INPUT and is left out of
+// the batch), time[k] and imu[k] (imu may be null: no entry has IMU angles).
+struct MapStepIn {
+  const lins_map_odom* odom;
+  const lins_stream_odom *d_odom, *h_odom;
+  const double* time;
+  const lins_slam_imu* imu;
+};
+int streams_map_step_run(lins_ctx* ctx, int n, const int32_t* streams, const MapStepIn& in, lins_map_step_result* out);
+// the resident map poses (null before lins_streams_map_init), for the fusion kernel
+const MapPoseRec* streams_map_poses(lins_ctx* ctx);
 
 }  // namespace lins

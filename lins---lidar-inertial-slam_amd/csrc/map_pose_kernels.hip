@@ -2,7 +2,8 @@
 // "Mapping node's step"; scalar text: map_pose_math.h).
 //
 // map_associate_kernel     transformAssociateToMap (LM:411-536): per entry, from the resident transformBefMapped /
-//                          transformAftMapped of the entry's stream and the uploaded transformSum, transformTobeMapped —
+//                          transformAftMapped of the entry's stream and transformSum — the entry's uploaded one, or with
+//                          `odom` the resident record's of the entry's stream (odom_kernels.hip) —, transformTobeMapped —
 //                          into the pose record, into the step's result record (tobe_start) and into the scan-to-map
 //                          result record the rounds start from (transform; counters zeroed).
 // map_pose_finish_kernel   behind the last round: transformUpdate's tail (LM:567-576) where the precondition of LM:1636
@@ -27,16 +28,17 @@ constexpr int kPoseThreads = 64;
 
 __global__ __launch_bounds__(kPoseThreads) void map_associate_kernel(int n, const MapPoseEntry* __restrict__ entries, const MapDev* __restrict__ probs,
                                                                      MapPoseRec* __restrict__ poses, lins_map_result* __restrict__ results,
-                                                                     lins_map_step_result* __restrict__ out) {
+                                                                     lins_map_step_result* __restrict__ out, const lins_stream_odom* __restrict__ odom) {
   const int k = blockIdx.x * kPoseThreads + threadIdx.x;
   if (k < n) {
     const MapPoseEntry e = entries[k];
     const int flag = probs ? probs[k].pad : 0;
     MapPoseRec* rec = poses + e.stream;
-    float bef[6], aft[6], tobe[6];
+    float bef[6], aft[6], sum[6], tobe[6];
+    const float* src = odom ? odom[e.stream].transform_sum : e.sum;
 #pragma unroll
-    for (int i = 0; i < 6; ++i) bef[i] = rec->bef[i], aft[i] = rec->aft[i];
-    mp_associate(bef, aft, e.sum, tobe);
+    for (int i = 0; i < 6; ++i) bef[i] = rec->bef[i], aft[i] = rec->aft[i], sum[i] = src[i];
+    mp_associate(bef, aft, sum, tobe);
 #pragma unroll
     for (int i = 0; i < 6; ++i) out[k].tobe_start[i] = tobe[i];
     if (flag >= 0) {
@@ -55,10 +57,14 @@ __global__ __launch_bounds__(kPoseThreads) void map_associate_kernel(int n, cons
 
 __global__ __launch_bounds__(kPoseThreads) void map_pose_finish_kernel(int n, const MapPoseEntry* __restrict__ entries, const MapDev* __restrict__ probs,
                                                                        MapPoseRec* __restrict__ poses, const lins_map_result* __restrict__ results,
-                                                                       lins_map_step_result* __restrict__ out) {
+                                                                       lins_map_step_result* __restrict__ out, const lins_stream_odom* __restrict__ odom) {
   const int k = blockIdx.x * kPoseThreads + threadIdx.x;
   if (k < n) {
     const MapPoseEntry e = entries[k];
+    float sum[6];
+    const float* src = odom ? odom[e.stream].transform_sum : e.sum;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) sum[i] = src[i];
     const int flag = probs[k].pad;
     const lins_map_result r = results[k];
     lins_map_step_result o = out[k];  // (tobe_start is the associate kernel's)
@@ -74,7 +80,7 @@ __global__ __launch_bounds__(kPoseThreads) void map_pose_finish_kernel(int n, co
       o.status = LINS_OK;
 #pragma unroll
       for (int i = 0; i < 6; ++i) rec.tobe[i] = r.transform[i];
-      if (flag > 0) mp_transform_update(rec.tobe, e.has_imu, e.imu_roll, e.imu_pitch, e.sum, rec.bef, rec.aft);
+      if (flag > 0) mp_transform_update(rec.tobe, e.has_imu, e.imu_roll, e.imu_pitch, sum, rec.bef, rec.aft);
       float key[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       if (mp_key_rule(rec.prev, rec.aft, rec.n_frames > 0)) {
         mp_key_pose(rec.tobe, rec.aft, rec.last, &rec.n_frames, key);
@@ -101,14 +107,14 @@ __global__ __launch_bounds__(kPoseThreads) void map_pose_correct_kernel(int n, c
 }  // namespace
 
 void launch_map_associate(hipStream_t stream, int n, const MapPoseEntry* entries, const MapDev* probs, MapPoseRec* poses, lins_map_result* results,
-                          lins_map_step_result* out) {
+                          lins_map_step_result* out, const lins_stream_odom* odom) {
   hipLaunchKernelGGL(map_associate_kernel, dim3((n + kPoseThreads - 1) / kPoseThreads), dim3(kPoseThreads), 0, stream, n, entries, probs, poses,
-                     results, out);
+                     results, out, odom);
 }
 void launch_map_pose_finish(hipStream_t stream, int n, const MapPoseEntry* entries, const MapDev* probs, MapPoseRec* poses,
-                            const lins_map_result* results, lins_map_step_result* out) {
+                            const lins_map_result* results, lins_map_step_result* out, const lins_stream_odom* odom) {
   hipLaunchKernelGGL(map_pose_finish_kernel, dim3((n + kPoseThreads - 1) / kPoseThreads), dim3(kPoseThreads), 0, stream, n, entries, probs, poses,
-                     results, out);
+                     results, out, odom);
 }
 
 void launch_map_pose_correct(hipStream_t stream, int n, const MapPoseFix* fixes, MapPoseRec* poses) {

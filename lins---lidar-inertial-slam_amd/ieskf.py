@@ -39,6 +39,7 @@ EXPORTS = [
     "lins_last_local_map_stage_ms",
     "lins_map_associate_batch", "lins_streams_map_init", "lins_streams_map_get_pose", "lins_streams_map_set_pose",
     "lins_streams_map_step", "lins_last_streams_map_ms",
+    "lins_streams_odometry", "lins_streams_map_step_resident", "lins_streams_fuse", "lins_streams_slam_step",
     "lins_pose_graph_default_params", "lins_pose_graph_init", "lins_pose_graph_push", "lins_pose_graph_add_loop",
     "lins_pose_graph_solve", "lins_pose_graph_poses", "lins_pose_graph_apply", "lins_pose_graph_count",
     "lins_last_pose_graph_stats", "lins_pose_graph_apply_batch",
