@@ -66,35 +66,6 @@ void make_dev_params(const lins_params& p, int search, DevParams& d) {
   }
 }
 
-struct RangeFlags {  // which kernel families the scans of a range can take
-  bool lds_ok = true, mr_ok = true, lds3_ok = true;
-};
-
-// Which kernel family a batch runs.  "auto": one workgroup per CU is all a small batch can use — the 1024-thread kernel
-// gives each scan the shortest critical path; beyond that the multi-resident kernel keeps two scans per CU.
-// The 3-lane shape is the single-round kernel: query sets beyond its 336 slots (more than a VLP-16
-// front-end can emit) take the 1-lane shapes, whose several-rounds path is the tested one.
-// (`n_total`: the batch a range belongs to — "auto" picks the family by the batch, so that a scan's bits do not depend
-// on how the batch was cut; `fl`: what the scans to launch can take)
-struct Family {
-  int search;            // the requested mode after "auto" and the 3-lane fall-back
-  bool use_mr, use_lds;  // the batch kernel / the full-residency kernel; neither: the any-size kernel
-  int ran;               // what lins_last_search reports (a scan that does not fit LDS: global-memory grid)
-};
-Family pick_family(const lins_ctx* ctx, int n_total, const RangeFlags& fl) {
-  int s = ctx->dprm.search;
-  if (s == SEARCH_AUTO) s = n_total > ctx->n_cu ? (int)SEARCH_MR : (int)SEARCH_LDS3;
-  if (s == SEARCH_LDS3 && !fl.lds3_ok) s = SEARCH_LDS;
-  const bool want_lds = s >= SEARCH_LDS, want_mr = s == SEARCH_MR;
-  const bool use_mr = want_mr && fl.mr_ok, use_lds = want_lds && !want_mr && fl.lds_ok;
-  return Family{s, use_mr, use_lds, use_mr ? (int)SEARCH_MR : (use_lds ? s : (want_lds ? (int)SEARCH_BINNED : s))};
-}
-RangeFlags uploaded_flags(const lins_ctx* ctx) {
-  RangeFlags fl;
-  fl.lds_ok = ctx->lds_ok, fl.mr_ok = ctx->mr_ok, fl.lds3_ok = ctx->lds3_ok;
-  return fl;
-}
-
 // pass 1 (serial, cheap): argument checks and the arena layout of the whole batch
 int layout_batch(lins_ctx* ctx, int n, const lins_scan_pair* in, size_t* arena_used, size_t* slots_used, uint64_t* bytes_iter) {
   if (!ctx || !in || n < 0) return LINS_E_ARG;
@@ -174,19 +145,6 @@ int pack_one(lins_ctx* ctx, const lins_scan_pair* in, int s) {
   return 0;
 }
 
-// kernel eligibility of the packed scans [lo, hi)
-RangeFlags range_flags(const lins_ctx* ctx, int lo, int hi) {
-  RangeFlags fl;
-  for (int s = lo; s < hi; ++s) {
-    const ScanDesc& d = ctx->h_desc[s];
-    const bool grid = d.surf_sorted && d.corner_sorted;
-    if (!grid || d.n_surf_t + d.n_corner_t > lds_np_cap()) fl.lds_ok = false;
-    if (!grid || d.n_surf_t + d.n_corner_t > lds_mr_np_cap()) fl.mr_ok = false;
-    if (d.n_surf_q + d.n_corner_q > 336) fl.lds3_ok = false;  // (16 waves x 21 query slots = the VLP-16 caps, 144 flat + 192 sharp)
-  }
-  return fl;
-}
-
 // search index of scans [lo, lo + cnt) of the uploaded descriptors, on the context's stream (grid kernels only: scans
 // that cannot take them run the any-size kernel, which bins for itself)
 int build_index_range(lins_ctx* ctx, int lo, int cnt, const RangeFlags& fl) {
@@ -235,7 +193,7 @@ int split_prepare(lins_ctx* ctx) {
 
 void set_batch_state(lins_ctx* ctx, int n, const RangeFlags& fl, size_t slots, uint64_t bytes) {
   ctx->n_uploaded = n;
-  ctx->lds_ok = fl.lds_ok, ctx->mr_ok = fl.mr_ok, ctx->lds3_ok = fl.lds3_ok;
+  ctx->fl = fl;
   ctx->slots_uploaded = slots;
   ctx->ran = false;
   ctx->bytes_per_iter = bytes;
@@ -261,7 +219,7 @@ int upload(lins_ctx* ctx, int n, const lins_scan_pair* in, bool wait = true) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if ((rc = parallel_scans(n, [&](int s) { return pack_one(ctx, in, s); }))) return rc;
   tr.mark("upload: validate + pack");
-  const RangeFlags fl = range_flags(ctx, 0, n);
+  const RangeFlags fl = range_flags(ctx->h_desc, n);
   tr.mark("upload: range flags");
   if ((rc = h2d_range(ctx, 0, n, off, ctx->stream))) return rc;
   tr.mark("upload: copies queued");
@@ -284,28 +242,15 @@ int upload(lins_ctx* ctx, int n, const lins_scan_pair* in, bool wait = true) {
   return LINS_OK;
 }
 
-// The update kernels of scans [lo, lo + cnt) of the uploaded batch on `st`, by the family picked for them (no events, no state
-// besides the launch number).  `order` / `relay`: launch order and several-part updates of the batch kernel (null: index
-// order, whole updates); `poses` / `scan_id_base`: of scan 0 of the batch.
-void run_family(lins_ctx* ctx, const Family& fam, hipStream_t st, int lo, int cnt, const int* order, const RelayArgs* relay,
-                   lins_pose_record* poses, int32_t scan_id_base, long long* prof) {
-  const ScanDesc* desc = ctx->d_desc + lo;
-  const double *st_in = ctx->d_state_in + (size_t)lo * 19, *cov_in = ctx->d_cov_in + (size_t)lo * 324;
-  double *st_out = ctx->d_state_out + (size_t)lo * 19, *cov_out = ctx->d_cov_out + (size_t)lo * 324, *a6 = ctx->d_a6 + (size_t)lo * 21;
-  OutRec* out = ctx->d_out + lo;
-  lins_pose_record* ps = poses ? poses + lo : nullptr;
-  if (fam.use_mr) {
-    launch_lds_mr(st, cnt, ctx->dprm, desc, order, ctx->d_arena, ctx->d_gsorted, ctx->d_gridtab + lo, st_in, cov_in, st_out, a6, cov_out, out, ctx->d_idx, ps,
-                  scan_id_base + lo, prof, relay, ctx->d_walk_cache, next_run_gen(ctx), ctx->d_relay_lane + (size_t)lo * kRelayLaneInts);
-  } else if (fam.use_lds) {
-    launch_lds(st, cnt, ctx->dprm, fam.search == SEARCH_LDS3 ? 3 : 1, desc, ctx->d_arena, ctx->d_gsorted, ctx->d_gridtab + lo, st_in, cov_in, st_out, a6, cov_out, out,
-               ctx->d_idx, ps, scan_id_base + lo, prof, ctx->d_relay_lane + (size_t)lo * kRelayLaneInts);  // (the Joseph update is the kernels' epilogue)
-  } else {
-    DevParams dp = ctx->dprm;
-    dp.search = fam.ran;  // a scan does not fit LDS: global-memory grid
-    launch_persistent(st, cnt, dp, desc, ctx->d_arena, st_in, cov_in, st_out, cov_out, a6, out, ctx->d_idx, ps,
-                      scan_id_base + lo, ctx->d_binned, prof);
-  }
+// where the update of scans [lo, ...) of the uploaded batch reads and writes; `poses` / `scan_id_base`: of scan 0 of the batch
+UpdateIo batch_io(const lins_ctx* ctx, int lo, lins_pose_record* poses, int32_t scan_id_base, long long* prof) {
+  UpdateIo io;
+  io.desc = ctx->d_desc + lo, io.arena = ctx->d_arena, io.gsorted = ctx->d_gsorted, io.gridtab = ctx->d_gridtab + lo, io.binned = ctx->d_binned;
+  io.state_in = ctx->d_state_in + (size_t)lo * 19, io.cov_in = ctx->d_cov_in + (size_t)lo * 324;
+  io.state_out = ctx->d_state_out + (size_t)lo * 19, io.cov_out = ctx->d_cov_out + (size_t)lo * 324, io.a6 = ctx->d_a6 + (size_t)lo * 21;
+  io.out = ctx->d_out + lo, io.relay_lane = ctx->d_relay_lane + (size_t)lo * kRelayLaneInts;
+  io.poses = poses ? poses + lo : nullptr, io.scan_id_base = scan_id_base + lo, io.prof = prof;
+  return io;
 }
 
 // The kernels of scans [lo, lo + cnt) of the uploaded batch on the context's stream (no events, no state)
@@ -314,7 +259,7 @@ int run_range(lins_ctx* ctx, int lo, int cnt, int n_total, const RangeFlags& fl,
   if (!st) st = ctx->stream;
   const Family fam = pick_family(ctx, n_total, fl);
   ctx->last_search = fam.ran;
-  run_family(ctx, fam, st, lo, cnt, nullptr, nullptr, poses, scan_id_base, nullptr);
+  run_family(ctx, fam, st, batch_io(ctx, lo, poses, scan_id_base, nullptr), cnt, nullptr, nullptr);
   HIP_TRY(ctx, hipGetLastError());
   return LINS_OK;
 }
@@ -360,7 +305,51 @@ int pipe_join(lins_ctx* ctx) {
   return LINS_OK;
 }
 
-int effective_search(const lins_ctx* ctx, int n) { return pick_family(ctx, n, uploaded_flags(ctx)).search; }
+// Which kernel family a batch runs.  "auto": one workgroup per CU is all a small batch can use — the 1024-thread kernel
+// gives each scan the shortest critical path; beyond that the multi-resident kernel keeps two scans per CU.
+// The 3-lane shape is the single-round kernel: query sets beyond its kLds3QueryMax slots (more than a VLP-16
+// front-end can emit) take the 1-lane shapes, whose several-rounds path is the tested one.
+// (`n_total`: the batch a range belongs to — "auto" picks the family by the batch, so that a scan's bits do not depend
+// on how the batch was cut; `fl`: what the scans to launch can take)
+Family pick_family(const lins_ctx* ctx, int n_total, const RangeFlags& fl) {
+  int s = ctx->dprm.search;
+  if (s == SEARCH_AUTO) s = n_total > ctx->n_cu ? (int)SEARCH_MR : (int)SEARCH_LDS3;
+  if (s == SEARCH_LDS3 && !fl.lds3_ok) s = SEARCH_LDS;
+  const bool want_lds = s >= SEARCH_LDS, want_mr = s == SEARCH_MR;
+  const bool use_mr = want_mr && fl.mr_ok, use_lds = want_lds && !want_mr && fl.lds_ok;
+  return Family{s, use_mr, use_lds, use_mr ? (int)SEARCH_MR : (use_lds ? s : (want_lds ? (int)SEARCH_BINNED : s))};
+}
+
+// kernel eligibility of the n scans the (host) descriptors describe
+RangeFlags range_flags(const ScanDesc* desc, int n) {
+  RangeFlags fl{true, true, true};
+  for (int s = 0; s < n; ++s) {
+    const ScanDesc& d = desc[s];
+    const bool grid = d.surf_sorted && d.corner_sorted;
+    if (!grid || d.n_surf_t + d.n_corner_t > lds_np_cap()) fl.lds_ok = false;
+    if (!grid || d.n_surf_t + d.n_corner_t > lds_mr_np_cap()) fl.mr_ok = false;
+    if (d.n_surf_q + d.n_corner_q > kLds3QueryMax) fl.lds3_ok = false;
+  }
+  return fl;
+}
+
+// The update kernels of `cnt` scans on `st`, by the family picked for them, reading and writing where `io` says (no events, no
+// state besides the launch number): the one launch site of an update, for the batch calls and the streams step alike.
+// `order` / `relay`: launch order and several-part updates of the batch kernel (null: index order, whole updates).
+void run_family(lins_ctx* ctx, const Family& fam, hipStream_t st, const UpdateIo& io, int cnt, const int* order, const RelayArgs* relay) {
+  if (fam.use_mr) {
+    launch_lds_mr(st, cnt, ctx->dprm, io.desc, order, io.arena, io.gsorted, io.gridtab, io.state_in, io.cov_in, io.state_out, io.a6, io.cov_out, io.out, ctx->d_idx,
+                  io.poses, io.scan_id_base, io.prof, relay, ctx->d_walk_cache, next_run_gen(ctx), io.relay_lane);
+  } else if (fam.use_lds) {
+    launch_lds(st, cnt, ctx->dprm, fam.search == SEARCH_LDS3 ? 3 : 1, io.desc, io.arena, io.gsorted, io.gridtab, io.state_in, io.cov_in, io.state_out, io.a6, io.cov_out,
+               io.out, ctx->d_idx, io.poses, io.scan_id_base, io.prof, io.relay_lane);  // (the Joseph update is the kernels' epilogue)
+  } else {
+    DevParams dp = ctx->dprm;
+    dp.search = fam.ran;  // a scan does not fit LDS: global-memory grid
+    launch_persistent(st, cnt, dp, io.desc, io.arena, io.state_in, io.cov_in, io.state_out, io.cov_out, io.a6, io.out, ctx->d_idx, io.poses, io.scan_id_base,
+                      io.binned, io.prof);
+  }
+}
 
 // Launch order of a batch on the multi-resident kernel: 1024 workgroups on 512 slots is two "rounds", and the dispatcher
 // hands workgroups out in index order — so the launch ends when the slowest pairing of an early and a late workgroup
@@ -704,7 +693,7 @@ int lins_batch_run(lins_ctx* ctx, void* d_poses, int32_t scan_id_base) {
   if (q.on) q.run_split[set] = false;
   const int h = (int)(ctx->hist_n % lins_ctx::kHist);
   HIP_TRY(ctx, hipEventRecord(ctx->hist0[h], ctx->stream));
-  const RangeFlags fl = uploaded_flags(ctx);
+  const RangeFlags& fl = ctx->fl;
   const Family fam = pick_family(ctx, ctx->n_uploaded, fl);
   const bool use_mr = fam.use_mr;
   ctx->last_search = fam.ran;
@@ -771,8 +760,8 @@ int lins_batch_run(lins_ctx* ctx, void* d_poses, int32_t scan_id_base) {
     if (q.on) q.run_split[set] = true, q.h_of[set] = h;  // (pipelined gather mode: the pose records of this run are complete when BOTH queues are through)
   } else {
     ctx->split_dirty = true;  // (a launch on the context's stream the second queue is not ordered behind)
-    run_family(ctx, fam, ctx->stream, 0, ctx->n_uploaded, relay ? ctx->d_order + ctx->max_batch : (ctx->use_order ? ctx->d_order : nullptr),
-                  relay ? &ra : nullptr, (lins_pose_record*)d_poses, scan_id_base, ctx->d_prof);
+    run_family(ctx, fam, ctx->stream, batch_io(ctx, 0, (lins_pose_record*)d_poses, scan_id_base, ctx->d_prof), ctx->n_uploaded,
+               relay ? ctx->d_order + ctx->max_batch : (ctx->use_order ? ctx->d_order : nullptr), relay ? &ra : nullptr);
     HIP_TRY(ctx, hipEventRecord(ctx->hist1[h], ctx->stream));
     if (q.on) q.h_of[set] = h;  // (the pose records of this run are complete at hist1[h])
     // (The Joseph update, SE:594-598, is the update kernel's epilogue since round 3: ieskf_lds_impl.h joseph_epilogue.
@@ -994,12 +983,12 @@ int lins_ieskf_update_batch(lins_ctx* ctx, int n, const lins_scan_pair* in, lins
 
   // (kernel family per CHUNK: a scan that cannot take the grid kernels sends its own chunk of 256, not the whole batch,
   // to the any-size kernel — every family returns the same results, so a scan's bits do not depend on the cut)
-  RangeFlags all;
+  RangeFlags all{true, true, true};
   rc = pack_pipelined(
       n, kChunk, [&](int s) { return pack_one(ctx, in, s); },
       [&](int lo, int hi) -> int {
         if (trace) std::fprintf(stderr, "scans %d..%d packed at %.3f ms\n", lo, hi, now_ms());
-        const RangeFlags fl = range_flags(ctx, lo, hi);
+        const RangeFlags fl = range_flags(ctx->h_desc + lo, hi - lo);
         const size_t arena_end = hi < n ? (size_t)ctx->h_desc[hi].off_surf_q : arena_used;
         int r = h2d_range(ctx, lo, hi, arena_end, ctx->copy_stream);
         if (r) return r;
@@ -1049,7 +1038,7 @@ int lins_icp_update_batch(lins_ctx* ctx, int n, const lins_scan_pair* in, lins_r
   if (rc) return rc;
   ctx->n_uploaded = 0;  // not an IESKF batch
   if (n == 0) return LINS_OK;
-  if (!ctx->mr_ok) return LINS_E_UNSUPPORTED;
+  if (!ctx->fl.mr_ok) return LINS_E_UNSUPPORTED;
   if (ctx->prm.icp_freq != 1) {
     // stored triplets are reused between searches: a scan starts with empty ones, as the oracle does (the
     // reference's arrays keep whatever the previous scan left, SE:206-211), and the deferred corner commit
@@ -1085,7 +1074,7 @@ static int run_pass(lins_ctx* ctx, const lins_scan_pair* in, const double* lin_s
   if (rc) return rc;
   ctx->n_uploaded = 0;  // the single-pass calls do not leave a runnable batch behind
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_lin, lin_state, 19 * 8, hipMemcpyHostToDevice, ctx->stream));
-  const Family fam = pick_family(ctx, 1, uploaded_flags(ctx));
+  const Family fam = pick_family(ctx, 1, ctx->fl);
   if (fam.use_mr) {
     launch_lds_mr_pass(ctx->stream, 1, ctx->dprm, ctx->d_desc, ctx->d_arena, ctx->d_gsorted, ctx->d_gridtab, ctx->d_lin,
                        ctx->d_state_in, iter, ctx->d_idx, dump ? ctx->d_dump : nullptr, sums ? ctx->d_sums : nullptr,

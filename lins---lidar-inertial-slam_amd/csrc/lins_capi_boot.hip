@@ -1,6 +1,6 @@
 // lins_capi_boot.hip — the streams' state machine in the C ABI (include/lins_streams_filter.h: lins_streams_machine_init,
 // lins_streams_process*, ...): the reference's status_ per stream and the two-scan bootstrap (SE:331-425) around the step of
-// lins_capi_frontend.hip.  Kernels: boot_kernels.hip; the bootstrap's ICP is the device ICP of the divergence fallback
+// lins_capi_streams.hip.  Kernels: boot_kernels.hip; the bootstrap's ICP is the device ICP of the divergence fallback
 // (launch_lds_mr_icp), one launch over the compact list of the streams taking their second scan.
 #include "boot_math.h"
 #include "filter_init.h"
@@ -207,7 +207,7 @@ static int process_impl(lins_ctx* ctx, const lins_segmented_scan* scans, const l
   if (int rc = resolve_imu_last(ctx, n_imu, imu, scan_imu, last, seen)) return rc;
   const StepImu si{n_imu, imu, global_state_out};
   const StepMachine sm{last.data(), scan_time, seen.data(), status_out};
-  const int rc = streams_step_impl(ctx, scans, raw, n_raw, nullptr, nullptr, scan_period, out, feature_counts, &si, &sm);
+  const int rc = streams_step_impl(ctx, StepScans{scans, raw, n_raw, scan_period}, StepPrior{nullptr, nullptr, &si, &sm}, out, feature_counts);
   if (rc == LINS_OK) t.b.imu_last = last, t.b.imu_seen = seen;
   return rc;
 }

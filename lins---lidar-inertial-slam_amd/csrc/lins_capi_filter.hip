@@ -1,5 +1,5 @@
 // lins_capi_filter.hip — the streams' device-resident filter in the C ABI (include/lins_streams_filter.h): loading and reading one
-// stream's filter, the IMU propagation between scans, and what lins_streams_step_imu(_raw) (lins_capi_frontend.hip)
+// stream's filter, the IMU propagation between scans, and what lins_streams_step_imu(_raw) (lins_capi_streams.hip)
 // queues around the update.  Kernels: filter_kernels.hip.
 #include "filter_math.h"
 #include "lins_ctx.h"

@@ -1,6 +1,6 @@
 // lins_ctx.h — the context of the C ABI (include/lins_ieskf.h) and what the C API files share: the struct itself, the
 // error macro, and the helpers more than one of lins_capi.hip / lins_capi_dist.hip / lins_capi_frontend.hip /
-// lins_capi_debug.hip needs.  (The scan-to-map files see a context through lins_ctx_priv.h only;
+// lins_capi_streams.hip / lins_capi_debug.hip needs.  (The scan-to-map files see a context through lins_ctx_priv.h only;
 // lins_streams_slam_capi.hip, which joins the streams' filter to their mapping step, includes this header.)
 #pragma once
 
@@ -43,6 +43,14 @@ typedef enum { ncclInt8 = 0, ncclChar = 0 } ncclDataType_t;
 #include "lins_records.h"
 
 using namespace lins;  // (a header of the C API files only)
+
+namespace lins {
+struct RangeFlags {  // which kernel families the scans of a range can take
+  bool lds_ok = false;   // every scan fits the LDS-resident kernel
+  bool mr_ok = false;    // ... the multi-resident (hybrid LDS / global) kernel
+  bool lds3_ok = false;  // ... has at most kLds3QueryMax queries (one round of the 3-lane shape)
+};
+}  // namespace lins
 
 struct lins_ctx {
   int device = 0;
@@ -109,7 +117,7 @@ struct lins_ctx {
   struct Frontend {
     int cap = 0;
     FeScan* d_scans = nullptr;
-    float4 *d_cloud = nullptr, *d_out = nullptr;  // d_out: per scan [192 | 1920 | 384 | LINS_CLOUD_MAX]
+    float4 *d_cloud = nullptr, *d_out = nullptr;  // d_out: kFeStride points per scan
     float* d_range = nullptr;
     unsigned* d_col = nullptr;
     unsigned char* d_ground = nullptr;
@@ -207,11 +215,9 @@ struct lins_ctx {
   double* d_sums = nullptr;
   int* d_counts = nullptr;
   int n_uploaded = 0;
-  bool lds_ok = false;  // every uploaded scan fits the LDS-resident kernel
-  bool mr_ok = false;   // ... the multi-resident (hybrid LDS / global) kernel
+  RangeFlags fl;        // what the uploaded scans can take
   int n_cu = 256;       // compute units of the device ("auto": batches beyond this take the mr kernel)
   int last_search = -1; // kernel family the last batch actually ran
-  bool lds3_ok = false; // every uploaded scan has at most 336 queries (one round of the 3-lane shape)
   bool ran = false;
   uint64_t bytes_per_iter = 0;
   uint64_t total_iters = 0;
@@ -265,18 +271,50 @@ namespace lins {
 
 inline size_t align4(size_t n) { return (n + 3) & ~size_t(3); }
 
+// the front-end's default output buffer (lins_ctx::Frontend::d_out), points per scan: [sharp | less sharp | flat | less flat]
+constexpr long long kFeSharp = 192, kFeLessSharp = 1920, kFeFlat = 384, kFeLessFlat = LINS_CLOUD_MAX;
+constexpr long long kFeStride = kFeSharp + kFeLessSharp + kFeFlat + kFeLessFlat;
+// queries of a scan the 3-lane shape of the full-residency kernel takes: one round, 16 waves x 21 query slots = the
+// VLP-16 caps (144 flat + 192 sharp)
+constexpr int kLds3QueryMax = 336;
+
 // ---- lins_capi.hip
 int split_join(lins_ctx* ctx);  // the context's stream behind the second launch queue
 int pipe_join(lins_ctx* ctx);   // ... and behind the gather stream of the pipelined mode
-int effective_search(const lins_ctx* ctx, int n);  // the search mode a batch of n scans runs ("auto" and the 3-lane fall-back applied)
+struct Family {
+  int search;            // the requested mode after "auto" and the 3-lane fall-back
+  bool use_mr, use_lds;  // the batch kernel / the full-residency kernel; neither: the any-size kernel
+  int ran;               // what lins_last_search reports (a scan that does not fit LDS: global-memory grid)
+};
+RangeFlags range_flags(const ScanDesc* desc, int n);
+Family pick_family(const lins_ctx* ctx, int n_total, const RangeFlags& fl);
+// where an update launch reads and writes: the uploaded batch's buffers (lins_capi.hip batch_io) or the streams' (lins_capi_streams.hip)
+struct UpdateIo {
+  const ScanDesc* desc;
+  const float4 *arena, *gsorted;  // the clouds and their grid-sorted copy (tables: gridtab)
+  const GridTables* gridtab;
+  float4* binned;  // the any-size kernel's (ring x column)-sorted scratch
+  const double *state_in, *cov_in;
+  double *state_out, *cov_out, *a6;
+  OutRec* out;
+  int* relay_lane;
+  lins_pose_record* poses;  // null, or the pose record of the first scan launched (its scan id: scan_id_base)
+  int32_t scan_id_base;
+  long long* prof;
+};
+void run_family(lins_ctx* ctx, const Family& fam, hipStream_t st, const UpdateIo& io, int cnt, const int* order, const RelayArgs* relay);
 void launch_order(lins_ctx* ctx, int n);
 int next_run_gen(lins_ctx* ctx);
 int relay_prepare(lins_ctx* ctx, int n, bool ordered, RelayArgs& ra);
 int relay_check(lins_ctx* ctx);
-// ---- lins_capi_dist.hip / lins_capi_frontend.hip: what lins_destroy frees
+// ---- lins_capi_dist.hip / lins_capi_frontend.hip / lins_capi_streams.hip: what lins_destroy frees
 void rccl_free(lins_ctx* ctx);
 void fe_free(lins_ctx* ctx);
 void streams_free(lins_ctx* ctx);
+// ---- lins_capi_frontend.hip: the stages in front of the update, as the streams step calls them (described there)
+int fe_run(lins_ctx* ctx, int n, const lins_segmented_scan* in, double scan_period, float4* out_base, const long long (*offs)[4], std::vector<int>& counts);
+int fe_launch(lins_ctx* ctx, int n, double scan_period, float4* out_base, std::vector<int>& counts, uint64_t bytes);
+int sg_run(lins_ctx* ctx, int n, const lins_point* const* raw, const int32_t* n_raw, const long long (*offs)[4], float4* outl = nullptr, const int* o_slots = nullptr);
 // ---- lins_capi_filter.hip
 void streams_filter_free(lins_ctx* ctx);
 int streams_filter_alloc(lins_ctx* ctx);
@@ -287,7 +325,7 @@ int streams_filter_predict_queue(lins_ctx* ctx, const int32_t* n_imu, const doub
 // queue the finish kernel (mode per stream as launch_filter_finish) behind the update
 int streams_filter_finish_queue(lins_ctx* ctx, const int* mode);
 
-// ---- lins_capi_boot.hip: the streams' state machine around the step of lins_capi_frontend.hip
+// ---- lins_capi_streams.hip: the step every lins_streams_step* / lins_streams_process* call ends in
 // what lins_streams_process* adds to a step: imu_last_ (n x 6, resolved by the caller) and time of each scan
 struct StepMachine {
   const double* scan_imu;
@@ -300,9 +338,19 @@ struct StepImu {  // the prior comes from the streams' device filter (lins_strea
   const double* const* rows;
   double* global_state_out;
 };
-int streams_step_impl(lins_ctx* ctx, const lins_segmented_scan* scans, const lins_point* const* raw, const int32_t* n_raw,
-                      const double* prior_state, const double* prior_cov, double scan_period, lins_result* out,
-                      int32_t* feature_counts, const StepImu* imu = nullptr, const StepMachine* mach = nullptr);
+struct StepScans {  // this call's scans: segmented by the caller, or (segmented == null) raw clouds
+  const lins_segmented_scan* segmented;
+  const lins_point* const* raw;
+  const int32_t* n_raw;
+  double scan_period;
+};
+struct StepPrior {  // the caller's priors (n x 19, n x 324), or (imu != null) the device filter's; mach (with imu): the state machine's step
+  const double *state, *cov;
+  const StepImu* imu;
+  const StepMachine* mach;
+};
+int streams_step_impl(lins_ctx* ctx, const StepScans& scans, const StepPrior& prior, lins_result* out, int32_t* feature_counts);
+// ---- lins_capi_boot.hip: the streams' state machine around that step
 void streams_boot_free(lins_ctx* ctx);
 void streams_slam_free(lins_ctx* ctx);  // lins_streams_slam_capi.hip
 // argument check of a machine-mode call's IMU rows (as streams_filter_check, without the need of a loaded filter)

@@ -14,7 +14,7 @@ void** ctx_map_slot(lins_ctx* ctx, void (*free_fn)(void*));       // attachment 
 // the context's event pair for kernel timing
 void ctx_events(lins_ctx* ctx, hipEvent_t* a, hipEvent_t* b);
 const lins_params* ctx_params(const lins_ctx* ctx);  // the parameters the context was created with
-// lins_capi_frontend.hip: the clouds of a stream's last step the mapping node reads, where they lie on the device, in the
+// lins_capi_streams.hip: the clouds of a stream's last step the mapping node reads, where they lie on the device, in the
 // sensor's axes (0 re-projected less sharp, 1 re-projected less flat, 2 outlier).  LINS_E_ARG for a bad stream index,
 // LINS_E_STATE before the stream's first step or on a failed streams context.
 struct StreamMapClouds {

@@ -68,7 +68,7 @@ def main():
     data = [bc.load(host, s, args.sweeps) for s in bc.SEQS]
     for ns in args.streams:
         seq = [data[i % len(data)] for i in range(ns)]
-        per_sweep = dict(one=[], chain=[], chain_poses=[])
+        per_sweep = dict(one=[], one_dev=[], chain=[], chain_poses=[])
         same = total = 0
         for r in range(args.runs):
             with ieskf.IeskfContext(pkg.default_params(num_iter=8), max_batch=ns, max_targets=16 * 1800) as a, \
@@ -78,7 +78,7 @@ def main():
                     c.streams_machine_init()
                     c.local_map_init(ns, args.window, 16384)
                     sm.init(c, ns, 0.0)  # (every sweep passes the interval gate: every sweep has mapping work)
-                t_one = t_chain = t_poses = 0.0
+                t_one = t_dev = t_chain = t_poses = 0.0
                 for k in range(args.sweeps):
                     raws = [np.ascontiguousarray(s["raws"][k], np.float32).reshape(-1, 4) for s in seq]
                     rptr = (pp * ns)(*[r.ctypes.data_as(pp) for r in raws])
@@ -140,14 +140,17 @@ def main():
                     total += 1
                     if k >= 1:
                         t_one += d
+                        t_dev += sum(a.streams_stats())  # (front-end + update + re-projection of the one call's streams step)
                         t_chain += e
                         t_poses += gp
                 per_sweep["one"].append(t_one * 1e3 / (args.sweeps - 1))
+                per_sweep["one_dev"].append(t_dev / (args.sweeps - 1))
                 per_sweep["chain"].append(t_chain * 1e3 / (args.sweeps - 1))
                 per_sweep["chain_poses"].append((t_chain + t_poses) * 1e3 / (args.sweeps - 1))
         say(f"{ns} streams, {args.sweeps} sweeps from INIT (sequences 11 / 12 / 13 in turn), window {args.window}; status and fused pose equal bit for bit "
             f"in {same} of {total} sweeps")
-        for name, v in (("lins_streams_slam_step, inside the call        ", per_sweep["one"]), ("the chain, inside its library calls            ", per_sweep["chain"]),
+        for name, v in (("lins_streams_slam_step, inside the call        ", per_sweep["one"]), ("  its streams step on the device (HIP events)  ", per_sweep["one_dev"]),
+                        ("the chain, inside its library calls            ", per_sweep["chain"]),
                         ("the chain, its pose downloads counted too      ", per_sweep["chain_poses"])):
             say(f"  {name}: median {statistics.median(v):9.4f} ms per sweep   min {min(v):9.4f}   max {max(v):9.4f}   ({len(v)} runs from fresh state)")
         m_one, m_chain = statistics.median(per_sweep["one"]), statistics.median(per_sweep["chain"])

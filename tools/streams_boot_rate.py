@@ -64,7 +64,7 @@ def main():
     for ns in args.streams:
         of = [seqs[i % 3] for i in range(ns)]
         pairs = [pairs3[i % 3] for i in range(ns)]
-        w = dict(pre=[], icp=[], fin=[], wall=[], one=[], batch=[])
+        w = dict(pre=[], icp=[], fin=[], wall=[], dev=[], one=[], batch=[])
         with ieskf.IeskfContext(prm, max_batch=ns, max_targets=16 * 1800) as ctx:
             ctx.streams_init(ns)
             for r in range(total):
@@ -76,7 +76,7 @@ def main():
                 assert all(v == defs.STREAM_RUNNING for v in status)
                 pm, im, fm = ctx.streams_boot_stats()
                 if r >= args.warmup:
-                    w["pre"].append(pm), w["icp"].append(im), w["fin"].append(fm), w["wall"].append((t1 - t0) * 1e3)
+                    w["pre"].append(pm), w["icp"].append(im), w["fin"].append(fm), w["wall"].append((t1 - t0) * 1e3), w["dev"].append(sum(ctx.streams_stats()))
             rounds = [r.iters for r in res[:3]]
         with ieskf.IeskfContext(prm, max_batch=ns, max_targets=16 * 1800) as ctx:
             for r in range(total):
@@ -93,6 +93,7 @@ def main():
         stat("index + start rows + ONE batched ICP launch (HIP events) ", w["icp"])
         stat("boot_finish_kernel (HIP events)                          ", w["fin"])
         stat("lins_streams_process_raw, wall (front-end, ... included) ", w["wall"])
+        stat("  of which front-end + update + re-projection (HIP events)", w["dev"])
         stat("before: lins_icp_update_batch stream by stream, wall     ", w["one"])
         stat("before: lins_icp_update_batch as one batch, wall         ", w["batch"])
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

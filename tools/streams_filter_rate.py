@@ -105,16 +105,17 @@ def main():
             f0 = new_filter()
             for i in range(n):
                 ctx.streams_filter_set(i, f0, g0)
-            t_all, t_pred, t_fin = [], [], []
+            t_all, t_pred, t_fin, t_dev = [], [], [], []
             for k in range(total):
                 t0 = time.perf_counter()
                 res, _, _ = ctx.streams_step_imu_raw([raws[k + 1]] * n, [rows[k + 1]] * n)
                 t_all.append(time.perf_counter() - t0)
                 pm, fm = ctx.streams_filter_stats()
-                t_pred.append(pm * 1e-3), t_fin.append(fm * 1e-3)
+                t_pred.append(pm * 1e-3), t_fin.append(fm * 1e-3), t_dev.append(sum(ctx.streams_stats()) * 1e-3)
             report("(b) device filter, whole step    ", t_all)
             report("    predict kernel (HIP events)  ", t_pred)
             report("    finish kernel (HIP events)   ", t_fin)
+            report("    fe + update + re-projection  ", t_dev)
             print(f"    PCIe per step: up {n * (raw_bytes + 40 * 7 * 8)} B, down {n * (res_bytes + 19 * 8)} B")
             print(f"    last step: iterations {sorted(set(r.iters for r in res))}, diverged {sum(1 for r in res if r.diverged)}")
 
