@@ -268,6 +268,19 @@ int lins_host_find_loop(const lins_key_pose* poses, const double* times, int n, 
  * for a chosen frame outside the input contract (nothing written), else LINS_OK (the cloud's own status in info->status). */
 int lins_host_submap(const lins_keyframe* frames, int n_frames, const int32_t* ids, int n_ids, int clouds, float leaf,
                      int flags, lins_point* out, lins_submap_info* info);
+/* extractSurroundingKeyFrames with the loop closure off (LM:1247-1315; lins_streams_map_surround in lins_streams_map.h).
+ * The list rule (LM:1261-1308, host/keyframe_select.h surround_update — the text the step compiles too): entries of
+ * `list` (surroundingExistingKeyPosesID, n_list ids, room for cap) whose id is not among ds are erased, the survivors
+ * keep their order; then each ds[i], in order, is appended unless the list holds it already (an id ds names twice enters
+ * once).  An id of ds is taken as it is.  Returns the new length; LINS_E_CAPACITY (list untouched) when it would exceed
+ * cap. */
+int lins_host_surround_update(int32_t* list, int n_list, int cap, const int32_t* ds, int n_ds);
+/* CPU restatement of lins_local_map_build_surround for one entry, a composition of the two restatements above: the map
+ * clouds are lins_host_submap(list, CORNER, 0.2) and lins_host_submap(list, SURF | OUTLIER, 0.4), the four scan clouds
+ * lins_host_local_map's.  out / sizes: as lins_host_local_map (out[0], out[1]: room for the points the list's frames
+ * hold); sizes->frames = n_list.  LINS_E_ARG for an id outside [0, n_frames). */
+int lins_host_surround_map(const lins_keyframe* frames, int n_frames, const int32_t* list, int n_list,
+                           const lins_local_scan* scan, lins_point* const* out, lins_local_map_sizes* sizes);
 
 /* ---- the loop-closure ICP on the CPU (host/loop_icp.cpp) ---------------------
  * The restatement lins_loop_icp_batch / lins_loop_icp_correspondences are checked against (include/lins_map.h has the

@@ -143,6 +143,22 @@ int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_
  * LINS_E_STATE.  The input contract is checked on the device: an entry with a scan point that is not finite or beyond
  * 1e6 gets status LINS_E_INPUT and empty clouds (as a window cloud outside the contract), the call returns LINS_OK.   */
 int lins_local_map_build_streams(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* streams, lins_local_map_sizes* out);
+/* extractSurroundingKeyFrames with the loop closure off (LM:1247-1315): the build with its map side read from a list of
+ * frames of the key-frame archive (below; slot slots[k] of it) instead of the ring.  Entry k's corner map is
+ * VG0.2(corner of ids[k][0], corner of ids[k][1], ...), its surf map VG0.4(surf_i, outlier_i, ...) in list order
+ * (LM:1310-1314), each frame moved by its archive pose — the clouds lins_archive_assemble gives for the specs
+ * {ids, CORNER, leaf 0.2} and {ids, SURF | OUTLIER, leaf 0.4}, bit for bit.  The four scan clouds, sizes, boxes and
+ * per-entry status are lins_local_map_build's / _build_streams'; sizes.frames = n_ids[k]; n_ids[k] == 0 gives empty
+ * maps, as an empty ring does.  The ring is neither read nor changed, and lins_local_map_download, LINS_MAP_LOCAL,
+ * lins_local_map_push_scans and lins_archive_push_scans work on this build as on any other.  A map job of more tiles than
+ * the archive's scan chunk has its scans split over workgroups as in an assembly (lins_archive_set_scan_chunk applies).
+ * LINS_E_STATE without lins_local_map_init or lins_archive_init; LINS_E_ARG for a slot that is not one of both, or an id
+ * that is no frame of its slot; a refused call changes nothing.  Which frames to list is the caller's rule —
+ * lins_archive_select_radius and lins_host_surround_update (lins_host.h), or lins_streams_map_surround. */
+int lins_local_map_build_surround(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* const* ids, const int32_t* n_ids,
+                                  const lins_local_scan* scans, lins_local_map_sizes* out);
+int lins_local_map_build_surround_streams(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* const* ids, const int32_t* n_ids,
+                                          const int32_t* streams, lins_local_map_sizes* out);
 /* HIP-event time (ms) of the staging kernel of the last lins_local_map_build_streams (part of the build's kernel_ms;
  * 0 after lins_local_map_build) */
 int lins_last_local_map_stage_ms(lins_ctx* ctx, float* stage_ms);

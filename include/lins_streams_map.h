@@ -86,7 +86,8 @@ int lins_streams_map_set_pose(lins_ctx* ctx, int stream, const lins_map_pose_sta
  *   gate        odom[k].time - last_time >= process_interval (f64), else status LINS_MAP_STEP_SKIPPED, nothing changes;
  *               the other entries form the batch, last_time <- time
  *   associate   transformAssociateToMap on the device from the resident pose
- *   local map   lins_local_map_build_streams for the batch (entry <-> stream, slot = stream)
+ *   local map   lins_local_map_build_streams for the batch (entry <-> stream, slot = stream); with
+ *               lins_streams_map_surround on, the surrounding key frames of the archive instead of the ring
  *   scan2map    lins_scan2map_batch's rounds with LINS_MAP_LOCAL, started where the associate kernel left the transform
  *   finish      transformUpdate if the precondition of LM:1636 held, the key-frame rule, the key pose; one download
  *   key frames  lins_local_map_push_scans and lins_archive_push_scans for the entries with key_frame set, with
@@ -109,6 +110,25 @@ int lins_streams_map_step(lins_ctx* ctx, int n, const int32_t* streams, const li
  * Either way the step remembers currentRobotPosPoint per stream: transform[3..5] of its last entry with status LINS_OK
  * (LM:1655-1658), which LINS_LOOP_CENTRE_STREAM reads.                                                                */
 int lins_streams_map_loop(lins_ctx* ctx, int on);
+/* on != 0: later steps build each entry's local map from the surrounding key frames — the mapping node with
+ * loopClosureEnableFlag off (LM:1247-1315) — with radius (surroundingKeyframeSearchRadius, 50) and pose_leaf (1.0,
+ * LM:288).  The "local map" stage of an entry then is: the archive of the stream's slot empty (LM:1202) -> the list is
+ * empty; else ds = lins_archive_select_radius(slot, centre = the remembered currentRobotPosPoint (zero before the
+ * stream's first completed step, as allocateMemory leaves it), radius, pose_leaf), and the stream's list
+ * (surroundingExistingKeyPosesID) goes through lins_host_surround_update's rule; one
+ * lins_local_map_build_surround_streams call serves the batch.  A selection whose box has more than 2^31 cells gives the
+ * entry status LINS_E_CAPACITY: it is left out of the batch, list and pose state as they were.  A build entry with a
+ * status keeps its list too.  Gate, associate, rounds, finish, the pushes to ring and archive and the result record are
+ * unchanged: the ring keeps being fed, so switching the mode off continues with the recent-frame map.
+ * One departure: the node keeps the transformed clouds of listed frames (surrounding*CloudKeyFrames); the step moves
+ * them anew from the archive's current poses.  In this mode the node never rewrites a key pose, so the bits are the
+ * same; after a caller's lins_archive_set_poses the next step uses the new poses.
+ * Off by default and again after lins_streams_map_init; switching on clears every list.  Needs lins_streams_map_init with
+ * an archive (LINS_E_STATE), and is exclusive with lins_streams_map_loop — the node's flag selects one of the two:
+ * whichever is asked for second gets LINS_E_STATE.  radius finite and >= 0, pose_leaf > 0 (LINS_E_ARG).                  */
+int lins_streams_map_surround(lins_ctx* ctx, int on, float radius, float pose_leaf);
+/* the stream's surroundingExistingKeyPosesID as the last step left it; returns the count, LINS_E_CAPACITY beyond cap   */
+int lins_streams_map_surround_list(lins_ctx* ctx, int stream, int32_t* ids, int cap);
 /* HIP-event times (ms) of the associate and finish kernels of the last step (0 when the step queued none)            */
 int lins_last_streams_map_ms(lins_ctx* ctx, float* associate_ms, float* finish_ms);
 

@@ -1,10 +1,12 @@
 // keyframe_archive.cpp — the key-frame archive's selection and assembly on the CPU (include/lins_host.h
-// lins_host_select_radius / _find_loop / _submap): the restatement lins_archive_assemble (archive_kernels.hip) is checked
+// lins_host_select_radius / _find_loop / _submap / _surround_update / _surround_map): the restatement lins_archive_assemble (archive_kernels.hip) is checked
 // against, bit for bit.
 //   publishGlobalMap    LM:984-1031   radius search + VoxelGrid of the key poses -> frames; corner, surf, outlier of each
 //                                     into the map frame (transformPointCloud, LM:654-686), VoxelGrid 0.4 m
 //   detectLoopClosure   LM:1043-1112  the candidate rule; latest corner + surf without (int)intensity < 0; the +-25 frames
 //                                     around the candidate, corner + surf, VoxelGrid 0.4 m
+//   extractSurroundingKeyFrames, loop closure off  LM:1247-1315  the list rule (keyframe_select.h surround_update); the
+//                                     map clouds are two submaps over the list, the scan clouds the local map's
 // The selection is host/keyframe_select.h (one definition for both libraries); transform and VoxelGrid are voxel_map.h.
 #include <vector>
 
@@ -79,5 +81,52 @@ extern "C" int lins_host_submap(const lins_keyframe* frames, int n_frames, const
   } else {
     for (int a = 0; a < 3; ++a) info->box_min[a] = 0, info->box_dim[a] = 1;
   }
+  return LINS_OK;
+}
+
+extern "C" int lins_host_surround_update(int32_t* list, int n_list, int cap, const int32_t* ds, int n_ds) {
+  if (n_list < 0 || cap < n_list || (n_list && !list) || n_ds < 0 || (n_ds && !ds)) return LINS_E_ARG;
+  std::vector<int> l(list, list + n_list);
+  lins_select::surround_update(l, std::vector<int>(ds, ds + n_ds));
+  if ((int)l.size() > cap) return LINS_E_CAPACITY;
+  if (!l.empty() && !list) return LINS_E_ARG;
+  for (size_t i = 0; i < l.size(); ++i) list[i] = l[i];
+  return (int)l.size();
+}
+
+extern "C" int lins_host_surround_map(const lins_keyframe* frames, int n_frames, const int32_t* list, int n_list,
+                                      const lins_local_scan* scan, lins_point* const* out, lins_local_map_sizes* sizes) {
+  if (n_frames < 0 || (n_frames && !frames) || n_list < 0 || (n_list && !list) || !scan || !out || !sizes) return LINS_E_ARG;
+  for (int i = 0; i < n_list; ++i)
+    if (list[i] < 0 || list[i] >= n_frames) return LINS_E_ARG;
+  // the two map clouds first (they refuse a frame outside the input contract before anything is written) ...
+  lins_submap_info info[2];
+  const int clouds[2] = {LINS_SUBMAP_CORNER, LINS_SUBMAP_SURF | LINS_SUBMAP_OUTLIER};
+  const float leaf[2] = {0.2f, 0.4f};
+  std::vector<lins_point> map[2];
+  for (int w = 0; w < 2; ++w) {
+    size_t room = 0;
+    for (int i = 0; i < n_list; ++i) {
+      const lins_keyframe& f = frames[list[i]];
+      if (f.n_corner < 0 || f.n_surf < 0 || f.n_outlier < 0) return LINS_E_INPUT;
+      room += w ? (size_t)f.n_surf + f.n_outlier : (size_t)f.n_corner;
+    }
+    map[w].resize(room + 1);
+    if (int rc = lins_host_submap(frames, n_frames, list, n_list, clouds[w], leaf[w], 0, map[w].data(), &info[w])) return rc;
+  }
+  // ... then the scan's four clouds: the local map over no frames
+  lins_local_map_sizes z;
+  if (int rc = lins_host_local_map(nullptr, 0, 1, scan, out, &z)) return rc;
+  z.frames = n_list;
+  for (int w = 0; w < 2; ++w)  // an entry's status as the build folds it: LINS_E_INPUT first, else the first one set
+    if (info[w].status == LINS_E_INPUT || (info[w].status && !z.status)) z.status = info[w].status;
+  for (int w = 0; w < 2; ++w) {
+    z.n[w] = z.status ? 0 : info[w].n;
+    if (z.n[w]) std::copy(map[w].begin(), map[w].begin() + z.n[w], out[w]);
+    for (int a = 0; a < 3; ++a) z.box_min[w][a] = z.n[w] ? info[w].box_min[a] : 0, z.box_dim[w][a] = z.n[w] ? info[w].box_dim[a] : 1;
+  }
+  if (z.status)
+    for (int c = 2; c < 6; ++c) z.n[c] = 0;
+  *sizes = z;
   return LINS_OK;
 }

@@ -56,6 +56,23 @@ inline int find_loop(const lins_key_pose* poses, const double* times, int n, con
   return -1;
 }
 
+// surroundingExistingKeyPosesID after one extractSurroundingKeyFrames with the loop closure off (LM:1261-1308), ds = the
+// frames select_radius chose: entries whose id is not among ds are erased in place (the survivors keep their order),
+// then each ds[i], in order, is appended unless the list — earlier appends included — holds it already.  An id of ds is
+// taken as it is (the truncated mean id of a voxel, which may name a frame outside the radius).
+inline void surround_update(std::vector<int>& list, const std::vector<int>& ds) {
+  for (int i = 0; i < (int)list.size(); ++i) {
+    bool existing = false;
+    for (size_t j = 0; j < ds.size() && !existing; ++j) existing = list[i] == ds[j];
+    if (!existing) list.erase(list.begin() + i), --i;
+  }
+  for (size_t i = 0; i < ds.size(); ++i) {
+    bool existing = false;
+    for (size_t j = 0; j < list.size() && !existing; ++j) existing = list[j] == ds[i];
+    if (!existing) list.push_back(ds[i]);
+  }
+}
+
 inline bool query_ok(const float centre[3], float radius) {
   return centre && std::isfinite(centre[0]) && std::isfinite(centre[1]) && std::isfinite(centre[2]) && std::isfinite(radius) && radius >= 0.f;
 }

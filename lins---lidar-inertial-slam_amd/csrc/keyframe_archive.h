@@ -7,6 +7,8 @@
 //   elements; chunk sums (one workgroup per chunk) -> exclusive scan of the job's chunk sums (one workgroup per job) ->
 //   each chunk re-scanned from its offset (one workgroup per chunk).  Integer sums: the same bits whatever the split.
 #pragma once
+#include <vector>
+
 #include "local_map.h"
 
 namespace lins {
@@ -40,5 +42,22 @@ struct ArchiveView {
   unsigned long long serial;  // counts the assemblies of the context: whose clouds these are
 };
 int archive_view(lins_ctx* ctx, ArchiveView* v);  // lins_archive_capi.hip
+
+// (host side) one stored key frame, and the store where the local map's surround build (lins_local_map_build_surround)
+// reads it: frame id of slot s is (*frames)[s][id], its clouds lie at d_arena + off.  LINS_E_STATE before lins_archive_init.
+struct ArFrame {
+  long long off;  // of the frame's block in the arena: corner, surf, outlier one after the other
+  int n[3];
+  lins_key_pose pose;
+  float t[9];  // ctRoll, stRoll, ctPitch, stPitch, ctYaw, stYaw, tInX, tInY, tInZ
+  double time;
+};
+struct ArchiveStore {
+  const float4* d_arena;
+  int n_slots;
+  int chunk;  // lins_archive_set_scan_chunk: a job of more tiles has its scans split
+  const std::vector<std::vector<ArFrame>>* frames;
+};
+int archive_store(lins_ctx* ctx, ArchiveStore* v);
 
 }  // namespace lins

@@ -23,14 +23,6 @@ using lins_hostmap::pose_ok;
 
 namespace {
 
-struct ArFrame {
-  long long off;  // of the frame's block in the arena: corner, surf, outlier one after the other
-  int n[3];
-  lins_key_pose pose;
-  float t[9];  // ctRoll, stRoll, ctPitch, stPitch, ctYaw, stYaw, tInX, tInY, tInZ
-  double time;
-};
-
 struct Archive {
   int n_slots = 0, max_frames = 0, chunk = kArScanChunk;
   long long max_points = 0, used = 0;
@@ -109,6 +101,12 @@ int archive_view(lins_ctx* ctx, ArchiveView* v) {
   if (!m->built) return LINS_E_STATE;
   v->d_out = m->d_out, v->n = (int)m->info.size(), v->off = m->off.data(), v->info = m->info.data(), v->filtered = m->filtered.data();
   v->serial = m->serial;
+  return LINS_OK;
+}
+int archive_store(lins_ctx* ctx, ArchiveStore* v) {
+  Archive* m = archive_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  v->d_arena = m->d_arena, v->n_slots = m->n_slots, v->chunk = m->chunk, v->frames = &m->frames;
   return LINS_OK;
 }
 }  // namespace lins

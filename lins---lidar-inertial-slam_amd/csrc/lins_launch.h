@@ -133,6 +133,10 @@ void launch_lm_stage_scans(hipStream_t s, int n_blocks, const LmScanSeg* segs, c
 // one stage: jobs [j0, j0 + n_jobs), tiles [0, n_tiles) of `tiles`
 void launch_lm_stage(hipStream_t s, int j0, int n_jobs, int n_tiles, const int2* tiles, const LmJob* jobs, LmState* states, float4* stage, unsigned* keys_a, unsigned* keys_b, int* vals_a, int* vals_b,
                      int* hist, int* tilecnt, int* starts, float4* out);
+// ... with the scans of its first n_split jobs split over many workgroups (launch_ar_scan below; chunks / splits: the
+// tables of keyframe_archive.h for those jobs, csum: one int per chunk).  n_split == 0: the launches of launch_lm_stage
+void launch_lm_stage_split(hipStream_t s, int j0, int n_split, int n_jobs, int n_tiles, const int2* tiles, const LmJob* jobs, LmState* states, float4* stage, unsigned* keys_a, unsigned* keys_b,
+                           int* vals_a, int* vals_b, int* hist, int* tilecnt, int* starts, float4* out, int chunk_tiles, int n_chunks, const ArChunk* chunks, const ArSplit* splits, int* csum);
 // the same kernels one by one (job kernels: jobs [j0, j0 + n_jobs); tile kernels: tiles [0, n_tiles) of `tiles`)
 void launch_lm_setup(hipStream_t s, int j0, int n_jobs, const LmJob* jobs, LmState* states);
 void launch_lm_keys(hipStream_t s, int n_tiles, const int2* tiles, const LmJob* jobs, const LmState* states, const float4* stage, unsigned* keys, int* vals);

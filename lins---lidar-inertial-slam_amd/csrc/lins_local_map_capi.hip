@@ -1,6 +1,7 @@
 // lins_local_map_capi.hip — C ABI of the mapping node's local map on the device (include/lins_map.h lins_local_map_*):
 // the key-frame rings, the packing of a build into the VoxelGrid jobs of local_map_kernels.hip, and the view scan-to-map
-// reads the built clouds through (LINS_MAP_LOCAL).  The rings hold the key frames in the sensor frame; the host keeps
+// reads the built clouds through (LINS_MAP_LOCAL).  A build's map side is the ring of the entry's slot, or — the
+// surround builds — a list of frames of the key-frame archive (keyframe_archive.h ArchiveStore).  The rings hold the key frames in the sensor frame; the host keeps
 // their counts, poses and trigonometry (std::cos / std::sin of float, once per pose, LM:612-624).
 #include <hip/hip_runtime.h>
 
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../include/lins_map.h"
+#include "keyframe_archive.h"
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
 #include "local_map.h"
@@ -33,11 +35,11 @@ struct LocalMap {
   // build arenas (grown, never shrunk)
   float4 *d_stage = nullptr, *d_out = nullptr;
   unsigned *d_ka = nullptr, *d_kb = nullptr;
-  int *d_va = nullptr, *d_vb = nullptr, *d_starts = nullptr, *d_hist = nullptr, *d_tilecnt = nullptr;
+  int *d_va = nullptr, *d_vb = nullptr, *d_starts = nullptr, *d_hist = nullptr, *d_tilecnt = nullptr, *d_csum = nullptr;
   char* d_tab = nullptr;
   float4* h_raw = nullptr;
   char *h_tab = nullptr, *h_states = nullptr;
-  size_t cap_stage = 0, cap_out = 0, cap_tiles = 0, cap_tab = 0, cap_raw = 0, cap_htab = 0, cap_hstates = 0;
+  size_t cap_stage = 0, cap_out = 0, cap_tiles = 0, cap_tab = 0, cap_raw = 0, cap_htab = 0, cap_hstates = 0, cap_csum = 0;
   // the last build
   bool built = false;
   std::vector<int> slots;
@@ -52,7 +54,7 @@ void local_free(void* p) {
   LocalMap* m = (LocalMap*)p;
   (void)hipFree(m->d_frames), (void)hipFree(m->d_stage), (void)hipFree(m->d_out), (void)hipFree(m->d_ka), (void)hipFree(m->d_kb);
   (void)hipFree(m->d_va), (void)hipFree(m->d_vb), (void)hipFree(m->d_starts), (void)hipFree(m->d_hist), (void)hipFree(m->d_tilecnt);
-  (void)hipFree(m->d_tab), (void)hipHostFree(m->h_raw), (void)hipHostFree(m->h_tab), (void)hipHostFree(m->h_states);
+  (void)hipFree(m->d_csum), (void)hipFree(m->d_tab), (void)hipHostFree(m->h_raw), (void)hipHostFree(m->h_tab), (void)hipHostFree(m->h_states);
   if (m->ev_stage) (void)hipEventDestroy(m->ev_stage);
   delete m;
 }
@@ -119,6 +121,14 @@ float4* frame_ptr(LocalMap* m, int slot, int idx) { return m->d_frames + ((size_
 
 size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
 
+// the map side of a build: the rings (ids null), or per entry the list ids[k][0 .. n_ids[k]) of frames of the archive
+// slot slots[k], in list order (ar: the store they lie in)
+struct MapSource {
+  const int32_t* const* ids = nullptr;
+  const int32_t* n_ids = nullptr;
+  ArchiveStore ar{};
+};
+
 }  // namespace
 
 namespace lins {
@@ -182,8 +192,11 @@ int lins_local_map_push(lins_ctx* ctx, int slot, const lins_keyframe* f) {
 // The build behind lins_local_map_build (scans: the entries' scan clouds on the host — checked, boxed and packed here,
 // one upload) and lins_local_map_build_streams (from: the same clouds where they lie in the streams' arenas — one
 // kernel does that work); arguments checked by the caller.  Everything else is the same job table and the same launches.
+// msrc: where the two map jobs of an entry read their frames.  Jobs are named by their logical index (stage A: 5 k + cloud,
+// stage B: 5 n + k) and stored at ph[logical]: the map jobs of more than the archive's chunk of tiles come first, so that
+// one stage launcher splits their scans (launch_lm_stage_split); a ring build has none and ph is the identity.
 static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t* slots, const lins_local_scan* scans,
-                                const StreamMapClouds* from, lins_local_map_sizes* out) {
+                                const StreamMapClouds* from, const MapSource& msrc, lins_local_map_sizes* out) {
   HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
   m->built = false;
   auto scan_n = [&](int k, int q) { return from ? from[k].n[q] : (q == 0 ? scans[k].n_corner : q == 1 ? scans[k].n_surf : scans[k].n_outlier); };
@@ -194,16 +207,24 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
   std::vector<int> frames_of(n);
   for (int k = 0; k < n; ++k) {
     const int s = slots[k];
-    frames_of[k] = m->count[s];
-    for (int i = 0; i < m->count[s]; ++i) {
-      const KeyFrame& f = m->meta[(size_t)s * m->window + (m->head[s] + i) % m->window];
-      cap[5 * k] += f.n[0], cap[5 * k + 1] += f.n[1] + f.n[2];
+    frames_of[k] = msrc.ids ? msrc.n_ids[k] : m->count[s];
+    for (int i = 0; i < frames_of[k]; ++i) {
+      const int* fn = msrc.ids ? (*msrc.ar.frames)[s][msrc.ids[k][i]].n : m->meta[(size_t)s * m->window + (m->head[s] + i) % m->window].n;
+      cap[5 * k] += fn[0], cap[5 * k + 1] += (long long)fn[1] + fn[2];
     }
     cap[5 * k + 2] = scan_n(k, 0), cap[5 * k + 3] = scan_n(k, 1), cap[5 * k + 4] = scan_n(k, 2);
     cap[5 * n + k] = (long long)scan_n(k, 1) + scan_n(k, 2);
   }
   for (int j = 0; j < NJ; ++j)
     if (cap[j] > INT_MAX / 2) return LINS_E_CAPACITY;
+  std::vector<int> ph(NJ, -1), lg;  // logical -> stored index and back
+  const int chunk = msrc.ids ? msrc.ar.chunk : INT_MAX;
+  for (int k = 0; k < n && msrc.ids; ++k)
+    for (int w = 0; w < 2; ++w)
+      if ((cap[5 * k + w] + kLmTile - 1) / kLmTile > chunk) ph[5 * k + w] = (int)lg.size(), lg.push_back(5 * k + w);
+  const int n_split = (int)lg.size();
+  for (int j = 0; j < NJ; ++j)
+    if (ph[j] < 0) ph[j] = (int)lg.size(), lg.push_back(j);
   // staging: the raw scans of all entries first (one upload), then the maps, then stage B
   std::vector<int> order;
   for (int k = 0; k < n; ++k)
@@ -213,11 +234,11 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
   for (int k = 0; k < n; ++k) order.push_back(5 * k), order.push_back(5 * k + 1);
   for (int k = 0; k < n; ++k) order.push_back(5 * n + k);
   size_t stage_total = 0, tiles_total = 0, out_total = 0;
-  for (int j : order) jobs[j].off_in = (long long)stage_total, stage_total += (size_t)cap[j];
+  for (int j : order) jobs[ph[j]].off_in = (long long)stage_total, stage_total += (size_t)cap[j];
   for (int j = 0; j < NJ; ++j) {
     LmJob& jb = jobs[j];
-    jb.cap = (int)cap[j];
-    jb.ntiles = (int)((cap[j] + kLmTile - 1) / kLmTile);
+    jb.cap = (int)cap[lg[j]];
+    jb.ntiles = (int)((cap[lg[j]] + kLmTile - 1) / kLmTile);
     jb.tile0 = (int)tiles_total, tiles_total += (size_t)jb.ntiles;
     jb.out_after = jb.src_a = jb.src_b = jb.feed = jb.feed_after = -1, jb.map = 0, jb.pad = 0;
     LmState& st = states[j];
@@ -227,21 +248,28 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
     st.n = j < 5 * n ? jb.cap : 0;
   }
   if (tiles_total > (size_t)INT_MAX / 256) return LINS_E_CAPACITY;
+  std::vector<ArChunk> chunks;  // the split jobs' chunk tables, as lins_archive_assemble builds them
+  std::vector<ArSplit> splits;
+  for (int j = 0; j < n_split; ++j) {
+    ArSplit sp{j, (int)chunks.size(), (jobs[j].ntiles + chunk - 1) / chunk, 0};
+    for (int c = 0; c < sp.nc; ++c) chunks.push_back(ArChunk{j, c, sp.c0, 0});
+    splits.push_back(sp);
+  }
   for (int k = 0; k < n; ++k) {
     const long long c2 = cap[5 * k + 2] + cap[5 * n + k];  // cornerDS, then surfTotalDS right behind it (the query layout)
     const long long ocap[5] = {cap[5 * k], cap[5 * k + 1], c2, cap[5 * k + 3], cap[5 * k + 4]};
     for (int c = 0; c < 5; ++c) {
-      LmJob& jb = jobs[5 * k + c];
+      LmJob& jb = jobs[ph[5 * k + c]];
       jb.off_out = (long long)out_total, out_total += (size_t)ocap[c];
       jb.inv = 1.0f / (c == 0 || c == 2 ? 0.2f : 0.4f);
     }
-    jobs[5 * k].map = jobs[5 * k + 1].map = 1;
-    LmJob& b = jobs[5 * n + k];
+    jobs[ph[5 * k]].map = jobs[ph[5 * k + 1]].map = 1;
+    LmJob& b = jobs[ph[5 * n + k]];
     b.inv = 1.0f / 0.4f;
-    b.off_out = jobs[5 * k + 2].off_out, b.out_after = 5 * k + 2;
-    b.src_a = 5 * k + 3, b.src_b = 5 * k + 4;
-    jobs[5 * k + 3].feed = jobs[5 * k + 4].feed = 5 * n + k;
-    jobs[5 * k + 4].feed_after = 5 * k + 3;
+    b.off_out = jobs[ph[5 * k + 2]].off_out, b.out_after = ph[5 * k + 2];
+    b.src_a = ph[5 * k + 3], b.src_b = ph[5 * k + 4];
+    jobs[ph[5 * k + 3]].feed = jobs[ph[5 * k + 4]].feed = ph[5 * n + k];
+    jobs[ph[5 * k + 4]].feed_after = ph[5 * k + 3];
   }
   int rc;
   if (scans && (rc = grow_pinned(ctx, &m->h_raw, &m->cap_raw, raw_total))) return rc;
@@ -251,7 +279,7 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
     const int cn[3] = {scans[k].n_corner, scans[k].n_surf, scans[k].n_outlier};
     for (int q = 0; q < 3; ++q) {
       if ((rc = cloud_check(c[q], cn[q]))) return rc;
-      const int j = 5 * k + 2 + q;
+      const int j = ph[5 * k + 2 + q];
       float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
       for (int i = 0; i < cn[q]; ++i) {
         const lins_point& p = c[q][i];
@@ -267,7 +295,7 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
   std::vector<int2> sblocks;
   for (int k = 0; k < n && from; ++k)
     for (int q = 0; q < 3; ++q) {
-      const int cnt = from[k].n[q], j = 5 * k + 2 + q;
+      const int cnt = from[k].n[q], j = ph[5 * k + 2 + q];
       if (!cnt) continue;
       for (int b = 0; b < (cnt + kLmTile - 1) / kLmTile; ++b) sblocks.push_back(make_int2((int)ssegs.size(), b));
       ssegs.push_back(LmScanSeg{from[k].src[q], jobs[j].off_in, cnt, j});
@@ -278,8 +306,25 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
   uint64_t pts_in = raw_total;
   for (int k = 0; k < n; ++k) {
     const int s = slots[k];
-    long long at[2] = {jobs[5 * k].off_in, jobs[5 * k + 1].off_in};
-    for (int i = 0; i < m->count[s]; ++i) {
+    long long at[2] = {jobs[ph[5 * k]].off_in, jobs[ph[5 * k + 1]].off_in};
+    // ... or the listed archive frames': corner_i -> corner map; surf_i and outlier_i, one behind the other in the arena
+    // and under one pose, -> surf map as one segment (LM:1310-1314)
+    for (int i = 0; i < frames_of[k] && msrc.ids; ++i) {
+      const ArFrame& f = (*msrc.ar.frames)[s][msrc.ids[k][i]];
+      const long long from_off[2] = {f.off, f.off + f.n[0]};
+      const int cnt[2] = {f.n[0], f.n[1] + f.n[2]};
+      for (int w = 0; w < 2; ++w) {
+        if (cnt[w]) {
+          LmSeg g{};
+          g.src = from_off[w], g.dst = at[w], g.n = cnt[w], g.job = ph[5 * k + w];
+          std::memcpy(g.t, f.t, sizeof g.t);
+          for (int b = 0; b < (cnt[w] + kLmTile - 1) / kLmTile; ++b) blocks.push_back(make_int2((int)segs.size(), b));
+          segs.push_back(g);
+        }
+        at[w] += cnt[w], pts_in += (uint64_t)cnt[w];
+      }
+    }
+    for (int i = 0; i < m->count[s] && !msrc.ids; ++i) {
       const int idx = (m->head[s] + i) % m->window;
       const KeyFrame& f = m->meta[(size_t)s * m->window + idx];
       long long src = (long long)(frame_ptr(m, s, idx) - m->d_frames);
@@ -287,7 +332,7 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
         const int w = q == 0 ? 0 : 1;
         if (f.n[q]) {
           LmSeg g{};
-          g.src = src, g.dst = at[w], g.n = f.n[q], g.job = 5 * k + w;
+          g.src = src, g.dst = at[w], g.n = f.n[q], g.job = ph[5 * k + w];
           std::memcpy(g.t, f.t, sizeof g.t);
           for (int b = 0; b < (f.n[q] + kLmTile - 1) / kLmTile; ++b) blocks.push_back(make_int2((int)segs.size(), b));
           segs.push_back(g);
@@ -300,13 +345,14 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
   tiles.reserve(tiles_total);
   for (int j = 0; j < NJ; ++j)
     for (int t = 0; t < jobs[j].ntiles; ++t) tiles.push_back(make_int2(j, t));
-  const int tiles_a = n ? jobs[5 * n].tile0 : 0;  // stage A's tiles come first
+  const int tiles_a = n ? jobs[5 * n].tile0 : 0;  // stage A's tiles come first (stage B's jobs are stored where they are named)
   const int tiles_b = (int)tiles_total - tiles_a;
-  // one table upload: jobs | states | segments | blocks | tiles | scan segments | scan blocks
+  // one table upload: jobs | states | segments | blocks | tiles | scan segments | scan blocks | chunks | splits
   const size_t o_jobs = 0, o_states = align64(o_jobs + NJ * sizeof(LmJob)), o_segs = align64(o_states + NJ * sizeof(LmState)),
                o_blocks = align64(o_segs + segs.size() * sizeof(LmSeg)), o_tiles = align64(o_blocks + blocks.size() * sizeof(int2)),
                o_ssegs = align64(o_tiles + tiles.size() * sizeof(int2)), o_sblocks = align64(o_ssegs + ssegs.size() * sizeof(LmScanSeg)),
-               tab_bytes = align64(o_sblocks + sblocks.size() * sizeof(int2));
+               o_chunks = align64(o_sblocks + sblocks.size() * sizeof(int2)), o_splits = align64(o_chunks + chunks.size() * sizeof(ArChunk)),
+               tab_bytes = align64(o_splits + splits.size() * sizeof(ArSplit));
   if ((rc = grow_pinned(ctx, &m->h_tab, &m->cap_htab, tab_bytes))) return rc;
   if ((rc = grow_pinned(ctx, &m->h_states, &m->cap_hstates, NJ * sizeof(LmState)))) return rc;
   std::memcpy(m->h_tab + o_jobs, jobs.data(), NJ * sizeof(LmJob));
@@ -316,6 +362,8 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
   if (!tiles.empty()) std::memcpy(m->h_tab + o_tiles, tiles.data(), tiles.size() * sizeof(int2));
   if (!ssegs.empty()) std::memcpy(m->h_tab + o_ssegs, ssegs.data(), ssegs.size() * sizeof(LmScanSeg));
   if (!sblocks.empty()) std::memcpy(m->h_tab + o_sblocks, sblocks.data(), sblocks.size() * sizeof(int2));
+  if (!chunks.empty()) std::memcpy(m->h_tab + o_chunks, chunks.data(), chunks.size() * sizeof(ArChunk));
+  if (!splits.empty()) std::memcpy(m->h_tab + o_splits, splits.data(), splits.size() * sizeof(ArSplit));
   if (from && !m->ev_stage) HIP_TRY(ctx, hipEventCreate(&m->ev_stage));
   if ((rc = grow(ctx, &m->d_tab, &m->cap_tab, tab_bytes))) return rc;
   if (m->cap_stage < std::max<size_t>(stage_total, 1)) {  // the staging arena and the sort's scratch: same extent
@@ -337,6 +385,7 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
     m->cap_tiles = c[1];
   }
   if ((rc = grow(ctx, &m->d_out, &m->cap_out, out_total))) return rc;
+  if (!chunks.empty() && (rc = grow(ctx, &m->d_csum, &m->cap_csum, chunks.size()))) return rc;
   hipStream_t st = ctx_stream(ctx);
   hipEvent_t e0, e1;
   ctx_events(ctx, &e0, &e1);
@@ -350,9 +399,13 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
     launch_lm_stage_scans(st, (int)sblocks.size(), (const LmScanSeg*)(m->d_tab + o_ssegs), (const int2*)(m->d_tab + o_sblocks), m->d_stage, d_states);
     HIP_TRY(ctx, hipEventRecord(m->ev_stage, st));
   }
-  launch_lm_transform(st, (int)blocks.size(), (const LmSeg*)(m->d_tab + o_segs), (const int2*)(m->d_tab + o_blocks), m->d_frames, m->d_stage, d_states);
-  launch_lm_stage(st, 0, 5 * n, tiles_a, d_tiles, d_jobs, d_states, m->d_stage, m->d_ka, m->d_kb, m->d_va, m->d_vb, m->d_hist,
-                  m->d_tilecnt, m->d_starts, m->d_out);
+  if (msrc.ids)
+    launch_ar_gather(st, (int)blocks.size(), (const LmSeg*)(m->d_tab + o_segs), (const int2*)(m->d_tab + o_blocks), msrc.ar.d_arena, m->d_stage, d_states);
+  else
+    launch_lm_transform(st, (int)blocks.size(), (const LmSeg*)(m->d_tab + o_segs), (const int2*)(m->d_tab + o_blocks), m->d_frames, m->d_stage, d_states);
+  launch_lm_stage_split(st, 0, n_split, 5 * n, tiles_a, d_tiles, d_jobs, d_states, m->d_stage, m->d_ka, m->d_kb, m->d_va, m->d_vb, m->d_hist,
+                        m->d_tilecnt, m->d_starts, m->d_out, chunk, (int)chunks.size(), (const ArChunk*)(m->d_tab + o_chunks),
+                        (const ArSplit*)(m->d_tab + o_splits), m->d_csum);
   launch_lm_stage(st, 5 * n, n, tiles_b, d_tiles + tiles_a, d_jobs, d_states, m->d_stage, m->d_ka, m->d_kb, m->d_va, m->d_vb,
                   m->d_hist, m->d_tilecnt, m->d_starts, m->d_out);
   HIP_TRY(ctx, hipGetLastError());
@@ -369,14 +422,14 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
   m->sizes.assign(n, lins_local_map_sizes{});
   for (int k = 0; k < n; ++k) {
     lins_local_map_sizes& z = m->sizes[k];
-    const int js[6] = {5 * k, 5 * k + 1, 5 * k + 2, 5 * k + 3, 5 * k + 4, 5 * n + k};
+    const int js[6] = {ph[5 * k], ph[5 * k + 1], ph[5 * k + 2], ph[5 * k + 3], ph[5 * k + 4], ph[5 * n + k]};
     int status = LINS_OK;
     for (int j : js)
       if (S[j].status == LINS_E_INPUT || (S[j].status && !status)) status = S[j].status;
     z.status = status, z.frames = frames_of[k];
     for (int c = 0; c < 6; ++c) {
       z.n[c] = status ? 0 : S[js[c]].nvox;
-      m->off[6 * k + c] = c < 5 ? jobs[js[c]].off_out : jobs[5 * k + 2].off_out + S[5 * k + 2].nvox;
+      m->off[6 * k + c] = c < 5 ? jobs[js[c]].off_out : jobs[js[2]].off_out + S[js[2]].nvox;
     }
     for (int w = 0; w < 2; ++w)
       for (int a = 0; a < 3; ++a) {
@@ -402,7 +455,7 @@ int lins_local_map_build(lins_ctx* ctx, int n, const int32_t* slots, const lins_
       return LINS_E_ARG;
   }
   static const lins_local_scan none{};
-  return local_map_build_impl(ctx, m, n, slots, n ? scans : &none, nullptr, out);
+  return local_map_build_impl(ctx, m, n, slots, n ? scans : &none, nullptr, MapSource{}, out);
 }
 
 int lins_local_map_build_streams(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* streams, lins_local_map_sizes* out) {
@@ -417,7 +470,52 @@ int lins_local_map_build_streams(lins_ctx* ctx, int n, const int32_t* slots, con
   }
   for (int k = 0; k < n; ++k)
     if (int rc = streams_map_clouds(ctx, streams[k], &from[k])) return rc;
-  return local_map_build_impl(ctx, m, n, slots, nullptr, from.data(), out);
+  return local_map_build_impl(ctx, m, n, slots, nullptr, from.data(), MapSource{}, out);
+}
+
+// the surround builds' own arguments: both stores there, every slot in both, every id a frame of its slot
+static int surround_source(lins_ctx* ctx, LocalMap* m, int n, const int32_t* slots, const int32_t* const* ids, const int32_t* n_ids, MapSource* src) {
+  if (!m->n_slots) return LINS_E_STATE;
+  if (int rc = archive_store(ctx, &src->ar)) return rc;
+  for (int k = 0; k < n; ++k) {
+    if (slots[k] < 0 || slots[k] >= m->n_slots || slots[k] >= src->ar.n_slots || n_ids[k] < 0 || (n_ids[k] && !ids[k])) return LINS_E_ARG;
+    const int have = (int)(*src->ar.frames)[slots[k]].size();
+    for (int i = 0; i < n_ids[k]; ++i)
+      if (ids[k][i] < 0 || ids[k][i] >= have) return LINS_E_ARG;
+  }
+  src->ids = ids, src->n_ids = n_ids;
+  return LINS_OK;
+}
+
+int lins_local_map_build_surround(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* const* ids, const int32_t* n_ids,
+                                  const lins_local_scan* scans, lins_local_map_sizes* out) {
+  if (!ctx || n < 0 || (n && (!slots || !ids || !n_ids || !scans))) return LINS_E_ARG;
+  LocalMap* m = local_of(ctx);
+  MapSource src;
+  if (int rc = surround_source(ctx, m, n, slots, ids, n_ids, &src)) return rc;
+  for (int k = 0; k < n; ++k) {
+    const lins_local_scan& s = scans[k];
+    if (s.n_corner < 0 || s.n_surf < 0 || s.n_outlier < 0 || (s.n_corner && !s.corner) || (s.n_surf && !s.surf) ||
+        (s.n_outlier && !s.outlier))
+      return LINS_E_ARG;
+  }
+  static const lins_local_scan none{};
+  return local_map_build_impl(ctx, m, n, slots, n ? scans : &none, nullptr, src, out);
+}
+
+int lins_local_map_build_surround_streams(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* const* ids, const int32_t* n_ids,
+                                          const int32_t* streams, lins_local_map_sizes* out) {
+  if (!ctx || n < 0 || (n && (!slots || !ids || !n_ids || !streams))) return LINS_E_ARG;
+  LocalMap* m = local_of(ctx);
+  MapSource src;
+  if (int rc = surround_source(ctx, m, n, slots, ids, n_ids, &src)) return rc;
+  std::vector<StreamMapClouds> from((size_t)std::max(n, 1));
+  for (int k = 0; k < n; ++k)
+    for (int i = 0; i < k; ++i)
+      if (streams[i] == streams[k]) return LINS_E_ARG;  // (a stream may appear once)
+  for (int k = 0; k < n; ++k)
+    if (int rc = streams_map_clouds(ctx, streams[k], &from[k])) return rc;
+  return local_map_build_impl(ctx, m, n, slots, nullptr, from.data(), src, out);
 }
 
 int lins_last_local_map_stage_ms(lins_ctx* ctx, float* stage_ms) {

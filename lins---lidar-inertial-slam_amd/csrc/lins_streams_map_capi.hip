@@ -12,6 +12,7 @@
 
 #include "../../include/lins_map.h"
 #include "../../include/lins_streams_map.h"
+#include "host/keyframe_select.h"
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
 #include "local_map.h"
@@ -37,6 +38,10 @@ struct StreamsMap {
   // lins_streams_map_loop: the step feeds the pose graph; transformLast per stream mirrored on the host
   bool loop = false;
   std::vector<float> last6;    // [n][6]
+  // lins_streams_map_surround: the local map is the surrounding key frames of the archive; the list per stream
+  bool surround = false;
+  float radius = 50.f, pose_leaf = 1.f;
+  std::vector<std::vector<int>> lists;  // [n] surroundingExistingKeyPosesID
   // a write-back's batch (lins_pose_graph_apply_batch): n entries at most
   MapPoseFix *d_fix = nullptr, *h_fix = nullptr;
   // lins_map_associate_batch's own buffers (grown, never shrunk)
@@ -50,7 +55,7 @@ void step_buffers_free(StreamsMap* m) {
   (void)hipFree(m->d_poses), (void)hipFree(m->d_entries), (void)hipFree(m->d_out), (void)hipFree(m->d_fix);
   (void)hipHostFree(m->h_entries), (void)hipHostFree(m->h_out), (void)hipHostFree(m->h_fix);
   m->d_poses = nullptr, m->d_entries = m->h_entries = nullptr, m->d_out = m->h_out = nullptr, m->d_fix = m->h_fix = nullptr, m->n = 0;
-  m->loop = false;
+  m->loop = m->surround = false;
 }
 
 void streams_map_free(void* p) {
@@ -171,6 +176,7 @@ int lins_streams_map_init(lins_ctx* ctx, int n_streams, double process_interval)
   m->last_time.assign((size_t)n_streams, -1.0);  // LM:356
   m->centre.assign(3 * (size_t)n_streams, 0.f), m->stepped.assign((size_t)n_streams, 0);
   m->last6.assign(6 * (size_t)n_streams, 0.f);
+  m->lists.assign((size_t)n_streams, {});
   m->interval = process_interval;
   m->use_archive = lins_archive_count(ctx, 0) >= 0;
   m->associate_ms = m->finish_ms = 0.f;
@@ -220,7 +226,7 @@ int lins_streams_map_loop(lins_ctx* ctx, int on) {
     m->loop = false;
     return LINS_OK;
   }
-  if (!m->use_archive || pose_graph_slots(ctx) < m->n) return LINS_E_STATE;
+  if (m->surround || !m->use_archive || pose_graph_slots(ctx) < m->n) return LINS_E_STATE;
   for (int s = 0; s < m->n; ++s) {
     const int in_archive = lins_archive_count(ctx, s);  // (an archive re-sized below the streams: no such slot)
     if (in_archive < 0 || in_archive != lins_pose_graph_count(ctx, s, nullptr)) return LINS_E_STATE;
@@ -232,6 +238,35 @@ int lins_streams_map_loop(lins_ctx* ctx, int on) {
   for (int s = 0; s < m->n; ++s) std::memcpy(&m->last6[6 * (size_t)s], recs[s].last, sizeof recs[s].last);
   m->loop = true;
   return LINS_OK;
+}
+
+int lins_streams_map_surround(lins_ctx* ctx, int on, float radius, float pose_leaf) {
+  if (!ctx) return LINS_E_ARG;
+  StreamsMap* m = state_of(ctx);
+  if (!m->n) return LINS_E_STATE;
+  if (!on) {
+    m->surround = false;
+    return LINS_OK;
+  }
+  if (!std::isfinite(radius) || radius < 0.f || !(pose_leaf > 0.f) || !std::isfinite(pose_leaf)) return LINS_E_ARG;
+  if (m->loop || !m->use_archive) return LINS_E_STATE;
+  for (int s = 0; s < m->n; ++s)
+    if (lins_archive_count(ctx, s) < 0) return LINS_E_STATE;  // (an archive re-sized below the streams: no such slot)
+  for (std::vector<int>& l : m->lists) l.clear();
+  m->surround = true, m->radius = radius, m->pose_leaf = pose_leaf;
+  return LINS_OK;
+}
+
+int lins_streams_map_surround_list(lins_ctx* ctx, int stream, int32_t* ids, int cap) {
+  if (!ctx || cap < 0) return LINS_E_ARG;
+  StreamsMap* m = state_of(ctx);
+  if (!m->n) return LINS_E_STATE;
+  if (stream < 0 || stream >= m->n) return LINS_E_ARG;
+  const std::vector<int>& l = m->lists[stream];
+  if ((int)l.size() > cap) return LINS_E_CAPACITY;
+  if (!l.empty() && !ids) return LINS_E_ARG;
+  for (size_t i = 0; i < l.size(); ++i) ids[i] = l[i];
+  return (int)l.size();
 }
 
 int lins_streams_map_step(lins_ctx* ctx, int n, const int32_t* streams, const lins_map_odom* odom, lins_map_step_result* out) {
@@ -264,13 +299,30 @@ int lins::streams_map_step_run(lins_ctx* ctx, int n, const int32_t* streams, con
   // the interval gate (LM:1821), f64
   std::vector<int> batch;     // positions in the call of the entries that run
   std::vector<int32_t> which;  // ... and their streams = their slots
+  std::vector<std::vector<int32_t>> lists;  // surround mode: the list each of them builds its map from
   for (int k = 0; k < n; ++k) {
     const bool no_record = !odom && !in.h_odom[streams[k]].valid;  // (the stream has no pose to map with: refused, entry alone)
-    if (!no_record && time_of(k) - m->last_time[streams[k]] >= m->interval) {
+    int refused = no_record ? LINS_E_INPUT : time_of(k) - m->last_time[streams[k]] >= m->interval ? LINS_OK : LINS_MAP_STEP_SKIPPED;
+    if (!refused && m->surround) {  // LM:1247-1308: the radius selection around currentRobotPosPoint, then the list rule
+      const int s = streams[k], have = lins_archive_count(ctx, s);
+      if (have < 0) return LINS_E_STATE;
+      std::vector<int32_t> ds((size_t)std::max(have, 1));
+      const int nd = have ? lins_archive_select_radius(ctx, s, &m->centre[3 * (size_t)s], m->radius, m->pose_leaf, ds.data(), have) : 0;
+      if (nd == LINS_E_CAPACITY) {
+        refused = LINS_E_CAPACITY;  // (the selection's box: the entry alone)
+      } else if (nd < 0) {
+        return nd;
+      } else {
+        std::vector<int> list = have ? m->lists[s] : std::vector<int>();  // (LM:1202: no key poses, nothing listed)
+        lins_select::surround_update(list, std::vector<int>(ds.begin(), ds.begin() + nd));
+        lists.emplace_back(list.begin(), list.end());
+      }
+    }
+    if (!refused) {
       batch.push_back(k), which.push_back(streams[k]);
     } else {
       out[k] = lins_map_step_result{};
-      out[k].status = no_record ? LINS_E_INPUT : LINS_MAP_STEP_SKIPPED, out[k].ring_age = -1, out[k].archive_id = -1;
+      out[k].status = refused, out[k].ring_age = -1, out[k].archive_id = -1;
     }
   }
   const int nb = (int)batch.size();
@@ -293,8 +345,18 @@ int lins::streams_map_step_run(lins_ctx* ctx, int n, const int32_t* streams, con
   }
   HIP_TRY(ctx, hipMemcpyAsync(m->d_entries, m->h_entries, (size_t)nb * sizeof(MapPoseEntry), hipMemcpyHostToDevice, st));
   // extractSurroundingKeyFrames + downsampleCurrentScan over the streams' clouds where they lie
-  int rc = lins_local_map_build_streams(ctx, nb, which.data(), which.data(), nullptr);
-  if (rc) return rc;
+  int rc;
+  if (m->surround) {
+    std::vector<const int32_t*> idp((size_t)nb);
+    std::vector<int32_t> idn((size_t)nb);
+    std::vector<lins_local_map_sizes> sizes((size_t)nb);
+    for (int j = 0; j < nb; ++j) idp[j] = lists[j].data(), idn[j] = (int32_t)lists[j].size();
+    if ((rc = lins_local_map_build_surround_streams(ctx, nb, which.data(), idp.data(), idn.data(), which.data(), sizes.data()))) return rc;
+    for (int j = 0; j < nb; ++j)  // (a build entry with a status keeps its list)
+      if (!sizes[j].status) m->lists[which[j]].assign(lists[j].begin(), lists[j].end());
+  } else if ((rc = lins_local_map_build_streams(ctx, nb, which.data(), which.data(), nullptr))) {
+    return rc;
+  }
   // transformAssociateToMap, scan2MapOptimization, transformUpdate, the key-frame rule
   if ((rc = scan2map_local_resident(ctx, nb, m->d_entries, m->d_poses, m->d_out, m->h_out, m->ev, odom ? nullptr : in.d_odom))) return rc;
   HIP_TRY(ctx, hipEventElapsedTime(&m->associate_ms, m->ev[0], m->ev[1]));

@@ -370,10 +370,12 @@ void launch_lm_sum(hipStream_t s, int n_tiles, const int2* tiles, const LmJob* j
   if (n_tiles) hipLaunchKernelGGL(lm_sum_kernel, dim3(n_tiles), dim3(kLmTile), 0, s, tiles, jobs, states, vals_a, vals_b, starts, stage, out);
 }
 
-// one stage: jobs [j0, j0 + n_jobs), tiles [0, n_tiles) of `tiles`
-void launch_lm_stage(hipStream_t s, int j0, int n_jobs, int n_tiles, const int2* tiles, const LmJob* jobs, LmState* states,
-                     float4* stage, unsigned* keys_a, unsigned* keys_b, int* vals_a, int* vals_b, int* hist, int* tilecnt,
-                     int* starts, float4* out) {
+// one stage: jobs [j0, j0 + n_jobs), tiles [0, n_tiles) of `tiles`.  The first n_split jobs have their two scans — each
+// radix pass's histogram, the per-tile run heads — split over many workgroups (launch_ar_scan over the chunk tables, as
+// lins_archive_assemble builds them); the others take the one-workgroup scans.  Both kinds share every other launch.
+void launch_lm_stage_split(hipStream_t s, int j0, int n_split, int n_jobs, int n_tiles, const int2* tiles, const LmJob* jobs, LmState* states,
+                           float4* stage, unsigned* keys_a, unsigned* keys_b, int* vals_a, int* vals_b, int* hist, int* tilecnt,
+                           int* starts, float4* out, int chunk_tiles, int n_chunks, const ArChunk* chunks, const ArSplit* splits, int* csum) {
   if (!n_jobs) return;
   launch_lm_setup(s, j0, n_jobs, jobs, states);
   if (!n_tiles) return;
@@ -382,13 +384,23 @@ void launch_lm_stage(hipStream_t s, int j0, int n_jobs, int n_tiles, const int2*
     unsigned *kin = (p & 1) ? keys_b : keys_a, *kout = (p & 1) ? keys_a : keys_b;
     int *vin = (p & 1) ? vals_b : vals_a, *vout = (p & 1) ? vals_a : vals_b;
     launch_lm_hist(s, p, n_tiles, tiles, jobs, states, kin, hist);
-    launch_lm_scan(s, p, j0, n_jobs, jobs, states, hist);
+    launch_lm_scan(s, p, j0 + n_split, n_jobs - n_split, jobs, states, hist);
+    launch_ar_scan(s, 256, p, chunk_tiles, n_chunks, chunks, n_split, splits, jobs, states, hist, csum);
     launch_lm_scatter(s, p, n_tiles, tiles, jobs, states, hist, kin, vin, kout, vout);
   }
   launch_lm_heads(s, n_tiles, tiles, jobs, states, keys_a, keys_b, tilecnt);
-  launch_lm_heads_scan(s, j0, n_jobs, jobs, states, tilecnt);
+  launch_lm_heads_scan(s, j0 + n_split, n_jobs - n_split, jobs, states, tilecnt);
+  launch_ar_scan(s, 1, -1, chunk_tiles, n_chunks, chunks, n_split, splits, jobs, states, tilecnt, csum);
   launch_lm_starts(s, n_tiles, tiles, jobs, states, keys_a, keys_b, tilecnt, starts);
   launch_lm_sum(s, n_tiles, tiles, jobs, states, vals_a, vals_b, starts, stage, out);
+}
+
+// a stage without split jobs
+void launch_lm_stage(hipStream_t s, int j0, int n_jobs, int n_tiles, const int2* tiles, const LmJob* jobs, LmState* states,
+                     float4* stage, unsigned* keys_a, unsigned* keys_b, int* vals_a, int* vals_b, int* hist, int* tilecnt,
+                     int* starts, float4* out) {
+  launch_lm_stage_split(s, j0, 0, n_jobs, n_tiles, tiles, jobs, states, stage, keys_a, keys_b, vals_a, vals_b, hist, tilecnt, starts, out, 0, 0,
+                        nullptr, nullptr, nullptr);
 }
 
 }  // namespace lins

@@ -374,6 +374,54 @@ def submap(frames, ids, clouds, leaf, flags=0):
     return out[:d["n"]].copy(), d
 
 
+def surround_update(lst, ds, cap=None):
+    """lins_host_surround_update: surroundingExistingKeyPosesID after one step with the loop closure off (LM:1261-1308)
+    -> the new list; cap: the room of the caller's array (default: enough).  Raises MemoryError on LINS_E_CAPACITY."""
+    L = lib()
+    cap = len(lst) + len(ds) if cap is None else int(cap)
+    buf = np.zeros(max(cap, len(lst), 1), np.int32)
+    buf[:len(lst)] = lst
+    dv = np.ascontiguousarray(ds, np.int32)
+    L.lins_host_surround_update.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    L.lins_host_surround_update.restype = C.c_int
+    rc = L.lins_host_surround_update(buf.ctypes.data, len(lst), cap, dv.ctypes.data, len(dv))
+    if rc == -3:  # LINS_E_CAPACITY: the list is as it was
+        assert buf[:len(lst)].tolist() == [int(v) for v in lst]
+        raise MemoryError("lins_host_surround_update: LINS_E_CAPACITY")
+    if rc < 0:
+        raise RuntimeError(f"lins_host_surround_update: {rc}")
+    return buf[:rc].tolist()
+
+
+def surround_map(frames, lst, scan):
+    """lins_host_surround_map: the CPU restatement of lins_local_map_build_surround for one entry.  frames: [(corner,
+    surf, outlier, pose)] by frame id; lst: the listed ids; scan: (corner, surf, outlier) raw.  Returns (the six clouds in
+    LOCAL_* order, sizes dict)."""
+    from ._ctypes_defs import KeyframeC, LocalMapSizesC, keyframe_c, local_scan_c
+
+    L = lib()
+    fr, keep = (KeyframeC * max(len(frames), 1))(), []
+    for k, f in enumerate(frames):
+        fr[k], kk = keyframe_c(*f)
+        keep.append(kk)
+    sc, skeep = local_scan_c(*scan)
+    idv = np.ascontiguousarray(lst, np.int32)
+    used = [frames[i] for i in idv if 0 <= i < len(frames)]
+    caps = [sum(len(f[0]) for f in used), sum(len(f[1]) + len(f[2]) for f in used), len(skeep[0]), len(skeep[1]), len(skeep[2]),
+            len(skeep[1]) + len(skeep[2])]
+    outs = [np.zeros((max(c, 1), 4), np.float32) for c in caps]
+    ptrs = (C.POINTER(Point) * 6)(*[o.ctypes.data_as(C.POINTER(Point)) for o in outs])
+    sizes = LocalMapSizesC()
+    L.lins_host_surround_map.argtypes = [C.POINTER(KeyframeC), C.c_int, C.c_void_p, C.c_int, C.POINTER(type(sc)), C.POINTER(C.POINTER(Point)),
+                                         C.POINTER(LocalMapSizesC)]
+    L.lins_host_surround_map.restype = C.c_int
+    rc = L.lins_host_surround_map(fr, len(frames), idv.ctypes.data, len(idv), C.byref(sc), ptrs, C.byref(sizes))
+    if rc != 0:
+        raise RuntimeError(f"lins_host_surround_map: {rc}")
+    d = sizes.as_dict()
+    return [o[:n].copy() for o, n in zip(outs, d["n"])], d
+
+
 def loop_icp_params(**kw):
     """lins_loop_icp_default_params with fields overridden by keyword (max_iterations=3, ...)"""
     from ._ctypes_defs import loop_icp_params as f

@@ -44,6 +44,7 @@ EXPORTS = [
     "lins_pose_graph_solve", "lins_pose_graph_poses", "lins_pose_graph_apply", "lins_pose_graph_count",
     "lins_last_pose_graph_stats", "lins_pose_graph_apply_batch",
     "lins_loop_step_default_params", "lins_loop_step", "lins_loop_closed_cloud", "lins_last_loop_step_stats", "lins_streams_map_loop",
+    "lins_local_map_build_surround", "lins_local_map_build_surround_streams", "lins_streams_map_surround", "lins_streams_map_surround_list",
 ]
 
 
@@ -280,6 +281,39 @@ class IeskfContext:
         self._check(L.lins_local_map_build_streams(self._h, n, sl.ctypes.data, stv.ctypes.data, out))
         self._local_sizes = [out[k].as_dict() for k in range(n)]
         return self._local_sizes
+
+    def _surround_build(self, fn, slots, ids, tail_types, tail):
+        from ._ctypes_defs import LocalMapSizesC
+
+        n = len(slots)
+        assert len(ids) == n
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        keep = [np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in ids]
+        idp = (C.c_void_p * max(n, 1))(*[v.ctypes.data for v in keep])
+        idn = np.ascontiguousarray([len(v) for v in keep] or [0], dtype=np.int32)
+        out = (LocalMapSizesC * max(n, 1))()
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + tail_types + [C.POINTER(LocalMapSizesC)]
+        self._local_sizes = []
+        self._check(fn(self._h, n, sl.ctypes.data, idp, idn.ctypes.data, *tail, out))
+        self._local_sizes = [out[k].as_dict() for k in range(n)]
+        return self._local_sizes
+
+    def local_map_build_surround(self, slots, ids, scans):
+        """lins_local_map_build_surround: local_map_build with entry k's map side read from the frames ids[k] (in that
+        order) of the key-frame archive's slot slots[k] instead of the ring.  Returns the per-entry sizes dicts."""
+        from ._ctypes_defs import LocalScanC, local_scan_c
+
+        keep, arr = [], (LocalScanC * max(len(slots), 1))()
+        for k, sc in enumerate(scans):
+            arr[k], kk = local_scan_c(*sc)
+            keep.append(kk)
+        return self._surround_build(lib().lins_local_map_build_surround, slots, ids, [C.POINTER(LocalScanC)], [arr])
+
+    def local_map_build_surround_streams(self, slots, ids, streams):
+        """lins_local_map_build_surround_streams: the same with the scan clouds taken from streams[k] where they lie"""
+        assert len(streams) == len(slots)
+        stv = np.ascontiguousarray(streams, dtype=np.int32)
+        return self._surround_build(lib().lins_local_map_build_surround_streams, slots, ids, [C.c_void_p], [stv.ctypes.data])
 
     def local_map_stage_ms(self):
         """HIP-event time (ms) of the staging kernel of the last local_map_build_streams"""

@@ -59,6 +59,30 @@ def loop(ctx, on=True):
     ctx._check(L.lins_streams_map_loop(ctx._h, int(bool(on))))
 
 
+def surround(ctx, on=True, radius=50.0, pose_leaf=1.0):
+    """lins_streams_map_surround: with it on, every step builds its local map from the key frames of the archive within
+    `radius` of the robot (the mapping node with loopClosureEnableFlag off, LM:1247-1315) instead of the ring"""
+    L = _ieskf.lib()
+    L.lins_streams_map_surround.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
+    ctx._check(L.lins_streams_map_surround(ctx._h, int(bool(on)), float(radius), float(pose_leaf)))
+
+
+def surround_list(ctx, stream):
+    """lins_streams_map_surround_list: the stream's surroundingExistingKeyPosesID as the last step left it"""
+    L = _ieskf.lib()
+    L.lins_streams_map_surround_list.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    cap = 64
+    while True:
+        ids = np.zeros(cap, np.int32)
+        rc = L.lins_streams_map_surround_list(ctx._h, int(stream), ids.ctypes.data, cap)
+        if rc == -3 and cap < (1 << 24):  # LINS_E_CAPACITY
+            cap *= 8
+            continue
+        if rc < 0:
+            ctx._check(rc)
+        return ids[:rc].tolist()
+
+
 def odom(transform_sum, time, imu_roll=0.0, imu_pitch=0.0, has_imu=False):
     o = MapOdomC()
     o.transform_sum[:] = [float(v) for v in np.asarray(transform_sum, np.float32)]
