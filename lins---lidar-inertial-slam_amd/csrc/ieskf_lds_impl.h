@@ -181,10 +181,12 @@ struct LCloud {  // one target cloud's grid (all pointers into LDS)
   int naz, stride, base, n;
   const float4* gs;  // hybrid storage: grid-sorted copy (x, y, z, index bits) of positions >= n_lds
   int n_lds;
+  int n_all;  // grid positions of the scan, both clouds (pt_rec clamps to them)
 };
 
 // ---- one grid position -> point.  Positions below n_lds are LDS-resident; in the hybrid layout
-// the others are read from the sorted global copy (L2): rare — the searches end in the low rings.
+// the others are read from the sorted global copy (L2).  In the batch shape the resident positions are the corner cloud
+// and surf rings 0-7: rings 8-15 — half of the plane queries' candidates — are never resident (tools/queue_trace.py).
 __device__ __forceinline__ void pt_xyz(const LdsStore& L, const LCloud& c, int p, float& x, float& y, float& z) {
   if (!kHybrid || p < c.n_lds) {
     const float4 v = L.pt[p];
@@ -203,6 +205,20 @@ __device__ __forceinline__ float pt_sqdist(const LdsStore& L, const LCloud& c, i
   pt_xyz(L, c, p, x, y, z);
   return sqdist3(x, y, z, sx, sy, sz);
 }
+// The whole record of a position — x, y, z and the index bits in .w — in ONE read that nothing guards: the position is
+// clamped into this scan's positions (unsigned min: -1 and whatever a stale carry record or walk-cache entry names end on
+// the last one) and the caller keeps the result only under the predicate that used to guard the read.  Written as
+// `p >= 0 ? pt_sqdist(p) : INFINITY` and `pt_idx(p)` the compiler sinks each read into its guard and waits for it there:
+// the certificates of a warm iteration were 4 + 9 round trips in series (profiles/cert_fetch.md); several pt_rec() in a
+// row are issued back to back in front of one wait (load_lds_grid below: the same cure).  A non-empty cloud, c.n > 0, is the
+// caller's to check (wave-uniform: a scan without targets of the kind has nothing to fetch).
+__device__ __forceinline__ float4 pt_rec(const LdsStore& L, const LCloud& c, int p) {
+  const unsigned q = min((unsigned)p, (unsigned)(c.n_all - 1));
+  const float4* src = (!kHybrid || q < (unsigned)c.n_lds) ? &L.pt[q] : &c.gs[q];
+  return *src;
+}
+__device__ __forceinline__ float rec_sqdist(const float4& r, float sx, float sy, float sz) { return sqdist3(r.x, r.y, r.z, sx, sy, sz); }
+__device__ __forceinline__ int rec_idx(const float4& r) { return __float_as_int(r.w); }
 
 // polar view of a de-skewed query, computed once and shared by both search passes
 struct QueryPolar {
@@ -798,8 +814,8 @@ constexpr bool kLeanBuild = false;
 #endif
 // one target cloud's grid view of the workgroup's LDS block (cs / cc of the kernel)
 __device__ __forceinline__ LCloud make_cloud(const LdsStore& L, bool is_surf, const float4* gs, int n_corner_t, int n_surf_t, int n_lds) {
-  return is_surf ? LCloud{L.gt.cell_end + kCellsCorner, L.gt.ring_start[0], &L.gt.el_ang[0][0], kAzSurf, 1, n_corner_t, n_surf_t, gs, n_lds}
-                 : LCloud{L.gt.cell_end, L.gt.ring_start[1], &L.gt.el_ang[1][0], kAzCorner, kAzSurf / kAzCorner, 0, n_corner_t, gs, n_lds};
+  return is_surf ? LCloud{L.gt.cell_end + kCellsCorner, L.gt.ring_start[0], &L.gt.el_ang[0][0], kAzSurf, 1, n_corner_t, n_surf_t, gs, n_lds, n_corner_t + n_surf_t}
+                 : LCloud{L.gt.cell_end, L.gt.ring_start[1], &L.gt.el_ang[1][0], kAzCorner, kAzSurf / kAzCorner, 0, n_corner_t, gs, n_lds, n_corner_t + n_surf_t};
 }
 // ---- grid load: the scan's prebuilt index (grid_index_kernel, ieskf_grid.hip — the reference's setInputCloud,
 // SE:1156-1160, outside performIESKF) into LDS: the tables and the first n_lds records of the sorted copy as 16-byte
@@ -988,9 +1004,9 @@ __device__ __forceinline__ bool ieskf_lds_update(const KernelArgs ka, const floa
   if (prof && tid == 0) L.prof_acc[0] = clock64() - t_begin;
 
   const LCloud cs{L.gt.cell_end + kCellsCorner, L.gt.ring_start[0], &L.gt.el_ang[0][0], kAzSurf, 1, sd.n_corner_t, sd.n_surf_t,
-                  gs, n_lds};
+                  gs, n_lds, n_all_t};
   const LCloud cc{L.gt.cell_end, L.gt.ring_start[1], &L.gt.el_ang[1][0], kAzCorner, kAzSurf / kAzCorner, 0, sd.n_corner_t,
-                  gs, n_lds};
+                  gs, n_lds, n_all_t};
   const int role = lane % LANES, lane_base = lane - role, q_in_wave = lane / LANES;
   const bool lane_used = lane < kQPerWave * LANES;
   // ---- query -> lane layout of the one-lane-per-query shapes: WAVE-ROUNDS -------------------------------------------------

@@ -218,10 +218,16 @@ __device__ __forceinline__ void walk_lean(const LdsStore& L, const LCloud& c, bo
   const WalkCtx w = make_walk_ctx(c, nq, j1, rho);
   c2 = t2_init(thr);
   c3 = t2_init(thr);
-  auto warm_cand = [&](Top2& b, int pos, bool on_ring_rho) {
+  // the records of the two warm candidates in one trip (pt_rec: clamped positions, kept only where pos >= 0)
+  float4 wr2 = make_float4(0.f, 0.f, 0.f, 0.f), wr3 = wr2;
+  if (c.n > 0) {  // (wave-uniform)
+    wr2 = pt_rec(L, c, warm2);
+    if (is_surf) wr3 = pt_rec(L, c, warm3);
+  }
+  auto warm_cand = [&](Top2& b, int pos, const float4& rec, bool on_ring_rho) {
     int rank;
     if (pos < 0) return;
-    const int j = pt_idx(L, c, pos);
+    const int j = rec_idx(rec);
     if (!walk_rank(w, j, rank)) return;
     if (check_class) {
       int r = 0;  // ring of index j: the last ring that starts at or before it
@@ -230,10 +236,10 @@ __device__ __forceinline__ void walk_lean(const LdsStore& L, const LCloud& c, bo
         if (c.ring_start[r + step] <= j) r += step;
       if ((r == rho) != on_ring_rho) return;
     }
-    t2_insert(b, ((unsigned long long)__float_as_uint(pt_sqdist(L, c, pos, sx, sy, sz)) << 32) | walk_low(rank, pos));
+    t2_insert(b, ((unsigned long long)__float_as_uint(rec_sqdist(rec, sx, sy, sz)) << 32) | walk_low(rank, pos));
   };
-  warm_cand(c2, warm2, is_surf);  // second point: ring rho for planes, another ring for lines
-  warm_cand(c3, warm3, false);    // third point (planes only): another ring
+  warm_cand(c2, warm2, wr2, is_surf);  // second point: ring rho for planes, another ring for lines
+  warm_cand(c3, warm3, wr3, false);    // third point (planes only): another ring
   // (reseed: the warm candidates stay in the lists, but the per-ring seed scans run as in a cold walk — see nn_lean)
   const bool w2 = (unsigned)c2.k != 0u && !reseed, w3 = (unsigned)c3.k != 0u && !reseed;
   if (is_surf && !w2) {  // class-2 seed on ring rho: all lanes of the query

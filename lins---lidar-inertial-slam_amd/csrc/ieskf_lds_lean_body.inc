@@ -64,7 +64,6 @@
 #endif
     PROF2_ADD(0, s1 - s0);
   }
-  auto dist_to = [&](int pos) { return pt_sqdist(L, c, pos, sel0, sel1f, sel2); };
   auto drift_from = [&](float cx, float cy, float cz) {
     const float ex = sel0 - cx, ey = sel1f - cy, ez = sel2 - cz;
     return bound_sqrtf(ex * ex + ey * ey + ez * ez);
@@ -83,6 +82,7 @@
     bool said = false;
     int pred = -1;
     bool reseed1 = false;  // the query moved far since its last search: the warm bound is loose, seed as a cold search does
+    int j1 = -1;           // original index of p1: from the record a certificate holds, or from the search's own key
     {
       int a1 = lo16(n0.x), b1c = hi16(n0.x);
       int ra1 = (int)(signed char)((n0.y >> 16) & 0xFFu), rb1 = (int)n0.y >> 24;
@@ -90,15 +90,20 @@
       bool flip = false;
       if (active && KNOBS && (pad & 0x80000) && warm_iter) {  // (counting aid: every certificate holds, unchecked)
         pred = a1, said = true;
+        if (a1 >= 0) j1 = pt_idx(L, c, a1);
       } else if (active) {
-        const float da = a1 >= 0 ? dist_to(a1) : INFINITY, db = b1c >= 0 ? dist_to(b1c) : INFINITY;
+        // the records of A and B in one trip (pt_rec: fetched on clamped positions, kept under the guards of the distances)
+        float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra;
+        if (c.n > 0) ra = pt_rec(L, c, a1), rb = pt_rec(L, c, b1c);  // (wave-uniform)
+        const float da = a1 >= 0 ? rec_sqdist(ra, sel0, sel1f, sel2) : INFINITY, db = b1c >= 0 ? rec_sqdist(rb, sel0, sel1f, sel2) : INFINITY;
         const float drift = drift_from(__uint_as_float(n0.w), __uint_as_float(n1.x), __uint_as_float(n1.y));
         reseed1 = drift > prm.reseed_drift;
         bool ok = warm_iter && !(KNOBS && (pad & 16)) && certified(fminf(fminf(da, db), thr), __uint_as_float(n0.z), drift);
-        const unsigned long long ka_ = da < thr ? pack_key(da, pt_idx(L, c, a1)) : kNone;
-        const unsigned long long kb_ = db < thr ? pack_key(db, pt_idx(L, c, b1c)) : kNone;
+        const unsigned long long ka_ = da < thr ? pack_key(da, rec_idx(ra)) : kNone;
+        const unsigned long long kb_ = db < thr ? pack_key(db, rec_idx(rb)) : kNone;
         flip = kb_ < ka_;
         pred = (flip ? kb_ : ka_) == kNone ? -1 : (flip ? b1c : a1);
+        j1 = rec_idx(flip ? rb : ra);  // original index of the prediction (read only where pred >= 0)
         said = ok;
         if (verify) ok = false;
         need_nn = !ok;
@@ -141,6 +146,7 @@
         if (done) {
           p1 = r.low ? nn_pos(r.low) : -1;  // (a winner beat the threshold sentinel, so its distance is < thr, SE:851)
           ring1 = r.low ? nn_ring(r.low) : -1;
+          j1 = (int)(r.low >> 18) - 1;  // (nn_low: index + 1 above the position and the ring)
           const int b = r.low2 ? nn_pos(r.low2) : -1, rb = r.low2 ? nn_ring(r.low2) : -1;
           if (KNOBS && said && p1 != pred) atomicAdd(&L.dbg[0], 1);
           nn_changed = p1 != sel_old;
@@ -162,7 +168,7 @@
     }
     // ---- second / third point: the walk part of the record, the walk cache, the certificate (owner) ---------------------------
     bool need_walk = false;
-    int warm2 = -1, warm3 = -1, j1 = -1;
+    int warm2 = -1, warm3 = -1;
     bool set_ok = !nn_changed;  // the recorded second / third points belong to this nearest neighbour
     bool said23 = false;
     int pred2 = -1, pred3 = -1;
@@ -192,6 +198,9 @@
           __builtin_amdgcn_raw_buffer_store_b128(v4u{gen16 | (unsigned)sel_old, w0.x, w0.y, w0.z}, rs, slot * 32, 0, 16);
           __builtin_amdgcn_raw_buffer_store_b128(v4u{w0.w, w1.x, w1.y, w1.z}, rs, slot * 32 + 16, 0, 16);
         }
+        // (both words of the entry have arrived when this block ends: left in flight on a miss, the second one's registers
+        // stand between the records the certificate fetches below and put a wait into the middle of their trip)
+        asm volatile("" ::"v"(e1.w));
         if (p1 >= 0 && e0.x == (gen16 | (unsigned)p1)) {
           w0 = v4u{e0.y, e0.z, e0.w, e1.x};
           w1 = v3u{e1.y, e1.z, e1.w};
@@ -200,27 +209,34 @@
       }
       int a2 = lo16(w0.x), b2c = hi16(w0.x), a3 = lo16(w0.y), b3c = hi16(w0.y);
       bool flip2 = false, flip3 = false;
-      if (active && p1 >= 0) {
-        j1 = pt_idx(L, c, p1);  // (p1 >= 0 => p1 is candidate A, on ring ring1)
+      // the records of the four tracked candidates in one trip, by every lane of a warm iteration — also by the lanes that
+      // will walk, and by those whose planes 2-3 are not their own (own_set below): pt_rec clamps what it is given, and
+      // judge() below keeps a record only where it read one before.  (Line queries have no third point and fetch a3 / b3c,
+      // -1 clamped, all the same: with them under `if (is_surf)` the other path's zeroes land between the loads, with a wait.)
+      float4 r2a = make_float4(0.f, 0.f, 0.f, 0.f), r2b = r2a, r3a = r2a, r3b = r2a;
+      if (warm_iter && c.n > 0) {  // (wave-uniform)
+        r2a = pt_rec(L, c, a2), r2b = pt_rec(L, c, b2c), r3a = pt_rec(L, c, a3), r3b = pt_rec(L, c, b3c);
+      }
+      if (active && p1 >= 0) {  // (p1 >= 0 => p1 is candidate A, on ring ring1, and j1 its original index)
         need_walk = !set_ok || !warm_iter;
         if (!need_walk && KNOBS && (pad & 0x80000)) {
           pred2 = a2, pred3 = a3, said23 = true;
         } else if (!need_walk) {
           const WalkCtx w = make_walk_ctx(c, is_surf ? sd.n_surf_q : sd.n_corner_q, j1, ring1);
           const float dB = drift_from(__uint_as_float(w1.x), __uint_as_float(w1.y), __uint_as_float(w1.z));
-          auto judge = [&](int pa, int pb, float lb, int& pd, bool& fl) {
-            const float da = pa >= 0 ? dist_to(pa) : INFINITY, db = pb >= 0 ? dist_to(pb) : INFINITY;
+          auto judge = [&](int pa, int pb, const float4& ra, const float4& rb, float lb, int& pd, bool& fl) {
+            const float da = pa >= 0 ? rec_sqdist(ra, sel0, sel1f, sel2) : INFINITY, db = pb >= 0 ? rec_sqdist(rb, sel0, sel1f, sel2) : INFINITY;
             int rka = 0, rkb = 0;
-            if (pa >= 0) walk_rank(w, pt_idx(L, c, pa), rka);
-            if (pb >= 0) walk_rank(w, pt_idx(L, c, pb), rkb);
+            if (pa >= 0) walk_rank(w, rec_idx(ra), rka);
+            if (pb >= 0) walk_rank(w, rec_idx(rb), rkb);
             const unsigned long long ka_ = da < thr ? pack_key(da, rka) : kNone;
             const unsigned long long kb_ = db < thr ? pack_key(db, rkb) : kNone;
             fl = kb_ < ka_;
             pd = (fl ? kb_ : ka_) == kNone ? -1 : (fl ? pb : pa);
             return certified(fminf(fminf(da, db), thr), lb, dB);
           };
-          bool ok23 = judge(a2, b2c, __uint_as_float(w0.z), pred2, flip2);
-          if (is_surf) ok23 = judge(a3, b3c, __uint_as_float(w0.w), pred3, flip3) && ok23;
+          bool ok23 = judge(a2, b2c, r2a, r2b, __uint_as_float(w0.z), pred2, flip2);
+          if (is_surf) ok23 = judge(a3, b3c, r3a, r3b, __uint_as_float(w0.w), pred3, flip3) && ok23;
           said23 = ok23;
           need_walk = !ok23 || verify;
         }
