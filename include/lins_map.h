@@ -250,6 +250,57 @@ int lins_last_archive_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* points_in
  * workgroups above it.  0: the default; INT_MAX: never split.  Results are the same bits for every value. */
 int lins_archive_set_scan_chunk(lins_ctx* ctx, int chunk_tiles);
 
+/* ---- key-pose selection on the device: lins_archive_select_radius / _find_loop / the surround list rule, batched ---------
+ * The archive keeps a device mirror of every slot's key poses (x, y, z) and times; lins_archive_push, _push_scans and
+ * _set_poses only note on the host from which id a slot's mirror is stale, and each call below brings the stale ranges of
+ * the slots it names up in its one upload.  A call is one upload, one chain of launches on the context's stream (one
+ * workgroup per entry), one download and one synchronisation.  The results are those of the single calls — the contract
+ * of csrc/host/keyframe_select.h — bit for bit, for every entry, whatever the batch; a slot may appear in several entries.
+ * An entry with more than 8 192 hits (or, in the surround call, a selected id that is no frame of the slot) is served by
+ * that host text inside the same call: result.host = 1, counted in lins_last_keyposes_stats, not an error.
+ * Errors: LINS_E_STATE before lins_archive_init; for the whole call, before anything is queued, LINS_E_ARG for what the
+ * single calls refuse so (a bad slot, a centre or radius that is not finite, radius < 0, pose_leaf) and for a bad stride
+ * or list, LINS_E_INPUT for a now that is not finite or a min_gap_s that is NaN; n = 0 is LINS_OK. */
+typedef struct lins_keyposes_query {
+  int32_t slot;
+  float centre[3];
+  float radius;    /* finite, >= 0 */
+  float pose_leaf; /* > 0, 1 / pose_leaf finite (not read by lins_keyposes_find_loop_batch) */
+} lins_keyposes_query;
+
+typedef struct lins_keyposes_loop_query {
+  lins_keyposes_query q;
+  double now;       /* timeLaserOdometry */
+  double min_gap_s; /* not NaN */
+} lins_keyposes_loop_query;
+
+typedef struct lins_keyposes_result {
+  int32_t n;      /* frames selected (0 with a status) */
+  int32_t hits;   /* poses within the radius */
+  int32_t status; /* LINS_OK; LINS_E_CAPACITY: the hits' pose_leaf box has more than 2^31 cells, or the entry's output is
+                     longer than stride — nothing is written for the entry */
+  int32_t host;   /* 1: the host text served the entry */
+} lins_keyposes_result;
+
+/* lins_archive_select_radius for n entries: entry k's ids go to ids + k * stride (stride >= 0) */
+int lins_keyposes_select_batch(lins_ctx* ctx, int n, const lins_keyposes_query* queries, int32_t* ids, int stride, lins_keyposes_result* results);
+/* lins_archive_find_loop for n entries: closest[k] = the id or -1 */
+int lins_keyposes_find_loop_batch(lins_ctx* ctx, int n, const lins_keyposes_loop_query* queries, int32_t* closest);
+/* the selection and surroundingExistingKeyPosesID's rule (lins_host_surround_update) in one call: entry k's list is the
+ * n_list[k] <= stride ids at lists + k * stride, every one a frame of its slot (else LINS_E_ARG); afterwards it holds the
+ * updated list and n_list[k] its length.  An entry with a status keeps its list and length. */
+int lins_keyposes_surround_batch(lins_ctx* ctx, int n, const lins_keyposes_query* queries, int32_t* lists, int stride, int32_t* n_list,
+                                 lins_keyposes_result* results);
+/* who selects for lins_streams_map_step in surround mode and for lins_loop_step's detect stage: the host loops (the
+ * default after lins_create, and the definition) or the batched calls above.  The results are the same bits. */
+#define LINS_KEYPOSES_HOST 0
+#define LINS_KEYPOSES_DEVICE 1
+int lins_keyposes_set_mode(lins_ctx* ctx, int mode);
+int lins_keyposes_mode(lins_ctx* ctx); /* LINS_KEYPOSES_* (>= 0) */
+/* of the last batched call: HIP-event time (ms) of its device sequence, the entries the host served, the hits over all
+ * entries (0 after lins_keyposes_find_loop_batch, which counts none) */
+int lins_last_keyposes_stats(lins_ctx* ctx, float* device_ms, int32_t* host_entries, uint64_t* hits);
+
 /* ---- loop-closure alignment: ICP over the archive's submaps (performLoopClosure, LM:1114-1186) ----------------------
  * pcl::IterativeClosestPoint as the mapping node sets it up (LM:1128-1132), restated with a fixed operation sequence:
  * the project's contract ("Loop-closure ICP"), one scalar definition in csrc/loop_icp_math.h compiled

@@ -323,6 +323,29 @@ class SubmapInfoC(C.Structure):
                     box_dim=list(self.box_dim), status=int(self.status))
 
 
+# ---- key-pose selection on the device (include/lins_map.h lins_keyposes_*) ------------------
+KEYPOSES_HOST, KEYPOSES_DEVICE = 0, 1
+
+
+class KeyposesQueryC(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("centre", C.c_float * 3), ("radius", C.c_float), ("pose_leaf", C.c_float)]
+
+
+class KeyposesLoopQueryC(C.Structure):
+    _fields_ = [("q", KeyposesQueryC), ("now", C.c_double), ("min_gap_s", C.c_double)]
+
+
+class KeyposesResultC(C.Structure):
+    _fields_ = [("n", C.c_int32), ("hits", C.c_int32), ("status", C.c_int32), ("host", C.c_int32)]
+
+    def as_dict(self):
+        return dict(n=int(self.n), hits=int(self.hits), status=int(self.status), host=int(self.host))
+
+
+def keyposes_query(slot, centre, radius, pose_leaf=1.0):
+    return KeyposesQueryC(int(slot), (C.c_float * 3)(*[float(v) for v in centre]), float(radius), float(pose_leaf))
+
+
 # ---- the loop-closure ICP (include/lins_map.h lins_loop_icp_*, include/lins_host.h lins_host_loop_icp*) --------
 ICP_NONE, ICP_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE, ICP_NO_CORRESPONDENCES = range(6)
 

@@ -1,6 +1,9 @@
 // keyframe_select.h — which key frames a global map or a loop closure takes (LM:989-1007, 1050-1067), defined ONCE and
 // compiled into both libraries (lins_archive_select_radius / _find_loop and lins_host_select_radius / _find_loop).  Key
-// poses are a few thousand points: this is host work.  The contract:
+// poses are a few thousand points: for one robot this is host work, and this text is the definition.  For a batch of
+// streams the same selection runs on the device, one workgroup per entry, with the bits of this text
+// (keypose_select_kernels.hip, lins_keyposes_*; profiles/keypose_select_rate.txt says where that pays); an entry the
+// kernels do not take is served by this text inside the same call.  The contract:
 //   radius search  the poses with f32 ((dx*dx + dy*dy) + dz*dz) <= radius*radius, ordered by ascending (that squared
 //                  distance, id).  PCL's FLANN radius search is not in the reference's text and cannot be pinned here —
 //                  like the 5-NN of scan-to-map it is restated as the exact search with a fixed order.

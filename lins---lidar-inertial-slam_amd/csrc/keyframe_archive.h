@@ -60,4 +60,33 @@ struct ArchiveStore {
 };
 int archive_store(lins_ctx* ctx, ArchiveStore* v);
 
+// ---- the key-pose selection on the device (keypose_select_kernels.hip, lins_keyposes_*): the slots' key poses and times
+// have a device mirror, frame id of slot s at s * max_frames + id.  One workgroup serves one entry.
+struct KpStale {  // one frame whose mirror record is out of date
+  double time;
+  float x, y, z;
+  int pad;
+  long long dst;  // its place in the mirror
+};
+static_assert(sizeof(KpStale) == 32, "KpStale layout");
+
+struct KpEntry {
+  long long base;      // the slot's first record in the mirror
+  long long mark_off;  // surround: the entry's 2 * nf ints of scratch (the list rule's marks, then the selection)
+  double now, gap;     // find-loop
+  float c[3], r2, inv; // centre, radius * radius and 1 / pose_leaf as the host forms them
+  int nf;              // frames of the slot
+  int stride;          // ids (select) / list ids (surround) the entry's output holds
+  int n_list;          // surround: the list's length
+};
+static_assert(sizeof(KpEntry) == 64, "KpEntry layout");
+
+struct KpOut {
+  int n, hits, status;
+  int host;    // 1: more hits than the kernel sorts, or a selected id that is no frame — the host text serves the entry
+  int n_list;  // surround: the list's length afterwards
+  int pad[3];
+};
+static_assert(sizeof(KpOut) == 32, "KpOut layout");
+
 }  // namespace lins

@@ -13,6 +13,7 @@
 #include "../../include/lins_map.h"
 #include "host/keyframe_select.h"
 #include "keyframe_archive.h"
+#include "keypose_select_math.h"
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
 #include "local_map.h"
@@ -42,6 +43,17 @@ struct Archive {
   std::vector<char> filtered;  // per entry: a VoxelGrid output (its info carries the 1 m box)
   float ms = 0.f;
   uint64_t points_in = 0;
+  // the key-pose selection on the device (lins_keyposes_*): the mirror of the slots' key poses and times, frame id of slot
+  // s at s * max_frames + id, current below stale_from[s]; one table up, one block of results down (pinned staging)
+  float4* d_kp_pose = nullptr;
+  double* d_kp_time = nullptr;
+  std::vector<int> stale_from;  // [slot]
+  char *d_kp_up = nullptr, *h_kp_up = nullptr, *d_kp_down = nullptr, *h_kp_down = nullptr;
+  int* d_kp_scratch = nullptr;
+  size_t cap_kp_up = 0, cap_kp_hup = 0, cap_kp_down = 0, cap_kp_hdown = 0, cap_kp_scratch = 0;
+  int kp_mode = LINS_KEYPOSES_HOST, kp_host = 0;
+  float kp_ms = 0.f;
+  uint64_t kp_hits = 0;
 };
 
 void archive_free(void* p) {
@@ -49,6 +61,8 @@ void archive_free(void* p) {
   (void)hipFree(m->d_arena), (void)hipFree(m->d_stage), (void)hipFree(m->d_out), (void)hipFree(m->d_ka), (void)hipFree(m->d_kb);
   (void)hipFree(m->d_va), (void)hipFree(m->d_vb), (void)hipFree(m->d_starts), (void)hipFree(m->d_hist), (void)hipFree(m->d_tilecnt);
   (void)hipFree(m->d_csum), (void)hipFree(m->d_tab), (void)hipHostFree(m->h_tab), (void)hipHostFree(m->h_states);
+  (void)hipFree(m->d_kp_pose), (void)hipFree(m->d_kp_time), (void)hipFree(m->d_kp_up), (void)hipFree(m->d_kp_down), (void)hipFree(m->d_kp_scratch);
+  (void)hipHostFree(m->h_kp_up), (void)hipHostFree(m->h_kp_down);
   delete m;
 }
 
@@ -87,6 +101,9 @@ void set_pose(ArFrame& f, const lins_key_pose& p) {  // updateTransformPointClou
 
 size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
 
+// the mirror of the slot's key poses is out of date from frame `id` on (brought up by the next lins_keyposes_* call)
+void stale_at(Archive* m, int slot, int id) { m->stale_from[slot] = std::min(m->stale_from[slot], id); }
+
 std::vector<lins_key_pose> poses_of(const std::vector<ArFrame>& fr) {
   std::vector<lins_key_pose> p(fr.size());
   for (size_t i = 0; i < fr.size(); ++i) p[i] = fr[i].pose;
@@ -118,12 +135,15 @@ int lins_archive_init(lins_ctx* ctx, int n_slots, int max_frames_per_slot, long 
   HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
   Archive* m = archive_of(ctx);
   HIP_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));  // (a push_scans copy may still write the old arena)
-  (void)hipFree(m->d_arena);
-  m->d_arena = nullptr, m->n_slots = 0, m->built = false, m->used = 0;
+  (void)hipFree(m->d_arena), (void)hipFree(m->d_kp_pose), (void)hipFree(m->d_kp_time);
+  m->d_arena = nullptr, m->d_kp_pose = nullptr, m->d_kp_time = nullptr, m->n_slots = 0, m->built = false, m->used = 0;
   m->frames.clear();
   HIP_TRY(ctx, hipMalloc((void**)&m->d_arena, (size_t)max_points_total * sizeof(float4)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_kp_pose, (size_t)n_slots * max_frames_per_slot * sizeof(float4)));
+  HIP_TRY(ctx, hipMalloc((void**)&m->d_kp_time, (size_t)n_slots * max_frames_per_slot * sizeof(double)));
   m->n_slots = n_slots, m->max_frames = max_frames_per_slot, m->max_points = max_points_total;
   m->frames.assign(n_slots, {});
+  m->stale_from.assign(n_slots, 0);
   return LINS_OK;
 }
 
@@ -155,6 +175,7 @@ int lins_archive_push(lins_ctx* ctx, int slot, const lins_keyframe* f, double ti
   HIP_TRY(ctx, hipStreamSynchronize(st));  // (the caller's clouds may go once this returns)
   m->used += total;
   m->frames[slot].push_back(fr);
+  stale_at(m, slot, (int)m->frames[slot].size() - 1);
   return (int)m->frames[slot].size() - 1;
 }
 
@@ -192,6 +213,7 @@ int lins_archive_push_scans(lins_ctx* ctx, int n, const int32_t* entries, const 
     set_pose(fr, poses[i]);
     m->used += (long long)fr.n[0] + fr.n[1] + fr.n[2];
     m->frames[s].push_back(fr);
+    stale_at(m, s, (int)m->frames[s].size() - 1);
     if (ids_out) ids_out[i] = (int32_t)m->frames[s].size() - 1;
   }
   return LINS_OK;
@@ -205,6 +227,7 @@ int lins_archive_set_poses(lins_ctx* ctx, int slot, int first_id, int n, const l
   for (int i = 0; i < n; ++i)
     if (!pose_ok(poses[i])) return LINS_E_INPUT;
   for (int i = 0; i < n; ++i) set_pose(m->frames[slot][first_id + i], poses[i]);
+  if (n) stale_at(m, slot, first_id);
   return LINS_OK;
 }
 
@@ -456,6 +479,179 @@ int lins_last_archive_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* points_in
   Archive* m = archive_of(ctx);
   if (kernel_ms) *kernel_ms = m->ms;
   if (points_in) *points_in = m->points_in;
+  return LINS_OK;
+}
+
+}  // extern "C"
+
+// ---- key-pose selection on the device (include/lins_map.h lins_keyposes_*) ------------------------------------------------
+namespace {
+
+enum KpKind { kKpSelect, kKpLoop, kKpSurround };
+
+// One batched selection: the whole call's refusals, then one upload (entries | stale mirror records | lists), one chain
+// of launches, one download (results | ids or lists or candidates) and one synchronisation; the entries the kernel hands
+// back (KpOut::host) are served by host/keyframe_select.h here.  q(k): entry k's query; lq: the loop queries or null.
+int kp_batch(lins_ctx* ctx, KpKind kind, int n, const lins_keyposes_query* qs, const lins_keyposes_loop_query* lq, int32_t* ids, int stride,
+             int32_t* n_list, int32_t* closest, lins_keyposes_result* results) {
+  if (!ctx || n < 0 || (n && !qs && !lq)) return LINS_E_ARG;
+  if (kind != kKpLoop && (stride < 0 || (n && (!results || (stride && !ids))))) return LINS_E_ARG;
+  if (kind == kKpLoop && n && !closest) return LINS_E_ARG;
+  if (kind == kKpSurround && n && !n_list) return LINS_E_ARG;
+  Archive* m = archive_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  auto q = [&](int k) -> const lins_keyposes_query& { return lq ? lq[k].q : qs[k]; };
+  for (int k = 0; k < n; ++k) {
+    const lins_keyposes_query& a = q(k);
+    if (a.slot < 0 || a.slot >= m->n_slots || !lins_select::query_ok(a.centre, a.radius)) return LINS_E_ARG;
+    if (kind != kKpLoop && (!(a.pose_leaf > 0.f) || !std::isfinite(1.0f / a.pose_leaf))) return LINS_E_ARG;
+    if (kind == kKpLoop && (!std::isfinite(lq[k].now) || std::isnan(lq[k].min_gap_s))) return LINS_E_INPUT;
+    if (kind == kKpSurround) {
+      const int nf = (int)m->frames[a.slot].size();
+      if (n_list[k] < 0 || n_list[k] > stride) return LINS_E_ARG;
+      for (int i = 0; i < n_list[k]; ++i)
+        if (ids[(size_t)k * stride + i] < 0 || ids[(size_t)k * stride + i] >= nf) return LINS_E_ARG;
+    }
+  }
+  m->kp_ms = 0.f, m->kp_host = 0, m->kp_hits = 0;
+  if (n == 0) return LINS_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  // the table: entries | stale records of the slots named | (surround) the lists
+  std::vector<KpEntry> entries((size_t)n);
+  std::vector<KpStale> stale;
+  long long scratch_total = 0;
+  for (int k = 0; k < n; ++k) {
+    const lins_keyposes_query& a = q(k);
+    const std::vector<ArFrame>& fr = m->frames[a.slot];
+    KpEntry& e = entries[k];
+    std::memset(&e, 0, sizeof e);
+    e.base = (long long)a.slot * m->max_frames, e.nf = (int)fr.size();
+    std::memcpy(e.c, a.centre, sizeof e.c);
+    e.r2 = a.radius * a.radius;
+    e.inv = kind == kKpLoop ? 0.f : 1.0f / a.pose_leaf;
+    e.stride = stride;
+    if (kind == kKpLoop) e.now = lq[k].now, e.gap = lq[k].min_gap_s;
+    if (kind == kKpSurround) e.n_list = n_list[k], e.mark_off = scratch_total, scratch_total += 2ll * e.nf;
+    for (int i = m->stale_from[a.slot]; i < e.nf; ++i)
+      stale.push_back(KpStale{fr[i].time, fr[i].pose.x, fr[i].pose.y, fr[i].pose.z, 0, e.base + i});
+    m->stale_from[a.slot] = e.nf;  // (a slot named again in this call adds nothing)
+  }
+  const size_t out_ints = kind == kKpLoop ? (size_t)n : (size_t)n * stride;
+  const size_t o_stale = align64(n * sizeof(KpEntry)), o_lists = align64(o_stale + stale.size() * sizeof(KpStale)),
+               up_bytes = align64(o_lists + (kind == kKpSurround ? out_ints * sizeof(int) : 0));
+  const size_t o_ints = align64(n * sizeof(KpOut)), down_bytes = align64(o_ints + out_ints * sizeof(int));
+  int rc;
+  if ((rc = grow_pinned(ctx, &m->h_kp_up, &m->cap_kp_hup, up_bytes)) || (rc = grow(ctx, &m->d_kp_up, &m->cap_kp_up, up_bytes)) ||
+      (rc = grow_pinned(ctx, &m->h_kp_down, &m->cap_kp_hdown, down_bytes)) || (rc = grow(ctx, &m->d_kp_down, &m->cap_kp_down, down_bytes)) ||
+      (rc = grow(ctx, &m->d_kp_scratch, &m->cap_kp_scratch, (size_t)scratch_total))) {
+    std::fill(m->stale_from.begin(), m->stale_from.end(), 0);  // (the records packed above did not go up)
+    return rc;
+  }
+  std::memcpy(m->h_kp_up, entries.data(), n * sizeof(KpEntry));
+  if (!stale.empty()) std::memcpy(m->h_kp_up + o_stale, stale.data(), stale.size() * sizeof(KpStale));
+  if (kind == kKpSurround && out_ints) std::memcpy(m->h_kp_up + o_lists, ids, out_ints * sizeof(int));
+  hipStream_t st = ctx_stream(ctx);
+  hipEvent_t e0, e1;
+  ctx_events(ctx, &e0, &e1);
+  const KpEntry* d_entries = (const KpEntry*)m->d_kp_up;
+  KpOut* d_out = (KpOut*)m->d_kp_down;
+  int* d_ints = (int*)(m->d_kp_down + o_ints);
+  hipError_t err = hipMemcpyAsync(m->d_kp_up, m->h_kp_up, up_bytes, hipMemcpyHostToDevice, st);
+  if (err == hipSuccess) err = hipEventRecord(e0, st);
+  if (err == hipSuccess) {
+    launch_kp_refresh(st, (int)stale.size(), (const KpStale*)(m->d_kp_up + o_stale), m->d_kp_pose, m->d_kp_time);
+    if (kind == kKpSelect) launch_kp_select(st, n, d_entries, m->d_kp_pose, d_ints, d_out);
+    if (kind == kKpSurround) launch_kp_surround(st, n, d_entries, m->d_kp_pose, (const int*)(m->d_kp_up + o_lists), d_ints, m->d_kp_scratch, d_out);
+    if (kind == kKpLoop) launch_kp_find_loop(st, n, d_entries, m->d_kp_pose, m->d_kp_time, d_ints);
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess) err = hipEventRecord(e1, st);
+  if (err == hipSuccess) err = hipMemcpyAsync(m->h_kp_down, m->d_kp_down, down_bytes, hipMemcpyDeviceToHost, st);
+  if (err == hipSuccess) err = hipStreamSynchronize(st);
+  if (err != hipSuccess) {
+    std::fill(m->stale_from.begin(), m->stale_from.end(), 0);  // (what of the mirror was written is not known)
+    return ctx_fail_hip(ctx, err, "lins_keyposes batch");
+  }
+  HIP_TRY(ctx, hipEventElapsedTime(&m->kp_ms, e0, e1));
+  const KpOut* O = (const KpOut*)m->h_kp_down;
+  const int* I = (const int*)(m->h_kp_down + o_ints);
+  if (kind == kKpLoop) {
+    for (int k = 0; k < n; ++k) closest[k] = I[k];
+    return LINS_OK;
+  }
+  for (int k = 0; k < n; ++k) {
+    const lins_keyposes_query& a = q(k);
+    lins_keyposes_result& r = results[k];
+    r = lins_keyposes_result{O[k].n, O[k].hits, O[k].status, O[k].host};
+    m->kp_hits += (uint64_t)O[k].hits;
+    int32_t* mine = ids + (size_t)k * stride;
+    if (!O[k].host) {
+      if (r.status) continue;
+      const int cnt = kind == kKpSelect ? O[k].n : O[k].n_list;
+      if (cnt) std::memcpy(mine, I + (size_t)k * stride, (size_t)cnt * sizeof(int));
+      if (kind == kKpSurround) n_list[k] = cnt;
+      continue;
+    }
+    m->kp_host += 1;  // the host text, with the same bits
+    const std::vector<lins_key_pose> poses = poses_of(m->frames[a.slot]);
+    std::vector<int> sel;
+    r.n = 0;
+    if (!lins_select::select_radius(poses.data(), (int)poses.size(), a.centre, a.radius, a.pose_leaf, sel)) {
+      r.status = LINS_E_CAPACITY;
+      continue;
+    }
+    if (kind == kKpSelect) {
+      if ((int)sel.size() > stride) {
+        r.status = LINS_E_CAPACITY;
+        continue;
+      }
+      std::copy(sel.begin(), sel.end(), mine);
+    } else {
+      std::vector<int> list(mine, mine + n_list[k]);
+      lins_select::surround_update(list, sel);
+      if ((int)list.size() > stride) {
+        r.status = LINS_E_CAPACITY;
+        continue;
+      }
+      std::copy(list.begin(), list.end(), mine);
+      n_list[k] = (int32_t)list.size();
+    }
+    r.n = (int32_t)sel.size();
+  }
+  return LINS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lins_keyposes_select_batch(lins_ctx* ctx, int n, const lins_keyposes_query* queries, int32_t* ids, int stride, lins_keyposes_result* results) {
+  return kp_batch(ctx, kKpSelect, n, queries, nullptr, ids, stride, nullptr, nullptr, results);
+}
+
+int lins_keyposes_find_loop_batch(lins_ctx* ctx, int n, const lins_keyposes_loop_query* queries, int32_t* closest) {
+  return kp_batch(ctx, kKpLoop, n, nullptr, queries, nullptr, 0, nullptr, closest, nullptr);
+}
+
+int lins_keyposes_surround_batch(lins_ctx* ctx, int n, const lins_keyposes_query* queries, int32_t* lists, int stride, int32_t* n_list,
+                                 lins_keyposes_result* results) {
+  return kp_batch(ctx, kKpSurround, n, queries, nullptr, lists, stride, n_list, nullptr, results);
+}
+
+int lins_keyposes_set_mode(lins_ctx* ctx, int mode) {
+  if (!ctx || (mode != LINS_KEYPOSES_HOST && mode != LINS_KEYPOSES_DEVICE)) return LINS_E_ARG;
+  archive_of(ctx)->kp_mode = mode;
+  return LINS_OK;
+}
+
+int lins_keyposes_mode(lins_ctx* ctx) { return ctx ? archive_of(ctx)->kp_mode : LINS_E_ARG; }
+
+int lins_last_keyposes_stats(lins_ctx* ctx, float* device_ms, int32_t* host_entries, uint64_t* hits) {
+  if (!ctx) return LINS_E_ARG;
+  Archive* m = archive_of(ctx);
+  if (device_ms) *device_ms = m->kp_ms;
+  if (host_entries) *host_entries = m->kp_host;
+  if (hits) *hits = m->kp_hits;
   return LINS_OK;
 }
 

@@ -28,6 +28,9 @@ struct LmJob;
 struct LmState;
 struct ArChunk;    // keyframe_archive.h
 struct ArSplit;
+struct KpStale;
+struct KpEntry;
+struct KpOut;
 
 // ---- ieskf_kernels.hip: the any-size update kernel (global-memory grid or exhaustive search), re-projection, copy probe
 void launch_persistent(hipStream_t stream, int n, const DevParams& prm, const ScanDesc* descs, const float4* arena, const double* state_in, const double* cov_in, double* state_out, double* cov_out,
@@ -166,6 +169,16 @@ void launch_ar_keep(hipStream_t s, int j0, int n_jobs, int n_tiles, const int2* 
                     const float4* stage, int* tilecnt);
 void launch_ar_compact(hipStream_t s, int n_tiles, const int2* tiles, const LmJob* jobs, const LmState* states, const int* jflags, const float4* stage,
                        const int* tilecnt, float4* out);
+
+// ---- keypose_select_kernels.hip: which key frames a map or a loop closure takes (keyframe_archive.h Kp*, keypose_select_math.h)
+// the stale records into the mirror, one lane each
+void launch_kp_refresh(hipStream_t s, int n, const KpStale* stale, float4* poses, double* times);
+// radius search + pose grid, one workgroup per entry: entry k's ids to ids + k * stride (stride: the entries' own)
+void launch_kp_select(hipStream_t s, int n, const KpEntry* entries, const float4* poses, int* ids, KpOut* out);
+// ... and the list rule behind it: entry k's list at list_in + k * stride, the list afterwards at list_out + k * stride
+void launch_kp_surround(hipStream_t s, int n, const KpEntry* entries, const float4* poses, const int* list_in, int* list_out, int* scratch, KpOut* out);
+// the loop candidate: closest[k] = the hit of smallest (d, id) with fabs(time - now) > gap, or -1
+void launch_kp_find_loop(hipStream_t s, int n, const KpEntry* entries, const float4* poses, const double* times, int* closest);
 
 // ---- pose_graph_kernels.hip: the pose graph's solve, one workgroup per problem (pose_graph.h) ----
 // the poses and the cost of every problem as it stands (the first launch of a solve)

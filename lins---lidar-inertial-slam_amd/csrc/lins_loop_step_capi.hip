@@ -99,12 +99,31 @@ int lins_loop_step(lins_ctx* ctx, int n, const lins_loop_step_entry* entries, co
   m->assemble_ms = m->icp_ms = m->solve_ms = 0.f, m->candidates = m->aligned = m->closed = 0;
   // ---- detect (host work: keyframe_select.h, loop_step.h) ----
   std::vector<int> cand;  // entries that go to the assembly
+  // LINS_KEYPOSES_DEVICE: the candidates of the entries that have frames in one lins_keyposes_find_loop_batch
+  const bool on_device = lins_keyposes_mode(ctx) == LINS_KEYPOSES_DEVICE;
+  std::vector<int> dev_at(on_device ? (size_t)n : 0, -1);
+  std::vector<int32_t> dev_closest;
+  if (on_device) {
+    std::vector<lins_keyposes_loop_query> qs;
+    for (int k = 0; k < n; ++k) {
+      if (lins_archive_count(ctx, slots[k]) < 1) continue;
+      const float* c = &centre[3 * (size_t)k];
+      dev_at[k] = (int)qs.size();
+      qs.push_back(lins_keyposes_loop_query{lins_keyposes_query{slots[k], {c[0], c[1], c[2]}, prm->search_radius, 0.f}, entries[k].now, prm->min_gap_s});
+    }
+    dev_closest.assign(qs.size(), -1);
+    if (int rc = lins_keyposes_find_loop_batch(ctx, (int)qs.size(), qs.data(), dev_closest.data())) return rc;
+  }
   for (int k = 0; k < n; ++k) {
     lins_loop_step_result& r = out[k];
     std::memset(&r, 0, sizeof r);
     r.outcome = LINS_LOOP_NONE, r.latest_id = lins_archive_count(ctx, slots[k]) - 1, r.closest_id = -1;
     if (r.latest_id < 0) continue;
-    if (int rc = lins_archive_find_loop(ctx, slots[k], &centre[3 * (size_t)k], prm->search_radius, entries[k].now, prm->min_gap_s, &r.closest_id)) return rc;
+    if (on_device) {
+      r.closest_id = dev_closest[dev_at[k]];
+    } else if (int rc = lins_archive_find_loop(ctx, slots[k], &centre[3 * (size_t)k], prm->search_radius, entries[k].now, prm->min_gap_s, &r.closest_id)) {
+      return rc;
+    }
     int loops_left = 0, last_latest = -1, last_closest = -1;
     pose_graph_room(ctx, slots[k], nullptr, &loops_left, &last_latest, &last_closest);
     const int what = lins_loop::candidate(r.latest_id, r.closest_id, last_latest, last_closest);

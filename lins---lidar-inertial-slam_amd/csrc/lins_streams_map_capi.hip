@@ -300,10 +300,48 @@ int lins::streams_map_step_run(lins_ctx* ctx, int n, const int32_t* streams, con
   std::vector<int> batch;     // positions in the call of the entries that run
   std::vector<int32_t> which;  // ... and their streams = their slots
   std::vector<std::vector<int32_t>> lists;  // surround mode: the list each of them builds its map from
-  for (int k = 0; k < n; ++k) {
+  auto gate = [&](int k) {
     const bool no_record = !odom && !in.h_odom[streams[k]].valid;  // (the stream has no pose to map with: refused, entry alone)
-    int refused = no_record ? LINS_E_INPUT : time_of(k) - m->last_time[streams[k]] >= m->interval ? LINS_OK : LINS_MAP_STEP_SKIPPED;
-    if (!refused && m->surround) {  // LM:1247-1308: the radius selection around currentRobotPosPoint, then the list rule
+    return no_record ? LINS_E_INPUT : time_of(k) - m->last_time[streams[k]] >= m->interval ? LINS_OK : LINS_MAP_STEP_SKIPPED;
+  };
+  // LINS_KEYPOSES_DEVICE: the selection and the list rule of every gated entry in one lins_keyposes_surround_batch
+  const bool on_device = m->surround && lins_keyposes_mode(ctx) == LINS_KEYPOSES_DEVICE;
+  std::vector<int> dev_at(on_device ? (size_t)n : 0, -1);  // position k of the call -> its entry of the batched selection
+  std::vector<int32_t> dev_lists, dev_n;
+  std::vector<lins_keyposes_result> dev_res;
+  int dev_stride = 1;
+  if (on_device) {
+    std::vector<lins_keyposes_query> qs;
+    for (int k = 0; k < n; ++k) {
+      if (gate(k)) continue;
+      const int s = streams[k], have = lins_archive_count(ctx, s);
+      if (have < 0) return LINS_E_STATE;
+      dev_at[k] = (int)qs.size();
+      qs.push_back(lins_keyposes_query{s, {m->centre[3 * (size_t)s], m->centre[3 * (size_t)s + 1], m->centre[3 * (size_t)s + 2]}, m->radius, m->pose_leaf});
+      dev_stride = std::max(dev_stride, have + (have ? (int)m->lists[s].size() : 0));  // (survivors + selection: no longer)
+    }
+    const int nq = (int)qs.size();
+    dev_lists.assign((size_t)nq * dev_stride, 0), dev_n.assign((size_t)nq, 0), dev_res.resize((size_t)nq);
+    for (int j = 0; j < nq; ++j) {
+      const std::vector<int>& l = m->lists[qs[j].slot];
+      if (lins_archive_count(ctx, qs[j].slot) == 0) continue;  // (LM:1202: no key poses, nothing listed)
+      dev_n[j] = (int32_t)l.size();
+      std::copy(l.begin(), l.end(), dev_lists.begin() + (size_t)j * dev_stride);
+    }
+    if (int rc = lins_keyposes_surround_batch(ctx, nq, qs.data(), dev_lists.data(), dev_stride, dev_n.data(), dev_res.data())) return rc;
+  }
+  for (int k = 0; k < n; ++k) {
+    int refused = gate(k);
+    if (!refused && on_device) {
+      const int j = dev_at[k];
+      if (dev_res[j].status == LINS_E_CAPACITY) {
+        refused = LINS_E_CAPACITY;  // (the selection's box: the entry alone)
+      } else if (dev_res[j].status) {
+        return dev_res[j].status;
+      } else {
+        lists.emplace_back(dev_lists.begin() + (size_t)j * dev_stride, dev_lists.begin() + (size_t)j * dev_stride + dev_n[j]);
+      }
+    } else if (!refused && m->surround) {  // LM:1247-1308: the radius selection around currentRobotPosPoint, then the list rule
       const int s = streams[k], have = lins_archive_count(ctx, s);
       if (have < 0) return LINS_E_STATE;
       std::vector<int32_t> ds((size_t)std::max(have, 1));

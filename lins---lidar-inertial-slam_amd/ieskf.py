@@ -45,6 +45,8 @@ EXPORTS = [
     "lins_last_pose_graph_stats", "lins_pose_graph_apply_batch",
     "lins_loop_step_default_params", "lins_loop_step", "lins_loop_closed_cloud", "lins_last_loop_step_stats", "lins_streams_map_loop",
     "lins_local_map_build_surround", "lins_local_map_build_surround_streams", "lins_streams_map_surround", "lins_streams_map_surround_list",
+    "lins_keyposes_select_batch", "lins_keyposes_find_loop_batch", "lins_keyposes_surround_batch", "lins_keyposes_set_mode",
+    "lins_keyposes_mode", "lins_last_keyposes_stats",
 ]
 
 
@@ -471,6 +473,77 @@ class IeskfContext:
         L = lib()
         L.lins_archive_set_scan_chunk.argtypes = [C.c_void_p, C.c_int]
         self._check(L.lins_archive_set_scan_chunk(self._h, int(chunk_tiles)))
+
+    # -- key-pose selection on the device (include/lins_map.h lins_keyposes_*) -----------------------
+    def keyposes_select_batch(self, queries, stride=None):
+        """lins_archive_select_radius for a batch.  queries: tuples (slot, centre, radius, pose_leaf); stride: ids an entry
+        may return (default: the most frames a named slot holds).  Returns (ids, results): per entry its ids (int32 array,
+        None with a status) and dict(n, hits, status, host)."""
+        from ._ctypes_defs import KeyposesQueryC, KeyposesResultC, keyposes_query
+
+        n = len(queries)
+        arr = (KeyposesQueryC * max(n, 1))(*[keyposes_query(*q) for q in queries])
+        if stride is None:
+            stride = max([self.archive_count(q[0]) for q in queries] + [1])
+        ids = np.full((max(n, 1), max(int(stride), 1)), -1, np.int32)
+        out = (KeyposesResultC * max(n, 1))()
+        L = lib()
+        L.lins_keyposes_select_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(KeyposesQueryC), C.c_void_p, C.c_int, C.POINTER(KeyposesResultC)]
+        self._check(L.lins_keyposes_select_batch(self._h, n, arr, ids.ctypes.data, int(stride), out))
+        res = [out[k].as_dict() for k in range(n)]
+        return [None if r["status"] else ids[k, :r["n"]].copy() for k, r in enumerate(res)], res
+
+    def keyposes_find_loop_batch(self, queries):
+        """lins_archive_find_loop for a batch.  queries: tuples (slot, centre, radius, now, min_gap_s); returns the ids (-1: none)"""
+        from ._ctypes_defs import KeyposesLoopQueryC, keyposes_query
+
+        n = len(queries)
+        arr = (KeyposesLoopQueryC * max(n, 1))(*[KeyposesLoopQueryC(keyposes_query(s, c, r, 0.0), float(now), float(gap)) for s, c, r, now, gap in queries])
+        out = np.full(max(n, 1), -2, np.int32)
+        L = lib()
+        L.lins_keyposes_find_loop_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(KeyposesLoopQueryC), C.c_void_p]
+        self._check(L.lins_keyposes_find_loop_batch(self._h, n, arr, out.ctypes.data))
+        return out[:n].tolist()
+
+    def keyposes_surround_batch(self, queries, lists, stride=None):
+        """the selection and the surround list rule in one call.  queries as keyposes_select_batch, lists: per entry the
+        list of ids before; stride default: list + frames of the slot.  Returns (lists afterwards — the list before for an
+        entry with a status —, results)."""
+        from ._ctypes_defs import KeyposesQueryC, KeyposesResultC, keyposes_query
+
+        n = len(queries)
+        arr = (KeyposesQueryC * max(n, 1))(*[keyposes_query(*q) for q in queries])
+        if stride is None:
+            stride = max([self.archive_count(q[0]) + len(l) for q, l in zip(queries, lists)] + [1])
+        buf = np.zeros((max(n, 1), max(int(stride), 1)), np.int32)
+        cnt = np.zeros(max(n, 1), np.int32)
+        for k, l in enumerate(lists):
+            buf[k, :len(l)] = np.asarray(l, np.int32)
+            cnt[k] = len(l)
+        out = (KeyposesResultC * max(n, 1))()
+        L = lib()
+        L.lins_keyposes_surround_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(KeyposesQueryC), C.c_void_p, C.c_int, C.c_void_p, C.POINTER(KeyposesResultC)]
+        self._check(L.lins_keyposes_surround_batch(self._h, n, arr, buf.ctypes.data, int(stride), cnt.ctypes.data, out))
+        return [buf[k, :cnt[k]].tolist() for k in range(n)], [out[k].as_dict() for k in range(n)]
+
+    def keyposes_set_mode(self, mode):
+        """who selects for the surround step and the loop step: KEYPOSES_HOST (default) or KEYPOSES_DEVICE"""
+        L = lib()
+        L.lins_keyposes_set_mode.argtypes = [C.c_void_p, C.c_int]
+        self._check(L.lins_keyposes_set_mode(self._h, int(mode)))
+
+    def keyposes_mode(self):
+        L = lib()
+        L.lins_keyposes_mode.argtypes = [C.c_void_p]
+        return self._rc(L.lins_keyposes_mode(self._h))
+
+    def keyposes_stats(self):
+        """dict(device_ms, host_entries, hits) of the last batched selection"""
+        ms, host, hits = C.c_float(0), C.c_int32(0), C.c_uint64(0)
+        L = lib()
+        L.lins_last_keyposes_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
+        self._check(L.lins_last_keyposes_stats(self._h, C.byref(ms), C.byref(host), C.byref(hits)))
+        return dict(device_ms=ms.value, host_entries=host.value, hits=hits.value)
 
     # -- the loop-closure ICP on the device (include/lins_map.h lins_loop_icp_*) ---------------------
     def loop_icp(self, problems, params=None):
