@@ -86,6 +86,11 @@ int lins_last_map_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* queries);
  * last min(window, K) frames of a slot into the map frame (transformPointCloud, LM:627-650, f32 as written),
  * concatenates them oldest first — corner map: corner_i; surf map: surf_i then outlier_i — and VoxelGrid-filters them
  * (corner 0.2 m, surf 0.4 m, LM:1316-1323); it filters the raw scan as downsampleCurrentScan does (LM:1326-1349).
+ * A departure from the reference: "the last min(window, K) frames, each once".  The node's deque holds those frames only
+ * while every scan that finds it full brings a new key frame; latestFrameID starts at 0 and the rebuild branch never sets
+ * it, so the first scan that finds 50 entries without a new key frame (also after correctPoses() cleared the deques) pops
+ * the oldest frame and pushes the newest a second time (LM:1225-1239).  Both behaviours are asserted by
+ * tests/test_ref_mapnode.py and tests/test_gpu_ref_mapnode.py (DESIGN.md §5.3 "The mapping node's local map").
  * VoxelGrid is the project's contract: f32 box, stable order by PCL's linear voxel index, centroid
  * = sequential f32 sums in input order / (float)count, output in ascending voxel order, no minimum count.           */
 typedef struct lins_key_pose {

@@ -2,6 +2,9 @@
 // device build of lins_local_map_build (local_map_kernels.hip) is checked against, bit for bit.
 //   extractSurroundingKeyFrames  LM:1201-1324  last min(window, K) key frames -> map frame (transformPointCloud,
 //                                              LM:627-650), concatenated oldest first, VoxelGrid 0.2 / 0.4 m
+//                                              (each frame once: where the node's deque doubles its newest frame,
+//                                              LM:1225-1239 with a stale latestFrameID, is a stated departure,
+//                                              include/lins_map.h; the caller may pass any list of frames)
 //   downsampleCurrentScan        LM:1326-1349  corner 0.2, surf 0.4, outlier 0.4, surfTotal = 0.4 of (surfDS ++ outlierDS)
 // VoxelGrid is the contract of frontend.cpp's voxel_grid with the leaf as an argument.
 #include <algorithm>

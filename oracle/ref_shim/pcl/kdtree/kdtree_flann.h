@@ -55,7 +55,8 @@ class KdTreeFLANN {
   }
 
   // every point within `radius` (by the same f32 distance), ascending (distance, index); brute force — the reference
-  // only calls it from its key-frame bookkeeping, which the _ref drivers never run
+  // calls it from its key-frame bookkeeping (LM:994, 1053, 1252: a few thousand key poses), which ref_mapnode_driver.cpp
+  // runs.  FLANN's order of equal distances is stated, not pinned.
   int radiusSearch(const PointT& p, double radius, std::vector<int>& k_indices, std::vector<float>& k_sqr_distances, unsigned max_nn = 0) const {
     std::vector<std::pair<float, int> > hits;
     const float r2 = static_cast<float>(radius * radius);

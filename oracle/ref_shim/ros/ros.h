@@ -37,6 +37,12 @@ struct Published {
     return m;
   }
 };
+// getNumSubscribers() per topic, 0 unless a driver sets it: the mapping node publishes its global map and its loop
+// closure's clouds only to a subscriber (LM:959-1031, 1103, 1144)
+inline std::map<std::string, unsigned>& subscribers() {
+  static thread_local std::map<std::string, unsigned> m;
+  return m;
+}
 }  // namespace lins_ref_shim
 namespace ros {
 class Subscriber {};
@@ -48,7 +54,11 @@ class Publisher {
   void publish(const M& msg) const {
     ::lins_ref_shim::Published<M>::by_topic()[topic_] = msg;
   }
-  unsigned getNumSubscribers() const { return 0; }
+  unsigned getNumSubscribers() const {
+    const std::map<std::string, unsigned>& m = ::lins_ref_shim::subscribers();
+    const std::map<std::string, unsigned>::const_iterator it = m.find(topic_);
+    return it == m.end() ? 0u : it->second;
+  }
 
  private:
   std::string topic_;

@@ -1,6 +1,6 @@
 // <tf/transform_datatypes.h> — STAND-IN (oracle/ref_shim/README.md): the names lidar_mapping_node.cpp's publishing and
-// message-handling methods use.  Never executed by the _ref driver (it runs the scan-to-map optimisation only); the
-// conversions return identities.
+// message-handling methods use.  The conversions return identities: ref_mapnode_driver.cpp runs publishTF / publishXYZTF
+// as part of run() and reads nothing they publish; the message handlers are never run.
 #ifndef LINS_REF_SHIM_TF_DATATYPES_
 #define LINS_REF_SHIM_TF_DATATYPES_
 #include <geometry_msgs/Quaternion.h>

@@ -15,7 +15,7 @@ import map_synth as ms
 
 pytestmark = pytest.mark.gpu
 defs = importlib.import_module("lins---lidar-inertial-slam_amd._ctypes_defs")
-BAR = 2e-5
+BAR = ms.SCAN2MAP_BAR
 
 
 def bits(a):
