@@ -27,14 +27,14 @@ namespace {
 struct Archive {
   int n_slots = 0, max_frames = 0, chunk = kArScanChunk;
   long long max_points = 0, used = 0;
-  float4* d_arena = nullptr;
+  DevBuf<float4> d_arena;
   std::vector<std::vector<ArFrame>> frames;  // [slot][id]
   // assembly arenas (grown, never shrunk)
-  float4 *d_stage = nullptr, *d_out = nullptr;
-  unsigned *d_ka = nullptr, *d_kb = nullptr;
-  int *d_va = nullptr, *d_vb = nullptr, *d_starts = nullptr, *d_hist = nullptr, *d_tilecnt = nullptr, *d_csum = nullptr;
-  char *d_tab = nullptr, *h_tab = nullptr, *h_states = nullptr;
-  size_t cap_stage = 0, cap_sort = 0, cap_out = 0, cap_hist = 0, cap_tilecnt = 0, cap_csum = 0, cap_tab = 0, cap_htab = 0, cap_hstates = 0;
+  DevBuf<float4> d_stage, d_out;
+  DevBuf<unsigned> d_ka, d_kb;  // (d_ka, d_kb, d_va, d_vb, d_starts: one group, d_ka answers)
+  DevBuf<int> d_va, d_vb, d_starts, d_hist, d_tilecnt, d_csum;
+  DevBuf<char> d_tab;  // (bytes)
+  PinBuf<char> h_tab, h_states;
   // the last assembly
   bool built = false;
   unsigned long long serial = 0;  // assemblies started so far
@@ -45,52 +45,23 @@ struct Archive {
   uint64_t points_in = 0;
   // the key-pose selection on the device (lins_keyposes_*): the mirror of the slots' key poses and times, frame id of slot
   // s at s * max_frames + id, current below stale_from[s]; one table up, one block of results down (pinned staging)
-  float4* d_kp_pose = nullptr;
-  double* d_kp_time = nullptr;
+  DevBuf<float4> d_kp_pose;
+  DevBuf<double> d_kp_time;
   std::vector<int> stale_from;  // [slot]
-  char *d_kp_up = nullptr, *h_kp_up = nullptr, *d_kp_down = nullptr, *h_kp_down = nullptr;
-  int* d_kp_scratch = nullptr;
-  size_t cap_kp_up = 0, cap_kp_hup = 0, cap_kp_down = 0, cap_kp_hdown = 0, cap_kp_scratch = 0;
+  DevBuf<char> d_kp_up, d_kp_down;  // (bytes)
+  PinBuf<char> h_kp_up, h_kp_down;
+  DevBuf<int> d_kp_scratch;
   int kp_mode = LINS_KEYPOSES_HOST, kp_host = 0;
   float kp_ms = 0.f;
   uint64_t kp_hits = 0;
 };
 
-void archive_free(void* p) {
-  Archive* m = (Archive*)p;
-  (void)hipFree(m->d_arena), (void)hipFree(m->d_stage), (void)hipFree(m->d_out), (void)hipFree(m->d_ka), (void)hipFree(m->d_kb);
-  (void)hipFree(m->d_va), (void)hipFree(m->d_vb), (void)hipFree(m->d_starts), (void)hipFree(m->d_hist), (void)hipFree(m->d_tilecnt);
-  (void)hipFree(m->d_csum), (void)hipFree(m->d_tab), (void)hipHostFree(m->h_tab), (void)hipHostFree(m->h_states);
-  (void)hipFree(m->d_kp_pose), (void)hipFree(m->d_kp_time), (void)hipFree(m->d_kp_up), (void)hipFree(m->d_kp_down), (void)hipFree(m->d_kp_scratch);
-  (void)hipHostFree(m->h_kp_up), (void)hipHostFree(m->h_kp_down);
-  delete m;
-}
+void archive_free(void* p) { delete (Archive*)p; }
 
 Archive* archive_of(lins_ctx* ctx) {
-  void** slot = map_archive_slot(ctx, archive_free);
+  void** slot = map_slot(ctx, kSlotArchive, archive_free);
   if (!*slot) *slot = new Archive();
   return (Archive*)*slot;
-}
-
-template <class T>
-int grow(lins_ctx* ctx, T** p, size_t* cap, size_t need) {
-  need = std::max<size_t>(need, 1);
-  if (*cap >= need) return LINS_OK;
-  (void)hipFree(*p);
-  *p = nullptr, *cap = 0;
-  HIP_TRY(ctx, hipMalloc((void**)p, need * sizeof(T)));
-  *cap = need;
-  return LINS_OK;
-}
-template <class T>
-int grow_pinned(lins_ctx* ctx, T** p, size_t* cap, size_t need) {
-  need = std::max<size_t>(need, 1);
-  if (*cap >= need) return LINS_OK;
-  (void)hipHostFree(*p);
-  *p = nullptr, *cap = 0;
-  HIP_TRY(ctx, hipHostMalloc((void**)p, need * sizeof(T)));
-  *cap = need;
-  return LINS_OK;
 }
 
 void set_pose(ArFrame& f, const lins_key_pose& p) {  // updateTransformPointCloudSinCos (LM:612-624), as the local map's set_pose
@@ -135,12 +106,12 @@ int lins_archive_init(lins_ctx* ctx, int n_slots, int max_frames_per_slot, long 
   HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
   Archive* m = archive_of(ctx);
   HIP_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));  // (a push_scans copy may still write the old arena)
-  (void)hipFree(m->d_arena), (void)hipFree(m->d_kp_pose), (void)hipFree(m->d_kp_time);
-  m->d_arena = nullptr, m->d_kp_pose = nullptr, m->d_kp_time = nullptr, m->n_slots = 0, m->built = false, m->used = 0;
+  m->d_arena.reset(), m->d_kp_pose.reset(), m->d_kp_time.reset();
+  m->n_slots = 0, m->built = false, m->used = 0;
   m->frames.clear();
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_arena, (size_t)max_points_total * sizeof(float4)));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_kp_pose, (size_t)n_slots * max_frames_per_slot * sizeof(float4)));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_kp_time, (size_t)n_slots * max_frames_per_slot * sizeof(double)));
+  BUF_TRY(ctx, m->d_arena.grow((size_t)max_points_total));
+  BUF_TRY(ctx, m->d_kp_pose.grow((size_t)n_slots * max_frames_per_slot));
+  BUF_TRY(ctx, m->d_kp_time.grow((size_t)n_slots * max_frames_per_slot));
   m->n_slots = n_slots, m->max_frames = max_frames_per_slot, m->max_points = max_points_total;
   m->frames.assign(n_slots, {});
   m->stale_from.assign(n_slots, 0);
@@ -378,9 +349,8 @@ int lins_archive_assemble(lins_ctx* ctx, int n, const lins_submap_spec* specs, l
                o_blocks = align64(o_segs + segs.size() * sizeof(LmSeg)), o_tiles = align64(o_blocks + blocks.size() * sizeof(int2)),
                o_flags = align64(o_tiles + tiles.size() * sizeof(int2)), o_chunks = align64(o_flags + n * sizeof(int)),
                o_splits = align64(o_chunks + chunks.size() * sizeof(ArChunk)), tab_bytes = align64(o_splits + splits.size() * sizeof(ArSplit));
-  int rc;
-  if ((rc = grow_pinned(ctx, &m->h_tab, &m->cap_htab, tab_bytes))) return rc;
-  if ((rc = grow_pinned(ctx, &m->h_states, &m->cap_hstates, n * sizeof(LmState)))) return rc;
+  BUF_TRY(ctx, m->h_tab.grow(tab_bytes));
+  BUF_TRY(ctx, m->h_states.grow(n * sizeof(LmState)));
   auto put = [&](size_t o, const void* p, size_t bytes) {
     if (bytes) std::memcpy(m->h_tab + o, p, bytes);
   };
@@ -388,19 +358,14 @@ int lins_archive_assemble(lins_ctx* ctx, int n, const lins_submap_spec* specs, l
   put(o_segs, segs.data(), segs.size() * sizeof(LmSeg)), put(o_blocks, blocks.data(), blocks.size() * sizeof(int2));
   put(o_tiles, tiles.data(), tiles.size() * sizeof(int2)), put(o_flags, jflags.data(), n * sizeof(int));
   put(o_chunks, chunks.data(), chunks.size() * sizeof(ArChunk)), put(o_splits, splits.data(), splits.size() * sizeof(ArSplit));
-  if ((rc = grow(ctx, &m->d_tab, &m->cap_tab, tab_bytes)) || (rc = grow(ctx, &m->d_stage, &m->cap_stage, stage_total)) ||
-      (rc = grow(ctx, &m->d_out, &m->cap_out, out_total)) || (rc = grow(ctx, &m->d_hist, &m->cap_hist, vg_tiles * 256)) ||
-      (rc = grow(ctx, &m->d_tilecnt, &m->cap_tilecnt, tiles_total)) || (rc = grow(ctx, &m->d_csum, &m->cap_csum, chunks.size())))
-    return rc;
-  if (m->cap_sort < std::max<size_t>(sort_total, 1)) {  // the sort's scratch: the extent of the VoxelGrid jobs' staging
-    size_t c[5] = {0, 0, 0, 0, 0};
-    (void)hipFree(m->d_ka), (void)hipFree(m->d_kb), (void)hipFree(m->d_va), (void)hipFree(m->d_vb), (void)hipFree(m->d_starts);
-    m->d_ka = m->d_kb = nullptr, m->d_va = m->d_vb = m->d_starts = nullptr, m->cap_sort = 0;
-    if ((rc = grow(ctx, &m->d_ka, &c[0], sort_total)) || (rc = grow(ctx, &m->d_kb, &c[1], sort_total)) || (rc = grow(ctx, &m->d_va, &c[2], sort_total)) ||
-        (rc = grow(ctx, &m->d_vb, &c[3], sort_total)) || (rc = grow(ctx, &m->d_starts, &c[4], sort_total)))
-      return rc;
-    m->cap_sort = c[0];
-  }
+  BUF_TRY(ctx, m->d_tab.grow(tab_bytes));
+  BUF_TRY(ctx, m->d_stage.grow(stage_total));
+  BUF_TRY(ctx, m->d_out.grow(out_total));
+  BUF_TRY(ctx, m->d_hist.grow(vg_tiles * 256));
+  BUF_TRY(ctx, m->d_tilecnt.grow(tiles_total));
+  BUF_TRY(ctx, m->d_csum.grow(chunks.size()));
+  // the sort's scratch: the extent of the VoxelGrid jobs' staging
+  BUF_TRY(ctx, grow_all(m->d_ka, sort_total, m->d_kb, sort_total, m->d_va, sort_total, m->d_vb, sort_total, m->d_starts, sort_total));
   hipStream_t st = ctx_stream(ctx);
   hipEvent_t e0, e1;
   ctx_events(ctx, &e0, &e1);
@@ -439,7 +404,7 @@ int lins_archive_assemble(lins_ctx* ctx, int n, const lins_submap_spec* specs, l
   HIP_TRY(ctx, hipStreamSynchronize(st));
   HIP_TRY(ctx, hipEventElapsedTime(&m->ms, e0, e1));
   m->points_in = pts_in;
-  const LmState* S = (const LmState*)m->h_states;
+  const LmState* S = (const LmState*)m->h_states.get();
   m->off.assign(n, 0);
   m->info.assign(n, lins_submap_info{});
   m->filtered.assign(n, 0);
@@ -540,10 +505,15 @@ int kp_batch(lins_ctx* ctx, KpKind kind, int n, const lins_keyposes_query* qs, c
   const size_t o_stale = align64(n * sizeof(KpEntry)), o_lists = align64(o_stale + stale.size() * sizeof(KpStale)),
                up_bytes = align64(o_lists + (kind == kKpSurround ? out_ints * sizeof(int) : 0));
   const size_t o_ints = align64(n * sizeof(KpOut)), down_bytes = align64(o_ints + out_ints * sizeof(int));
-  int rc;
-  if ((rc = grow_pinned(ctx, &m->h_kp_up, &m->cap_kp_hup, up_bytes)) || (rc = grow(ctx, &m->d_kp_up, &m->cap_kp_up, up_bytes)) ||
-      (rc = grow_pinned(ctx, &m->h_kp_down, &m->cap_kp_hdown, down_bytes)) || (rc = grow(ctx, &m->d_kp_down, &m->cap_kp_down, down_bytes)) ||
-      (rc = grow(ctx, &m->d_kp_scratch, &m->cap_kp_scratch, (size_t)scratch_total))) {
+  auto grow_staging = [&]() -> int {
+    BUF_TRY(ctx, m->h_kp_up.grow(up_bytes));
+    BUF_TRY(ctx, m->d_kp_up.grow(up_bytes));
+    BUF_TRY(ctx, m->h_kp_down.grow(down_bytes));
+    BUF_TRY(ctx, m->d_kp_down.grow(down_bytes));
+    BUF_TRY(ctx, m->d_kp_scratch.grow((size_t)scratch_total));
+    return LINS_OK;
+  };
+  if (const int rc = grow_staging()) {
     std::fill(m->stale_from.begin(), m->stale_from.end(), 0);  // (the records packed above did not go up)
     return rc;
   }
@@ -553,8 +523,8 @@ int kp_batch(lins_ctx* ctx, KpKind kind, int n, const lins_keyposes_query* qs, c
   hipStream_t st = ctx_stream(ctx);
   hipEvent_t e0, e1;
   ctx_events(ctx, &e0, &e1);
-  const KpEntry* d_entries = (const KpEntry*)m->d_kp_up;
-  KpOut* d_out = (KpOut*)m->d_kp_down;
+  const KpEntry* d_entries = (const KpEntry*)m->d_kp_up.get();
+  KpOut* d_out = (KpOut*)m->d_kp_down.get();
   int* d_ints = (int*)(m->d_kp_down + o_ints);
   hipError_t err = hipMemcpyAsync(m->d_kp_up, m->h_kp_up, up_bytes, hipMemcpyHostToDevice, st);
   if (err == hipSuccess) err = hipEventRecord(e0, st);
@@ -573,7 +543,7 @@ int kp_batch(lins_ctx* ctx, KpKind kind, int n, const lins_keyposes_query* qs, c
     return ctx_fail_hip(ctx, err, "lins_keyposes batch");
   }
   HIP_TRY(ctx, hipEventElapsedTime(&m->kp_ms, e0, e1));
-  const KpOut* O = (const KpOut*)m->h_kp_down;
+  const KpOut* O = (const KpOut*)m->h_kp_down.get();
   const int* I = (const int*)(m->h_kp_down + o_ints);
   if (kind == kKpLoop) {
     for (int k = 0; k < n; ++k) closest[k] = I[k];

@@ -562,9 +562,6 @@ void lins_destroy(lins_ctx* ctx) {
   (void)hipFree(ctx->d_meta_in), (void)hipFree(ctx->d_meta_out);  // (d_state_in, d_cov_in, d_desc; d_state_out, d_cov_out, d_out)
   (void)hipFree(ctx->d_lin);
   (void)hipFree(ctx->d_a6);
-  (void)hipFree(ctx->d_prof);
-  (void)hipFree(ctx->d_aux);
-  (void)hipFree(ctx->d_jobs);
   fe_free(ctx);
   streams_free(ctx);
   if (ctx->map_state && ctx->map_state_free) ctx->map_state_free(ctx->map_state);
@@ -586,10 +583,9 @@ void lins_destroy(lins_ctx* ctx) {
   }
   pipe_free(ctx);
   rccl_free(ctx);
-  if (ctx->ev_copy) (void)hipEventDestroy(ctx->ev_copy);
   if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  delete ctx;  // (with it what was allocated after lins_create: lins_buf.h members, the device still current)
 }
 
 int lins_set_search(lins_ctx* ctx, const char* mode) {
@@ -972,7 +968,7 @@ int lins_ieskf_update_batch(lins_ctx* ctx, int n, const lins_scan_pair* in, lins
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (!ctx->copy_stream) {
     HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_copy, hipEventDisableTiming));
+    BUF_TRY(ctx, ctx->ev_copy.create(hipEventDisableTiming));
   }
   ctx->n_uploaded = 0, ctx->ran = false;
   // the uploads below overwrite the inputs of whatever is still queued on the compute stream (an earlier asynchronous

@@ -12,15 +12,7 @@ using lins_filt::kAux;
 
 namespace lins {
 
-void streams_boot_free(lins_ctx* ctx) {
-  auto& b = ctx->st.b;
-  void* dev[] = {b.d_tmpl, b.d_pre, b.d_rows, b.d_scan, b.d_ints, b.d_desc, b.d_tab, b.d_icp_in, b.d_icp_out, b.d_out};
-  for (void* p : dev) (void)hipFree(p);
-  (void)hipHostFree(b.h_rows), (void)hipHostFree(b.h_scan), (void)hipHostFree(b.h_ints), (void)hipHostFree(b.h_out);
-  for (hipEvent_t e : b.ev)
-    if (e) (void)hipEventDestroy(e);
-  b = lins_ctx::Streams::Boot{};
-}
+void streams_boot_free(lins_ctx* ctx) { ctx->st.b = lins_ctx::Streams::Boot{}; }
 
 int streams_boot_check(lins_ctx* ctx, const int32_t* n_imu, const double* const* imu) {
   auto& t = ctx->st;
@@ -132,21 +124,21 @@ int lins_streams_machine_init(lins_ctx* ctx, const lins_boot_params* prm) {
   streams_boot_free(ctx);
   auto& b = t.b;
   const size_t n = (size_t)t.n;
-  HIP_TRY(ctx, hipMalloc((void**)&b.d_tmpl, kTmpl * 8));
-  HIP_TRY(ctx, hipMalloc((void**)&b.d_pre, n * kPre * 8));
-  HIP_TRY(ctx, hipMalloc((void**)&b.d_rows, n * LINS_STREAMS_IMU_MAX * 7 * 8));
-  HIP_TRY(ctx, hipHostMalloc((void**)&b.h_rows, n * LINS_STREAMS_IMU_MAX * 7 * 8));
-  HIP_TRY(ctx, hipMalloc((void**)&b.d_scan, n * 8 * 8));
-  HIP_TRY(ctx, hipHostMalloc((void**)&b.h_scan, n * 8 * 8));
-  HIP_TRY(ctx, hipMalloc((void**)&b.d_ints, n * 4 * sizeof(int)));
-  HIP_TRY(ctx, hipHostMalloc((void**)&b.h_ints, n * 4 * sizeof(int)));
-  HIP_TRY(ctx, hipMalloc((void**)&b.d_desc, n * sizeof(ScanDesc)));
-  HIP_TRY(ctx, hipMalloc((void**)&b.d_tab, n * sizeof(GridTables)));
-  HIP_TRY(ctx, hipMalloc((void**)&b.d_icp_in, n * 19 * 8));
-  HIP_TRY(ctx, hipMalloc((void**)&b.d_icp_out, n * 19 * 8));
-  HIP_TRY(ctx, hipMalloc((void**)&b.d_out, n * sizeof(OutRec)));
-  HIP_TRY(ctx, hipHostMalloc((void**)&b.h_out, n * sizeof(OutRec)));
-  for (hipEvent_t& e : b.ev) HIP_TRY(ctx, hipEventCreate(&e));
+  BUF_TRY(ctx, b.d_tmpl.grow(kTmpl));
+  BUF_TRY(ctx, b.d_pre.grow(n * kPre));
+  BUF_TRY(ctx, b.d_rows.grow(n * LINS_STREAMS_IMU_MAX * 7));
+  BUF_TRY(ctx, b.h_rows.grow(n * LINS_STREAMS_IMU_MAX * 7));
+  BUF_TRY(ctx, b.d_scan.grow(n * 8));
+  BUF_TRY(ctx, b.h_scan.grow(n * 8));
+  BUF_TRY(ctx, b.d_ints.grow(n * 4));
+  BUF_TRY(ctx, b.h_ints.grow(n * 4));
+  BUF_TRY(ctx, b.d_desc.grow(n));
+  BUF_TRY(ctx, b.d_tab.grow(n));
+  BUF_TRY(ctx, b.d_icp_in.grow(n * 19));
+  BUF_TRY(ctx, b.d_icp_out.grow(n * 19));
+  BUF_TRY(ctx, b.d_out.grow(n));
+  BUF_TRY(ctx, b.h_out.grow(n));
+  for (Event& e : b.ev) BUF_TRY(ctx, e.create());
   b.prm = *prm;
   // the template: what lins_filter_init forms, and the variances reset(1) re-installs (as lins_streams_filter_set)
   b.h_tmpl.assign(kTmpl, 0.0);

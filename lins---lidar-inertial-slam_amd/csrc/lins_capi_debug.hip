@@ -15,14 +15,13 @@ extern "C" {
 int lins_debug_math(lins_ctx* ctx, int op, int n, const double* in, int n_in, double* out, int n_out) {
   if (ctx && in && out && op >= 100 && op <= 111 && n >= 1 && n_in >= 9 && n_out == 2) {  // cycle microbenchmarks, n blocks
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    double *d_in = nullptr, *d_out = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d_in, 9 * 8));
-    HIP_TRY(ctx, hipMalloc((void**)&d_out, (size_t)n * 2 * 8));
+    DevBuf<double> d_in, d_out;
+    BUF_TRY(ctx, d_in.grow(9));
+    BUF_TRY(ctx, d_out.grow((size_t)n * 2));
     HIP_TRY(ctx, hipMemcpy(d_in, in, 9 * 8, hipMemcpyHostToDevice));
     launch_debug_cycles(ctx->stream, op, n, d_in, d_out);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(out, d_out, (size_t)n * 2 * 8, hipMemcpyDeviceToHost));
-    (void)hipFree(d_in), (void)hipFree(d_out);
     return LINS_OK;
   }
   static const int kIn[20] = {4, 3, 3, 37, 38, 4, 24, 42, 42, 448, 448, 42, 42, 3, 4, 4, 43, 43, 72, 72};
@@ -30,10 +29,10 @@ int lins_debug_math(lins_ctx* ctx, int op, int n, const double* in, int n_in, do
   if (!ctx || !in || !out || op < 0 || op > 19 || n < 0 || n_in != kIn[op] || n_out != kOut[op]) return LINS_E_ARG;
   if (n == 0) return LINS_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  double *d_in = nullptr, *d_out = nullptr;
-  LmCarry* d_lm = nullptr;
-  HIP_TRY(ctx, hipMalloc((void**)&d_in, (size_t)n * n_in * 8));
-  hipError_t e = hipMalloc((void**)&d_out, (size_t)n * n_out * 8);
+  DevBuf<double> d_in, d_out;
+  DevBuf<LmCarry> d_lm;
+  BUF_TRY(ctx, d_in.grow((size_t)n * n_in));
+  hipError_t e = (hipError_t)d_out.grow((size_t)n * n_out);
   if (e == hipSuccess) e = hipMemcpyAsync(d_in, in, (size_t)n * n_in * 8, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
     if (op == 9 || op == 10)
@@ -43,7 +42,7 @@ int lins_debug_math(lins_ctx* ctx, int op, int n, const double* in, int n_in, do
     else if (op == 16 || op == 17)
       launch_debug_icp_gn(ctx->stream, n, op == 17, d_in, d_out);
     else if (op == 18 || op == 19) {  // lm_step_from_sums: one thread (lm_math.h) / over a wave (lm_wave.h); 72 in, 44 out
-      e = hipMalloc(&d_lm, (size_t)n * sizeof(LmCarry));
+      e = (hipError_t)d_lm.grow((size_t)n);
       if (e == hipSuccess) launch_debug_lm_step(ctx->stream, n, op == 19, d_in, d_out, d_lm);
     }
     else
@@ -52,7 +51,6 @@ int lins_debug_math(lins_ctx* ctx, int op, int n, const double* in, int n_in, do
   }
   if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * n_out * 8, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_in), (void)hipFree(d_out), (void)hipFree(d_lm);
   if (e != hipSuccess) return ctx_fail_hip(ctx, e, "lins_debug_math");
   return LINS_OK;
 }
@@ -87,7 +85,7 @@ int lins_debug_phase_profile(lins_ctx* ctx, int enable, long long* out, int n_sc
   if (enable && !ctx->d_prof) {
     // (16 words per scan, then — behind the records of the launch — 32 words per scan of per-wave phase ticks, written by
     // libraries built with -DLINS_PROF2=k: lins_debug_wave_phases)
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_prof, (size_t)ctx->max_batch * 80 * sizeof(long long)));
+    BUF_TRY(ctx, ctx->d_prof.grow((size_t)ctx->max_batch * 80));
     HIP_TRY(ctx, hipMemset(ctx->d_prof, 0, (size_t)ctx->max_batch * 80 * sizeof(long long)));
   }
   if (out && ctx->d_prof) {
@@ -95,10 +93,7 @@ int lins_debug_phase_profile(lins_ctx* ctx, int enable, long long* out, int n_sc
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(out, ctx->d_prof, (size_t)n_scans * 16 * sizeof(long long), hipMemcpyDeviceToHost));
   }
-  if (!enable && ctx->d_prof) {
-    (void)hipFree(ctx->d_prof);
-    ctx->d_prof = nullptr;
-  }
+  if (!enable) ctx->d_prof.reset();
   return LINS_OK;
 }
 
@@ -242,15 +237,12 @@ int lins_debug_loop_icp_step(lins_ctx* ctx, int n, int blocks_per_problem, const
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t np = (size_t)n * blocks_per_problem * lins_licp::kSums;
-  LoopDev* d_probs = nullptr;
-  lins_licp::State* d_states = nullptr;
-  double* d_partials = nullptr;
-  int* d_running = nullptr;
+  DevBuf<LoopDev> d_probs;
+  DevBuf<lins_licp::State> d_states;
+  DevBuf<double> d_partials;
+  DevBuf<int> d_running;
   int running = 0;
-  hipError_t e = hipMalloc((void**)&d_probs, (size_t)n * sizeof(LoopDev));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_states, (size_t)n * sizeof(lins_licp::State));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_partials, np * sizeof(double));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_running, sizeof(int));
+  hipError_t e = (hipError_t)grow_all(d_probs, (size_t)n, d_states, (size_t)n, d_partials, np, d_running, 1);
   if (e == hipSuccess) e = hipMemcpyAsync(d_probs, probs.data(), (size_t)n * sizeof(LoopDev), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_states, st.data(), (size_t)n * sizeof(lins_licp::State), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_partials, partials, np * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
@@ -262,7 +254,6 @@ int lins_debug_loop_icp_step(lins_ctx* ctx, int n, int blocks_per_problem, const
   if (e == hipSuccess) e = hipMemcpyAsync(st.data(), d_states, (size_t)n * sizeof(lins_licp::State), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(&running, d_running, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_probs), (void)hipFree(d_states), (void)hipFree(d_partials), (void)hipFree(d_running);
   if (e != hipSuccess) return ctx_fail_hip(ctx, e, "lins_debug_loop_icp_step");
   for (int k = 0; k < n; ++k) lins_licp::state_to_public(st[k], states[k]);  // (every problem: what the kernel left)
   if (still_running) *still_running = running;
@@ -281,14 +272,11 @@ int lins_debug_cov_update(lins_ctx* ctx, int path, int n, const double* P, const
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   std::vector<OutRec> recs(n, OutRec{});
   for (int k = 0; k < n; ++k) recs[k].diverged = diverged[k] != 0;
-  double *d_P = nullptr, *d_sums = nullptr, *d_out = nullptr;
-  int* d_div = nullptr;
-  OutRec* d_recs = nullptr;
-  hipError_t e = hipMalloc((void**)&d_P, (size_t)n * 324 * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_sums, (size_t)n * 21 * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_out, (size_t)n * 324 * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_div, (size_t)n * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_recs, (size_t)n * sizeof(OutRec));
+  const size_t c = (size_t)n;
+  DevBuf<double> d_P, d_sums, d_out;
+  DevBuf<int> d_div;
+  DevBuf<OutRec> d_recs;
+  hipError_t e = (hipError_t)grow_all(d_P, c * 324, d_sums, c * 21, d_out, c * 324, d_div, c, d_recs, c);
   if (e == hipSuccess) e = hipMemcpyAsync(d_P, P, (size_t)n * 324 * 8, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_sums, sums, (size_t)n * 21 * 8, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_div, diverged, (size_t)n * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
@@ -308,7 +296,6 @@ int lins_debug_cov_update(lins_ctx* ctx, int path, int n, const double* P, const
   }
   if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * 324 * 8, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_P), (void)hipFree(d_sums), (void)hipFree(d_out), (void)hipFree(d_div), (void)hipFree(d_recs);
   if (e != hipSuccess) return ctx_fail_hip(ctx, e, "lins_debug_cov_update");
   return LINS_OK;
 }

@@ -9,31 +9,23 @@ using namespace lins_filt;
 
 namespace lins {
 
-void streams_filter_free(lins_ctx* ctx) {
-  auto& f = ctx->st.f;
-  void* dev[] = {f.d_state, f.d_cov, f.d_noise, f.d_aux, f.d_gstate, f.d_imu, f.d_ints};
-  for (void* p : dev) (void)hipFree(p);
-  (void)hipHostFree(f.h_imu), (void)hipHostFree(f.h_ints);
-  for (hipEvent_t e : f.ev)
-    if (e) (void)hipEventDestroy(e);
-  f = lins_ctx::Streams::Filter{};
-}
+void streams_filter_free(lins_ctx* ctx) { ctx->st.f = lins_ctx::Streams::Filter{}; }
 
 int streams_filter_alloc(lins_ctx* ctx) {
   auto& t = ctx->st;
   auto& f = t.f;
   if (f.d_state) return LINS_OK;
   const size_t n = (size_t)t.n;
-  HIP_TRY(ctx, hipMalloc((void**)&f.d_state, n * 19 * 8));
-  HIP_TRY(ctx, hipMalloc((void**)&f.d_cov, n * 324 * 8));
-  HIP_TRY(ctx, hipMalloc((void**)&f.d_noise, n * 144 * 8));
-  HIP_TRY(ctx, hipMalloc((void**)&f.d_aux, n * kAux * 8));
-  HIP_TRY(ctx, hipMalloc((void**)&f.d_gstate, n * 19 * 8));
-  HIP_TRY(ctx, hipMalloc((void**)&f.d_imu, n * LINS_STREAMS_IMU_MAX * 7 * 8));
-  HIP_TRY(ctx, hipHostMalloc((void**)&f.h_imu, n * LINS_STREAMS_IMU_MAX * 7 * 8));
-  HIP_TRY(ctx, hipMalloc((void**)&f.d_ints, n * 3 * sizeof(int)));
-  HIP_TRY(ctx, hipHostMalloc((void**)&f.h_ints, n * 3 * sizeof(int)));
-  for (hipEvent_t& e : f.ev) HIP_TRY(ctx, hipEventCreate(&e));
+  BUF_TRY(ctx, f.d_state.grow(n * 19));
+  BUF_TRY(ctx, f.d_cov.grow(n * 324));
+  BUF_TRY(ctx, f.d_noise.grow(n * 144));
+  BUF_TRY(ctx, f.d_aux.grow(n * kAux));
+  BUF_TRY(ctx, f.d_gstate.grow(n * 19));
+  BUF_TRY(ctx, f.d_imu.grow(n * LINS_STREAMS_IMU_MAX * 7));
+  BUF_TRY(ctx, f.h_imu.grow(n * LINS_STREAMS_IMU_MAX * 7));
+  BUF_TRY(ctx, f.d_ints.grow(n * 3));
+  BUF_TRY(ctx, f.h_ints.grow(n * 3));
+  for (Event& e : f.ev) BUF_TRY(ctx, e.create());
   f.set.assign(n, 0);
   f.prm.assign(n, lins_filter_params{});
   return LINS_OK;

@@ -7,32 +7,16 @@
 using namespace lins;
 
 namespace lins {
-void fe_free(lins_ctx* ctx) {
-  auto& f = ctx->fe;
-  void* ptrs[] = {f.d_scans, f.d_cloud, f.d_out, f.d_range, f.d_col, f.d_ground, f.d_picks, f.d_counts};
-  for (void* p : ptrs) (void)hipFree(p);
-  void* sg[] = {f.d_raw, f.d_raws, f.d_cellidx, f.d_segrows, f.d_outliers, f.d_outl};
-  for (void* p : sg) (void)hipFree(p);
-  (void)hipHostFree(f.h_raw);
-  (void)hipHostFree(f.h_cloud), (void)hipHostFree(f.h_range), (void)hipHostFree(f.h_col), (void)hipHostFree(f.h_ground);
-  f = lins_ctx::Frontend{};
-}
+void fe_free(lins_ctx* ctx) { ctx->fe = lins_ctx::Frontend{}; }
 
 // device buffers of the front-end for n scans (inputs, scratch, and the default output buffer d_out)
 static int fe_alloc(lins_ctx* ctx, int n) {
   auto& f = ctx->fe;
-  if (f.cap >= n) return LINS_OK;
+  if (f.d_scans.cap() >= (size_t)n) return LINS_OK;
   fe_free(ctx);
   const size_t c = (size_t)n, N = LINS_CLOUD_MAX;
-  HIP_TRY(ctx, hipMalloc(&f.d_scans, c * sizeof(FeScan)));
-  HIP_TRY(ctx, hipMalloc((void**)&f.d_cloud, c * N * sizeof(float4)));
-  HIP_TRY(ctx, hipMalloc((void**)&f.d_range, c * N * sizeof(float)));
-  HIP_TRY(ctx, hipMalloc((void**)&f.d_col, c * N * sizeof(unsigned)));
-  HIP_TRY(ctx, hipMalloc((void**)&f.d_ground, c * N));
-  HIP_TRY(ctx, hipMalloc((void**)&f.d_picks, c * fe_pick_stride() * sizeof(int)));
-  HIP_TRY(ctx, hipMalloc((void**)&f.d_out, c * kFeStride * sizeof(float4)));
-  HIP_TRY(ctx, hipMalloc((void**)&f.d_counts, c * 4 * sizeof(int)));
-  f.cap = n;
+  BUF_TRY(ctx, grow_all(f.d_scans, c, f.d_cloud, c * N, f.d_range, c * N, f.d_col, c * N, f.d_ground, c * N, f.d_picks, c * fe_pick_stride(), f.d_out,
+                        c * kFeStride, f.d_counts, c * 4));
   return LINS_OK;
 }
 
@@ -61,15 +45,7 @@ int fe_run(lins_ctx* ctx, int n, const lins_segmented_scan* in, double scan_peri
   int rc0 = fe_alloc(ctx, n);
   if (rc0) return rc0;
   auto& f = ctx->fe;
-  if (f.h_cap < total) {
-    (void)hipHostFree(f.h_cloud), (void)hipHostFree(f.h_range), (void)hipHostFree(f.h_col), (void)hipHostFree(f.h_ground);
-    f.h_cloud = nullptr, f.h_range = nullptr, f.h_col = nullptr, f.h_ground = nullptr, f.h_cap = 0;
-    HIP_TRY(ctx, hipHostMalloc((void**)&f.h_cloud, total * sizeof(float4)));
-    HIP_TRY(ctx, hipHostMalloc((void**)&f.h_range, total * sizeof(float)));
-    HIP_TRY(ctx, hipHostMalloc((void**)&f.h_col, total * sizeof(unsigned)));
-    HIP_TRY(ctx, hipHostMalloc((void**)&f.h_ground, total));
-    f.h_cap = total;
-  }
+  BUF_TRY(ctx, grow_all(f.h_cloud, total, f.h_range, total, f.h_col, total, f.h_ground, total));
   // pass 2 (host pool): input contract + packing into the pinned staging; every complete chunk of scans is sent
   // while the next ones are being packed
   const int rcv = pack_pipelined(
@@ -146,29 +122,10 @@ int sg_run(lins_ctx* ctx, int n, const lins_point* const* raw, const int32_t* n_
   int rc = fe_alloc(ctx, n);
   if (rc) return rc;
   auto& f = ctx->fe;
-  if (f.sg_cap < n) {
-    void* old[] = {f.d_raws, f.d_cellidx, f.d_segrows, f.d_outliers};
-    for (void* p : old) (void)hipFree(p);
-    f.d_raws = nullptr, f.d_cellidx = nullptr, f.d_segrows = nullptr, f.d_outliers = nullptr, f.sg_cap = 0;
-    const size_t c = (size_t)n;
-    HIP_TRY(ctx, hipMalloc(&f.d_raws, c * sizeof(SgRaw)));
-    HIP_TRY(ctx, hipMalloc((void**)&f.d_cellidx, c * N * sizeof(unsigned)));
-    HIP_TRY(ctx, hipMalloc((void**)&f.d_segrows, c * N * sizeof(int)));
-    HIP_TRY(ctx, hipMalloc((void**)&f.d_outliers, c * sizeof(int)));
-    f.sg_cap = n;
-  }
-  if (f.raw_cap < total) {
-    (void)hipFree(f.d_raw);
-    f.d_raw = nullptr, f.raw_cap = 0;
-    HIP_TRY(ctx, hipMalloc((void**)&f.d_raw, total * sizeof(float4)));
-    f.raw_cap = total;
-  }
-  if (f.h_raw_cap < total) {
-    (void)hipHostFree(f.h_raw);
-    f.h_raw = nullptr, f.h_raw_cap = 0;
-    HIP_TRY(ctx, hipHostMalloc((void**)&f.h_raw, total * sizeof(float4)));
-    f.h_raw_cap = total;
-  }
+  const size_t c = (size_t)n;
+  BUF_TRY(ctx, grow_all(f.d_raws, c, f.d_cellidx, c * N, f.d_segrows, c * N, f.d_outliers, c));
+  BUF_TRY(ctx, f.d_raw.grow(total));
+  BUF_TRY(ctx, f.h_raw.grow(total));
   const int rcv = pack_pipelined(
       n, 64,
       [&](int k) -> int {
@@ -237,12 +194,7 @@ static int segment_batch_impl(lins_ctx* ctx, int n, const lins_point* const* raw
   std::vector<int> o_slots((size_t)n);
   if (outlier) {
     if (int rc0 = fe_alloc(ctx, n)) return rc0;  // (first: growing the front-end's buffers drops every buffer of `f`)
-    if (f.outl_cap < n) {
-      (void)hipFree(f.d_outl);
-      f.d_outl = nullptr, f.outl_cap = 0;
-      HIP_TRY(ctx, hipMalloc((void**)&f.d_outl, (size_t)n * LINS_OUTLIER_MAX * sizeof(float4)));
-      f.outl_cap = n;
-    }
+    BUF_TRY(ctx, f.d_outl.grow((size_t)n * LINS_OUTLIER_MAX));
     for (int k = 0; k < n; ++k) o_slots[k] = k;
   }
   int rc = sg_run(ctx, n, raw, n_raw, reinterpret_cast<const long long(*)[4]>(offs.data()), outlier ? f.d_outl : nullptr, o_slots.data());
@@ -360,10 +312,9 @@ int lins_transform_to_end_batch(lins_ctx* ctx, int n_jobs, const lins_reproject_
     max_n = j.n > max_n ? j.n : max_n;
     off += align4(j.n);
   }
-  if (any_yzx && !ctx->d_aux) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_aux, ctx->arena_cap * sizeof(float4)));
-  (void)hipFree(ctx->d_jobs);
-  ctx->d_jobs = nullptr;
-  HIP_TRY(ctx, hipMalloc(&ctx->d_jobs, (size_t)n_jobs * sizeof(ReprojectJob)));
+  if (any_yzx) BUF_TRY(ctx, ctx->d_aux.grow(ctx->arena_cap));
+  ctx->d_jobs.reset();  // (a block of exactly this call's extent)
+  BUF_TRY(ctx, ctx->d_jobs.grow((size_t)n_jobs));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_jobs, hj.data(), (size_t)n_jobs * sizeof(ReprojectJob), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_arena, ctx->h_arena, off * sizeof(float4), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));

@@ -29,16 +29,7 @@ ScanDesc stream_desc(int stream, int qs, int n_flat, int n_sharp, int ts, int n_
 }  // namespace
 
 namespace lins {
-void streams_free(lins_ctx* ctx) {
-  auto& t = ctx->st;
-  (void)hipFree(t.d_arena), (void)hipFree(t.d_sorted), (void)hipFree(t.d_desc), (void)hipFree(t.d_jobs), (void)hipFree(t.d_desc_next);
-  t.d_desc_next = nullptr, t.index_ready = false;
-  streams_filter_free(ctx);
-  streams_boot_free(ctx);
-  streams_slam_free(ctx);
-  (void)hipFree(t.d_gsorted), (void)hipFree(t.d_gridtab), (void)hipFree(t.d_outl);
-  t = lins_ctx::Streams{};
-}
+void streams_free(lins_ctx* ctx) { ctx->st = lins_ctx::Streams{}; }  // (with its filter, state machine and odometry records)
 
 int streams_count(lins_ctx* ctx) { return ctx->st.failed ? 0 : ctx->st.n; }
 
@@ -416,15 +407,15 @@ int lins_streams_init(lins_ctx* ctx, int n_streams) {
   auto& t = ctx->st;
   const size_t pts = (size_t)n_streams * 2 * kSlotSize;
   if (pts >= (1ull << 31)) return LINS_E_CAPACITY;  // ScanDesc offsets are ints
-  HIP_TRY(ctx, hipMalloc((void**)&t.d_arena, pts * sizeof(float4)));
-  HIP_TRY(ctx, hipMalloc((void**)&t.d_sorted, pts * sizeof(float4)));
-  HIP_TRY(ctx, hipMalloc((void**)&t.d_gsorted, pts * sizeof(float4)));
-  HIP_TRY(ctx, hipMalloc((void**)&t.d_gridtab, (size_t)n_streams * sizeof(GridTables)));
-  HIP_TRY(ctx, hipMalloc((void**)&t.d_desc, (size_t)n_streams * sizeof(ScanDesc)));
-  HIP_TRY(ctx, hipMalloc((void**)&t.d_desc_next, (size_t)n_streams * sizeof(ScanDesc)));
+  BUF_TRY(ctx, t.d_arena.grow(pts));
+  BUF_TRY(ctx, t.d_sorted.grow(pts));
+  BUF_TRY(ctx, t.d_gsorted.grow(pts));
+  BUF_TRY(ctx, t.d_gridtab.grow((size_t)n_streams));
+  BUF_TRY(ctx, t.d_desc.grow((size_t)n_streams));
+  BUF_TRY(ctx, t.d_desc_next.grow((size_t)n_streams));
   t.index_ready = false;
-  HIP_TRY(ctx, hipMalloc(&t.d_jobs, (size_t)n_streams * 2 * sizeof(StreamCloud)));
-  HIP_TRY(ctx, hipMalloc((void**)&t.d_outl, (size_t)n_streams * 2 * LINS_OUTLIER_MAX * sizeof(float4)));
+  BUF_TRY(ctx, t.d_jobs.grow((size_t)n_streams * 2));
+  BUF_TRY(ctx, t.d_outl.grow((size_t)n_streams * 2 * LINS_OUTLIER_MAX));
   t.outl_counts.assign((size_t)n_streams * 2, 0), t.outl_put.assign((size_t)n_streams, 0), t.outl_pending = false;
   t.n = n_streams, t.cur.assign((size_t)n_streams, 0);
   t.last_counts.assign((size_t)n_streams * 2, -1);

@@ -57,7 +57,7 @@ struct lins_ctx {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;  // IESKF kernel start / end, Joseph kernel end
   hipStream_t copy_stream = nullptr;  // lins_ieskf_update_batch: uploads of the next chunk beside the running one
-  hipEvent_t ev_copy = nullptr;
+  Event ev_copy;  // (created with copy_stream)
   size_t slots_uploaded = 0;    // query slots of the uploaded batch
   lins_params prm{};
   DevParams dprm{};
@@ -109,36 +109,32 @@ struct lins_ctx {
   int *h_order = nullptr, *d_order = nullptr;  // launch order of the uploaded batch (longest-expected-first), see launch_order()
   double *d_state_in = nullptr, *d_cov_in = nullptr, *d_state_out = nullptr, *d_cov_out = nullptr;
   double* d_lin = nullptr;
-  float4* d_aux = nullptr;     // third point arena (YZX copies of the re-projection), lazily allocated
-  ReprojectJob* d_jobs = nullptr;
+  DevBuf<float4> d_aux;     // third point arena (YZX copies of the re-projection), lazily allocated
+  DevBuf<ReprojectJob> d_jobs;  // the jobs of the last lins_transform_to_end_batch
   float reproject_ms = 0.f;
   uint64_t reproject_bytes = 0;
-  // feature front-end (lins_extract_features_batch): device buffers, allocated on first use for fe_cap scans
+  // feature front-end (lins_extract_features_batch): device buffers, allocated on first use, for the largest batch so far
   struct Frontend {
-    int cap = 0;
-    FeScan* d_scans = nullptr;
-    float4 *d_cloud = nullptr, *d_out = nullptr;  // d_out: kFeStride points per scan
-    float* d_range = nullptr;
-    unsigned* d_col = nullptr;
-    unsigned char* d_ground = nullptr;
-    int *d_picks = nullptr, *d_counts = nullptr;
-    // pinned host staging of the packed inputs (grow-only, h_cap points)
-    size_t h_cap = 0;
-    float4* h_cloud = nullptr;
-    float* h_range = nullptr;
-    unsigned* h_col = nullptr;
-    unsigned char* h_ground = nullptr;
+    DevBuf<FeScan> d_scans;  // (its capacity: the scans the group below is allocated for)
+    DevBuf<float4> d_cloud, d_out;  // d_out: kFeStride points per scan
+    DevBuf<float> d_range;
+    DevBuf<unsigned> d_col;
+    DevBuf<unsigned char> d_ground;
+    DevBuf<int> d_picks, d_counts;
+    // pinned host staging of the packed inputs (one group, grow-only; h_cloud answers, in points)
+    PinBuf<float4> h_cloud;
+    PinBuf<float> h_range;
+    PinBuf<unsigned> h_col;
+    PinBuf<unsigned char> h_ground;
     float ms = 0.f;
     uint64_t bytes = 0;
     // image_projection stage (lins_segment_batch / the raw-cloud streams path): raw points + per-cell scratch
-    int sg_cap = 0;
-    size_t raw_cap = 0, h_raw_cap = 0;
-    float4 *d_raw = nullptr, *h_raw = nullptr;
-    SgRaw* d_raws = nullptr;
-    unsigned* d_cellidx = nullptr;
-    int *d_segrows = nullptr, *d_outliers = nullptr;
-    float4* d_outl = nullptr;  // lins_segment_batch_outliers: the outlier clouds, LINS_OUTLIER_MAX points per scan (outl_cap scans)
-    int outl_cap = 0;
+    DevBuf<float4> d_raw;
+    PinBuf<float4> h_raw;
+    DevBuf<SgRaw> d_raws;  // (d_raws, d_cellidx, d_segrows, d_outliers: one group, d_raws answers, in scans)
+    DevBuf<unsigned> d_cellidx;
+    DevBuf<int> d_segrows, d_outliers;
+    DevBuf<float4> d_outl;  // lins_segment_batch_outliers: the outlier clouds, LINS_OUTLIER_MAX points per scan
     float sg_ms = 0.f;
   } fe;
   // device-resident streams (lins_streams_step): per stream two feature slots (this scan's / the last
@@ -146,16 +142,16 @@ struct lins_ctx {
   struct Streams {
     int n = 0;
     std::vector<int> cur;         // per stream: slot the NEXT scan's features go to (a gated scan does not flip its stream's)
-    float4 *d_arena = nullptr, *d_sorted = nullptr, *d_gsorted = nullptr;
-    GridTables* d_gridtab = nullptr;
-    ScanDesc* d_desc = nullptr;
-    ScanDesc* d_desc_next = nullptr;  // the clouds of the scan just taken in as the NEXT step's targets (fused re-projection + index)
+    DevBuf<float4> d_arena, d_sorted, d_gsorted;
+    DevBuf<GridTables> d_gridtab;
+    DevBuf<ScanDesc> d_desc;
+    DevBuf<ScanDesc> d_desc_next;  // the clouds of the scan just taken in as the NEXT step's targets (fused re-projection + index)
     bool index_ready = false;         // d_gsorted / d_gridtab hold the index of the resident last scans (built by the step before)
-    StreamCloud* d_jobs = nullptr;
+    DevBuf<StreamCloud> d_jobs;
     std::vector<int> last_counts;  // per stream: less sharp, less flat of the resident last scan (-1: none yet)
     // the outlier clouds (lins_streams_map_cloud, lins_local_map_build_streams): two slots of LINS_OUTLIER_MAX points per
     // stream, flipped with the feature slots — a raw step's segmentation writes slot cur, lins_streams_put_outliers too
-    float4* d_outl = nullptr;
+    DevBuf<float4> d_outl;
     std::vector<int> outl_counts;  // [stream][slot]
     std::vector<int> outl_put;     // per stream: the count lins_streams_put_outliers left for the next segmented step
     bool outl_pending = false;
@@ -165,12 +161,14 @@ struct lins_ctx {
     // and globalState_, one row per stream in the layout of d_state_in / d_cov_in — the update kernels read the predicted
     // prior where it lies.  Allocated by the first lins_streams_filter_set.
     struct Filter {
-      double *d_state = nullptr, *d_cov = nullptr, *d_noise = nullptr, *d_aux = nullptr, *d_gstate = nullptr;  // n x 19 / 324 / 144 / kAux / 19
-      double *d_imu = nullptr, *h_imu = nullptr;  // this call's IMU rows, packed (n x LINS_STREAMS_IMU_MAX x 7 at most; h_: pinned)
-      int *d_ints = nullptr, *h_ints = nullptr;   // [n_imu | row offset | finish mode] x n (h_: pinned)
+      DevBuf<double> d_state, d_cov, d_noise, d_aux, d_gstate;  // n x 19 / 324 / 144 / kAux / 19
+      DevBuf<double> d_imu;  // this call's IMU rows, packed (n x LINS_STREAMS_IMU_MAX x 7 at most; h_: pinned)
+      PinBuf<double> h_imu;
+      DevBuf<int> d_ints;    // [n_imu | row offset | finish mode] x n (h_: pinned)
+      PinBuf<int> h_ints;
       std::vector<char> set;                      // per stream: a filter has been loaded
       std::vector<lins_filter_params> prm;        // ... and its parameters (lins_streams_filter_get returns them)
-      hipEvent_t ev[4] = {};                      // predict start / end, finish start / end
+      Event ev[4];                                // predict start / end, finish start / end
       bool predict_timed = false, finish_timed = false;
       float predict_ms = 0.f, finish_ms = 0.f;
     } f;
@@ -183,31 +181,38 @@ struct lins_ctx {
       std::vector<char> imu_seen;    // the stream has been given an IMU row (or a scan_imu)
       std::vector<double> imu_last;  // ... the newest one: n x 6 (acc, gyr)
       std::vector<double> h_tmpl;    // host copy of the template (lins_boot::kTmpl doubles)
-      double *d_tmpl = nullptr, *d_pre = nullptr;  // the template; n x lins_boot::kPre pre-integration records
-      double *d_rows = nullptr, *h_rows = nullptr; // this call's rows of the FIRST_SCAN streams, component-major (h_: pinned)
-      double *d_scan = nullptr, *h_scan = nullptr; // n x 8: imu_last_ and time of this call's scans
-      int *d_ints = nullptr, *h_ints = nullptr;    // [rows per stream | finish mode | ICP slot | ICP list] x n
+      DevBuf<double> d_tmpl, d_pre;  // the template; n x lins_boot::kPre pre-integration records
+      DevBuf<double> d_rows;         // this call's rows of the FIRST_SCAN streams, component-major (h_: pinned)
+      PinBuf<double> h_rows;
+      DevBuf<double> d_scan;         // n x 8: imu_last_ and time of this call's scans
+      PinBuf<double> h_scan;
+      DevBuf<int> d_ints;            // [rows per stream | finish mode | ICP slot | ICP list] x n
+      PinBuf<int> h_ints;
       // the batched ICP of the second scans: compact descriptors, index tables, start / result rows, out records
-      ScanDesc* d_desc = nullptr;
-      GridTables* d_tab = nullptr;
-      double *d_icp_in = nullptr, *d_icp_out = nullptr;
-      OutRec *d_out = nullptr, *h_out = nullptr;
-      hipEvent_t ev[6] = {};  // pre-integration, ICP, finish: start / end
+      DevBuf<ScanDesc> d_desc;
+      DevBuf<GridTables> d_tab;
+      DevBuf<double> d_icp_in, d_icp_out;
+      DevBuf<OutRec> d_out;
+      PinBuf<OutRec> h_out;
+      Event ev[6];  // pre-integration, ICP, finish: start / end
       bool pre_timed = false, icp_timed = false, finish_timed = false;
       float pre_ms = 0.f, icp_ms = 0.f, finish_ms = 0.f;
     } b;
     // streams end to end (lins_streams_slam.h; lins_streams_slam_capi.hip): the odometry records derived from d_gstate and
     // the staging of the fusion.  Allocated by the first call that derives the records.
     struct Slam {
-      lins_stream_odom *d_odom = nullptr, *h_odom = nullptr;  // n records (h_: pinned)
-      int *d_ints = nullptr, *h_ints = nullptr;               // [stream has a globalState_ | fusion list] x n (h_: pinned)
-      lins_fused_pose *d_fused = nullptr, *h_fused = nullptr; // n fused poses (h_: pinned)
+      DevBuf<lins_stream_odom> d_odom;  // n records (h_: pinned)
+      PinBuf<lins_stream_odom> h_odom;
+      DevBuf<int> d_ints;               // [stream has a globalState_ | fusion list] x n (h_: pinned)
+      PinBuf<int> h_ints;
+      DevBuf<lins_fused_pose> d_fused;  // n fused poses (h_: pinned)
+      PinBuf<lins_fused_pose> h_fused;
       bool have = false;                                      // the records have been derived at least once
     } s;
   } st;
   void* map_state = nullptr;  // scan-to-map row (lins_map_capi.hip), freed through map_state_free
   void (*map_state_free)(void*) = nullptr;
-  long long* d_prof = nullptr;  // optional per-workgroup phase profile (lins_debug_phase_profile)
+  DevBuf<long long> d_prof;  // optional per-workgroup phase profile (lins_debug_phase_profile)
   double* d_a6 = nullptr;  // upper triangle of the last iteration's H^T H, per scan
   OutRec* d_out = nullptr;
   int4* d_idx = nullptr;

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/lins_ieskf.h"
+#include "lins_buf.h"
 
 namespace lins {
 hipStream_t ctx_stream(lins_ctx* ctx);
@@ -31,4 +32,10 @@ int streams_count(lins_ctx* ctx);  // streams of lins_streams_init (0: none, or 
   do {                                              \
     hipError_t e__ = (expr);                        \
     if (e__ != hipSuccess) return ctx_fail_hip(ctx, e__, #expr); \
+  } while (0)
+// growth of a lins_buf.h buffer or group (the policy's int is the hipError_t): HIP_TRY's contract, the message names the growth
+#define BUF_TRY(ctx, expr)                          \
+  do {                                              \
+    int e__ = (expr);                               \
+    if (e__) return ctx_fail_hip(ctx, (hipError_t)e__, #expr); \
   } while (0)

@@ -29,61 +29,32 @@ struct KeyFrame {
 
 struct LocalMap {
   int n_slots = 0, window = 0, max_pts = 0;
-  float4* d_frames = nullptr;  // [slot][window][max_pts]
+  DevBuf<float4> d_frames;  // [slot][window][max_pts]
   std::vector<KeyFrame> meta;  // [slot][window]
   std::vector<int> head, count;
   // build arenas (grown, never shrunk)
-  float4 *d_stage = nullptr, *d_out = nullptr;
-  unsigned *d_ka = nullptr, *d_kb = nullptr;
-  int *d_va = nullptr, *d_vb = nullptr, *d_starts = nullptr, *d_hist = nullptr, *d_tilecnt = nullptr, *d_csum = nullptr;
-  char* d_tab = nullptr;
-  float4* h_raw = nullptr;
-  char *h_tab = nullptr, *h_states = nullptr;
-  size_t cap_stage = 0, cap_out = 0, cap_tiles = 0, cap_tab = 0, cap_raw = 0, cap_htab = 0, cap_hstates = 0, cap_csum = 0;
+  DevBuf<float4> d_stage, d_out;
+  DevBuf<unsigned> d_ka, d_kb;  // (d_stage, d_ka, d_kb, d_va, d_vb, d_starts: one group, d_stage answers)
+  DevBuf<int> d_va, d_vb, d_starts, d_hist, d_tilecnt, d_csum;  // (d_hist, d_tilecnt: one group, d_hist answers)
+  DevBuf<char> d_tab;  // (bytes)
+  PinBuf<float4> h_raw;
+  PinBuf<char> h_tab, h_states;  // (bytes)
   // the last build
   bool built = false;
   std::vector<int> slots;
   std::vector<long long> off;  // 6 per entry
   std::vector<lins_local_map_sizes> sizes;
   float ms = 0.f, stage_ms = 0.f;  // stage_ms: the staging kernel of lins_local_map_build_streams (inside ms)
-  hipEvent_t ev_stage = nullptr;
+  Event ev_stage;
   uint64_t points_in = 0;
 };
 
-void local_free(void* p) {
-  LocalMap* m = (LocalMap*)p;
-  (void)hipFree(m->d_frames), (void)hipFree(m->d_stage), (void)hipFree(m->d_out), (void)hipFree(m->d_ka), (void)hipFree(m->d_kb);
-  (void)hipFree(m->d_va), (void)hipFree(m->d_vb), (void)hipFree(m->d_starts), (void)hipFree(m->d_hist), (void)hipFree(m->d_tilecnt);
-  (void)hipFree(m->d_csum), (void)hipFree(m->d_tab), (void)hipHostFree(m->h_raw), (void)hipHostFree(m->h_tab), (void)hipHostFree(m->h_states);
-  if (m->ev_stage) (void)hipEventDestroy(m->ev_stage);
-  delete m;
-}
+void local_free(void* p) { delete (LocalMap*)p; }
 
 LocalMap* local_of(lins_ctx* ctx) {
-  void** slot = map_local_slot(ctx, local_free);
+  void** slot = map_slot(ctx, kSlotLocal, local_free);
   if (!*slot) *slot = new LocalMap();
   return (LocalMap*)*slot;
-}
-
-template <class T>
-int grow(lins_ctx* ctx, T** p, size_t* cap, size_t need) {
-  need = std::max<size_t>(need, 1);
-  if (*cap >= need) return LINS_OK;
-  (void)hipFree(*p);
-  *p = nullptr, *cap = 0;
-  HIP_TRY(ctx, hipMalloc((void**)p, need * sizeof(T)));
-  *cap = need;
-  return LINS_OK;
-}
-template <class T>
-int grow_pinned(lins_ctx* ctx, T** p, size_t* cap, size_t need) {
-  need = std::max<size_t>(need, 1);
-  if (*cap >= need) return LINS_OK;
-  (void)hipHostFree(*p);
-  *p = nullptr, *cap = 0;
-  HIP_TRY(ctx, hipHostMalloc((void**)p, need * sizeof(T)));
-  *cap = need;
-  return LINS_OK;
 }
 
 bool point_ok(const lins_point& p) {
@@ -154,9 +125,9 @@ int lins_local_map_init(lins_ctx* ctx, int n_slots, int window, int max_points_p
   HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
   LocalMap* m = local_of(ctx);
   HIP_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));  // (a push_scans copy may still read the old rings)
-  (void)hipFree(m->d_frames);
-  m->d_frames = nullptr, m->n_slots = 0, m->built = false;
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_frames, (size_t)n_slots * window * max_points_per_frame * sizeof(float4)));
+  m->d_frames.reset();
+  m->n_slots = 0, m->built = false;
+  BUF_TRY(ctx, m->d_frames.grow((size_t)n_slots * window * max_points_per_frame));
   m->n_slots = n_slots, m->window = window, m->max_pts = max_points_per_frame;
   m->meta.assign((size_t)n_slots * window, KeyFrame{});
   m->head.assign(n_slots, 0), m->count.assign(n_slots, 0);
@@ -272,7 +243,7 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
     jobs[ph[5 * k + 4]].feed_after = ph[5 * k + 3];
   }
   int rc;
-  if (scans && (rc = grow_pinned(ctx, &m->h_raw, &m->cap_raw, raw_total))) return rc;
+  if (scans) BUF_TRY(ctx, m->h_raw.grow(raw_total));
   // raw scans: input contract, f32 box (the min / max the device would fold), packed for one upload
   for (int k = 0; k < n && scans; ++k) {
     const lins_point* c[3] = {scans[k].corner, scans[k].surf, scans[k].outlier};
@@ -353,8 +324,8 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
                o_ssegs = align64(o_tiles + tiles.size() * sizeof(int2)), o_sblocks = align64(o_ssegs + ssegs.size() * sizeof(LmScanSeg)),
                o_chunks = align64(o_sblocks + sblocks.size() * sizeof(int2)), o_splits = align64(o_chunks + chunks.size() * sizeof(ArChunk)),
                tab_bytes = align64(o_splits + splits.size() * sizeof(ArSplit));
-  if ((rc = grow_pinned(ctx, &m->h_tab, &m->cap_htab, tab_bytes))) return rc;
-  if ((rc = grow_pinned(ctx, &m->h_states, &m->cap_hstates, NJ * sizeof(LmState)))) return rc;
+  BUF_TRY(ctx, m->h_tab.grow(tab_bytes));
+  BUF_TRY(ctx, m->h_states.grow(NJ * sizeof(LmState)));
   std::memcpy(m->h_tab + o_jobs, jobs.data(), NJ * sizeof(LmJob));
   std::memcpy(m->h_tab + o_states, states.data(), NJ * sizeof(LmState));
   if (!segs.empty()) std::memcpy(m->h_tab + o_segs, segs.data(), segs.size() * sizeof(LmSeg));
@@ -364,28 +335,13 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
   if (!sblocks.empty()) std::memcpy(m->h_tab + o_sblocks, sblocks.data(), sblocks.size() * sizeof(int2));
   if (!chunks.empty()) std::memcpy(m->h_tab + o_chunks, chunks.data(), chunks.size() * sizeof(ArChunk));
   if (!splits.empty()) std::memcpy(m->h_tab + o_splits, splits.data(), splits.size() * sizeof(ArSplit));
-  if (from && !m->ev_stage) HIP_TRY(ctx, hipEventCreate(&m->ev_stage));
-  if ((rc = grow(ctx, &m->d_tab, &m->cap_tab, tab_bytes))) return rc;
-  if (m->cap_stage < std::max<size_t>(stage_total, 1)) {  // the staging arena and the sort's scratch: same extent
-    size_t c[7] = {0, 0, 0, 0, 0, 0, 0};
-    (void)hipFree(m->d_stage), (void)hipFree(m->d_ka), (void)hipFree(m->d_kb), (void)hipFree(m->d_va), (void)hipFree(m->d_vb);
-    (void)hipFree(m->d_starts);
-    m->d_stage = nullptr, m->d_ka = m->d_kb = nullptr, m->d_va = m->d_vb = m->d_starts = nullptr, m->cap_stage = 0;
-    if ((rc = grow(ctx, &m->d_stage, &c[0], stage_total)) || (rc = grow(ctx, &m->d_ka, &c[1], stage_total)) ||
-        (rc = grow(ctx, &m->d_kb, &c[2], stage_total)) || (rc = grow(ctx, &m->d_va, &c[3], stage_total)) ||
-        (rc = grow(ctx, &m->d_vb, &c[4], stage_total)) || (rc = grow(ctx, &m->d_starts, &c[5], stage_total)))
-      return rc;
-    m->cap_stage = c[0];
-  }
-  if (m->cap_tiles < std::max<size_t>(tiles_total, 1)) {
-    size_t c[2] = {0, 0};
-    (void)hipFree(m->d_hist), (void)hipFree(m->d_tilecnt);
-    m->d_hist = m->d_tilecnt = nullptr, m->cap_tiles = 0;
-    if ((rc = grow(ctx, &m->d_hist, &c[0], tiles_total * 256)) || (rc = grow(ctx, &m->d_tilecnt, &c[1], tiles_total))) return rc;
-    m->cap_tiles = c[1];
-  }
-  if ((rc = grow(ctx, &m->d_out, &m->cap_out, out_total))) return rc;
-  if (!chunks.empty() && (rc = grow(ctx, &m->d_csum, &m->cap_csum, chunks.size()))) return rc;
+  if (from) BUF_TRY(ctx, m->ev_stage.create());
+  BUF_TRY(ctx, m->d_tab.grow(tab_bytes));
+  // the staging arena and the sort's scratch: same extent
+  BUF_TRY(ctx, grow_all(m->d_stage, stage_total, m->d_ka, stage_total, m->d_kb, stage_total, m->d_va, stage_total, m->d_vb, stage_total, m->d_starts, stage_total));
+  BUF_TRY(ctx, grow_all(m->d_hist, tiles_total * 256, m->d_tilecnt, tiles_total));
+  BUF_TRY(ctx, m->d_out.grow(out_total));
+  if (!chunks.empty()) BUF_TRY(ctx, m->d_csum.grow(chunks.size()));
   hipStream_t st = ctx_stream(ctx);
   hipEvent_t e0, e1;
   ctx_events(ctx, &e0, &e1);
@@ -416,7 +372,7 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
   m->stage_ms = 0.f;
   if (from) HIP_TRY(ctx, hipEventElapsedTime(&m->stage_ms, e0, m->ev_stage));
   m->points_in = pts_in;
-  const LmState* S = (const LmState*)m->h_states;
+  const LmState* S = (const LmState*)m->h_states.get();
   m->slots.assign(slots, slots + n);
   m->off.assign((size_t)6 * n, 0);
   m->sizes.assign(n, lins_local_map_sizes{});

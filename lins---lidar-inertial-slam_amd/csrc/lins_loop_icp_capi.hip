@@ -30,18 +30,17 @@ namespace {
 constexpr int kLoopGroup = 8;
 
 struct LoopMem {
-  float4 *d_src = nullptr, *d_raw = nullptr, *d_pts = nullptr;
-  float4* h_up = nullptr;  // pinned staging of the host clouds of one call
-  int* d_cells = nullptr;
-  LoopDev* d_probs = nullptr;
-  State* d_states = nullptr;
-  MapGridJob* d_jobs = nullptr;
-  double* d_partials = nullptr;
-  int *d_running = nullptr, *h_running = nullptr;
-  int32_t* d_idx = nullptr;
-  float* d_d = nullptr;
-  size_t cap_src = 0, cap_raw = 0, cap_pts = 0, cap_up = 0, cap_cells = 0, cap_probs = 0, cap_states = 0, cap_jobs = 0, cap_partials = 0,
-         cap_running = 0, cap_hrunning = 0, cap_idx = 0, cap_d = 0;
+  DevBuf<float4> d_src, d_raw, d_pts;
+  PinBuf<float4> h_up;  // pinned staging of the host clouds of one call
+  DevBuf<int> d_cells;
+  DevBuf<LoopDev> d_probs;
+  DevBuf<State> d_states;
+  DevBuf<MapGridJob> d_jobs;
+  DevBuf<double> d_partials;
+  DevBuf<int> d_running;
+  PinBuf<int> h_running;
+  DevBuf<int32_t> d_idx;
+  DevBuf<float> d_d;
   int max_rounds = 0;  // lins_debug_loop_icp_rounds (0: off)
   int shells = kLoopShells;
   int group = kLoopGroup;
@@ -50,29 +49,12 @@ struct LoopMem {
   unsigned last_far = 0;
 };
 
-void loop_free(void* p) {
-  LoopMem* m = (LoopMem*)p;
-  (void)hipFree(m->d_src), (void)hipFree(m->d_raw), (void)hipFree(m->d_pts), (void)hipFree(m->d_cells), (void)hipFree(m->d_probs);
-  (void)hipFree(m->d_states), (void)hipFree(m->d_jobs), (void)hipFree(m->d_partials), (void)hipFree(m->d_running), (void)hipFree(m->d_idx);
-  (void)hipFree(m->d_d), (void)hipHostFree(m->h_up), (void)hipHostFree(m->h_running);
-  delete m;
-}
+void loop_free(void* p) { delete (LoopMem*)p; }
 
 LoopMem* mem_of(lins_ctx* ctx) {
-  void** slot = map_loop_slot(ctx, loop_free);
+  void** slot = map_slot(ctx, kSlotLoop, loop_free);
   if (!*slot) *slot = new LoopMem();
   return (LoopMem*)*slot;
-}
-
-template <class T>
-int grow(lins_ctx* ctx, T** p, size_t* cap, size_t need, bool pinned = false) {
-  need = std::max<size_t>(need, 1);
-  if (*cap >= need) return LINS_OK;
-  (void)(pinned ? hipHostFree(*p) : hipFree(*p));
-  *p = nullptr, *cap = 0;
-  HIP_TRY(ctx, pinned ? hipHostMalloc((void**)p, need * sizeof(T)) : hipMalloc((void**)p, need * sizeof(T)));
-  *cap = need;
-  return LINS_OK;
 }
 
 bool cloud_finite(const lins_point* p, int n) {
@@ -131,10 +113,9 @@ int prepare(lins_ctx* ctx, LoopMem* m, int n, const lins_loop_icp_problem* in, P
     if (in[k].target_entry < 0 && !cloud_finite(in[k].target, in[k].n_target)) return LINS_E_INPUT;
   }
   hipStream_t st = ctx_stream(ctx);
-  int rc;
-  if ((rc = grow(ctx, &m->d_src, &m->cap_src, up_src)) || (rc = grow(ctx, &m->d_raw, &m->cap_raw, up_tgt)) ||
-      (rc = grow(ctx, &m->h_up, &m->cap_up, up_src + up_tgt, true)))
-    return rc;
+  BUF_TRY(ctx, m->d_src.grow(up_src));
+  BUF_TRY(ctx, m->d_raw.grow(up_tgt));
+  BUF_TRY(ctx, m->h_up.grow(up_src + up_tgt));
   // descriptors and grid jobs: the host targets' jobs first (raw = the upload arena), then the entries' (raw = the
   // archive's cloud arena) — map_grid_kernel takes one raw arena a launch
   P.dev.assign(n, LoopDev{});
@@ -188,11 +169,14 @@ int prepare(lins_ctx* ctx, LoopMem* m, int n, const lins_loop_icp_problem* in, P
   P.bpp = std::max(1, (max_src + kLoopQPerBlock - 1) / kLoopQPerBlock);
   const size_t nh = jobs_host.size(), ne = jobs_entry.size();
   jobs_host.insert(jobs_host.end(), jobs_entry.begin(), jobs_entry.end());
-  if ((rc = grow(ctx, &m->d_pts, &m->cap_pts, tot_pts)) || (rc = grow(ctx, &m->d_cells, &m->cap_cells, tot_cells)) ||
-      (rc = grow(ctx, &m->d_probs, &m->cap_probs, (size_t)n)) || (rc = grow(ctx, &m->d_states, &m->cap_states, (size_t)n)) ||
-      (rc = grow(ctx, &m->d_jobs, &m->cap_jobs, jobs_host.size())) || (rc = grow(ctx, &m->d_partials, &m->cap_partials, (size_t)n * P.bpp * kSums)) ||
-      (rc = grow(ctx, &m->d_running, &m->cap_running, 128)) || (rc = grow(ctx, &m->h_running, &m->cap_hrunning, 1, true)))
-    return rc;
+  BUF_TRY(ctx, m->d_pts.grow(tot_pts));
+  BUF_TRY(ctx, m->d_cells.grow(tot_cells));
+  BUF_TRY(ctx, m->d_probs.grow((size_t)n));
+  BUF_TRY(ctx, m->d_states.grow((size_t)n));
+  BUF_TRY(ctx, m->d_jobs.grow(jobs_host.size()));
+  BUF_TRY(ctx, m->d_partials.grow((size_t)n * P.bpp * kSums));
+  BUF_TRY(ctx, m->d_running.grow(128));
+  BUF_TRY(ctx, m->h_running.grow(1));
   if (up_src) HIP_TRY(ctx, hipMemcpyAsync(m->d_src, m->h_up, up_src * sizeof(float4), hipMemcpyHostToDevice, st));
   if (up_tgt) HIP_TRY(ctx, hipMemcpyAsync(m->d_raw, m->h_up + up_src, up_tgt * sizeof(float4), hipMemcpyHostToDevice, st));
   if (!jobs_host.empty()) HIP_TRY(ctx, hipMemcpyAsync(m->d_jobs, jobs_host.data(), jobs_host.size() * sizeof(MapGridJob), hipMemcpyHostToDevice, st));
@@ -300,7 +284,8 @@ int lins_loop_icp_correspondences(lins_ctx* ctx, const lins_loop_icp_problem* in
   if (P.dev[0].status) return P.dev[0].status;
   const int ns = P.dev[0].n_src;
   if (ns && (!idx || !sqdist)) return LINS_E_ARG;
-  if ((rc = grow(ctx, &m->d_idx, &m->cap_idx, (size_t)ns)) || (rc = grow(ctx, &m->d_d, &m->cap_d, (size_t)ns))) return rc;
+  BUF_TRY(ctx, m->d_idx.grow((size_t)ns));
+  BUF_TRY(ctx, m->d_d.grow((size_t)ns));
   hipStream_t st = ctx_stream(ctx);
   State s;
   lins_licp::state_init(s);

@@ -39,7 +39,7 @@ struct LoopStepMem {
 void loop_step_free(void* p) { delete (LoopStepMem*)p; }
 
 LoopStepMem* mem_of(lins_ctx* ctx) {
-  void** slot = map_loop_step_slot(ctx, loop_step_free);
+  void** slot = map_slot(ctx, kSlotLoopStep, loop_step_free);
   if (!*slot) *slot = new LoopStepMem();
   return (LoopStepMem*)*slot;
 }

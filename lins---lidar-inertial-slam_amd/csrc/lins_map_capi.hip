@@ -25,19 +25,19 @@ using namespace lins;
 namespace {
 
 struct MapState {
-  float4 *d_raw = nullptr, *d_pts = nullptr, *d_q = nullptr;
-  float4* h_q = nullptr;  // pinned staging of the queries of one call (one copy instead of two per problem)
-  size_t cap_hq = 0;
-  int* d_cells = nullptr;
-  lins_map_corr* d_rec = nullptr;
-  double* d_partials = nullptr;
-  MapDev* d_probs = nullptr;
-  MapRoundParams* d_rounds = nullptr;
-  MapGridJob* d_jobs = nullptr;
-  LmCarry* d_carry = nullptr;
-  lins_map_result* d_results = nullptr;
-  size_t cap_raw = 0, cap_pts = 0, cap_q = 0, cap_cells = 0, cap_partials = 0;
-  int cap_probs = 0;
+  DevBuf<float4> d_raw, d_pts;
+  PinBuf<float4> h_q;  // pinned staging of the queries of one call (one copy instead of two per problem)
+  DevBuf<int> d_cells;
+  DevBuf<double> d_partials;
+  // one capacity (queries): grown together, d_q answers
+  DevBuf<float4> d_q;
+  DevBuf<lins_map_corr> d_rec;
+  // one capacity (problems): grown together, d_probs answers
+  DevBuf<MapDev> d_probs;
+  DevBuf<MapRoundParams> d_rounds;
+  DevBuf<MapGridJob> d_jobs;  // two per problem
+  DevBuf<LmCarry> d_carry;
+  DevBuf<lins_map_result> d_results;
   // the maps resident on the device (gridded): sizes per problem of the last upload, for LINS_MAP_REUSE
   std::vector<int> resident_sizes;
   std::vector<MapDev> resident_dev;
@@ -45,48 +45,19 @@ struct MapState {
   uint64_t queries = 0;
   bool selfcheck_done = false;
   int max_rounds = 10;  // lins_debug_map_rounds (test aid): the rounds lins_scan2map_batch runs at most
-  // the local-map state of lins_local_map_* (lins_local_map_capi.hip), freed with this one
-  void* local = nullptr;
-  void (*local_free)(void*) = nullptr;
-  // the key-frame archive of lins_archive_* (lins_archive_capi.hip), likewise
-  void* archive = nullptr;
-  void (*archive_free)(void*) = nullptr;
-  // the loop-closure ICP's of lins_loop_icp_* (lins_loop_icp_capi.hip), likewise
-  void* loop = nullptr;
-  void (*loop_free)(void*) = nullptr;
-  // the streams' map poses of lins_streams_map_* (lins_streams_map_capi.hip), likewise
-  void* pose = nullptr;
-  void (*pose_free)(void*) = nullptr;
-  // the pose graphs of lins_pose_graph_* (lins_pose_graph_capi.hip), likewise
-  void* graph = nullptr;
-  void (*graph_free)(void*) = nullptr;
-  // the loop thread's step of lins_loop_step (lins_loop_step_capi.hip), likewise
-  void* loop_step = nullptr;
-  void (*loop_step_free)(void*) = nullptr;
+  // what the other mapping files keep per context (local_map.h MapSlot), freed with this state in the enum's order
+  void* slot[kSlotCount] = {};
+  void (*slot_free[kSlotCount])(void*) = {};
+
+  int grow_problems(size_t n) { return grow_all(d_probs, n, d_rounds, n, d_jobs, 2 * n, d_carry, n, d_results, n); }
+  int grow_queries(size_t n) { return grow_all(d_q, n, d_rec, n); }
 };
 
 void map_state_free(void* p) {
   MapState* m = (MapState*)p;
-  (void)hipFree(m->d_raw), (void)hipFree(m->d_pts), (void)hipFree(m->d_q), (void)hipFree(m->d_cells), (void)hipFree(m->d_rec);
-  (void)hipFree(m->d_partials), (void)hipFree(m->d_probs), (void)hipFree(m->d_rounds), (void)hipFree(m->d_jobs);
-  (void)hipFree(m->d_carry), (void)hipFree(m->d_results), (void)hipHostFree(m->h_q);
-  if (m->local) m->local_free(m->local);
-  if (m->archive) m->archive_free(m->archive);
-  if (m->loop) m->loop_free(m->loop);
-  if (m->pose) m->pose_free(m->pose);
-  if (m->graph) m->graph_free(m->graph);
-  if (m->loop_step) m->loop_step_free(m->loop_step);
+  for (int i = 0; i < kSlotCount; ++i)
+    if (m->slot[i]) m->slot_free[i](m->slot[i]);
   delete m;
-}
-
-template <class T>
-int grow(lins_ctx* ctx, T** p, size_t* cap, size_t need) {
-  if (*cap >= need) return LINS_OK;
-  (void)hipFree(*p);
-  *p = nullptr, *cap = 0;
-  HIP_TRY(ctx, hipMalloc((void**)p, need * sizeof(T)));
-  *cap = need;
-  return LINS_OK;
 }
 
 template <class F>
@@ -161,19 +132,10 @@ int map_upload(lins_ctx* ctx, MapState* m, int n, const lins_map_problem* in, st
         for (int a = 0; a < 3; ++a) dev[k].g[w].cmin[a] = jb.cmin[a], dev[k].g[w].cdim[a] = jb.cdim[a];
         tot_pts += (size_t)jb.n, tot_cells += 2 * ((size_t)jb.ncell + 1);  // starts + scratch cursors
       }
-    if ((rc = grow(ctx, &m->d_raw, &m->cap_raw, std::max<size_t>(tot_pts, 1)))) return rc;
-    if ((rc = grow(ctx, &m->d_pts, &m->cap_pts, std::max<size_t>(tot_pts, 1)))) return rc;
-    if ((rc = grow(ctx, &m->d_cells, &m->cap_cells, std::max<size_t>(tot_cells, 1)))) return rc;
-    if (m->cap_probs < n) {
-      (void)hipFree(m->d_probs), (void)hipFree(m->d_rounds), (void)hipFree(m->d_jobs), (void)hipFree(m->d_carry), (void)hipFree(m->d_results);
-      m->d_probs = nullptr, m->d_rounds = nullptr, m->d_jobs = nullptr, m->d_carry = nullptr, m->d_results = nullptr, m->cap_probs = 0;
-      HIP_TRY(ctx, hipMalloc(&m->d_probs, (size_t)n * sizeof(MapDev)));
-      HIP_TRY(ctx, hipMalloc(&m->d_rounds, (size_t)n * sizeof(MapRoundParams)));
-      HIP_TRY(ctx, hipMalloc(&m->d_jobs, (size_t)n * 2 * sizeof(MapGridJob)));
-      HIP_TRY(ctx, hipMalloc(&m->d_carry, (size_t)n * sizeof(LmCarry)));
-      HIP_TRY(ctx, hipMalloc((void**)&m->d_results, (size_t)n * sizeof(lins_map_result)));
-      m->cap_probs = n;
-    }
+    BUF_TRY(ctx, m->d_raw.grow(tot_pts));
+    BUF_TRY(ctx, m->d_pts.grow(tot_pts));
+    BUF_TRY(ctx, m->d_cells.grow(tot_cells));
+    BUF_TRY(ctx, m->grow_problems((size_t)n));
     for (int k = 0; k < n; ++k) {
       if (in[k].n_map_corner)
         HIP_TRY(ctx, hipMemcpyAsync(m->d_raw + jobs[(size_t)k * 2].off_raw, in[k].map_corner, (size_t)in[k].n_map_corner * sizeof(float4), hipMemcpyHostToDevice, st));
@@ -197,12 +159,7 @@ int map_upload(lins_ctx* ctx, MapState* m, int n, const lins_map_problem* in, st
     tot_q += (size_t)dev[k].n_q[0] + dev[k].n_q[1];
     *max_q = std::max(*max_q, dev[k].n_q[0] + dev[k].n_q[1]);
   }
-  if (m->cap_hq < std::max<size_t>(tot_q, 1)) {
-    (void)hipHostFree(m->h_q);
-    m->h_q = nullptr, m->cap_hq = 0;
-    HIP_TRY(ctx, hipHostMalloc((void**)&m->h_q, std::max<size_t>(tot_q, 1) * sizeof(float4)));
-    m->cap_hq = std::max<size_t>(tot_q, 1);
-  }
+  BUF_TRY(ctx, m->h_q.grow(tot_q));
   rc = parallel_for(n, [&](int k) {  // input contract + packing into the pinned staging buffer
     float4* dst = m->h_q + dev[k].off_q;
     for (int i = 0; i < in[k].n_scan_corner + in[k].n_scan_surf; ++i) {
@@ -213,13 +170,7 @@ int map_upload(lins_ctx* ctx, MapState* m, int n, const lins_map_problem* in, st
     return (int)LINS_OK;
   });
   if (rc) return rc;
-  if (m->cap_q < std::max<size_t>(tot_q, 1)) {
-    (void)hipFree(m->d_q), (void)hipFree(m->d_rec);
-    m->d_q = nullptr, m->d_rec = nullptr, m->cap_q = 0;
-    HIP_TRY(ctx, hipMalloc((void**)&m->d_q, std::max<size_t>(tot_q, 1) * sizeof(float4)));
-    HIP_TRY(ctx, hipMalloc((void**)&m->d_rec, std::max<size_t>(tot_q, 1) * sizeof(lins_map_corr)));
-    m->cap_q = std::max<size_t>(tot_q, 1);
-  }
+  BUF_TRY(ctx, m->grow_queries(tot_q));
   if (tot_q) HIP_TRY(ctx, hipMemcpyAsync(m->d_q, m->h_q, tot_q * sizeof(float4), hipMemcpyHostToDevice, st));
   m->resident_dev = dev;
   return LINS_OK;
@@ -253,26 +204,10 @@ int map_upload_local(lins_ctx* ctx, MapState* m, const LocalMapView& lv, std::ve
     tot_q += (size_t)dev[k].n_q[0] + dev[k].n_q[1];
     *max_q = std::max(*max_q, dev[k].n_q[0] + dev[k].n_q[1]);
   }
-  int rc;
-  if ((rc = grow(ctx, &m->d_pts, &m->cap_pts, std::max<size_t>(tot_pts, 1)))) return rc;
-  if ((rc = grow(ctx, &m->d_cells, &m->cap_cells, std::max<size_t>(tot_cells, 1)))) return rc;
-  if (m->cap_probs < n) {
-    (void)hipFree(m->d_probs), (void)hipFree(m->d_rounds), (void)hipFree(m->d_jobs), (void)hipFree(m->d_carry), (void)hipFree(m->d_results);
-    m->d_probs = nullptr, m->d_rounds = nullptr, m->d_jobs = nullptr, m->d_carry = nullptr, m->d_results = nullptr, m->cap_probs = 0;
-    HIP_TRY(ctx, hipMalloc(&m->d_probs, (size_t)n * sizeof(MapDev)));
-    HIP_TRY(ctx, hipMalloc(&m->d_rounds, (size_t)n * sizeof(MapRoundParams)));
-    HIP_TRY(ctx, hipMalloc(&m->d_jobs, (size_t)n * 2 * sizeof(MapGridJob)));
-    HIP_TRY(ctx, hipMalloc(&m->d_carry, (size_t)n * sizeof(LmCarry)));
-    HIP_TRY(ctx, hipMalloc((void**)&m->d_results, (size_t)n * sizeof(lins_map_result)));
-    m->cap_probs = n;
-  }
-  if (m->cap_q < std::max<size_t>(tot_q, 1)) {
-    (void)hipFree(m->d_q), (void)hipFree(m->d_rec);
-    m->d_q = nullptr, m->d_rec = nullptr, m->cap_q = 0;
-    HIP_TRY(ctx, hipMalloc((void**)&m->d_q, std::max<size_t>(tot_q, 1) * sizeof(float4)));
-    HIP_TRY(ctx, hipMalloc((void**)&m->d_rec, std::max<size_t>(tot_q, 1) * sizeof(lins_map_corr)));
-    m->cap_q = std::max<size_t>(tot_q, 1);
-  }
+  BUF_TRY(ctx, m->d_pts.grow(tot_pts));
+  BUF_TRY(ctx, m->d_cells.grow(tot_cells));
+  BUF_TRY(ctx, m->grow_problems((size_t)n));
+  BUF_TRY(ctx, m->grow_queries(tot_q));
   hipStream_t st = ctx_stream(ctx);
   HIP_TRY(ctx, hipMemcpyAsync(m->d_jobs, jobs.data(), jobs.size() * sizeof(MapGridJob), hipMemcpyHostToDevice, st));
   launch_map_grid(st, 2 * n, m->d_jobs, lv.d_out, m->d_pts, m->d_cells);
@@ -300,13 +235,12 @@ MapState* state_of(lins_ctx* ctx) {
 // once per context: the device plane fit on a known wall (see map_selfcheck_kernel)
 int map_selfcheck(lins_ctx* ctx, MapState* m) {
   if (m->selfcheck_done) return LINS_OK;
-  float* d = nullptr;
+  DevBuf<float> d;
   float h[5] = {0, 0, 0, 0, 0};
-  HIP_TRY(ctx, hipMalloc((void**)&d, sizeof h));
+  BUF_TRY(ctx, d.grow(5));
   launch_map_selfcheck(ctx_stream(ctx), d);
   hipError_t e = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, ctx_stream(ctx));
   if (e == hipSuccess) e = hipStreamSynchronize(ctx_stream(ctx));
-  (void)hipFree(d);
   if (e != hipSuccess) return ctx_fail_hip(ctx, e, "map self-check");
   // normal (0, -1, 0) scaled by the weight s ~ 0.97, signed distance -0.05 scaled likewise, accepted
   const bool ok = h[4] == 1.f && std::fabs(h[0]) < 1e-3f && std::fabs(h[2]) < 1e-3f && h[1] < -0.9f && std::fabs(h[3] + 0.0485f) < 2e-3f;
@@ -318,35 +252,10 @@ int map_selfcheck(lins_ctx* ctx, MapState* m) {
 }  // namespace
 
 namespace lins {
-void** map_local_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
+void** map_slot(lins_ctx* ctx, MapSlot which, void (*free_fn)(void*)) {
   MapState* m = state_of(ctx);
-  m->local_free = free_fn;
-  return &m->local;
-}
-void** map_archive_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
-  MapState* m = state_of(ctx);
-  m->archive_free = free_fn;
-  return &m->archive;
-}
-void** map_loop_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
-  MapState* m = state_of(ctx);
-  m->loop_free = free_fn;
-  return &m->loop;
-}
-void** map_pose_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
-  MapState* m = state_of(ctx);
-  m->pose_free = free_fn;
-  return &m->pose;
-}
-void** map_graph_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
-  MapState* m = state_of(ctx);
-  m->graph_free = free_fn;
-  return &m->graph;
-}
-void** map_loop_step_slot(lins_ctx* ctx, void (*free_fn)(void*)) {
-  MapState* m = state_of(ctx);
-  m->loop_step_free = free_fn;
-  return &m->loop_step;
+  m->slot_free[which] = free_fn;
+  return &m->slot[which];
 }
 
 // lins_scan2map_batch with LINS_MAP_LOCAL for the step of lins_streams_map_capi.hip: the same gridding, the same rounds,
@@ -370,7 +279,7 @@ int scan2map_local_resident(lins_ctx* ctx, int n, const MapPoseEntry* d_entries,
   }
   for (int k = 0; k < n; ++k) dev[k].pad = lv.sizes[k].status ? lv.sizes[k].status : dev[k].active;  // (for the two pose kernels)
   const int bpp = std::max(1, (max_q + map_block() - 1) / map_block());
-  if ((rc = grow(ctx, &m->d_partials, &m->cap_partials, (size_t)n * bpp * 28))) return rc;
+  BUF_TRY(ctx, m->d_partials.grow((size_t)n * bpp * 28));
   hipStream_t st = ctx_stream(ctx);
   hipEvent_t e0, e1;
   ctx_events(ctx, &e0, &e1);
@@ -432,7 +341,7 @@ int lins_scan2map_batch(lins_ctx* ctx, int n, const lins_map_problem* in, lins_m
   }
   const float4* d_q = n_local ? lv.d_out : m->d_q;
   const int bpp = std::max(1, (max_q + map_block() - 1) / map_block());
-  if ((rc = grow(ctx, &m->d_partials, &m->cap_partials, (size_t)n * bpp * 28))) return rc;
+  BUF_TRY(ctx, m->d_partials.grow((size_t)n * bpp * 28));
   hipStream_t st = ctx_stream(ctx);
   hipEvent_t e0, e1;
   ctx_events(ctx, &e0, &e1);
@@ -476,7 +385,7 @@ int lins_map_correspondences(lins_ctx* ctx, const lins_map_problem* in, lins_map
   }
   dev[0].active = 1;  // a single pass is evaluated whatever the map sizes
   const int bpp = std::max(1, (max_q + map_block() - 1) / map_block());
-  if ((rc = grow(ctx, &m->d_partials, &m->cap_partials, (size_t)bpp * 28))) return rc;
+  BUF_TRY(ctx, m->d_partials.grow((size_t)bpp * 28));
   hipStream_t st = ctx_stream(ctx);
   const MapRoundParams rd = lm_make_round(in->transform);
   HIP_TRY(ctx, hipMemcpyAsync(m->d_probs, dev.data(), sizeof(MapDev), hipMemcpyHostToDevice, st));

@@ -35,31 +35,23 @@ struct PgMem {
   int n_slots = 0, F = 0, L = 0;
   std::vector<Graph> g;
   std::vector<int> up_frames, up_loops;  // what of each slot is on the device
-  double *d_Z = nullptr, *d_D = nullptr, *d_Dt = nullptr, *d_I = nullptr, *d_T = nullptr, *d_Tt = nullptr, *d_Q = nullptr;
-  double *d_B = nullptr, *d_c = nullptr, *d_P = nullptr, *d_q = nullptr, *d_S = nullptr, *d_y = nullptr;
-  LoopRec* d_loops = nullptr;
-  State* d_st = nullptr;
-  Prob* d_probs = nullptr;
-  int *d_running = nullptr, *h_running = nullptr;
+  DevBuf<double> d_Z, d_D, d_Dt, d_I, d_T, d_Tt, d_Q;
+  DevBuf<double> d_B, d_c, d_P, d_q, d_S, d_y;
+  DevBuf<LoopRec> d_loops;
+  DevBuf<State> d_st;
+  DevBuf<Prob> d_probs;
+  DevBuf<int> d_running;
+  PinBuf<int> h_running;
   float ms = 0.f;
   uint64_t iterations = 0;
   size_t nq() const { return (size_t)F / lins_pg::kPrefixBlock + 2; }
 };
 
-void pg_release(PgMem* m) {
-  (void)hipFree(m->d_Z), (void)hipFree(m->d_D), (void)hipFree(m->d_Dt), (void)hipFree(m->d_I), (void)hipFree(m->d_T), (void)hipFree(m->d_Tt);
-  (void)hipFree(m->d_Q), (void)hipFree(m->d_B), (void)hipFree(m->d_c), (void)hipFree(m->d_P), (void)hipFree(m->d_q), (void)hipFree(m->d_S);
-  (void)hipFree(m->d_y), (void)hipFree(m->d_loops), (void)hipFree(m->d_st), (void)hipFree(m->d_probs), (void)hipFree(m->d_running);
-  (void)hipHostFree(m->h_running);
-  *m = PgMem();
-}
-void pg_free(void* p) {
-  pg_release((PgMem*)p);
-  delete (PgMem*)p;
-}
+void pg_release(PgMem* m) { *m = PgMem(); }
+void pg_free(void* p) { delete (PgMem*)p; }
 
 PgMem* mem_of(lins_ctx* ctx) {
-  void** slot = map_graph_slot(ctx, pg_free);
+  void** slot = map_slot(ctx, kSlotGraph, pg_free);
   if (!*slot) *slot = new PgMem();
   return (PgMem*)*slot;
 }
@@ -133,20 +125,19 @@ int lins_pose_graph_init(lins_ctx* ctx, int n_slots, int max_frames, int max_loo
   pg_release(m);
   const size_t n = (size_t)n_slots, F = (size_t)max_frames, L = (size_t)std::max(max_loops, 1);
   m->F = max_frames, m->L = (int)L;
-  double** frames12[] = {&m->d_Z, &m->d_D, &m->d_Dt, &m->d_I, &m->d_T, &m->d_Tt};
-  for (double** p : frames12) HIP_TRY(ctx, hipMalloc((void**)p, n * F * 12 * sizeof(double)));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_Q, n * m->nq() * 12 * sizeof(double)));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_B, n * F * 36 * sizeof(double)));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_P, n * F * 36 * sizeof(double)));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_c, n * F * 6 * sizeof(double)));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_q, n * F * 6 * sizeof(double)));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_S, n * 36 * L * L * sizeof(double)));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_y, n * 18 * L * sizeof(double)));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_loops, n * L * sizeof(LoopRec)));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_st, n * sizeof(State)));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_probs, n * sizeof(Prob)));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_running, 128 * sizeof(int)));
-  HIP_TRY(ctx, hipHostMalloc((void**)&m->h_running, sizeof(int)));
+  for (DevBuf<double>* p : {&m->d_Z, &m->d_D, &m->d_Dt, &m->d_I, &m->d_T, &m->d_Tt}) BUF_TRY(ctx, p->grow(n * F * 12));
+  BUF_TRY(ctx, m->d_Q.grow(n * m->nq() * 12));
+  BUF_TRY(ctx, m->d_B.grow(n * F * 36));
+  BUF_TRY(ctx, m->d_P.grow(n * F * 36));
+  BUF_TRY(ctx, m->d_c.grow(n * F * 6));
+  BUF_TRY(ctx, m->d_q.grow(n * F * 6));
+  BUF_TRY(ctx, m->d_S.grow(n * 36 * L * L));
+  BUF_TRY(ctx, m->d_y.grow(n * 18 * L));
+  BUF_TRY(ctx, m->d_loops.grow(n * L));
+  BUF_TRY(ctx, m->d_st.grow(n));
+  BUF_TRY(ctx, m->d_probs.grow(n));
+  BUF_TRY(ctx, m->d_running.grow(128));
+  BUF_TRY(ctx, m->h_running.grow(1));
   m->g.assign(n, Graph());
   for (Graph& g : m->g) g.max_frames = max_frames, g.max_loops = max_loops;
   m->up_frames.assign(n, 0), m->up_loops.assign(n, 0);

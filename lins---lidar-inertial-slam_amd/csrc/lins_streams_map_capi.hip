@@ -25,12 +25,14 @@ struct StreamsMap {
   int n = 0;  // streams (0: lins_streams_map_init has not run)
   double interval = 0.3;
   bool use_archive = false;
-  MapPoseRec* d_poses = nullptr;  // [n]
+  DevBuf<MapPoseRec> d_poses;  // [n]
   std::vector<double> last_time;  // timeLastProcessing per stream
   // one step's batch: entries up, result records down (pinned staging), n entries at most
-  MapPoseEntry *d_entries = nullptr, *h_entries = nullptr;
-  lins_map_step_result *d_out = nullptr, *h_out = nullptr;
-  hipEvent_t ev[4] = {};  // associate start / end, finish start / end
+  DevBuf<MapPoseEntry> d_entries;
+  PinBuf<MapPoseEntry> h_entries;
+  DevBuf<lins_map_step_result> d_out;
+  PinBuf<lins_map_step_result> h_out;
+  Event ev[4];  // associate start / end, finish start / end
   float associate_ms = 0.f, finish_ms = 0.f;
   // currentRobotPosPoint per stream (LM:1655-1658): transform[3..5] of its last entry with status OK
   std::vector<float> centre;   // [n][3]
@@ -43,32 +45,25 @@ struct StreamsMap {
   float radius = 50.f, pose_leaf = 1.f;
   std::vector<std::vector<int>> lists;  // [n] surroundingExistingKeyPosesID
   // a write-back's batch (lins_pose_graph_apply_batch): n entries at most
-  MapPoseFix *d_fix = nullptr, *h_fix = nullptr;
-  // lins_map_associate_batch's own buffers (grown, never shrunk)
-  MapPoseRec* d_ab_poses = nullptr;
-  MapPoseEntry* d_ab_entries = nullptr;
-  lins_map_step_result* d_ab_out = nullptr;
-  size_t cap_ab = 0;
+  DevBuf<MapPoseFix> d_fix;
+  PinBuf<MapPoseFix> h_fix;
+  // lins_map_associate_batch's own buffers (grown together, never shrunk; d_ab_poses answers)
+  DevBuf<MapPoseRec> d_ab_poses;
+  DevBuf<MapPoseEntry> d_ab_entries;
+  DevBuf<lins_map_step_result> d_ab_out;
 };
 
 void step_buffers_free(StreamsMap* m) {
-  (void)hipFree(m->d_poses), (void)hipFree(m->d_entries), (void)hipFree(m->d_out), (void)hipFree(m->d_fix);
-  (void)hipHostFree(m->h_entries), (void)hipHostFree(m->h_out), (void)hipHostFree(m->h_fix);
-  m->d_poses = nullptr, m->d_entries = m->h_entries = nullptr, m->d_out = m->h_out = nullptr, m->d_fix = m->h_fix = nullptr, m->n = 0;
+  m->d_poses.reset(), m->d_entries.reset(), m->d_out.reset(), m->d_fix.reset();
+  m->h_entries.reset(), m->h_out.reset(), m->h_fix.reset();
+  m->n = 0;
   m->loop = m->surround = false;
 }
 
-void streams_map_free(void* p) {
-  StreamsMap* m = (StreamsMap*)p;
-  step_buffers_free(m);
-  (void)hipFree(m->d_ab_poses), (void)hipFree(m->d_ab_entries), (void)hipFree(m->d_ab_out);
-  for (hipEvent_t e : m->ev)
-    if (e) (void)hipEventDestroy(e);
-  delete m;
-}
+void streams_map_free(void* p) { delete (StreamsMap*)p; }
 
 StreamsMap* state_of(lins_ctx* ctx) {
-  void** slot = map_pose_slot(ctx, streams_map_free);
+  void** slot = map_slot(ctx, kSlotPose, streams_map_free);
   if (!*slot) *slot = new StreamsMap();
   return (StreamsMap*)*slot;
 }
@@ -127,14 +122,7 @@ int lins_map_associate_batch(lins_ctx* ctx, int n, const float* bef6, const floa
     if (!finite6(bef6 + 6 * k) || !finite6(aft6 + 6 * k) || !finite6(sum6 + 6 * k)) return LINS_E_INPUT;
   HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
   StreamsMap* m = state_of(ctx);
-  if (m->cap_ab < (size_t)n) {
-    (void)hipFree(m->d_ab_poses), (void)hipFree(m->d_ab_entries), (void)hipFree(m->d_ab_out);
-    m->d_ab_poses = nullptr, m->d_ab_entries = nullptr, m->d_ab_out = nullptr, m->cap_ab = 0;
-    HIP_TRY(ctx, hipMalloc((void**)&m->d_ab_poses, (size_t)n * sizeof(MapPoseRec)));
-    HIP_TRY(ctx, hipMalloc((void**)&m->d_ab_entries, (size_t)n * sizeof(MapPoseEntry)));
-    HIP_TRY(ctx, hipMalloc((void**)&m->d_ab_out, (size_t)n * sizeof(lins_map_step_result)));
-    m->cap_ab = (size_t)n;
-  }
+  BUF_TRY(ctx, grow_all(m->d_ab_poses, (size_t)n, m->d_ab_entries, (size_t)n, m->d_ab_out, (size_t)n));
   std::vector<MapPoseRec> recs((size_t)n, MapPoseRec{});
   std::vector<MapPoseEntry> ent((size_t)n, MapPoseEntry{});
   std::vector<lins_map_step_result> res((size_t)n);
@@ -162,15 +150,14 @@ int lins_streams_map_init(lins_ctx* ctx, int n_streams, double process_interval)
   StreamsMap* m = state_of(ctx);
   HIP_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));
   step_buffers_free(m);
-  for (hipEvent_t& e : m->ev)
-    if (!e) HIP_TRY(ctx, hipEventCreate(&e));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_poses, (size_t)n_streams * sizeof(MapPoseRec)));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_entries, (size_t)n_streams * sizeof(MapPoseEntry)));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_out, (size_t)n_streams * sizeof(lins_map_step_result)));
-  HIP_TRY(ctx, hipHostMalloc((void**)&m->h_entries, (size_t)n_streams * sizeof(MapPoseEntry)));
-  HIP_TRY(ctx, hipHostMalloc((void**)&m->h_out, (size_t)n_streams * sizeof(lins_map_step_result)));
-  HIP_TRY(ctx, hipMalloc((void**)&m->d_fix, (size_t)n_streams * sizeof(MapPoseFix)));
-  HIP_TRY(ctx, hipHostMalloc((void**)&m->h_fix, (size_t)n_streams * sizeof(MapPoseFix)));
+  for (Event& e : m->ev) BUF_TRY(ctx, e.create());
+  BUF_TRY(ctx, m->d_poses.grow((size_t)n_streams));
+  BUF_TRY(ctx, m->d_entries.grow((size_t)n_streams));
+  BUF_TRY(ctx, m->d_out.grow((size_t)n_streams));
+  BUF_TRY(ctx, m->h_entries.grow((size_t)n_streams));
+  BUF_TRY(ctx, m->h_out.grow((size_t)n_streams));
+  BUF_TRY(ctx, m->d_fix.grow((size_t)n_streams));
+  BUF_TRY(ctx, m->h_fix.grow((size_t)n_streams));
   HIP_TRY(ctx, hipMemsetAsync(m->d_poses, 0, (size_t)n_streams * sizeof(MapPoseRec), ctx_stream(ctx)));  // allocateMemory (LM:305-409)
   HIP_TRY(ctx, hipStreamSynchronize(ctx_stream(ctx)));
   m->last_time.assign((size_t)n_streams, -1.0);  // LM:356
@@ -396,7 +383,8 @@ int lins::streams_map_step_run(lins_ctx* ctx, int n, const int32_t* streams, con
     return rc;
   }
   // transformAssociateToMap, scan2MapOptimization, transformUpdate, the key-frame rule
-  if ((rc = scan2map_local_resident(ctx, nb, m->d_entries, m->d_poses, m->d_out, m->h_out, m->ev, odom ? nullptr : in.d_odom))) return rc;
+  hipEvent_t ev[4] = {m->ev[0], m->ev[1], m->ev[2], m->ev[3]};
+  if ((rc = scan2map_local_resident(ctx, nb, m->d_entries, m->d_poses, m->d_out, m->h_out, ev, odom ? nullptr : in.d_odom))) return rc;
   HIP_TRY(ctx, hipEventElapsedTime(&m->associate_ms, m->ev[0], m->ev[1]));
   HIP_TRY(ctx, hipEventElapsedTime(&m->finish_ms, m->ev[2], m->ev[3]));
   std::vector<int32_t> key_entries;

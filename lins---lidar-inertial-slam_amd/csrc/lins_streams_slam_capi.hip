@@ -9,12 +9,7 @@ using namespace lins;
 
 namespace lins {
 
-void streams_slam_free(lins_ctx* ctx) {
-  auto& s = ctx->st.s;
-  (void)hipFree(s.d_odom), (void)hipFree(s.d_ints), (void)hipFree(s.d_fused);
-  (void)hipHostFree(s.h_odom), (void)hipHostFree(s.h_ints), (void)hipHostFree(s.h_fused);
-  s = lins_ctx::Streams::Slam{};
-}
+void streams_slam_free(lins_ctx* ctx) { ctx->st.s = lins_ctx::Streams::Slam{}; }
 
 // the records of an earlier run are not this run's: lins_streams_machine_init and lins_streams_map_init call this
 void streams_slam_reset(lins_ctx* ctx) { ctx->st.s.have = false; }
@@ -26,12 +21,12 @@ int slam_alloc(lins_ctx* ctx) {
   auto& s = t.s;
   if (s.d_odom) return LINS_OK;
   const size_t n = (size_t)t.n;
-  HIP_TRY(ctx, hipMalloc((void**)&s.d_odom, n * sizeof(lins_stream_odom)));
-  HIP_TRY(ctx, hipHostMalloc((void**)&s.h_odom, n * sizeof(lins_stream_odom)));
-  HIP_TRY(ctx, hipMalloc((void**)&s.d_ints, n * 2 * sizeof(int)));
-  HIP_TRY(ctx, hipHostMalloc((void**)&s.h_ints, n * 2 * sizeof(int)));
-  HIP_TRY(ctx, hipMalloc((void**)&s.d_fused, n * sizeof(lins_fused_pose)));
-  HIP_TRY(ctx, hipHostMalloc((void**)&s.h_fused, n * sizeof(lins_fused_pose)));
+  BUF_TRY(ctx, s.d_odom.grow(n));
+  BUF_TRY(ctx, s.h_odom.grow(n));
+  BUF_TRY(ctx, s.d_ints.grow(n * 2));
+  BUF_TRY(ctx, s.h_ints.grow(n * 2));
+  BUF_TRY(ctx, s.d_fused.grow(n));
+  BUF_TRY(ctx, s.h_fused.grow(n));
   return LINS_OK;
 }
 

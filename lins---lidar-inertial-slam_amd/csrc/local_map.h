@@ -84,12 +84,12 @@ struct LocalMapView {
 int local_map_view(lins_ctx* ctx, LocalMapView* v);
 int local_map_slots(lins_ctx* ctx);  // n_slots of lins_local_map_init (0 before it)
 int local_map_ring(lins_ctx* ctx, int slot, int* window);  // frames on the ring of slot (-1: no such slot) and the rings' window
-void** map_local_slot(lins_ctx* ctx, void (*free_fn)(void*));  // lins_map_capi.hip: held by the scan-to-map state
-void** map_archive_slot(lins_ctx* ctx, void (*free_fn)(void*));  // ... and the key-frame archive's (lins_archive_capi.hip)
-void** map_loop_slot(lins_ctx* ctx, void (*free_fn)(void*));     // ... and the loop-closure ICP's (lins_loop_icp_capi.hip)
-void** map_pose_slot(lins_ctx* ctx, void (*free_fn)(void*));     // ... and the streams' map poses (lins_streams_map_capi.hip)
-void** map_graph_slot(lins_ctx* ctx, void (*free_fn)(void*));    // ... and the pose graphs (lins_pose_graph_capi.hip)
-void** map_loop_step_slot(lins_ctx* ctx, void (*free_fn)(void*));  // ... and the loop thread's step (lins_loop_step_capi.hip)
+// lins_map_capi.hip: what the scan-to-map state holds for the other mapping files and frees with itself, in this order —
+// the local map (lins_local_map_capi.hip), the key-frame archive (lins_archive_capi.hip), the loop-closure ICP
+// (lins_loop_icp_capi.hip), the streams' map poses (lins_streams_map_capi.hip), the pose graphs
+// (lins_pose_graph_capi.hip), the loop thread's step (lins_loop_step_capi.hip)
+enum MapSlot { kSlotLocal, kSlotArchive, kSlotLoop, kSlotPose, kSlotGraph, kSlotLoopStep, kSlotCount };
+void** map_slot(lins_ctx* ctx, MapSlot which, void (*free_fn)(void*));
 
 // lins_streams_map_capi.hip, for the write-back of a loop closure and the loop thread's step
 int streams_map_streams(lins_ctx* ctx);  // streams of lins_streams_map_init (0 before it)
