@@ -595,3 +595,12 @@ class FusedPoseC(C.Structure):
 
 class SlamImuC(C.Structure):
     _fields_ = [("roll", C.c_float), ("pitch", C.c_float), ("has_imu", C.c_int32), ("reserved", C.c_int32)]
+
+
+# ---- stream lifecycle (include/lins_lifecycle.h): the records of the compaction plan ----
+class ArenaBlockC(C.Structure):
+    _fields_ = [("off", C.c_longlong), ("n", C.c_longlong), ("keep", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ArenaSegmentC(C.Structure):
+    _fields_ = [("src", C.c_longlong), ("dst", C.c_longlong), ("n", C.c_longlong), ("pass_", C.c_int32), ("direct", C.c_int32)]

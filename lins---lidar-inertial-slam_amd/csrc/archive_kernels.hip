@@ -9,6 +9,8 @@
 //               Integer sums: the same bits as the one-workgroup scan, whatever the chunk
 //   compaction  leaf == 0: per-tile keep counts -> the same scan -> stable scatter in input order
 // Every kernel takes all jobs of a call in one launch, over a (job, tile) or a (job, chunk) table.
+// The arena itself is compacted when slots are released (include/lins_lifecycle.h): ar_reclaim_gather / _scatter / _move
+// at the end of this file run the passes of the plan of host/arena_reclaim.h over a (segment, tile) table.
 #include <hip/hip_runtime.h>
 
 #include "../../include/lins_ieskf.h"
@@ -219,7 +221,47 @@ __global__ __launch_bounds__(kLmTile) void ar_compact_kernel(const int2* __restr
   out[jb.off_out + before + __popcll(kb & lane_lt())] = p;
 }
 
+// ---- the arena's compaction (lins_archive_release_slots): one workgroup per (segment, tile) entry of a pass, one float4
+// per lane, one guarded block.  No lane reads what another lane of the same launch writes: gather and scatter have the
+// staging buffer on one side, and a pass is moved inside the arena only when its destination range ends at or before
+// its first source (host/arena_reclaim.h "direct").
+__global__ __launch_bounds__(kLmTile) void ar_reclaim_gather_kernel(const ArMove* __restrict__ segs, const int2* __restrict__ blocks,
+                                                                    const float4* __restrict__ arena, float4* __restrict__ stage) {
+  const int2 b = blocks[blockIdx.x];
+  const ArMove& s = segs[b.x];
+  const long long i = (long long)b.y * kLmTile + threadIdx.x;
+  if (i < s.n) stage[s.stg + i] = arena[s.src + i];
+}
+
+__global__ __launch_bounds__(kLmTile) void ar_reclaim_scatter_kernel(const ArMove* __restrict__ segs, const int2* __restrict__ blocks,
+                                                                     const float4* __restrict__ stage, float4* __restrict__ arena) {
+  const int2 b = blocks[blockIdx.x];
+  const ArMove& s = segs[b.x];
+  const long long i = (long long)b.y * kLmTile + threadIdx.x;
+  if (i < s.n) arena[s.dst + i] = stage[s.stg + i];
+}
+
+__global__ __launch_bounds__(kLmTile) void ar_reclaim_move_kernel(const ArMove* __restrict__ segs, const int2* __restrict__ blocks,
+                                                                  float4* arena) {
+  const int2 b = blocks[blockIdx.x];
+  const ArMove& s = segs[b.x];
+  const long long i = (long long)b.y * kLmTile + threadIdx.x;
+  if (i < s.n) arena[s.dst + i] = arena[s.src + i];
+}
+
 }  // namespace
+
+void launch_ar_reclaim_gather(hipStream_t s, int n_blocks, const ArMove* segs, const int2* blocks, const float4* arena, float4* stage) {
+  if (n_blocks) hipLaunchKernelGGL(ar_reclaim_gather_kernel, dim3(n_blocks), dim3(kLmTile), 0, s, segs, blocks, arena, stage);
+}
+
+void launch_ar_reclaim_scatter(hipStream_t s, int n_blocks, const ArMove* segs, const int2* blocks, const float4* stage, float4* arena) {
+  if (n_blocks) hipLaunchKernelGGL(ar_reclaim_scatter_kernel, dim3(n_blocks), dim3(kLmTile), 0, s, segs, blocks, stage, arena);
+}
+
+void launch_ar_reclaim_move(hipStream_t s, int n_blocks, const ArMove* segs, const int2* blocks, float4* arena) {
+  if (n_blocks) hipLaunchKernelGGL(ar_reclaim_move_kernel, dim3(n_blocks), dim3(kLmTile), 0, s, segs, blocks, arena);
+}
 
 void launch_ar_gather(hipStream_t s, int n_blocks, const LmSeg* segs, const int2* blocks, const float4* arena, float4* stage, LmState* states) {
   if (n_blocks) hipLaunchKernelGGL(ar_gather_kernel, dim3(n_blocks), dim3(kLmTile), 0, s, segs, blocks, arena, stage, states);

@@ -30,6 +30,15 @@ struct ArSplit {  // one split job
 };
 static_assert(sizeof(ArSplit) == 16, "ArSplit layout");
 
+// ---- the arena's compaction (lins_archive_release_slots; the plan: host/arena_reclaim.h).  One segment of one pass:
+// n points from arena + src to arena + dst, a staged pass by way of stage + stg (the pass's points lie packed there)
+struct ArMove {
+  long long src, dst, n;
+  long long stg;
+};
+static_assert(sizeof(ArMove) == 32, "ArMove layout");
+constexpr long long kArReclaimChunk = 1ll << 20;  // default points per pass (16 MiB of staging; DESIGN.md "Stream lifecycle")
+
 // (host side) the clouds of the last assembly where the loop-closure ICP reads them: cloud k starts at d_out + off[k]
 // and holds info[k].n points; filtered[k]: it went through VoxelGrid, so info[k] carries its 1 m box.  LINS_E_STATE
 // when there was no assembly.

@@ -1,7 +1,8 @@
 // lins_archive_capi.hip — C ABI of the key-frame archive (include/lins_map.h lins_archive_*): every key frame of a slot
 // in one bump-allocated device arena, the host's list of frames (offset, counts, pose, trigonometry, time), the
 // selection of frames (host/keyframe_select.h — the same inline code liblins_host.so exports), and the packing of an
-// assembly into the jobs of archive_kernels.hip / local_map_kernels.hip.
+// assembly into the jobs of archive_kernels.hip / local_map_kernels.hip.  Slots are released, and the arena compacted
+// behind them, by lins_archive_release_slots (include/lins_lifecycle.h; archive_release_apply below).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -10,10 +11,13 @@
 #include <cstring>
 #include <vector>
 
+#include "../../include/lins_lifecycle.h"
 #include "../../include/lins_map.h"
+#include "host/arena_reclaim.h"
 #include "host/keyframe_select.h"
 #include "keyframe_archive.h"
 #include "keypose_select_math.h"
+#include "lifecycle.h"
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
 #include "local_map.h"
@@ -54,6 +58,15 @@ struct Archive {
   int kp_mode = LINS_KEYPOSES_HOST, kp_host = 0;
   float kp_ms = 0.f;
   uint64_t kp_hits = 0;
+  // the arena's compaction (lins_archive_release_slots): points per pass, the staging buffer of that many points
+  // (allocated by the first staged pass), one table up (segments | blocks; pinned staging), the last compaction
+  long long reclaim_chunk = kArReclaimChunk;
+  DevBuf<float4> d_reclaim;
+  DevBuf<char> d_rc_tab;  // (bytes)
+  PinBuf<char> h_rc_tab;
+  float rc_ms = 0.f;
+  uint64_t rc_moved = 0;
+  int rc_staged = 0, rc_direct = 0;
 };
 
 void archive_free(void* p) { delete (Archive*)p; }
@@ -95,6 +108,98 @@ int archive_store(lins_ctx* ctx, ArchiveStore* v) {
   Archive* m = archive_of(ctx);
   if (!m->n_slots) return LINS_E_STATE;
   v->d_arena = m->d_arena, v->n_slots = m->n_slots, v->chunk = m->chunk, v->frames = &m->frames;
+  return LINS_OK;
+}
+
+int archive_slots(lins_ctx* ctx) { return archive_of(ctx)->n_slots; }
+
+// The frames of the slots named go, the arena closes up behind them (host/arena_reclaim.h: the plan; archive_kernels.hip
+// ar_reclaim_*: its passes).  One table upload in front, every pass queued back to back, one synchronisation behind;
+// the host's records change only after that synchronisation.  Arguments checked by the caller, context quiesced.
+int archive_release_apply(lins_ctx* ctx, int n, const int32_t* slots, long long* released) {
+  Archive* m = archive_of(ctx);
+  m->rc_ms = 0.f, m->rc_moved = 0, m->rc_staged = m->rc_direct = 0;
+  if (released) *released = 0;
+  if (n == 0) return LINS_OK;
+  std::vector<char> drop((size_t)m->n_slots, 0);
+  for (int k = 0; k < n; ++k) drop[slots[k]] = 1;
+  // the arena's blocks in offset order: one per frame (pushes are appended, so a slot's frames ascend already)
+  struct Ref {
+    int slot, id;
+  };
+  std::vector<Ref> refs;
+  for (int s = 0; s < m->n_slots; ++s)
+    for (int i = 0; i < (int)m->frames[s].size(); ++i) refs.push_back(Ref{s, i});
+  auto total_of = [](const ArFrame& f) { return (long long)f.n[0] + f.n[1] + f.n[2]; };
+  std::sort(refs.begin(), refs.end(), [&](const Ref& a, const Ref& b) {  // (an empty frame shares its offset with the next one: it goes first)
+    const ArFrame &fa = m->frames[a.slot][a.id], &fb = m->frames[b.slot][b.id];
+    return fa.off != fb.off ? fa.off < fb.off : (total_of(fa) != 0) < (total_of(fb) != 0);
+  });
+  std::vector<lins_arena_block> blocks(refs.size());
+  long long freed = 0;
+  for (size_t i = 0; i < refs.size(); ++i) {
+    const ArFrame& f = m->frames[refs[i].slot][refs[i].id];
+    blocks[i] = lins_arena_block{f.off, (long long)f.n[0] + f.n[1] + f.n[2], drop[refs[i].slot] ? 0 : 1, 0};
+    if (drop[refs[i].slot]) freed += blocks[i].n;
+  }
+  if (!lins_reclaim::blocks_ok((int)blocks.size(), blocks.data())) return LINS_E_STATE;  // (the records are the archive's own)
+  std::vector<lins_arena_segment> plan;
+  const int n_passes = lins_reclaim::plan((int)blocks.size(), blocks.data(), m->reclaim_chunk, plan);
+  if (!plan.empty()) {
+    // the table: segments | (segment, tile) entries, pass p's entries at [first[p], first[p + 1])
+    std::vector<ArMove> segs(plan.size());
+    std::vector<int2> tiles;
+    std::vector<size_t> first((size_t)n_passes + 1, 0);
+    std::vector<char> direct((size_t)n_passes, 0);
+    long long stg = 0, need_stage = 0;
+    uint64_t moved = 0;
+    for (size_t i = 0; i < plan.size(); ++i) {
+      const lins_arena_segment& g = plan[i];
+      if (i == 0 || plan[i - 1].pass != g.pass) stg = 0, first[g.pass] = tiles.size(), direct[g.pass] = (char)g.direct;
+      if (g.src < g.dst || g.dst < 0 || g.n < 1 || g.src + g.n > m->used || stg + g.n > m->reclaim_chunk) return LINS_E_STATE;
+      segs[i] = ArMove{g.src, g.dst, g.n, stg};
+      stg += g.n, moved += (uint64_t)g.n;
+      if (!g.direct) need_stage = std::max(need_stage, stg);
+      const long long nt = (g.n + kLmTile - 1) / kLmTile;
+      if (i > (size_t)INT_MAX || nt > INT_MAX || tiles.size() + (size_t)nt > (size_t)INT_MAX) return LINS_E_CAPACITY;
+      for (long long t = 0; t < nt; ++t) tiles.push_back(make_int2((int)i, (int)t));
+    }
+    first[n_passes] = tiles.size();
+    const size_t o_tiles = align64(segs.size() * sizeof(ArMove)), tab_bytes = align64(o_tiles + tiles.size() * sizeof(int2));
+    BUF_TRY(ctx, m->h_rc_tab.grow(tab_bytes));
+    BUF_TRY(ctx, m->d_rc_tab.grow(tab_bytes));
+    if (need_stage) BUF_TRY(ctx, m->d_reclaim.grow((size_t)std::min(m->reclaim_chunk, m->max_points)));
+    std::memcpy(m->h_rc_tab, segs.data(), segs.size() * sizeof(ArMove));
+    std::memcpy(m->h_rc_tab + o_tiles, tiles.data(), tiles.size() * sizeof(int2));
+    hipStream_t st = ctx_stream(ctx);
+    hipEvent_t e0, e1;
+    ctx_events(ctx, &e0, &e1);
+    HIP_TRY(ctx, hipMemcpyAsync(m->d_rc_tab, m->h_rc_tab, tab_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipEventRecord(e0, st));
+    const ArMove* d_segs = (const ArMove*)m->d_rc_tab.get();
+    const int2* d_tiles = (const int2*)(m->d_rc_tab + o_tiles);
+    for (int p = 0; p < n_passes; ++p) {
+      const int cnt = (int)(first[p + 1] - first[p]);
+      if (direct[p]) {
+        launch_ar_reclaim_move(st, cnt, d_segs, d_tiles + first[p], m->d_arena);
+      } else {
+        launch_ar_reclaim_gather(st, cnt, d_segs, d_tiles + first[p], m->d_arena, m->d_reclaim);
+        launch_ar_reclaim_scatter(st, cnt, d_segs, d_tiles + first[p], m->d_reclaim, m->d_arena);
+      }
+      (direct[p] ? m->rc_direct : m->rc_staged) += 1;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(e1, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    HIP_TRY(ctx, hipEventElapsedTime(&m->rc_ms, e0, e1));
+    m->rc_moved = moved;
+  }
+  const std::vector<long long> to = lins_reclaim::new_offsets((int)blocks.size(), blocks.data());
+  for (size_t i = 0; i < refs.size(); ++i)
+    if (blocks[i].keep) m->frames[refs[i].slot][refs[i].id].off = to[i];
+  for (int k = 0; k < n; ++k) m->frames[slots[k]].clear(), m->stale_from[slots[k]] = 0;
+  m->used -= freed;
+  if (released) *released = freed;
   return LINS_OK;
 }
 }  // namespace lins
@@ -437,6 +542,41 @@ int lins_archive_download(lins_ctx* ctx, int entry, lins_point* out, int cap) {
   HIP_TRY(ctx, hipMemcpyAsync(out, m->d_out + m->off[entry], (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   return cnt;
+}
+
+// ---- include/lins_lifecycle.h: the archive's part
+int lins_archive_usage(lins_ctx* ctx, long long* used, long long* capacity) {
+  if (!ctx) return LINS_E_ARG;
+  Archive* m = archive_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (used) *used = m->used;
+  if (capacity) *capacity = m->max_points;
+  return LINS_OK;
+}
+
+int lins_archive_release_slots(lins_ctx* ctx, int n, const int32_t* slots, long long* released) {
+  if (!ctx) return LINS_E_ARG;
+  Archive* m = archive_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (int rc = release_list_check(n, slots, m->n_slots)) return rc;
+  if (int rc = ctx_quiesce(ctx)) return rc;
+  return archive_release_apply(ctx, n, slots, released);
+}
+
+int lins_archive_set_reclaim_chunk(lins_ctx* ctx, long long chunk_points) {
+  if (!ctx || chunk_points < 0) return LINS_E_ARG;
+  archive_of(ctx)->reclaim_chunk = chunk_points ? chunk_points : kArReclaimChunk;
+  return LINS_OK;
+}
+
+int lins_last_reclaim_stats(lins_ctx* ctx, float* ms, uint64_t* points_moved, int32_t* staged_passes, int32_t* direct_passes) {
+  if (!ctx) return LINS_E_ARG;
+  Archive* m = archive_of(ctx);
+  if (ms) *ms = m->rc_ms;
+  if (points_moved) *points_moved = m->rc_moved;
+  if (staged_passes) *staged_passes = m->rc_staged;
+  if (direct_passes) *direct_passes = m->rc_direct;
+  return LINS_OK;
 }
 
 int lins_last_archive_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* points_in) {

@@ -5,6 +5,7 @@
 // state + covariance, and pinned host staging.  Caller owns every host buffer it
 // passes in; nothing is retained after a call returns.
 
+#include "lifecycle.h"
 #include "lins_ctx.h"
 
 using namespace lins;
@@ -292,6 +293,14 @@ int split_join(lins_ctx* ctx) {
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->hist1b[ctx->split_h], 0));
     ctx->split_pending = false;
   }
+  return LINS_OK;
+}
+
+// (lifecycle.h) what every release call does before it touches state: nothing of the context is still running
+int ctx_quiesce(lins_ctx* ctx) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = split_join(ctx)) return rc;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return LINS_OK;
 }
 

@@ -28,6 +28,7 @@ struct LmJob;
 struct LmState;
 struct ArChunk;    // keyframe_archive.h
 struct ArSplit;
+struct ArMove;
 struct KpStale;
 struct KpEntry;
 struct KpOut;
@@ -169,6 +170,12 @@ void launch_ar_keep(hipStream_t s, int j0, int n_jobs, int n_tiles, const int2* 
                     const float4* stage, int* tilecnt);
 void launch_ar_compact(hipStream_t s, int n_tiles, const int2* tiles, const LmJob* jobs, const LmState* states, const int* jflags, const float4* stage,
                        const int* tilecnt, float4* out);
+// the arena's compaction, one pass of the plan (host/arena_reclaim.h): blocks: the pass's (segment, tile) entries.  A
+// staged pass is gather (arena -> stage) then scatter (stage -> arena); a direct pass — destination range in front of
+// its first source — is one move inside the arena
+void launch_ar_reclaim_gather(hipStream_t s, int n_blocks, const ArMove* segs, const int2* blocks, const float4* arena, float4* stage);
+void launch_ar_reclaim_scatter(hipStream_t s, int n_blocks, const ArMove* segs, const int2* blocks, const float4* stage, float4* arena);
+void launch_ar_reclaim_move(hipStream_t s, int n_blocks, const ArMove* segs, const int2* blocks, float4* arena);
 
 // ---- keypose_select_kernels.hip: which key frames a map or a loop closure takes (keyframe_archive.h Kp*, keypose_select_math.h)
 // the stale records into the mirror, one lane each

@@ -11,8 +11,10 @@
 #include <cstring>
 #include <vector>
 
+#include "../../include/lins_lifecycle.h"
 #include "../../include/lins_map.h"
 #include "keyframe_archive.h"
+#include "lifecycle.h"
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
 #include "local_map.h"
@@ -116,9 +118,29 @@ int local_map_ring(lins_ctx* ctx, int slot, int* window) {
   if (window) *window = m->window;
   return m->count[slot];
 }
+// (lifecycle.h) the rings of the slots named as lins_local_map_init leaves them; the last build's clouds stay
+int local_map_release_apply(lins_ctx* ctx, int n, const int32_t* slots) {
+  LocalMap* m = local_of(ctx);
+  for (int k = 0; k < n; ++k) {
+    const int s = slots[k];
+    m->head[s] = m->count[s] = 0;
+    std::fill(m->meta.begin() + (size_t)s * m->window, m->meta.begin() + (size_t)(s + 1) * m->window, KeyFrame{});
+  }
+  return LINS_OK;
+}
 }  // namespace lins
 
 extern "C" {
+
+int lins_local_map_release_slot(lins_ctx* ctx, int slot) {
+  if (!ctx) return LINS_E_ARG;
+  LocalMap* m = local_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  const int32_t s = slot;
+  if (int rc = release_list_check(1, &s, m->n_slots)) return rc;
+  if (int rc = ctx_quiesce(ctx)) return rc;  // (a push_scans copy may still read the ring)
+  return local_map_release_apply(ctx, 1, &s);
+}
 
 int lins_local_map_init(lins_ctx* ctx, int n_slots, int window, int max_points_per_frame) {
   if (!ctx || n_slots < 1 || window < 1 || window > 4096 || max_points_per_frame < 1) return LINS_E_ARG;

@@ -10,9 +10,11 @@
 #include <cstring>
 #include <vector>
 
+#include "../../include/lins_lifecycle.h"
 #include "../../include/lins_map.h"
 #include "../../include/lins_streams_map.h"
 #include "host/voxel_map.h"
+#include "lifecycle.h"
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
 #include "local_map.h"
@@ -109,9 +111,33 @@ int pose_graph_apply_check(lins_ctx* ctx, int n, const int32_t* slots, const int
   }
   return LINS_OK;
 }
+
+// (lifecycle.h) the graphs of the slots named as lins_pose_graph_init leaves them: no frames, no loops, nothing of
+// them on the device (the next solve uploads from frame 0)
+int pose_graph_release_apply(lins_ctx* ctx, int n, const int32_t* slots) {
+  PgMem* m = mem_of(ctx);
+  for (int k = 0; k < n; ++k) {
+    Graph& g = m->g[slots[k]];
+    const int max_frames = g.max_frames, max_loops = g.max_loops;
+    g = Graph();
+    g.max_frames = max_frames, g.max_loops = max_loops;
+    m->up_frames[slots[k]] = m->up_loops[slots[k]] = 0;
+  }
+  return LINS_OK;
+}
 }  // namespace lins
 
 extern "C" {
+
+int lins_pose_graph_release_slot(lins_ctx* ctx, int slot) {
+  if (!ctx) return LINS_E_ARG;
+  PgMem* m = mem_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  const int32_t s = slot;
+  if (int rc = release_list_check(1, &s, m->n_slots)) return rc;
+  if (int rc = ctx_quiesce(ctx)) return rc;
+  return pose_graph_release_apply(ctx, 1, &s);
+}
 
 void lins_pose_graph_default_params(lins_pose_graph_params* p) {
   if (p) lins_pg::default_params(p);

@@ -10,9 +10,11 @@
 #include <cstring>
 #include <vector>
 
+#include "../../include/lins_lifecycle.h"
 #include "../../include/lins_map.h"
 #include "../../include/lins_streams_map.h"
 #include "host/keyframe_select.h"
+#include "lifecycle.h"
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
 #include "local_map.h"
@@ -111,9 +113,36 @@ int streams_map_correct(lins_ctx* ctx, int n, const int32_t* streams, const floa
     for (int k = 0; k < n; ++k) std::memcpy(&m->last6[6 * (size_t)streams[k]], six + 6 * k, 6 * sizeof(float));
   return LINS_OK;
 }
+
+// (lifecycle.h) the streams named as lins_streams_map_init leaves them: allocateMemory's map pose (LM:305-409),
+// timeLastProcessing = -1 (LM:356), no currentRobotPosPoint, no surrounding key poses; the context's modes stay
+int streams_map_release_apply(lins_ctx* ctx, int n, const int32_t* streams) {
+  StreamsMap* m = state_of(ctx);
+  hipStream_t st = ctx_stream(ctx);
+  for (int k = 0; k < n; ++k) {
+    const size_t s = (size_t)streams[k];
+    HIP_TRY(ctx, hipMemsetAsync(m->d_poses + s, 0, sizeof(MapPoseRec), st));
+    m->last_time[s] = -1.0;
+    std::fill(m->centre.begin() + 3 * s, m->centre.begin() + 3 * s + 3, 0.f);
+    m->stepped[s] = 0;
+    std::fill(m->last6.begin() + 6 * s, m->last6.begin() + 6 * s + 6, 0.f);
+    m->lists[s].clear();
+  }
+  if (n) HIP_TRY(ctx, hipStreamSynchronize(st));
+  return LINS_OK;
+}
 }  // namespace lins
 
 extern "C" {
+
+int lins_streams_map_release(lins_ctx* ctx, int n, const int32_t* streams) {
+  if (!ctx) return LINS_E_ARG;
+  StreamsMap* m = state_of(ctx);
+  if (!m->n) return LINS_E_STATE;
+  if (int rc = release_list_check(n, streams, m->n)) return rc;
+  if (int rc = ctx_quiesce(ctx)) return rc;
+  return streams_map_release_apply(ctx, n, streams);
+}
 
 int lins_map_associate_batch(lins_ctx* ctx, int n, const float* bef6, const float* aft6, const float* sum6, float* tobe6) {
   if (!ctx || n < 0 || (n && (!bef6 || !aft6 || !sum6 || !tobe6))) return LINS_E_ARG;

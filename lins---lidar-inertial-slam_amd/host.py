@@ -553,6 +553,35 @@ def loop_variance(fitness):
     return bool(ok), float(v.value)
 
 
+def arena_reclaim_plan(blocks, chunk):
+    """lins_host_arena_reclaim_plan (csrc/host/arena_reclaim.h): the compaction of an arena whose blocks are the tuples
+    (offset, points, keep) in ascending offset order, in passes of at most `chunk` points.  Returns the passes, each a
+    dict(direct=bool, segments=[(src, dst, n), ...]) with its segments in arena order."""
+    from ._ctypes_defs import ArenaBlockC, ArenaSegmentC
+
+    L = lib()
+    n = len(blocks)
+    arr = (ArenaBlockC * max(n, 1))(*[ArenaBlockC(int(o), int(c), int(bool(k)), 0) for o, c, k in blocks])
+    L.lins_host_arena_reclaim_plan.argtypes = [C.c_int, C.POINTER(ArenaBlockC), C.c_longlong, C.POINTER(ArenaSegmentC), C.c_longlong,
+                                               C.POINTER(C.c_int32)]
+    L.lins_host_arena_reclaim_plan.restype = C.c_longlong
+    np_ = C.c_int32(0)
+    cnt = L.lins_host_arena_reclaim_plan(n, arr, int(chunk), None, 0, C.byref(np_))
+    if cnt < 0:
+        raise RuntimeError(f"lins_host_arena_reclaim_plan: {cnt}")
+    segs = (ArenaSegmentC * max(cnt, 1))()
+    got = L.lins_host_arena_reclaim_plan(n, arr, int(chunk), segs, cnt, C.byref(np_))
+    assert got == cnt
+    passes = [dict(direct=None, segments=[]) for _ in range(np_.value)]
+    for i in range(cnt):
+        g = segs[i]
+        p = passes[g.pass_]
+        assert p["direct"] in (None, bool(g.direct))  # (one flag per pass)
+        p["direct"] = bool(g.direct)
+        p["segments"].append((int(g.src), int(g.dst), int(g.n)))
+    return passes
+
+
 def _buf(n):
     a = np.zeros((n, 4), dtype=np.float32)
     return a, a.ctypes.data_as(C.POINTER(Point))

@@ -48,6 +48,12 @@ EXPORTS = [
     "lins_keyposes_select_batch", "lins_keyposes_find_loop_batch", "lins_keyposes_surround_batch", "lins_keyposes_set_mode",
     "lins_keyposes_mode", "lins_last_keyposes_stats",
 ]
+# the calls of include/lins_lifecycle.h, a list of their own (tests/test_abi_archive.py counts the lins_archive_* calls of
+# include/lins_map.h in EXPORTS); lib() resolves every one of them, so a library without them does not load
+LIFECYCLE_EXPORTS = [
+    "lins_archive_usage", "lins_archive_release_slots", "lins_archive_set_reclaim_chunk", "lins_pose_graph_release_slot",
+    "lins_local_map_release_slot", "lins_streams_release", "lins_streams_map_release", "lins_streams_retire", "lins_last_reclaim_stats",
+]
 
 
 class LinsError(RuntimeError):
@@ -114,6 +120,10 @@ def lib():
                 if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                     continue  # (an older build under A/B timing)
                 getattr(L, name).restype = C.c_int
+        for name in LIFECYCLE_EXPORTS:
+            if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
+                continue  # (an older build under A/B timing)
+            getattr(L, name).restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -657,6 +667,63 @@ class IeskfContext:
         L = lib()
         L.lins_pose_graph_apply_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         self._check(L.lins_pose_graph_apply_batch(self._h, len(sl), sl.ctypes.data, st.ctypes.data))
+
+    # -- stream lifecycle (include/lins_lifecycle.h) ----------------------------------------------------
+    def _release_list(self, fn, ids):
+        a = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        self._check(fn(self._h, len(a), a.ctypes.data))
+
+    def archive_usage(self):
+        """(points in use, points of capacity) of the archive's arena"""
+        L, used, cap = lib(), C.c_longlong(0), C.c_longlong(0)
+        L.lins_archive_usage.argtypes = [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+        self._check(L.lins_archive_usage(self._h, C.byref(used), C.byref(cap)))
+        return int(used.value), int(cap.value)
+
+    def archive_release_slots(self, slots):
+        """drop every frame of `slots`, compact the arena on the device; returns the points freed"""
+        L, freed = lib(), C.c_longlong(0)
+        a = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        L.lins_archive_release_slots.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_longlong)]
+        self._check(L.lins_archive_release_slots(self._h, len(a), a.ctypes.data, C.byref(freed)))
+        return int(freed.value)
+
+    def archive_set_reclaim_chunk(self, chunk_points):
+        """test hook: points moved per compaction pass (0: the default); the results do not depend on it"""
+        L = lib()
+        L.lins_archive_set_reclaim_chunk.argtypes = [C.c_void_p, C.c_longlong]
+        self._check(L.lins_archive_set_reclaim_chunk(self._h, int(chunk_points)))
+
+    def reclaim_stats(self):
+        """dict(ms, points_moved, staged_passes, direct_passes) of the last compaction"""
+        L = lib()
+        ms, moved, st, di = C.c_float(0), C.c_uint64(0), C.c_int32(0), C.c_int32(0)
+        L.lins_last_reclaim_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        self._check(L.lins_last_reclaim_stats(self._h, C.byref(ms), C.byref(moved), C.byref(st), C.byref(di)))
+        return dict(ms=ms.value, points_moved=int(moved.value), staged_passes=int(st.value), direct_passes=int(di.value))
+
+    def pose_graph_release_slot(self, slot):
+        L = lib()
+        L.lins_pose_graph_release_slot.argtypes = [C.c_void_p, C.c_int]
+        self._check(L.lins_pose_graph_release_slot(self._h, int(slot)))
+
+    def local_map_release_slot(self, slot):
+        L = lib()
+        L.lins_local_map_release_slot.argtypes = [C.c_void_p, C.c_int]
+        self._check(L.lins_local_map_release_slot(self._h, int(slot)))
+
+    def streams_release(self, streams):
+        """the filter side of `streams` as lins_streams_init (+ lins_streams_machine_init) leave it"""
+        self._release_list(lib().lins_streams_release, streams)
+
+    def streams_map_release(self, streams):
+        """the mapping side of `streams` as lins_streams_map_init leaves it"""
+        self._release_list(lib().lins_streams_map_release, streams)
+
+    def streams_retire(self, streams):
+        """every initialised module's release for stream == slot, one call: the slots are what a fresh init leaves"""
+        self._release_list(lib().lins_streams_retire, streams)
 
     # -- the loop thread's step (include/lins_map.h lins_loop_step) ------------------------------------
     def loop_step(self, entries, params=None):
