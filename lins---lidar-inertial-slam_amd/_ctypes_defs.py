@@ -604,3 +604,80 @@ class ArenaBlockC(C.Structure):
 
 class ArenaSegmentC(C.Structure):
     _fields_ = [("src", C.c_longlong), ("dst", C.c_longlong), ("n", C.c_longlong), ("pass_", C.c_int32), ("direct", C.c_int32)]
+
+
+# ---- stream snapshots (include/lins_snapshot.h): the blob's header and records, the plan's records ----
+SNAPSHOT_MAGIC, SNAPSHOT_VERSION = 0x3150414E534E494C, 1
+SNAP_STREAM, SNAP_FILTER, SNAP_BOOT, SNAP_ODOM, SNAP_MAP_POSE, SNAP_RING, SNAP_ARCHIVE, SNAP_GRAPH = (1 << k for k in range(8))
+SNAP_SECTIONS, SNAP_FIRST_DEVICE_SEC, SNAP_FIRST_UNIT8_SEC = 14, 5, 9
+SNAP_SEC_NAMES = ("stream_rec", "surround", "ring_meta", "ar_meta", "pg_host", "scan_pts", "outl_pts", "ring_pts", "ar_pts", "filter_rows",
+                  "boot_pre", "odom", "map_pose", "pg_d")
+SNAP_BUFFERS, SNAP_FIRST_UNIT8_BUF = 13, 4
+
+
+class _FilterParamsC(C.Structure):  # lins_filter_params (host.FilterParams has the same layout)
+    _fields_ = [("acc_n", C.c_double), ("gyr_n", C.c_double), ("acc_w", C.c_double), ("gyr_w", C.c_double), ("init_pos_std", C.c_double * 3),
+                ("init_vel_std", C.c_double * 3), ("init_att_std", C.c_double * 3), ("init_acc_std", C.c_double * 3), ("init_gyr_std", C.c_double * 3)]
+
+
+class _BootParamsC(C.Structure):
+    _fields_ = [("filter", _FilterParamsC), ("init_ba", C.c_double * 3), ("init_bw", C.c_double * 3)]
+
+
+class SnapshotCountsC(C.Structure):
+    _fields_ = [("has_scan", C.c_int32), ("less_sharp", C.c_int32), ("less_flat", C.c_int32), ("outliers", C.c_int32), ("ring_frames", C.c_int32),
+                ("archive_frames", C.c_int32), ("ring_points", C.c_int64), ("archive_points", C.c_int64), ("graph_frames", C.c_int32),
+                ("graph_loops", C.c_int32), ("graph_up_frames", C.c_int32), ("surround", C.c_int32)]
+
+
+class SnapshotFactsC(C.Structure):
+    _fields_ = [("params", Params), ("boot", _BootParamsC), ("machine", C.c_int32), ("loop", C.c_int32), ("surround", C.c_int32),
+                ("ring_window", C.c_int32), ("map_interval", C.c_double), ("surround_radius", C.c_float), ("surround_pose_leaf", C.c_float)]
+
+
+class SnapshotInfoC(C.Structure):
+    _fields_ = [("magic", C.c_uint64), ("version", C.c_uint32), ("header_bytes", C.c_uint32), ("total_bytes", C.c_uint64), ("checksum", C.c_uint64),
+                ("modules", C.c_uint32), ("n_sections", C.c_uint32), ("counts", SnapshotCountsC), ("facts", SnapshotFactsC),
+                ("header_checksum", C.c_uint64)]
+
+    def as_dict(self):
+        c, f = self.counts, self.facts
+        return dict(version=int(self.version), total_bytes=int(self.total_bytes), modules=int(self.modules),
+                    counts={n: int(getattr(c, n)) for n, _ in SnapshotCountsC._fields_},
+                    facts=dict(num_iter=int(f.params.num_iter), machine=int(f.machine), loop=int(f.loop), surround=int(f.surround),
+                               ring_window=int(f.ring_window), map_interval=float(f.map_interval), surround_radius=float(f.surround_radius),
+                               surround_pose_leaf=float(f.surround_pose_leaf)))
+
+
+class SnapshotDirentC(C.Structure):
+    _fields_ = [("id", C.c_uint32), ("unit", C.c_uint32), ("offset", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class SnapshotStreamRecC(C.Structure):
+    _fields_ = [("outl_put", C.c_int32), ("filter_set", C.c_int32), ("status", C.c_int32), ("imu_seen", C.c_int32), ("filter_prm", _FilterParamsC),
+                ("imu_last", C.c_double * 6), ("map_last_time", C.c_double), ("centre", C.c_float * 3), ("stepped", C.c_int32),
+                ("last6", C.c_float * 6), ("reserved", C.c_int64)]
+
+
+class SnapshotFrameC(C.Structure):
+    _fields_ = [("n", C.c_int32 * 3), ("reserved", C.c_int32), ("pose", C.c_float * 6), ("t", C.c_float * 9), ("reserved2", C.c_float),
+                ("time", C.c_double)]
+
+
+class SnapshotLoopC(C.Structure):
+    _fields_ = [("Z", C.c_double * 12), ("var", C.c_double), ("latest", C.c_int32), ("closest", C.c_int32)]
+
+
+class SnapshotLimitsC(C.Structure):
+    _fields_ = [("modules", C.c_uint32), ("less_sharp_max", C.c_int32), ("less_flat_max", C.c_int32), ("outlier_max", C.c_int32),
+                ("ring_window", C.c_int32), ("ring_max_pts", C.c_int32), ("archive_frames", C.c_int32), ("graph_frames", C.c_int32),
+                ("graph_loops", C.c_int32), ("surround_max", C.c_int32), ("archive_points", C.c_int64)]
+
+
+class SnapshotPlaceC(C.Structure):
+    _fields_ = [("row", C.c_int64), ("scan_off", C.c_int64 * 2), ("outl_off", C.c_int64), ("graph_off", C.c_int64), ("ring_off", C.c_void_p),
+                ("ar_off", C.c_void_p), ("ring_n", C.c_void_p), ("ar_n", C.c_void_p)]
+
+
+class SnapshotSegmentC(C.Structure):
+    _fields_ = [("buffer", C.c_int32), ("unit", C.c_int32), ("buf_off", C.c_int64), ("stg_off", C.c_int64), ("units", C.c_int64)]

@@ -21,6 +21,7 @@
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
 #include "local_map.h"
+#include "snapshot.h"
 
 using namespace lins;
 using lins_hostmap::cloud_ok;
@@ -201,6 +202,70 @@ int archive_release_apply(lins_ctx* ctx, int n, const int32_t* slots, long long*
   m->used -= freed;
   if (released) *released = freed;
   return LINS_OK;
+}
+
+// ---- snapshot.h: every frame of the slot in id order.  A restore appends them at the arena's `used`, one after the
+// other, so ids survive; the key-pose mirror is brought up by the next lins_keyposes_* call (stale_from = 0).
+void archive_snapshot_context(lins_ctx* ctx, SnapContext& c) {
+  Archive* m = archive_of(ctx);
+  if (!m->n_slots) return;
+  c.modules |= LINS_SNAP_ARCHIVE;
+  c.base[LINS_SNAP_BUF_ARENA] = m->d_arena.get(), c.units[LINS_SNAP_BUF_ARENA] = m->max_points;
+}
+
+int archive_snapshot_describe(lins_ctx* ctx, int slot, SnapStream& s) {
+  Archive* m = archive_of(ctx);
+  const std::vector<ArFrame>& fr = m->frames[slot];
+  s.modules |= LINS_SNAP_ARCHIVE;
+  s.counts.archive_frames = (int32_t)fr.size(), s.counts.archive_points = 0;
+  lins_snapshot_frame* out = s.host_section<lins_snapshot_frame>(LINS_SNAP_SEC_AR_META, fr.size());
+  s.ar_off.resize(fr.size()), s.ar_n.resize(fr.size());
+  for (size_t i = 0; i < fr.size(); ++i) {
+    const ArFrame& f = fr[i];
+    std::memcpy(out[i].n, f.n, sizeof f.n);
+    const float pose[6] = {f.pose.x, f.pose.y, f.pose.z, f.pose.roll, f.pose.pitch, f.pose.yaw};
+    std::memcpy(out[i].pose, pose, sizeof pose);
+    std::memcpy(out[i].t, f.t, sizeof f.t);
+    out[i].time = f.time;
+    s.ar_off[i] = f.off, s.ar_n[i] = f.n[0] + f.n[1] + f.n[2];
+    s.counts.archive_points += s.ar_n[i];
+  }
+  return LINS_OK;
+}
+
+int archive_restore_check(lins_ctx* ctx, int slot, lins_snapshot_limits& lim) {
+  Archive* m = archive_of(ctx);
+  if (!m->frames[slot].empty()) return LINS_E_STATE;
+  lim.archive_frames = m->max_frames, lim.archive_points = m->max_points - m->used;
+  return LINS_OK;
+}
+
+void archive_restore_place(lins_ctx* ctx, int slot, const SnapView& v, SnapStream& s, long long* arena_at) {
+  const int cnt = v.info.counts.archive_frames;
+  s.ar_off.resize(cnt), s.ar_n.resize(cnt);
+  for (int i = 0; i < cnt; ++i) {
+    lins_snapshot_frame f;
+    std::memcpy(&f, v.sec(LINS_SNAP_SEC_AR_META) + (size_t)i * sizeof f, sizeof f);
+    s.ar_off[i] = *arena_at, s.ar_n[i] = f.n[0] + f.n[1] + f.n[2];
+    *arena_at += s.ar_n[i];
+  }
+}
+
+void archive_restore_apply(lins_ctx* ctx, int slot, const SnapView& v, const SnapStream& s) {
+  Archive* m = archive_of(ctx);
+  const int cnt = v.info.counts.archive_frames;
+  std::vector<ArFrame>& fr = m->frames[slot];
+  fr.assign((size_t)cnt, ArFrame{});
+  for (int i = 0; i < cnt; ++i) {
+    lins_snapshot_frame f;
+    std::memcpy(&f, v.sec(LINS_SNAP_SEC_AR_META) + (size_t)i * sizeof f, sizeof f);
+    fr[i].off = s.ar_off[i], fr[i].time = f.time;
+    std::memcpy(fr[i].n, f.n, sizeof f.n);
+    fr[i].pose = lins_key_pose{f.pose[0], f.pose[1], f.pose[2], f.pose[3], f.pose[4], f.pose[5]};
+    std::memcpy(fr[i].t, f.t, sizeof f.t);
+  }
+  m->used += v.info.counts.archive_points;
+  m->stale_from[slot] = 0;
 }
 }  // namespace lins
 

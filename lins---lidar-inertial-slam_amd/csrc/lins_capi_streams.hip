@@ -4,6 +4,7 @@
 // _stats, _peek; lins_streams_put_outliers).  The step is a sequence of named phases over one per-call record (StepPlan);
 // its update goes out through the batch path's launcher, run_family() in lins_capi.hip.
 #include "lins_ctx.h"
+#include "snapshot.h"
 
 using namespace lins;
 
@@ -44,6 +45,15 @@ int streams_map_clouds(lins_ctx* ctx, int stream, StreamMapClouds* v) {
   v->src[1] = t.d_arena + b + kSlotLessFlat, v->n[1] = t.last_counts[(size_t)stream * 2 + 1];
   v->src[2] = t.d_outl + (size_t)(stream * 2 + last) * LINS_OUTLIER_MAX, v->n[2] = t.outl_counts[(size_t)stream * 2 + last];
   return LINS_OK;
+}
+
+// (snapshot.h) the two clouds a later step reads of a resident scan — less flat, less sharp: the next update's targets
+// and the mapping node's input — where they lie in feature slot `slot` of `stream`, and what they hold at most
+void streams_scan_place(int stream, int slot, int64_t off[2], int32_t caps[2], int64_t* slot_points) {
+  const long long b = slot_base(stream, slot);
+  off[0] = b + kSlotLessFlat, off[1] = b + kSlotLessSharp;
+  caps[0] = LINS_CLOUD_MAX, caps[1] = (int32_t)(kSlotSize - kSlotLessSharp);
+  if (slot_points) *slot_points = kSlotSize;
 }
 }  // namespace lins
 

@@ -210,6 +210,15 @@ struct lins_ctx {
       bool have = false;                                      // the records have been derived at least once
     } s;
   } st;
+  // stream snapshots (include/lins_snapshot.h; lins_snapshot_capi.hip): the staging buffer of a pack / unpack — the
+  // device part of the call's blobs — with its pinned mirror, the table (bases | segments | tiles), the last call's figures
+  struct Snap {
+    DevBuf<char> d_stage, d_tab;  // (bytes)
+    PinBuf<char> h_stage, h_tab;
+    float pack_ms = 0.f, unpack_ms = 0.f;
+    uint64_t bytes = 0;
+    int segments = 0;
+  } snap;
   void* map_state = nullptr;  // scan-to-map row (lins_map_capi.hip), freed through map_state_free
   void (*map_state_free)(void*) = nullptr;
   DevBuf<long long> d_prof;  // optional per-workgroup phase profile (lins_debug_phase_profile)

@@ -13,6 +13,7 @@
 namespace lins_pg {
 struct Prob;  // pose_graph.h
 }
+struct lins_snapshot_segment;  // include/lins_snapshot.h
 
 namespace lins {
 
@@ -192,5 +193,11 @@ void launch_kp_find_loop(hipStream_t s, int n, const KpEntry* entries, const flo
 void launch_pose_graph_begin(hipStream_t s, int n_problems, const lins_pg::Prob* probs);
 // one Levenberg-Marquardt trial of every problem still active; still_running (may be null) += the problems that go on
 void launch_pose_graph_trial(hipStream_t s, int n_problems, const lins_pg::Prob* probs, const lins_pose_graph_params& prm, int* still_running);
+
+// ---- snapshot_kernels.hip: the device-resident pieces of a call's streams into / out of one staging buffer (include/
+// lins_snapshot.h).  tiles: the (segment, tile) entries of the segments of `unit` bytes (16 or 8); bases: the module
+// buffers by buffer id, on the device.  The segments have passed lins_snap::segments_ok.
+void launch_snap_pack(hipStream_t s, int unit, int n_tiles, const ::lins_snapshot_segment* segs, const int2* tiles, void* const* bases, char* stage);
+void launch_snap_unpack(hipStream_t s, int unit, int n_tiles, const ::lins_snapshot_segment* segs, const int2* tiles, void* const* bases, const char* stage);
 
 }  // namespace lins

@@ -18,6 +18,7 @@
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
 #include "local_map.h"
+#include "snapshot.h"
 
 using namespace lins;
 
@@ -127,6 +128,67 @@ int local_map_release_apply(lins_ctx* ctx, int n, const int32_t* slots) {
     std::fill(m->meta.begin() + (size_t)s * m->window, m->meta.begin() + (size_t)(s + 1) * m->window, KeyFrame{});
   }
   return LINS_OK;
+}
+
+// ---- snapshot.h: the ring in age order, oldest first.  A build reads the ring's frames by age alone ((head + i) %
+// window, i = 0 .. count - 1, above), so a ring restored with head = 0 gives the bits of the ring it was taken from.
+void local_map_snapshot_context(lins_ctx* ctx, SnapContext& c) {
+  LocalMap* m = local_of(ctx);
+  if (!m->n_slots) return;
+  c.modules |= LINS_SNAP_RING, c.facts.ring_window = m->window;
+  c.base[LINS_SNAP_BUF_RING] = m->d_frames.get(), c.units[LINS_SNAP_BUF_RING] = (int64_t)m->n_slots * m->window * m->max_pts;
+}
+
+int local_map_snapshot_describe(lins_ctx* ctx, int slot, SnapStream& s) {
+  LocalMap* m = local_of(ctx);
+  s.modules |= LINS_SNAP_RING;
+  const int cnt = m->count[slot];
+  s.counts.ring_frames = cnt, s.counts.ring_points = 0;
+  lins_snapshot_frame* fr = s.host_section<lins_snapshot_frame>(LINS_SNAP_SEC_RING_META, (size_t)cnt);
+  s.ring_off.resize(cnt), s.ring_n.resize(cnt);
+  for (int i = 0; i < cnt; ++i) {
+    const int idx = (m->head[slot] + i) % m->window;
+    const KeyFrame& kf = m->meta[(size_t)slot * m->window + idx];
+    std::memcpy(fr[i].n, kf.n, sizeof kf.n);
+    const float pose[6] = {kf.pose.x, kf.pose.y, kf.pose.z, kf.pose.roll, kf.pose.pitch, kf.pose.yaw};
+    std::memcpy(fr[i].pose, pose, sizeof pose);
+    std::memcpy(fr[i].t, kf.t, sizeof kf.t);
+    s.ring_off[i] = ((int64_t)slot * m->window + idx) * m->max_pts, s.ring_n[i] = kf.n[0] + kf.n[1] + kf.n[2];
+    s.counts.ring_points += s.ring_n[i];
+  }
+  return LINS_OK;
+}
+
+int local_map_restore_check(lins_ctx* ctx, int slot, lins_snapshot_limits& lim) {
+  LocalMap* m = local_of(ctx);
+  if (m->head[slot] || m->count[slot]) return LINS_E_STATE;
+  lim.ring_window = m->window, lim.ring_max_pts = m->max_pts;
+  return LINS_OK;
+}
+
+void local_map_restore_place(lins_ctx* ctx, int slot, const SnapView& v, SnapStream& s) {
+  LocalMap* m = local_of(ctx);
+  const int cnt = v.info.counts.ring_frames;
+  s.ring_off.resize(cnt), s.ring_n.resize(cnt);
+  for (int i = 0; i < cnt; ++i) {
+    lins_snapshot_frame f;
+    std::memcpy(&f, v.sec(LINS_SNAP_SEC_RING_META) + (size_t)i * sizeof f, sizeof f);
+    s.ring_off[i] = ((int64_t)slot * m->window + i) * m->max_pts, s.ring_n[i] = f.n[0] + f.n[1] + f.n[2];
+  }
+}
+
+void local_map_restore_apply(lins_ctx* ctx, int slot, const SnapView& v) {
+  LocalMap* m = local_of(ctx);
+  const int cnt = v.info.counts.ring_frames;
+  m->head[slot] = 0, m->count[slot] = cnt;
+  for (int i = 0; i < cnt; ++i) {
+    lins_snapshot_frame f;
+    std::memcpy(&f, v.sec(LINS_SNAP_SEC_RING_META) + (size_t)i * sizeof f, sizeof f);
+    KeyFrame& kf = m->meta[(size_t)slot * m->window + i];
+    std::memcpy(kf.n, f.n, sizeof kf.n);
+    kf.pose = lins_key_pose{f.pose[0], f.pose[1], f.pose[2], f.pose[3], f.pose[4], f.pose[5]};
+    std::memcpy(kf.t, f.t, sizeof kf.t);
+  }
 }
 }  // namespace lins
 

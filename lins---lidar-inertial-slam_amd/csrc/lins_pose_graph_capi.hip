@@ -19,6 +19,7 @@
 #include "lins_launch.h"
 #include "local_map.h"
 #include "pose_graph.h"
+#include "snapshot.h"
 
 using namespace lins;
 using lins_pg::Graph;
@@ -122,6 +123,75 @@ int pose_graph_release_apply(lins_ctx* ctx, int n, const int32_t* slots) {
     g = Graph();
     g.max_frames = max_frames, g.max_loops = max_loops;
     m->up_frames[slots[k]] = m->up_loops[slots[k]] = 0;
+  }
+  return LINS_OK;
+}
+
+// ---- snapshot.h.  The host's Graph travels whole (Z, T, held, the loops' measurements; its D mirrors Z in this
+// library).  Of what prob_of addresses, a solve reads before it writes (pose_graph.h solve_begin / solve_trial):
+//   Z, D     rows below up_frames — D holds the solved increments after a solve with loops, nowhere else
+//   loops    Z, var, latest, closest of the records below up_loops — the host's records, uploaded again (up_loops = 0)
+// and writes before it reads: I, Q, T (phase_poses from D), Dt, Tt, B, c, P, q, S, y, the loops' M, r, w, and the state
+// (uploaded).  So the D rows travel through the kernel, the Z rows are uploaded from the restored Graph, and the next
+// solve starts from the same bits.
+void pose_graph_snapshot_context(lins_ctx* ctx, SnapContext& c) {
+  PgMem* m = mem_of(ctx);
+  if (!m->n_slots) return;
+  c.modules |= LINS_SNAP_GRAPH;
+  c.base[LINS_SNAP_BUF_PG_D] = m->d_D.get(), c.units[LINS_SNAP_BUF_PG_D] = (int64_t)m->n_slots * m->F * 12;
+}
+
+int pose_graph_snapshot_describe(lins_ctx* ctx, int slot, SnapStream& s) {
+  PgMem* m = mem_of(ctx);
+  const Graph& g = m->g[slot];
+  const size_t N = (size_t)g.n_frames(), L = g.loops.size();
+  s.modules |= LINS_SNAP_GRAPH;
+  s.counts.graph_frames = (int32_t)N, s.counts.graph_loops = (int32_t)L, s.counts.graph_up_frames = m->up_frames[slot];
+  s.place.graph_off = (int64_t)slot * m->F * 12;
+  char* p = s.host_section<char>(LINS_SNAP_SEC_PG_HOST, 216 * N + sizeof(lins_snapshot_loop) * L);
+  std::memcpy(p, g.Z.data(), 96 * N), std::memcpy(p + 96 * N, g.T.data(), 96 * N), std::memcpy(p + 192 * N, g.held.data(), 24 * N);
+  for (size_t l = 0; l < L; ++l) {
+    lins_snapshot_loop R;
+    std::memset(&R, 0, sizeof R);
+    std::memcpy(R.Z, g.loops[l].Z, sizeof R.Z);
+    R.var = g.loops[l].var, R.latest = g.loops[l].latest, R.closest = g.loops[l].closest;
+    std::memcpy(p + 216 * N + l * sizeof R, &R, sizeof R);
+  }
+  return LINS_OK;
+}
+
+int pose_graph_restore_check(lins_ctx* ctx, int slot, lins_snapshot_limits& lim) {
+  PgMem* m = mem_of(ctx);
+  const Graph& g = m->g[slot];
+  if (g.n_frames() || !g.loops.empty() || m->up_frames[slot] || m->up_loops[slot]) return LINS_E_STATE;
+  lim.graph_frames = g.max_frames, lim.graph_loops = g.max_loops;
+  return LINS_OK;
+}
+
+void pose_graph_restore_place(lins_ctx* ctx, int slot, const SnapView& v, SnapStream& s) {
+  s.place.graph_off = (int64_t)slot * mem_of(ctx)->F * 12;
+}
+
+int pose_graph_restore_apply(lins_ctx* ctx, int slot, const SnapView& v) {
+  PgMem* m = mem_of(ctx);
+  Graph& g = m->g[slot];
+  const size_t N = (size_t)v.info.counts.graph_frames, L = (size_t)v.info.counts.graph_loops, up = (size_t)v.info.counts.graph_up_frames;
+  const char* p = v.sec(LINS_SNAP_SEC_PG_HOST);
+  g.Z.resize(12 * N), g.T.resize(12 * N), g.held.resize(6 * N);
+  std::memcpy(g.Z.data(), p, 96 * N), std::memcpy(g.T.data(), p + 96 * N, 96 * N), std::memcpy(g.held.data(), p + 192 * N, 24 * N);
+  g.D = g.Z;
+  g.loops.assign(L, LoopRec{});
+  for (size_t l = 0; l < L; ++l) {
+    lins_snapshot_loop R;
+    std::memcpy(&R, p + 216 * N + l * sizeof R, sizeof R);
+    std::memcpy(g.loops[l].Z, R.Z, sizeof R.Z);
+    g.loops[l].var = R.var, g.loops[l].latest = R.latest, g.loops[l].closest = R.closest;
+  }
+  m->up_frames[slot] = (int)up, m->up_loops[slot] = 0;
+  if (up) {
+    hipStream_t st = ctx_stream(ctx);
+    HIP_TRY(ctx, hipMemcpyAsync(m->d_Z + (size_t)slot * m->F * 12, g.Z.data(), 96 * up, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
   }
   return LINS_OK;
 }

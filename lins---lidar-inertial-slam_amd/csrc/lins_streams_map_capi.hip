@@ -18,8 +18,11 @@
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
 #include "local_map.h"
+#include "snapshot.h"
 
 using namespace lins;
+
+static_assert(sizeof(MapPoseRec) == 8 * lins_snap::kRowMapPose, "the map pose record as the snapshot's plan copies it");
 
 namespace {
 
@@ -130,6 +133,50 @@ int streams_map_release_apply(lins_ctx* ctx, int n, const int32_t* streams) {
   }
   if (n) HIP_TRY(ctx, hipStreamSynchronize(st));
   return LINS_OK;
+}
+
+// ---- snapshot.h: the same fields.  The map pose record travels as 14 units of 8 bytes through the kernel.
+void streams_map_snapshot_context(lins_ctx* ctx, SnapContext& c) {
+  StreamsMap* m = state_of(ctx);
+  if (!m->n) return;
+  c.modules |= LINS_SNAP_MAP_POSE;
+  c.facts.map_interval = m->interval, c.facts.loop = m->loop ? 1 : 0, c.facts.surround = m->surround ? 1 : 0;
+  if (m->surround) c.facts.surround_radius = m->radius, c.facts.surround_pose_leaf = m->pose_leaf;
+  c.base[LINS_SNAP_BUF_MAP_POSE] = m->d_poses.get(), c.units[LINS_SNAP_BUF_MAP_POSE] = (int64_t)lins_snap::kRowMapPose * m->n;
+}
+
+int streams_map_snapshot_describe(lins_ctx* ctx, int stream, SnapStream& s) {
+  StreamsMap* m = state_of(ctx);
+  const size_t k = (size_t)stream;
+  s.modules |= LINS_SNAP_MAP_POSE;
+  lins_snapshot_stream_rec* r = (lins_snapshot_stream_rec*)s.host[LINS_SNAP_SEC_STREAM_REC].data();
+  r->map_last_time = m->last_time[k], r->stepped = m->stepped[k] ? 1 : 0;
+  std::memcpy(r->centre, &m->centre[3 * k], sizeof r->centre);
+  std::memcpy(r->last6, &m->last6[6 * k], sizeof r->last6);
+  s.counts.surround = (int32_t)m->lists[k].size();
+  int32_t* ids = s.host_section<int32_t>(LINS_SNAP_SEC_SURROUND, m->lists[k].size());
+  std::copy(m->lists[k].begin(), m->lists[k].end(), ids);
+  return LINS_OK;
+}
+
+int streams_map_restore_check(lins_ctx* ctx, int stream, lins_snapshot_limits& lim) {
+  StreamsMap* m = state_of(ctx);
+  const size_t k = (size_t)stream;
+  if (m->last_time[k] != -1.0 || m->stepped[k] || !m->lists[k].empty()) return LINS_E_STATE;
+  lim.surround_max = 0x7fffffff;  // (the list names key frames: bounded by the archive's frames, which the format checks)
+  return LINS_OK;
+}
+
+void streams_map_restore_apply(lins_ctx* ctx, int stream, const SnapView& v) {
+  StreamsMap* m = state_of(ctx);
+  const size_t k = (size_t)stream;
+  lins_snapshot_stream_rec r;
+  std::memcpy(&r, v.sec(LINS_SNAP_SEC_STREAM_REC), sizeof r);
+  m->last_time[k] = r.map_last_time, m->stepped[k] = (char)r.stepped;
+  std::memcpy(&m->centre[3 * k], r.centre, sizeof r.centre);
+  std::memcpy(&m->last6[6 * k], r.last6, sizeof r.last6);
+  m->lists[k].assign((size_t)v.info.counts.surround, 0);
+  if (v.info.counts.surround) std::memcpy(m->lists[k].data(), v.sec(LINS_SNAP_SEC_SURROUND), 4 * (size_t)v.info.counts.surround);
 }
 }  // namespace lins
 

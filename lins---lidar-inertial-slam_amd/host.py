@@ -582,6 +582,21 @@ def arena_reclaim_plan(blocks, chunk):
     return passes
 
 
+def snapshot_info(blob):
+    """lins_host_snapshot_info (csrc/host/snapshot_format.h): the header of a stream snapshot's blob (bytes) as a dict
+    after the whole format check — no device needed; RuntimeError with the code when the blob is refused"""
+    from ._ctypes_defs import SnapshotInfoC
+
+    L = lib()
+    buf = np.frombuffer(blob, np.uint8)
+    out = SnapshotInfoC()
+    L.lins_host_snapshot_info.argtypes, L.lins_host_snapshot_info.restype = [C.c_void_p, C.c_uint64, C.POINTER(SnapshotInfoC)], C.c_int
+    rc = L.lins_host_snapshot_info(buf.ctypes.data if len(buf) else None, len(buf), C.byref(out))
+    if rc != 0:
+        raise RuntimeError(f"lins_host_snapshot_info: {rc}")
+    return out.as_dict()
+
+
 def _buf(n):
     a = np.zeros((n, 4), dtype=np.float32)
     return a, a.ctypes.data_as(C.POINTER(Point))

@@ -54,6 +54,11 @@ LIFECYCLE_EXPORTS = [
     "lins_archive_usage", "lins_archive_release_slots", "lins_archive_set_reclaim_chunk", "lins_pose_graph_release_slot",
     "lins_local_map_release_slot", "lins_streams_release", "lins_streams_map_release", "lins_streams_retire", "lins_last_reclaim_stats",
 ]
+# the calls of include/lins_snapshot.h, for the same reason a list of their own; lib() resolves every one of them
+SNAPSHOT_EXPORTS = [
+    "lins_streams_snapshot_size", "lins_streams_snapshot", "lins_streams_restore", "lins_streams_migrate", "lins_snapshot_info_get",
+    "lins_last_snapshot_stats",
+]
 
 
 class LinsError(RuntimeError):
@@ -120,7 +125,7 @@ def lib():
                 if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                     continue  # (an older build under A/B timing)
                 getattr(L, name).restype = C.c_int
-        for name in LIFECYCLE_EXPORTS:
+        for name in LIFECYCLE_EXPORTS + SNAPSHOT_EXPORTS:
             if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                 continue  # (an older build under A/B timing)
             getattr(L, name).restype = C.c_int
@@ -724,6 +729,59 @@ class IeskfContext:
     def streams_retire(self, streams):
         """every initialised module's release for stream == slot, one call: the slots are what a fresh init leaves"""
         self._release_list(lib().lins_streams_retire, streams)
+
+    # -- stream snapshots (include/lins_snapshot.h) ------------------------------------------------------
+    def streams_snapshot_size(self, streams):
+        """bytes the blob of each of `streams` takes now"""
+        L = lib()
+        a = np.ascontiguousarray(streams, dtype=np.int32).reshape(-1)
+        out = np.zeros(max(len(a), 1), np.uint64)
+        L.lins_streams_snapshot_size.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        self._check(L.lins_streams_snapshot_size(self._h, len(a), a.ctypes.data, out.ctypes.data))
+        return [int(x) for x in out[:len(a)]]
+
+    def streams_snapshot(self, streams, caps=None):
+        """the blobs of `streams` as a list of bytes objects: plain host memory, the same bytes for the same stream state
+        wherever it lives.  caps (a test hook): the capacities offered instead of the sizes asked for."""
+        L = lib()
+        a = np.ascontiguousarray(streams, dtype=np.int32).reshape(-1)
+        n = len(a)
+        sizes = self.streams_snapshot_size(a) if caps is None else [int(c) for c in caps]
+        bufs = [np.zeros(max(s, 1), np.uint8) for s in sizes]
+        ptrs = (C.c_void_p * max(n, 1))(*[b.ctypes.data for b in bufs])
+        cap = np.array(sizes + [0] * (1 - min(n, 1)), np.uint64)
+        got = np.zeros(max(n, 1), np.uint64)
+        L.lins_streams_snapshot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        rc = L.lins_streams_snapshot(self._h, n, a.ctypes.data, ptrs, cap.ctypes.data, got.ctypes.data)
+        self._snapshot_bytes = [int(x) for x in got[:n]]  # (set on LINS_E_CAPACITY too)
+        self._check(rc)
+        return [bufs[k][:int(got[k])].tobytes() for k in range(n)]
+
+    def streams_restore(self, streams, blobs):
+        """blobs[k] (bytes) continues as stream streams[k] of this context; the slot must be what init / release leave"""
+        L = lib()
+        a = np.ascontiguousarray(streams, dtype=np.int32).reshape(-1)
+        n = len(a)
+        assert n == len(blobs)
+        keep = [np.frombuffer(b, np.uint8) for b in blobs]
+        ptrs = (C.c_void_p * max(n, 1))(*[k.ctypes.data if len(k) else None for k in keep])
+        sizes = np.array([len(b) for b in blobs] + [0] * (1 - min(n, 1)), np.uint64)
+        L.lins_streams_restore.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._check(L.lins_streams_restore(self._h, n, a.ctypes.data, ptrs, sizes.ctypes.data))
+
+    def streams_migrate(self, stream, dst, dst_stream):
+        """snapshot of `stream`, restore into dst_stream of the context dst, retire of `stream` here — dst is asked first"""
+        L = lib()
+        L.lins_streams_migrate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+        self._check(L.lins_streams_migrate(self._h, int(stream), dst._h, int(dst_stream)))
+
+    def snapshot_stats(self):
+        """dict(pack_ms, unpack_ms, bytes, segments) of the last snapshot / restore of this context"""
+        L = lib()
+        p, u, b, s = C.c_float(0), C.c_float(0), C.c_uint64(0), C.c_int32(0)
+        L.lins_last_snapshot_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
+        self._check(L.lins_last_snapshot_stats(self._h, C.byref(p), C.byref(u), C.byref(b), C.byref(s)))
+        return dict(pack_ms=p.value, unpack_ms=u.value, bytes=int(b.value), segments=int(s.value))
 
     # -- the loop thread's step (include/lins_map.h lins_loop_step) ------------------------------------
     def loop_step(self, entries, params=None):
@@ -1399,3 +1457,17 @@ def host_solve_from_sums(params, pair, lin_state, sums):
     W = np.linalg.inv(r2 * np.eye(18) + P @ A)
     dx = -W @ P @ (g + A @ d) + d
     return dx, A, W
+
+
+def snapshot_info(blob):
+    """the header of a snapshot blob (bytes) as a dict, after the whole format check; LinsError when it is refused"""
+    from ._ctypes_defs import SnapshotInfoC
+
+    L = lib()
+    buf = np.frombuffer(blob, np.uint8)
+    out = SnapshotInfoC()
+    L.lins_snapshot_info_get.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(SnapshotInfoC)]
+    rc = L.lins_snapshot_info_get(buf.ctypes.data if len(buf) else None, len(buf), C.byref(out))
+    if rc != 0:
+        raise LinsError(f"liblins_ieskf error {rc}: {L.lins_strerror(rc).decode()}")
+    return out.as_dict()
