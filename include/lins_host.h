@@ -399,6 +399,39 @@ int lins_host_pose_graph_linearize(lins_host_pose_graph* g, const double* poses,
 void lins_host_pose_from6(const float p[6], double T[12]);
 void lins_host_pose_to6(const double T[12], float p[6]);
 
+/* ---- place recognition on the CPU (host/place.cpp) -----------------------------------------------------------------
+ * The DEFINITION the device calls of include/lins_place.h are held to, bit for bit (the scalar text is
+ * csrc/host/place_math.h in both libraries; DESIGN.md §5.3 "Place recognition").  A descriptor is LINS_PLACE_CELLS f32,
+ * D[ring][sector] row-major.  Clouds: finite, |coord| <= 1e6 (LINS_E_INPUT). */
+#define LINS_PLACE_RINGS 20
+#define LINS_PLACE_SECTORS 60
+#define LINS_PLACE_CELLS (LINS_PLACE_RINGS * LINS_PLACE_SECTORS)
+typedef struct lins_place_params {
+  float r_max;     /* 80 m: points at or beyond it are dropped */
+  float lift;      /* 2 m: added to every height */
+  int32_t up_axis; /* 1: index of the vertical coordinate of the stored clouds (0, 1 or 2) */
+  int32_t clouds;  /* LINS_SUBMAP_CORNER | _SURF | _OUTLIER: the clouds of a frame that are described */
+} lins_place_params;
+void lins_place_default_params(lins_place_params* p); /* exported by both libraries */
+/* the descriptor of one frame; the frame's pose is not read; the clouds outside prm->clouds are skipped */
+int lins_host_place_descriptor(const lins_keyframe* frame, const lins_place_params* prm, float out[LINS_PLACE_CELLS]);
+/* one pair under every shift: d[k], k < LINS_PLACE_SECTORS */
+int lins_host_place_distance(const float* query, const float* candidate, float d[LINS_PLACE_SECTORS]);
+/* the minimum of (d, id, shift) over the n candidates (descs: n x LINS_PLACE_CELLS) with fabs(times[c] - now) >
+ * min_gap_s and c != skip_id (-1: skip none); *id = -1 without one (then *shift = 0, *distance = 1).  candidates (may
+ * be NULL): how many were admissible.  LINS_E_INPUT for a NaN gap or a now that is not finite. */
+int lins_host_place_search(const float* query, const float* descs, const double* times, int n, int skip_id, double now, double min_gap_s,
+                           int32_t* id, int32_t* shift, float* distance, int32_t* candidates);
+/* T0 = M_c R_up(shift 2 pi / LINS_PLACE_SECTORS) M_q^-1 in f64, row-major: the start transform of an ICP whose source is
+ * the query frame assembled at its stored pose and whose target lies around the candidate's.  M: a key pose as the
+ * archive's assembly applies it, R = Ry(pitch) Rx(roll) Rz(yaw) with translation (x, y, z).  Shift k: what the query
+ * sees at azimuth phi the candidate sees at phi + k 2 pi / LINS_PLACE_SECTORS, azimuth growing from axis (up + 1) % 3
+ * towards axis (up + 2) % 3.  LINS_E_ARG for a bad axis or shift. */
+int lins_host_place_guess(const lins_key_pose* pose_q, const lins_key_pose* pose_c, int shift, int up_axis, double T0[16]);
+/* lins_host_loop_icp with T_0 given instead of the identity (LINS_E_INPUT when it is not finite) */
+int lins_host_loop_icp_from(const lins_point* source, int n_source, const lins_point* target, int n_target, const double T0[16],
+                            const lins_loop_icp_params* prm, int max_rounds, lins_loop_icp_result* out);
+
 #ifdef __cplusplus
 }
 #endif

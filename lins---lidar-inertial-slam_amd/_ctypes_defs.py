@@ -606,6 +606,45 @@ class ArenaSegmentC(C.Structure):
     _fields_ = [("src", C.c_longlong), ("dst", C.c_longlong), ("n", C.c_longlong), ("pass_", C.c_int32), ("direct", C.c_int32)]
 
 
+# ---- place recognition (include/lins_place.h, include/lins_host.h lins_host_place_*) ----
+PLACE_RINGS, PLACE_SECTORS, PLACE_CELLS = 20, 60, 1200
+
+
+class PlaceParamsC(C.Structure):
+    _fields_ = [("r_max", C.c_float), ("lift", C.c_float), ("up_axis", C.c_int32), ("clouds", C.c_int32)]
+
+
+class PlaceQueryC(C.Structure):
+    _fields_ = [("query_slot", C.c_int32), ("query_id", C.c_int32), ("target_slot", C.c_int32), ("reserved", C.c_int32),
+                ("now", C.c_double), ("min_gap_s", C.c_double)]
+
+
+class PlaceResultC(C.Structure):
+    _fields_ = [("id", C.c_int32), ("shift", C.c_int32), ("distance", C.c_float), ("candidates", C.c_int32), ("status", C.c_int32),
+                ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return dict(id=int(self.id), shift=int(self.shift), distance=np.float32(self.distance), candidates=int(self.candidates),
+                    status=int(self.status))
+
+
+def place_params(L, **kw):
+    """lins_place_default_params of library L with fields overridden by keyword (up_axis=2, ...)"""
+    p = PlaceParamsC()
+    L.lins_place_default_params.argtypes = [C.POINTER(PlaceParamsC)]
+    L.lins_place_default_params.restype = None
+    L.lins_place_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise AttributeError(k)
+        setattr(p, k, v)
+    return p
+
+
+def place_query(query_slot, query_id, target_slot, now, min_gap_s):
+    return PlaceQueryC(int(query_slot), int(query_id), int(target_slot), 0, float(now), float(min_gap_s))
+
+
 # ---- stream snapshots (include/lins_snapshot.h): the blob's header and records, the plan's records ----
 SNAPSHOT_MAGIC, SNAPSHOT_VERSION = 0x3150414E534E494C, 1
 SNAP_STREAM, SNAP_FILTER, SNAP_BOOT, SNAP_ODOM, SNAP_MAP_POSE, SNAP_RING, SNAP_ARCHIVE, SNAP_GRAPH = (1 << k for k in range(8))

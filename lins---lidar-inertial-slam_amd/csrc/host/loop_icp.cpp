@@ -62,12 +62,19 @@ void sums_in_order(const lins_point* G, int ns, const int32_t* idx, const float*
 
 bool params_ok(const lins_loop_icp_params* p) { return p && p->max_iterations >= 1 && p->min_correspondences >= 0 && std::isfinite(p->max_corr_dist); }
 
+// T0: null (the identity) or the start transform (lins_host_loop_icp_from)
 int run(const lins_point* S, int ns, const lins_point* G, int ng, const lins_loop_icp_params* prm, int max_rounds, lins_loop_icp_round* rounds,
-        int cap_rounds, lins_loop_icp_result* out) {
+        int cap_rounds, lins_loop_icp_result* out, const double* T0 = nullptr) {
   if (ns < 0 || ng < 0 || (ns && !S) || (ng && !G) || !params_ok(prm) || !out || max_rounds < 0 || (cap_rounds && !rounds)) return LINS_E_ARG;
   if (!cloud_ok(S, ns) || !cloud_ok(G, ng)) return LINS_E_INPUT;
   State s;
   state_init(s);
+  if (T0) {
+    for (int i = 0; i < 16; ++i)
+      if (!std::isfinite(T0[i])) return LINS_E_INPUT;
+    std::memcpy(s.T, T0, sizeof s.T);
+    make_move(s.T, s.M);
+  }
   std::vector<int32_t> idx(ns ? ns : 1);
   std::vector<float> sq(ns ? ns : 1), moved(ns ? 3 * (size_t)ns : 1);
   const float cap2 = prm->max_corr_dist * prm->max_corr_dist;
@@ -107,6 +114,13 @@ void lins_loop_icp_default_params(lins_loop_icp_params* p) {
 int lins_host_loop_icp(const lins_point* source, int n_source, const lins_point* target, int n_target, const lins_loop_icp_params* prm,
                        int max_rounds, lins_loop_icp_result* out) {
   const int rc = run(source, n_source, target, n_target, prm, max_rounds, nullptr, 0, out);
+  return rc < 0 ? rc : LINS_OK;
+}
+
+int lins_host_loop_icp_from(const lins_point* source, int n_source, const lins_point* target, int n_target, const double T0[16],
+                            const lins_loop_icp_params* prm, int max_rounds, lins_loop_icp_result* out) {
+  if (!T0) return LINS_E_ARG;
+  const int rc = run(source, n_source, target, n_target, prm, max_rounds, nullptr, 0, out, T0);
   return rc < 0 ? rc : LINS_OK;
 }
 

@@ -58,13 +58,29 @@ inline bool variance(double fitness, double* var) {
   return std::isfinite(v) && v > 0.0;
 }
 
-// getTransformation(x, y, z, roll, pitch, yaw) = Rz(yaw) Ry(pitch) Rx(roll) with translation (x, y, z), f32
-inline void get_transformation(float x, float y, float z, float roll, float pitch, float yaw, float* t) {
-  const float cr = std::cos(roll), sr = std::sin(roll), cp = std::cos(pitch), sp = std::sin(pitch), cy = std::cos(yaw), sy = std::sin(yaw);
+// getTransformation(x, y, z, roll, pitch, yaw) = Rz(yaw) Ry(pitch) Rx(roll) with translation (x, y, z); f32 in the
+// reference's text (pose_from below), f64 for the place-recognition guess (key_pose_matrix)
+template <class T>
+inline void get_transformation(T x, T y, T z, T roll, T pitch, T yaw, T* t) {
+  const T cr = std::cos(roll), sr = std::sin(roll), cp = std::cos(pitch), sp = std::sin(pitch), cy = std::cos(yaw), sy = std::sin(yaw);
   t[0] = cy * cp, t[1] = cy * sp * sr - sy * cr, t[2] = cy * sp * cr + sy * sr, t[3] = x;
   t[4] = sy * cp, t[5] = sy * sp * sr + cy * cr, t[6] = sy * sp * cr - cy * sr, t[7] = y;
   t[8] = -sp, t[9] = cp * sr, t[10] = cp * cr, t[11] = z;
-  t[12] = t[13] = t[14] = 0.f, t[15] = 1.f;
+  t[12] = t[13] = t[14] = T(0), t[15] = T(1);
+}
+// A stored key pose as a 4 x 4 in the axes it is stored in (the mapping node's camera axes), f64: pose_from's
+// pclPointToAffine3fCameraToLidar — getTransformation(z, x, y, yaw, roll, pitch), in lidar axes (x, y, z) = camera (z, x, y) —
+// taken back to camera axes.  It is Ry(pitch) Rx(roll) Rz(yaw) with translation (x, y, z): what the archive's assembly
+// applies to a frame's points (lm_transform_kernel).
+inline void key_pose_matrix(const lins_key_pose& p, double* M) {
+  double L[16];
+  get_transformation<double>(p.z, p.x, p.y, p.yaw, p.roll, p.pitch, L);
+  const int lidar_of[3] = {1, 2, 0};  // camera axis -> the lidar axis that is the same direction
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) M[4 * i + j] = L[4 * lidar_of[i] + lidar_of[j]];
+    M[4 * i + 3] = L[4 * lidar_of[i] + 3];
+  }
+  M[12] = M[13] = M[14] = 0.0, M[15] = 1.0;
 }
 // getTranslationAndEulerAngles
 inline void euler_of(const float* t, float& x, float& y, float& z, float& roll, float& pitch, float& yaw) {

@@ -1,0 +1,126 @@
+// place.cpp — place recognition on the CPU (include/lins_host.h lins_host_place_*): the DEFINITION the device calls of
+// include/lins_place.h are held to.  The scalar text is place_math.h, compiled into both libraries; here it runs in
+// the contract's own order, one pair and one shift at a time.  DESIGN.md §5.3 "Place recognition".
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../../include/lins_host.h"
+#include "loop_step.h"
+#include "place_math.h"
+#include "voxel_map.h"
+
+using namespace lins_place;
+using lins_hostmap::cloud_ok;
+
+namespace {
+
+// the normalised columns of D, column-major: U[s * kNR + r]; valid[s]
+void columns_of(const float* D, float* U, bool* valid) {
+  for (int s = 0; s < kNS; ++s) valid[s] = column(D, s, U + s * kNR) > 0.f;
+}
+
+void distances(const float* Uq, const bool* vq, const float* Uc, const bool* vc, float* d) {
+  for (int k = 0; k < kNS; ++k) {
+    float sim = 0.f;
+    int cnt = 0;
+    for (int j = 0; j < kNS; ++j) {
+      const int jc = (j + k) % kNS;
+      if (!vq[j] || !vc[jc]) continue;
+      sim += dot_columns(Uq + j * kNR, Uc + jc * kNR);
+      cnt += 1;
+    }
+    d[k] = distance_of(sim, cnt);
+  }
+}
+
+void mul4(const double* A, const double* B, double* C) {
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) C[4 * i + j] = A[4 * i] * B[j] + A[4 * i + 1] * B[4 + j] + A[4 * i + 2] * B[8 + j] + A[4 * i + 3] * B[12 + j];
+}
+
+}  // namespace
+
+extern "C" {
+
+void lins_place_default_params(lins_place_params* p) {
+  if (p) default_params(p);
+}
+
+int lins_host_place_descriptor(const lins_keyframe* f, const lins_place_params* prm, float* out) {
+  if (!f || !out || !params_ok(prm)) return LINS_E_ARG;
+  const lins_point* c[3] = {f->corner, f->surf, f->outlier};
+  const int n[3] = {f->n_corner, f->n_surf, f->n_outlier};
+  for (int q = 0; q < 3; ++q) {
+    if (n[q] < 0 || (n[q] && !c[q])) return LINS_E_ARG;
+    if (!cloud_ok(c[q], n[q])) return LINS_E_INPUT;
+  }
+  const int up = prm->up_axis, a = (up + 1) % 3, b = (up + 2) % 3;
+  const float inv_r = inv_r_of(prm->r_max);
+  for (int i = 0; i < kCells; ++i) out[i] = 0.f;
+  for (int q = 0; q < 3; ++q) {
+    if (!(prm->clouds & (1 << q))) continue;
+    for (int i = 0; i < n[q]; ++i) {
+      const float p[3] = {c[q][i].x, c[q][i].y, c[q][i].z};
+      float h;
+      const int cell = cell_of(p[up], p[a], p[b], prm->r_max, prm->lift, inv_r, &h);
+      if (cell >= 0 && h > out[cell]) out[cell] = h;
+    }
+  }
+  return LINS_OK;
+}
+
+int lins_host_place_distance(const float* query, const float* candidate, float* d) {
+  if (!query || !candidate || !d) return LINS_E_ARG;
+  std::vector<float> Uq(kCells), Uc(kCells);
+  bool vq[kNS], vc[kNS];
+  columns_of(query, Uq.data(), vq), columns_of(candidate, Uc.data(), vc);
+  distances(Uq.data(), vq, Uc.data(), vc, d);
+  return LINS_OK;
+}
+
+int lins_host_place_search(const float* query, const float* descs, const double* times, int n, int skip_id, double now, double min_gap_s,
+                           int32_t* id, int32_t* shift, float* distance, int32_t* candidates) {
+  if (!query || n < 0 || n > kMaxId || (n && (!descs || !times)) || !id || !shift || !distance) return LINS_E_ARG;
+  if (!std::isfinite(now) || std::isnan(min_gap_s)) return LINS_E_INPUT;
+  std::vector<float> Uq(kCells), Uc(kCells);
+  bool vq[kNS], vc[kNS];
+  float d[kNS];
+  columns_of(query, Uq.data(), vq);
+  unsigned long long best = kNoKey;
+  int cnt = 0;
+  for (int c = 0; c < n; ++c) {
+    if (c == skip_id || !time_admits(times[c], now, min_gap_s)) continue;
+    ++cnt;
+    columns_of(descs + (size_t)c * kCells, Uc.data(), vc);
+    distances(Uq.data(), vq, Uc.data(), vc, d);
+    for (int k = 0; k < kNS; ++k) {
+      const unsigned long long key = pack_key(d[k], c, k);
+      if (key < best) best = key;
+    }
+  }
+  *id = -1, *shift = 0, *distance = 1.f;
+  if (best != kNoKey) unpack_key(best, distance, id, shift);
+  if (candidates) *candidates = cnt;
+  return LINS_OK;
+}
+
+int lins_host_place_guess(const lins_key_pose* pose_q, const lins_key_pose* pose_c, int shift, int up_axis, double* T0) {
+  if (!pose_q || !pose_c || !T0 || shift < 0 || shift >= kNS || up_axis < 0 || up_axis > 2) return LINS_E_ARG;
+  double Mq[16], Mc[16], Mi[16], R[16], A[16];
+  lins_loop::key_pose_matrix(*pose_q, Mq), lins_loop::key_pose_matrix(*pose_c, Mc);  // (loop_step.h: the conversion behind pose_from)
+  // M_q^-1 = (R^T, -R^T t)
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) Mi[4 * i + j] = Mq[4 * j + i];
+    Mi[4 * i + 3] = -(Mq[i] * Mq[3] + Mq[4 + i] * Mq[7] + Mq[8 + i] * Mq[11]);
+  }
+  Mi[12] = Mi[13] = Mi[14] = 0.0, Mi[15] = 1.0;
+  const double th = shift * (6.283185307179586476925 / kNS), c = std::cos(th), s = std::sin(th);
+  const int a = (up_axis + 1) % 3, b = (up_axis + 2) % 3;
+  for (int i = 0; i < 16; ++i) R[i] = (i % 5 == 0) ? 1.0 : 0.0;
+  R[4 * a + a] = c, R[4 * a + b] = -s, R[4 * b + a] = s, R[4 * b + b] = c;
+  mul4(Mc, R, A), mul4(A, Mi, T0);
+  return LINS_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,89 @@
+// place_math.h — place recognition over the key-frame archive (Scan Context, Kim & Kim, IROS 2018), the ONE scalar text
+// of both libraries (host/place.cpp: the definition; place_kernels.hip: held to its bits).  DESIGN.md §5.3 "Place
+// recognition" states the contract and its departures from the paper.  Everything is f32 with a fixed operation
+// sequence; the files that include this are compiled with -ffp-contract=off, every fused multiply-add is an fmaf here.
+//   cell        h = p[up] + lift, rho = sqrtf(p[a] * p[a] + p[b] * p[b]) (a = (up + 1) % 3, b = (up + 2) % 3); the point
+//               counts iff rho < r_max and h >= 2^-10; ring min(NR - 1, (int)(rho * inv_r)), sector
+//               min(NS - 1, (int)((lins_atan2f(p[b], p[a]) + pi) * inv_s)); D[ring][sector] = the maximum h, 0 when empty
+//   columns     n2[s] = the fmaf chain over the rings ascending of D * D from 0, norm = sqrtf(n2), valid iff norm > 0,
+//               U = D / norm (an invalid column: U = 0 — a term of exactly +0 wherever it is added)
+//   distance    for j ascending, jc = (j + k) % NS, both columns valid: dot = the fmaf chain over the rings ascending of
+//               Uq[r][j] * Uc[r][jc] from 0; sim += dot, cnt += 1; d(k) = cnt ? max(0, 1 - sim / (float)cnt) : 1
+//   search      the minimum of (d, id, k), lexicographic: as the packed key (bits(d) << 32) | (id << 6) | k — d >= 0, so
+//               its bits order as the distances do
+#pragma once
+#include <stdint.h>
+
+#include "../../../include/lins_host.h"
+#include "../lins_math.h"
+
+namespace lins_place {
+
+constexpr int kNR = 20, kNS = 60, kCells = kNR * kNS;
+constexpr float kPiF = 3.14159265f;
+constexpr float kInvS = (float)(kNS / 6.283185307179586476925);  // sectors per radian
+constexpr float kFloor = 0x1p-10f;                                // the smallest height that counts
+constexpr int kMaxId = 1 << 26;                                   // ids a packed key holds
+constexpr unsigned long long kNoKey = ~0ull;
+
+LINS_HD float inv_r_of(float r_max) { return (float)kNR / r_max; }
+
+// lins_place_default_params and the parameter check of both libraries (host side)
+inline void default_params(lins_place_params* p) {
+  p->r_max = 80.f, p->lift = 2.f, p->up_axis = 1;
+  p->clouds = LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF | LINS_SUBMAP_OUTLIER;
+}
+inline bool params_ok(const lins_place_params* p) {
+  const int all = LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF | LINS_SUBMAP_OUTLIER;
+  return p && p->r_max > 0.f && fabsf(p->r_max) <= __FLT_MAX__ && fabsf(inv_r_of(p->r_max)) <= __FLT_MAX__ && fabsf(p->lift) <= __FLT_MAX__ &&
+         p->up_axis >= 0 && p->up_axis <= 2 && p->clouds > 0 && !(p->clouds & ~all);
+}
+
+// the cell of a point, -1: the point does not count; *h: its height
+LINS_HD int cell_of(float pu, float pa, float pb, float r_max, float lift, float inv_r, float* h) {
+  *h = pu + lift;
+  const float rho = sqrtf(pa * pa + pb * pb);
+  if (!(rho < r_max) || !(*h >= kFloor)) return -1;
+  int r = (int)(rho * inv_r);
+  r = r < kNR - 1 ? r : kNR - 1;
+  int s = (int)((lins::lins_atan2f(pb, pa) + kPiF) * kInvS);
+  s = s < kNS - 1 ? s : kNS - 1;
+  return r * kNS + s;
+}
+
+// column s of D (row-major [ring][sector]) -> its norm; u[r] = the normalised column (zeros when the norm is 0)
+LINS_HD float column(const float* D, int s, float* u) {
+  float n2 = 0.f;
+  for (int r = 0; r < kNR; ++r) n2 = fmaf(D[r * kNS + s], D[r * kNS + s], n2);
+  const float norm = sqrtf(n2);
+  for (int r = 0; r < kNR; ++r) u[r] = norm > 0.f ? D[r * kNS + s] / norm : 0.f;
+  return norm;
+}
+
+LINS_HD float dot_columns(const float* uq, const float* uc) {
+  float d = 0.f;
+  for (int r = 0; r < kNR; ++r) d = fmaf(uq[r], uc[r], d);
+  return d;
+}
+
+LINS_HD float distance_of(float sim, int cnt) {
+  if (!cnt) return 1.f;
+  const float d = 1.f - sim / (float)cnt;
+  return d > 0.f ? d : 0.f;
+}
+
+LINS_HD unsigned long long pack_key(float d, int id, int k) {
+  unsigned u;
+  __builtin_memcpy(&u, &d, 4);
+  return ((unsigned long long)u << 32) | ((unsigned long long)(unsigned)id << 6) | (unsigned long long)(unsigned)k;
+}
+LINS_HD void unpack_key(unsigned long long key, float* d, int* id, int* k) {
+  const unsigned u = (unsigned)(key >> 32);
+  __builtin_memcpy(d, &u, 4);
+  *id = (int)((key & 0xffffffffull) >> 6), *k = (int)(key & 63ull);
+}
+
+// find_loop's gate (keyframe_select.h): at equality the candidate is not admissible; gap < 0 admits every time
+LINS_HD bool time_admits(double time_c, double now, double gap) { return fabs(time_c - now) > gap; }
+
+}  // namespace lins_place

@@ -21,6 +21,7 @@
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
 #include "local_map.h"
+#include "place.h"
 #include "snapshot.h"
 
 using namespace lins;
@@ -68,6 +69,8 @@ struct Archive {
   float rc_ms = 0.f;
   uint64_t rc_moved = 0;
   int rc_staged = 0, rc_direct = 0;
+  // place recognition's descriptors (place.h, lins_place_*): a second derived mirror, current below place.described[s]
+  PlaceStore place;
 };
 
 void archive_free(void* p) { delete (Archive*)p; }
@@ -88,6 +91,13 @@ size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
 
 // the mirror of the slot's key poses is out of date from frame `id` on (brought up by the next lins_keyposes_* call)
 void stale_at(Archive* m, int slot, int id) { m->stale_from[slot] = std::min(m->stale_from[slot], id); }
+
+// the slot's frames are other frames from now on: both mirrors start over (a descriptor depends on a frame's points only,
+// so a changed pose — stale_at — or a moved block leaves it)
+void mirrors_drop(Archive* m, int slot) {
+  m->stale_from[slot] = 0;
+  if (m->place.on) m->place.described[slot] = 0;
+}
 
 std::vector<lins_key_pose> poses_of(const std::vector<ArFrame>& fr) {
   std::vector<lins_key_pose> p(fr.size());
@@ -113,6 +123,13 @@ int archive_store(lins_ctx* ctx, ArchiveStore* v) {
 }
 
 int archive_slots(lins_ctx* ctx) { return archive_of(ctx)->n_slots; }
+
+int archive_place(lins_ctx* ctx, ArchivePlace* v) {
+  Archive* m = archive_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  v->store = &m->place, v->d_arena = m->d_arena, v->n_slots = m->n_slots, v->max_frames = m->max_frames, v->frames = &m->frames;
+  return LINS_OK;
+}
 
 // The frames of the slots named go, the arena closes up behind them (host/arena_reclaim.h: the plan; archive_kernels.hip
 // ar_reclaim_*: its passes).  One table upload in front, every pass queued back to back, one synchronisation behind;
@@ -198,7 +215,7 @@ int archive_release_apply(lins_ctx* ctx, int n, const int32_t* slots, long long*
   const std::vector<long long> to = lins_reclaim::new_offsets((int)blocks.size(), blocks.data());
   for (size_t i = 0; i < refs.size(); ++i)
     if (blocks[i].keep) m->frames[refs[i].slot][refs[i].id].off = to[i];
-  for (int k = 0; k < n; ++k) m->frames[slots[k]].clear(), m->stale_from[slots[k]] = 0;
+  for (int k = 0; k < n; ++k) m->frames[slots[k]].clear(), mirrors_drop(m, slots[k]);
   m->used -= freed;
   if (released) *released = freed;
   return LINS_OK;
@@ -265,7 +282,7 @@ void archive_restore_apply(lins_ctx* ctx, int slot, const SnapView& v, const Sna
     std::memcpy(fr[i].t, f.t, sizeof f.t);
   }
   m->used += v.info.counts.archive_points;
-  m->stale_from[slot] = 0;
+  mirrors_drop(m, slot);
 }
 }  // namespace lins
 
@@ -279,6 +296,7 @@ int lins_archive_init(lins_ctx* ctx, int n_slots, int max_frames_per_slot, long 
   m->d_arena.reset(), m->d_kp_pose.reset(), m->d_kp_time.reset();
   m->n_slots = 0, m->built = false, m->used = 0;
   m->frames.clear();
+  m->place.on = false, m->place.described.clear(), m->place.d_D.reset(), m->place.d_rec.reset();  // (sized by lins_place_init)
   BUF_TRY(ctx, m->d_arena.grow((size_t)max_points_total));
   BUF_TRY(ctx, m->d_kp_pose.grow((size_t)n_slots * max_frames_per_slot));
   BUF_TRY(ctx, m->d_kp_time.grow((size_t)n_slots * max_frames_per_slot));

@@ -33,6 +33,9 @@ struct ArMove;
 struct KpStale;
 struct KpEntry;
 struct KpOut;
+struct PlStale;    // place.h
+struct PlParams;
+struct PlEntry;
 
 // ---- ieskf_kernels.hip: the any-size update kernel (global-memory grid or exhaustive search), re-projection, copy probe
 void launch_persistent(hipStream_t stream, int n, const DevParams& prm, const ScanDesc* descs, const float4* arena, const double* state_in, const double* cov_in, double* state_out, double* cov_out,
@@ -187,6 +190,14 @@ void launch_kp_select(hipStream_t s, int n, const KpEntry* entries, const float4
 void launch_kp_surround(hipStream_t s, int n, const KpEntry* entries, const float4* poses, const int* list_in, int* list_out, int* scratch, KpOut* out);
 // the loop candidate: closest[k] = the hit of smallest (d, id) with fabs(time - now) > gap, or -1
 void launch_kp_find_loop(hipStream_t s, int n, const KpEntry* entries, const float4* poses, const double* times, int* closest);
+
+// ---- place_kernels.hip: place recognition over the archive's frames (place.h, host/place_math.h)
+// the descriptors of the stale frames, one workgroup each: D to D + dst * 1200, the normalised columns to recs + dst * kPlRecWords
+void launch_place_build(hipStream_t s, int n, const PlStale* stale, const float4* arena, const PlParams& prm, float* D, float* recs);
+// one workgroup per (entry, first candidate) of `chunks`, `chunk` candidates each: its best key to chunk_best; then one
+// workgroup per entry: the minimum of its chunks' bests to out.  row (may be null): every candidate's best key, at the entry's `row`
+void launch_place_search(hipStream_t s, int n_entries, int n_chunks, const PlEntry* entries, const int2* chunks, int chunk, const float* recs,
+                         unsigned long long* chunk_best, unsigned long long* row, unsigned long long* out);
 
 // ---- pose_graph_kernels.hip: the pose graph's solve, one workgroup per problem (pose_graph.h) ----
 // the poses and the cost of every problem as it stands (the first launch of a solve)

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/lins_map.h"
+#include "../../include/lins_place.h"
 #include "keyframe_archive.h"
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
@@ -214,7 +215,8 @@ void lins_loop_icp_default_params(lins_loop_icp_params* p) {
   if (p) lins_licp::default_params(p);
 }
 
-int lins_loop_icp_batch(lins_ctx* ctx, int n, const lins_loop_icp_problem* in, const lins_loop_icp_params* prm, lins_loop_icp_result* out) {
+// T0: null (every problem starts from the identity) or n x 16 start transforms, checked by the caller
+static int icp_batch(lins_ctx* ctx, int n, const lins_loop_icp_problem* in, const double* T0, const lins_loop_icp_params* prm, lins_loop_icp_result* out) {
   if (!ctx || n < 0 || (n && (!in || !out)) || !params_ok(prm)) return LINS_E_ARG;
   if (n == 0) return LINS_OK;
   HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
@@ -224,7 +226,10 @@ int lins_loop_icp_batch(lins_ctx* ctx, int n, const lins_loop_icp_problem* in, c
   if (rc) return rc;
   hipStream_t st = ctx_stream(ctx);
   std::vector<State> states(n);
-  for (int k = 0; k < n; ++k) lins_licp::state_init(states[k]);
+  for (int k = 0; k < n; ++k) {
+    lins_licp::state_init(states[k]);
+    if (T0) std::memcpy(states[k].T, T0 + 16 * (size_t)k, sizeof states[k].T), lins_licp::make_move(states[k].T, states[k].M);
+  }
   const float cap2 = prm->max_corr_dist * prm->max_corr_dist;
   const int max_rounds = m->max_rounds ? std::min(m->max_rounds, prm->max_iterations) : prm->max_iterations;
   hipEvent_t e0, e1;
@@ -270,6 +275,18 @@ int lins_loop_icp_batch(lins_ctx* ctx, int n, const lins_loop_icp_problem* in, c
     m->last_far += s.far;
   }
   return LINS_OK;
+}
+
+int lins_loop_icp_batch(lins_ctx* ctx, int n, const lins_loop_icp_problem* in, const lins_loop_icp_params* prm, lins_loop_icp_result* out) {
+  return icp_batch(ctx, n, in, nullptr, prm, out);
+}
+
+int lins_loop_icp_batch_from(lins_ctx* ctx, int n, const lins_loop_icp_problem* in, const double* T0, const lins_loop_icp_params* prm,
+                             lins_loop_icp_result* out) {
+  if (n > 0 && !T0) return LINS_E_ARG;
+  for (size_t i = 0; n > 0 && i < 16 * (size_t)n; ++i)
+    if (!std::isfinite(T0[i])) return LINS_E_INPUT;
+  return icp_batch(ctx, n, in, n > 0 ? T0 : nullptr, prm, out);
 }
 
 int lins_loop_icp_correspondences(lins_ctx* ctx, const lins_loop_icp_problem* in, const double T[16], float cap, int32_t* idx, float* sqdist) {

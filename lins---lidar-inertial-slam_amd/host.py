@@ -453,6 +453,89 @@ def loop_icp(source, target, params=None, max_rounds=0):
     return out.as_dict()
 
 
+def loop_icp_from(source, target, T0, params=None, max_rounds=0):
+    """lins_host_loop_icp_from: loop_icp started from T0 (4 x 4) -> result dict, or the C return code of a refusal"""
+    from ._ctypes_defs import LoopIcpParamsC, LoopIcpResultC
+
+    L = lib()
+    s, t, ps, pt = _loop_clouds(source, target)
+    prm = params if params is not None else loop_icp_params()
+    out = LoopIcpResultC()
+    T = np.ascontiguousarray(T0, np.float64).reshape(16)
+    L.lins_host_loop_icp_from.argtypes = [C.POINTER(Point), C.c_int, C.POINTER(Point), C.c_int, C.c_void_p, C.POINTER(LoopIcpParamsC), C.c_int,
+                                          C.POINTER(LoopIcpResultC)]
+    L.lins_host_loop_icp_from.restype = C.c_int
+    rc = L.lins_host_loop_icp_from(ps, len(s), pt, len(t), T.ctypes.data, C.byref(prm), int(max_rounds), C.byref(out))
+    return out.as_dict() if rc == 0 else rc
+
+
+# ---- place recognition (include/lins_host.h lins_host_place_*: the definition the device is held to) ----
+def place_params(**kw):
+    from ._ctypes_defs import place_params as f
+
+    return f(lib(), **kw)
+
+
+def place_descriptor(corner, surf, outlier, params=None):
+    """lins_host_place_descriptor -> D[ring][sector], (20, 60) f32"""
+    from ._ctypes_defs import KeyframeC, PlaceParamsC, keyframe_c
+
+    L = lib()
+    f, _keep = keyframe_c(corner, surf, outlier, (0, 0, 0, 0, 0, 0))
+    prm = params if params is not None else place_params()
+    out = np.zeros((20, 60), np.float32)
+    L.lins_host_place_descriptor.argtypes = [C.POINTER(KeyframeC), C.POINTER(PlaceParamsC), C.c_void_p]
+    L.lins_host_place_descriptor.restype = C.c_int
+    rc = L.lins_host_place_descriptor(C.byref(f), C.byref(prm), out.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"lins_host_place_descriptor: {rc}")
+    return out
+
+
+def place_distance(query, candidate):
+    """lins_host_place_distance: one pair of descriptors -> d[shift], 60 f32"""
+    L = lib()
+    q, c = np.ascontiguousarray(query, np.float32).reshape(1200), np.ascontiguousarray(candidate, np.float32).reshape(1200)
+    d = np.zeros(60, np.float32)
+    L.lins_host_place_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lins_host_place_distance.restype = C.c_int
+    rc = L.lins_host_place_distance(q.ctypes.data, c.ctypes.data, d.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"lins_host_place_distance: {rc}")
+    return d
+
+
+def place_search(query, descs, times, now, min_gap_s, skip_id=-1):
+    """lins_host_place_search -> dict(id, shift, distance (np.float32), candidates), or the C return code of a refusal"""
+    L = lib()
+    q = np.ascontiguousarray(query, np.float32).reshape(1200)
+    n = len(descs)
+    D = np.ascontiguousarray(descs, np.float32).reshape(max(n, 1) if n else 0, 1200) if n else np.zeros((1, 1200), np.float32)
+    t = np.ascontiguousarray(times, np.float64) if n else np.zeros(1)
+    i, k, d, c = C.c_int32(-2), C.c_int32(-2), C.c_float(0), C.c_int32(0)
+    L.lins_host_place_search.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_int32)]
+    L.lins_host_place_search.restype = C.c_int
+    rc = L.lins_host_place_search(q.ctypes.data, D.ctypes.data, t.ctypes.data, n, int(skip_id), float(now), float(min_gap_s), C.byref(i), C.byref(k),
+                                  C.byref(d), C.byref(c))
+    if rc != 0:
+        return rc
+    return dict(id=int(i.value), shift=int(k.value), distance=np.float32(d.value), candidates=int(c.value))
+
+
+def place_guess(pose_q, pose_c, shift, up_axis=1):
+    """lins_host_place_guess -> T0 (4 x 4 f64), or the C return code of a refusal"""
+    from ._ctypes_defs import KeyPoseC, key_pose
+
+    L = lib()
+    T = np.zeros(16, np.float64)
+    pq, pc = key_pose(pose_q), key_pose(pose_c)
+    L.lins_host_place_guess.argtypes = [C.POINTER(KeyPoseC), C.POINTER(KeyPoseC), C.c_int, C.c_int, C.c_void_p]
+    L.lins_host_place_guess.restype = C.c_int
+    rc = L.lins_host_place_guess(C.byref(pq), C.byref(pc), int(shift), int(up_axis), T.ctypes.data)
+    return T.reshape(4, 4) if rc == 0 else rc
+
+
 def loop_icp_trace(source, target, params=None):
     """lins_host_loop_icp_trace -> (rounds: list of dicts (T_in, n_corr, mse, delta, T_out, stop, reason), result dict)"""
     from ._ctypes_defs import LoopIcpParamsC, LoopIcpResultC, LoopIcpRoundC

@@ -59,6 +59,11 @@ SNAPSHOT_EXPORTS = [
     "lins_streams_snapshot_size", "lins_streams_snapshot", "lins_streams_restore", "lins_streams_migrate", "lins_snapshot_info_get",
     "lins_last_snapshot_stats",
 ]
+# the calls of include/lins_place.h, for the same reason a list of their own; lib() resolves every one of them
+PLACE_EXPORTS = [
+    "lins_place_default_params", "lins_place_init", "lins_place_sync", "lins_place_search_batch", "lins_place_descriptor",
+    "lins_place_distances", "lins_place_set_chunk", "lins_last_place_stats", "lins_loop_icp_batch_from",
+]
 
 
 class LinsError(RuntimeError):
@@ -125,10 +130,10 @@ def lib():
                 if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                     continue  # (an older build under A/B timing)
                 getattr(L, name).restype = C.c_int
-        for name in LIFECYCLE_EXPORTS + SNAPSHOT_EXPORTS:
+        for name in LIFECYCLE_EXPORTS + SNAPSHOT_EXPORTS + PLACE_EXPORTS:
             if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                 continue  # (an older build under A/B timing)
-            getattr(L, name).restype = C.c_int
+            getattr(L, name).restype = None if name == "lins_place_default_params" else C.c_int
         _LIB = L
     return _LIB
 
@@ -578,6 +583,94 @@ class IeskfContext:
         L.lins_loop_icp_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(LoopIcpProblemC), C.POINTER(LoopIcpParamsC), C.POINTER(LoopIcpResultC)]
         self._check(L.lins_loop_icp_batch(self._h, n, arr, C.byref(prm), out))
         return [out[k].as_dict() for k in range(n)]
+
+    def loop_icp_from(self, problems, T0, params=None):
+        """lins_loop_icp_batch_from: loop_icp with problem k started from T0[k] (4 x 4, e.g. host.place_guess) instead of
+        the identity; returns the C return code as a negative int for a refusal, else the result dicts"""
+        from ._ctypes_defs import LoopIcpParamsC, LoopIcpProblemC, LoopIcpResultC, loop_icp_params, loop_icp_problem_c
+
+        L = lib()
+        prm = params if params is not None else loop_icp_params(L)
+        n = len(problems)
+        arr, keep = (LoopIcpProblemC * max(n, 1))(), []
+        for k, (s, t) in enumerate(problems):
+            arr[k], kk = loop_icp_problem_c(s, t)
+            keep.append(kk)
+        T = np.ascontiguousarray(T0, np.float64).reshape(n, 16) if n else np.zeros((1, 16))
+        out = (LoopIcpResultC * max(n, 1))()
+        L.lins_loop_icp_batch_from.argtypes = [C.c_void_p, C.c_int, C.POINTER(LoopIcpProblemC), C.c_void_p, C.POINTER(LoopIcpParamsC),
+                                               C.POINTER(LoopIcpResultC)]
+        rc = L.lins_loop_icp_batch_from(self._h, n, arr, T.ctypes.data, C.byref(prm), out)
+        if rc in (-1, -4):
+            return rc
+        self._check(rc)
+        return [out[k].as_dict() for k in range(n)]
+
+    # -- place recognition over the archive (include/lins_place.h) -----------------------------------
+    def place_init(self, **kw):
+        """lins_place_init with lins_place_default_params overridden by keyword (up_axis=2, clouds=2, ...); returns the C return code"""
+        from ._ctypes_defs import PlaceParamsC, place_params
+
+        L = lib()
+        prm = place_params(L, **kw)
+        L.lins_place_init.argtypes = [C.c_void_p, C.POINTER(PlaceParamsC)]
+        return L.lins_place_init(self._h, C.byref(prm))
+
+    def place_sync(self, slots):
+        s = np.ascontiguousarray(slots, np.int32)
+        L = lib()
+        L.lins_place_sync.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        return L.lins_place_sync(self._h, len(s), s.ctypes.data)
+
+    def place_search(self, queries):
+        """queries: tuples (query_slot, query_id, target_slot, now, min_gap_s).  Returns the result dicts (id, shift,
+        distance (np.float32), candidates, status), or the C return code (a negative int) of a refused call."""
+        from ._ctypes_defs import PlaceQueryC, PlaceResultC, place_query
+
+        n = len(queries)
+        arr = (PlaceQueryC * max(n, 1))(*[place_query(*q) for q in queries])
+        out = (PlaceResultC * max(n, 1))()
+        L = lib()
+        L.lins_place_search_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(PlaceQueryC), C.POINTER(PlaceResultC)]
+        rc = L.lins_place_search_batch(self._h, n, arr, out)
+        if rc in (-1, -4, -6):
+            return rc
+        self._check(rc)
+        return [out[k].as_dict() for k in range(n)]
+
+    def place_descriptor(self, slot, id):
+        """D[ring][sector] of one frame, (20, 60) f32"""
+        out = np.zeros((20, 60), np.float32)
+        L = lib()
+        L.lins_place_descriptor.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        self._check(L.lins_place_descriptor(self._h, int(slot), int(id), out.ctypes.data))
+        return out
+
+    def place_distances(self, query):
+        """test aid: one entry's row -> (d, shift) per frame of the target slot (-1, -1: inadmissible)"""
+        from ._ctypes_defs import PlaceQueryC, place_query
+
+        q = place_query(*query)
+        cap = max(self.archive_count(q.target_slot), 1)
+        d, sh = np.zeros(cap, np.float32), np.zeros(cap, np.int32)
+        L = lib()
+        L.lins_place_distances.argtypes = [C.c_void_p, C.POINTER(PlaceQueryC), C.c_void_p, C.c_void_p, C.c_int]
+        n = self._rc(L.lins_place_distances(self._h, C.byref(q), d.ctypes.data, sh.ctypes.data, cap))
+        return d[:n].copy(), sh[:n].copy()
+
+    def place_set_chunk(self, chunk):
+        """test hook: candidates per workgroup of the search (0: default)"""
+        L = lib()
+        L.lins_place_set_chunk.argtypes = [C.c_void_p, C.c_int]
+        return L.lins_place_set_chunk(self._h, int(chunk))
+
+    def place_stats(self):
+        """dict(build_ms, search_ms, pairs, frames_built) of the last place call"""
+        b, s, p, f = C.c_float(0), C.c_float(0), C.c_uint64(0), C.c_int32(0)
+        L = lib()
+        L.lins_last_place_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
+        self._check(L.lins_last_place_stats(self._h, C.byref(b), C.byref(s), C.byref(p), C.byref(f)))
+        return dict(build_ms=b.value, search_ms=s.value, pairs=p.value, frames_built=f.value)
 
     def loop_icp_correspondences(self, source, target, T, cap=0.0):
         """one pass of the move + search at T (4 x 4): (idx (-1: none), d) per source point; cap <= 0: no distance cap"""
