@@ -335,11 +335,14 @@ int lins_host_loop_pose_from(const double T[16], const lins_key_pose* wrong, lin
  * (latest, closest) is the pair of the slot's most recent loop factor (-1, -1: none yet), else -1: the pair is aligned.
  * accept (LM:1140-1141): converged && !(fitness > (double)max_fitness), 1 or 0.  A NaN passes, as in the reference's
  * expression; the variance stops it.
- * variance (LM:1171-1175): *variance = (double)(float)fitness; returns 1 when it is finite and > 0, else 0 — a rejection. */
+ * variance (LM:1171-1175): *variance = (double)(float)fitness; returns 1 when it is finite and > 0, else 0 — a rejection.
+ * choose (lins_loop_step_place): among k verified candidates the rank with the smallest fitness of those `accept`
+ * accepts, the lower rank at a tie; -1 when none is accepted (k <= 0 included). */
 int lins_host_loop_window(int latest, int closest, int search_num, int32_t* ids, int cap);
 int lins_host_loop_candidate(int latest, int closest, int last_latest, int last_closest);
 int lins_host_loop_accept(int converged, double fitness, float max_fitness);
 int lins_host_loop_variance(double fitness, double* variance);
+int lins_host_loop_choose(int k, const int32_t* converged, const double* fitness, float max_fitness);
 
 /* ---- the mapping node's own pose arithmetic (csrc/map_pose_math.h; the CPU restatement of lins_streams_map_step's two
  * kernels, lins_streams_map.h).  Pose vectors are (rx, ry, rz, tx, ty, tz) as transformTobeMapped; all f32.
@@ -422,6 +425,14 @@ int lins_host_place_distance(const float* query, const float* candidate, float d
  * be NULL): how many were admissible.  LINS_E_INPUT for a NaN gap or a now that is not finite. */
 int lins_host_place_search(const float* query, const float* descs, const double* times, int n, int skip_id, double now, double min_gap_s,
                            int32_t* id, int32_t* shift, float* distance, int32_t* candidates);
+/* The k best SEPARATED candidates of the same search (the definition of lins_place_topk_batch).  A candidate's row key
+ * is the minimum of (d, id, shift) over its shifts.  Rank 0 is the minimum row key — lins_host_place_search's answer;
+ * rank j the minimum among the candidates c with |c - ids[i]| > min_sep for every earlier rank i; the ranks end at k or
+ * when no admissible candidate is left.  Returns the number of ranks filled (>= 0); the k - filled entries behind them
+ * are id -1, shift 0, distance 1.  LINS_E_ARG for k outside [1, LINS_PLACE_MAX_K] or min_sep < 0. */
+#define LINS_PLACE_MAX_K 8
+int lins_host_place_topk(const float* query, const float* descs, const double* times, int n, int skip_id, double now, double min_gap_s, int k,
+                         int min_sep, int32_t* ids, int32_t* shifts, float* distances, int32_t* candidates);
 /* T0 = M_c R_up(shift 2 pi / LINS_PLACE_SECTORS) M_q^-1 in f64, row-major: the start transform of an ICP whose source is
  * the query frame assembled at its stored pose and whose target lies around the candidate's.  M: a key pose as the
  * archive's assembly applies it, R = Ry(pitch) Rx(roll) Rz(yaw) with translation (x, y, z).  Shift k: what the query

@@ -533,7 +533,9 @@ typedef struct lins_loop_step_result { /* fields of stages that did not run are 
  * slot, stream or flag, a slot or stream named twice, a named slot whose archive and graph hold different frame counts,
  * parameters outside the ranges of the calls they are handed to, or a write-back lins_pose_graph_apply would refuse;
  * LINS_E_INPUT for a non-finite centre or now.  The archive's last assembly and the ICP's buffers are this call's
- * afterwards, as after the explicit calls. */
+ * afterwards, as after the explicit calls.
+ * The same step with its candidates found by APPEARANCE — the K best separated places of the latest frame, every one
+ * verified by ICP — is lins_loop_step_place of lins_place.h (its result carries a lins_place_result per candidate). */
 int lins_loop_step(lins_ctx* ctx, int n, const lins_loop_step_entry* entries, const lins_loop_step_params* prm, lins_loop_step_result* out);
 /* closed_cloud (LM:1143-1154) of entry `entry` of the last lins_loop_step, which must have been aligned (else LINS_E_ARG)
  * with no lins_archive_assemble since (LINS_E_STATE): the ICP contract's step 1 at the final T — M = T rounded to f32,

@@ -57,6 +57,17 @@ int lins_place_sync(lins_ctx* ctx, int n, const int32_t* slots);
  * on what the context ran before.  n = 0 is LINS_OK. */
 int lins_place_search_batch(lins_ctx* ctx, int n, const lins_place_query* queries, lins_place_result* results);
 
+/* n searches for the k best SEPARATED candidates each (k in [1, LINS_PLACE_MAX_K] of lins_host.h, min_sep >= 0, else
+ * LINS_E_ARG; everything else as lins_place_search_batch): bit for bit lins_host_place_topk.  A candidate's row key is the
+ * minimum of (distance, id, shift) over its shifts; rank 0 is the minimum row key — what lins_place_search_batch
+ * returns, for every min_sep —, rank j the minimum among the candidates c with |c - id_i| > min_sep for every earlier
+ * rank i.  results holds n * k records, entry e's ranks at results[e * k ..]; counts[e] is the number of ranks filled,
+ * the records behind them are id -1, shift 0, distance 1; `candidates` is the entry's count in each of its records.
+ * Device sequence: the search with its row buffer on (one key per candidate, sized for the batch), then one select
+ * workgroup per entry; only the n * (1 + k) keys come back.  An entry's bits depend neither on its batch, nor on the
+ * chunk, nor on what the context ran before. */
+int lins_place_topk_batch(lins_ctx* ctx, int n, const lins_place_query* queries, int k, int min_sep, lins_place_result* results, int32_t* counts);
+
 /* the descriptor of one frame, D[ring][sector] */
 int lins_place_descriptor(lins_ctx* ctx, int slot, int id, float out[LINS_PLACE_CELLS]);
 
@@ -73,10 +84,63 @@ int lins_place_set_chunk(lins_ctx* ctx, int chunk);
  * described, (query, candidate) pairs compared — inadmissible ones included, they are computed and masked */
 int lins_last_place_stats(lins_ctx* ctx, float* build_ms, float* search_ms, uint64_t* pairs, int32_t* frames_built);
 
+/* HIP-event time (ms) of the select launch of the last lins_place_topk_batch (0 after any other place call) */
+int lins_last_place_select_ms(lins_ctx* ctx, float* select_ms);
+
 /* lins_loop_icp_batch with T_0 = T0[16 k .. 16 k + 16) (row-major f64) instead of the identity for problem k:
  * lins_host_place_guess gives the start.  LINS_E_INPUT for a T0 that is not finite. */
 int lins_loop_icp_batch_from(lins_ctx* ctx, int n, const lins_loop_icp_problem* in, const double* T0, const lins_loop_icp_params* prm,
                              lins_loop_icp_result* out);
+
+/* ---- the loop thread's step with loops detected by APPEARANCE (lins_map.h lins_loop_step detects them from the poses) ----
+ * The descriptor shortlists, the geometry decides: per entry the k best separated places of the slot's latest frame
+ * (lins_place_topk_batch), every one verified by the ICP from its own guess in ONE batch, the best accepted fit closed by
+ * lins_loop_step's own tail.  Stages, each one batched call over the entries that reach it:
+ *   detect    lins_place_topk_batch: query = the slot's latest frame, target = the same slot, now = entry.now, min_gap_s
+ *             = prm->min_gap_s.  Ranks with distance > max_distance are dropped; lins_host_loop_candidate per rank — a rank
+ *             it calls a repeat is dropped; an entry whose ranks were all dropped as repeats is LINS_LOOP_REPEAT, one left
+ *             without a rank LINS_LOOP_NONE.  The loop-capacity check is lins_loop_step's.
+ *   assemble  one lins_archive_assemble: per entry the source (the latest frame, corner | surf, leaf 0, DROP_NEGATIVE) and
+ *             one target per surviving rank, lins_host_loop_window(latest, id, search_num) at history_leaf
+ *   align     one lins_loop_icp_batch_from over every (entry, rank): T0 = lins_host_place_guess(stored key pose of the
+ *             latest frame, of the candidate, shift, the up_axis of lins_place_init)
+ *   choose    lins_host_loop_choose per entry; -1: LINS_LOOP_REJECTED
+ *   close     the chosen rank goes lins_loop_step's way by the same code: pose_from, the variance rule, the factor, one
+ *             solve, one lins_pose_graph_apply_batch
+ * An entry's result bits and the state it leaves are those of the explicit chain for its slot (DESIGN.md section 5.3 "Loop
+ * thread's step by appearance"), independent of batch, order and history.  In LINS_LOOP_DETECT_POSE_THEN_PLACE an entry
+ * whose pose search has a candidate is bit for bit lins_loop_step's entry (detect 0, cand[0].id = closest_id, its icp in
+ * icp[0] when it was aligned).
+ * Refusals: lins_loop_step's (in DETECT_PLACE the centre is not read, so its two do not apply), LINS_E_STATE before
+ * lins_place_init, LINS_E_ARG for a mode outside the two, k outside [1, LINS_PLACE_MAX_K] or min_sep < -1;
+ * LINS_E_CAPACITY when n (1 + k) submaps or n k alignments exceed what one assembly or one ICP batch takes.  All are
+ * asked before anything is queued: a refused call changes nothing. */
+#define LINS_LOOP_DETECT_PLACE 0           /* appearance only; entry.centre is not read */
+#define LINS_LOOP_DETECT_POSE_THEN_PLACE 1 /* lins_loop_step's detect first; appearance only for entries it leaves without a candidate */
+
+typedef struct lins_loop_place_params {
+  int32_t mode;       /* LINS_LOOP_DETECT_* (default PLACE) */
+  int32_t k;          /* 4: candidates verified per entry */
+  int32_t min_sep;    /* -1: prm->search_num — two candidates closer than the window's half-width assemble nearly the same target */
+  int32_t reserved;
+  float max_distance; /* 1: distances lie in [0, 1], so the default gates nothing and the ICP is the gate */
+  float pad;
+} lins_loop_place_params;
+void lins_loop_place_default_params(lins_loop_place_params* p);
+
+typedef struct lins_loop_place_result {
+  lins_loop_step_result step; /* as lins_loop_step's, for the chosen candidate (closest_id = its id, history = its window, icp = its
+                                 alignment); without one: latest as assembled, closest_id -1, history and icp zero */
+  int32_t detect;             /* 0: the candidate came from the pose search, 1: from appearance */
+  int32_t n_candidates;       /* ranks that went to the alignment */
+  int32_t chosen;             /* the chosen rank, or -1 */
+  int32_t reserved;
+  lins_place_result cand[LINS_PLACE_MAX_K]; /* the surviving ranks, in rank order; behind them id -1, shift 0, distance 1 */
+  lins_loop_icp_result icp[LINS_PLACE_MAX_K];
+} lins_loop_place_result;
+
+int lins_loop_step_place(lins_ctx* ctx, int n, const lins_loop_step_entry* entries, const lins_loop_step_params* prm,
+                         const lins_loop_place_params* place, lins_loop_place_result* out);
 
 #ifdef __cplusplus
 }

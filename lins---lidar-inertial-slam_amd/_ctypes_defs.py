@@ -645,6 +645,39 @@ def place_query(query_slot, query_id, target_slot, now, min_gap_s):
     return PlaceQueryC(int(query_slot), int(query_id), int(target_slot), 0, float(now), float(min_gap_s))
 
 
+# ---- the loop thread's step by appearance (include/lins_place.h lins_loop_step_place) ----
+PLACE_MAX_K = 8
+LOOP_DETECT_PLACE, LOOP_DETECT_POSE_THEN_PLACE = 0, 1
+
+
+class LoopPlaceParamsC(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("k", C.c_int32), ("min_sep", C.c_int32), ("reserved", C.c_int32), ("max_distance", C.c_float),
+                ("pad", C.c_float)]
+
+
+class LoopPlaceResultC(C.Structure):
+    _fields_ = [("step", LoopStepResultC), ("detect", C.c_int32), ("n_candidates", C.c_int32), ("chosen", C.c_int32), ("reserved", C.c_int32),
+                ("cand", PlaceResultC * PLACE_MAX_K), ("icp", LoopIcpResultC * PLACE_MAX_K)]
+
+    def as_dict(self):
+        n = int(self.n_candidates)
+        return dict(step=self.step.as_dict(), detect=int(self.detect), n_candidates=n, chosen=int(self.chosen),
+                    cand=[self.cand[j].as_dict() for j in range(n)], icp=[self.icp[j].as_dict() for j in range(n)])
+
+
+def loop_place_params(lib, **kw):
+    """lins_loop_place_default_params with fields overridden by keyword (mode=, k=, min_sep=, max_distance=)"""
+    p = LoopPlaceParamsC()
+    lib.lins_loop_place_default_params.argtypes = [C.POINTER(LoopPlaceParamsC)]
+    lib.lins_loop_place_default_params.restype = None
+    lib.lins_loop_place_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"lins_loop_place_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
 # ---- stream snapshots (include/lins_snapshot.h): the blob's header and records, the plan's records ----
 SNAPSHOT_MAGIC, SNAPSHOT_VERSION = 0x3150414E534E494C, 1
 SNAP_STREAM, SNAP_FILTER, SNAP_BOOT, SNAP_ODOM, SNAP_MAP_POSE, SNAP_RING, SNAP_ARCHIVE, SNAP_GRAPH = (1 << k for k in range(8))

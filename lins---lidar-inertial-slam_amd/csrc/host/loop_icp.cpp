@@ -173,6 +173,11 @@ int lins_host_loop_accept(int converged, double fitness, float max_fitness) { re
 
 int lins_host_loop_variance(double fitness, double* variance) { return lins_loop::variance(fitness, variance) ? 1 : 0; }
 
+int lins_host_loop_choose(int k, const int32_t* converged, const double* fitness, float max_fitness) {
+  if (k <= 0 || !converged || !fitness) return -1;
+  return lins_loop::choose(k, converged, fitness, max_fitness);
+}
+
 int lins_host_loop_pose_from(const double T[16], const lins_key_pose* wrong, lins_key_pose* pose_from) {
   if (!T || !wrong || !pose_from) return LINS_E_ARG;
   lins_loop::pose_from(T, *wrong, pose_from);

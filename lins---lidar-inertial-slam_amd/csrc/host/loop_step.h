@@ -51,6 +51,18 @@ inline int candidate(int latest, int closest, int last_latest, int last_closest)
 
 inline bool accept(int converged, double fitness, float max_fitness) { return converged && !(fitness > (double)max_fitness); }
 
+// lins_loop_step_place's choice among the k candidates the ICP verified: the rank of the smallest fitness among those
+// `accept` accepts, the lower rank at a tie, -1 when none is.  (A NaN passes `accept`; it is "smallest" only when every
+// accepted fitness is a NaN — the variance rule then rejects the entry.)
+inline int choose(int k, const int32_t* converged, const double* fitness, float max_fitness) {
+  int at = -1;
+  for (int j = 0; j < k; ++j) {
+    if (!accept(converged[j], fitness[j], max_fitness)) continue;
+    if (at < 0 || fitness[j] < fitness[at] || (std::isnan(fitness[at]) && !std::isnan(fitness[j]))) at = j;
+  }
+  return at;
+}
+
 // false: a rejection; *var is the factor's variance either way
 inline bool variance(double fitness, double* var) {
   const double v = (double)(float)fitness;

@@ -6,7 +6,7 @@
 #include <vector>
 
 #include "../../../include/lins_host.h"
-#include "loop_step.h"
+#include "place_guess.h"
 #include "place_math.h"
 #include "voxel_map.h"
 
@@ -32,11 +32,6 @@ void distances(const float* Uq, const bool* vq, const float* Uc, const bool* vc,
     }
     d[k] = distance_of(sim, cnt);
   }
-}
-
-void mul4(const double* A, const double* B, double* C) {
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j) C[4 * i + j] = A[4 * i] * B[j] + A[4 * i + 1] * B[4 + j] + A[4 * i + 2] * B[8 + j] + A[4 * i + 3] * B[12 + j];
 }
 
 }  // namespace
@@ -105,21 +100,39 @@ int lins_host_place_search(const float* query, const float* descs, const double*
   return LINS_OK;
 }
 
+int lins_host_place_topk(const float* query, const float* descs, const double* times, int n, int skip_id, double now, double min_gap_s, int k,
+                         int min_sep, int32_t* ids, int32_t* shifts, float* dist, int32_t* candidates) {
+  if (!query || n < 0 || n > kMaxId || (n && (!descs || !times)) || k < 1 || k > kMaxK || min_sep < 0 || !ids || !shifts || !dist) return LINS_E_ARG;
+  if (!std::isfinite(now) || std::isnan(min_gap_s)) return LINS_E_INPUT;
+  std::vector<float> Uq(kCells), Uc(kCells);
+  bool vq[kNS], vc[kNS];
+  float d[kNS];
+  columns_of(query, Uq.data(), vq);
+  std::vector<unsigned long long> row((size_t)n, kNoKey);
+  int cnt = 0;
+  for (int c = 0; c < n; ++c) {
+    if (c == skip_id || !time_admits(times[c], now, min_gap_s)) continue;
+    ++cnt;
+    columns_of(descs + (size_t)c * kCells, Uc.data(), vc);
+    distances(Uq.data(), vq, Uc.data(), vc, d);
+    for (int s = 0; s < kNS; ++s) {
+      const unsigned long long key = pack_key(d[s], c, s);
+      if (key < row[c]) row[c] = key;
+    }
+  }
+  unsigned long long keys[kMaxK];
+  const int filled = select_topk(row.data(), n, k, min_sep, keys);
+  for (int j = 0; j < k; ++j) {
+    ids[j] = -1, shifts[j] = 0, dist[j] = 1.f;
+    if (keys[j] != kNoKey) unpack_key(keys[j], &dist[j], &ids[j], &shifts[j]);
+  }
+  if (candidates) *candidates = cnt;
+  return filled;
+}
+
 int lins_host_place_guess(const lins_key_pose* pose_q, const lins_key_pose* pose_c, int shift, int up_axis, double* T0) {
   if (!pose_q || !pose_c || !T0 || shift < 0 || shift >= kNS || up_axis < 0 || up_axis > 2) return LINS_E_ARG;
-  double Mq[16], Mc[16], Mi[16], R[16], A[16];
-  lins_loop::key_pose_matrix(*pose_q, Mq), lins_loop::key_pose_matrix(*pose_c, Mc);  // (loop_step.h: the conversion behind pose_from)
-  // M_q^-1 = (R^T, -R^T t)
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) Mi[4 * i + j] = Mq[4 * j + i];
-    Mi[4 * i + 3] = -(Mq[i] * Mq[3] + Mq[4 + i] * Mq[7] + Mq[8 + i] * Mq[11]);
-  }
-  Mi[12] = Mi[13] = Mi[14] = 0.0, Mi[15] = 1.0;
-  const double th = shift * (6.283185307179586476925 / kNS), c = std::cos(th), s = std::sin(th);
-  const int a = (up_axis + 1) % 3, b = (up_axis + 2) % 3;
-  for (int i = 0; i < 16; ++i) R[i] = (i % 5 == 0) ? 1.0 : 0.0;
-  R[4 * a + a] = c, R[4 * a + b] = -s, R[4 * b + a] = s, R[4 * b + b] = c;
-  mul4(Mc, R, A), mul4(A, Mi, T0);
+  guess(*pose_q, *pose_c, shift, up_axis, T0);
   return LINS_OK;
 }
 

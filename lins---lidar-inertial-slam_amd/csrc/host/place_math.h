@@ -11,6 +11,10 @@
 //               Uq[r][j] * Uc[r][jc] from 0; sim += dot, cnt += 1; d(k) = cnt ? max(0, 1 - sim / (float)cnt) : 1
 //   search      the minimum of (d, id, k), lexicographic: as the packed key (bits(d) << 32) | (id << 6) | k — d >= 0, so
 //               its bits order as the distances do
+//   top-K       a candidate's row key = the minimum over the shifts of its packed keys, kNoKey when it is not admissible.
+//               Rank 0 = the minimum row key; rank j = the minimum row key among the candidates c with |c - id_i| > min_sep
+//               for every earlier rank i; the ranks end at k or when only kNoKey remains (select_topk; the device takes
+//               each rank's minimum in parallel over the same predicate, `separated`)
 #pragma once
 #include <stdint.h>
 
@@ -25,6 +29,7 @@ constexpr float kInvS = (float)(kNS / 6.283185307179586476925);  // sectors per 
 constexpr float kFloor = 0x1p-10f;                                // the smallest height that counts
 constexpr int kMaxId = 1 << 26;                                   // ids a packed key holds
 constexpr unsigned long long kNoKey = ~0ull;
+constexpr int kMaxK = 8;                                          // LINS_PLACE_MAX_K: ranks of a top-K search
 
 LINS_HD float inv_r_of(float r_max) { return (float)kNR / r_max; }
 
@@ -81,6 +86,29 @@ LINS_HD void unpack_key(unsigned long long key, float* d, int* id, int* k) {
   const unsigned u = (unsigned)(key >> 32);
   __builtin_memcpy(d, &u, 4);
   *id = (int)((key & 0xffffffffull) >> 6), *k = (int)(key & 63ull);
+}
+
+// top-K: candidate c may still be chosen — it lies more than min_sep ids from every id chosen so far (ids < 2^26, min_sep >= 0)
+LINS_HD bool separated(int c, const int* chosen, int n_chosen, int min_sep) {
+  for (int i = 0; i < n_chosen; ++i) {
+    const int gap = c > chosen[i] ? c - chosen[i] : chosen[i] - c;
+    if (gap <= min_sep) return false;
+  }
+  return true;
+}
+// row[c] = candidate c's row key, c < n.  out[0 .. k): the ranks' keys, kNoKey behind the last one filled; returns how many are
+inline int select_topk(const unsigned long long* row, int n, int k, int min_sep, unsigned long long* out) {
+  int chosen[kMaxK], cnt = 0;
+  for (int j = 0; j < k; ++j) out[j] = kNoKey;
+  while (cnt < k) {
+    unsigned long long best = kNoKey;
+    int at = -1;
+    for (int c = 0; c < n; ++c)
+      if (row[c] < best && separated(c, chosen, cnt, min_sep)) best = row[c], at = c;
+    if (at < 0) break;
+    out[cnt] = best, chosen[cnt] = at, ++cnt;
+  }
+  return cnt;
 }
 
 // find_loop's gate (keyframe_select.h): at equality the candidate is not admissible; gap < 0 admits every time

@@ -198,6 +198,10 @@ void launch_place_build(hipStream_t s, int n, const PlStale* stale, const float4
 // workgroup per entry: the minimum of its chunks' bests to out.  row (may be null): every candidate's best key, at the entry's `row`
 void launch_place_search(hipStream_t s, int n_entries, int n_chunks, const PlEntry* entries, const int2* chunks, int chunk, const float* recs,
                          unsigned long long* chunk_best, unsigned long long* row, unsigned long long* out);
+// behind a search that wrote `row`: one workgroup per entry, the keys of its k best candidates more than min_sep ids apart
+// to out + entry * k (kNoKey behind the last rank filled)
+void launch_place_select(hipStream_t s, int n_entries, const PlEntry* entries, const unsigned long long* row, int k, int min_sep,
+                         unsigned long long* out);
 
 // ---- pose_graph_kernels.hip: the pose graph's solve, one workgroup per problem (pose_graph.h) ----
 // the poses and the cost of every problem as it stands (the first launch of a solve)

@@ -13,11 +13,14 @@
 #include "../../include/lins_map.h"
 #include "../../include/lins_streams_map.h"
 #include "host/keyframe_select.h"
+#include "../../include/lins_place.h"
 #include "host/loop_step.h"
+#include "host/place_guess.h"
 #include "keyframe_archive.h"
 #include "lins_ctx_priv.h"
 #include "local_map.h"
 #include "loop_icp_math.h"
+#include "place.h"
 #include "pose_graph.h"
 
 using namespace lins;
@@ -52,6 +55,100 @@ bool params_ok(const lins_loop_step_params* p) {
          std::isfinite(p->icp.max_corr_dist) && lins_pg::params_ok(&p->graph);
 }
 
+// entry k's step record: lins_loop_step's results are an array of them, lins_loop_step_place's begin with one
+lins_loop_step_result& step_at(void* out, size_t stride, int k) { return *(lins_loop_step_result*)((char*)out + (size_t)k * stride); }
+
+// The whole call's errors of both entry points, before anything is queued; fills slots, streams and (read_centre) centre.
+int check_call(lins_ctx* ctx, int n, const lins_loop_step_entry* entries, const lins_loop_step_params* prm, bool read_centre,
+               std::vector<int32_t>& slots, std::vector<int32_t>& streams, std::vector<float>& centre) {
+  slots.assign(n, 0), streams.assign(n, 0), centre.assign(3 * (size_t)n, 0.f);
+  for (int k = 0; k < n; ++k) {
+    const lins_loop_step_entry& e = entries[k];
+    const int in_archive = lins_archive_count(ctx, e.slot);
+    if (in_archive < 0 || e.slot >= pose_graph_slots(ctx) || in_archive != lins_pose_graph_count(ctx, e.slot, nullptr)) return LINS_E_ARG;
+    if (e.stream < -1 || e.stream >= streams_map_streams(ctx) || (e.flags & ~LINS_LOOP_CENTRE_STREAM)) return LINS_E_ARG;
+    if ((e.flags & LINS_LOOP_CENTRE_STREAM) && e.stream < 0) return LINS_E_ARG;
+    for (int i = 0; i < k; ++i)
+      if (entries[i].slot == e.slot || (e.stream >= 0 && entries[i].stream == e.stream)) return LINS_E_ARG;
+    slots[k] = e.slot, streams[k] = e.stream;
+  }
+  for (int k = 0; k < n; ++k) {
+    const lins_loop_step_entry& e = entries[k];
+    if (!read_centre) {
+      if (!std::isfinite(e.now)) return LINS_E_INPUT;
+      continue;
+    }
+    if (e.flags & LINS_LOOP_CENTRE_STREAM) {
+      if (int rc = streams_map_centre(ctx, e.stream, &centre[3 * (size_t)k])) return rc;  // LINS_E_STATE: has not stepped
+    } else {
+      std::memcpy(&centre[3 * (size_t)k], e.centre, 3 * sizeof(float));
+    }
+    if (!lins_select::query_ok(&centre[3 * (size_t)k], prm->search_radius) || !std::isfinite(e.now)) return LINS_E_INPUT;
+  }
+  std::vector<int32_t> with_frames_slots, with_frames_streams;  // the write-back's refusals (a slot without frames closes nothing)
+  for (int k = 0; k < n; ++k)
+    if (lins_archive_count(ctx, slots[k]) > 0) with_frames_slots.push_back(slots[k]), with_frames_streams.push_back(streams[k]);
+  return pose_graph_apply_check(ctx, (int)with_frames_slots.size(), with_frames_slots.data(), with_frames_streams.data());
+}
+
+// lins_archive_find_loop's answer per entry (-1: none, or a slot without frames); LINS_KEYPOSES_DEVICE: the entries that
+// have frames in one lins_keyposes_find_loop_batch
+int pose_detect(lins_ctx* ctx, int n, const lins_loop_step_entry* entries, const lins_loop_step_params* prm, const std::vector<int32_t>& slots,
+                const std::vector<float>& centre, std::vector<int32_t>& closest) {
+  closest.assign(n, -1);
+  if (lins_keyposes_mode(ctx) == LINS_KEYPOSES_DEVICE) {
+    std::vector<int> at;
+    std::vector<lins_keyposes_loop_query> qs;
+    for (int k = 0; k < n; ++k) {
+      if (lins_archive_count(ctx, slots[k]) < 1) continue;
+      const float* c = &centre[3 * (size_t)k];
+      at.push_back(k);
+      qs.push_back(lins_keyposes_loop_query{lins_keyposes_query{slots[k], {c[0], c[1], c[2]}, prm->search_radius, 0.f}, entries[k].now, prm->min_gap_s});
+    }
+    std::vector<int32_t> found(qs.size(), -1);
+    if (int rc = lins_keyposes_find_loop_batch(ctx, (int)qs.size(), qs.data(), found.data())) return rc;
+    for (size_t i = 0; i < at.size(); ++i) closest[at[i]] = found[i];
+    return LINS_OK;
+  }
+  for (int k = 0; k < n; ++k) {
+    if (lins_archive_count(ctx, slots[k]) < 1) continue;
+    if (int rc = lins_archive_find_loop(ctx, slots[k], &centre[3 * (size_t)k], prm->search_radius, entries[k].now, prm->min_gap_s, &closest[k])) return rc;
+  }
+  return LINS_OK;
+}
+
+// The tail both entry points share (LM:1140-1181, 1767-1795).  `judged`: the entries whose step record holds an alignment
+// (icp, closest_id) and the outcome LINS_LOOP_REJECTED.  The factor of every accepted one, then the solve and the
+// correction of the history, one call each over the slots that gained a loop.
+int close_loops(lins_ctx* ctx, LoopStepMem* m, const lins_loop_step_params* prm, const std::vector<int32_t>& slots, const std::vector<int32_t>& streams,
+                const std::vector<int>& judged, void* out, size_t stride) {
+  std::vector<int> closed;  // entries
+  for (int k : judged) {
+    lins_loop_step_result& r = step_at(out, stride, k);
+    if (!lins_loop::accept(r.icp.converged, r.icp.fitness, prm->max_fitness) || !lins_loop::variance(r.icp.fitness, nullptr)) continue;
+    lins_key_pose wrong;
+    if (int rc = lins_pose_graph_poses(ctx, slots[k], r.latest_id, 1, &wrong)) return rc;
+    lins_loop::pose_from(r.icp.transform, wrong, &r.pose_from);
+    if (int rc = lins_pose_graph_add_loop(ctx, slots[k], r.latest_id, r.closest_id, &r.pose_from, r.icp.fitness)) {
+      r.status = rc;  // (a pose_from that is not finite)
+      continue;
+    }
+    closed.push_back(k);
+  }
+  const int ns = (int)closed.size();
+  if (ns == 0) return LINS_OK;
+  std::vector<int32_t> s_slots(ns), s_streams(ns);
+  std::vector<lins_pose_graph_result> solved(ns);
+  for (int i = 0; i < ns; ++i) s_slots[i] = slots[closed[i]], s_streams[i] = streams[closed[i]];
+  if (int rc = lins_pose_graph_solve(ctx, ns, s_slots.data(), &prm->graph, solved.data())) return rc;
+  (void)lins_last_pose_graph_stats(ctx, &m->solve_ms, nullptr);
+  for (int i = 0; i < ns; ++i) step_at(out, stride, closed[i]).graph = solved[i];
+  if (int rc = lins_pose_graph_apply_batch(ctx, ns, s_slots.data(), s_streams.data())) return rc;
+  for (int i = 0; i < ns; ++i) step_at(out, stride, closed[i]).outcome = LINS_LOOP_CLOSED;
+  m->closed = ns;
+  return LINS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -68,62 +165,22 @@ int lins_loop_step(lins_ctx* ctx, int n, const lins_loop_step_entry* entries, co
   if (lins_archive_count(ctx, 0) == LINS_E_STATE || !pose_graph_slots(ctx)) return LINS_E_STATE;
   if (!params_ok(prm)) return LINS_E_ARG;
   // ---- the whole call's errors, before anything is queued ----
-  std::vector<int32_t> slots(n), streams(n);
-  std::vector<float> centre(3 * (size_t)n);
-  for (int k = 0; k < n; ++k) {
-    const lins_loop_step_entry& e = entries[k];
-    const int in_archive = lins_archive_count(ctx, e.slot);
-    if (in_archive < 0 || e.slot >= pose_graph_slots(ctx) || in_archive != lins_pose_graph_count(ctx, e.slot, nullptr)) return LINS_E_ARG;
-    if (e.stream < -1 || e.stream >= streams_map_streams(ctx) || (e.flags & ~LINS_LOOP_CENTRE_STREAM)) return LINS_E_ARG;
-    if ((e.flags & LINS_LOOP_CENTRE_STREAM) && e.stream < 0) return LINS_E_ARG;
-    for (int i = 0; i < k; ++i)
-      if (entries[i].slot == e.slot || (e.stream >= 0 && entries[i].stream == e.stream)) return LINS_E_ARG;
-    slots[k] = e.slot, streams[k] = e.stream;
-  }
-  for (int k = 0; k < n; ++k) {
-    const lins_loop_step_entry& e = entries[k];
-    if (e.flags & LINS_LOOP_CENTRE_STREAM) {
-      if (int rc = streams_map_centre(ctx, e.stream, &centre[3 * (size_t)k])) return rc;  // LINS_E_STATE: has not stepped
-    } else {
-      std::memcpy(&centre[3 * (size_t)k], e.centre, 3 * sizeof(float));
-    }
-    if (!lins_select::query_ok(&centre[3 * (size_t)k], prm->search_radius) || !std::isfinite(e.now)) return LINS_E_INPUT;
-  }
-  std::vector<int32_t> with_frames_slots, with_frames_streams;  // the write-back's refusals (a slot without frames closes nothing)
-  for (int k = 0; k < n; ++k)
-    if (lins_archive_count(ctx, slots[k]) > 0) with_frames_slots.push_back(slots[k]), with_frames_streams.push_back(streams[k]);
-  if (int rc = pose_graph_apply_check(ctx, (int)with_frames_slots.size(), with_frames_slots.data(), with_frames_streams.data())) return rc;
+  std::vector<int32_t> slots, streams, closest;
+  std::vector<float> centre;
+  if (int rc = check_call(ctx, n, entries, prm, true, slots, streams, centre)) return rc;
 
   LoopStepMem* m = mem_of(ctx);
   m->last.assign(n, Aligned());
   m->assemble_ms = m->icp_ms = m->solve_ms = 0.f, m->candidates = m->aligned = m->closed = 0;
   // ---- detect (host work: keyframe_select.h, loop_step.h) ----
   std::vector<int> cand;  // entries that go to the assembly
-  // LINS_KEYPOSES_DEVICE: the candidates of the entries that have frames in one lins_keyposes_find_loop_batch
-  const bool on_device = lins_keyposes_mode(ctx) == LINS_KEYPOSES_DEVICE;
-  std::vector<int> dev_at(on_device ? (size_t)n : 0, -1);
-  std::vector<int32_t> dev_closest;
-  if (on_device) {
-    std::vector<lins_keyposes_loop_query> qs;
-    for (int k = 0; k < n; ++k) {
-      if (lins_archive_count(ctx, slots[k]) < 1) continue;
-      const float* c = &centre[3 * (size_t)k];
-      dev_at[k] = (int)qs.size();
-      qs.push_back(lins_keyposes_loop_query{lins_keyposes_query{slots[k], {c[0], c[1], c[2]}, prm->search_radius, 0.f}, entries[k].now, prm->min_gap_s});
-    }
-    dev_closest.assign(qs.size(), -1);
-    if (int rc = lins_keyposes_find_loop_batch(ctx, (int)qs.size(), qs.data(), dev_closest.data())) return rc;
-  }
+  if (int rc = pose_detect(ctx, n, entries, prm, slots, centre, closest)) return rc;
   for (int k = 0; k < n; ++k) {
     lins_loop_step_result& r = out[k];
     std::memset(&r, 0, sizeof r);
     r.outcome = LINS_LOOP_NONE, r.latest_id = lins_archive_count(ctx, slots[k]) - 1, r.closest_id = -1;
     if (r.latest_id < 0) continue;
-    if (on_device) {
-      r.closest_id = dev_closest[dev_at[k]];
-    } else if (int rc = lins_archive_find_loop(ctx, slots[k], &centre[3 * (size_t)k], prm->search_radius, entries[k].now, prm->min_gap_s, &r.closest_id)) {
-      return rc;
-    }
+    r.closest_id = closest[k];
     int loops_left = 0, last_latest = -1, last_closest = -1;
     pose_graph_room(ctx, slots[k], nullptr, &loops_left, &last_latest, &last_closest);
     const int what = lins_loop::candidate(r.latest_id, r.closest_id, last_latest, last_closest);
@@ -174,8 +231,8 @@ int lins_loop_step(lins_ctx* ctx, int n, const lins_loop_step_entry* entries, co
   std::vector<lins_loop_icp_result> icp(na);
   if (int rc = lins_loop_icp_batch(ctx, na, probs.data(), &prm->icp, icp.data())) return rc;
   (void)lins_last_loop_icp_stats(ctx, &m->icp_ms, nullptr);
-  // ---- the factor of every accepted entry (LM:1140-1181) ----
-  std::vector<int> closed;  // entries
+  // ---- the factor of every accepted entry, the solve, the correction (close_loops) ----
+  std::vector<int> judged;  // entries
   for (int j = 0; j < na; ++j) {
     const int k = cand[run[j]];
     lins_loop_step_result& r = out[k];
@@ -188,29 +245,196 @@ int lins_loop_step(lins_ctx* ctx, int n, const lins_loop_step_entry* entries, co
     std::memcpy(m->last[k].T, r.icp.transform, sizeof r.icp.transform);
     m->aligned += 1;
     r.outcome = LINS_LOOP_REJECTED;
-    if (!lins_loop::accept(r.icp.converged, r.icp.fitness, prm->max_fitness) || !lins_loop::variance(r.icp.fitness, nullptr)) continue;
-    lins_key_pose wrong;
-    if (int rc = lins_pose_graph_poses(ctx, slots[k], r.latest_id, 1, &wrong)) return rc;
-    lins_loop::pose_from(r.icp.transform, wrong, &r.pose_from);
-    if (int rc = lins_pose_graph_add_loop(ctx, slots[k], r.latest_id, r.closest_id, &r.pose_from, r.icp.fitness)) {
-      r.status = rc;  // (a pose_from that is not finite)
+    judged.push_back(k);
+  }
+  return close_loops(ctx, m, prm, slots, streams, judged, out, sizeof(lins_loop_step_result));
+}
+
+void lins_loop_place_default_params(lins_loop_place_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof *p);
+  p->mode = LINS_LOOP_DETECT_PLACE, p->k = 4, p->min_sep = -1, p->max_distance = 1.f;
+}
+
+// (include/lins_place.h) lins_loop_step with the candidates found by appearance: every stage below is ONE batched call
+int lins_loop_step_place(lins_ctx* ctx, int n, const lins_loop_step_entry* entries, const lins_loop_step_params* prm,
+                         const lins_loop_place_params* place, lins_loop_place_result* out) {
+  if (!ctx || n < 0 || (n && (!entries || !out))) return LINS_E_ARG;
+  if (lins_archive_count(ctx, 0) == LINS_E_STATE || !pose_graph_slots(ctx)) return LINS_E_STATE;
+  ArchivePlace ap;
+  if (archive_place(ctx, &ap) || !ap.store->on) return LINS_E_STATE;
+  if (!params_ok(prm) || !place) return LINS_E_ARG;
+  const bool pose_first = place->mode == LINS_LOOP_DETECT_POSE_THEN_PLACE;
+  if ((place->mode != LINS_LOOP_DETECT_PLACE && !pose_first) || place->k < 1 || place->k > LINS_PLACE_MAX_K || place->min_sep < -1 ||
+      std::isnan(place->max_distance))
+    return LINS_E_ARG;
+  const int K = place->k, min_sep = place->min_sep < 0 ? prm->search_num : place->min_sep;
+  // ---- the whole call's errors, before anything is queued ----
+  std::vector<int32_t> slots, streams, closest(n, -1);
+  std::vector<float> centre;
+  if (int rc = check_call(ctx, n, entries, prm, pose_first, slots, streams, centre)) return rc;
+  if ((long long)n * (1 + K) > 2147483647ll) return LINS_E_CAPACITY;  // (specs of one assembly; the n K alignments are fewer)
+
+  LoopStepMem* m = mem_of(ctx);
+  m->last.assign(n, Aligned());
+  m->assemble_ms = m->icp_ms = m->solve_ms = 0.f, m->candidates = m->aligned = m->closed = 0;
+  const size_t stride = sizeof(lins_loop_place_result);
+  // ---- detect: the pose search where the mode asks for it, then one top-K search over the entries it left empty-handed ----
+  if (pose_first)
+    if (int rc = pose_detect(ctx, n, entries, prm, slots, centre, closest)) return rc;
+  std::vector<int> asking;  // entries of the place search
+  std::vector<lins_place_query> qs;
+  for (int k = 0; k < n; ++k) {
+    lins_loop_place_result& o = out[k];
+    std::memset(&o, 0, sizeof o);
+    o.step.outcome = LINS_LOOP_NONE, o.step.latest_id = lins_archive_count(ctx, slots[k]) - 1, o.step.closest_id = -1, o.chosen = -1;
+    for (int j = 0; j < LINS_PLACE_MAX_K; ++j) o.cand[j].id = -1, o.cand[j].distance = 1.f;
+    if (o.step.latest_id < 0) continue;
+    if (closest[k] >= 0) continue;  // (detect 0: lins_loop_step's entry)
+    o.detect = 1;
+    asking.push_back(k);
+    qs.push_back(lins_place_query{slots[k], o.step.latest_id, slots[k], 0, entries[k].now, prm->min_gap_s});
+  }
+  std::vector<lins_place_result> found(qs.size() * (size_t)K);
+  std::vector<int32_t> filled(qs.size(), 0);
+  if (!qs.empty())
+    if (int rc = lins_place_topk_batch(ctx, (int)qs.size(), qs.data(), K, min_sep, found.data(), filled.data())) return rc;
+  std::vector<int> at_query(n, -1);
+  for (size_t i = 0; i < asking.size(); ++i) at_query[asking[i]] = (int)i;
+  std::vector<int> cand;  // entries that go to the assembly
+  for (int k = 0; k < n; ++k) {
+    lins_loop_place_result& o = out[k];
+    lins_loop_step_result& r = o.step;
+    if (r.latest_id < 0) continue;
+    int loops_left = 0, last_latest = -1, last_closest = -1, what = LINS_LOOP_NONE;
+    pose_graph_room(ctx, slots[k], nullptr, &loops_left, &last_latest, &last_closest);
+    if (!o.detect) {
+      r.closest_id = closest[k];
+      what = lins_loop::candidate(r.latest_id, r.closest_id, last_latest, last_closest);
+      if (what == lins_loop::kAlign) o.cand[0].id = r.closest_id, o.n_candidates = 1;
+    } else {
+      const lins_place_result* f = &found[(size_t)at_query[k] * K];
+      for (int j = 0; j < filled[at_query[k]]; ++j) {
+        if (f[j].distance > place->max_distance) continue;
+        const int w = lins_loop::candidate(r.latest_id, f[j].id, last_latest, last_closest);
+        if (w == LINS_LOOP_REPEAT) what = LINS_LOOP_REPEAT;
+        if (w == lins_loop::kAlign) o.cand[o.n_candidates++] = f[j];
+      }
+      if (o.n_candidates) what = lins_loop::kAlign;
+    }
+    if (what != lins_loop::kAlign) {
+      r.outcome = what;
+    } else if (loops_left < 1) {
+      r.status = LINS_E_CAPACITY, o.n_candidates = 0;
+      for (int j = 0; j < LINS_PLACE_MAX_K; ++j) o.cand[j] = lins_place_result{-1, 0, 1.f, 0, 0, 0};
+    } else {
+      cand.push_back(k);
+    }
+  }
+  const int nc = (int)cand.size();
+  m->candidates = nc;
+  if (nc == 0) return LINS_OK;
+  // ---- assemble: per candidate entry the latest frame, then one history window per rank; one call ----
+  std::vector<int> first(nc + 1, 0);  // an entry's first spec (its source)
+  for (int i = 0; i < nc; ++i) first[i + 1] = first[i] + 1 + out[cand[i]].n_candidates;
+  const int n_specs = first[nc];
+  std::vector<std::vector<int32_t>> ids(n_specs);
+  std::vector<lins_submap_spec> specs(n_specs);
+  std::vector<lins_submap_info> infos(n_specs);
+  for (int i = 0; i < nc; ++i) {
+    const lins_loop_place_result& o = out[cand[i]];
+    const int latest = o.step.latest_id, s0 = first[i];
+    ids[s0].assign(1, latest);
+    specs[s0] = lins_submap_spec{ids[s0].data(), 1, slots[cand[i]], LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF, LINS_SUBMAP_DROP_NEGATIVE, 0.f, 0};
+    for (int j = 0; j < o.n_candidates; ++j) {
+      std::vector<int32_t>& w = ids[s0 + 1 + j];
+      w.resize(lins_loop::window_size(latest, o.cand[j].id, prm->search_num));
+      lins_loop::window(latest, o.cand[j].id, prm->search_num, w.data());
+      specs[s0 + 1 + j] = lins_submap_spec{w.data(), (int32_t)w.size(), slots[cand[i]], LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF, 0, prm->history_leaf, 0};
+    }
+  }
+  if (int rc = lins_archive_assemble(ctx, n_specs, specs.data(), infos.data())) return rc;
+  (void)lins_last_archive_stats(ctx, &m->assemble_ms, nullptr);
+  ArchiveView av{};
+  if (int rc = archive_view(ctx, &av)) return rc;
+  m->serial = av.serial;
+  // ---- align: one batch over every (entry, rank) of the entries whose assemblies have no status ----
+  std::vector<int> run;  // positions in cand
+  std::vector<int> prob0;  // their first problem
+  std::vector<lins_loop_icp_problem> probs;
+  std::vector<double> T0;
+  const std::vector<std::vector<ArFrame>>& frames = *ap.frames;
+  for (int i = 0; i < nc; ++i) {
+    lins_loop_place_result& o = out[cand[i]];
+    lins_loop_step_result& r = o.step;
+    r.latest = infos[first[i]];
+    if (!o.detect) r.history = infos[first[i] + 1];
+    int status = r.latest.status;
+    for (int j = 0; j < o.n_candidates && !status; ++j) status = infos[first[i] + 1 + j].status;
+    if (status) {  // (the entry's first: nothing is aligned for it)
+      r.status = status;
       continue;
     }
-    closed.push_back(k);
+    run.push_back(i), prob0.push_back((int)probs.size());
+    for (int j = 0; j < o.n_candidates; ++j) {
+      probs.push_back(lins_loop_icp_problem{first[i], first[i] + 1 + j, nullptr, nullptr, 0, 0});
+      T0.resize(T0.size() + 16, 0.0);
+      double* T = &T0[T0.size() - 16];
+      if (o.detect) {
+        const std::vector<ArFrame>& fr = frames[slots[cand[i]]];
+        lins_place::guess(fr[r.latest_id].pose, fr[o.cand[j].id].pose, o.cand[j].shift, ap.store->prm.up_axis, T);
+      } else {
+        T[0] = T[5] = T[10] = T[15] = 1.0;  // (lins_loop_icp_batch's start)
+      }
+    }
   }
-  const int ns = (int)closed.size();
-  if (ns == 0) return LINS_OK;
-  // ---- solve, then correct the history: one call each over the slots that gained a loop ----
-  std::vector<int32_t> s_slots(ns), s_streams(ns);
-  std::vector<lins_pose_graph_result> solved(ns);
-  for (int i = 0; i < ns; ++i) s_slots[i] = slots[closed[i]], s_streams[i] = streams[closed[i]];
-  if (int rc = lins_pose_graph_solve(ctx, ns, s_slots.data(), &prm->graph, solved.data())) return rc;
-  (void)lins_last_pose_graph_stats(ctx, &m->solve_ms, nullptr);
-  for (int i = 0; i < ns; ++i) out[closed[i]].graph = solved[i];
-  if (int rc = lins_pose_graph_apply_batch(ctx, ns, s_slots.data(), s_streams.data())) return rc;
-  for (int i = 0; i < ns; ++i) out[closed[i]].outcome = LINS_LOOP_CLOSED;
-  m->closed = ns;
-  return LINS_OK;
+  if (run.empty()) return LINS_OK;
+  std::vector<lins_loop_icp_result> icp(probs.size());
+  if (int rc = lins_loop_icp_batch_from(ctx, (int)probs.size(), probs.data(), T0.data(), &prm->icp, icp.data())) return rc;
+  (void)lins_last_loop_icp_stats(ctx, &m->icp_ms, nullptr);
+  // ---- choose: the best accepted fit of every entry goes on to the tail ----
+  std::vector<int> judged;  // entries
+  for (size_t a = 0; a < run.size(); ++a) {
+    const int i = run[a], k = cand[i];
+    lins_loop_place_result& o = out[k];
+    lins_loop_step_result& r = o.step;
+    int32_t conv[LINS_PLACE_MAX_K];
+    double fit[LINS_PLACE_MAX_K];
+    int status = 0, ran = 0;
+    for (int j = 0; j < o.n_candidates; ++j) {
+      o.icp[j] = icp[prob0[a] + j];
+      conv[j] = o.icp[j].status ? 0 : o.icp[j].converged, fit[j] = o.icp[j].fitness;  // (a target box beyond the gridding's limit: nothing was run)
+      if (o.icp[j].status && !status) status = o.icp[j].status;
+      ran += o.icp[j].status ? 0 : 1;
+    }
+    if (!o.detect) {  // lins_loop_step's entry
+      r.icp = o.icp[0];
+      if (status) {
+        r.status = status;
+        continue;
+      }
+      o.chosen = lins_loop::choose(1, conv, fit, prm->max_fitness);
+      m->last[k].source = first[i];
+      std::memcpy(m->last[k].T, r.icp.transform, sizeof r.icp.transform);
+      m->aligned += 1;
+      r.outcome = LINS_LOOP_REJECTED;
+      judged.push_back(k);
+      continue;
+    }
+    if (!ran) {
+      r.status = status;
+      continue;
+    }
+    m->aligned += 1;
+    r.outcome = LINS_LOOP_REJECTED;
+    o.chosen = lins_loop::choose(o.n_candidates, conv, fit, prm->max_fitness);
+    if (o.chosen < 0) continue;
+    r.closest_id = o.cand[o.chosen].id, r.history = infos[first[i] + 1 + o.chosen], r.icp = o.icp[o.chosen];
+    m->last[k].source = first[i];
+    std::memcpy(m->last[k].T, r.icp.transform, sizeof r.icp.transform);
+    judged.push_back(k);
+  }
+  return close_loops(ctx, m, prm, slots, streams, judged, out, stride);
 }
 
 int lins_loop_closed_cloud(lins_ctx* ctx, int entry, lins_point* out, int cap) {

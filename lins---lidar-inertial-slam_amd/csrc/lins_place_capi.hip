@@ -39,11 +39,14 @@ int query_check(const ArchivePlace& A, const lins_place_query& q) {
 }
 
 // One call: describes the stale frames of `slots` and of every slot the n queries name, then searches.  keys_row: null, or
-// (n == 1) room for one key per frame of the target slot.  Arguments checked by the caller.
+// (n == 1) room for one key per frame of the target slot.  topk > 0: the search writes every entry's row on the device and
+// the select launch behind it takes the topk best candidates more than min_sep ids apart — results holds n * topk records,
+// rank-major per entry, counts (n) the ranks filled; the row stays on the device.  Arguments checked by the caller.
 int run(lins_ctx* ctx, const ArchivePlace& A, int n_slots_named, const int32_t* slots, int n, const lins_place_query* qs, lins_place_result* results,
-        unsigned long long* keys_row) {
+        unsigned long long* keys_row, int topk = 0, int min_sep = 0, int32_t* counts = nullptr) {
   PlaceStore* m = A.store;
-  m->build_ms = m->search_ms = 0.f, m->pairs = 0, m->built = 0;
+  m->build_ms = m->search_ms = m->select_ms = 0.f, m->pairs = 0, m->built = 0;
+  const bool with_row = keys_row || topk > 0;
   const std::vector<std::vector<ArFrame>>& frames = *A.frames;
   std::vector<int> mark = m->described;  // as they will stand after this call
   std::vector<PlStale> stale;
@@ -75,7 +78,7 @@ int run(lins_ctx* ctx, const ArchivePlace& A, int n_slots_named, const int32_t* 
     e.nf = (int)frames[q.target_slot].size();
     e.skip = q.target_slot == q.query_slot ? q.query_id : -1;
     e.row = row_total;
-    if (keys_row) row_total += e.nf;
+    if (with_row) row_total += e.nf;
     e.chunk0 = (int)chunks.size();
     for (long long c = 0; c < e.nf; c += chunk) {
       if (chunks.size() >= (size_t)INT_MAX) return LINS_E_CAPACITY;
@@ -86,16 +89,17 @@ int run(lins_ctx* ctx, const ArchivePlace& A, int n_slots_named, const int32_t* 
   }
   if (stale.empty() && n == 0) return LINS_OK;
   HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
-  // up: stale | entries | chunks.  down: the entries' keys | the row's keys, and behind them (not downloaded) the chunks' bests
+  // up: stale | entries | chunks.  down: the entries' keys | their top-K keys | the row's keys (downloaded for the test aid
+  // only), and behind them (never downloaded) the chunks' bests
   const size_t o_entries = align64(stale.size() * sizeof(PlStale)), o_chunks = align64(o_entries + (size_t)n * sizeof(PlEntry)),
                up_bytes = align64(o_chunks + chunks.size() * sizeof(int2));
-  const size_t o_row = align64((size_t)n * 8), o_best = align64(o_row + (size_t)row_total * 8), down_bytes = o_best,
-               down_cap = align64(o_best + chunks.size() * 8);
+  const size_t o_top = align64((size_t)n * 8), o_row = align64(o_top + (size_t)n * topk * 8), o_best = align64(o_row + (size_t)row_total * 8),
+               down_bytes = keys_row ? o_best : o_row, down_cap = align64(o_best + chunks.size() * 8);
   BUF_TRY(ctx, m->h_up.grow(up_bytes));
   BUF_TRY(ctx, m->d_up.grow(up_bytes));
   BUF_TRY(ctx, m->h_down.grow(down_bytes));
   BUF_TRY(ctx, m->d_down.grow(down_cap));
-  for (int i = 0; i < 3; ++i) BUF_TRY(ctx, m->ev[i].create());
+  for (int i = 0; i < 4; ++i) BUF_TRY(ctx, m->ev[i].create());
   if (!stale.empty()) std::memcpy(m->h_up, stale.data(), stale.size() * sizeof(PlStale));
   if (n) std::memcpy(m->h_up + o_entries, entries.data(), (size_t)n * sizeof(PlEntry));
   if (!chunks.empty()) std::memcpy(m->h_up + o_chunks, chunks.data(), chunks.size() * sizeof(int2));
@@ -107,25 +111,40 @@ int run(lins_ctx* ctx, const ArchivePlace& A, int n_slots_named, const int32_t* 
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(m->ev[1], st));
   launch_place_search(st, n, (int)chunks.size(), (const PlEntry*)(m->d_up + o_entries), (const int2*)(m->d_up + o_chunks), chunk, m->d_rec,
-                      (unsigned long long*)(m->d_down + o_best), keys_row ? (unsigned long long*)(m->d_down + o_row) : nullptr,
+                      (unsigned long long*)(m->d_down + o_best), with_row ? (unsigned long long*)(m->d_down + o_row) : nullptr,
                       (unsigned long long*)m->d_down.get());
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipEventRecord(m->ev[2], st));
+  if (topk > 0) {
+    launch_place_select(st, n, (const PlEntry*)(m->d_up + o_entries), (const unsigned long long*)(m->d_down + o_row), topk, min_sep,
+                        (unsigned long long*)(m->d_down + o_top));
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(m->ev[3], st));
+  }
   if (n) HIP_TRY(ctx, hipMemcpyAsync(m->h_down, m->d_down, down_bytes, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   HIP_TRY(ctx, hipEventElapsedTime(&m->build_ms, m->ev[0], m->ev[1]));
   HIP_TRY(ctx, hipEventElapsedTime(&m->search_ms, m->ev[1], m->ev[2]));
+  if (topk > 0) HIP_TRY(ctx, hipEventElapsedTime(&m->select_ms, m->ev[2], m->ev[3]));
   m->described = mark;
   m->built = (int)stale.size(), m->pairs = pairs;
   const unsigned long long* K = (const unsigned long long*)m->h_down.get();
+  const unsigned long long* top = (const unsigned long long*)(m->h_down + o_top);
+  const int per = topk > 0 ? topk : 1;
   for (int k = 0; k < n && results; ++k) {
-    lins_place_result& r = results[k];
-    std::memset(&r, 0, sizeof r);
-    r.id = -1, r.shift = 0, r.distance = 1.f;
-    if (K[k] != kNoKey) unpack_key(K[k], &r.distance, &r.id, &r.shift);
+    int admissible = 0;
     const std::vector<ArFrame>& fr = frames[qs[k].target_slot];
     for (int c = 0; c < (int)fr.size(); ++c)
-      if (c != entries[k].skip && time_admits(fr[c].time, qs[k].now, qs[k].min_gap_s)) r.candidates += 1;
+      if (c != entries[k].skip && time_admits(fr[c].time, qs[k].now, qs[k].min_gap_s)) admissible += 1;
+    int filled = 0;
+    for (int j = 0; j < per; ++j) {
+      lins_place_result& r = results[(size_t)k * per + j];
+      const unsigned long long key = topk > 0 ? top[(size_t)k * per + j] : K[k];
+      std::memset(&r, 0, sizeof r);
+      r.id = -1, r.shift = 0, r.distance = 1.f, r.candidates = admissible;
+      if (key != kNoKey) unpack_key(key, &r.distance, &r.id, &r.shift), filled += 1;
+    }
+    if (counts) counts[k] = filled;
   }
   if (keys_row && row_total) std::memcpy(keys_row, m->h_down + o_row, (size_t)row_total * 8);
   return LINS_OK;
@@ -153,7 +172,7 @@ int lins_place_init(lins_ctx* ctx, const lins_place_params* params) {
   BUF_TRY(ctx, m->d_rec.grow(recs * kPlRecWords));
   m->prm = *params;
   m->described.assign(A.n_slots, 0);
-  m->build_ms = m->search_ms = 0.f, m->pairs = 0, m->built = 0;
+  m->build_ms = m->search_ms = m->select_ms = 0.f, m->pairs = 0, m->built = 0;
   m->on = true;
   return LINS_OK;
 }
@@ -174,6 +193,16 @@ int lins_place_search_batch(lins_ctx* ctx, int n, const lins_place_query* querie
   for (int k = 0; k < n; ++k)
     if (int rc = query_check(A, queries[k])) return rc;
   return run(ctx, A, 0, nullptr, n, queries, results, nullptr);
+}
+
+int lins_place_topk_batch(lins_ctx* ctx, int n, const lins_place_query* queries, int k, int min_sep, lins_place_result* results, int32_t* counts) {
+  if (!ctx || n < 0 || (n && (!queries || !results || !counts))) return LINS_E_ARG;
+  ArchivePlace A;
+  if (int rc = store_of(ctx, &A)) return rc;
+  if (k < 1 || k > LINS_PLACE_MAX_K || min_sep < 0) return LINS_E_ARG;
+  for (int i = 0; i < n; ++i)
+    if (int rc = query_check(A, queries[i])) return rc;
+  return run(ctx, A, 0, nullptr, n, queries, results, nullptr, k, min_sep, counts);
 }
 
 int lins_place_descriptor(lins_ctx* ctx, int slot, int id, float* out) {
@@ -214,6 +243,14 @@ int lins_place_set_chunk(lins_ctx* ctx, int chunk) {
   ArchivePlace A;
   if (int rc = archive_place(ctx, &A)) return rc;
   A.store->chunk = chunk ? chunk : kPlChunk;
+  return LINS_OK;
+}
+
+int lins_last_place_select_ms(lins_ctx* ctx, float* select_ms) {
+  if (!ctx) return LINS_E_ARG;
+  ArchivePlace A;
+  if (int rc = archive_place(ctx, &A)) return rc;
+  if (select_ms) *select_ms = A.store->select_ms;
   return LINS_OK;
 }
 

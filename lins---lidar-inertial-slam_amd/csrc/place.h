@@ -23,6 +23,7 @@ constexpr int kPlMaskWord = 1200;   // valid bits: sector s is bit s of the 64-b
 constexpr int kPlTimeWord = 1202;   // the frame's time
 constexpr int kPlBuildBlock = 256;  // threads of the build kernel: the tile of points it takes per step
 constexpr int kPlChunk = 20;        // default candidates per workgroup of the search
+constexpr int kPlSelectBlock = 256; // threads of the top-K select: four waves stride an entry's row
 
 struct PlStale {  // one frame whose descriptor is to be built
   long long src;  // its block in the archive's arena: corner, surf, outlier one after the other
@@ -57,8 +58,8 @@ struct PlaceStore {
   DevBuf<float> d_D, d_rec;
   DevBuf<char> d_up, d_down;  // (bytes)
   PinBuf<char> h_up, h_down;
-  Event ev[3];  // before the build, between build and search, behind the search
-  float build_ms = 0.f, search_ms = 0.f;
+  Event ev[4];  // before the build, between build and search, behind the search, behind the select
+  float build_ms = 0.f, search_ms = 0.f, select_ms = 0.f;
   uint64_t pairs = 0;
   int built = 0;  // frames the last call described
 };

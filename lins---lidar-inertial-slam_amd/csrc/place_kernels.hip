@@ -179,7 +179,55 @@ __global__ __launch_bounds__(64) void place_reduce_kernel(const PlEntry* __restr
   }
 }
 
+// The k best separated candidates of an entry from its row (place_math.h "top-K"): one workgroup per entry, k rounds.  A
+// round: each lane takes the minimum of the row keys it strides over whose candidate `separated` still admits — the ids
+// chosen so far sit in LDS, the same in every lane —, the wave's minimum comes by shuffles on the key's two 32-bit
+// halves, the workgroup's through LDS across the waves; lane 0 publishes the round's winner.  The row is re-read from L2
+// every round (at most 64 KB an entry).  A minimum depends on no order: the bits are select_topk's.  Plain vector stores.
+__global__ __launch_bounds__(kPlSelectBlock) void place_select_kernel(const PlEntry* __restrict__ entries, const unsigned long long* __restrict__ row, int k,
+                                                                      int min_sep, unsigned long long* __restrict__ out) {
+  constexpr int kWaves = kPlSelectBlock / 64;
+  __shared__ unsigned long long part[kWaves];
+  __shared__ unsigned long long winner;
+  __shared__ int chosen[kMaxK];
+  const int tid = threadIdx.x;
+  const PlEntry e = entries[blockIdx.x];
+  const unsigned long long* __restrict__ R = row + e.row;
+  unsigned long long* __restrict__ O = out + (long long)blockIdx.x * k;
+  int j = 0;
+  for (; j < k; ++j) {  // (j and the exit are uniform over the workgroup)
+    unsigned long long best = kNoKey;
+    for (int c = tid; c < e.nf; c += kPlSelectBlock) {
+      const unsigned long long key = R[c];
+      if (key < best && separated(c, chosen, j, min_sep)) best = key;
+    }
+    unsigned hi = (unsigned)(best >> 32), lo = (unsigned)best;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      const unsigned ohi = __shfl_xor(hi, off), olo = __shfl_xor(lo, off);
+      const bool less = ohi < hi || (ohi == hi && olo < lo);
+      hi = less ? ohi : hi, lo = less ? olo : lo;
+    }
+    if ((tid & 63) == 0) part[tid >> 6] = ((unsigned long long)hi << 32) | lo;
+    __syncthreads();
+    if (tid == 0) {
+      unsigned long long w = part[0];
+      for (int i = 1; i < kWaves; ++i) w = part[i] < w ? part[i] : w;
+      winner = w;
+      if (w != kNoKey) chosen[j] = (int)((w & 0xffffffffull) >> 6), O[j] = w;
+    }
+    __syncthreads();  // (winner and chosen[j] are written; part is free for the next round)
+    if (winner == kNoKey) break;
+  }
+  for (int i = j + tid; i < k; i += kPlSelectBlock) O[i] = kNoKey;
+}
+
 }  // namespace
+
+void launch_place_select(hipStream_t s, int n_entries, const PlEntry* entries, const unsigned long long* row, int k, int min_sep,
+                         unsigned long long* out) {
+  if (n_entries > 0) hipLaunchKernelGGL(place_select_kernel, dim3(n_entries), dim3(kPlSelectBlock), 0, s, entries, row, k, min_sep, out);
+}
 
 void launch_place_build(hipStream_t s, int n, const PlStale* stale, const float4* arena, const PlParams& prm, float* D, float* recs) {
   if (n > 0) hipLaunchKernelGGL(place_build_kernel, dim3(n), dim3(kPlBuildBlock), 0, s, stale, arena, prm, D, recs);

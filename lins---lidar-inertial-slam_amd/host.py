@@ -523,6 +523,35 @@ def place_search(query, descs, times, now, min_gap_s, skip_id=-1):
     return dict(id=int(i.value), shift=int(k.value), distance=np.float32(d.value), candidates=int(c.value))
 
 
+def place_topk(query, descs, times, now, min_gap_s, k, min_sep, skip_id=-1, raw=False):
+    """lins_host_place_topk -> (the filled ranks' dicts (id, shift, distance (np.float32)), candidates), or the C return
+    code (a negative int) of a refusal.  raw: all k ranks, the unfilled ones as the call leaves them."""
+    L = lib()
+    q = np.ascontiguousarray(query, np.float32).reshape(1200)
+    n = len(descs)
+    D = np.ascontiguousarray(descs, np.float32).reshape(n, 1200) if n else np.zeros((1, 1200), np.float32)
+    t = np.ascontiguousarray(times, np.float64) if n else np.zeros(1)
+    kk = max(int(k), 1)
+    ids, sh, d, c = np.full(kk, -2, np.int32), np.full(kk, -2, np.int32), np.zeros(kk, np.float32), C.c_int32(0)
+    L.lins_host_place_topk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+    L.lins_host_place_topk.restype = C.c_int
+    rc = L.lins_host_place_topk(q.ctypes.data, D.ctypes.data, t.ctypes.data, n, int(skip_id), float(now), float(min_gap_s), int(k), int(min_sep),
+                                ids.ctypes.data, sh.ctypes.data, d.ctypes.data, C.byref(c))
+    if rc < 0:
+        return rc
+    return [dict(id=int(ids[j]), shift=int(sh[j]), distance=np.float32(d[j])) for j in range(kk if raw else rc)], int(c.value)
+
+
+def loop_choose(converged, fitness, max_fitness=0.3):
+    """lins_host_loop_choose: the rank of the smallest accepted fitness (the lower rank at a tie), -1: none accepted"""
+    L = lib()
+    cv, ft = np.ascontiguousarray(converged, np.int32), np.ascontiguousarray(fitness, np.float64)
+    assert len(cv) == len(ft)
+    L.lins_host_loop_choose.argtypes, L.lins_host_loop_choose.restype = [C.c_int, C.c_void_p, C.c_void_p, C.c_float], C.c_int
+    return int(L.lins_host_loop_choose(len(cv), cv.ctypes.data if len(cv) else None, ft.ctypes.data if len(ft) else None, float(max_fitness)))
+
+
 def place_guess(pose_q, pose_c, shift, up_axis=1):
     """lins_host_place_guess -> T0 (4 x 4 f64), or the C return code of a refusal"""
     from ._ctypes_defs import KeyPoseC, key_pose

@@ -63,6 +63,7 @@ SNAPSHOT_EXPORTS = [
 PLACE_EXPORTS = [
     "lins_place_default_params", "lins_place_init", "lins_place_sync", "lins_place_search_batch", "lins_place_descriptor",
     "lins_place_distances", "lins_place_set_chunk", "lins_last_place_stats", "lins_loop_icp_batch_from",
+    "lins_place_topk_batch", "lins_last_place_select_ms", "lins_loop_place_default_params", "lins_loop_step_place",
 ]
 
 
@@ -133,7 +134,7 @@ def lib():
         for name in LIFECYCLE_EXPORTS + SNAPSHOT_EXPORTS + PLACE_EXPORTS:
             if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                 continue  # (an older build under A/B timing)
-            getattr(L, name).restype = None if name == "lins_place_default_params" else C.c_int
+            getattr(L, name).restype = None if name in ("lins_place_default_params", "lins_loop_place_default_params") else C.c_int
         _LIB = L
     return _LIB
 
@@ -638,6 +639,34 @@ class IeskfContext:
         self._check(rc)
         return [out[k].as_dict() for k in range(n)]
 
+    def place_topk(self, queries, k, min_sep):
+        """lins_place_topk_batch: per query the list of its filled ranks' result dicts (at most k, more than min_sep ids
+        apart); an entry without a rank gives [].  `candidates` of the entry is in each of its dicts — and in
+        self.place_topk_candidates per entry.  Returns the C return code (a negative int) of a refused call."""
+        from ._ctypes_defs import PlaceQueryC, PlaceResultC, place_query
+
+        n = len(queries)
+        arr = (PlaceQueryC * max(n, 1))(*[place_query(*q) for q in queries])
+        out = (PlaceResultC * max(n * max(int(k), 1), 1))()
+        counts = np.zeros(max(n, 1), np.int32)
+        L = lib()
+        L.lins_place_topk_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(PlaceQueryC), C.c_int, C.c_int, C.POINTER(PlaceResultC), C.c_void_p]
+        rc = L.lins_place_topk_batch(self._h, n, arr, int(k), int(min_sep), out, counts.ctypes.data)
+        if rc in (-1, -4, -6):
+            return rc
+        self._check(rc)
+        self.place_topk_candidates = [int(out[e * k].candidates) for e in range(n)]
+        self.place_topk_raw = [[out[e * k + j].as_dict() for j in range(k)] for e in range(n)]  # (the unfilled ranks too)
+        return [[out[e * k + j].as_dict() for j in range(int(counts[e]))] for e in range(n)]
+
+    def place_select_ms(self):
+        """HIP-event ms of the select launch of the last place_topk"""
+        ms = C.c_float(0)
+        L = lib()
+        L.lins_last_place_select_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        self._check(L.lins_last_place_select_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def place_descriptor(self, slot, id):
         """D[ring][sector] of one frame, (20, 60) f32"""
         out = np.zeros((20, 60), np.float32)
@@ -895,6 +924,30 @@ class IeskfContext:
         self._loop_step_sizes = [r["latest"]["n"] for r in res]
         # the step's assembly is the archive's last one: two clouds per entry that had a candidate, in entry order
         self._archive_info = [r[k] for r in res if r["latest"]["frames"] for k in ("latest", "history")]
+        return res
+
+    def loop_step_place(self, entries, params=None, place=None):
+        """lins_loop_step_place: loop_step with the candidates found by appearance.  place: a LoopPlaceParamsC (default:
+        lins_loop_place_default_params).  Returns the per-entry result dicts (step, detect, n_candidates, chosen, cand,
+        icp), or the C return code (a negative int) of a refused call."""
+        from ._ctypes_defs import (LoopPlaceParamsC, LoopPlaceResultC, LoopStepEntryC, LoopStepParamsC, loop_place_params, loop_step_entry,
+                                   loop_step_params)
+
+        L = lib()
+        prm = params if params is not None else loop_step_params(L)
+        pl = place if place is not None else loop_place_params(L)
+        n = len(entries)
+        arr = (LoopStepEntryC * max(n, 1))(*[e if isinstance(e, LoopStepEntryC) else loop_step_entry(*e) for e in entries])
+        out = (LoopPlaceResultC * max(n, 1))()
+        L.lins_loop_step_place.argtypes = [C.c_void_p, C.c_int, C.POINTER(LoopStepEntryC), C.POINTER(LoopStepParamsC), C.POINTER(LoopPlaceParamsC),
+                                           C.POINTER(LoopPlaceResultC)]
+        self._loop_step_sizes = []
+        rc = L.lins_loop_step_place(self._h, n, arr, C.byref(prm), C.byref(pl), out)
+        if rc in (-1, -3, -4, -6):
+            return rc
+        self._check(rc)
+        res = [out[k].as_dict() for k in range(n)]
+        self._loop_step_sizes = [r["step"]["latest"]["n"] for r in res]
         return res
 
     def loop_closed_cloud(self, entry):
