@@ -392,6 +392,11 @@ int lins_host_pose_graph_poses(lins_host_pose_graph* g, int first_id, int n, lin
 int lins_host_pose_graph_count(lins_host_pose_graph* g, int32_t* n_loops);
 int lins_host_pose_graph_poses_f64(lins_host_pose_graph* g, int first_id, int n, double* out); /* n x 12: R row-major, t */
 int lins_host_pose_graph_loop_z(lins_host_pose_graph* g, int loop, double z[12]);
+/* The rebase of include/lins_team.h lins_pose_graph_rebase_batch on the CPU, through the same csrc/pose_graph.h text:
+ * Z[0] <- X Z[0] by one product, every pose formed again by the solve's phase_poses from the increments as they stand.  X: 4 x 4
+ * row-major f64 in the archive's axes.  LINS_E_ARG for a graph without frames, LINS_E_INPUT for an X that lins_team.h refuses;
+ * a refused call changes nothing. */
+int lins_host_pose_graph_rebase(lins_host_pose_graph* g, const double X[16]);
 /* The linearisation at given absolute poses (N x 12; NULL: the estimate), for the finite-difference test: per odometry
  * factor k = 1 .. N - 1 the residual r_odo[6 (k - 1)], the Hessian block D[36 (k - 1)] = J^T Sigma^-1 J and the gradient
  * g[6 (k - 1)] = J^T Sigma^-1 r with respect to the right perturbation of the increment T_{k-1}^-1 T_k; per loop l the
@@ -442,6 +447,53 @@ int lins_host_place_guess(const lins_key_pose* pose_q, const lins_key_pose* pose
 /* lins_host_loop_icp with T_0 given instead of the identity (LINS_E_INPUT when it is not finite) */
 int lins_host_loop_icp_from(const lins_point* source, int n_source, const lins_point* target, int n_target, const double T0[16],
                             const lins_loop_icp_params* prm, int max_rounds, lins_loop_icp_result* out);
+
+/* ---- team search on the CPU (host/place.cpp): the DEFINITION of include/lins_team.h's lins_place_team_topk_batch -----
+ * One query frame against the frames of MANY slots (DESIGN.md §5.3 "Rendezvous"; the scalar text is the lower part of
+ * csrc/host/place_math.h).  Ring key of a frame: occ[r] = the number of sectors with D[r][s] > 0 — it does not change
+ * when the frame turns about the vertical.  Key distance dk = the sum over the rings of (occ_q[r] - occ_c[r])^2, an
+ * integer.  A candidate (s, c) is admissible iff s != query_slot, or c != query_id and fabs(time_c - now) > min_gap_s:
+ * the time gate holds inside the query's own slot only.
+ *   shortlist  the `shortlist` smallest (dk, slot, id) over the admissible candidates of the target slots (fewer when
+ *              fewer exist): a total order, so the list does not depend on the order of the targets
+ *   row key    of the candidate at shortlist position m: the minimum of (d, m, shift) over the shifts, d as
+ *              lins_host_place_distance gives it — equal distances resolve by dk, then slot, then id
+ *   top-K      rank 0 = the minimum row key; rank j = the minimum among the shortlisted candidates that are not in
+ *              conflict with an earlier rank: same slot and |id - id_i| <= min_sep */
+#define LINS_PLACE_MAX_SHORTLIST 64
+#define LINS_PLACE_MAX_TEAM_SLOTS 65536 /* slot numbers a shortlist key holds */
+typedef struct lins_place_team_params {
+  int32_t shortlist; /* 32: candidates that reach the full comparison, in [1, LINS_PLACE_MAX_SHORTLIST] */
+  int32_t k;         /* 4: ranks returned, in [1, LINS_PLACE_MAX_K] */
+  int32_t min_sep;   /* 0: two ranks of one slot lie more than this many ids apart (>= 0) */
+  int32_t reserved;
+} lins_place_team_params;
+void lins_place_team_default_params(lins_place_team_params* p); /* exported by both libraries */
+
+typedef struct lins_place_team_result {
+  int32_t slot, id;   /* -1, -1: the rank is not filled (then shift 0, distance 1, dk -1) */
+  int32_t shift;
+  float distance;
+  int32_t dk;         /* the key distance that shortlisted it */
+  int32_t candidates; /* admissible candidates of the entry, over every target slot */
+  int32_t status;
+  int32_t reserved;
+} lins_place_team_result;
+
+/* query: the descriptor of frame query_id of slot query_slot.  Target t is slot target_slots[t] (each in [0,
+ * LINS_PLACE_MAX_TEAM_SLOTS), no slot twice: LINS_E_ARG) with counts[t] frames, descriptors descs[t] (counts[t] x
+ * LINS_PLACE_CELLS) and times times[t]; counts[t] = 0 is allowed.  out: prm->k records.  Returns the ranks filled (>= 0);
+ * LINS_E_ARG for parameters out of range, LINS_E_INPUT for a NaN gap or a now that is not finite. */
+int lins_host_place_team_topk(const float* query, int query_slot, int query_id, double now, double min_gap_s, int n_targets,
+                              const int32_t* target_slots, const float* const* descs, const double* const* times, const int32_t* counts,
+                              const lins_place_team_params* prm, lins_place_team_result* out);
+/* lins_host_place_guess's formula for lins_rendezvous_step, the poses taken from two slots: T0 takes the query slot's map
+ * frame into the candidate's.  Every sine and cosine comes from one sincos call, so that both libraries form the same
+ * bits whatever their compilers make of adjacent sin and cos calls (lins_host_place_guess's bits differ by an ulp
+ * between the two libraries at some angles, e.g. shift 8). */
+int lins_host_place_team_guess(const lins_key_pose* pose_q, const lins_key_pose* pose_c, int shift, int up_axis, double T0[16]);
+/* the ring key of a descriptor: occ[LINS_PLACE_RINGS] and the sum of their squares */
+int lins_host_place_ring_key(const float* desc, uint8_t occ[LINS_PLACE_RINGS], uint32_t* sumsq);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,146 @@
+/*
+ * lins_team.h — rendezvous: which frame of ANOTHER robot looks like this one (entry points of liblins_ieskf.so;
+ * csrc/lins_team_capi.hip, kernels csrc/team_kernels.hip; the definition is liblins_host.so's
+ * lins_host_place_team_topk of lins_host.h, the scalar text the lower part of csrc/host/place_math.h in both libraries).
+ *
+ * lins_place_search_batch compares a query with every frame of ONE target slot under every yaw shift.  Over a team of
+ * slots that is not affordable, so a team search shortlists first: every frame carries a ring key — per ring the number
+ * of occupied sectors, Scan Context's rotation-invariant ring key kept as integers — and the candidates of every target
+ * slot are ranked by the integer key distance; only the `shortlist` best of them reach the full comparison.  DESIGN.md
+ * section 5.3 "Rendezvous" has the contract and its departures from the paper.
+ *
+ * The ring keys are a second derived mirror inside the place store, 32 bytes a frame (20 occupancy counts, the sum of
+ * their squares, the frame's time), allocated for n_slots x max_frames_per_slot frames by the FIRST team call: a caller
+ * who never searches a team pays nothing.  A slot's keys are dropped exactly where its descriptors are — lins_place_init,
+ * lins_archive_release_slots, a restore — and built again on first use, from the descriptors.
+ *
+ * Conventions: lins_place.h's.  LINS_E_CAPACITY for an archive of more than LINS_PLACE_MAX_TEAM_SLOTS slots.
+ */
+#ifndef LINS_TEAM_H_
+#define LINS_TEAM_H_
+
+#include "lins_place.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct lins_place_team_query {
+  int32_t query_slot, query_id; /* the frame that asks */
+  double now;       /* inside query_slot a candidate c is admissible iff c != query_id and fabs(time_c - now) > min_gap_s; */
+  double min_gap_s; /* a frame of any other slot is always admissible: another robot's frame of the same second is what a rendezvous looks like */
+} lins_place_team_query;
+
+/* n queries against the frames of the n_targets slots of target_slots (one list for the call; it may hold a query's own
+ * slot; no slot twice: LINS_E_ARG; n_targets = 0 or a slot without frames is allowed), bit for bit
+ * lins_host_place_team_topk per query.  results holds n * prm->k records, entry e's ranks at results[e * k ..]; counts[e] is
+ * the number of ranks filled, the records behind them are slot -1, id -1, shift 0, distance 1, dk -1; `candidates` is the
+ * entry's count of admissible candidates in each of its records.
+ * Device sequence: the stale frames of every slot named are described (lins_place_sync's launch), then ONE upload, the
+ * key launch for the frames without a key, the shortlist launch (one workgroup per (query, chunk of the concatenated
+ * candidates)) and its merge (one workgroup per query), the pair launch (the search's column walk over the n * shortlist
+ * (query, candidate) pairs), one download of the n * shortlist shortlist and row keys, one synchronisation; the ranks are
+ * chosen on the host.  An entry's bits depend neither on its batch, nor on the order of the target list, nor on the chunk,
+ * nor on what the context ran before.  n = 0 is LINS_OK. */
+int lins_place_team_topk_batch(lins_ctx* ctx, int n, const lins_place_team_query* queries, int n_targets, const int32_t* target_slots,
+                               const lins_place_team_params* prm, lins_place_team_result* results, int32_t* counts);
+
+/* the ring key of one frame as the device holds it (built on demand) */
+int lins_place_team_key(lins_ctx* ctx, int slot, int id, uint8_t occ[LINS_PLACE_RINGS], uint32_t* sumsq, double* time);
+
+/* test hook, as lins_place_set_chunk: candidates per workgroup of the shortlist launch; 0 = default, values beyond the
+ * default (what the workgroup's LDS holds) are cut to it; results are the same bits for every value >= 1 */
+int lins_place_team_set_chunk(lins_ctx* ctx, int chunk);
+
+/* the last lins_place_team_topk_batch: HIP-event time (ms) of the key launch, of the shortlist launches (with the
+ * merge) and of the pair launch; frames that got a key; (query, candidate) pairs the shortlist scanned — inadmissible ones
+ * included, they are computed and masked */
+int lins_last_place_team_stats(lins_ctx* ctx, float* key_ms, float* shortlist_ms, float* pair_ms, int32_t* frames_keyed, uint64_t* scanned);
+
+/* ---- verification: did the robot of `slot` just see a place another robot has mapped, and how do the two map frames relate ----
+ * The key shortlists, the descriptor ranks, the geometry decides.  Stages, each ONE batched call over the entries that
+ * reach it:
+ *   detect    lins_place_team_topk_batch: query = the slot's latest frame, now = entry.now, min_gap_s = prm->min_gap_s, the
+ *             call's target list; team->min_sep = -1 means prm->search_num.  Ranks with distance > max_distance are dropped.
+ *   assemble  one lins_archive_assemble: per entry the source (its latest frame, corner | surf, leaf 0, DROP_NEGATIVE) and
+ *             one target per surviving rank, lins_host_loop_window(latest frame of the CANDIDATE's slot, id, search_num) at
+ *             history_leaf, assembled from the candidate's slot
+ *   align     one lins_loop_icp_batch_from over every (entry, rank): T0 = lins_host_place_team_guess(stored key pose of the
+ *             query frame, of the candidate frame, shift, the up_axis of lins_place_init) — with the two poses taken from two
+ *             slots it takes the query's map frame into the target's
+ *   choose    lins_host_loop_choose per entry; -1: LINS_RENDEZVOUS_REJECTED
+ * The call reads and changes no pose graph, no ring and no map pose.  An entry's bits are those of the explicit chain of the
+ * four calls for its slot, in any batch and order.  Of prm the call reads max_fitness, history_leaf, search_num, min_gap_s
+ * and icp.
+ * Refusals: LINS_E_STATE before lins_archive_init / lins_place_init; LINS_E_ARG for a slot out of range or named twice among
+ * the entries or among the targets, for parameters out of lins_loop_step's or lins_place_team_topk_batch's ranges
+ * (min_sep < -1) or a NaN max_distance; LINS_E_INPUT for a now that is not finite; LINS_E_CAPACITY when n (1 + k) submaps
+ * exceed what one assembly takes — asked of the most the ranks could ask for, every window as large as the largest target
+ * slot's whole history (a submap of more than INT_MAX / 2 points, more than INT_MAX / 256 tiles of 512 points in the call).  All are asked before anything is queued: a refused call changes nothing. */
+#define LINS_RENDEZVOUS_NONE 0     /* no frame, or no rank within max_distance */
+#define LINS_RENDEZVOUS_REJECTED 1 /* ranks were aligned and none was accepted */
+#define LINS_RENDEZVOUS_FOUND 2
+
+typedef struct lins_rendezvous_entry {
+  int32_t slot; /* the robot that asks: its latest frame is the query */
+  int32_t reserved;
+  double now;
+} lins_rendezvous_entry;
+
+typedef struct lins_rendezvous_params {
+  lins_place_team_params team; /* shortlist 32, k 4, min_sep -1: prm->search_num */
+  float max_distance;          /* 1: distances lie in [0, 1], so the default gates nothing and the ICP is the gate */
+  float pad;
+} lins_rendezvous_params;
+void lins_rendezvous_default_params(lins_rendezvous_params* p);
+
+typedef struct lins_rendezvous_result {
+  int32_t outcome;                /* LINS_RENDEZVOUS_* */
+  int32_t status;                 /* LINS_OK, or the first status of the entry's assemblies / alignments (then nothing is chosen) */
+  int32_t latest_id;              /* the query frame; -1: the slot has no frame */
+  int32_t n_candidates;           /* ranks that went to the alignment */
+  int32_t chosen;                 /* the chosen rank, or -1 */
+  int32_t target_slot, target_id; /* the chosen candidate, or -1, -1 */
+  int32_t reserved;
+  lins_submap_info latest;        /* the source as assembled */
+  lins_place_team_result cand[LINS_PLACE_MAX_K]; /* the surviving ranks, in rank order; behind them slot -1, id -1, shift 0, distance 1, dk -1 */
+  lins_submap_info target[LINS_PLACE_MAX_K];     /* their windows as assembled */
+  lins_loop_icp_result icp[LINS_PLACE_MAX_K];
+  double X[16]; /* FOUND: the chosen alignment, row-major f64 — it takes coordinates of the query slot's map frame to the
+                   target slot's; otherwise zero */
+} lins_rendezvous_result;
+
+int lins_rendezvous_step(lins_ctx* ctx, int n, const lins_rendezvous_entry* entries, int n_targets, const int32_t* target_slots,
+                         const lins_loop_step_params* prm, const lins_rendezvous_params* team, lins_rendezvous_result* out);
+
+/* ---- merge: move a robot's whole history into the frame of the robot it met ----
+ * The pose graph's unknowns are increments and its prior is satisfied exactly, so a change of map frame is a change of the
+ * prior alone.  lins_pose_graph_rebase_batch, for each of the n slots (X + 16 k belongs to slots[k]):
+ *   Z[0] <- X Z[0] in f64, by ONE product (csrc/pose_graph_math.h compose); no increment and no loop measurement is touched,
+ *   so every factor's residual and the cost keep their values up to the rounding of the poses;
+ *   the absolute poses of EVERY frame, frame 0 included, are formed again by the solve's phase_poses in its prefix order,
+ *   through the solve's begin launch (one workgroup per slot) — for a graph without loops as well — and become the estimate
+ *   (f64, and the six floats rounded once); the changed prior is uploaded.
+ * X is 4 x 4 row-major f64 in the archive's axes: those of lins_key_pose's x, y, z, of the clouds, and of
+ * lins_rendezvous_result.X, which can be passed as it is.  The graph's own axes are a permutation of them; the entries of X
+ * are moved, not recomputed.
+ * A graph that was never solved holds the poses as they were PUSHED; after a rebase it holds them COMPOSED from its
+ * measurements.  So a rebase by the identity may move the bits of such a graph (by the rounding of the composition), and it
+ * leaves the bits of a rebased or solved graph's f64 poses only as far as the composition repeats them.
+ * lins_host_pose_graph_rebase (lins_host.h) is the same text on the CPU; device and host differ where libm does.
+ * Refusals, all asked before anything is queued: LINS_E_STATE before lins_pose_graph_init; LINS_E_ARG for a slot out of
+ * range, named twice, or without frames; LINS_E_INPUT for an X with an entry that is not finite, with a last row other than
+ * 0 0 0 1, with |R^T R - I| > 1e-9 in some entry, or with det R <= 0.  n = 0 is LINS_OK. */
+int lins_pose_graph_rebase_batch(lins_ctx* ctx, int n, const int32_t* slots, const double* X);
+
+/* lins_pose_graph_rebase_batch followed by lins_pose_graph_apply_batch(ctx, n, slots, streams): the archive's key poses, the
+ * local map's ring and the map poses of the streams named (streams[k] = -1: none) follow the graph through the code that
+ * follows a solve.  Refusals: the union of the two calls', asked first on the graph as it stands.  The rebased poses
+ * themselves must be ones the archive and the ring take (|x|, |y|, |z| <= 1e6): that is asked of the poses the begin launch
+ * formed, before they are stored — LINS_E_INPUT then, and the graphs, the archive, the rings and the streams are as they were. */
+int lins_team_rebase(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* streams, const double* X);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

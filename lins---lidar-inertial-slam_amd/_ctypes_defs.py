@@ -678,6 +678,81 @@ def loop_place_params(lib, **kw):
     return p
 
 
+# ---- team search (include/lins_team.h, include/lins_host.h lins_host_place_team_topk) ----
+PLACE_MAX_SHORTLIST, PLACE_MAX_TEAM_SLOTS = 64, 65536
+
+
+class PlaceTeamParamsC(C.Structure):
+    _fields_ = [("shortlist", C.c_int32), ("k", C.c_int32), ("min_sep", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PlaceTeamQueryC(C.Structure):
+    _fields_ = [("query_slot", C.c_int32), ("query_id", C.c_int32), ("now", C.c_double), ("min_gap_s", C.c_double)]
+
+
+class PlaceTeamResultC(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("id", C.c_int32), ("shift", C.c_int32), ("distance", C.c_float), ("dk", C.c_int32),
+                ("candidates", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return dict(slot=int(self.slot), id=int(self.id), shift=int(self.shift), distance=np.float32(self.distance), dk=int(self.dk),
+                    candidates=int(self.candidates), status=int(self.status))
+
+
+def place_team_params(lib, **kw):
+    """lins_place_team_default_params of library `lib` with fields overridden by keyword (shortlist=, k=, min_sep=)"""
+    p = PlaceTeamParamsC()
+    lib.lins_place_team_default_params.argtypes = [C.POINTER(PlaceTeamParamsC)]
+    lib.lins_place_team_default_params.restype = None
+    lib.lins_place_team_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"lins_place_team_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+RENDEZVOUS_NONE, RENDEZVOUS_REJECTED, RENDEZVOUS_FOUND = 0, 1, 2
+
+
+class RendezvousEntryC(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("reserved", C.c_int32), ("now", C.c_double)]
+
+
+class RendezvousParamsC(C.Structure):
+    _fields_ = [("team", PlaceTeamParamsC), ("max_distance", C.c_float), ("pad", C.c_float)]
+
+
+class RendezvousResultC(C.Structure):
+    _fields_ = [("outcome", C.c_int32), ("status", C.c_int32), ("latest_id", C.c_int32), ("n_candidates", C.c_int32), ("chosen", C.c_int32),
+                ("target_slot", C.c_int32), ("target_id", C.c_int32), ("reserved", C.c_int32), ("latest", SubmapInfoC),
+                ("cand", PlaceTeamResultC * PLACE_MAX_K), ("target", SubmapInfoC * PLACE_MAX_K), ("icp", LoopIcpResultC * PLACE_MAX_K),
+                ("X", C.c_double * 16)]
+
+    def as_dict(self):
+        n = int(self.n_candidates)
+        return dict(outcome=int(self.outcome), status=int(self.status), latest_id=int(self.latest_id), n_candidates=n, chosen=int(self.chosen),
+                    target_slot=int(self.target_slot), target_id=int(self.target_id), latest=self.latest.as_dict(),
+                    cand=[self.cand[j].as_dict() for j in range(n)], target=[self.target[j].as_dict() for j in range(n)],
+                    icp=[self.icp[j].as_dict() for j in range(n)], X=np.array(self.X[:], np.float64).reshape(4, 4))
+
+
+def rendezvous_params(lib, **kw):
+    """lins_rendezvous_default_params with fields overridden by keyword: shortlist=, k=, min_sep= (of .team), max_distance="""
+    p = RendezvousParamsC()
+    lib.lins_rendezvous_default_params.argtypes = [C.POINTER(RendezvousParamsC)]
+    lib.lins_rendezvous_default_params.restype = None
+    lib.lins_rendezvous_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k == "max_distance":
+            p.max_distance = v
+        elif hasattr(p.team, k):
+            setattr(p.team, k, v)
+        else:
+            raise TypeError(f"lins_rendezvous_params has no field {k}")
+    return p
+
+
 # ---- stream snapshots (include/lins_snapshot.h): the blob's header and records, the plan's records ----
 SNAPSHOT_MAGIC, SNAPSHOT_VERSION = 0x3150414E534E494C, 1
 SNAP_STREAM, SNAP_FILTER, SNAP_BOOT, SNAP_ODOM, SNAP_MAP_POSE, SNAP_RING, SNAP_ARCHIVE, SNAP_GRAPH = (1 << k for k in range(8))

@@ -130,9 +130,83 @@ int lins_host_place_topk(const float* query, const float* descs, const double* t
   return filled;
 }
 
+void lins_place_team_default_params(lins_place_team_params* p) {
+  if (p) team_default_params(p);
+}
+
+int lins_host_place_ring_key(const float* desc, uint8_t* occ, uint32_t* sumsq) {
+  if (!desc || !occ || !sumsq) return LINS_E_ARG;
+  RingKey key;
+  ring_key(desc, 0.0, &key);
+  std::memcpy(occ, key.occ, sizeof key.occ);
+  *sumsq = key.sumsq;
+  return LINS_OK;
+}
+
+int lins_host_place_team_topk(const float* query, int query_slot, int query_id, double now, double min_gap_s, int n_targets,
+                              const int32_t* target_slots, const float* const* descs, const double* const* times, const int32_t* counts,
+                              const lins_place_team_params* prm, lins_place_team_result* out) {
+  if (!query || !out || !team_params_ok(prm) || n_targets < 0 || (n_targets && (!target_slots || !descs || !times || !counts))) return LINS_E_ARG;
+  if (query_slot < 0 || query_slot >= kMaxTeamSlots || query_id < 0 || query_id >= kMaxId) return LINS_E_ARG;
+  for (int t = 0; t < n_targets; ++t) {
+    if (target_slots[t] < 0 || target_slots[t] >= kMaxTeamSlots || counts[t] < 0 || counts[t] > kMaxId) return LINS_E_ARG;
+    if (counts[t] && (!descs[t] || !times[t])) return LINS_E_ARG;
+    for (int u = 0; u < t; ++u)
+      if (target_slots[u] == target_slots[t]) return LINS_E_ARG;
+  }
+  if (!std::isfinite(now) || std::isnan(min_gap_s)) return LINS_E_INPUT;
+  // stage 1: the M smallest shortlist keys, one minimum above the last at a time (the keys are distinct)
+  RingKey kq, kc;
+  ring_key(query, 0.0, &kq);
+  std::vector<unsigned long long> keys;
+  for (int t = 0; t < n_targets; ++t)
+    for (int c = 0; c < counts[t]; ++c) {
+      if (!team_admits(target_slots[t], c, times[t][c], query_slot, query_id, now, min_gap_s)) continue;
+      ring_key(descs[t] + (size_t)c * kCells, times[t][c], &kc);
+      keys.push_back(pack_team_key(key_distance(kq, kc), target_slots[t], c));
+    }
+  const int candidates = (int)keys.size();
+  unsigned long long shortlist[kMaxShortlist], row[kMaxShortlist];
+  int n_short = 0;
+  for (; n_short < prm->shortlist; ++n_short) {
+    unsigned long long best = kNoKey;
+    for (unsigned long long key : keys)
+      if (key < best && (!n_short || key > shortlist[n_short - 1])) best = key;
+    if (best == kNoKey) break;
+    shortlist[n_short] = best;
+  }
+  // stage 2: the row key of every shortlisted candidate
+  std::vector<float> Uq(kCells), Uc(kCells);
+  bool vq[kNS], vc[kNS];
+  float d[kNS];
+  columns_of(query, Uq.data(), vq);
+  for (int m = 0; m < n_short; ++m) {
+    int dk, slot, id, t = 0;
+    unpack_team_key(shortlist[m], &dk, &slot, &id);
+    while (target_slots[t] != slot) ++t;
+    columns_of(descs[t] + (size_t)id * kCells, Uc.data(), vc);
+    distances(Uq.data(), vq, Uc.data(), vc, d);
+    row[m] = kNoKey;
+    for (int s = 0; s < kNS; ++s) {
+      const unsigned long long key = pack_key(d[s], m, s);
+      if (key < row[m]) row[m] = key;
+    }
+  }
+  int pos[kMaxK];
+  const int filled = select_team(row, shortlist, n_short, prm->k, prm->min_sep, pos);
+  team_results(row, shortlist, pos, prm->k, candidates, out);
+  return filled;
+}
+
 int lins_host_place_guess(const lins_key_pose* pose_q, const lins_key_pose* pose_c, int shift, int up_axis, double* T0) {
   if (!pose_q || !pose_c || !T0 || shift < 0 || shift >= kNS || up_axis < 0 || up_axis > 2) return LINS_E_ARG;
   guess(*pose_q, *pose_c, shift, up_axis, T0);
+  return LINS_OK;
+}
+
+int lins_host_place_team_guess(const lins_key_pose* pose_q, const lins_key_pose* pose_c, int shift, int up_axis, double* T0) {
+  if (!pose_q || !pose_c || !T0 || shift < 0 || shift >= kNS || up_axis < 0 || up_axis > 2) return LINS_E_ARG;
+  guess_team(*pose_q, *pose_c, shift, up_axis, T0);
   return LINS_OK;
 }
 

@@ -114,4 +114,105 @@ inline int select_topk(const unsigned long long* row, int n, int k, int min_sep,
 // find_loop's gate (keyframe_select.h): at equality the candidate is not admissible; gap < 0 admits every time
 LINS_HD bool time_admits(double time_c, double now, double gap) { return fabs(time_c - now) > gap; }
 
+// ---- team search (include/lins_team.h; DESIGN.md §5.3 "Rendezvous"): a shortlist over the frames of MANY slots by a
+// rotation-invariant integer key, then the distance text above for the shortlist only.
+//   ring key    occ[r] = the number of sectors s with D[r][s] > 0 — Scan Context's ring key (the mean occupancy of a
+//               ring) kept as an integer; sumsq = the sum of occ[r]^2; the frame's time rides along
+//   key dist    dk = the sum over the rings of (occ_q[r] - occ_c[r])^2: an integer <= 20 * 60^2, the same in any order
+//               and in the form sumsq_q + sumsq_c - 2 dot the device takes
+//   admissible  (s, c) for a query (qs, qid): s != qs, or c != qid and time_admits — the time gate holds inside the
+//               query's own slot only
+//   shortlist   the M smallest (dk << 42) | (slot << 26) | id over the admissible candidates: a total order
+//   row key     of the candidate at shortlist position m: the minimum over the shifts of pack_key(d, m, shift)
+//   top-K       rank 0 = the minimum row key; rank j = the minimum among the positions not in conflict with an earlier
+//               rank: same slot and |id - id_i| <= min_sep (select_team)
+constexpr int kMaxShortlist = 64;        // M of a team search
+constexpr int kMaxTeamSlots = 1 << 16;   // slots a shortlist key holds
+constexpr int kMaxKeyDist = kNR * kNS * kNS;
+
+struct RingKey {
+  uint8_t occ[kNR];
+  uint32_t sumsq;
+  double time;
+};
+static_assert(sizeof(RingKey) == 32, "RingKey layout");
+
+LINS_HD void ring_key(const float* D, double time, RingKey* key) {
+  uint32_t sq = 0;
+  for (int r = 0; r < kNR; ++r) {
+    int occ = 0;
+    for (int s = 0; s < kNS; ++s) occ += D[r * kNS + s] > 0.f ? 1 : 0;
+    key->occ[r] = (uint8_t)occ, sq += (uint32_t)(occ * occ);
+  }
+  key->sumsq = sq, key->time = time;
+}
+
+LINS_HD int key_distance(const RingKey& q, const RingKey& c) {
+  int dk = 0;
+  for (int r = 0; r < kNR; ++r) {
+    const int e = (int)q.occ[r] - (int)c.occ[r];
+    dk += e * e;
+  }
+  return dk;
+}
+
+LINS_HD unsigned long long pack_team_key(int dk, int slot, int id) {
+  return ((unsigned long long)(unsigned)dk << 42) | ((unsigned long long)(unsigned)slot << 26) | (unsigned long long)(unsigned)id;
+}
+LINS_HD void unpack_team_key(unsigned long long key, int* dk, int* slot, int* id) {
+  *dk = (int)(key >> 42), *slot = (int)((key >> 26) & 0xffffull), *id = (int)(key & 0x3ffffffull);
+}
+
+LINS_HD bool team_admits(int slot, int id, double time_c, int query_slot, int query_id, double now, double gap) {
+  return slot != query_slot || (id != query_id && time_admits(time_c, now, gap));
+}
+
+LINS_HD bool team_conflict(int slot_a, int id_a, int slot_b, int id_b, int min_sep) {
+  const int gap = id_a > id_b ? id_a - id_b : id_b - id_a;
+  return slot_a == slot_b && gap <= min_sep;
+}
+
+// row[m] = the row key of shortlist position m, shortlist[m] = its shortlist key (kNoKey: the position is empty), m < n_short.
+// pos[0 .. k): the ranks' shortlist positions, -1 behind the last one filled; returns how many are
+inline int select_team(const unsigned long long* row, const unsigned long long* shortlist, int n_short, int k, int min_sep, int* pos) {
+  int cnt = 0;
+  for (int j = 0; j < k; ++j) pos[j] = -1;
+  while (cnt < k) {
+    unsigned long long best = kNoKey;
+    int at = -1;
+    for (int m = 0; m < n_short; ++m) {
+      if (shortlist[m] == kNoKey || !(row[m] < best)) continue;
+      int dk, slot, id, dk_i, slot_i, id_i;
+      unpack_team_key(shortlist[m], &dk, &slot, &id);
+      bool free_of_all = true;
+      for (int i = 0; i < cnt && free_of_all; ++i) {
+        unpack_team_key(shortlist[pos[i]], &dk_i, &slot_i, &id_i);
+        free_of_all = !team_conflict(slot, id, slot_i, id_i, min_sep);
+      }
+      if (free_of_all) best = row[m], at = m;
+    }
+    if (at < 0) break;
+    pos[cnt++] = at;
+  }
+  return cnt;
+}
+
+// lins_place_team_default_params, the parameter check and the result records of both libraries (host side)
+inline void team_default_params(lins_place_team_params* p) { p->shortlist = 32, p->k = 4, p->min_sep = 0, p->reserved = 0; }
+inline bool team_params_ok(const lins_place_team_params* p) {
+  return p && p->shortlist >= 1 && p->shortlist <= kMaxShortlist && p->k >= 1 && p->k <= kMaxK && p->min_sep >= 0;
+}
+// the k records of one entry from its shortlist keys, its row keys and the positions select_team chose
+inline void team_results(const unsigned long long* row, const unsigned long long* shortlist, const int* pos, int k, int candidates,
+                         lins_place_team_result* out) {
+  for (int j = 0; j < k; ++j) {
+    lins_place_team_result& r = out[j];
+    r.slot = r.id = -1, r.shift = 0, r.distance = 1.f, r.dk = -1, r.candidates = candidates, r.status = 0, r.reserved = 0;
+    if (pos[j] < 0) continue;
+    int m;
+    unpack_key(row[pos[j]], &r.distance, &m, &r.shift);
+    unpack_team_key(shortlist[pos[j]], &r.dk, &r.slot, &r.id);
+  }
+}
+
 }  // namespace lins_place

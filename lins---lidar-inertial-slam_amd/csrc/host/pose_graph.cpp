@@ -83,6 +83,25 @@ int lins_host_pose_graph_solve(lins_host_pose_graph* h, const lins_pose_graph_pa
   return LINS_OK;
 }
 
+int lins_host_pose_graph_rebase(lins_host_pose_graph* h, const double X[16]) {
+  if (!h || !X || h->g.n_frames() == 0) return LINS_E_ARG;
+  if (!rebase_x_ok(X)) return LINS_E_INPUT;
+  Graph& g = h->g;
+  double Xg[12], Z0[12];
+  rebase_x_pose(X, Xg);
+  g.rebased_prior(Xg, Z0);
+  Work w;
+  Prob P = w.prob(g);
+  pose_copy(Z0, P.Z);
+  lins_pose_graph_params prm;
+  default_params(&prm);
+  state_init(w.st, prm);
+  double sh[kShared];
+  solve_begin(HostExec{}, P, sh);  // phase_poses from the increments as they stand, in the solve's prefix order
+  g.store_rebased(Z0, P.T);
+  return LINS_OK;
+}
+
 int lins_host_pose_graph_poses(lins_host_pose_graph* h, int first_id, int n, lins_key_pose* out) {
   if (!h || first_id < 0 || n < 0 || first_id + n > h->g.n_frames() || (n && !out)) return LINS_E_ARG;
   for (int i = 0; i < n; ++i) h->g.key_pose(first_id + i, out + i);

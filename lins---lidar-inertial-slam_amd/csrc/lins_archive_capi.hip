@@ -96,7 +96,7 @@ void stale_at(Archive* m, int slot, int id) { m->stale_from[slot] = std::min(m->
 // so a changed pose — stale_at — or a moved block leaves it)
 void mirrors_drop(Archive* m, int slot) {
   m->stale_from[slot] = 0;
-  if (m->place.on) m->place.described[slot] = 0;
+  if (m->place.on) m->place.described[slot] = 0, m->place.team.drop_slot(slot);
 }
 
 std::vector<lins_key_pose> poses_of(const std::vector<ArFrame>& fr) {
@@ -297,6 +297,7 @@ int lins_archive_init(lins_ctx* ctx, int n_slots, int max_frames_per_slot, long 
   m->n_slots = 0, m->built = false, m->used = 0;
   m->frames.clear();
   m->place.on = false, m->place.described.clear(), m->place.d_D.reset(), m->place.d_rec.reset();  // (sized by lins_place_init)
+  m->place.team.drop();
   BUF_TRY(ctx, m->d_arena.grow((size_t)max_points_total));
   BUF_TRY(ctx, m->d_kp_pose.grow((size_t)n_slots * max_frames_per_slot));
   BUF_TRY(ctx, m->d_kp_time.grow((size_t)n_slots * max_frames_per_slot));

@@ -36,6 +36,9 @@ struct KpOut;
 struct PlStale;    // place.h
 struct PlParams;
 struct PlEntry;
+struct TmStale;
+struct TmTarget;
+struct TmQuery;
 
 // ---- ieskf_kernels.hip: the any-size update kernel (global-memory grid or exhaustive search), re-projection, copy probe
 void launch_persistent(hipStream_t stream, int n, const DevParams& prm, const ScanDesc* descs, const float4* arena, const double* state_in, const double* cov_in, double* state_out, double* cov_out,
@@ -202,6 +205,19 @@ void launch_place_search(hipStream_t s, int n_entries, int n_chunks, const PlEnt
 // to out + entry * k (kNoKey behind the last rank filled)
 void launch_place_select(hipStream_t s, int n_entries, const PlEntry* entries, const unsigned long long* row, int k, int min_sep,
                          unsigned long long* out);
+
+// ---- team_kernels.hip: the team search over the frames of many slots (place.h, the lower part of host/place_math.h)
+// the ring keys of the stale frames, one wave each: two 16-byte words to keys + 2 * rec, read from D + rec * 1200
+void launch_team_keys(hipStream_t s, int n, const TmStale* stale, const float* D, uint4* keys);
+// one workgroup per (query, chunk) over the `total` concatenated candidates of `targets`, `chunk` <= kTmChunk each: the M
+// smallest shortlist keys of the chunk to lists + (query * n_chunks + chunk) * M; then one workgroup per query: the M
+// smallest of its lists to shortlist + query * M (kNoKey behind the last one there is)
+void launch_team_shortlist(hipStream_t s, int n_queries, const TmQuery* queries, int n_targets, const TmTarget* targets, long long total, int chunk,
+                           int n_chunks, int M, const uint4* keys, unsigned long long* lists, unsigned long long* shortlist);
+// one workgroup per (query, ten shortlist positions): the row key of position m to row + query * M + m (kNoKey where the
+// shortlist ends)
+void launch_team_pairs(hipStream_t s, int n_queries, const TmQuery* queries, int M, int max_frames, const unsigned long long* shortlist,
+                       const float* recs, unsigned long long* row);
 
 // ---- pose_graph_kernels.hip: the pose graph's solve, one workgroup per problem (pose_graph.h) ----
 // the poses and the cost of every problem as it stands (the first launch of a solve)

@@ -172,6 +172,7 @@ int lins_place_init(lins_ctx* ctx, const lins_place_params* params) {
   BUF_TRY(ctx, m->d_rec.grow(recs * kPlRecWords));
   m->prm = *params;
   m->described.assign(A.n_slots, 0);
+  m->team.drop();  // (the ring keys are derived from the descriptors: the first team call sizes them again)
   m->build_ms = m->search_ms = m->select_ms = 0.f, m->pairs = 0, m->built = 0;
   m->on = true;
   return LINS_OK;

@@ -13,6 +13,7 @@
 #include "../../include/lins_lifecycle.h"
 #include "../../include/lins_map.h"
 #include "../../include/lins_streams_map.h"
+#include "../../include/lins_team.h"
 #include "host/voxel_map.h"
 #include "lifecycle.h"
 #include "lins_ctx_priv.h"
@@ -381,6 +382,106 @@ int lins_pose_graph_apply_batch(lins_ctx* ctx, int n, const int32_t* slots, cons
     }
   }
   return streams_map_correct(ctx, (int)to.size(), to.data(), six.data());  // LM:1737-1749
+}
+
+}  // extern "C"
+
+namespace {
+
+// what lins_pose_graph_rebase_batch refuses
+int rebase_check(PgMem* m, int n, const int32_t* slots, const double* X) {
+  if (n > m->n_slots) return LINS_E_ARG;
+  for (int k = 0; k < n; ++k) {
+    if (slots[k] < 0 || slots[k] >= m->n_slots || m->g[slots[k]].n_frames() == 0) return LINS_E_ARG;
+    for (int i = 0; i < k; ++i)
+      if (slots[i] == slots[k]) return LINS_E_ARG;
+  }
+  for (int k = 0; k < n; ++k)
+    if (!lins_pg::rebase_x_ok(X + 16 * (size_t)k)) return LINS_E_INPUT;
+  return LINS_OK;
+}
+
+// The rebase of n checked slots.  The device's copy of a slot is brought up to its graph as a solve does it, the new prior
+// goes into row 0 of its Z, the solve's begin launch forms the poses, and they come back.  poses_ok: what the caller
+// goes on to do with the poses takes them (lins_team_rebase: lins_pose_graph_apply_batch's pose_ok); when it does not, the
+// old priors go back into the device's rows — T on the device is written before it is read by every solve — and nothing
+// of the graphs has changed.
+int rebase_run(lins_ctx* ctx, PgMem* m, int n, const int32_t* slots, const double* X, bool poses_ok) {
+  if (n == 0) return LINS_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  hipStream_t st = ctx_stream(ctx);
+  std::vector<Prob> probs(n);
+  std::vector<State> states(n);
+  std::vector<double> Z0(12 * (size_t)n), old(12 * (size_t)n);
+  lins_pose_graph_params prm;
+  lins_pg::default_params(&prm);
+  for (int i = 0; i < n; ++i) {
+    const int slot = slots[i];
+    const Graph& g = m->g[slot];
+    double Xg[12];
+    lins_pg::rebase_x_pose(X + 16 * (size_t)i, Xg);
+    g.rebased_prior(Xg, &Z0[12 * (size_t)i]);
+    lins_pg::pose_copy(g.Z.data(), &old[12 * (size_t)i]);
+    probs[i] = prob_of(m, slot, i);
+    lins_pg::state_init(states[i], prm);
+    const int f0 = m->up_frames[slot], f1 = g.n_frames(), l0 = m->up_loops[slot], l1 = (int)g.loops.size();
+    if (f1 > f0) {
+      HIP_TRY(ctx, hipMemcpyAsync(probs[i].Z + 12 * (size_t)f0, g.Z.data() + 12 * (size_t)f0, 12 * (size_t)(f1 - f0) * sizeof(double), hipMemcpyHostToDevice, st));
+      HIP_TRY(ctx, hipMemcpyAsync(probs[i].D + 12 * (size_t)f0, g.Z.data() + 12 * (size_t)f0, 12 * (size_t)(f1 - f0) * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    if (l1 > l0) HIP_TRY(ctx, hipMemcpyAsync(probs[i].loops + l0, g.loops.data() + l0, (size_t)(l1 - l0) * sizeof(LoopRec), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(probs[i].Z, &Z0[12 * (size_t)i], 12 * sizeof(double), hipMemcpyHostToDevice, st));  // the changed prior
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(m->d_probs, probs.data(), (size_t)n * sizeof(Prob), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(m->d_st, states.data(), (size_t)n * sizeof(State), hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  for (int i = 0; i < n; ++i) m->up_frames[slots[i]] = probs[i].n_frames, m->up_loops[slots[i]] = probs[i].n_loops;
+  launch_pose_graph_begin(st, n, m->d_probs);
+  HIP_TRY(ctx, hipGetLastError());
+  std::vector<std::vector<double>> T(n);
+  for (int i = 0; i < n; ++i) {
+    T[i].resize(12 * (size_t)probs[i].n_frames);
+    HIP_TRY(ctx, hipMemcpyAsync(T[i].data(), probs[i].T, T[i].size() * sizeof(double), hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  bool ok = true;
+  for (int i = 0; i < n && ok && poses_ok; ++i)
+    for (int k = 0; k < probs[i].n_frames && ok; ++k) {
+      float p[6];
+      lins_pg::pose_to6(&T[i][12 * (size_t)k], p);
+      ok = lins_hostmap::pose_ok(lins_key_pose{p[3], p[4], p[5], p[0], p[1], p[2]});
+    }
+  if (!ok) {
+    for (int i = 0; i < n; ++i) HIP_TRY(ctx, hipMemcpyAsync(probs[i].Z, &old[12 * (size_t)i], 12 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return LINS_E_INPUT;
+  }
+  for (int i = 0; i < n; ++i) m->g[slots[i]].store_rebased(&Z0[12 * (size_t)i], T[i].data());
+  return LINS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lins_pose_graph_rebase_batch(lins_ctx* ctx, int n, const int32_t* slots, const double* X) {
+  if (!ctx || n < 0 || (n && (!slots || !X))) return LINS_E_ARG;
+  PgMem* m = mem_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  if (int rc = rebase_check(m, n, slots, X)) return rc;
+  return rebase_run(ctx, m, n, slots, X, false);
+}
+
+int lins_team_rebase(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* streams, const double* X) {
+  if (!ctx || n < 0 || (n && (!slots || !streams || !X))) return LINS_E_ARG;
+  PgMem* m = mem_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  // the union of the two calls' refusals, asked first (the poses as they stand; the rebased ones inside rebase_run)
+  if (int rc = rebase_check(m, n, slots, X)) return rc;
+  if (int rc = pose_graph_apply_check(ctx, n, slots, streams)) return rc;
+  const bool taken = lins_archive_count(ctx, 0) != LINS_E_STATE || local_map_slots(ctx) > 0;  // (what pose_graph_apply_check looks at)
+  if (int rc = rebase_run(ctx, m, n, slots, X, taken)) return rc;
+  return lins_pose_graph_apply_batch(ctx, n, slots, streams);
 }
 
 int lins_pose_graph_apply(lins_ctx* ctx, int slot, int stream) {

@@ -1,0 +1,365 @@
+// lins_team_capi.hip — C ABI of the team search (include/lins_team.h): host orchestration around team_kernels.hip.
+// The ring keys live in the place store (place.h TeamStore), allocated by the first call here.  A call has the stale
+// frames of every slot it names described by lins_place_sync, then packs ONE table — the frames without a key | the
+// queries | the targets —, uploads it, queues the key launch, the shortlist launches and the pair launch, downloads the
+// n * M shortlist keys and the n * M row keys and synchronises once; select_team takes the ranks here.  The marks "keyed
+// below id" move only after that synchronisation.
+// lins_rendezvous_step is host orchestration only, as lins_loop_step_place is: every device stage is a batched call that
+// exists, run ONCE over the entries that reach it.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "../../include/lins_team.h"
+#include "host/loop_step.h"
+#include "host/place_guess.h"
+#include "host/place_math.h"
+#include "keyframe_archive.h"
+#include "lins_ctx_priv.h"
+#include "lins_launch.h"
+#include "local_map.h"
+#include "place.h"
+
+using namespace lins;
+using namespace lins_place;
+
+namespace {
+
+size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
+
+// the store, switched on, of an archive whose slots a shortlist key holds
+int store_of(lins_ctx* ctx, ArchivePlace* A) {
+  if (int rc = archive_place(ctx, A)) return rc;
+  if (!A->store->on) return LINS_E_STATE;
+  return A->n_slots > kMaxTeamSlots ? LINS_E_CAPACITY : LINS_OK;
+}
+
+// the mirror, sized for the archive (the first call after lins_place_init allocates it)
+int keys_ready(lins_ctx* ctx, const ArchivePlace& A) {
+  TeamStore& t = A.store->team;
+  if (!t.keyed.empty()) return LINS_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  BUF_TRY(ctx, t.d_key.grow((size_t)A.n_slots * A.max_frames * 2));
+  t.keyed.assign(A.n_slots, 0);
+  return LINS_OK;
+}
+
+// Describes and keys the stale frames of `slots` and of the queries' slots, then answers the n queries.  Arguments
+// checked by the caller.
+int run(lins_ctx* ctx, const ArchivePlace& A, int n, const lins_place_team_query* qs, int n_targets, const int32_t* slots,
+        const lins_place_team_params& prm, lins_place_team_result* results, int32_t* counts) {
+  TeamStore& t = A.store->team;
+  t.key_ms = t.shortlist_ms = t.pair_ms = 0.f, t.scanned = 0, t.built = 0;
+  const std::vector<std::vector<ArFrame>>& frames = *A.frames;
+  std::vector<int32_t> named(slots, slots + n_targets);
+  for (int k = 0; k < n; ++k) named.push_back(qs[k].query_slot);
+  std::vector<int> mark = t.keyed.empty() ? std::vector<int>((size_t)A.n_slots, 0) : t.keyed;  // as they will stand after this call
+  std::vector<TmStale> stale;
+  for (int32_t s : named) {
+    const std::vector<ArFrame>& fr = frames[s];
+    for (int i = mark[s]; i < (int)fr.size(); ++i) stale.push_back(TmStale{(long long)s * A.max_frames + i, fr[i].time});
+    mark[s] = (int)fr.size();  // (a slot named again in this call adds nothing)
+  }
+  if (stale.size() > (size_t)INT_MAX) return LINS_E_CAPACITY;
+  std::vector<TmTarget> targets((size_t)n_targets);
+  long long total = 0;
+  for (int k = 0; k < n_targets; ++k) {
+    targets[k] = TmTarget{(long long)slots[k] * A.max_frames, total, slots[k], (int)frames[slots[k]].size()};
+    total += targets[k].nf;
+  }
+  const int M = prm.shortlist, chunk = t.chunk;
+  const long long n_chunks = (total + chunk - 1) / chunk;
+  if ((long long)n * n_chunks > INT_MAX || n_chunks * M > INT_MAX) return LINS_E_CAPACITY;
+  if (stale.empty() && n == 0) return LINS_OK;
+  // (every refusal is behind us: from here on only a HIP error ends the call)
+  if (int rc = lins_place_sync(ctx, (int)named.size(), named.data())) return rc;
+  if (int rc = keys_ready(ctx, A)) return rc;
+  std::vector<TmQuery> queries((size_t)n);
+  for (int k = 0; k < n; ++k)
+    queries[k] = TmQuery{(long long)qs[k].query_slot * A.max_frames + qs[k].query_id, qs[k].now, qs[k].min_gap_s, qs[k].query_slot, qs[k].query_id};
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  // up: stale | queries | targets.  down: the shortlists | the rows, and behind them (never downloaded) the chunks' lists
+  const size_t o_queries = align64(stale.size() * sizeof(TmStale)), o_targets = align64(o_queries + (size_t)n * sizeof(TmQuery)),
+               up_bytes = align64(o_targets + (size_t)n_targets * sizeof(TmTarget));
+  const size_t o_row = align64((size_t)n * M * 8), o_lists = align64(o_row + (size_t)n * M * 8), down_bytes = o_lists,
+               down_cap = align64(o_lists + (size_t)n * (size_t)n_chunks * M * 8);
+  BUF_TRY(ctx, t.h_up.grow(up_bytes));
+  BUF_TRY(ctx, t.d_up.grow(up_bytes));
+  BUF_TRY(ctx, t.h_down.grow(down_bytes));
+  BUF_TRY(ctx, t.d_down.grow(down_cap));
+  for (int i = 0; i < 4; ++i) BUF_TRY(ctx, t.ev[i].create());
+  if (!stale.empty()) std::memcpy(t.h_up, stale.data(), stale.size() * sizeof(TmStale));
+  if (n) std::memcpy(t.h_up + o_queries, queries.data(), (size_t)n * sizeof(TmQuery));
+  if (n_targets) std::memcpy(t.h_up + o_targets, targets.data(), (size_t)n_targets * sizeof(TmTarget));
+  hipStream_t st = ctx_stream(ctx);
+  const TmQuery* d_queries = (const TmQuery*)(t.d_up + o_queries);
+  unsigned long long* d_short = (unsigned long long*)t.d_down.get();
+  unsigned long long* d_row = (unsigned long long*)(t.d_down + o_row);
+  HIP_TRY(ctx, hipMemcpyAsync(t.d_up, t.h_up, up_bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipEventRecord(t.ev[0], st));
+  launch_team_keys(st, (int)stale.size(), (const TmStale*)t.d_up.get(), A.store->d_D, t.d_key);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(t.ev[1], st));
+  launch_team_shortlist(st, n, d_queries, n_targets, (const TmTarget*)(t.d_up + o_targets), total, chunk, (int)n_chunks, M, t.d_key,
+                        (unsigned long long*)(t.d_down + o_lists), d_short);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(t.ev[2], st));
+  launch_team_pairs(st, n, d_queries, M, A.max_frames, d_short, A.store->d_rec, d_row);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(t.ev[3], st));
+  if (n) HIP_TRY(ctx, hipMemcpyAsync(t.h_down, t.d_down, down_bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  HIP_TRY(ctx, hipEventElapsedTime(&t.key_ms, t.ev[0], t.ev[1]));
+  HIP_TRY(ctx, hipEventElapsedTime(&t.shortlist_ms, t.ev[1], t.ev[2]));
+  HIP_TRY(ctx, hipEventElapsedTime(&t.pair_ms, t.ev[2], t.ev[3]));
+  t.keyed = mark;
+  t.built = (int)stale.size(), t.scanned = (uint64_t)n * (uint64_t)total;
+  const unsigned long long* S = (const unsigned long long*)t.h_down.get();
+  const unsigned long long* R = (const unsigned long long*)(t.h_down + o_row);
+  for (int k = 0; k < n; ++k) {
+    // admissible candidates: every frame of another slot; of the query's own, those the gate admits
+    long long admissible = 0;
+    for (int j = 0; j < n_targets; ++j) {
+      const std::vector<ArFrame>& fr = frames[slots[j]];
+      if (slots[j] != qs[k].query_slot) {
+        admissible += (long long)fr.size();
+        continue;
+      }
+      for (int c = 0; c < (int)fr.size(); ++c)
+        if (team_admits(slots[j], c, fr[c].time, qs[k].query_slot, qs[k].query_id, qs[k].now, qs[k].min_gap_s)) admissible += 1;
+    }
+    int pos[kMaxK];
+    const int filled = select_team(R + (size_t)k * M, S + (size_t)k * M, M, prm.k, prm.min_sep, pos);
+    team_results(R + (size_t)k * M, S + (size_t)k * M, pos, prm.k, (int)(admissible > INT_MAX ? INT_MAX : admissible), results + (size_t)k * prm.k);
+    counts[k] = filled;
+  }
+  return LINS_OK;
+}
+
+int slots_check(const ArchivePlace& A, int n_targets, const int32_t* slots) {
+  if (n_targets < 0 || (n_targets && !slots)) return LINS_E_ARG;
+  std::vector<char> seen((size_t)A.n_slots, 0);
+  for (int k = 0; k < n_targets; ++k) {
+    if (slots[k] < 0 || slots[k] >= A.n_slots || seen[slots[k]]) return LINS_E_ARG;
+    seen[slots[k]] = 1;
+  }
+  return LINS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void lins_place_team_default_params(lins_place_team_params* p) {
+  if (p) team_default_params(p);
+}
+
+int lins_place_team_topk_batch(lins_ctx* ctx, int n, const lins_place_team_query* queries, int n_targets, const int32_t* target_slots,
+                               const lins_place_team_params* prm, lins_place_team_result* results, int32_t* counts) {
+  if (!ctx || n < 0 || (n && (!queries || !results || !counts))) return LINS_E_ARG;
+  ArchivePlace A;
+  if (int rc = store_of(ctx, &A)) return rc;
+  if (!team_params_ok(prm)) return LINS_E_ARG;
+  if (int rc = slots_check(A, n_targets, target_slots)) return rc;
+  for (int k = 0; k < n; ++k) {
+    const lins_place_team_query& q = queries[k];
+    if (q.query_slot < 0 || q.query_slot >= A.n_slots || q.query_id < 0 || q.query_id >= (int)(*A.frames)[q.query_slot].size()) return LINS_E_ARG;
+  }
+  for (int k = 0; k < n; ++k)
+    if (!std::isfinite(queries[k].now) || std::isnan(queries[k].min_gap_s)) return LINS_E_INPUT;
+  return run(ctx, A, n, queries, n_targets, target_slots, *prm, results, counts);
+}
+
+int lins_place_team_key(lins_ctx* ctx, int slot, int id, uint8_t* occ, uint32_t* sumsq, double* time) {
+  if (!ctx || !occ || !sumsq || !time) return LINS_E_ARG;
+  ArchivePlace A;
+  if (int rc = store_of(ctx, &A)) return rc;
+  if (slot < 0 || slot >= A.n_slots || id < 0 || id >= (int)(*A.frames)[slot].size()) return LINS_E_ARG;
+  const int32_t s = slot;
+  lins_place_team_params prm;
+  team_default_params(&prm);
+  if (int rc = run(ctx, A, 0, nullptr, 1, &s, prm, nullptr, nullptr)) return rc;
+  RingKey key;
+  hipStream_t st = ctx_stream(ctx);
+  HIP_TRY(ctx, hipMemcpyAsync(&key, A.store->team.d_key + ((size_t)slot * A.max_frames + id) * 2, sizeof key, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  std::memcpy(occ, key.occ, sizeof key.occ);
+  *sumsq = key.sumsq, *time = key.time;
+  return LINS_OK;
+}
+
+int lins_place_team_set_chunk(lins_ctx* ctx, int chunk) {
+  if (!ctx || chunk < 0) return LINS_E_ARG;
+  ArchivePlace A;
+  if (int rc = archive_place(ctx, &A)) return rc;
+  A.store->team.chunk = chunk && chunk < kTmChunk ? chunk : kTmChunk;
+  return LINS_OK;
+}
+
+int lins_last_place_team_stats(lins_ctx* ctx, float* key_ms, float* shortlist_ms, float* pair_ms, int32_t* frames_keyed, uint64_t* scanned) {
+  if (!ctx) return LINS_E_ARG;
+  ArchivePlace A;
+  if (int rc = archive_place(ctx, &A)) return rc;
+  const TeamStore& t = A.store->team;
+  if (key_ms) *key_ms = t.key_ms;
+  if (shortlist_ms) *shortlist_ms = t.shortlist_ms;
+  if (pair_ms) *pair_ms = t.pair_ms;
+  if (frames_keyed) *frames_keyed = t.built;
+  if (scanned) *scanned = t.scanned;
+  return LINS_OK;
+}
+
+void lins_rendezvous_default_params(lins_rendezvous_params* p) {
+  if (!p) return;
+  std::memset(p, 0, sizeof *p);
+  team_default_params(&p->team);
+  p->team.min_sep = -1, p->max_distance = 1.f;
+}
+
+int lins_rendezvous_step(lins_ctx* ctx, int n, const lins_rendezvous_entry* entries, int n_targets, const int32_t* target_slots,
+                         const lins_loop_step_params* prm, const lins_rendezvous_params* team, lins_rendezvous_result* out) {
+  if (!ctx || n < 0 || (n && (!entries || !out))) return LINS_E_ARG;
+  ArchivePlace A;
+  if (int rc = store_of(ctx, &A)) return rc;
+  // ---- the whole call's errors, before anything is queued ----
+  if (!prm || !team || std::isnan(prm->max_fitness) || !std::isfinite(prm->history_leaf) || prm->history_leaf < 0.f || prm->search_num < 0 ||
+      std::isnan(prm->min_gap_s) || prm->icp.max_iterations < 1 || prm->icp.min_correspondences < 0 || !std::isfinite(prm->icp.max_corr_dist))
+    return LINS_E_ARG;
+  lins_place_team_params tp = team->team;
+  if (tp.min_sep < -1 || std::isnan(team->max_distance)) return LINS_E_ARG;
+  if (tp.min_sep < 0) tp.min_sep = prm->search_num;
+  if (!team_params_ok(&tp)) return LINS_E_ARG;
+  if (int rc = slots_check(A, n_targets, target_slots)) return rc;
+  for (int k = 0; k < n; ++k) {
+    if (entries[k].slot < 0 || entries[k].slot >= A.n_slots) return LINS_E_ARG;
+    for (int i = 0; i < k; ++i)
+      if (entries[i].slot == entries[k].slot) return LINS_E_ARG;
+  }
+  for (int k = 0; k < n; ++k)
+    if (!std::isfinite(entries[k].now)) return LINS_E_INPUT;
+  const int K = tp.k;
+  if ((long long)n * (1 + K) > 2147483647ll) return LINS_E_CAPACITY;
+  const std::vector<std::vector<ArFrame>>& frames = *A.frames;
+  // what lins_archive_assemble refuses (a submap of more than INT_MAX / 2 points, more than INT_MAX / 256 tiles in a call),
+  // asked of the most the assembly can be given — the ranks are not known yet: every window as large as the largest
+  // target slot's whole history.  So the assembly behind the detect stage cannot refuse.
+  {
+    auto both = [](const ArFrame& f) { return (long long)f.n[0] + f.n[1]; };  // corner | surf
+    long long widest = 0, tiles = 0;
+    for (int t = 0; t < n_targets; ++t) {
+      long long sum = 0;
+      for (const ArFrame& f : frames[target_slots[t]]) sum += both(f);
+      widest = std::max(widest, sum);
+    }
+    if (widest > INT_MAX / 2) return LINS_E_CAPACITY;
+    for (int k = 0; k < n; ++k) {
+      const std::vector<ArFrame>& fr = frames[entries[k].slot];
+      if (fr.empty()) continue;
+      tiles += (both(fr.back()) + kLmTile - 1) / kLmTile + (long long)K * ((widest + kLmTile - 1) / kLmTile);
+    }
+    if (tiles > INT_MAX / 256) return LINS_E_CAPACITY;
+  }
+  // ---- detect: one team search over the entries that have a frame ----
+  std::vector<int> asking;
+  std::vector<lins_place_team_query> qs;
+  for (int k = 0; k < n; ++k) {
+    lins_rendezvous_result& o = out[k];
+    std::memset(&o, 0, sizeof o);
+    o.outcome = LINS_RENDEZVOUS_NONE, o.latest_id = (int)frames[entries[k].slot].size() - 1, o.chosen = o.target_slot = o.target_id = -1;
+    for (int j = 0; j < LINS_PLACE_MAX_K; ++j) o.cand[j].slot = o.cand[j].id = o.cand[j].dk = -1, o.cand[j].distance = 1.f;
+    if (o.latest_id < 0) continue;
+    asking.push_back(k);
+    qs.push_back(lins_place_team_query{entries[k].slot, o.latest_id, entries[k].now, prm->min_gap_s});
+  }
+  if (asking.empty()) return LINS_OK;
+  std::vector<lins_place_team_result> found(qs.size() * (size_t)K);
+  std::vector<int32_t> filled(qs.size(), 0);
+  if (int rc = run(ctx, A, (int)qs.size(), qs.data(), n_targets, target_slots, tp, found.data(), filled.data())) return rc;
+  std::vector<int> cand;  // entries that go to the assembly
+  for (size_t a = 0; a < asking.size(); ++a) {
+    lins_rendezvous_result& o = out[asking[a]];
+    for (int j = 0; j < filled[a]; ++j)
+      if (!(found[a * K + j].distance > team->max_distance)) o.cand[o.n_candidates++] = found[a * K + j];
+    if (o.n_candidates) cand.push_back(asking[a]);
+  }
+  const int nc = (int)cand.size();
+  if (nc == 0) return LINS_OK;
+  // ---- assemble: per entry its latest frame, then one window per rank from the rank's own slot; one call ----
+  std::vector<int> first(nc + 1, 0);  // an entry's first spec (its source)
+  for (int i = 0; i < nc; ++i) first[i + 1] = first[i] + 1 + out[cand[i]].n_candidates;
+  const int n_specs = first[nc];
+  std::vector<std::vector<int32_t>> ids(n_specs);
+  std::vector<lins_submap_spec> specs(n_specs);
+  std::vector<lins_submap_info> infos(n_specs);
+  for (int i = 0; i < nc; ++i) {
+    const lins_rendezvous_result& o = out[cand[i]];
+    const int s0 = first[i];
+    ids[s0].assign(1, o.latest_id);
+    specs[s0] = lins_submap_spec{ids[s0].data(), 1, entries[cand[i]].slot, LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF, LINS_SUBMAP_DROP_NEGATIVE, 0.f, 0};
+    for (int j = 0; j < o.n_candidates; ++j) {
+      const int latest = (int)frames[o.cand[j].slot].size() - 1;
+      std::vector<int32_t>& w = ids[s0 + 1 + j];
+      w.resize(lins_loop::window_size(latest, o.cand[j].id, prm->search_num));
+      lins_loop::window(latest, o.cand[j].id, prm->search_num, w.data());
+      specs[s0 + 1 + j] = lins_submap_spec{w.data(), (int32_t)w.size(), o.cand[j].slot, LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF, 0, prm->history_leaf, 0};
+    }
+  }
+  if (int rc = lins_archive_assemble(ctx, n_specs, specs.data(), infos.data())) return rc;
+  // ---- align: one batch over every (entry, rank) of the entries whose assemblies have no status ----
+  std::vector<int> ran;    // positions in cand
+  std::vector<int> prob0;  // their first problem
+  std::vector<lins_loop_icp_problem> probs;
+  std::vector<double> T0;
+  for (int i = 0; i < nc; ++i) {
+    lins_rendezvous_result& o = out[cand[i]];
+    o.latest = infos[first[i]];
+    int status = o.latest.status;
+    for (int j = 0; j < o.n_candidates; ++j) {
+      o.target[j] = infos[first[i] + 1 + j];
+      if (!status) status = o.target[j].status;
+    }
+    if (status) {  // (the entry's first: nothing is aligned for it)
+      o.status = status;
+      continue;
+    }
+    ran.push_back(i), prob0.push_back((int)probs.size());
+    for (int j = 0; j < o.n_candidates; ++j) {
+      probs.push_back(lins_loop_icp_problem{first[i], first[i] + 1 + j, nullptr, nullptr, 0, 0});
+      T0.resize(T0.size() + 16, 0.0);
+      lins_place::guess_team(frames[entries[cand[i]].slot][o.latest_id].pose, frames[o.cand[j].slot][o.cand[j].id].pose, o.cand[j].shift,
+                        A.store->prm.up_axis, &T0[T0.size() - 16]);
+    }
+  }
+  if (ran.empty()) return LINS_OK;
+  std::vector<lins_loop_icp_result> icp(probs.size());
+  if (int rc = lins_loop_icp_batch_from(ctx, (int)probs.size(), probs.data(), T0.data(), &prm->icp, icp.data())) return rc;
+  // ---- choose ----
+  for (size_t a = 0; a < ran.size(); ++a) {
+    lins_rendezvous_result& o = out[cand[ran[a]]];
+    int32_t conv[LINS_PLACE_MAX_K];
+    double fit[LINS_PLACE_MAX_K];
+    int status = 0, aligned = 0;
+    for (int j = 0; j < o.n_candidates; ++j) {
+      o.icp[j] = icp[prob0[a] + j];
+      conv[j] = o.icp[j].status ? 0 : o.icp[j].converged, fit[j] = o.icp[j].fitness;  // (a target box beyond the gridding's limit: nothing was run)
+      if (o.icp[j].status && !status) status = o.icp[j].status;
+      aligned += o.icp[j].status ? 0 : 1;
+    }
+    if (!aligned) {
+      o.status = status;
+      continue;
+    }
+    o.outcome = LINS_RENDEZVOUS_REJECTED;
+    o.chosen = lins_loop::choose(o.n_candidates, conv, fit, prm->max_fitness);
+    if (o.chosen < 0) continue;
+    o.outcome = LINS_RENDEZVOUS_FOUND, o.target_slot = o.cand[o.chosen].slot, o.target_id = o.cand[o.chosen].id;
+    std::memcpy(o.X, o.icp[o.chosen].transform, sizeof o.X);
+  }
+  return LINS_OK;
+}
+
+}  // extern "C"

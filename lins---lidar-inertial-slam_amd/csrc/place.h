@@ -50,6 +50,47 @@ struct PlEntry {  // one search
 };
 static_assert(sizeof(PlEntry) == 56, "PlEntry layout");
 
+// ---- team search (include/lins_team.h; team_kernels.hip, lins_team_capi.hip): the ring keys, 32 bytes a frame beside
+// its descriptor — lins_place::RingKey, two 16-byte words: occ[0 .. 16) | occ[16 .. 20), sumsq, the frame's time
+constexpr int kTmBlock = 256;     // threads of the key, shortlist and merge kernels
+constexpr int kTmChunk = 2048;    // candidates per workgroup of the shortlist, at most: their keys lie in LDS (16 KB)
+
+struct TmStale {  // one frame whose key is to be built
+  long long rec;  // its record
+  double time;
+};
+static_assert(sizeof(TmStale) == 16, "TmStale layout");
+
+struct TmTarget {  // one target slot of a call
+  long long base;   // its first record
+  long long first;  // the place of its frame 0 among the call's concatenated candidates
+  int slot, nf;
+};
+static_assert(sizeof(TmTarget) == 24, "TmTarget layout");
+
+struct TmQuery {
+  long long q_rec;  // the query's record
+  double now, gap;
+  int slot, id;
+};
+static_assert(sizeof(TmQuery) == 32, "TmQuery layout");
+
+struct TeamStore {
+  std::vector<int> keyed;  // [slot]: ring keys are current below this id; empty until the first team call
+  DevBuf<uint4> d_key;     // two a frame; allocated by the first team call
+  int chunk = kTmChunk;
+  DevBuf<char> d_up, d_down;  // (bytes)
+  PinBuf<char> h_up, h_down;
+  Event ev[4];  // before the keys, between keys and shortlist, between merge and pairs, behind the pairs
+  float key_ms = 0.f, shortlist_ms = 0.f, pair_ms = 0.f;
+  uint64_t scanned = 0;
+  int built = 0;  // frames the last call keyed
+  void drop() { keyed.clear(), d_key.reset(); }
+  void drop_slot(int slot) {
+    if (!keyed.empty()) keyed[slot] = 0;
+  }
+};
+
 struct PlaceStore {
   bool on = false;
   lins_place_params prm{};
@@ -62,6 +103,7 @@ struct PlaceStore {
   float build_ms = 0.f, search_ms = 0.f, select_ms = 0.f;
   uint64_t pairs = 0;
   int built = 0;  // frames the last call described
+  TeamStore team;  // the ring keys: marks drop wherever `described` drops
 };
 
 // (host side) the store and the archive it describes; LINS_E_STATE before lins_archive_init

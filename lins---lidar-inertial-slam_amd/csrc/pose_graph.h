@@ -423,11 +423,49 @@ struct Graph {
       pose_to6(Tsolved + 12 * k, &held[6 * (size_t)k]);
     }
   }
+  // ---- rebase (include/lins_team.h lins_pose_graph_rebase_batch): the whole history moves into another frame by the prior
+  // alone, Z[0] <- X Z[0] — the unknowns are increments and the prior holds exactly, so no factor's residual moves.
+  // the prior a rebase by Xg (a pose in the graph's axes) gives: ONE compose
+  void rebased_prior(const double* Xg, double* Z0) const { compose(Xg, &Z[0], Z0); }
+  // the new prior with the poses phase_poses formed from it, every frame's — frame 0 is the prior and moves with it
+  void store_rebased(const double* Z0, const double* Tnew) {
+    pose_copy(Z0, &Z[0]), pose_copy(Z0, &D[0]);
+    for (int k = 0; k < n_frames(); ++k) {
+      pose_copy(Tnew + 12 * k, &T[12 * (size_t)k]);
+      pose_to6(Tnew + 12 * k, &held[6 * (size_t)k]);
+    }
+  }
   // PointTypePose as LM:1721-1733 assigns it
   void key_pose(int id, lins_key_pose* out) const {
     const float* p = &held[6 * (size_t)id];
     out->x = p[3], out->y = p[4], out->z = p[5], out->roll = p[0], out->pitch = p[1], out->yaw = p[2];
   }
 };
+
+// ---- the X of a rebase: 4 x 4 row-major f64 in the archive's axes — what lins_rendezvous_step returns, the axes of
+// lins_key_pose's x, y, z and of the clouds.  The graph's axes are those permuted (pose_from6: t = (z, x, y) of the key
+// pose), so X in the graph's axes is X's entries moved, exactly.
+// what a rebase accepts (else LINS_E_INPUT): sixteen finite entries, a last row of 0 0 0 1, |R^T R - I| <= 1e-9 in every
+// entry and det R > 0
+inline bool rebase_x_ok(const double* X) {
+  if (!X) return false;
+  for (int i = 0; i < 16; ++i)
+    if (!std::isfinite(X[i])) return false;
+  if (X[12] != 0.0 || X[13] != 0.0 || X[14] != 0.0 || X[15] != 1.0) return false;
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double s = (X[i] * X[j] + X[4 + i] * X[4 + j]) + X[8 + i] * X[8 + j];
+      if (!(std::fabs(s - (i == j ? 1.0 : 0.0)) <= 1e-9)) return false;
+    }
+  const double det = X[0] * (X[5] * X[10] - X[6] * X[9]) - X[1] * (X[4] * X[10] - X[6] * X[8]) + X[2] * (X[4] * X[9] - X[5] * X[8]);
+  return det > 0.0;
+}
+inline void rebase_x_pose(const double* X, double* Xg) {
+  const int archive_of[3] = {2, 0, 1};  // graph axis -> the archive axis that is the same direction
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) Xg[3 * i + j] = X[4 * archive_of[i] + archive_of[j]];
+    Xg[9 + i] = X[4 * archive_of[i] + 3];
+  }
+}
 
 }  // namespace lins_pg

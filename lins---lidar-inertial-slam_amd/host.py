@@ -871,6 +871,13 @@ class PoseGraph:
         n = L.lins_host_pose_graph_count(self._h, C.byref(nl))
         return n, int(nl.value)
 
+    def rebase(self, X):
+        """lins_host_pose_graph_rebase: the history moves into the frame X (4 x 4 f64, the archive's axes) -> the C return code"""
+        L = lib()
+        x = np.ascontiguousarray(X, np.float64).reshape(16)
+        L.lins_host_pose_graph_rebase.argtypes, L.lins_host_pose_graph_rebase.restype = [C.c_void_p, C.c_void_p], C.c_int
+        return L.lins_host_pose_graph_rebase(self._h, x.ctypes.data)
+
     def solve(self, params=None):
         from ._ctypes_defs import PoseGraphParamsC, PoseGraphResultC
 

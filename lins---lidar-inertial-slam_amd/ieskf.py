@@ -65,6 +65,12 @@ PLACE_EXPORTS = [
     "lins_place_distances", "lins_place_set_chunk", "lins_last_place_stats", "lins_loop_icp_batch_from",
     "lins_place_topk_batch", "lins_last_place_select_ms", "lins_loop_place_default_params", "lins_loop_step_place",
 ]
+# the calls of include/lins_team.h (team.py wraps them); lib() resolves every one of them
+TEAM_EXPORTS = [
+    "lins_place_team_default_params", "lins_place_team_topk_batch", "lins_place_team_key", "lins_place_team_set_chunk",
+    "lins_last_place_team_stats", "lins_rendezvous_default_params", "lins_rendezvous_step",
+    "lins_pose_graph_rebase_batch", "lins_team_rebase",
+]
 
 
 class LinsError(RuntimeError):
@@ -131,10 +137,10 @@ def lib():
                 if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                     continue  # (an older build under A/B timing)
                 getattr(L, name).restype = C.c_int
-        for name in LIFECYCLE_EXPORTS + SNAPSHOT_EXPORTS + PLACE_EXPORTS:
+        for name in LIFECYCLE_EXPORTS + SNAPSHOT_EXPORTS + PLACE_EXPORTS + TEAM_EXPORTS:
             if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                 continue  # (an older build under A/B timing)
-            getattr(L, name).restype = None if name in ("lins_place_default_params", "lins_loop_place_default_params") else C.c_int
+            getattr(L, name).restype = None if name.endswith("_default_params") else C.c_int
         _LIB = L
     return _LIB
 

@@ -1,0 +1,165 @@
+"""Rendezvous (include/lins_team.h): the team search over the frames of many slots — the device calls on an
+ieskf.IeskfContext, and their definition on the CPU (include/lins_host.h lins_host_place_team_topk).
+
+A query is (query_slot, query_id, now, min_gap_s); a rank is a dict(slot, id, shift, distance (np.float32), dk,
+candidates, status).  There is no fall-back: the device calls need liblins_ieskf.so and a GPU."""
+import ctypes as C
+
+import numpy as np
+
+from . import host as _host
+from . import ieskf as _ieskf
+from ._ctypes_defs import (PLACE_RINGS, LoopStepParamsC, PlaceTeamParamsC, PlaceTeamQueryC, PlaceTeamResultC, RendezvousEntryC, RendezvousParamsC,
+                           RendezvousResultC, loop_step_params, place_team_params, rendezvous_params)
+
+
+def params(lib=None, **kw):
+    """lins_place_team_default_params (shortlist 32, k 4, min_sep 0) overridden by keyword"""
+    return place_team_params(lib if lib is not None else _host.lib(), **kw)
+
+
+def _raw(out, k, filled):
+    return [out[j].as_dict() for j in range(k)], int(filled)
+
+
+def topk(ctx, queries, target_slots, raw=False, **kw):
+    """lins_place_team_topk_batch on context `ctx`: per query the list of its filled ranks' dicts, or the C return code (a
+    negative int) of a refused call.  raw: per query (all k records, ranks filled).  kw: shortlist=, k=, min_sep=."""
+    L = _ieskf.lib()
+    prm = place_team_params(L, **kw)
+    n, k = len(queries), max(int(prm.k), 1)
+    arr = (PlaceTeamQueryC * max(n, 1))(*[PlaceTeamQueryC(int(s), int(i), float(now), float(gap)) for s, i, now, gap in queries])
+    slots = np.ascontiguousarray(target_slots, np.int32)
+    out = (PlaceTeamResultC * max(n * k, 1))()
+    counts = np.zeros(max(n, 1), np.int32)
+    L.lins_place_team_topk_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(PlaceTeamQueryC), C.c_int, C.c_void_p, C.POINTER(PlaceTeamParamsC),
+                                             C.POINTER(PlaceTeamResultC), C.c_void_p]
+    rc = L.lins_place_team_topk_batch(ctx._h, n, arr, len(slots), slots.ctypes.data if len(slots) else None, C.byref(prm), out, counts.ctypes.data)
+    if rc != 0:
+        return rc
+    res = [_raw(out[e * k:(e + 1) * k], k, counts[e]) for e in range(n)]
+    return res if raw else [r[:f] for r, f in res]
+
+
+def key(ctx, slot, id):
+    """lins_place_team_key -> (occ (20,) uint8, sumsq, time) of one frame as the device holds it"""
+    L = _ieskf.lib()
+    occ, sq, t = np.zeros(PLACE_RINGS, np.uint8), C.c_uint32(0), C.c_double(0)
+    L.lins_place_team_key.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_double)]
+    ctx._check(L.lins_place_team_key(ctx._h, int(slot), int(id), occ.ctypes.data, C.byref(sq), C.byref(t)))
+    return occ, int(sq.value), float(t.value)
+
+
+def set_chunk(ctx, chunk):
+    """lins_place_team_set_chunk (test hook): candidates per workgroup of the shortlist; 0 = default"""
+    L = _ieskf.lib()
+    L.lins_place_team_set_chunk.argtypes = [C.c_void_p, C.c_int]
+    return L.lins_place_team_set_chunk(ctx._h, int(chunk))
+
+
+def stats(ctx):
+    """dict(key_ms, shortlist_ms, pair_ms, frames_keyed, scanned) of the last team search"""
+    L = _ieskf.lib()
+    a, b, c, f, s = C.c_float(0), C.c_float(0), C.c_float(0), C.c_int32(0), C.c_uint64(0)
+    L.lins_last_place_team_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                             C.POINTER(C.c_uint64)]
+    ctx._check(L.lins_last_place_team_stats(ctx._h, C.byref(a), C.byref(b), C.byref(c), C.byref(f), C.byref(s)))
+    return dict(key_ms=a.value, shortlist_ms=b.value, pair_ms=c.value, frames_keyed=int(f.value), scanned=int(s.value))
+
+
+def rendezvous_step(ctx, entries, target_slots, params=None, **kw):
+    """lins_rendezvous_step: entries [(slot, now)] against the frames of target_slots.  params: a LoopStepParamsC (default:
+    lins_loop_step_default_params); kw: shortlist=, k=, min_sep=, max_distance=.  Returns the per-entry result dicts (outcome,
+    status, latest_id, n_candidates, chosen, target_slot, target_id, latest, cand, target, icp, X (4 x 4 f64)), or the C
+    return code (a negative int) of a refused call."""
+    L = _ieskf.lib()
+    prm = params if params is not None else loop_step_params(L)
+    tp = rendezvous_params(L, **kw)
+    n = len(entries)
+    arr = (RendezvousEntryC * max(n, 1))(*[RendezvousEntryC(int(s), 0, float(now)) for s, now in entries])
+    slots = np.ascontiguousarray(target_slots, np.int32)
+    out = (RendezvousResultC * max(n, 1))()
+    L.lins_rendezvous_step.argtypes = [C.c_void_p, C.c_int, C.POINTER(RendezvousEntryC), C.c_int, C.c_void_p, C.POINTER(LoopStepParamsC),
+                                       C.POINTER(RendezvousParamsC), C.POINTER(RendezvousResultC)]
+    rc = L.lins_rendezvous_step(ctx._h, n, arr, len(slots), slots.ctypes.data if len(slots) else None, C.byref(prm), C.byref(tp), out)
+    return [out[k].as_dict() for k in range(n)] if rc == 0 else rc
+
+
+def _xs(X, n):
+    return np.ascontiguousarray(X, np.float64).reshape(n, 16)
+
+
+def pose_graph_rebase(ctx, slots, X):
+    """lins_pose_graph_rebase_batch: the graphs of `slots` move into the frames X (one 4 x 4 f64 per slot, in the archive's
+    axes, as rendezvous_step's X) -> the C return code"""
+    L = _ieskf.lib()
+    s = np.ascontiguousarray(slots, np.int32)
+    x = _xs(X, len(s)) if len(s) else np.zeros((1, 16))
+    L.lins_pose_graph_rebase_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    return L.lins_pose_graph_rebase_batch(ctx._h, len(s), s.ctypes.data if len(s) else None, x.ctypes.data if len(s) else None)
+
+
+def rebase(ctx, slots, X, streams=None):
+    """lins_team_rebase: pose_graph_rebase, then the archive, the ring and the map poses of `streams` (default: none, -1)
+    follow -> the C return code"""
+    L = _ieskf.lib()
+    s = np.ascontiguousarray(slots, np.int32)
+    t = np.ascontiguousarray(streams if streams is not None else [-1] * len(s), np.int32)
+    assert len(t) == len(s)
+    x = _xs(X, len(s)) if len(s) else np.zeros((1, 16))
+    L.lins_team_rebase.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    return L.lins_team_rebase(ctx._h, len(s), s.ctypes.data if len(s) else None, t.ctypes.data if len(s) else None, x.ctypes.data if len(s) else None)
+
+
+# ---- the definition on the CPU ----
+def host_ring_key(desc):
+    """lins_host_place_ring_key -> (occ (20,) uint8, sumsq)"""
+    L = _host.lib()
+    d = np.ascontiguousarray(desc, np.float32).reshape(1200)
+    occ, sq = np.zeros(PLACE_RINGS, np.uint8), C.c_uint32(0)
+    L.lins_host_place_ring_key.argtypes, L.lins_host_place_ring_key.restype = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)], C.c_int
+    rc = L.lins_host_place_ring_key(d.ctypes.data, occ.ctypes.data, C.byref(sq))
+    if rc != 0:
+        raise RuntimeError(f"lins_host_place_ring_key: {rc}")
+    return occ, int(sq.value)
+
+
+def host_guess(pose_q, pose_c, shift, up_axis=1):
+    """lins_host_place_team_guess -> T0 (4 x 4 f64): the start of lins_rendezvous_step's alignments, or the C return code"""
+    from ._ctypes_defs import KeyPoseC, key_pose
+
+    L = _host.lib()
+    T = np.zeros(16, np.float64)
+    pq, pc = key_pose(pose_q), key_pose(pose_c)
+    L.lins_host_place_team_guess.argtypes, L.lins_host_place_team_guess.restype = [C.POINTER(KeyPoseC), C.POINTER(KeyPoseC), C.c_int, C.c_int, C.c_void_p], C.c_int
+    rc = L.lins_host_place_team_guess(C.byref(pq), C.byref(pc), int(shift), int(up_axis), T.ctypes.data)
+    return T.reshape(4, 4) if rc == 0 else rc
+
+
+def host_topk(query, query_slot, query_id, now, min_gap_s, targets, raw=False, **kw):
+    """lins_host_place_team_topk.  targets: [(slot, descs (n x 1200 or a list of (20, 60)), times)] -> the filled ranks'
+    dicts, or the C return code (a negative int) of a refusal.  raw: (all k records, ranks filled)."""
+    L = _host.lib()
+    prm = place_team_params(L, **kw)
+    k, n = max(int(prm.k), 1), len(targets)
+    q = np.ascontiguousarray(query, np.float32).reshape(1200)
+    keep = []
+    slots, cnt = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    dp, tp = (C.c_void_p * max(n, 1))(), (C.c_void_p * max(n, 1))()
+    for t, (slot, descs, times) in enumerate(targets):
+        m = len(descs)
+        D = np.ascontiguousarray(descs, np.float32).reshape(m, 1200) if m else np.zeros((1, 1200), np.float32)
+        T = np.ascontiguousarray(times, np.float64) if m else np.zeros(1)
+        assert len(T) >= m
+        keep += [D, T]
+        slots[t], cnt[t], dp[t], tp[t] = slot, m, D.ctypes.data, T.ctypes.data
+    out = (PlaceTeamResultC * k)()
+    L.lins_host_place_team_topk.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.POINTER(PlaceTeamParamsC), C.POINTER(PlaceTeamResultC)]
+    L.lins_host_place_team_topk.restype = C.c_int
+    rc = L.lins_host_place_team_topk(q.ctypes.data, int(query_slot), int(query_id), float(now), float(min_gap_s), n, slots.ctypes.data, dp, tp,
+                                     cnt.ctypes.data, C.byref(prm), out)
+    if rc < 0:
+        return rc
+    res = _raw(out, k, rc)
+    return res if raw else res[0][:rc]
