@@ -282,6 +282,20 @@ int lins_host_surround_update(int32_t* list, int n_list, int cap, const int32_t*
 int lins_host_surround_map(const lins_keyframe* frames, int n_frames, const int32_t* list, int n_list,
                            const lins_local_scan* scan, lins_point* const* out, lins_local_map_sizes* sizes);
 
+/* ---- the team map on the CPU: the selection over the slots of a team and the surround map over (slot, id) pairs ---------
+ * lins_keyposes_team_select_batch's definition (csrc/host/team_select.h, the same inline code in both libraries; the
+ * contract is in lins_map.h).  Target t is slot slots[t] with the counts[t] key poses at poses[t], by frame id; pairs gets
+ * the survivors as (slot, id), ascending.  Returns their count; LINS_E_ARG for a slot named twice or negative,
+ * LINS_E_INPUT for a pose outside the input contract, LINS_E_CAPACITY for a cell box of more than 2^31 cells or more than
+ * cap survivors (nothing written). */
+int lins_host_team_select(int n_targets, const int32_t* slots, const lins_key_pose* const* poses, const int32_t* counts,
+                          const float centre[3], float radius, float pose_leaf, int32_t* pairs, int cap);
+/* CPU restatement of lins_local_map_build_team for one entry: lins_host_surround_map over the frames the n_pairs
+ * (slot, id) pairs name, in list order (frames[s]: the n_frames[s] frames of slot s by id).  sizes->frames = n_pairs.
+ * LINS_E_ARG for a pair whose slot or id does not exist. */
+int lins_host_team_map(int n_slots, const lins_keyframe* const* frames, const int32_t* n_frames, const int32_t* pairs, int n_pairs,
+                       const lins_local_scan* scan, lins_point* const* out, lins_local_map_sizes* sizes);
+
 /* ---- the loop-closure ICP on the CPU (host/loop_icp.cpp) ---------------------
  * The restatement lins_loop_icp_batch / lins_loop_icp_correspondences are checked against (include/lins_map.h has the
  * contract; the arithmetic is csrc/loop_icp_math.h in both libraries, the search here is the exhaustive one).  Clouds:

@@ -164,6 +164,17 @@ int lins_local_map_build_surround(lins_ctx* ctx, int n, const int32_t* slots, co
                                   const lins_local_scan* scans, lins_local_map_sizes* out);
 int lins_local_map_build_surround_streams(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* const* ids, const int32_t* n_ids,
                                           const int32_t* streams, lins_local_map_sizes* out);
+/* The team map: lins_local_map_build_surround / _surround_streams with each list entry naming its own archive slot.
+ * Entry k's list is the n_pairs[k] (slot, id) pairs at pairs[k] (2 * n_pairs[k] ints) — lins_keyposes_team_select_batch's
+ * output, or any list; slots[k] stays the slot whose scan clouds and resident build the entry is.  The frames are moved
+ * with their archive's current poses, so the slots listed must share a map frame (lins_team_rebase).  The same job table
+ * and launches as the surround build: the bits are those of a surround build over one slot holding the same frames in
+ * list order.  Refusals as the surround build's, plus LINS_E_ARG for a pair whose slot or id does not exist; a refused
+ * call changes nothing. */
+int lins_local_map_build_team(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* const* pairs, const int32_t* n_pairs,
+                              const lins_local_scan* scans, lins_local_map_sizes* out);
+int lins_local_map_build_team_streams(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* const* pairs, const int32_t* n_pairs,
+                                      const int32_t* streams, lins_local_map_sizes* out);
 /* HIP-event time (ms) of the staging kernel of the last lins_local_map_build_streams (part of the build's kernel_ms;
  * 0 after lins_local_map_build) */
 int lins_last_local_map_stage_ms(lins_ctx* ctx, float* stage_ms);
@@ -305,6 +316,38 @@ int lins_keyposes_mode(lins_ctx* ctx); /* LINS_KEYPOSES_* (>= 0) */
 /* of the last batched call: HIP-event time (ms) of its device sequence, the entries the host served, the hits over all
  * entries (0 after lins_keyposes_find_loop_batch, which counts none) */
 int lins_last_keyposes_stats(lins_ctx* ctx, float* device_ms, int32_t* host_entries, uint64_t* hits);
+
+/* ---- the team selection: the key frames of SEVERAL slots around a centre, for a merged local map ---------------------------
+ * Slots whose maps share a frame (after lins_team_rebase, lins_team.h) are a team.  The node's rule cannot be carried
+ * over one: it keeps the truncated mean id of each pose voxel, and a mean of ids of two robots names nothing.  The team
+ * rule is the project's own (csrc/host/team_select.h, the one text both libraries compile; DESIGN.md §5.3 "Team map"):
+ *   candidates  every frame of every target slot (a slot without frames is allowed; a slot named twice is LINS_E_ARG)
+ *   hit         d = (dx dx + dy dy) + dz dz <= radius * radius in f32, uncontracted
+ *   cell        floor(coord * (1 / pose_leaf)) per axis; the box of the hits' cells follows VoxelGrid's 2^31-cell rule
+ *               (beyond it: per-entry LINS_E_CAPACITY, nothing selected)
+ *   thinning    in every occupied cell exactly one hit survives, the one of smallest (d, slot, id)
+ *   output      the survivors as (slot, id) pairs in ascending (slot, id); more than stride: per-entry LINS_E_CAPACITY
+ * A total order decides, so the answer depends neither on the order of the target list nor on the batch, and there is no
+ * list that persists between calls.  Conventions as the calls above (one upload with the stale mirror ranges of every
+ * slot named, one chain of launches, one download, one synchronisation; every refusal before anything is queued; n = 0
+ * is LINS_OK).  One workgroup serves one entry with a table of the occupied cells in LDS: the number of hits is not
+ * bounded, the number of OCCUPIED CELLS is — an entry with more than LINS_KEYPOSES_TEAM_CELLS of them is served by the
+ * host text inside the call (result.host = 1, counted in lins_last_keyposes_team_stats, the same bits). */
+#define LINS_KEYPOSES_TEAM_CELLS 4096
+typedef struct lins_keyposes_team_query {
+  float centre[3];
+  float radius;         /* finite, >= 0 */
+  float pose_leaf;      /* > 0, 1 / pose_leaf finite */
+  int32_t n_targets;    /* >= 0 */
+  int32_t first_target; /* the entry's targets are targets[first_target .. first_target + n_targets) of the call's table */
+  int32_t reserved;
+} lins_keyposes_team_query;
+/* targets: the call's table of n_table slot numbers the queries point into (entries may share a range).  Entry k's
+ * survivors go to pairs + 2 * k * stride as (slot, id), results[k].n of them; results as lins_keyposes_select_batch. */
+int lins_keyposes_team_select_batch(lins_ctx* ctx, int n, const lins_keyposes_team_query* queries, const int32_t* targets, int n_table,
+                                    int32_t* pairs, int stride, lins_keyposes_result* results);
+/* of the last team selection: HIP-event time (ms), the entries the host served, the hits over all entries */
+int lins_last_keyposes_team_stats(lins_ctx* ctx, float* device_ms, int32_t* host_entries, uint64_t* hits);
 
 /* ---- loop-closure alignment: ICP over the archive's submaps (performLoopClosure, LM:1114-1186) ----------------------
  * pcl::IterativeClosestPoint as the mapping node sets it up (LM:1128-1132), restated with a fixed operation sequence:

@@ -14,6 +14,11 @@
  * sections first, then the sections that lie on the device, each 16-byte aligned.  Canonical: no pointers, no arena
  * offsets, no slot index, no uninitialised padding; the same stream state gives the same bytes wherever it lives.
  * The header records the context-wide facts a continuation's bits depend on; a destination that differs in one refuses.
+ * Not in the blob: the team map's settings (lins_streams_map.h lins_streams_map_team and the groups of
+ * lins_streams_map_team_groups).  They are context settings like lins_keyposes_set_mode — which slots share a map frame
+ * is a fact about the destination's other slots, not about the stream — and the team selection keeps no list per
+ * stream, so there is nothing of it to carry: the caller repeats mode and groups on the destination.  The format and
+ * lins_snapshot_facts are unchanged.
  *
  * Conventions of lins_lifecycle.h: LINS_E_STATE before lins_streams_init; LINS_E_ARG for a stream out of range in any
  * initialised module or named twice; n = 0 is LINS_OK.  Everything that can refuse is asked first: a refused call

@@ -87,7 +87,8 @@ int lins_streams_map_set_pose(lins_ctx* ctx, int stream, const lins_map_pose_sta
  *               the other entries form the batch, last_time <- time
  *   associate   transformAssociateToMap on the device from the resident pose
  *   local map   lins_local_map_build_streams for the batch (entry <-> stream, slot = stream); with
- *               lins_streams_map_surround on, the surrounding key frames of the archive instead of the ring
+ *               lins_streams_map_surround on, the surrounding key frames of the archive instead of the ring; with
+ *               lins_streams_map_team on, the selected key frames of every slot of the stream's group
  *   scan2map    lins_scan2map_batch's rounds with LINS_MAP_LOCAL, started where the associate kernel left the transform
  *   finish      transformUpdate if the precondition of LM:1636 held, the key-frame rule, the key pose; one download
  *   key frames  lins_local_map_push_scans and lins_archive_push_scans for the entries with key_frame set, with
@@ -129,6 +130,36 @@ int lins_streams_map_loop(lins_ctx* ctx, int on);
 int lins_streams_map_surround(lins_ctx* ctx, int on, float radius, float pose_leaf);
 /* the stream's surroundingExistingKeyPosesID as the last step left it; returns the count, LINS_E_CAPACITY beyond cap   */
 int lins_streams_map_surround_list(lins_ctx* ctx, int stream, int32_t* ids, int cap);
+/* ---- the team map: scan-to-map over the key frames of every robot met -------------------------------------------------
+ * Slots whose maps share a frame are a group; the caller names the groups after lins_team_rebase (lins_team.h) has moved
+ * one robot's history into the other's frame.  on != 0: the "local map" stage of every gated entry becomes
+ *   targets    the slots of the stream's group (group -1, the default: the slot alone), as many as the archive holds
+ *   centre     the remembered currentRobotPosPoint, as the surround mode takes it
+ *   selection  the team selection's rule (lins_map.h lins_keyposes_team_select_batch: per pose cell of pose_leaf the
+ *              nearest hit within radius, ties by (slot, id)) — one selection for the batch, the batched device call
+ *              under LINS_KEYPOSES_DEVICE, the host text otherwise, the same bits either way
+ *   build      one lins_local_map_build_team_streams over the selected (slot, id) pairs; sizes->frames is the list length
+ * and everything else in the step is unchanged: gate, associate, rounds, finish, the pushes to ring, archive and pose
+ * graph, the result record.  The project's own rule, not the node's (DESIGN.md §5.3 "Team map"): there is no list that
+ * persists between steps — the selection is a pure function of the key poses and the centre — and listed frames are moved
+ * anew from the archive's current poses every step, so a loop closure or a rebase shows in the next map.  A selection
+ * whose box has more than 2^31 cells gives the entry status LINS_E_CAPACITY: it is left out of the batch, its state as it
+ * was.  A slot of the group whose archive holds no frames (never fed, or released) contributes none.
+ * Off by default and again after lins_streams_map_init.  Needs lins_streams_map_init with an archive (LINS_E_STATE).
+ * Exclusive with lins_streams_map_surround (whichever is asked for second gets LINS_E_STATE); compatible with
+ * lins_streams_map_loop — the graph must keep being fed, or there is nothing to rebase.  radius finite and >= 0,
+ * pose_leaf > 0 with a finite inverse (LINS_E_ARG).  lins_streams_map_step_resident and lins_streams_slam_step share the
+ * step's body and get the mode with it.  Mode and groups are context settings, like lins_keyposes_set_mode: they are not
+ * in a snapshot's blob, and the caller repeats them on the destination (lins_snapshot.h). */
+int lins_streams_map_team(lins_ctx* ctx, int on, float radius, float pose_leaf);
+/* slots[k] joins group groups[k] (>= 0), or stands alone again (-1).  lins_streams_map_release, and so
+ * lins_streams_retire, puts a released slot's group back to -1.  LINS_E_ARG for a slot that is no stream or a group < -1
+ * (nothing changes); the mode need not be on. */
+int lins_streams_map_team_groups(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* groups);
+int lins_streams_map_team_group(lins_ctx* ctx, int slot, int32_t* group);
+/* the (slot, id) pairs the stream's last completed team build listed (a record for the caller; an input to nothing);
+ * returns the count of pairs, LINS_E_CAPACITY beyond cap */
+int lins_streams_map_team_list(lins_ctx* ctx, int stream, int32_t* pairs, int cap);
 /* HIP-event times (ms) of the associate and finish kernels of the last step (0 when the step queued none)            */
 int lins_last_streams_map_ms(lins_ctx* ctx, float* associate_ms, float* finish_ms);
 

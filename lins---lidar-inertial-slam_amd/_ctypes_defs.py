@@ -346,6 +346,19 @@ def keyposes_query(slot, centre, radius, pose_leaf=1.0):
     return KeyposesQueryC(int(slot), (C.c_float * 3)(*[float(v) for v in centre]), float(radius), float(pose_leaf))
 
 
+# ---- the team selection (include/lins_map.h lins_keyposes_team_select_batch) -----------------
+KEYPOSES_TEAM_CELLS = 4096
+
+
+class KeyposesTeamQueryC(C.Structure):
+    _fields_ = [("centre", C.c_float * 3), ("radius", C.c_float), ("pose_leaf", C.c_float), ("n_targets", C.c_int32),
+                ("first_target", C.c_int32), ("reserved", C.c_int32)]
+
+
+def keyposes_team_query(centre, radius, pose_leaf, n_targets, first_target):
+    return KeyposesTeamQueryC((C.c_float * 3)(*[float(v) for v in centre]), float(radius), float(pose_leaf), int(n_targets), int(first_target), 0)
+
+
 # ---- the loop-closure ICP (include/lins_map.h lins_loop_icp_*, include/lins_host.h lins_host_loop_icp*) --------
 ICP_NONE, ICP_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE, ICP_NO_CORRESPONDENCES = range(6)
 

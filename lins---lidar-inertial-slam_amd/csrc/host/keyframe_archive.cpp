@@ -7,11 +7,14 @@
 //                                     around the candidate, corner + surf, VoxelGrid 0.4 m
 //   extractSurroundingKeyFrames, loop closure off  LM:1247-1315  the list rule (keyframe_select.h surround_update); the
 //                                     map clouds are two submaps over the list, the scan clouds the local map's
+//   the team map (no counterpart in the node)     the selection over the slots of a team (host/team_select.h) and the
+//                                     surround map over a list of (slot, id) pairs: lins_host_team_select / _team_map
 // The selection is host/keyframe_select.h (one definition for both libraries); transform and VoxelGrid are voxel_map.h.
 #include <vector>
 
 #include "../../../include/lins_host.h"
 #include "keyframe_select.h"
+#include "team_select.h"
 #include "voxel_map.h"
 
 using namespace lins_hostmap;
@@ -129,4 +132,39 @@ extern "C" int lins_host_surround_map(const lins_keyframe* frames, int n_frames,
     for (int c = 2; c < 6; ++c) z.n[c] = 0;
   *sizes = z;
   return LINS_OK;
+}
+
+extern "C" int lins_host_team_select(int n_targets, const int32_t* slots, const lins_key_pose* const* poses, const int32_t* counts,
+                                     const float centre[3], float radius, float pose_leaf, int32_t* pairs, int cap) {
+  if (n_targets < 0 || (n_targets && (!slots || !poses || !counts)) || cap < 0 || !lins_select::query_ok(centre, radius) ||
+      !lins_team_select::leaf_ok(pose_leaf))
+    return LINS_E_ARG;
+  for (int t = 0; t < n_targets; ++t)
+    if (slots[t] < 0 || counts[t] < 0 || (counts[t] && !poses[t])) return LINS_E_ARG;
+  for (int t = 0; t < n_targets; ++t)
+    for (int i = 0; i < counts[t]; ++i)
+      if (!pose_ok(poses[t][i])) return LINS_E_INPUT;
+  std::vector<lins_team_select::Pair> sel;
+  const int rc = lins_team_select::select(n_targets, slots, poses, counts, centre, radius, pose_leaf, sel, nullptr);
+  if (rc == lins_team_select::kDuplicate) return LINS_E_ARG;
+  if (rc == lins_team_select::kTooManyCells || (int)sel.size() > cap) return LINS_E_CAPACITY;
+  if (!sel.empty() && !pairs) return LINS_E_ARG;
+  for (size_t i = 0; i < sel.size(); ++i) pairs[2 * i] = sel[i].slot, pairs[2 * i + 1] = sel[i].id;
+  return (int)sel.size();
+}
+
+extern "C" int lins_host_team_map(int n_slots, const lins_keyframe* const* frames, const int32_t* n_frames, const int32_t* pairs, int n_pairs,
+                                  const lins_local_scan* scan, lins_point* const* out, lins_local_map_sizes* sizes) {
+  if (n_slots < 0 || (n_slots && (!frames || !n_frames)) || n_pairs < 0 || (n_pairs && !pairs)) return LINS_E_ARG;
+  for (int s = 0; s < n_slots; ++s)
+    if (n_frames[s] < 0 || (n_frames[s] && !frames[s])) return LINS_E_ARG;
+  // the listed frames in list order as one frame array: the surround map over ids 0 .. n_pairs - 1 of it
+  std::vector<lins_keyframe> listed((size_t)n_pairs);
+  std::vector<int32_t> ids((size_t)n_pairs);
+  for (int i = 0; i < n_pairs; ++i) {
+    const int32_t slot = pairs[2 * i], id = pairs[2 * i + 1];
+    if (slot < 0 || slot >= n_slots || id < 0 || id >= n_frames[slot]) return LINS_E_ARG;
+    listed[i] = frames[slot][id], ids[i] = i;
+  }
+  return lins_host_surround_map(listed.data(), n_pairs, ids.data(), n_pairs, scan, out, sizes);
 }

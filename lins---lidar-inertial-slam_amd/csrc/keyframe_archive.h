@@ -69,6 +69,12 @@ struct ArchiveStore {
 };
 int archive_store(lins_ctx* ctx, ArchiveStore* v);
 
+// (host side) the team selection's host text (host/team_select.h) over the archive's own key poses, for the callers that
+// select without the device: pairs gets the survivors as (slot, id), flattened.  LINS_OK, LINS_E_CAPACITY (the cell box)
+// or LINS_E_ARG (a slot that is none, or named twice); LINS_E_STATE before lins_archive_init.
+int archive_team_select_host(lins_ctx* ctx, int n_targets, const int32_t* slots, const float centre[3], float radius, float pose_leaf,
+                             std::vector<int32_t>& pairs);
+
 // ---- the key-pose selection on the device (keypose_select_kernels.hip, lins_keyposes_*): the slots' key poses and times
 // have a device mirror, frame id of slot s at s * max_frames + id.  One workgroup serves one entry.
 struct KpStale {  // one frame whose mirror record is out of date
@@ -97,5 +103,30 @@ struct KpOut {
   int pad[3];
 };
 static_assert(sizeof(KpOut) == 32, "KpOut layout");
+
+// ---- the team selection (team_select_kernels.hip, lins_keyposes_team_select_batch; the contract: host/team_select.h).
+// An entry's candidates are the frames of its targets, concatenated in ascending slot order: the candidate at place g
+// is frame g - first of the last target whose first is <= g (a slot without frames shares its successor's place and is
+// passed over).  A place orders as (slot, id).
+constexpr int kTsCells = LINS_KEYPOSES_TEAM_CELLS;  // occupied cells an entry's LDS table serves; above: the host text
+constexpr int kTsSlots = 2 * kTsCells;              // the table's places (open addressing, linear probing)
+
+struct TsTarget {
+  long long base;  // the slot's first record in the mirror
+  int first;       // the place of its frame 0 in the entry's concatenation
+  int slot;
+};
+static_assert(sizeof(TsTarget) == 16, "TsTarget layout");
+
+struct TsEntry {
+  float c[3], r2, inv;  // centre, radius * radius and 1 / pose_leaf as the host forms them
+  int n_targets;
+  int t0;               // the entry's first record in the call's TsTarget table
+  int total;            // candidates: the frames of all targets
+  int stride;           // pairs the entry's output holds
+  int host;             // 1: the host text serves the entry whatever it holds (more candidates than a place can number)
+  int pad[6];
+};
+static_assert(sizeof(TsEntry) == 64, "TsEntry layout");
 
 }  // namespace lins

@@ -15,6 +15,7 @@
 #include "../../include/lins_map.h"
 #include "host/arena_reclaim.h"
 #include "host/keyframe_select.h"
+#include "host/team_select.h"
 #include "keyframe_archive.h"
 #include "keypose_select_math.h"
 #include "lifecycle.h"
@@ -60,6 +61,10 @@ struct Archive {
   int kp_mode = LINS_KEYPOSES_HOST, kp_host = 0;
   float kp_ms = 0.f;
   uint64_t kp_hits = 0;
+  // the team selection (lins_keyposes_team_select_batch): the same mirror and staging; the last call
+  int ts_host = 0;
+  float ts_ms = 0.f;
+  uint64_t ts_hits = 0;
   // the arena's compaction (lins_archive_release_slots): points per pass, the staging buffer of that many points
   // (allocated by the first staged pass), one table up (segments | blocks; pinned staging), the last compaction
   long long reclaim_chunk = kArReclaimChunk;
@@ -123,6 +128,28 @@ int archive_store(lins_ctx* ctx, ArchiveStore* v) {
 }
 
 int archive_slots(lins_ctx* ctx) { return archive_of(ctx)->n_slots; }
+
+int archive_team_select_host(lins_ctx* ctx, int n_targets, const int32_t* slots, const float centre[3], float radius, float pose_leaf,
+                             std::vector<int32_t>& pairs) {
+  Archive* m = archive_of(ctx);
+  pairs.clear();
+  if (!m->n_slots) return LINS_E_STATE;
+  if (n_targets < 0 || !lins_select::query_ok(centre, radius) || !lins_team_select::leaf_ok(pose_leaf)) return LINS_E_ARG;
+  std::vector<std::vector<lins_key_pose>> keep((size_t)n_targets);
+  std::vector<const lins_key_pose*> ptr((size_t)n_targets);
+  std::vector<int32_t> cnt((size_t)n_targets);
+  for (int t = 0; t < n_targets; ++t) {
+    if (slots[t] < 0 || slots[t] >= m->n_slots) return LINS_E_ARG;
+    keep[t] = poses_of(m->frames[slots[t]]);
+    ptr[t] = keep[t].data(), cnt[t] = (int32_t)keep[t].size();
+  }
+  std::vector<lins_team_select::Pair> sel;
+  const int rc = lins_team_select::select(n_targets, slots, ptr.data(), cnt.data(), centre, radius, pose_leaf, sel, nullptr);
+  if (rc == lins_team_select::kDuplicate) return LINS_E_ARG;
+  if (rc == lins_team_select::kTooManyCells) return LINS_E_CAPACITY;
+  for (const lins_team_select::Pair& p : sel) pairs.push_back(p.slot), pairs.push_back(p.id);
+  return LINS_OK;
+}
 
 int archive_place(lins_ctx* ctx, ArchivePlace* v) {
   Archive* m = archive_of(ctx);
@@ -815,6 +842,127 @@ int kp_batch(lins_ctx* ctx, KpKind kind, int n, const lins_keyposes_query* qs, c
   return LINS_OK;
 }
 
+// The team selection, batched: the conventions of kp_batch (the whole call's refusals, one upload: entries | targets |
+// stale mirror records of every slot named, the refresh and one workgroup per entry, one download, one synchronisation);
+// the entries the kernel hands back are served by host/team_select.h here, with the same bits.
+int ts_batch(lins_ctx* ctx, int n, const lins_keyposes_team_query* qs, const int32_t* table, int n_table, int32_t* pairs, int stride,
+             lins_keyposes_result* results) {
+  if (!ctx || n < 0 || n_table < 0 || stride < 0 || (n_table && !table) || (n && (!qs || !results || (stride && !pairs)))) return LINS_E_ARG;
+  Archive* m = archive_of(ctx);
+  if (!m->n_slots) return LINS_E_STATE;
+  for (int t = 0; t < n_table; ++t)
+    if (table[t] < 0 || table[t] >= m->n_slots) return LINS_E_ARG;
+  std::vector<std::vector<int>> order((size_t)n);  // entry k's targets in ascending slot order (positions in its range)
+  size_t n_rec = 0;
+  for (int k = 0; k < n; ++k) {
+    const lins_keyposes_team_query& a = qs[k];
+    if (!lins_select::query_ok(a.centre, a.radius) || !lins_team_select::leaf_ok(a.pose_leaf)) return LINS_E_ARG;
+    if (a.n_targets < 0 || a.first_target < 0 || (long long)a.first_target + a.n_targets > n_table) return LINS_E_ARG;
+    if (!lins_team_select::order_targets(a.n_targets, table + a.first_target, order[k])) return LINS_E_ARG;
+    n_rec += (size_t)a.n_targets;
+  }
+  if (n_rec > (size_t)INT_MAX || (stride && (size_t)n > (size_t)INT_MAX / 2 / (size_t)stride)) return LINS_E_CAPACITY;
+  m->ts_ms = 0.f, m->ts_host = 0, m->ts_hits = 0;
+  if (n == 0) return LINS_OK;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  std::vector<TsEntry> entries((size_t)n);
+  std::vector<TsTarget> recs;
+  std::vector<KpStale> stale;
+  recs.reserve(n_rec);
+  for (int k = 0; k < n; ++k) {
+    const lins_keyposes_team_query& a = qs[k];
+    TsEntry& e = entries[k];
+    std::memset(&e, 0, sizeof e);
+    std::memcpy(e.c, a.centre, sizeof e.c);
+    e.r2 = a.radius * a.radius, e.inv = 1.0f / a.pose_leaf;
+    e.n_targets = a.n_targets, e.t0 = (int)recs.size(), e.stride = stride;
+    long long total = 0;
+    for (int t : order[k]) {
+      const int slot = table[a.first_target + t];
+      const std::vector<ArFrame>& fr = m->frames[slot];
+      const long long base = (long long)slot * m->max_frames;
+      recs.push_back(TsTarget{base, (int)std::min<long long>(total, INT_MAX), slot});
+      total += (long long)fr.size();
+      for (int i = m->stale_from[slot]; i < (int)fr.size(); ++i)
+        stale.push_back(KpStale{fr[i].time, fr[i].pose.x, fr[i].pose.y, fr[i].pose.z, 0, base + i});
+      m->stale_from[slot] = (int)fr.size();  // (a slot named again in this call adds nothing)
+    }
+    e.host = total > INT_MAX;  // (a place is an int; the records of such an entry are not read)
+    e.total = e.host ? 0 : (int)total;
+  }
+  const size_t out_ints = (size_t)n * stride * 2;
+  const size_t o_recs = align64(n * sizeof(TsEntry)), o_stale = align64(o_recs + recs.size() * sizeof(TsTarget)),
+               up_bytes = align64(o_stale + stale.size() * sizeof(KpStale));
+  const size_t o_ints = align64(n * sizeof(KpOut)), down_bytes = align64(o_ints + out_ints * sizeof(int));
+  auto grow_staging = [&]() -> int {
+    BUF_TRY(ctx, m->h_kp_up.grow(up_bytes));
+    BUF_TRY(ctx, m->d_kp_up.grow(up_bytes));
+    BUF_TRY(ctx, m->h_kp_down.grow(down_bytes));
+    BUF_TRY(ctx, m->d_kp_down.grow(down_bytes));
+    return LINS_OK;
+  };
+  if (const int rc = grow_staging()) {
+    std::fill(m->stale_from.begin(), m->stale_from.end(), 0);  // (the records packed above did not go up)
+    return rc;
+  }
+  std::memcpy(m->h_kp_up, entries.data(), n * sizeof(TsEntry));
+  if (!recs.empty()) std::memcpy(m->h_kp_up + o_recs, recs.data(), recs.size() * sizeof(TsTarget));
+  if (!stale.empty()) std::memcpy(m->h_kp_up + o_stale, stale.data(), stale.size() * sizeof(KpStale));
+  hipStream_t st = ctx_stream(ctx);
+  hipEvent_t e0, e1;
+  ctx_events(ctx, &e0, &e1);
+  KpOut* d_out = (KpOut*)m->d_kp_down.get();
+  hipError_t err = hipMemcpyAsync(m->d_kp_up, m->h_kp_up, up_bytes, hipMemcpyHostToDevice, st);
+  if (err == hipSuccess) err = hipEventRecord(e0, st);
+  if (err == hipSuccess) {
+    launch_kp_refresh(st, (int)stale.size(), (const KpStale*)(m->d_kp_up + o_stale), m->d_kp_pose, m->d_kp_time);
+    launch_team_select(st, n, (const TsEntry*)m->d_kp_up.get(), (const TsTarget*)(m->d_kp_up + o_recs), m->d_kp_pose,
+                       (int2*)(m->d_kp_down + o_ints), d_out);
+    err = hipGetLastError();
+  }
+  if (err == hipSuccess) err = hipEventRecord(e1, st);
+  if (err == hipSuccess) err = hipMemcpyAsync(m->h_kp_down, m->d_kp_down, down_bytes, hipMemcpyDeviceToHost, st);
+  if (err == hipSuccess) err = hipStreamSynchronize(st);
+  if (err != hipSuccess) {
+    std::fill(m->stale_from.begin(), m->stale_from.end(), 0);  // (what of the mirror was written is not known)
+    return ctx_fail_hip(ctx, err, "lins_keyposes_team_select_batch");
+  }
+  HIP_TRY(ctx, hipEventElapsedTime(&m->ts_ms, e0, e1));
+  const KpOut* O = (const KpOut*)m->h_kp_down.get();
+  const int* I = (const int*)(m->h_kp_down + o_ints);
+  for (int k = 0; k < n; ++k) {
+    const lins_keyposes_team_query& a = qs[k];
+    lins_keyposes_result& r = results[k];
+    r = lins_keyposes_result{O[k].n, O[k].hits, O[k].status, O[k].host};
+    int32_t* mine = pairs + (size_t)k * stride * 2;
+    if (!O[k].host) {
+      m->ts_hits += (uint64_t)O[k].hits;
+      if (!r.status && r.n) std::memcpy(mine, I + (size_t)k * stride * 2, (size_t)r.n * 2 * sizeof(int));
+      continue;
+    }
+    m->ts_host += 1;  // the host text, with the same bits
+    std::vector<std::vector<lins_key_pose>> keep((size_t)a.n_targets);
+    std::vector<const lins_key_pose*> ptr((size_t)a.n_targets);
+    std::vector<int32_t> cnt((size_t)a.n_targets);
+    for (int t = 0; t < a.n_targets; ++t) {
+      keep[t] = poses_of(m->frames[table[a.first_target + t]]);
+      ptr[t] = keep[t].data(), cnt[t] = (int32_t)keep[t].size();
+    }
+    std::vector<lins_team_select::Pair> sel;
+    long long hits = 0;
+    const int rc = lins_team_select::select(a.n_targets, table + a.first_target, ptr.data(), cnt.data(), a.centre, a.radius, a.pose_leaf, sel, &hits);
+    r.n = 0, r.hits = (int32_t)std::min<long long>(hits, INT_MAX);
+    m->ts_hits += (uint64_t)hits;
+    if (rc != lins_team_select::kOk || (int)sel.size() > stride) {
+      r.status = LINS_E_CAPACITY;
+      continue;
+    }
+    for (size_t i = 0; i < sel.size(); ++i) mine[2 * i] = sel[i].slot, mine[2 * i + 1] = sel[i].id;
+    r.n = (int32_t)sel.size();
+  }
+  return LINS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -839,6 +987,20 @@ int lins_keyposes_set_mode(lins_ctx* ctx, int mode) {
 }
 
 int lins_keyposes_mode(lins_ctx* ctx) { return ctx ? archive_of(ctx)->kp_mode : LINS_E_ARG; }
+
+int lins_keyposes_team_select_batch(lins_ctx* ctx, int n, const lins_keyposes_team_query* queries, const int32_t* targets, int n_table,
+                                    int32_t* pairs, int stride, lins_keyposes_result* results) {
+  return ts_batch(ctx, n, queries, targets, n_table, pairs, stride, results);
+}
+
+int lins_last_keyposes_team_stats(lins_ctx* ctx, float* device_ms, int32_t* host_entries, uint64_t* hits) {
+  if (!ctx) return LINS_E_ARG;
+  Archive* m = archive_of(ctx);
+  if (device_ms) *device_ms = m->ts_ms;
+  if (host_entries) *host_entries = m->ts_host;
+  if (hits) *hits = m->ts_hits;
+  return LINS_OK;
+}
 
 int lins_last_keyposes_stats(lins_ctx* ctx, float* device_ms, int32_t* host_entries, uint64_t* hits) {
   if (!ctx) return LINS_E_ARG;

@@ -33,6 +33,8 @@ struct ArMove;
 struct KpStale;
 struct KpEntry;
 struct KpOut;
+struct TsTarget;
+struct TsEntry;
 struct PlStale;    // place.h
 struct PlParams;
 struct PlEntry;
@@ -193,6 +195,9 @@ void launch_kp_select(hipStream_t s, int n, const KpEntry* entries, const float4
 void launch_kp_surround(hipStream_t s, int n, const KpEntry* entries, const float4* poses, const int* list_in, int* list_out, int* scratch, KpOut* out);
 // the loop candidate: closest[k] = the hit of smallest (d, id) with fabs(time - now) > gap, or -1
 void launch_kp_find_loop(hipStream_t s, int n, const KpEntry* entries, const float4* poses, const double* times, int* closest);
+// ---- team_select_kernels.hip: the key frames of a team of slots around a centre (keyframe_archive.h Ts*, host/team_select.h)
+// one workgroup per entry: entry k's survivors as (slot, id) to pairs + k * stride, ascending
+void launch_team_select(hipStream_t s, int n, const TsEntry* entries, const TsTarget* targets, const float4* poses, int2* pairs, KpOut* out);
 
 // ---- place_kernels.hip: place recognition over the archive's frames (place.h, host/place_math.h)
 // the descriptors of the stale frames, one workgroup each: D to D + dst * 1200, the normalised columns to recs + dst * kPlRecWords

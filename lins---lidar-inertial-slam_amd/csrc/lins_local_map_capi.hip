@@ -98,9 +98,14 @@ size_t align64(size_t x) { return (x + 63) & ~(size_t)63; }
 // the map side of a build: the rings (ids null), or per entry the list ids[k][0 .. n_ids[k]) of frames of the archive
 // slot slots[k], in list order (ar: the store they lie in)
 struct MapSource {
-  const int32_t* const* ids = nullptr;
+  const int32_t* const* ids = nullptr;  // entry k's list: ids of its own slot, or (pairs) (slot, id) pairs
   const int32_t* n_ids = nullptr;
+  bool pairs = false;
   ArchiveStore ar{};
+  // the i-th listed frame of entry k, whose own slot is s
+  const ArFrame& frame(int k, int s, int i) const {
+    return pairs ? (*ar.frames)[ids[k][2 * i]][ids[k][2 * i + 1]] : (*ar.frames)[s][ids[k][i]];
+  }
 };
 
 }  // namespace
@@ -264,7 +269,7 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
     const int s = slots[k];
     frames_of[k] = msrc.ids ? msrc.n_ids[k] : m->count[s];
     for (int i = 0; i < frames_of[k]; ++i) {
-      const int* fn = msrc.ids ? (*msrc.ar.frames)[s][msrc.ids[k][i]].n : m->meta[(size_t)s * m->window + (m->head[s] + i) % m->window].n;
+      const int* fn = msrc.ids ? msrc.frame(k, s, i).n : m->meta[(size_t)s * m->window + (m->head[s] + i) % m->window].n;
       cap[5 * k] += fn[0], cap[5 * k + 1] += (long long)fn[1] + fn[2];
     }
     cap[5 * k + 2] = scan_n(k, 0), cap[5 * k + 3] = scan_n(k, 1), cap[5 * k + 4] = scan_n(k, 2);
@@ -365,7 +370,7 @@ static int local_map_build_impl(lins_ctx* ctx, LocalMap* m, int n, const int32_t
     // ... or the listed archive frames': corner_i -> corner map; surf_i and outlier_i, one behind the other in the arena
     // and under one pose, -> surf map as one segment (LM:1310-1314)
     for (int i = 0; i < frames_of[k] && msrc.ids; ++i) {
-      const ArFrame& f = (*msrc.ar.frames)[s][msrc.ids[k][i]];
+      const ArFrame& f = msrc.frame(k, s, i);
       const long long from_off[2] = {f.off, f.off + f.n[0]};
       const int cnt[2] = {f.n[0], f.n[1] + f.n[2]};
       for (int w = 0; w < 2; ++w) {
@@ -549,6 +554,52 @@ int lins_local_map_build_surround_streams(lins_ctx* ctx, int n, const int32_t* s
   LocalMap* m = local_of(ctx);
   MapSource src;
   if (int rc = surround_source(ctx, m, n, slots, ids, n_ids, &src)) return rc;
+  std::vector<StreamMapClouds> from((size_t)std::max(n, 1));
+  for (int k = 0; k < n; ++k)
+    for (int i = 0; i < k; ++i)
+      if (streams[i] == streams[k]) return LINS_E_ARG;  // (a stream may appear once)
+  for (int k = 0; k < n; ++k)
+    if (int rc = streams_map_clouds(ctx, streams[k], &from[k])) return rc;
+  return local_map_build_impl(ctx, m, n, slots, nullptr, from.data(), src, out);
+}
+
+// the team builds' own arguments: as surround_source, each list entry naming its own archive slot
+static int team_source(lins_ctx* ctx, LocalMap* m, int n, const int32_t* slots, const int32_t* const* pairs, const int32_t* n_pairs, MapSource* src) {
+  if (!m->n_slots) return LINS_E_STATE;
+  if (int rc = archive_store(ctx, &src->ar)) return rc;
+  for (int k = 0; k < n; ++k) {
+    if (slots[k] < 0 || slots[k] >= m->n_slots || slots[k] >= src->ar.n_slots || n_pairs[k] < 0 || (n_pairs[k] && !pairs[k])) return LINS_E_ARG;
+    for (int i = 0; i < n_pairs[k]; ++i) {
+      const int32_t slot = pairs[k][2 * i], id = pairs[k][2 * i + 1];
+      if (slot < 0 || slot >= src->ar.n_slots || id < 0 || id >= (int)(*src->ar.frames)[slot].size()) return LINS_E_ARG;
+    }
+  }
+  src->ids = pairs, src->n_ids = n_pairs, src->pairs = true;
+  return LINS_OK;
+}
+
+int lins_local_map_build_team(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* const* pairs, const int32_t* n_pairs,
+                              const lins_local_scan* scans, lins_local_map_sizes* out) {
+  if (!ctx || n < 0 || (n && (!slots || !pairs || !n_pairs || !scans))) return LINS_E_ARG;
+  LocalMap* m = local_of(ctx);
+  MapSource src;
+  if (int rc = team_source(ctx, m, n, slots, pairs, n_pairs, &src)) return rc;
+  for (int k = 0; k < n; ++k) {
+    const lins_local_scan& s = scans[k];
+    if (s.n_corner < 0 || s.n_surf < 0 || s.n_outlier < 0 || (s.n_corner && !s.corner) || (s.n_surf && !s.surf) ||
+        (s.n_outlier && !s.outlier))
+      return LINS_E_ARG;
+  }
+  static const lins_local_scan none{};
+  return local_map_build_impl(ctx, m, n, slots, n ? scans : &none, nullptr, src, out);
+}
+
+int lins_local_map_build_team_streams(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* const* pairs, const int32_t* n_pairs,
+                                      const int32_t* streams, lins_local_map_sizes* out) {
+  if (!ctx || n < 0 || (n && (!slots || !pairs || !n_pairs || !streams))) return LINS_E_ARG;
+  LocalMap* m = local_of(ctx);
+  MapSource src;
+  if (int rc = team_source(ctx, m, n, slots, pairs, n_pairs, &src)) return rc;
   std::vector<StreamMapClouds> from((size_t)std::max(n, 1));
   for (int k = 0; k < n; ++k)
     for (int i = 0; i < k; ++i)

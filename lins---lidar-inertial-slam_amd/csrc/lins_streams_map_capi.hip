@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstddef>
 #include <cstring>
@@ -14,6 +15,7 @@
 #include "../../include/lins_map.h"
 #include "../../include/lins_streams_map.h"
 #include "host/keyframe_select.h"
+#include "keyframe_archive.h"
 #include "lifecycle.h"
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
@@ -49,6 +51,13 @@ struct StreamsMap {
   bool surround = false;
   float radius = 50.f, pose_leaf = 1.f;
   std::vector<std::vector<int>> lists;  // [n] surroundingExistingKeyPosesID
+  // lins_streams_map_team: the local map is the team selection over the slots of the stream's group.  A context setting
+  // like the modes above; the selection is a pure function of the key poses and the centre, so nothing persists per
+  // stream but the record of the last list (read back by lins_streams_map_team_list, an input to nothing)
+  bool team = false;
+  float team_radius = 50.f, team_leaf = 1.f;
+  std::vector<int32_t> groups;                       // [n] >= 0: the slots of one map frame; -1: the slot alone
+  std::vector<std::vector<int32_t>> team_lists;      // [n] (slot, id) pairs of the stream's last build
   // a write-back's batch (lins_pose_graph_apply_batch): n entries at most
   DevBuf<MapPoseFix> d_fix;
   PinBuf<MapPoseFix> h_fix;
@@ -62,7 +71,7 @@ void step_buffers_free(StreamsMap* m) {
   m->d_poses.reset(), m->d_entries.reset(), m->d_out.reset(), m->d_fix.reset();
   m->h_entries.reset(), m->h_out.reset(), m->h_fix.reset();
   m->n = 0;
-  m->loop = m->surround = false;
+  m->loop = m->surround = m->team = false;
 }
 
 void streams_map_free(void* p) { delete (StreamsMap*)p; }
@@ -130,6 +139,7 @@ int streams_map_release_apply(lins_ctx* ctx, int n, const int32_t* streams) {
     m->stepped[s] = 0;
     std::fill(m->last6.begin() + 6 * s, m->last6.begin() + 6 * s + 6, 0.f);
     m->lists[s].clear();
+    m->groups[s] = -1, m->team_lists[s].clear();
   }
   if (n) HIP_TRY(ctx, hipStreamSynchronize(st));
   return LINS_OK;
@@ -240,6 +250,7 @@ int lins_streams_map_init(lins_ctx* ctx, int n_streams, double process_interval)
   m->centre.assign(3 * (size_t)n_streams, 0.f), m->stepped.assign((size_t)n_streams, 0);
   m->last6.assign(6 * (size_t)n_streams, 0.f);
   m->lists.assign((size_t)n_streams, {});
+  m->groups.assign((size_t)n_streams, -1), m->team_lists.assign((size_t)n_streams, {});
   m->interval = process_interval;
   m->use_archive = lins_archive_count(ctx, 0) >= 0;
   m->associate_ms = m->finish_ms = 0.f;
@@ -312,7 +323,7 @@ int lins_streams_map_surround(lins_ctx* ctx, int on, float radius, float pose_le
     return LINS_OK;
   }
   if (!std::isfinite(radius) || radius < 0.f || !(pose_leaf > 0.f) || !std::isfinite(pose_leaf)) return LINS_E_ARG;
-  if (m->loop || !m->use_archive) return LINS_E_STATE;
+  if (m->loop || m->team || !m->use_archive) return LINS_E_STATE;
   for (int s = 0; s < m->n; ++s)
     if (lins_archive_count(ctx, s) < 0) return LINS_E_STATE;  // (an archive re-sized below the streams: no such slot)
   for (std::vector<int>& l : m->lists) l.clear();
@@ -330,6 +341,54 @@ int lins_streams_map_surround_list(lins_ctx* ctx, int stream, int32_t* ids, int 
   if (!l.empty() && !ids) return LINS_E_ARG;
   for (size_t i = 0; i < l.size(); ++i) ids[i] = l[i];
   return (int)l.size();
+}
+
+int lins_streams_map_team(lins_ctx* ctx, int on, float radius, float pose_leaf) {
+  if (!ctx) return LINS_E_ARG;
+  StreamsMap* m = state_of(ctx);
+  if (!m->n) return LINS_E_STATE;
+  if (!on) {
+    m->team = false;
+    return LINS_OK;
+  }
+  if (!std::isfinite(radius) || radius < 0.f || !(pose_leaf > 0.f) || !std::isfinite(1.0f / pose_leaf)) return LINS_E_ARG;
+  if (m->surround || !m->use_archive) return LINS_E_STATE;
+  for (int s = 0; s < m->n; ++s)
+    if (lins_archive_count(ctx, s) < 0) return LINS_E_STATE;  // (an archive re-sized below the streams: no such slot)
+  for (std::vector<int32_t>& l : m->team_lists) l.clear();
+  m->team = true, m->team_radius = radius, m->team_leaf = pose_leaf;
+  return LINS_OK;
+}
+
+int lins_streams_map_team_groups(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* groups) {
+  if (!ctx || n < 0 || (n && (!slots || !groups))) return LINS_E_ARG;
+  StreamsMap* m = state_of(ctx);
+  if (!m->n) return LINS_E_STATE;
+  for (int k = 0; k < n; ++k)
+    if (slots[k] < 0 || slots[k] >= m->n || groups[k] < -1) return LINS_E_ARG;
+  for (int k = 0; k < n; ++k) m->groups[slots[k]] = groups[k];
+  return LINS_OK;
+}
+
+int lins_streams_map_team_group(lins_ctx* ctx, int slot, int32_t* group) {
+  if (!ctx || !group) return LINS_E_ARG;
+  StreamsMap* m = state_of(ctx);
+  if (!m->n) return LINS_E_STATE;
+  if (slot < 0 || slot >= m->n) return LINS_E_ARG;
+  *group = m->groups[slot];
+  return LINS_OK;
+}
+
+int lins_streams_map_team_list(lins_ctx* ctx, int stream, int32_t* pairs, int cap) {
+  if (!ctx || cap < 0) return LINS_E_ARG;
+  StreamsMap* m = state_of(ctx);
+  if (!m->n) return LINS_E_STATE;
+  if (stream < 0 || stream >= m->n) return LINS_E_ARG;
+  const std::vector<int32_t>& l = m->team_lists[stream];
+  if ((int)(l.size() / 2) > cap) return LINS_E_CAPACITY;
+  if (!l.empty() && !pairs) return LINS_E_ARG;
+  std::copy(l.begin(), l.end(), pairs);
+  return (int)(l.size() / 2);
 }
 
 int lins_streams_map_step(lins_ctx* ctx, int n, const int32_t* streams, const lins_map_odom* odom, lins_map_step_result* out) {
@@ -393,9 +452,61 @@ int lins::streams_map_step_run(lins_ctx* ctx, int n, const int32_t* streams, con
     }
     if (int rc = lins_keyposes_surround_batch(ctx, nq, qs.data(), dev_lists.data(), dev_stride, dev_n.data(), dev_res.data())) return rc;
   }
+  // team mode: the targets of every gated entry are the slots of its stream's group, the centre the remembered
+  // currentRobotPosPoint; one selection for the batch — the batched device call or the host text, the same bits
+  std::vector<int> team_at(m->team ? (size_t)n : 0, -1);  // position k of the call -> its entry of the selection
+  std::vector<std::vector<int32_t>> team_sel;             // per selection entry: its (slot, id) pairs
+  std::vector<int> team_status;
+  if (m->team) {
+    std::vector<lins_keyposes_team_query> qs;
+    std::vector<int32_t> table;
+    long long stride = 1;
+    for (int k = 0; k < n; ++k) {
+      if (gate(k)) continue;
+      const int s = streams[k];
+      lins_keyposes_team_query q{{m->centre[3 * (size_t)s], m->centre[3 * (size_t)s + 1], m->centre[3 * (size_t)s + 2]}, m->team_radius, m->team_leaf,
+                                 0, (int32_t)table.size(), 0};
+      long long frames = 0;
+      for (int t = 0; t < m->n; ++t) {
+        if (t != s && (m->groups[s] < 0 || m->groups[t] != m->groups[s])) continue;
+        const int have = lins_archive_count(ctx, t);
+        if (have < 0) return LINS_E_STATE;
+        table.push_back(t), q.n_targets += 1, frames += have;
+      }
+      stride = std::max(stride, frames);
+      team_at[k] = (int)qs.size();
+      qs.push_back(q);
+    }
+    const int nq = (int)qs.size();
+    team_sel.resize((size_t)nq), team_status.assign((size_t)nq, LINS_OK);
+    if (nq && lins_keyposes_mode(ctx) == LINS_KEYPOSES_DEVICE) {
+      if (stride > INT_MAX / 2 / nq) return LINS_E_CAPACITY;
+      std::vector<int32_t> pairs((size_t)nq * (size_t)stride * 2);
+      std::vector<lins_keyposes_result> res((size_t)nq);
+      if (int rc = lins_keyposes_team_select_batch(ctx, nq, qs.data(), table.data(), (int)table.size(), pairs.data(), (int)stride, res.data())) return rc;
+      for (int j = 0; j < nq; ++j) {
+        team_status[j] = res[j].status;
+        if (!res[j].status) team_sel[j].assign(pairs.begin() + (size_t)j * stride * 2, pairs.begin() + ((size_t)j * stride + res[j].n) * 2);
+      }
+    } else {
+      for (int j = 0; j < nq; ++j)
+        if ((team_status[j] = archive_team_select_host(ctx, qs[j].n_targets, table.data() + qs[j].first_target, qs[j].centre, qs[j].radius,
+                                                       qs[j].pose_leaf, team_sel[j])) < 0 && team_status[j] != LINS_E_CAPACITY)
+          return team_status[j];
+    }
+  }
   for (int k = 0; k < n; ++k) {
     int refused = gate(k);
-    if (!refused && on_device) {
+    if (!refused && m->team) {
+      const int j = team_at[k];
+      if (team_status[j] == LINS_E_CAPACITY) {
+        refused = LINS_E_CAPACITY;  // (the selection's box: the entry alone)
+      } else if (team_status[j]) {
+        return team_status[j];
+      } else {
+        lists.emplace_back(std::move(team_sel[j]));
+      }
+    } else if (!refused && on_device) {
       const int j = dev_at[k];
       if (dev_res[j].status == LINS_E_CAPACITY) {
         refused = LINS_E_CAPACITY;  // (the selection's box: the entry alone)
@@ -447,7 +558,15 @@ int lins::streams_map_step_run(lins_ctx* ctx, int n, const int32_t* streams, con
   HIP_TRY(ctx, hipMemcpyAsync(m->d_entries, m->h_entries, (size_t)nb * sizeof(MapPoseEntry), hipMemcpyHostToDevice, st));
   // extractSurroundingKeyFrames + downsampleCurrentScan over the streams' clouds where they lie
   int rc;
-  if (m->surround) {
+  if (m->team) {
+    std::vector<const int32_t*> idp((size_t)nb);
+    std::vector<int32_t> idn((size_t)nb);
+    std::vector<lins_local_map_sizes> sizes((size_t)nb);
+    for (int j = 0; j < nb; ++j) idp[j] = lists[j].data(), idn[j] = (int32_t)(lists[j].size() / 2);
+    if ((rc = lins_local_map_build_team_streams(ctx, nb, which.data(), idp.data(), idn.data(), which.data(), sizes.data()))) return rc;
+    for (int j = 0; j < nb; ++j)  // (the record of the last build; an input to nothing)
+      if (!sizes[j].status) m->team_lists[which[j]] = lists[j];
+  } else if (m->surround) {
     std::vector<const int32_t*> idp((size_t)nb);
     std::vector<int32_t> idn((size_t)nb);
     std::vector<lins_local_map_sizes> sizes((size_t)nb);

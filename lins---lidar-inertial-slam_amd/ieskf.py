@@ -71,6 +71,12 @@ TEAM_EXPORTS = [
     "lins_last_place_team_stats", "lins_rendezvous_default_params", "lins_rendezvous_step",
     "lins_pose_graph_rebase_batch", "lins_team_rebase",
 ]
+# the team map's calls (include/lins_map.h; team.py wraps them); lib() resolves every one of them
+TEAM_MAP_EXPORTS = [
+    "lins_keyposes_team_select_batch", "lins_last_keyposes_team_stats", "lins_local_map_build_team",
+    "lins_local_map_build_team_streams", "lins_streams_map_team", "lins_streams_map_team_groups", "lins_streams_map_team_group",
+    "lins_streams_map_team_list",
+]
 
 
 class LinsError(RuntimeError):
@@ -137,7 +143,7 @@ def lib():
                 if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                     continue  # (an older build under A/B timing)
                 getattr(L, name).restype = C.c_int
-        for name in LIFECYCLE_EXPORTS + SNAPSHOT_EXPORTS + PLACE_EXPORTS + TEAM_EXPORTS:
+        for name in LIFECYCLE_EXPORTS + SNAPSHOT_EXPORTS + PLACE_EXPORTS + TEAM_EXPORTS + TEAM_MAP_EXPORTS:
             if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                 continue  # (an older build under A/B timing)
             getattr(L, name).restype = None if name.endswith("_default_params") else C.c_int
@@ -311,7 +317,8 @@ class IeskfContext:
         self._local_sizes = [out[k].as_dict() for k in range(n)]
         return self._local_sizes
 
-    def _surround_build(self, fn, slots, ids, tail_types, tail):
+    def _surround_build(self, fn, slots, ids, tail_types, tail, per=1):
+        """per: ints per list entry (1: ids of the entry's slot; 2: (slot, id) pairs)"""
         from ._ctypes_defs import LocalMapSizesC
 
         n = len(slots)
@@ -319,7 +326,7 @@ class IeskfContext:
         sl = np.ascontiguousarray(slots, dtype=np.int32)
         keep = [np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in ids]
         idp = (C.c_void_p * max(n, 1))(*[v.ctypes.data for v in keep])
-        idn = np.ascontiguousarray([len(v) for v in keep] or [0], dtype=np.int32)
+        idn = np.ascontiguousarray([len(v) // per for v in keep] or [0], dtype=np.int32)
         out = (LocalMapSizesC * max(n, 1))()
         fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p] + tail_types + [C.POINTER(LocalMapSizesC)]
         self._local_sizes = []
@@ -343,6 +350,23 @@ class IeskfContext:
         assert len(streams) == len(slots)
         stv = np.ascontiguousarray(streams, dtype=np.int32)
         return self._surround_build(lib().lins_local_map_build_surround_streams, slots, ids, [C.c_void_p], [stv.ctypes.data])
+
+    def local_map_build_team(self, slots, pairs, scans):
+        """lins_local_map_build_team: local_map_build_surround with each list entry naming its own archive slot — pairs[k]:
+        the (slot, id) pairs of entry k, in list order.  Returns the per-entry sizes dicts."""
+        from ._ctypes_defs import LocalScanC, local_scan_c
+
+        keep, arr = [], (LocalScanC * max(len(slots), 1))()
+        for k, sc in enumerate(scans):
+            arr[k], kk = local_scan_c(*sc)
+            keep.append(kk)
+        return self._surround_build(lib().lins_local_map_build_team, slots, pairs, [C.POINTER(LocalScanC)], [arr], per=2)
+
+    def local_map_build_team_streams(self, slots, pairs, streams):
+        """lins_local_map_build_team_streams: the same with the scan clouds taken from streams[k] where they lie"""
+        assert len(streams) == len(slots)
+        stv = np.ascontiguousarray(streams, dtype=np.int32)
+        return self._surround_build(lib().lins_local_map_build_team_streams, slots, pairs, [C.c_void_p], [stv.ctypes.data], per=2)
 
     def local_map_stage_ms(self):
         """HIP-event time (ms) of the staging kernel of the last local_map_build_streams"""

@@ -83,6 +83,48 @@ def surround_list(ctx, stream):
         return ids[:rc].tolist()
 
 
+def team(ctx, on=True, radius=50.0, pose_leaf=1.0):
+    """lins_streams_map_team: with it on, every step builds its local map from the key frames of every slot of the
+    stream's group (team_groups) that the team selection takes around the robot -> the C return code"""
+    L = _ieskf.lib()
+    L.lins_streams_map_team.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
+    return L.lins_streams_map_team(ctx._h, int(bool(on)), float(radius), float(pose_leaf))
+
+
+def team_groups(ctx, slots, groups):
+    """lins_streams_map_team_groups: slots[k] joins group groups[k] (>= 0) or stands alone (-1) -> the C return code"""
+    sv, gv = np.ascontiguousarray(slots, np.int32), np.ascontiguousarray(groups, np.int32)
+    assert len(sv) == len(gv)
+    L = _ieskf.lib()
+    L.lins_streams_map_team_groups.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    return L.lins_streams_map_team_groups(ctx._h, len(sv), sv.ctypes.data if len(sv) else None, gv.ctypes.data if len(sv) else None)
+
+
+def team_group(ctx, slot):
+    """lins_streams_map_team_group: the slot's group (-1: alone)"""
+    g = C.c_int32(-2)
+    L = _ieskf.lib()
+    L.lins_streams_map_team_group.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
+    ctx._check(L.lins_streams_map_team_group(ctx._h, int(slot), C.byref(g)))
+    return int(g.value)
+
+
+def team_list(ctx, stream):
+    """lins_streams_map_team_list: the (slot, id) pairs of the stream's last completed team build, as a list of tuples"""
+    L = _ieskf.lib()
+    L.lins_streams_map_team_list.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    cap = 64
+    while True:
+        pairs = np.zeros((cap, 2), np.int32)
+        rc = L.lins_streams_map_team_list(ctx._h, int(stream), pairs.ctypes.data, cap)
+        if rc == -3 and cap < (1 << 24):  # LINS_E_CAPACITY
+            cap *= 8
+            continue
+        if rc < 0:
+            ctx._check(rc)
+        return [tuple(p) for p in pairs[:rc].tolist()]
+
+
 def odom(transform_sum, time, imu_roll=0.0, imu_pitch=0.0, has_imu=False):
     o = MapOdomC()
     o.transform_sum[:] = [float(v) for v in np.asarray(transform_sum, np.float32)]

@@ -1,5 +1,7 @@
 """Rendezvous (include/lins_team.h): the team search over the frames of many slots — the device calls on an
-ieskf.IeskfContext, and their definition on the CPU (include/lins_host.h lins_host_place_team_topk).
+ieskf.IeskfContext, and their definition on the CPU (include/lins_host.h lins_host_place_team_topk) — and the team map
+(include/lins_map.h lins_keyposes_team_select_batch; lins_host_team_select / _team_map): which key frames of a team of
+slots a merged local map takes.
 
 A query is (query_slot, query_id, now, min_gap_s); a rank is a dict(slot, id, shift, distance (np.float32), dk,
 candidates, status).  There is no fall-back: the device calls need liblins_ieskf.so and a GPU."""
@@ -109,6 +111,100 @@ def rebase(ctx, slots, X, streams=None):
     x = _xs(X, len(s)) if len(s) else np.zeros((1, 16))
     L.lins_team_rebase.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     return L.lins_team_rebase(ctx._h, len(s), s.ctypes.data if len(s) else None, t.ctypes.data if len(s) else None, x.ctypes.data if len(s) else None)
+
+
+# ---- the team map ----
+def select(ctx, queries, stride=None):
+    """lins_keyposes_team_select_batch.  queries: tuples (centre, radius, pose_leaf, target slots); stride: pairs an entry
+    may return (default: the frames of the largest team).  Returns (pairs, results): per entry its (slot, id) pairs as an
+    (n, 2) int32 array (None with a status) and dict(n, hits, status, host) — or the C return code of a refused call."""
+    from ._ctypes_defs import KeyposesResultC, KeyposesTeamQueryC, keyposes_team_query
+
+    L = _ieskf.lib()
+    n = len(queries)
+    table, arr = [], (KeyposesTeamQueryC * max(n, 1))()
+    for k, (centre, radius, leaf, slots) in enumerate(queries):
+        arr[k] = keyposes_team_query(centre, radius, leaf, len(slots), len(table))
+        table += [int(s) for s in slots]
+    if stride is None:
+        L.lins_archive_count.argtypes = [C.c_void_p, C.c_int]
+        stride = max([sum(max(L.lins_archive_count(ctx._h, int(s)), 0) for s in set(q[3])) for q in queries] + [1])
+    tab = np.ascontiguousarray(table, np.int32)
+    pairs = np.full((max(n, 1), max(int(stride), 1), 2), -1, np.int32)
+    out = (KeyposesResultC * max(n, 1))()
+    L.lins_keyposes_team_select_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(KeyposesTeamQueryC), C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                                  C.POINTER(KeyposesResultC)]
+    rc = L.lins_keyposes_team_select_batch(ctx._h, n, arr, tab.ctypes.data if len(tab) else None, len(tab), pairs.ctypes.data, int(stride), out)
+    if rc != 0:
+        return rc
+    res = [out[k].as_dict() for k in range(n)]
+    return [None if r["status"] else pairs[k, :r["n"]].copy() for k, r in enumerate(res)], res
+
+
+def select_stats(ctx):
+    """dict(device_ms, host_entries, hits) of the last team selection"""
+    L = _ieskf.lib()
+    ms, hst, hits = C.c_float(0), C.c_int32(0), C.c_uint64(0)
+    L.lins_last_keyposes_team_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
+    ctx._check(L.lins_last_keyposes_team_stats(ctx._h, C.byref(ms), C.byref(hst), C.byref(hits)))
+    return dict(device_ms=ms.value, host_entries=hst.value, hits=hits.value)
+
+
+def host_select(targets, centre, radius, pose_leaf, cap=None):
+    """lins_host_team_select.  targets: [(slot, key poses (n, 6))] -> the (slot, id) pairs as an (n, 2) int32 array, or the C
+    return code (a negative int) of a refusal.  cap: the room of the caller's array (default: every candidate)."""
+    from ._ctypes_defs import KeyPoseC
+
+    L = _host.lib()
+    n = len(targets)
+    slots, cnt = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    pp, keep = (C.c_void_p * max(n, 1))(), []
+    for t, (slot, poses) in enumerate(targets):
+        kp = _host._key_poses(poses)
+        keep.append(kp)
+        slots[t], cnt[t], pp[t] = slot, len(poses), C.addressof(kp)
+    cap = int(cnt[:n].sum()) if cap is None else int(cap)
+    pairs = np.full((max(cap, 1), 2), -1, np.int32)
+    c = (C.c_float * 3)(*[float(v) for v in centre])
+    L.lins_host_team_select.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_void_p, C.c_int]
+    L.lins_host_team_select.restype = C.c_int
+    rc = L.lins_host_team_select(n, slots.ctypes.data, pp, cnt.ctypes.data, c, float(radius), float(pose_leaf), pairs.ctypes.data, cap)
+    return pairs[:rc].copy() if rc >= 0 else rc
+
+
+def host_map(frames, pairs, scan):
+    """lins_host_team_map: the CPU restatement of the team build for one entry.  frames: per slot [(corner, surf, outlier,
+    pose)] by frame id; pairs: the listed (slot, id); scan: (corner, surf, outlier) raw.  Returns (the six clouds in LOCAL_*
+    order, sizes dict), or the C return code of a refusal."""
+    from ._ctypes_defs import KeyframeC, LocalMapSizesC, Point, keyframe_c, local_scan_c
+
+    L = _host.lib()
+    ns = len(frames)
+    arrs, keep = [], []
+    fp, cnt = (C.c_void_p * max(ns, 1))(), np.zeros(max(ns, 1), np.int32)
+    for s, fs in enumerate(frames):
+        fr = (KeyframeC * max(len(fs), 1))()
+        for k, f in enumerate(fs):
+            fr[k], kk = keyframe_c(*f)
+            keep.append(kk)
+        arrs.append(fr)
+        fp[s], cnt[s] = C.addressof(fr), len(fs)
+    sc, skeep = local_scan_c(*scan)
+    pv = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    used = [frames[s][i] for s, i in pv if 0 <= s < ns and 0 <= i < len(frames[s])]
+    caps = [sum(len(f[0]) for f in used), sum(len(f[1]) + len(f[2]) for f in used), len(skeep[0]), len(skeep[1]), len(skeep[2]),
+            len(skeep[1]) + len(skeep[2])]
+    outs = [np.zeros((max(c, 1), 4), np.float32) for c in caps]
+    ptrs = (C.POINTER(Point) * 6)(*[o.ctypes.data_as(C.POINTER(Point)) for o in outs])
+    sizes = LocalMapSizesC()
+    L.lins_host_team_map.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(type(sc)), C.POINTER(C.POINTER(Point)),
+                                     C.POINTER(LocalMapSizesC)]
+    L.lins_host_team_map.restype = C.c_int
+    rc = L.lins_host_team_map(ns, fp, cnt.ctypes.data, pv.ctypes.data, len(pv), C.byref(sc), ptrs, C.byref(sizes))
+    if rc != 0:
+        return rc
+    d = sizes.as_dict()
+    return [o[:n].copy() for o, n in zip(outs, d["n"])], d
 
 
 # ---- the definition on the CPU ----
