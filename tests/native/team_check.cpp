@@ -1,7 +1,7 @@
 // team_check.cpp — the team search's scalar text (the lower part of csrc/host/place_math.h) and its definition
 // (csrc/host/place.cpp lins_host_place_team_topk) on the CPU, under AddressSanitizer and UBSan
 // (tests/test_place_team_host.py builds and runs it; a stand-alone program, never loaded into Python).
-//   team_check keys | select | search      one case each; exit 0 and "ok <case>" when every check holds
+//   team_check keys | select | search | layout_b | layout_c      one case each; exit 0 and "ok <case>" when every check holds
 // Every descriptor block and every time array lives in a heap block of exactly its size.
 #include <algorithm>
 #include <cmath>
@@ -185,6 +185,149 @@ int search_case() {
   return 0;
 }
 
+// a team of exact-size heap blocks, one per slot
+struct Team {
+  std::vector<std::unique_ptr<float[]>> descs;
+  std::vector<std::unique_ptr<double[]>> times;
+  std::vector<const float*> dp;
+  std::vector<const double*> tp;
+  std::vector<int32_t> slots, counts;
+  float* add(int slot, int n) {
+    descs.emplace_back(new float[(size_t)n * kCells]), times.emplace_back(new double[n]);
+    for (int c = 0; c < n; ++c) times.back()[c] = (double)c;
+    slots.push_back(slot), counts.push_back(n), dp.push_back(descs.back().get()), tp.push_back(times.back().get());
+    return descs.back().get();
+  }
+  int topk(const float* Q, int qs, int qid, int M, int k, lins_place_team_result* out) const {
+    lins_place_team_params prm;
+    lins_place_team_default_params(&prm);
+    prm.shortlist = M, prm.k = k, prm.min_sep = 0;
+    return lins_host_place_team_topk(Q, qs, qid, 1e6, -1.0, (int)slots.size(), slots.data(), dp.data(), tp.data(), counts.data(), &prm, out);
+  }
+};
+
+float least_distance(const float* Q, const float* C) {
+  float d[kNS];
+  lins_host_place_distance(Q, C, d);
+  return *std::min_element(d, d + kNS);
+}
+
+// tests/team_sizes_cases.py's layout B, built here from cells: slots of 300, 257 and 64 frames (an empty slot between
+// them); 63 frames with exactly the query's cells and other heights at places >= 256 of the concatenation, `near` (the
+// query less one cell of a column that keeps others: dk 1) and `nearer` (less two cells alone in their columns, in two
+// rings: dk 2, d below near's); every other frame far in dk.  The cut of the shortlist at M decides rank 0.
+int layout_b_case() {
+  std::mt19937 g(4);
+  std::uniform_real_distribution<float> u(0.f, 1.f);
+  std::unique_ptr<float[]> Q(new float[kCells]);
+  std::fill(Q.get(), Q.get() + kCells, 0.f);
+  std::vector<int> cells;
+  while ((int)cells.size() < 140) {
+    const int c = (int)(g() % kCells);
+    if (Q[c] == 0.f) Q[c] = 0.5f + 5.5f * u(g), cells.push_back(c);
+  }
+  int per_col[kNS] = {0};
+  for (int c : cells) per_col[c % kNS] += 1;
+  int shared = -1, alone_a = -1, alone_b = -1;
+  for (int c : cells) {
+    if (per_col[c % kNS] >= 3 && shared < 0) shared = c;
+    if (per_col[c % kNS] == 1 && alone_a < 0) alone_a = c;
+    else if (per_col[c % kNS] == 1 && alone_a >= 0 && alone_b < 0 && c / kNS != alone_a / kNS) alone_b = c;
+  }
+  CHECK(shared >= 0 && alone_a >= 0 && alone_b >= 0);
+  Team T;
+  const int n[] = {300, 0, 257, 64}, slot_of[] = {2, 3, 4, 5};
+  float* D[4];
+  for (int t = 0; t < 4; ++t) {
+    D[t] = T.add(slot_of[t], n[t]);
+    for (int c = 0; c < n[t]; ++c) random_desc(g, 0.3f, D[t] + (size_t)c * kCells);
+  }
+  const int same_at[3][2] = {{0, 262}, {2, 215}, {3, 20}};  // (target, first id): 21 frames each
+  for (const auto& at : same_at)
+    for (int i = 0; i < 21; ++i) {
+      float* d = D[at[0]] + (size_t)(at[1] + i) * kCells;
+      for (int c = 0; c < kCells; ++c) d[c] = Q[c] != 0.f ? 0.5f + 5.5f * u(g) : 0.f;
+    }
+  float* near = D[2] + (size_t)250 * kCells;
+  float* nearer = D[0] + (size_t)5 * kCells;
+  std::memcpy(near, Q.get(), kCells * sizeof(float)), std::memcpy(nearer, Q.get(), kCells * sizeof(float));
+  near[shared] = 0.f, nearer[alone_a] = 0.f, nearer[alone_b] = 0.f;
+  // the statement: sort the keys
+  RingKey kq, kc;
+  ring_key(Q.get(), 0.0, &kq);
+  std::vector<std::tuple<int, int, int>> order;
+  for (int t = 0; t < 4; ++t)
+    for (int c = 0; c < n[t]; ++c) ring_key(D[t] + (size_t)c * kCells, 0.0, &kc), order.emplace_back(key_distance(kq, kc), slot_of[t], c);
+  std::sort(order.begin(), order.end());
+  CHECK(std::get<0>(order[62]) == 0 && order[63] == std::make_tuple(1, 4, 250) && order[64] == std::make_tuple(2, 2, 5) && std::get<0>(order[65]) > 2);
+  const float d_near = least_distance(Q.get(), near), d_nearer = least_distance(Q.get(), nearer);
+  CHECK(d_nearer < d_near);
+  std::unique_ptr<lins_place_team_result[]> out(new lins_place_team_result[kMaxK]);
+  CHECK(T.topk(Q.get(), 7, 3, 64, kMaxK, out.get()) == kMaxK);
+  CHECK(out[0].slot == 4 && out[0].id == 250 && out[0].dk == 1 && out[0].distance == d_near && out[0].candidates == 621);
+  for (int j = 1; j < kMaxK; ++j) CHECK(out[j].dk == 0 && out[j].distance > d_near && out[j - 1].distance <= out[j].distance);
+  CHECK(T.topk(Q.get(), 7, 3, 63, kMaxK, out.get()) == kMaxK);
+  for (int j = 0; j < kMaxK; ++j) CHECK(out[j].dk == 0);  // near is not among them
+  // M <= 8 ranks show the whole shortlist
+  for (int M = 1; M <= kMaxK; ++M) {
+    CHECK(T.topk(Q.get(), 7, 3, M, kMaxK, out.get()) == M);
+    std::vector<std::tuple<int, int, int>> got;
+    for (int j = 0; j < M; ++j) got.emplace_back(out[j].dk, out[j].slot, out[j].id);
+    std::sort(got.begin(), got.end());
+    CHECK(std::equal(got.begin(), got.end(), order.begin()));
+  }
+  return 0;
+}
+
+// layout C: the ends of the key's range — no cell, one cell, one column, every cell, every cell but one ring's — in a pair
+// of slots, the second in reverse; each asks in turn
+int layout_c_case() {
+  const int kinds = 5;
+  auto fill = [](int kind, float* d) {
+    for (int r = 0; r < kNR; ++r)
+      for (int s = 0; s < kNS; ++s) {
+        const bool on = kind == 0 ? false : kind == 1 ? (r == 2 && s == 33) : kind == 2 ? s == 32 : kind == 3 ? true : r != 13;
+        d[r * kNS + s] = on ? 0.5f + 0.25f * (float)((7 * r + 3 * s) % 11) : 0.f;
+      }
+  };
+  Team T;
+  float* A = T.add(8, kinds);
+  float* B = T.add(9, kinds);
+  for (int i = 0; i < kinds; ++i) fill(i, A + (size_t)i * kCells), fill(i, B + (size_t)(kinds - 1 - i) * kCells);
+  RingKey key[kinds];
+  for (int i = 0; i < kinds; ++i) ring_key(A + (size_t)i * kCells, 0.0, &key[i]);
+  CHECK(key[0].sumsq == 0 && key[1].sumsq == 1 && key[2].sumsq == 20 && key[3].sumsq == (unsigned)kMaxKeyDist && key[4].sumsq == 68400);
+  CHECK(key_distance(key[0], key[3]) == kMaxKeyDist && key_distance(key[3], key[4]) == 3600 && key_distance(key[0], key[4]) == 68400);
+  for (int i = 0; i < kinds; ++i)
+    for (int j = 0; j < kinds; ++j) {
+      unsigned dot = 0;
+      for (int r = 0; r < kNR; ++r) dot += (unsigned)key[i].occ[r] * key[j].occ[r];
+      CHECK((unsigned)key_distance(key[i], key[j]) == key[i].sumsq + key[j].sumsq - 2u * dot);  // the form the device takes, at its ends
+    }
+  std::unique_ptr<lins_place_team_result[]> out(new lins_place_team_result[kMaxK]);
+  for (int i = 0; i < kinds; ++i) {
+    CHECK(T.topk(A + (size_t)i * kCells, 8, i, 64, kMaxK, out.get()) == kMaxK);
+    for (int j = 0; j < kMaxK; ++j) {
+      const lins_place_team_result& r = out[j];
+      CHECK(r.candidates == 2 * kinds - 1 && !(r.slot == 8 && r.id == i));
+      const int kind = r.slot == 8 ? r.id : kinds - 1 - r.id;
+      CHECK(r.dk == key_distance(key[i], key[kind]));
+      if (i == 0 || kind == 0) CHECK(r.distance == 1.f && r.shift == 0);  // no column to compare
+      if (j) CHECK(out[j - 1].distance <= r.distance);
+    }
+    if (i) CHECK(out[0].slot == 9 && out[0].id == kinds - 1 - i && out[0].dk == 0 && out[0].distance < 1e-6f);  // its twin
+    if (i == 0) {  // every d is 1: the ranks are the shortlist's order
+      CHECK(out[0].slot == 9 && out[0].id == kinds - 1 && out[0].dk == 0 && out[kMaxK - 1].dk == kMaxKeyDist);
+      for (int j = 1; j < kMaxK; ++j)
+        CHECK(std::make_tuple(out[j - 1].dk, out[j - 1].slot, out[j - 1].id) < std::make_tuple(out[j].dk, out[j].slot, out[j].id));
+    }
+  }
+  // a shortlist of one: the full frame's holds its twin, the empty frame's the other empty frame
+  CHECK(T.topk(A + (size_t)3 * kCells, 8, 3, 1, 1, out.get()) == 1 && out[0].slot == 9 && out[0].id == 1 && out[0].dk == 0);
+  CHECK(T.topk(A, 8, 0, 1, 1, out.get()) == 1 && out[0].slot == 9 && out[0].id == kinds - 1 && out[0].dk == 0 && out[0].distance == 1.f);
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -193,6 +336,8 @@ int main(int argc, char** argv) {
   if (!std::strcmp(name, "keys")) rc = keys_case();
   else if (!std::strcmp(name, "select")) rc = select_case();
   else if (!std::strcmp(name, "search")) rc = search_case();
+  else if (!std::strcmp(name, "layout_b")) rc = layout_b_case();
+  else if (!std::strcmp(name, "layout_c")) rc = layout_c_case();
   if (rc == 0) std::printf("ok %s\n", name);
   return rc;
 }

@@ -119,10 +119,11 @@ def exe(tmp_path_factory):
     return out
 
 
-@pytest.mark.parametrize("name", ("keys", "select", "search"))
+@pytest.mark.parametrize("name", ("keys", "select", "search", "layout_b", "layout_c"))
 def test_the_scalar_text_under_the_sanitizers(exe, name):
     """tests/native/team_check.cpp: ring_key / key_distance / pack_team_key on random descriptors, select_team on 200
-    random key sets against a sort, lins_host_place_team_topk on random small teams"""
+    random key sets against a sort, lins_host_place_team_topk on random small teams, on a shortlist whose cut at position
+    M decides rank 0 (622 candidates) and on frames at the ends of the key's range"""
     run = subprocess.run([exe, name], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert run.returncode == 0, run.stderr.decode()
     assert run.stdout.decode() == "ok %s\n" % name
