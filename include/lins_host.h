@@ -509,6 +509,56 @@ int lins_host_place_team_guess(const lins_key_pose* pose_q, const lins_key_pose*
 /* the ring key of a descriptor: occ[LINS_PLACE_RINGS] and the sum of their squares */
 int lins_host_place_ring_key(const float* desc, uint8_t occ[LINS_PLACE_RINGS], uint32_t* sumsq);
 
+/* ---- rendezvous over a window on the CPU: the DEFINITION of include/lins_team.h's lins_rendezvous_consensus_batch -------
+ * Which of the alignments of several query frames agree on one transform (DESIGN.md §5.3 "Rendezvous over a window"; the
+ * scalar text is csrc/host/rendezvous_consensus.h, the same inline code in both libraries).  f64, products and sums in
+ * the order written, contraction off.
+ *   consistent  a != b are consistent iff both are admissible, name the same target_slot, come from different `query`,
+ *               sum_ij Ra[i][j] Rb[i][j] >= 1 + 2 min_cos_rotation (the trace of Ra^T Rb, row-major from the left) and,
+ *               for p in {p_a, p_b}, d = Xa p - Xb p has (dx dx + dy dy) + dz dz <= max_translation^2; a coordinate of
+ *               X p is ((r0 px + r1 py) + r2 pz) + t.  Symmetric by construction.
+ *   support     of a: the number of distinct `query` among a and the hypotheses consistent with a (0 when a is not
+ *               admissible)
+ *   winner      the admissible hypothesis with the largest support, then the smallest fitness, then the largest `query`
+ *               (the more recent frame), then the smallest rank; its members are itself and the hypotheses consistent
+ *               with it — a star: two members may differ from each other by up to twice the bars */
+#define LINS_RENDEZVOUS_MAX_WINDOW 16
+#define LINS_RENDEZVOUS_MAX_HYP (LINS_RENDEZVOUS_MAX_WINDOW * LINS_PLACE_MAX_K) /* 128 */
+typedef struct lins_consensus_hyp {
+  double X[16];        /* row-major, as lins_loop_icp_result.transform: the asking slot's map frame to target_slot's */
+  double p[3];         /* the stored key-pose position of its query frame, in the archive's axes */
+  double fitness;
+  int32_t query;       /* which frame of the window it came from, in [0, LINS_RENDEZVOUS_MAX_WINDOW) */
+  int32_t rank;        /* in [0, LINS_PLACE_MAX_K); no (query, rank) twice in one table */
+  int32_t target_slot;
+  int32_t admissible;  /* 0 or 1 */
+} lins_consensus_hyp;  /* 176 bytes */
+
+typedef struct lins_consensus_params {
+  int32_t window;          /* 5: frames asked, in [1, LINS_RENDEZVOUS_MAX_WINDOW] */
+  int32_t stride;          /* 1: the queries are the frames latest - j stride (>= 1) */
+  int32_t min_support;     /* 3: frames that must agree, in [1, window] */
+  int32_t reserved;
+  double max_translation;  /* 1.0 m (finite, >= 0) */
+  double min_cos_rotation; /* 0.99619469809174555 = cos 5 degrees (not a NaN): there is no libm on the device, the caller passes the cosine */
+} lins_consensus_params;
+void lins_rendezvous_consensus_default_params(lins_consensus_params* p); /* exported by both libraries */
+
+typedef struct lins_consensus_result {
+  int32_t winner;       /* its index in the table, -1 when nothing is admissible (then support 0, no member) */
+  int32_t support;
+  int32_t n_admissible;
+  int32_t reserved;
+  uint32_t members[4];  /* hypothesis h is bit h % 32 of members[h / 32] */
+} lins_consensus_result; /* 32 bytes */
+
+/* One table of n_hyp hypotheses in [0, LINS_RENDEZVOUS_MAX_HYP].  Of prm only max_translation and min_cos_rotation are
+ * read.  LINS_E_ARG for a null pointer, n_hyp out of range, a bar out of range, a query or rank out of range, an
+ * `admissible` other than 0 or 1 or a (query, rank) named twice; LINS_E_INPUT for an admissible hypothesis with an entry
+ * of X or p that is not finite or a fitness that is not finite or < 0 (an inadmissible one is not read beyond its four
+ * integers).  A refused call writes nothing. */
+int lins_host_rendezvous_consensus(const lins_consensus_hyp* hyp, int n_hyp, const lins_consensus_params* prm, lins_consensus_result* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,6 +140,91 @@ int lins_pose_graph_rebase_batch(lins_ctx* ctx, int n, const int32_t* slots, con
  * formed, before they are stored — LINS_E_INPUT then, and the graphs, the archive, the rings and the streams are as they were. */
 int lins_team_rebase(lins_ctx* ctx, int n, const int32_t* slots, const int32_t* streams, const double* X);
 
+/* ---- rendezvous over a window: merge only where several frames agree on X ----
+ * lins_rendezvous_step decides from ONE frame, and nothing undoes a lins_team_rebase.  Here the last `window` frames of a
+ * robot ask, and a merge is reported only where min_support of them agree on the same transform (DESIGN.md section 5.3
+ * "Rendezvous over a window").
+ *
+ * The consensus rule is lins_host.h's lins_host_rendezvous_consensus (the scalar text csrc/host/rendezvous_consensus.h in
+ * both libraries; the kernel, csrc/rendezvous_consensus_kernels.hip, calls that text).  lins_rendezvous_consensus_batch
+ * answers n tables in one launch, one workgroup per table, bit for bit the host call per table.
+ * Layout: `hypotheses` is ONE array of lins_consensus_hyp (176 bytes: X[16], p[3], fitness as 20 doubles, then query, rank,
+ * target_slot, admissible) holding the tables back to back; `offsets` holds n + 1 entries, offsets[0] = 0, ascending;
+ * table e is hypotheses[offsets[e] .. offsets[e + 1]), at most LINS_RENDEZVOUS_MAX_HYP of them (an empty table is allowed:
+ * winner -1); results holds n records.  Of prm the call reads max_translation and min_cos_rotation.
+ * Device sequence: ONE upload (the hypotheses | the offsets), one launch, one download, one synchronisation.  An entry's
+ * bits depend neither on its batch, nor on the order of its hypotheses (up to the index mapping), nor on what the context
+ * ran before.  n = 0 is LINS_OK.  The call needs a context only: no archive, no place store.
+ * Refusals, all before anything is queued: LINS_E_ARG for a null pointer, offsets that do not start at 0, descend or give
+ * a table more than LINS_RENDEZVOUS_MAX_HYP hypotheses, and whatever lins_host_rendezvous_consensus refuses with
+ * LINS_E_ARG in some table; LINS_E_INPUT where it refuses with LINS_E_INPUT (an admissible hypothesis with an entry of X
+ * or p that is not finite, or a fitness that is not finite or < 0). */
+int lins_rendezvous_consensus_batch(lins_ctx* ctx, int n, const lins_consensus_hyp* hypotheses, const int32_t* offsets,
+                                    const lins_consensus_params* prm, lins_consensus_result* results);
+/* HIP-event time (ms) of the last consensus launch */
+int lins_last_rendezvous_consensus_stats(lins_ctx* ctx, float* kernel_ms);
+
+/* lins_rendezvous_window_step.  Stages, each ONE batched call over the entries that reach it, the whole a composition of
+ * the public calls:
+ *   queries   per entry the frames latest - j * stride, j = 0 .. window - 1, that exist (query 0 is the latest frame);
+ *             every query uses entry.now
+ *   detect    one lins_place_team_topk_batch over all queries of all entries, as lins_rendezvous_step.  Ranks with
+ *             distance > max_distance are dropped, and so are the ranks INSIDE THE ASKING SLOT: a robot's own older frames
+ *             would agree with each other on X = I and win.  They are never aligned.
+ *   assemble  one lins_archive_assemble: per (entry, query) the source, per surviving rank the target window, the specs
+ *             exactly lins_rendezvous_step's
+ *   align     one lins_loop_icp_batch_from over every (entry, query, rank), T0 = lins_host_place_team_guess from that
+ *             query frame's own stored pose
+ *   consensus admissible = the alignment ran (status 0) and lins_host_loop_accept(converged, fitness, max_fitness) and
+ *             its fitness and transform are finite (a NaN fitness passes lins_host_loop_accept; it is no witness here);
+ *             p = the query frame's stored position; one lins_rendezvous_consensus_batch over the entries with a hypothesis
+ *   outcome   NONE: no frame, or no rank survived.  REJECTED: ranks were aligned and none is admissible.  UNCONFIRMED: the
+ *             winner's support is below min_support.  FOUND: X, target_slot, target_id are the winner's; X is its ICP
+ *             transform unchanged and can go to lins_team_rebase as it is.
+ * With window 1 and min_support 1 the outcome, the target and X are lins_rendezvous_step's wherever that step's ranks
+ * hold none of the asking slot.
+ * hyp: room for n * window * k records (k = team->team.k); entry e's records are hyp[e * window * k ..], n_hypotheses of
+ * them in (query, rank) order — the order of the entry's consensus table, so `winner` and `members` index them; the records
+ * behind them are zero.  The call reads and changes no pose graph, no ring and no map pose.  An entry's bits are those of
+ * the explicit chain of the five calls for its slot, in any batch and order.
+ * Refusals: lins_rendezvous_step's, LINS_E_ARG for consensus parameters out of range (window outside [1,
+ * LINS_RENDEZVOUS_MAX_WINDOW], stride < 1, min_support outside [1, window], max_translation not finite or < 0, a NaN
+ * min_cos_rotation) or a null hyp with n > 0; LINS_E_CAPACITY as lins_rendezvous_step, asked of the most the window can
+ * ask for: n * window * (1 + k) submaps, every entry's queries that exist with k windows each as large as the largest
+ * target slot's whole history.  All are asked before anything is queued: a refused call changes nothing. */
+#define LINS_RENDEZVOUS_UNCONFIRMED 3 /* alignments were accepted, but fewer than min_support frames agree */
+
+typedef struct lins_rendezvous_hypothesis {
+  int32_t query, rank;        /* query: j of the frame latest - j * stride; rank: among that query's surviving ranks */
+  int32_t admissible, member; /* member: 1 iff it is the winner or consistent with it */
+  lins_place_team_result cand;
+  lins_submap_info target;    /* its window as assembled */
+  lins_loop_icp_result icp;
+} lins_rendezvous_hypothesis;
+
+typedef struct lins_rendezvous_window_result {
+  int32_t outcome;                /* LINS_RENDEZVOUS_* */
+  int32_t status;                 /* LINS_OK, or the first status of the entry's assemblies / alignments (then nothing is chosen) */
+  int32_t n_queries;              /* frames that asked */
+  int32_t n_hypotheses;           /* ranks that went to the alignment, over all queries */
+  int32_t winner;                 /* index among the entry's hypotheses, or -1 */
+  int32_t support, n_admissible;
+  int32_t target_slot, target_id; /* FOUND: the winner's candidate; otherwise -1, -1 */
+  int32_t reserved;
+  uint32_t members[4];            /* as lins_consensus_result */
+  int32_t query_id[LINS_RENDEZVOUS_MAX_WINDOW];     /* the frames that asked, query 0 first; -1 behind them */
+  int32_t n_ranks[LINS_RENDEZVOUS_MAX_WINDOW];      /* per query: ranks that went to the alignment */
+  lins_submap_info source[LINS_RENDEZVOUS_MAX_WINDOW]; /* per query: the source as assembled (zero when none of its ranks survived) */
+  double X[16];                   /* FOUND: the winner's alignment; otherwise zero */
+} lins_rendezvous_window_result;
+
+int lins_rendezvous_window_step(lins_ctx* ctx, int n, const lins_rendezvous_entry* entries, int n_targets, const int32_t* target_slots,
+                                const lins_loop_step_params* prm, const lins_rendezvous_params* team, const lins_consensus_params* consensus,
+                                lins_rendezvous_window_result* out, lins_rendezvous_hypothesis* hyp);
+/* the last lins_rendezvous_window_step: host-clock time (ms) of its stages — detect, assemble, align, consensus — and of
+ * the whole call (each stage ends in a synchronisation) */
+int lins_last_rendezvous_window_stats(lins_ctx* ctx, float* detect_ms, float* assemble_ms, float* align_ms, float* consensus_ms, float* total_ms);
+
 #ifdef __cplusplus
 }
 #endif

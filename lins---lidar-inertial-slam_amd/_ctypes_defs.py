@@ -766,6 +766,82 @@ def rendezvous_params(lib, **kw):
     return p
 
 
+# ---- rendezvous over a window (include/lins_team.h; the consensus records are include/lins_host.h's) ----
+RENDEZVOUS_UNCONFIRMED = 3
+RENDEZVOUS_MAX_WINDOW, RENDEZVOUS_MAX_HYP = 16, 128
+
+
+class ConsensusHypC(C.Structure):
+    _fields_ = [("X", C.c_double * 16), ("p", C.c_double * 3), ("fitness", C.c_double), ("query", C.c_int32), ("rank", C.c_int32),
+                ("target_slot", C.c_int32), ("admissible", C.c_int32)]
+
+
+class ConsensusParamsC(C.Structure):
+    _fields_ = [("window", C.c_int32), ("stride", C.c_int32), ("min_support", C.c_int32), ("reserved", C.c_int32),
+                ("max_translation", C.c_double), ("min_cos_rotation", C.c_double)]
+
+
+class ConsensusResultC(C.Structure):
+    _fields_ = [("winner", C.c_int32), ("support", C.c_int32), ("n_admissible", C.c_int32), ("reserved", C.c_int32), ("members", C.c_uint32 * 4)]
+
+    def as_dict(self):
+        return dict(winner=int(self.winner), support=int(self.support), n_admissible=int(self.n_admissible), members=members_of(self.members))
+
+
+def members_of(words):
+    """the set bits of a 128-bit member mask, ascending"""
+    return [h for h in range(RENDEZVOUS_MAX_HYP) if (int(words[h >> 5]) >> (h & 31)) & 1]
+
+
+class RendezvousHypothesisC(C.Structure):
+    _fields_ = [("query", C.c_int32), ("rank", C.c_int32), ("admissible", C.c_int32), ("member", C.c_int32), ("cand", PlaceTeamResultC),
+                ("target", SubmapInfoC), ("icp", LoopIcpResultC)]
+
+    def as_dict(self):
+        return dict(query=int(self.query), rank=int(self.rank), admissible=int(self.admissible), member=int(self.member), cand=self.cand.as_dict(),
+                    target=self.target.as_dict(), icp=self.icp.as_dict())
+
+
+class RendezvousWindowResultC(C.Structure):
+    _fields_ = [("outcome", C.c_int32), ("status", C.c_int32), ("n_queries", C.c_int32), ("n_hypotheses", C.c_int32), ("winner", C.c_int32),
+                ("support", C.c_int32), ("n_admissible", C.c_int32), ("target_slot", C.c_int32), ("target_id", C.c_int32), ("reserved", C.c_int32),
+                ("members", C.c_uint32 * 4), ("query_id", C.c_int32 * RENDEZVOUS_MAX_WINDOW), ("n_ranks", C.c_int32 * RENDEZVOUS_MAX_WINDOW),
+                ("source", SubmapInfoC * RENDEZVOUS_MAX_WINDOW), ("X", C.c_double * 16)]
+
+    def as_dict(self):
+        nq = int(self.n_queries)
+        return dict(outcome=int(self.outcome), status=int(self.status), n_queries=nq, n_hypotheses=int(self.n_hypotheses), winner=int(self.winner),
+                    support=int(self.support), n_admissible=int(self.n_admissible), target_slot=int(self.target_slot), target_id=int(self.target_id),
+                    members=members_of(self.members), query_id=[int(self.query_id[j]) for j in range(nq)],
+                    n_ranks=[int(self.n_ranks[j]) for j in range(nq)], source=[self.source[j].as_dict() for j in range(nq)],
+                    X=np.array(self.X[:], np.float64).reshape(4, 4))
+
+
+def consensus_params(lib, **kw):
+    """lins_rendezvous_consensus_default_params of library `lib` (window 5, stride 1, min_support 3, max_translation 1.0,
+    min_cos_rotation cos 5 degrees) with fields overridden by keyword"""
+    p = ConsensusParamsC()
+    lib.lins_rendezvous_consensus_default_params.argtypes = [C.POINTER(ConsensusParamsC)]
+    lib.lins_rendezvous_consensus_default_params.restype = None
+    lib.lins_rendezvous_consensus_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"lins_consensus_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def consensus_table(hyps):
+    """[dict(X, p, fitness, query, rank, target_slot, admissible)] -> a ConsensusHypC array (at least one element)"""
+    arr = (ConsensusHypC * max(len(hyps), 1))()
+    for i, h in enumerate(hyps):
+        arr[i].X[:] = [float(v) for v in np.asarray(h["X"], np.float64).reshape(16)]
+        arr[i].p[:] = [float(v) for v in np.asarray(h["p"], np.float64).reshape(3)]
+        arr[i].fitness = float(h["fitness"])
+        arr[i].query, arr[i].rank, arr[i].target_slot, arr[i].admissible = int(h["query"]), int(h["rank"]), int(h["target_slot"]), int(h["admissible"])
+    return arr
+
+
 # ---- stream snapshots (include/lins_snapshot.h): the blob's header and records, the plan's records ----
 SNAPSHOT_MAGIC, SNAPSHOT_VERSION = 0x3150414E534E494C, 1
 SNAP_STREAM, SNAP_FILTER, SNAP_BOOT, SNAP_ODOM, SNAP_MAP_POSE, SNAP_RING, SNAP_ARCHIVE, SNAP_GRAPH = (1 << k for k in range(8))

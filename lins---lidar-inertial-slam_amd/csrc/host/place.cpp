@@ -8,6 +8,7 @@
 #include "../../../include/lins_host.h"
 #include "place_guess.h"
 #include "place_math.h"
+#include "rendezvous_consensus.h"
 #include "voxel_map.h"
 
 using namespace lins_place;
@@ -207,6 +208,19 @@ int lins_host_place_guess(const lins_key_pose* pose_q, const lins_key_pose* pose
 int lins_host_place_team_guess(const lins_key_pose* pose_q, const lins_key_pose* pose_c, int shift, int up_axis, double* T0) {
   if (!pose_q || !pose_c || !T0 || shift < 0 || shift >= kNS || up_axis < 0 || up_axis > 2) return LINS_E_ARG;
   guess_team(*pose_q, *pose_c, shift, up_axis, T0);
+  return LINS_OK;
+}
+
+// ---- rendezvous over a window: the consensus rule (rendezvous_consensus.h) ----
+void lins_rendezvous_consensus_default_params(lins_consensus_params* p) {
+  if (p) lins_consensus::default_params(p);
+}
+
+int lins_host_rendezvous_consensus(const lins_consensus_hyp* hyp, int n_hyp, const lins_consensus_params* prm, lins_consensus_result* out) {
+  using namespace lins_consensus;
+  if (!out || n_hyp < 0 || n_hyp > kMaxHyp || (n_hyp && !hyp) || !bars_ok(prm)) return LINS_E_ARG;
+  if (int rc = table_check(hyp, n_hyp)) return rc;
+  evaluate(hyp, n_hyp, bars_of(prm->max_translation, prm->min_cos_rotation), out);
   return LINS_OK;
 }
 

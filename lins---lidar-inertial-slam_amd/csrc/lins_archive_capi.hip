@@ -151,6 +151,8 @@ int archive_team_select_host(lins_ctx* ctx, int n_targets, const int32_t* slots,
   return LINS_OK;
 }
 
+ConsensusStore* archive_consensus(lins_ctx* ctx) { return &archive_of(ctx)->place.team.consensus; }
+
 int archive_place(lins_ctx* ctx, ArchivePlace* v) {
   Archive* m = archive_of(ctx);
   if (!m->n_slots) return LINS_E_STATE;

@@ -224,6 +224,13 @@ void launch_team_shortlist(hipStream_t s, int n_queries, const TmQuery* queries,
 void launch_team_pairs(hipStream_t s, int n_queries, const TmQuery* queries, int M, int max_frames, const unsigned long long* shortlist,
                        const float* recs, unsigned long long* row);
 
+// ---- rendezvous_consensus_kernels.hip: which alignments of a window of query frames agree (host/rendezvous_consensus.h)
+// one workgroup of kCsBlock lanes per entry: entry e's hypotheses are table[offsets[e] .. offsets[e + 1]), at most
+// kCsBlock of them, checked by lins_consensus::table_check; its record goes to out + e
+constexpr int kCsBlock = 128;
+void launch_rendezvous_consensus(hipStream_t s, int n, const ::lins_consensus_hyp* table, const int* offsets, double max_translation,
+                                 double min_cos_rotation, ::lins_consensus_result* out);
+
 // ---- pose_graph_kernels.hip: the pose graph's solve, one workgroup per problem (pose_graph.h) ----
 // the poses and the cost of every problem as it stands (the first launch of a solve)
 void launch_pose_graph_begin(hipStream_t s, int n_problems, const lins_pg::Prob* probs);

@@ -5,10 +5,13 @@
 // n * M shortlist keys and the n * M row keys and synchronises once; select_team takes the ranks here.  The marks "keyed
 // below id" move only after that synchronisation.
 // lins_rendezvous_step is host orchestration only, as lins_loop_step_place is: every device stage is a batched call that
-// exists, run ONCE over the entries that reach it.
+// exists, run ONCE over the entries that reach it.  lins_rendezvous_window_step is the same composition over the last
+// frames of every entry, with one more stage: lins_rendezvous_consensus_batch (rendezvous_consensus_kernels.hip; its
+// staging is place.h ConsensusStore) decides which alignments agree.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -18,6 +21,7 @@
 #include "host/loop_step.h"
 #include "host/place_guess.h"
 #include "host/place_math.h"
+#include "host/rendezvous_consensus.h"
 #include "keyframe_archive.h"
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
@@ -359,6 +363,296 @@ int lins_rendezvous_step(lins_ctx* ctx, int n, const lins_rendezvous_entry* entr
     o.outcome = LINS_RENDEZVOUS_FOUND, o.target_slot = o.cand[o.chosen].slot, o.target_id = o.cand[o.chosen].id;
     std::memcpy(o.X, o.icp[o.chosen].transform, sizeof o.X);
   }
+  return LINS_OK;
+}
+
+// ---- rendezvous over a window ----
+void lins_rendezvous_consensus_default_params(lins_consensus_params* p) {
+  if (p) lins_consensus::default_params(p);
+}
+
+int lins_rendezvous_consensus_batch(lins_ctx* ctx, int n, const lins_consensus_hyp* hypotheses, const int32_t* offsets,
+                                    const lins_consensus_params* prm, lins_consensus_result* results) {
+  using namespace lins_consensus;
+  if (!ctx || n < 0 || !bars_ok(prm) || (n && (!offsets || !results))) return LINS_E_ARG;
+  if (n == 0) return LINS_OK;
+  if (offsets[0] != 0) return LINS_E_ARG;
+  for (int e = 0; e < n; ++e)
+    if (offsets[e + 1] < offsets[e] || offsets[e + 1] - offsets[e] > kMaxHyp) return LINS_E_ARG;
+  const int total = offsets[n];
+  if (total && !hypotheses) return LINS_E_ARG;
+  int input = LINS_OK;  // (an argument error in any table comes before an input error in an earlier one)
+  for (int e = 0; e < n; ++e) {
+    const int rc = table_check(hypotheses + offsets[e], offsets[e + 1] - offsets[e]);
+    if (rc == LINS_E_ARG) return rc;
+    if (rc && !input) input = rc;
+  }
+  if (input) return input;
+  // (every refusal is behind us)
+  ConsensusStore& c = *archive_consensus(ctx);
+  c.kernel_ms = 0.f;
+  HIP_TRY(ctx, hipSetDevice(ctx_device(ctx)));
+  const size_t o_off = align64((size_t)total * sizeof(lins_consensus_hyp)), up_bytes = align64(o_off + ((size_t)n + 1) * sizeof(int32_t)),
+               down_bytes = (size_t)n * sizeof(lins_consensus_result);
+  BUF_TRY(ctx, c.h_up.grow(up_bytes));
+  BUF_TRY(ctx, c.d_up.grow(up_bytes));
+  BUF_TRY(ctx, c.h_down.grow(down_bytes));
+  BUF_TRY(ctx, c.d_down.grow(down_bytes));
+  for (int i = 0; i < 2; ++i) BUF_TRY(ctx, c.ev[i].create());
+  if (total) std::memcpy(c.h_up, hypotheses, (size_t)total * sizeof(lins_consensus_hyp));
+  std::memcpy(c.h_up + o_off, offsets, ((size_t)n + 1) * sizeof(int32_t));
+  hipStream_t st = ctx_stream(ctx);
+  HIP_TRY(ctx, hipMemcpyAsync(c.d_up, c.h_up, up_bytes, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipEventRecord(c.ev[0], st));
+  launch_rendezvous_consensus(st, n, (const lins_consensus_hyp*)c.d_up.get(), (const int*)(c.d_up + o_off), prm->max_translation,
+                              prm->min_cos_rotation, (lins_consensus_result*)c.d_down.get());
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipEventRecord(c.ev[1], st));
+  HIP_TRY(ctx, hipMemcpyAsync(c.h_down, c.d_down, down_bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  HIP_TRY(ctx, hipEventElapsedTime(&c.kernel_ms, c.ev[0], c.ev[1]));
+  std::memcpy(results, c.h_down, down_bytes);
+  return LINS_OK;
+}
+
+int lins_last_rendezvous_consensus_stats(lins_ctx* ctx, float* kernel_ms) {
+  if (!ctx) return LINS_E_ARG;
+  if (kernel_ms) *kernel_ms = archive_consensus(ctx)->kernel_ms;
+  return LINS_OK;
+}
+
+int lins_last_rendezvous_window_stats(lins_ctx* ctx, float* detect_ms, float* assemble_ms, float* align_ms, float* consensus_ms, float* total_ms) {
+  if (!ctx) return LINS_E_ARG;
+  const float* t = archive_consensus(ctx)->stage_ms;
+  float* const dst[5] = {detect_ms, assemble_ms, align_ms, consensus_ms, total_ms};
+  for (int i = 0; i < 5; ++i)
+    if (dst[i]) *dst[i] = t[i];
+  return LINS_OK;
+}
+
+int lins_rendezvous_window_step(lins_ctx* ctx, int n, const lins_rendezvous_entry* entries, int n_targets, const int32_t* target_slots,
+                                const lins_loop_step_params* prm, const lins_rendezvous_params* team, const lins_consensus_params* consensus,
+                                lins_rendezvous_window_result* out, lins_rendezvous_hypothesis* hyp) {
+  using clock = std::chrono::steady_clock;
+  if (!ctx || n < 0 || (n && (!entries || !out || !hyp))) return LINS_E_ARG;
+  ArchivePlace A;
+  if (int rc = store_of(ctx, &A)) return rc;
+  // ---- the whole call's errors, before anything is queued (lins_rendezvous_step's, and the window's) ----
+  if (!prm || !team || std::isnan(prm->max_fitness) || !std::isfinite(prm->history_leaf) || prm->history_leaf < 0.f || prm->search_num < 0 ||
+      std::isnan(prm->min_gap_s) || prm->icp.max_iterations < 1 || prm->icp.min_correspondences < 0 || !std::isfinite(prm->icp.max_corr_dist))
+    return LINS_E_ARG;
+  if (!lins_consensus::params_ok(consensus)) return LINS_E_ARG;
+  lins_place_team_params tp = team->team;
+  if (tp.min_sep < -1 || std::isnan(team->max_distance)) return LINS_E_ARG;
+  if (tp.min_sep < 0) tp.min_sep = prm->search_num;
+  if (!team_params_ok(&tp)) return LINS_E_ARG;
+  if (int rc = slots_check(A, n_targets, target_slots)) return rc;
+  for (int k = 0; k < n; ++k) {
+    if (entries[k].slot < 0 || entries[k].slot >= A.n_slots) return LINS_E_ARG;
+    for (int i = 0; i < k; ++i)
+      if (entries[i].slot == entries[k].slot) return LINS_E_ARG;
+  }
+  for (int k = 0; k < n; ++k)
+    if (!std::isfinite(entries[k].now)) return LINS_E_INPUT;
+  const int K = tp.k, W = consensus->window, stride = consensus->stride;
+  static_assert(LINS_RENDEZVOUS_MAX_WINDOW * LINS_PLACE_MAX_K == LINS_RENDEZVOUS_MAX_HYP, "an entry's hypotheses fill one consensus table at the most");
+  if ((long long)n * W * (1 + K) > 2147483647ll) return LINS_E_CAPACITY;
+  const std::vector<std::vector<ArFrame>>& frames = *A.frames;
+  // query j of a slot with `count` frames: latest - j * stride, while it exists
+  auto queries_of = [&](int count) {
+    int nq = 0;
+    while (nq < W && (long long)(count - 1) - (long long)nq * stride >= 0) ++nq;
+    return nq;
+  };
+  // lins_rendezvous_step's capacity question, asked of the most the window can ask for
+  {
+    auto both = [](const ArFrame& f) { return (long long)f.n[0] + f.n[1]; };  // corner | surf
+    long long widest = 0, tiles = 0;
+    for (int t = 0; t < n_targets; ++t) {
+      long long sum = 0;
+      for (const ArFrame& f : frames[target_slots[t]]) sum += both(f);
+      widest = std::max(widest, sum);
+    }
+    if (widest > INT_MAX / 2) return LINS_E_CAPACITY;
+    for (int k = 0; k < n; ++k) {
+      const std::vector<ArFrame>& fr = frames[entries[k].slot];
+      const int nq = queries_of((int)fr.size());
+      for (int j = 0; j < nq; ++j)
+        tiles += (both(fr[fr.size() - 1 - (size_t)j * stride]) + kLmTile - 1) / kLmTile + (long long)K * ((widest + kLmTile - 1) / kLmTile);
+      if (tiles > INT_MAX / 256) return LINS_E_CAPACITY;
+    }
+  }
+  ConsensusStore& cs = *archive_consensus(ctx);
+  for (float& t : cs.stage_ms) t = 0.f;
+  const clock::time_point t_begin = clock::now();
+  clock::time_point t_stage = t_begin;
+  auto lap = [&](int stage) {
+    const clock::time_point now = clock::now();
+    cs.stage_ms[stage] = std::chrono::duration<float, std::milli>(now - t_stage).count();
+    cs.stage_ms[4] = std::chrono::duration<float, std::milli>(now - t_begin).count();
+    t_stage = now;
+  };
+  // ---- queries and detect: one team search over every (entry, query) ----
+  struct Ask {
+    int entry, query;
+  };
+  std::vector<Ask> asks;
+  std::vector<lins_place_team_query> qs;
+  const size_t per_entry = (size_t)W * K;
+  for (int k = 0; k < n; ++k) {
+    lins_rendezvous_window_result& o = out[k];
+    std::memset(&o, 0, sizeof o);
+    std::memset(hyp + k * per_entry, 0, per_entry * sizeof *hyp);
+    o.outcome = LINS_RENDEZVOUS_NONE, o.winner = o.target_slot = o.target_id = -1;
+    const int count = (int)frames[entries[k].slot].size();
+    o.n_queries = queries_of(count);
+    for (int j = 0; j < LINS_RENDEZVOUS_MAX_WINDOW; ++j) o.query_id[j] = j < o.n_queries ? count - 1 - j * stride : -1;
+    for (int j = 0; j < o.n_queries; ++j) {
+      asks.push_back(Ask{k, j});
+      qs.push_back(lins_place_team_query{entries[k].slot, o.query_id[j], entries[k].now, prm->min_gap_s});
+    }
+  }
+  if (asks.empty()) return LINS_OK;
+  std::vector<lins_place_team_result> found(qs.size() * (size_t)K);
+  std::vector<int32_t> filled(qs.size(), 0);
+  if (int rc = run(ctx, A, (int)qs.size(), qs.data(), n_targets, target_slots, tp, found.data(), filled.data())) return rc;
+  lap(0);
+  for (size_t a = 0; a < asks.size(); ++a) {
+    lins_rendezvous_window_result& o = out[asks[a].entry];
+    lins_rendezvous_hypothesis* h = hyp + asks[a].entry * per_entry;
+    for (int j = 0; j < filled[a]; ++j) {
+      const lins_place_team_result& r = found[a * K + j];
+      if (r.distance > team->max_distance || r.slot == entries[asks[a].entry].slot) continue;
+      lins_rendezvous_hypothesis& x = h[o.n_hypotheses++];
+      x.query = asks[a].query, x.rank = o.n_ranks[asks[a].query]++, x.cand = r;
+    }
+  }
+  // ---- assemble: per (entry, query) with a rank its source, then one window per rank from the rank's own slot; one call ----
+  std::vector<int> cand;  // entries that go to the assembly
+  for (int k = 0; k < n; ++k)
+    if (out[k].n_hypotheses) cand.push_back(k);
+  const int nc = (int)cand.size();
+  if (nc == 0) return LINS_OK;
+  std::vector<int> first(nc + 1, 0);  // an entry's first spec
+  for (int i = 0; i < nc; ++i) {
+    const lins_rendezvous_window_result& o = out[cand[i]];
+    int sources = 0;
+    for (int j = 0; j < o.n_queries; ++j) sources += o.n_ranks[j] ? 1 : 0;
+    first[i + 1] = first[i] + sources + o.n_hypotheses;
+  }
+  const int n_specs = first[nc];
+  std::vector<std::vector<int32_t>> ids(n_specs);
+  std::vector<lins_submap_spec> specs(n_specs);
+  std::vector<lins_submap_info> infos(n_specs);
+  std::vector<int> src_spec((size_t)n * LINS_RENDEZVOUS_MAX_WINDOW, -1);  // [entry][query]: the source's spec
+  std::vector<int> tgt_spec((size_t)n * per_entry, -1);                     // [entry][hypothesis]: the target's
+  for (int i = 0; i < nc; ++i) {
+    const int k = cand[i];
+    const lins_rendezvous_window_result& o = out[k];
+    const lins_rendezvous_hypothesis* h = hyp + k * per_entry;
+    int s = first[i];
+    for (int x = 0; x < o.n_hypotheses; ++x) {
+      if (h[x].rank == 0) {  // the query's source goes in front of its ranks
+        ids[s].assign(1, o.query_id[h[x].query]);
+        specs[s] = lins_submap_spec{ids[s].data(), 1, entries[k].slot, LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF, LINS_SUBMAP_DROP_NEGATIVE, 0.f, 0};
+        src_spec[(size_t)k * LINS_RENDEZVOUS_MAX_WINDOW + h[x].query] = s++;
+      }
+      const lins_place_team_result& c = h[x].cand;
+      const int latest = (int)frames[c.slot].size() - 1;
+      std::vector<int32_t>& w = ids[s];
+      w.resize(lins_loop::window_size(latest, c.id, prm->search_num));
+      lins_loop::window(latest, c.id, prm->search_num, w.data());
+      specs[s] = lins_submap_spec{w.data(), (int32_t)w.size(), c.slot, LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF, 0, prm->history_leaf, 0};
+      tgt_spec[k * per_entry + x] = s++;
+    }
+  }
+  if (int rc = lins_archive_assemble(ctx, n_specs, specs.data(), infos.data())) return rc;
+  lap(1);
+  // ---- align: one batch over every (entry, query, rank) of the entries whose assemblies have no status ----
+  std::vector<int> ran;    // positions in cand
+  std::vector<int> prob0;  // their first problem
+  std::vector<lins_loop_icp_problem> probs;
+  std::vector<double> T0;
+  for (int i = 0; i < nc; ++i) {
+    const int k = cand[i];
+    lins_rendezvous_window_result& o = out[k];
+    lins_rendezvous_hypothesis* h = hyp + k * per_entry;
+    int status = 0;
+    for (int x = 0; x < o.n_hypotheses; ++x) {
+      const int ss = src_spec[(size_t)k * LINS_RENDEZVOUS_MAX_WINDOW + h[x].query];
+      if (h[x].rank == 0) {
+        o.source[h[x].query] = infos[ss];
+        if (!status) status = infos[ss].status;
+      }
+      h[x].target = infos[tgt_spec[k * per_entry + x]];
+      if (!status) status = h[x].target.status;
+    }
+    if (status) {  // (the entry's first: nothing is aligned for it)
+      o.status = status;
+      continue;
+    }
+    ran.push_back(i), prob0.push_back((int)probs.size());
+    for (int x = 0; x < o.n_hypotheses; ++x) {
+      probs.push_back(lins_loop_icp_problem{src_spec[(size_t)k * LINS_RENDEZVOUS_MAX_WINDOW + h[x].query], tgt_spec[k * per_entry + x], nullptr, nullptr, 0, 0});
+      T0.resize(T0.size() + 16, 0.0);
+      lins_place::guess_team(frames[entries[k].slot][o.query_id[h[x].query]].pose, frames[h[x].cand.slot][h[x].cand.id].pose, h[x].cand.shift,
+                             A.store->prm.up_axis, &T0[T0.size() - 16]);
+    }
+  }
+  if (ran.empty()) return LINS_OK;
+  std::vector<lins_loop_icp_result> icp(probs.size());
+  if (int rc = lins_loop_icp_batch_from(ctx, (int)probs.size(), probs.data(), T0.data(), &prm->icp, icp.data())) return rc;
+  lap(2);
+  // ---- consensus: one table per entry that was aligned, one launch ----
+  std::vector<int> judged;  // positions in cand
+  std::vector<lins_consensus_hyp> table;
+  std::vector<int32_t> offsets(1, 0);
+  for (size_t a = 0; a < ran.size(); ++a) {
+    const int k = cand[ran[a]];
+    lins_rendezvous_window_result& o = out[k];
+    lins_rendezvous_hypothesis* h = hyp + k * per_entry;
+    int status = 0, aligned = 0;
+    for (int x = 0; x < o.n_hypotheses; ++x) {
+      const lins_loop_icp_result& r = h[x].icp = icp[prob0[a] + x];
+      if (r.status && !status) status = r.status;  // (a target box beyond the gridding's limit: nothing was run)
+      aligned += r.status ? 0 : 1;
+      bool finite = lins_consensus::finite64(r.fitness) && r.fitness >= 0.0;
+      for (int j = 0; j < 16; ++j) finite = finite && lins_consensus::finite64(r.transform[j]);
+      h[x].admissible = !r.status && finite && lins_loop::accept(r.converged, r.fitness, prm->max_fitness) ? 1 : 0;
+    }
+    if (!aligned) {
+      o.status = status;
+      continue;
+    }
+    judged.push_back(k);
+    for (int x = 0; x < o.n_hypotheses; ++x) {
+      lins_consensus_hyp c;
+      std::memset(&c, 0, sizeof c);
+      const lins_key_pose& p = frames[entries[k].slot][o.query_id[h[x].query]].pose;
+      if (h[x].admissible) std::memcpy(c.X, h[x].icp.transform, sizeof c.X), c.fitness = h[x].icp.fitness;
+      c.p[0] = (double)p.x, c.p[1] = (double)p.y, c.p[2] = (double)p.z;
+      c.query = h[x].query, c.rank = h[x].rank, c.target_slot = h[x].cand.slot, c.admissible = h[x].admissible;
+      table.push_back(c);
+    }
+    offsets.push_back((int32_t)table.size());
+  }
+  if (judged.empty()) return LINS_OK;
+  std::vector<lins_consensus_result> verdict(judged.size());
+  if (int rc = lins_rendezvous_consensus_batch(ctx, (int)judged.size(), table.data(), offsets.data(), consensus, verdict.data())) return rc;
+  // ---- outcome ----
+  for (size_t a = 0; a < judged.size(); ++a) {
+    lins_rendezvous_window_result& o = out[judged[a]];
+    lins_rendezvous_hypothesis* h = hyp + judged[a] * per_entry;
+    const lins_consensus_result& v = verdict[a];
+    o.winner = v.winner, o.support = v.support, o.n_admissible = v.n_admissible;
+    std::memcpy(o.members, v.members, sizeof o.members);
+    for (int x = 0; x < o.n_hypotheses; ++x) h[x].member = (int32_t)((v.members[x >> 5] >> (x & 31)) & 1u);
+    o.outcome = v.winner < 0 ? LINS_RENDEZVOUS_REJECTED : (v.support < consensus->min_support ? LINS_RENDEZVOUS_UNCONFIRMED : LINS_RENDEZVOUS_FOUND);
+    if (o.outcome != LINS_RENDEZVOUS_FOUND) continue;
+    o.target_slot = h[v.winner].cand.slot, o.target_id = h[v.winner].cand.id;
+    std::memcpy(o.X, h[v.winner].icp.transform, sizeof o.X);
+  }
+  lap(3);
   return LINS_OK;
 }
 

@@ -75,6 +75,16 @@ struct TmQuery {
 };
 static_assert(sizeof(TmQuery) == 32, "TmQuery layout");
 
+// the staging of lins_rendezvous_consensus_batch and the last calls' times: no frame's state, nothing a snapshot carries
+struct ConsensusStore {
+  DevBuf<char> d_up, d_down;  // (bytes) the hypotheses | the offsets; the results
+  PinBuf<char> h_up, h_down;
+  Event ev[2];  // around the launch
+  float kernel_ms = 0.f;
+  float stage_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};  // the last lins_rendezvous_window_step: detect, assemble, align, consensus, the whole call (host clock)
+};
+ConsensusStore* archive_consensus(lins_ctx* ctx);  // lins_archive_capi.hip: the context's, before lins_archive_init as well
+
 struct TeamStore {
   std::vector<int> keyed;  // [slot]: ring keys are current below this id; empty until the first team call
   DevBuf<uint4> d_key;     // two a frame; allocated by the first team call
@@ -85,6 +95,7 @@ struct TeamStore {
   float key_ms = 0.f, shortlist_ms = 0.f, pair_ms = 0.f;
   uint64_t scanned = 0;
   int built = 0;  // frames the last call keyed
+  ConsensusStore consensus;
   void drop() { keyed.clear(), d_key.reset(); }
   void drop_slot(int slot) {
     if (!keyed.empty()) keyed[slot] = 0;

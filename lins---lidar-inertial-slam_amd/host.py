@@ -552,6 +552,23 @@ def loop_choose(converged, fitness, max_fitness=0.3):
     return int(L.lins_host_loop_choose(len(cv), cv.ctypes.data if len(cv) else None, ft.ctypes.data if len(ft) else None, float(max_fitness)))
 
 
+def rendezvous_consensus(hyps, n_hyp=None, **kw):
+    """lins_host_rendezvous_consensus: the definition of the consensus rule of a rendezvous over a window.  hyps: a list of
+    dicts (X 4 x 4 f64, p (3,), fitness, query, rank, target_slot, admissible) or a ConsensusHypC array (then n_hyp says how
+    many count); kw: fields of lins_consensus_params (max_translation=, min_cos_rotation=).  Returns dict(winner, support,
+    n_admissible, members (ascending indices)), or the C return code (a negative int) of a refusal."""
+    from ._ctypes_defs import ConsensusHypC, ConsensusParamsC, ConsensusResultC, consensus_params, consensus_table
+
+    L = lib()
+    arr = consensus_table(hyps) if isinstance(hyps, (list, tuple)) else hyps
+    n = len(hyps) if n_hyp is None else int(n_hyp)
+    prm, out = consensus_params(L, **kw), ConsensusResultC()
+    L.lins_host_rendezvous_consensus.argtypes = [C.POINTER(ConsensusHypC), C.c_int, C.POINTER(ConsensusParamsC), C.POINTER(ConsensusResultC)]
+    L.lins_host_rendezvous_consensus.restype = C.c_int
+    rc = L.lins_host_rendezvous_consensus(arr, n, C.byref(prm), C.byref(out))
+    return out.as_dict() if rc == 0 else rc
+
+
 def place_guess(pose_q, pose_c, shift, up_axis=1):
     """lins_host_place_guess -> T0 (4 x 4 f64), or the C return code of a refusal"""
     from ._ctypes_defs import KeyPoseC, key_pose

@@ -47,6 +47,8 @@ EXPORTS = [
     "lins_local_map_build_surround", "lins_local_map_build_surround_streams", "lins_streams_map_surround", "lins_streams_map_surround_list",
     "lins_keyposes_select_batch", "lins_keyposes_find_loop_batch", "lins_keyposes_surround_batch", "lins_keyposes_set_mode",
     "lins_keyposes_mode", "lins_last_keyposes_stats",
+    "lins_rendezvous_consensus_default_params", "lins_rendezvous_consensus_batch", "lins_last_rendezvous_consensus_stats",
+    "lins_rendezvous_window_step", "lins_last_rendezvous_window_stats",
 ]
 # the calls of include/lins_lifecycle.h, a list of their own (tests/test_abi_archive.py counts the lins_archive_* calls of
 # include/lins_map.h in EXPORTS); lib() resolves every one of them, so a library without them does not load
@@ -139,7 +141,8 @@ def lib():
         L.lins_last_reproject_stats.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
         for name in EXPORTS:
             if name not in ("lins_destroy", "lins_strerror", "lins_last_hip_error", "lins_last_search", "lins_loop_icp_default_params",
-                            "lins_boot_default_params", "lins_pose_graph_default_params", "lins_loop_step_default_params"):
+                            "lins_boot_default_params", "lins_pose_graph_default_params", "lins_loop_step_default_params",
+                            "lins_rendezvous_consensus_default_params"):
                 if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                     continue  # (an older build under A/B timing)
                 getattr(L, name).restype = C.c_int

@@ -1,7 +1,8 @@
 """Rendezvous (include/lins_team.h): the team search over the frames of many slots — the device calls on an
 ieskf.IeskfContext, and their definition on the CPU (include/lins_host.h lins_host_place_team_topk) — and the team map
 (include/lins_map.h lins_keyposes_team_select_batch; lins_host_team_select / _team_map): which key frames of a team of
-slots a merged local map takes.
+slots a merged local map takes.  Rendezvous over a window: consensus_batch / rendezvous_window_step (the rule's definition on the
+CPU is host.rendezvous_consensus).
 
 A query is (query_slot, query_id, now, min_gap_s); a rank is a dict(slot, id, shift, distance (np.float32), dk,
 candidates, status).  There is no fall-back: the device calls need liblins_ieskf.so and a GPU."""
@@ -85,6 +86,77 @@ def rendezvous_step(ctx, entries, target_slots, params=None, **kw):
                                        C.POINTER(RendezvousParamsC), C.POINTER(RendezvousResultC)]
     rc = L.lins_rendezvous_step(ctx._h, n, arr, len(slots), slots.ctypes.data if len(slots) else None, C.byref(prm), C.byref(tp), out)
     return [out[k].as_dict() for k in range(n)] if rc == 0 else rc
+
+
+def consensus_batch(ctx, tables, offsets=None, **kw):
+    """lins_rendezvous_consensus_batch: one launch over `tables`, each a list of hypothesis dicts (X, p, fitness, query, rank,
+    target_slot, admissible: host.rendezvous_consensus's).  offsets: the n + 1 offsets to pass instead of the tables' own
+    (for the refusals); kw: fields of lins_consensus_params.  Returns per table dict(winner, support, n_admissible, members),
+    or the C return code (a negative int) of a refused call."""
+    from ._ctypes_defs import ConsensusHypC, ConsensusParamsC, ConsensusResultC, consensus_params, consensus_table
+
+    L = _ieskf.lib()
+    n = len(tables)
+    arr = consensus_table([h for t in tables for h in t])
+    off = np.ascontiguousarray(np.cumsum([0] + [len(t) for t in tables]) if offsets is None else offsets, np.int32)
+    prm, out = consensus_params(L, **kw), (ConsensusResultC * max(n, 1))()
+    L.lins_rendezvous_consensus_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(ConsensusHypC), C.c_void_p, C.POINTER(ConsensusParamsC),
+                                                  C.POINTER(ConsensusResultC)]
+    rc = L.lins_rendezvous_consensus_batch(ctx._h, n, arr, off.ctypes.data, C.byref(prm), out)
+    return [out[e].as_dict() for e in range(n)] if rc == 0 else rc
+
+
+def consensus_stats(ctx):
+    """HIP-event ms of the last consensus launch"""
+    L = _ieskf.lib()
+    ms = C.c_float(0)
+    L.lins_last_rendezvous_consensus_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    ctx._check(L.lins_last_rendezvous_consensus_stats(ctx._h, C.byref(ms)))
+    return ms.value
+
+
+def rendezvous_window_step(ctx, entries, target_slots, params=None, consensus=None, **kw):
+    """lins_rendezvous_window_step: entries [(slot, now)] against the frames of target_slots; the last `window` frames of every
+    entry ask, and a merge is FOUND only where min_support of them agree.  params: a LoopStepParamsC (default:
+    lins_loop_step_default_params); consensus: a dict of lins_consensus_params fields (window=, stride=, min_support=,
+    max_translation=, min_cos_rotation=) over the defaults; kw: shortlist=, k=, min_sep=, max_distance=.  Returns the per-entry
+    result dicts (outcome, status, n_queries, n_hypotheses, winner, support, n_admissible, target_slot, target_id, members,
+    query_id, n_ranks, source, X (4 x 4 f64), hyp: the entry's hypotheses as dicts query, rank, admissible, member, cand,
+    target, icp), or the C return code (a negative int) of a refused call."""
+    from ._ctypes_defs import ConsensusParamsC, RendezvousHypothesisC, RendezvousWindowResultC, consensus_params
+
+    L = _ieskf.lib()
+    prm = params if params is not None else loop_step_params(L)
+    tp = rendezvous_params(L, **kw)
+    cp = consensus_params(L, **(consensus or {}))
+    n = len(entries)
+    per = max(int(cp.window), 1) * max(int(tp.team.k), 1)
+    arr = (RendezvousEntryC * max(n, 1))(*[RendezvousEntryC(int(s), 0, float(now)) for s, now in entries])
+    slots = np.ascontiguousarray(target_slots, np.int32)
+    out = (RendezvousWindowResultC * max(n, 1))()
+    hyp = (RendezvousHypothesisC * max(n * per, 1))()
+    L.lins_rendezvous_window_step.argtypes = [C.c_void_p, C.c_int, C.POINTER(RendezvousEntryC), C.c_int, C.c_void_p, C.POINTER(LoopStepParamsC),
+                                              C.POINTER(RendezvousParamsC), C.POINTER(ConsensusParamsC), C.POINTER(RendezvousWindowResultC),
+                                              C.POINTER(RendezvousHypothesisC)]
+    rc = L.lins_rendezvous_window_step(ctx._h, n, arr, len(slots), slots.ctypes.data if len(slots) else None, C.byref(prm), C.byref(tp),
+                                       C.byref(cp), out, hyp)
+    if rc != 0:
+        return rc
+    res = []
+    for e in range(n):
+        r = out[e].as_dict()
+        r["hyp"] = [hyp[e * per + x].as_dict() for x in range(r["n_hypotheses"])]
+        res.append(r)
+    return res
+
+
+def rendezvous_window_stats(ctx):
+    """dict(detect_ms, assemble_ms, align_ms, consensus_ms, total_ms) of the last window step (host clock)"""
+    L = _ieskf.lib()
+    v = [C.c_float(0) for _ in range(5)]
+    L.lins_last_rendezvous_window_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_float)] * 5
+    ctx._check(L.lins_last_rendezvous_window_stats(ctx._h, *[C.byref(x) for x in v]))
+    return dict(zip(("detect_ms", "assemble_ms", "align_ms", "consensus_ms", "total_ms"), [x.value for x in v]))
 
 
 def _xs(X, n):
