@@ -1,9 +1,11 @@
 // lins_loop_step_capi.hip — C ABI of the loop thread's step (include/lins_map.h lins_loop_step, lins_loop_closed_cloud):
 // performLoopClosure + correctPoses (LM:1033-1186, 1767-1795) for n slots in one call.  Host orchestration only: every
-// device stage is the batched call that already exists — lins_archive_assemble, lins_loop_icp_batch,
+// device stage is the batched call that already exists — lins_archive_assemble, lins_loop_icp_batch_from,
 // lins_pose_graph_solve, lins_pose_graph_apply_batch — run ONCE over the entries that reach it, so an entry's bits are
 // those of the explicit chain for its slot; what is decided between the stages is host/loop_step.h, the text
-// liblins_host.so exports.
+// liblins_host.so exports.  lins_loop_step and lins_loop_step_place are one function (step): the front end detects by
+// pose or by appearance, the assemble-and-align stage in the middle is the one the rendezvous steps share
+// (loop_verify.h, laid out by host/verify_plan.h), the back end is close_loops.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -20,6 +22,7 @@
 #include "lins_ctx_priv.h"
 #include "local_map.h"
 #include "loop_icp_math.h"
+#include "loop_verify.h"
 #include "place.h"
 #include "pose_graph.h"
 
@@ -47,12 +50,10 @@ LoopStepMem* mem_of(lins_ctx* ctx) {
   return (LoopStepMem*)*slot;
 }
 
-// the ranges of the calls the parameters are handed to: lins_archive_find_loop, lins_archive_assemble, lins_loop_icp_batch,
-// lins_pose_graph_solve
+// the ranges of the calls the parameters are handed to: lins_archive_find_loop, lins_archive_assemble,
+// lins_loop_icp_batch_from, lins_pose_graph_solve
 bool params_ok(const lins_loop_step_params* p) {
-  return p && std::isfinite(p->search_radius) && p->search_radius >= 0.f && !std::isnan(p->max_fitness) && std::isfinite(p->history_leaf) &&
-         p->history_leaf >= 0.f && p->search_num >= 0 && !std::isnan(p->min_gap_s) && p->icp.max_iterations >= 1 && p->icp.min_correspondences >= 0 &&
-         std::isfinite(p->icp.max_corr_dist) && lins_pg::params_ok(&p->graph);
+  return lins_verify::params_ok(p) && std::isfinite(p->search_radius) && p->search_radius >= 0.f && lins_pg::params_ok(&p->graph);
 }
 
 // entry k's step record: lins_loop_step's results are an array of them, lins_loop_step_place's begin with one
@@ -149,6 +150,148 @@ int close_loops(lins_ctx* ctx, LoopStepMem* m, const lins_loop_step_params* prm,
   return LINS_OK;
 }
 
+// Both entry points, arguments and parameters checked: check -> detect -> plan -> verify_assemble -> start transforms ->
+// verify_align -> choose -> close_loops.  `out`: records `stride` bytes apart that begin with a step record (step_at).
+// place == nullptr: lins_loop_step — the records are step records, every entry is detected by pose (one hypothesis) and
+// the place store `ap` is not read; else they are lins_loop_place_result.
+int step(lins_ctx* ctx, int n, const lins_loop_step_entry* entries, const lins_loop_step_params* prm, const lins_loop_place_params* place,
+         const ArchivePlace* ap, void* out, size_t stride) {
+  lins_loop_place_result* po = place ? (lins_loop_place_result*)out : nullptr;
+  const bool pose_first = !place || place->mode == LINS_LOOP_DETECT_POSE_THEN_PLACE;
+  const int K = place ? place->k : 1, min_sep = !place ? 0 : place->min_sep < 0 ? prm->search_num : place->min_sep;
+  // ---- the whole call's errors, before anything is queued ----
+  std::vector<int32_t> slots, streams, closest(n, -1);
+  std::vector<float> centre;
+  if (int rc = check_call(ctx, n, entries, prm, pose_first, slots, streams, centre)) return rc;
+  if (place && (long long)n * (1 + K) > 2147483647ll) return LINS_E_CAPACITY;  // (specs of one assembly; the n K alignments are fewer)
+
+  LoopStepMem* m = mem_of(ctx);
+  m->last.assign(n, Aligned());
+  m->assemble_ms = m->icp_ms = m->solve_ms = 0.f, m->candidates = m->aligned = m->closed = 0;
+  // ---- detect: the pose search where the mode asks for it, then one top-K search over the entries it left empty-handed ----
+  if (pose_first)
+    if (int rc = pose_detect(ctx, n, entries, prm, slots, centre, closest)) return rc;
+  std::vector<int> asking;  // entries of the place search
+  std::vector<lins_place_query> qs;
+  for (int k = 0; k < n; ++k) {
+    lins_loop_step_result& r = step_at(out, stride, k);
+    std::memset((void*)&r, 0, stride);
+    r.outcome = LINS_LOOP_NONE, r.latest_id = lins_archive_count(ctx, slots[k]) - 1, r.closest_id = -1;
+    if (!po) continue;
+    po[k].chosen = -1;
+    for (int j = 0; j < LINS_PLACE_MAX_K; ++j) po[k].cand[j].id = -1, po[k].cand[j].distance = 1.f;
+    if (r.latest_id < 0 || closest[k] >= 0) continue;  // (detect 0: lins_loop_step's entry)
+    po[k].detect = 1;
+    asking.push_back(k);
+    qs.push_back(lins_place_query{slots[k], r.latest_id, slots[k], 0, entries[k].now, prm->min_gap_s});
+  }
+  std::vector<lins_place_result> found(qs.size() * (size_t)K);
+  std::vector<int32_t> filled(qs.size(), 0);
+  if (!qs.empty())
+    if (int rc = lins_place_topk_batch(ctx, (int)qs.size(), qs.data(), K, min_sep, found.data(), filled.data())) return rc;
+  std::vector<int> at_query(n, -1);
+  for (size_t i = 0; i < asking.size(); ++i) at_query[asking[i]] = (int)i;
+  // ---- plan: per candidate entry the latest frame against one history window per rank ----
+  Verify v;
+  for (int k = 0; k < n; ++k) {
+    lins_loop_step_result& r = step_at(out, stride, k);
+    if (r.latest_id < 0) continue;
+    int loops_left = 0, last_latest = -1, last_closest = -1, what = LINS_LOOP_NONE, nc = 0;
+    int32_t ids[LINS_PLACE_MAX_K];  // the frames that go to the alignment
+    pose_graph_room(ctx, slots[k], nullptr, &loops_left, &last_latest, &last_closest);
+    if (!po || !po[k].detect) {
+      r.closest_id = closest[k];
+      what = lins_loop::candidate(r.latest_id, r.closest_id, last_latest, last_closest);
+      if (what == lins_loop::kAlign) ids[nc++] = r.closest_id;
+      if (po && nc) po[k].cand[0].id = r.closest_id;
+    } else {
+      const lins_place_result* f = &found[(size_t)at_query[k] * K];
+      for (int j = 0; j < filled[at_query[k]]; ++j) {
+        if (f[j].distance > place->max_distance) continue;
+        const int w = lins_loop::candidate(r.latest_id, f[j].id, last_latest, last_closest);
+        if (w == LINS_LOOP_REPEAT) what = LINS_LOOP_REPEAT;
+        if (w == lins_loop::kAlign) po[k].cand[nc] = f[j], ids[nc++] = f[j].id;
+      }
+      if (nc) what = lins_loop::kAlign;
+    }
+    if (what != lins_loop::kAlign) {
+      r.outcome = what;
+    } else if (loops_left < 1) {
+      r.status = LINS_E_CAPACITY;
+      for (int j = 0; po && j < LINS_PLACE_MAX_K; ++j) po[k].cand[j] = lins_place_result{-1, 0, 1.f, 0, 0, 0};
+    } else {
+      if (po) po[k].n_candidates = nc;
+      v.entry(k, slots[k]);
+      for (int j = 0; j < nc; ++j) v.hyp(r.latest_id, slots[k], ids[j], r.latest_id);
+    }
+  }
+  m->candidates = v.n();
+  if (v.n() == 0) return LINS_OK;
+  // ---- assemble ----
+  if (int rc = verify_assemble(ctx, v, prm->search_num, prm->history_leaf)) return rc;
+  (void)lins_last_archive_stats(ctx, &m->assemble_ms, nullptr);
+  ArchiveView av{};
+  if (int rc = archive_view(ctx, &av)) return rc;
+  m->serial = av.serial;
+  // ---- start transforms: the appearance's guess, or the identity (lins_loop_icp_batch's start) ----
+  std::vector<double> T0(16 * v.hyps.size(), 0.0);
+  for (int i = 0; i < v.n(); ++i) {
+    const int k = v.of[i], x0 = v.hyp0[i];
+    const bool detect = po && po[k].detect;
+    lins_loop_step_result& r = step_at(out, stride, k);
+    r.latest = v.infos[v.src_spec[x0]];
+    if (!detect) r.history = v.infos[v.tgt_spec[x0]];
+    if (v.status[i]) {  // (nothing is aligned for it)
+      r.status = v.status[i];
+      continue;
+    }
+    for (int x = x0; x < v.hyp0[i + 1]; ++x) {
+      double* T = &T0[16 * (size_t)x];
+      if (detect) {
+        const std::vector<ArFrame>& fr = (*ap->frames)[slots[k]];
+        const lins_place_result& c = po[k].cand[x - x0];
+        lins_place::guess(fr[r.latest_id].pose, fr[c.id].pose, c.shift, ap->store->prm.up_axis, T);
+      } else {
+        T[0] = T[5] = T[10] = T[15] = 1.0;
+      }
+    }
+  }
+  // ---- align ----
+  if (int rc = verify_align(ctx, v, T0.data(), &prm->icp)) return rc;
+  if (!v.n_ran) return LINS_OK;
+  (void)lins_last_loop_icp_stats(ctx, &m->icp_ms, nullptr);
+  // ---- choose: the best accepted fit of every entry goes on to the tail ----
+  std::vector<int> judged;  // entries
+  for (int i = 0; i < v.n(); ++i) {
+    if (v.status[i]) continue;
+    const int k = v.of[i], x0 = v.hyp0[i], nc = v.hyp0[i + 1] - x0;
+    const bool detect = po && po[k].detect;
+    const lins_loop_icp_result* icp = &v.icp[x0];
+    lins_loop_step_result& r = step_at(out, stride, k);
+    int32_t conv[LINS_PLACE_MAX_K];
+    double fit[LINS_PLACE_MAX_K];
+    if (po) std::memcpy(po[k].icp, icp, nc * sizeof icp[0]);
+    const lins_verify::IcpSummary s = lins_verify::icp_summary(icp, nc, conv, fit);
+    if (!detect) r.icp = icp[0];
+    if (!s.ran) {
+      r.status = s.status;
+      continue;
+    }
+    m->aligned += 1;
+    r.outcome = LINS_LOOP_REJECTED;
+    const int chosen = lins_loop::choose(nc, conv, fit, prm->max_fitness);
+    if (po) po[k].chosen = chosen;
+    if (detect) {
+      if (chosen < 0) continue;
+      r.closest_id = po[k].cand[chosen].id, r.history = v.infos[v.tgt_spec[x0 + chosen]], r.icp = icp[chosen];
+    }
+    m->last[k].source = v.src_spec[x0];
+    std::memcpy(m->last[k].T, r.icp.transform, sizeof r.icp.transform);
+    judged.push_back(k);
+  }
+  return close_loops(ctx, m, prm, slots, streams, judged, out, stride);
+}
+
 }  // namespace
 
 extern "C" {
@@ -164,90 +307,7 @@ int lins_loop_step(lins_ctx* ctx, int n, const lins_loop_step_entry* entries, co
   if (!ctx || n < 0 || (n && (!entries || !out))) return LINS_E_ARG;
   if (lins_archive_count(ctx, 0) == LINS_E_STATE || !pose_graph_slots(ctx)) return LINS_E_STATE;
   if (!params_ok(prm)) return LINS_E_ARG;
-  // ---- the whole call's errors, before anything is queued ----
-  std::vector<int32_t> slots, streams, closest;
-  std::vector<float> centre;
-  if (int rc = check_call(ctx, n, entries, prm, true, slots, streams, centre)) return rc;
-
-  LoopStepMem* m = mem_of(ctx);
-  m->last.assign(n, Aligned());
-  m->assemble_ms = m->icp_ms = m->solve_ms = 0.f, m->candidates = m->aligned = m->closed = 0;
-  // ---- detect (host work: keyframe_select.h, loop_step.h) ----
-  std::vector<int> cand;  // entries that go to the assembly
-  if (int rc = pose_detect(ctx, n, entries, prm, slots, centre, closest)) return rc;
-  for (int k = 0; k < n; ++k) {
-    lins_loop_step_result& r = out[k];
-    std::memset(&r, 0, sizeof r);
-    r.outcome = LINS_LOOP_NONE, r.latest_id = lins_archive_count(ctx, slots[k]) - 1, r.closest_id = -1;
-    if (r.latest_id < 0) continue;
-    r.closest_id = closest[k];
-    int loops_left = 0, last_latest = -1, last_closest = -1;
-    pose_graph_room(ctx, slots[k], nullptr, &loops_left, &last_latest, &last_closest);
-    const int what = lins_loop::candidate(r.latest_id, r.closest_id, last_latest, last_closest);
-    if (what != lins_loop::kAlign) {
-      r.outcome = what;
-    } else if (loops_left < 1) {
-      r.status = LINS_E_CAPACITY;
-    } else {
-      cand.push_back(k);
-    }
-  }
-  const int nc = (int)cand.size();
-  m->candidates = nc;
-  if (nc == 0) return LINS_OK;
-  // ---- assemble: per candidate the latest frame and the history window, one call ----
-  std::vector<std::vector<int32_t>> ids(2 * (size_t)nc);
-  std::vector<lins_submap_spec> specs(2 * (size_t)nc);
-  std::vector<lins_submap_info> infos(2 * (size_t)nc);
-  for (int i = 0; i < nc; ++i) {
-    const lins_loop_step_result& r = out[cand[i]];
-    ids[2 * i].assign(1, r.latest_id);
-    ids[2 * i + 1].resize(lins_loop::window_size(r.latest_id, r.closest_id, prm->search_num));
-    lins_loop::window(r.latest_id, r.closest_id, prm->search_num, ids[2 * i + 1].data());
-    specs[2 * i] = lins_submap_spec{ids[2 * i].data(), 1, slots[cand[i]], LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF, LINS_SUBMAP_DROP_NEGATIVE, 0.f, 0};
-    specs[2 * i + 1] = lins_submap_spec{ids[2 * i + 1].data(), (int32_t)ids[2 * i + 1].size(), slots[cand[i]], LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF, 0,
-                                        prm->history_leaf, 0};
-  }
-  if (int rc = lins_archive_assemble(ctx, 2 * nc, specs.data(), infos.data())) return rc;
-  (void)lins_last_archive_stats(ctx, &m->assemble_ms, nullptr);
-  ArchiveView av{};
-  if (int rc = archive_view(ctx, &av)) return rc;
-  m->serial = av.serial;
-  // ---- align: one batch over the entries whose assemblies have no status ----
-  std::vector<int> run;  // positions in cand
-  std::vector<lins_loop_icp_problem> probs;
-  for (int i = 0; i < nc; ++i) {
-    lins_loop_step_result& r = out[cand[i]];
-    r.latest = infos[2 * i], r.history = infos[2 * i + 1];
-    if (r.latest.status || r.history.status) {
-      r.status = r.latest.status ? r.latest.status : r.history.status;
-      continue;
-    }
-    run.push_back(i);
-    probs.push_back(lins_loop_icp_problem{2 * i, 2 * i + 1, nullptr, nullptr, 0, 0});
-  }
-  const int na = (int)run.size();
-  if (na == 0) return LINS_OK;
-  std::vector<lins_loop_icp_result> icp(na);
-  if (int rc = lins_loop_icp_batch(ctx, na, probs.data(), &prm->icp, icp.data())) return rc;
-  (void)lins_last_loop_icp_stats(ctx, &m->icp_ms, nullptr);
-  // ---- the factor of every accepted entry, the solve, the correction (close_loops) ----
-  std::vector<int> judged;  // entries
-  for (int j = 0; j < na; ++j) {
-    const int k = cand[run[j]];
-    lins_loop_step_result& r = out[k];
-    r.icp = icp[j];
-    if (r.icp.status) {  // (a target box beyond the gridding's limit: nothing was run)
-      r.status = r.icp.status;
-      continue;
-    }
-    m->last[k].source = 2 * run[j];
-    std::memcpy(m->last[k].T, r.icp.transform, sizeof r.icp.transform);
-    m->aligned += 1;
-    r.outcome = LINS_LOOP_REJECTED;
-    judged.push_back(k);
-  }
-  return close_loops(ctx, m, prm, slots, streams, judged, out, sizeof(lins_loop_step_result));
+  return step(ctx, n, entries, prm, nullptr, nullptr, out, sizeof *out);
 }
 
 void lins_loop_place_default_params(lins_loop_place_params* p) {
@@ -256,7 +316,7 @@ void lins_loop_place_default_params(lins_loop_place_params* p) {
   p->mode = LINS_LOOP_DETECT_PLACE, p->k = 4, p->min_sep = -1, p->max_distance = 1.f;
 }
 
-// (include/lins_place.h) lins_loop_step with the candidates found by appearance: every stage below is ONE batched call
+// (include/lins_place.h) lins_loop_step with the candidates found by appearance: every stage is ONE batched call
 int lins_loop_step_place(lins_ctx* ctx, int n, const lins_loop_step_entry* entries, const lins_loop_step_params* prm,
                          const lins_loop_place_params* place, lins_loop_place_result* out) {
   if (!ctx || n < 0 || (n && (!entries || !out))) return LINS_E_ARG;
@@ -264,177 +324,10 @@ int lins_loop_step_place(lins_ctx* ctx, int n, const lins_loop_step_entry* entri
   ArchivePlace ap;
   if (archive_place(ctx, &ap) || !ap.store->on) return LINS_E_STATE;
   if (!params_ok(prm) || !place) return LINS_E_ARG;
-  const bool pose_first = place->mode == LINS_LOOP_DETECT_POSE_THEN_PLACE;
-  if ((place->mode != LINS_LOOP_DETECT_PLACE && !pose_first) || place->k < 1 || place->k > LINS_PLACE_MAX_K || place->min_sep < -1 ||
-      std::isnan(place->max_distance))
+  if ((place->mode != LINS_LOOP_DETECT_PLACE && place->mode != LINS_LOOP_DETECT_POSE_THEN_PLACE) || place->k < 1 || place->k > LINS_PLACE_MAX_K ||
+      place->min_sep < -1 || std::isnan(place->max_distance))
     return LINS_E_ARG;
-  const int K = place->k, min_sep = place->min_sep < 0 ? prm->search_num : place->min_sep;
-  // ---- the whole call's errors, before anything is queued ----
-  std::vector<int32_t> slots, streams, closest(n, -1);
-  std::vector<float> centre;
-  if (int rc = check_call(ctx, n, entries, prm, pose_first, slots, streams, centre)) return rc;
-  if ((long long)n * (1 + K) > 2147483647ll) return LINS_E_CAPACITY;  // (specs of one assembly; the n K alignments are fewer)
-
-  LoopStepMem* m = mem_of(ctx);
-  m->last.assign(n, Aligned());
-  m->assemble_ms = m->icp_ms = m->solve_ms = 0.f, m->candidates = m->aligned = m->closed = 0;
-  const size_t stride = sizeof(lins_loop_place_result);
-  // ---- detect: the pose search where the mode asks for it, then one top-K search over the entries it left empty-handed ----
-  if (pose_first)
-    if (int rc = pose_detect(ctx, n, entries, prm, slots, centre, closest)) return rc;
-  std::vector<int> asking;  // entries of the place search
-  std::vector<lins_place_query> qs;
-  for (int k = 0; k < n; ++k) {
-    lins_loop_place_result& o = out[k];
-    std::memset(&o, 0, sizeof o);
-    o.step.outcome = LINS_LOOP_NONE, o.step.latest_id = lins_archive_count(ctx, slots[k]) - 1, o.step.closest_id = -1, o.chosen = -1;
-    for (int j = 0; j < LINS_PLACE_MAX_K; ++j) o.cand[j].id = -1, o.cand[j].distance = 1.f;
-    if (o.step.latest_id < 0) continue;
-    if (closest[k] >= 0) continue;  // (detect 0: lins_loop_step's entry)
-    o.detect = 1;
-    asking.push_back(k);
-    qs.push_back(lins_place_query{slots[k], o.step.latest_id, slots[k], 0, entries[k].now, prm->min_gap_s});
-  }
-  std::vector<lins_place_result> found(qs.size() * (size_t)K);
-  std::vector<int32_t> filled(qs.size(), 0);
-  if (!qs.empty())
-    if (int rc = lins_place_topk_batch(ctx, (int)qs.size(), qs.data(), K, min_sep, found.data(), filled.data())) return rc;
-  std::vector<int> at_query(n, -1);
-  for (size_t i = 0; i < asking.size(); ++i) at_query[asking[i]] = (int)i;
-  std::vector<int> cand;  // entries that go to the assembly
-  for (int k = 0; k < n; ++k) {
-    lins_loop_place_result& o = out[k];
-    lins_loop_step_result& r = o.step;
-    if (r.latest_id < 0) continue;
-    int loops_left = 0, last_latest = -1, last_closest = -1, what = LINS_LOOP_NONE;
-    pose_graph_room(ctx, slots[k], nullptr, &loops_left, &last_latest, &last_closest);
-    if (!o.detect) {
-      r.closest_id = closest[k];
-      what = lins_loop::candidate(r.latest_id, r.closest_id, last_latest, last_closest);
-      if (what == lins_loop::kAlign) o.cand[0].id = r.closest_id, o.n_candidates = 1;
-    } else {
-      const lins_place_result* f = &found[(size_t)at_query[k] * K];
-      for (int j = 0; j < filled[at_query[k]]; ++j) {
-        if (f[j].distance > place->max_distance) continue;
-        const int w = lins_loop::candidate(r.latest_id, f[j].id, last_latest, last_closest);
-        if (w == LINS_LOOP_REPEAT) what = LINS_LOOP_REPEAT;
-        if (w == lins_loop::kAlign) o.cand[o.n_candidates++] = f[j];
-      }
-      if (o.n_candidates) what = lins_loop::kAlign;
-    }
-    if (what != lins_loop::kAlign) {
-      r.outcome = what;
-    } else if (loops_left < 1) {
-      r.status = LINS_E_CAPACITY, o.n_candidates = 0;
-      for (int j = 0; j < LINS_PLACE_MAX_K; ++j) o.cand[j] = lins_place_result{-1, 0, 1.f, 0, 0, 0};
-    } else {
-      cand.push_back(k);
-    }
-  }
-  const int nc = (int)cand.size();
-  m->candidates = nc;
-  if (nc == 0) return LINS_OK;
-  // ---- assemble: per candidate entry the latest frame, then one history window per rank; one call ----
-  std::vector<int> first(nc + 1, 0);  // an entry's first spec (its source)
-  for (int i = 0; i < nc; ++i) first[i + 1] = first[i] + 1 + out[cand[i]].n_candidates;
-  const int n_specs = first[nc];
-  std::vector<std::vector<int32_t>> ids(n_specs);
-  std::vector<lins_submap_spec> specs(n_specs);
-  std::vector<lins_submap_info> infos(n_specs);
-  for (int i = 0; i < nc; ++i) {
-    const lins_loop_place_result& o = out[cand[i]];
-    const int latest = o.step.latest_id, s0 = first[i];
-    ids[s0].assign(1, latest);
-    specs[s0] = lins_submap_spec{ids[s0].data(), 1, slots[cand[i]], LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF, LINS_SUBMAP_DROP_NEGATIVE, 0.f, 0};
-    for (int j = 0; j < o.n_candidates; ++j) {
-      std::vector<int32_t>& w = ids[s0 + 1 + j];
-      w.resize(lins_loop::window_size(latest, o.cand[j].id, prm->search_num));
-      lins_loop::window(latest, o.cand[j].id, prm->search_num, w.data());
-      specs[s0 + 1 + j] = lins_submap_spec{w.data(), (int32_t)w.size(), slots[cand[i]], LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF, 0, prm->history_leaf, 0};
-    }
-  }
-  if (int rc = lins_archive_assemble(ctx, n_specs, specs.data(), infos.data())) return rc;
-  (void)lins_last_archive_stats(ctx, &m->assemble_ms, nullptr);
-  ArchiveView av{};
-  if (int rc = archive_view(ctx, &av)) return rc;
-  m->serial = av.serial;
-  // ---- align: one batch over every (entry, rank) of the entries whose assemblies have no status ----
-  std::vector<int> run;  // positions in cand
-  std::vector<int> prob0;  // their first problem
-  std::vector<lins_loop_icp_problem> probs;
-  std::vector<double> T0;
-  const std::vector<std::vector<ArFrame>>& frames = *ap.frames;
-  for (int i = 0; i < nc; ++i) {
-    lins_loop_place_result& o = out[cand[i]];
-    lins_loop_step_result& r = o.step;
-    r.latest = infos[first[i]];
-    if (!o.detect) r.history = infos[first[i] + 1];
-    int status = r.latest.status;
-    for (int j = 0; j < o.n_candidates && !status; ++j) status = infos[first[i] + 1 + j].status;
-    if (status) {  // (the entry's first: nothing is aligned for it)
-      r.status = status;
-      continue;
-    }
-    run.push_back(i), prob0.push_back((int)probs.size());
-    for (int j = 0; j < o.n_candidates; ++j) {
-      probs.push_back(lins_loop_icp_problem{first[i], first[i] + 1 + j, nullptr, nullptr, 0, 0});
-      T0.resize(T0.size() + 16, 0.0);
-      double* T = &T0[T0.size() - 16];
-      if (o.detect) {
-        const std::vector<ArFrame>& fr = frames[slots[cand[i]]];
-        lins_place::guess(fr[r.latest_id].pose, fr[o.cand[j].id].pose, o.cand[j].shift, ap.store->prm.up_axis, T);
-      } else {
-        T[0] = T[5] = T[10] = T[15] = 1.0;  // (lins_loop_icp_batch's start)
-      }
-    }
-  }
-  if (run.empty()) return LINS_OK;
-  std::vector<lins_loop_icp_result> icp(probs.size());
-  if (int rc = lins_loop_icp_batch_from(ctx, (int)probs.size(), probs.data(), T0.data(), &prm->icp, icp.data())) return rc;
-  (void)lins_last_loop_icp_stats(ctx, &m->icp_ms, nullptr);
-  // ---- choose: the best accepted fit of every entry goes on to the tail ----
-  std::vector<int> judged;  // entries
-  for (size_t a = 0; a < run.size(); ++a) {
-    const int i = run[a], k = cand[i];
-    lins_loop_place_result& o = out[k];
-    lins_loop_step_result& r = o.step;
-    int32_t conv[LINS_PLACE_MAX_K];
-    double fit[LINS_PLACE_MAX_K];
-    int status = 0, ran = 0;
-    for (int j = 0; j < o.n_candidates; ++j) {
-      o.icp[j] = icp[prob0[a] + j];
-      conv[j] = o.icp[j].status ? 0 : o.icp[j].converged, fit[j] = o.icp[j].fitness;  // (a target box beyond the gridding's limit: nothing was run)
-      if (o.icp[j].status && !status) status = o.icp[j].status;
-      ran += o.icp[j].status ? 0 : 1;
-    }
-    if (!o.detect) {  // lins_loop_step's entry
-      r.icp = o.icp[0];
-      if (status) {
-        r.status = status;
-        continue;
-      }
-      o.chosen = lins_loop::choose(1, conv, fit, prm->max_fitness);
-      m->last[k].source = first[i];
-      std::memcpy(m->last[k].T, r.icp.transform, sizeof r.icp.transform);
-      m->aligned += 1;
-      r.outcome = LINS_LOOP_REJECTED;
-      judged.push_back(k);
-      continue;
-    }
-    if (!ran) {
-      r.status = status;
-      continue;
-    }
-    m->aligned += 1;
-    r.outcome = LINS_LOOP_REJECTED;
-    o.chosen = lins_loop::choose(o.n_candidates, conv, fit, prm->max_fitness);
-    if (o.chosen < 0) continue;
-    r.closest_id = o.cand[o.chosen].id, r.history = infos[first[i] + 1 + o.chosen], r.icp = o.icp[o.chosen];
-    m->last[k].source = first[i];
-    std::memcpy(m->last[k].T, r.icp.transform, sizeof r.icp.transform);
-    judged.push_back(k);
-  }
-  return close_loops(ctx, m, prm, slots, streams, judged, out, stride);
+  return step(ctx, n, entries, prm, place, &ap, out, sizeof *out);
 }
 
 int lins_loop_closed_cloud(lins_ctx* ctx, int entry, lins_point* out, int cap) {

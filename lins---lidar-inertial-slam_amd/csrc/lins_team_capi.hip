@@ -7,7 +7,9 @@
 // lins_rendezvous_step is host orchestration only, as lins_loop_step_place is: every device stage is a batched call that
 // exists, run ONCE over the entries that reach it.  lins_rendezvous_window_step is the same composition over the last
 // frames of every entry, with one more stage: lins_rendezvous_consensus_batch (rendezvous_consensus_kernels.hip; its
-// staging is place.h ConsensusStore) decides which alignments agree.
+// staging is place.h ConsensusStore) decides which alignments agree.  The two share their checks (rendezvous_check,
+// assembly_room) and, with the loop thread's steps, the assemble-and-align stage in the middle (loop_verify.h, laid out
+// by host/verify_plan.h); each keeps its own detect filter and its own decision.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,6 +28,7 @@
 #include "lins_ctx_priv.h"
 #include "lins_launch.h"
 #include "local_map.h"
+#include "loop_verify.h"
 #include "place.h"
 
 using namespace lins;
@@ -154,6 +157,66 @@ int slots_check(const ArchivePlace& A, int n_targets, const int32_t* slots) {
   return LINS_OK;
 }
 
+// ---- what the two rendezvous steps share in front of their detect stages ----
+// The whole call's errors, before anything is queued; *tp: the team search's parameters, min_sep resolved.
+int rendezvous_check(const ArchivePlace& A, int n, const lins_rendezvous_entry* entries, int n_targets, const int32_t* target_slots,
+                     const lins_loop_step_params* prm, const lins_rendezvous_params* team, lins_place_team_params* tp) {
+  if (!lins_verify::params_ok(prm) || !team) return LINS_E_ARG;
+  *tp = team->team;
+  if (tp->min_sep < -1 || std::isnan(team->max_distance)) return LINS_E_ARG;
+  if (tp->min_sep < 0) tp->min_sep = prm->search_num;
+  if (!team_params_ok(tp)) return LINS_E_ARG;
+  if (int rc = slots_check(A, n_targets, target_slots)) return rc;
+  for (int k = 0; k < n; ++k) {
+    if (entries[k].slot < 0 || entries[k].slot >= A.n_slots) return LINS_E_ARG;
+    for (int i = 0; i < k; ++i)
+      if (entries[i].slot == entries[k].slot) return LINS_E_ARG;
+  }
+  for (int k = 0; k < n; ++k)
+    if (!std::isfinite(entries[k].now)) return LINS_E_INPUT;
+  return LINS_OK;
+}
+
+// the frames of a slot with `count` frames that ask, of a window of W: latest - j * stride, while it exists
+int queries_of(int count, int W, int stride) {
+  int nq = 0;
+  while (nq < W && (long long)(count - 1) - (long long)nq * stride >= 0) ++nq;
+  return nq;
+}
+
+// What lins_archive_assemble refuses (a submap of more than INT_MAX / 2 points, more than INT_MAX / 256 tiles in a call),
+// asked of the most the assembly can be given — the ranks are not known yet: K windows a query, every window as large as
+// the largest target slot's whole history.  So the assembly behind the detect stage cannot refuse.  (lins_rendezvous_step:
+// a window of one.)
+int assembly_room(const std::vector<std::vector<ArFrame>>& frames, int n, const lins_rendezvous_entry* entries, int n_targets,
+                  const int32_t* target_slots, int K, int W, int stride) {
+  if ((long long)n * W * (1 + K) > 2147483647ll) return LINS_E_CAPACITY;
+  auto both = [](const ArFrame& f) { return (long long)f.n[0] + f.n[1]; };  // corner | surf
+  long long widest = 0, tiles = 0;
+  for (int t = 0; t < n_targets; ++t) {
+    long long sum = 0;
+    for (const ArFrame& f : frames[target_slots[t]]) sum += both(f);
+    widest = std::max(widest, sum);
+  }
+  if (widest > INT_MAX / 2) return LINS_E_CAPACITY;
+  for (int k = 0; k < n; ++k) {
+    const std::vector<ArFrame>& fr = frames[entries[k].slot];
+    const int nq = queries_of((int)fr.size(), W, stride);
+    for (int j = 0; j < nq; ++j)
+      tiles += (both(fr[fr.size() - 1 - (size_t)j * stride]) + kLmTile - 1) / kLmTile + (long long)K * ((widest + kLmTile - 1) / kLmTile);
+    if (tiles > INT_MAX / 256) return LINS_E_CAPACITY;
+  }
+  return LINS_OK;
+}
+
+// a result record before anything is known of its entry
+template <class R>
+R& blank(R& o) {
+  std::memset(&o, 0, sizeof o);
+  o.outcome = LINS_RENDEZVOUS_NONE, o.target_slot = o.target_id = -1;
+  return o;
+}
+
 }  // namespace
 
 extern "C" {
@@ -230,50 +293,17 @@ int lins_rendezvous_step(lins_ctx* ctx, int n, const lins_rendezvous_entry* entr
   ArchivePlace A;
   if (int rc = store_of(ctx, &A)) return rc;
   // ---- the whole call's errors, before anything is queued ----
-  if (!prm || !team || std::isnan(prm->max_fitness) || !std::isfinite(prm->history_leaf) || prm->history_leaf < 0.f || prm->search_num < 0 ||
-      std::isnan(prm->min_gap_s) || prm->icp.max_iterations < 1 || prm->icp.min_correspondences < 0 || !std::isfinite(prm->icp.max_corr_dist))
-    return LINS_E_ARG;
-  lins_place_team_params tp = team->team;
-  if (tp.min_sep < -1 || std::isnan(team->max_distance)) return LINS_E_ARG;
-  if (tp.min_sep < 0) tp.min_sep = prm->search_num;
-  if (!team_params_ok(&tp)) return LINS_E_ARG;
-  if (int rc = slots_check(A, n_targets, target_slots)) return rc;
-  for (int k = 0; k < n; ++k) {
-    if (entries[k].slot < 0 || entries[k].slot >= A.n_slots) return LINS_E_ARG;
-    for (int i = 0; i < k; ++i)
-      if (entries[i].slot == entries[k].slot) return LINS_E_ARG;
-  }
-  for (int k = 0; k < n; ++k)
-    if (!std::isfinite(entries[k].now)) return LINS_E_INPUT;
+  lins_place_team_params tp;
+  if (int rc = rendezvous_check(A, n, entries, n_targets, target_slots, prm, team, &tp)) return rc;
   const int K = tp.k;
-  if ((long long)n * (1 + K) > 2147483647ll) return LINS_E_CAPACITY;
   const std::vector<std::vector<ArFrame>>& frames = *A.frames;
-  // what lins_archive_assemble refuses (a submap of more than INT_MAX / 2 points, more than INT_MAX / 256 tiles in a call),
-  // asked of the most the assembly can be given — the ranks are not known yet: every window as large as the largest
-  // target slot's whole history.  So the assembly behind the detect stage cannot refuse.
-  {
-    auto both = [](const ArFrame& f) { return (long long)f.n[0] + f.n[1]; };  // corner | surf
-    long long widest = 0, tiles = 0;
-    for (int t = 0; t < n_targets; ++t) {
-      long long sum = 0;
-      for (const ArFrame& f : frames[target_slots[t]]) sum += both(f);
-      widest = std::max(widest, sum);
-    }
-    if (widest > INT_MAX / 2) return LINS_E_CAPACITY;
-    for (int k = 0; k < n; ++k) {
-      const std::vector<ArFrame>& fr = frames[entries[k].slot];
-      if (fr.empty()) continue;
-      tiles += (both(fr.back()) + kLmTile - 1) / kLmTile + (long long)K * ((widest + kLmTile - 1) / kLmTile);
-    }
-    if (tiles > INT_MAX / 256) return LINS_E_CAPACITY;
-  }
+  if (int rc = assembly_room(frames, n, entries, n_targets, target_slots, K, 1, 1)) return rc;
   // ---- detect: one team search over the entries that have a frame ----
   std::vector<int> asking;
   std::vector<lins_place_team_query> qs;
   for (int k = 0; k < n; ++k) {
-    lins_rendezvous_result& o = out[k];
-    std::memset(&o, 0, sizeof o);
-    o.outcome = LINS_RENDEZVOUS_NONE, o.latest_id = (int)frames[entries[k].slot].size() - 1, o.chosen = o.target_slot = o.target_id = -1;
+    lins_rendezvous_result& o = blank(out[k]);
+    o.latest_id = (int)frames[entries[k].slot].size() - 1, o.chosen = -1;
     for (int j = 0; j < LINS_PLACE_MAX_K; ++j) o.cand[j].slot = o.cand[j].id = o.cand[j].dk = -1, o.cand[j].distance = 1.f;
     if (o.latest_id < 0) continue;
     asking.push_back(k);
@@ -283,78 +313,43 @@ int lins_rendezvous_step(lins_ctx* ctx, int n, const lins_rendezvous_entry* entr
   std::vector<lins_place_team_result> found(qs.size() * (size_t)K);
   std::vector<int32_t> filled(qs.size(), 0);
   if (int rc = run(ctx, A, (int)qs.size(), qs.data(), n_targets, target_slots, tp, found.data(), filled.data())) return rc;
-  std::vector<int> cand;  // entries that go to the assembly
+  // ---- plan: per entry its latest frame against one window per rank, from the rank's own slot ----
+  Verify v;
   for (size_t a = 0; a < asking.size(); ++a) {
     lins_rendezvous_result& o = out[asking[a]];
     for (int j = 0; j < filled[a]; ++j)
       if (!(found[a * K + j].distance > team->max_distance)) o.cand[o.n_candidates++] = found[a * K + j];
-    if (o.n_candidates) cand.push_back(asking[a]);
+    if (o.n_candidates) v.entry(asking[a], entries[asking[a]].slot);
+    for (int j = 0; j < o.n_candidates; ++j) v.hyp(o.latest_id, o.cand[j].slot, o.cand[j].id, (int)frames[o.cand[j].slot].size() - 1);
   }
-  const int nc = (int)cand.size();
-  if (nc == 0) return LINS_OK;
-  // ---- assemble: per entry its latest frame, then one window per rank from the rank's own slot; one call ----
-  std::vector<int> first(nc + 1, 0);  // an entry's first spec (its source)
-  for (int i = 0; i < nc; ++i) first[i + 1] = first[i] + 1 + out[cand[i]].n_candidates;
-  const int n_specs = first[nc];
-  std::vector<std::vector<int32_t>> ids(n_specs);
-  std::vector<lins_submap_spec> specs(n_specs);
-  std::vector<lins_submap_info> infos(n_specs);
-  for (int i = 0; i < nc; ++i) {
-    const lins_rendezvous_result& o = out[cand[i]];
-    const int s0 = first[i];
-    ids[s0].assign(1, o.latest_id);
-    specs[s0] = lins_submap_spec{ids[s0].data(), 1, entries[cand[i]].slot, LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF, LINS_SUBMAP_DROP_NEGATIVE, 0.f, 0};
-    for (int j = 0; j < o.n_candidates; ++j) {
-      const int latest = (int)frames[o.cand[j].slot].size() - 1;
-      std::vector<int32_t>& w = ids[s0 + 1 + j];
-      w.resize(lins_loop::window_size(latest, o.cand[j].id, prm->search_num));
-      lins_loop::window(latest, o.cand[j].id, prm->search_num, w.data());
-      specs[s0 + 1 + j] = lins_submap_spec{w.data(), (int32_t)w.size(), o.cand[j].slot, LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF, 0, prm->history_leaf, 0};
-    }
+  if (v.n() == 0) return LINS_OK;
+  // ---- assemble ----
+  if (int rc = verify_assemble(ctx, v, prm->search_num, prm->history_leaf)) return rc;
+  // ---- start transforms: the appearance's guess between the two maps ----
+  std::vector<double> T0(16 * v.hyps.size(), 0.0);
+  for (int i = 0; i < v.n(); ++i) {
+    lins_rendezvous_result& o = out[v.of[i]];
+    const int x0 = v.hyp0[i];
+    o.latest = v.infos[v.src_spec[x0]];
+    for (int j = 0; j < o.n_candidates; ++j) o.target[j] = v.infos[v.tgt_spec[x0 + j]];
+    o.status = v.status[i];  // (not zero: nothing is aligned for it)
+    for (int j = 0; j < o.n_candidates && !o.status; ++j)
+      lins_place::guess_team(frames[v.slots[i]][o.latest_id].pose, frames[o.cand[j].slot][o.cand[j].id].pose, o.cand[j].shift, A.store->prm.up_axis,
+                             &T0[16 * (size_t)(x0 + j)]);
   }
-  if (int rc = lins_archive_assemble(ctx, n_specs, specs.data(), infos.data())) return rc;
-  // ---- align: one batch over every (entry, rank) of the entries whose assemblies have no status ----
-  std::vector<int> ran;    // positions in cand
-  std::vector<int> prob0;  // their first problem
-  std::vector<lins_loop_icp_problem> probs;
-  std::vector<double> T0;
-  for (int i = 0; i < nc; ++i) {
-    lins_rendezvous_result& o = out[cand[i]];
-    o.latest = infos[first[i]];
-    int status = o.latest.status;
-    for (int j = 0; j < o.n_candidates; ++j) {
-      o.target[j] = infos[first[i] + 1 + j];
-      if (!status) status = o.target[j].status;
-    }
-    if (status) {  // (the entry's first: nothing is aligned for it)
-      o.status = status;
-      continue;
-    }
-    ran.push_back(i), prob0.push_back((int)probs.size());
-    for (int j = 0; j < o.n_candidates; ++j) {
-      probs.push_back(lins_loop_icp_problem{first[i], first[i] + 1 + j, nullptr, nullptr, 0, 0});
-      T0.resize(T0.size() + 16, 0.0);
-      lins_place::guess_team(frames[entries[cand[i]].slot][o.latest_id].pose, frames[o.cand[j].slot][o.cand[j].id].pose, o.cand[j].shift,
-                        A.store->prm.up_axis, &T0[T0.size() - 16]);
-    }
-  }
-  if (ran.empty()) return LINS_OK;
-  std::vector<lins_loop_icp_result> icp(probs.size());
-  if (int rc = lins_loop_icp_batch_from(ctx, (int)probs.size(), probs.data(), T0.data(), &prm->icp, icp.data())) return rc;
+  // ---- align ----
+  if (int rc = verify_align(ctx, v, T0.data(), &prm->icp)) return rc;
+  if (!v.n_ran) return LINS_OK;
   // ---- choose ----
-  for (size_t a = 0; a < ran.size(); ++a) {
-    lins_rendezvous_result& o = out[cand[ran[a]]];
+  for (int i = 0; i < v.n(); ++i) {
+    if (v.status[i]) continue;
+    lins_rendezvous_result& o = out[v.of[i]];
     int32_t conv[LINS_PLACE_MAX_K];
     double fit[LINS_PLACE_MAX_K];
-    int status = 0, aligned = 0;
-    for (int j = 0; j < o.n_candidates; ++j) {
-      o.icp[j] = icp[prob0[a] + j];
-      conv[j] = o.icp[j].status ? 0 : o.icp[j].converged, fit[j] = o.icp[j].fitness;  // (a target box beyond the gridding's limit: nothing was run)
-      if (o.icp[j].status && !status) status = o.icp[j].status;
-      aligned += o.icp[j].status ? 0 : 1;
-    }
-    if (!aligned) {
-      o.status = status;
+    std::memcpy(o.icp, &v.icp[v.hyp0[i]], o.n_candidates * sizeof o.icp[0]);
+    const lins_verify::IcpSummary s = lins_verify::icp_summary(o.icp, o.n_candidates, conv, fit);
+    if (!s.ran) {
+      o.status = s.status;
       continue;
     }
     o.outcome = LINS_RENDEZVOUS_REJECTED;
@@ -437,51 +432,14 @@ int lins_rendezvous_window_step(lins_ctx* ctx, int n, const lins_rendezvous_entr
   if (!ctx || n < 0 || (n && (!entries || !out || !hyp))) return LINS_E_ARG;
   ArchivePlace A;
   if (int rc = store_of(ctx, &A)) return rc;
-  // ---- the whole call's errors, before anything is queued (lins_rendezvous_step's, and the window's) ----
-  if (!prm || !team || std::isnan(prm->max_fitness) || !std::isfinite(prm->history_leaf) || prm->history_leaf < 0.f || prm->search_num < 0 ||
-      std::isnan(prm->min_gap_s) || prm->icp.max_iterations < 1 || prm->icp.min_correspondences < 0 || !std::isfinite(prm->icp.max_corr_dist))
-    return LINS_E_ARG;
+  // ---- the whole call's errors, before anything is queued (the window's, and lins_rendezvous_step's) ----
   if (!lins_consensus::params_ok(consensus)) return LINS_E_ARG;
-  lins_place_team_params tp = team->team;
-  if (tp.min_sep < -1 || std::isnan(team->max_distance)) return LINS_E_ARG;
-  if (tp.min_sep < 0) tp.min_sep = prm->search_num;
-  if (!team_params_ok(&tp)) return LINS_E_ARG;
-  if (int rc = slots_check(A, n_targets, target_slots)) return rc;
-  for (int k = 0; k < n; ++k) {
-    if (entries[k].slot < 0 || entries[k].slot >= A.n_slots) return LINS_E_ARG;
-    for (int i = 0; i < k; ++i)
-      if (entries[i].slot == entries[k].slot) return LINS_E_ARG;
-  }
-  for (int k = 0; k < n; ++k)
-    if (!std::isfinite(entries[k].now)) return LINS_E_INPUT;
+  lins_place_team_params tp;
+  if (int rc = rendezvous_check(A, n, entries, n_targets, target_slots, prm, team, &tp)) return rc;
   const int K = tp.k, W = consensus->window, stride = consensus->stride;
   static_assert(LINS_RENDEZVOUS_MAX_WINDOW * LINS_PLACE_MAX_K == LINS_RENDEZVOUS_MAX_HYP, "an entry's hypotheses fill one consensus table at the most");
-  if ((long long)n * W * (1 + K) > 2147483647ll) return LINS_E_CAPACITY;
   const std::vector<std::vector<ArFrame>>& frames = *A.frames;
-  // query j of a slot with `count` frames: latest - j * stride, while it exists
-  auto queries_of = [&](int count) {
-    int nq = 0;
-    while (nq < W && (long long)(count - 1) - (long long)nq * stride >= 0) ++nq;
-    return nq;
-  };
-  // lins_rendezvous_step's capacity question, asked of the most the window can ask for
-  {
-    auto both = [](const ArFrame& f) { return (long long)f.n[0] + f.n[1]; };  // corner | surf
-    long long widest = 0, tiles = 0;
-    for (int t = 0; t < n_targets; ++t) {
-      long long sum = 0;
-      for (const ArFrame& f : frames[target_slots[t]]) sum += both(f);
-      widest = std::max(widest, sum);
-    }
-    if (widest > INT_MAX / 2) return LINS_E_CAPACITY;
-    for (int k = 0; k < n; ++k) {
-      const std::vector<ArFrame>& fr = frames[entries[k].slot];
-      const int nq = queries_of((int)fr.size());
-      for (int j = 0; j < nq; ++j)
-        tiles += (both(fr[fr.size() - 1 - (size_t)j * stride]) + kLmTile - 1) / kLmTile + (long long)K * ((widest + kLmTile - 1) / kLmTile);
-      if (tiles > INT_MAX / 256) return LINS_E_CAPACITY;
-    }
-  }
+  if (int rc = assembly_room(frames, n, entries, n_targets, target_slots, K, W, stride)) return rc;
   ConsensusStore& cs = *archive_consensus(ctx);
   for (float& t : cs.stage_ms) t = 0.f;
   const clock::time_point t_begin = clock::now();
@@ -500,12 +458,11 @@ int lins_rendezvous_window_step(lins_ctx* ctx, int n, const lins_rendezvous_entr
   std::vector<lins_place_team_query> qs;
   const size_t per_entry = (size_t)W * K;
   for (int k = 0; k < n; ++k) {
-    lins_rendezvous_window_result& o = out[k];
-    std::memset(&o, 0, sizeof o);
+    lins_rendezvous_window_result& o = blank(out[k]);
     std::memset(hyp + k * per_entry, 0, per_entry * sizeof *hyp);
-    o.outcome = LINS_RENDEZVOUS_NONE, o.winner = o.target_slot = o.target_id = -1;
+    o.winner = -1;
     const int count = (int)frames[entries[k].slot].size();
-    o.n_queries = queries_of(count);
+    o.n_queries = queries_of(count, W, stride);
     for (int j = 0; j < LINS_RENDEZVOUS_MAX_WINDOW; ++j) o.query_id[j] = j < o.n_queries ? count - 1 - j * stride : -1;
     for (int j = 0; j < o.n_queries; ++j) {
       asks.push_back(Ask{k, j});
@@ -527,101 +484,55 @@ int lins_rendezvous_window_step(lins_ctx* ctx, int n, const lins_rendezvous_entr
       x.query = asks[a].query, x.rank = o.n_ranks[asks[a].query]++, x.cand = r;
     }
   }
-  // ---- assemble: per (entry, query) with a rank its source, then one window per rank from the rank's own slot; one call ----
-  std::vector<int> cand;  // entries that go to the assembly
-  for (int k = 0; k < n; ++k)
-    if (out[k].n_hypotheses) cand.push_back(k);
-  const int nc = (int)cand.size();
-  if (nc == 0) return LINS_OK;
-  std::vector<int> first(nc + 1, 0);  // an entry's first spec
-  for (int i = 0; i < nc; ++i) {
-    const lins_rendezvous_window_result& o = out[cand[i]];
-    int sources = 0;
-    for (int j = 0; j < o.n_queries; ++j) sources += o.n_ranks[j] ? 1 : 0;
-    first[i + 1] = first[i] + sources + o.n_hypotheses;
-  }
-  const int n_specs = first[nc];
-  std::vector<std::vector<int32_t>> ids(n_specs);
-  std::vector<lins_submap_spec> specs(n_specs);
-  std::vector<lins_submap_info> infos(n_specs);
-  std::vector<int> src_spec((size_t)n * LINS_RENDEZVOUS_MAX_WINDOW, -1);  // [entry][query]: the source's spec
-  std::vector<int> tgt_spec((size_t)n * per_entry, -1);                     // [entry][hypothesis]: the target's
-  for (int i = 0; i < nc; ++i) {
-    const int k = cand[i];
-    const lins_rendezvous_window_result& o = out[k];
+  // ---- plan: per hypothesis its query's frame against the window around the rank, from the rank's own slot ----
+  Verify v;
+  for (int k = 0; k < n; ++k) {
     const lins_rendezvous_hypothesis* h = hyp + k * per_entry;
-    int s = first[i];
-    for (int x = 0; x < o.n_hypotheses; ++x) {
-      if (h[x].rank == 0) {  // the query's source goes in front of its ranks
-        ids[s].assign(1, o.query_id[h[x].query]);
-        specs[s] = lins_submap_spec{ids[s].data(), 1, entries[k].slot, LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF, LINS_SUBMAP_DROP_NEGATIVE, 0.f, 0};
-        src_spec[(size_t)k * LINS_RENDEZVOUS_MAX_WINDOW + h[x].query] = s++;
-      }
-      const lins_place_team_result& c = h[x].cand;
-      const int latest = (int)frames[c.slot].size() - 1;
-      std::vector<int32_t>& w = ids[s];
-      w.resize(lins_loop::window_size(latest, c.id, prm->search_num));
-      lins_loop::window(latest, c.id, prm->search_num, w.data());
-      specs[s] = lins_submap_spec{w.data(), (int32_t)w.size(), c.slot, LINS_SUBMAP_CORNER | LINS_SUBMAP_SURF, 0, prm->history_leaf, 0};
-      tgt_spec[k * per_entry + x] = s++;
-    }
+    if (out[k].n_hypotheses) v.entry(k, entries[k].slot);
+    for (int x = 0; x < out[k].n_hypotheses; ++x)
+      v.hyp(out[k].query_id[h[x].query], h[x].cand.slot, h[x].cand.id, (int)frames[h[x].cand.slot].size() - 1);
   }
-  if (int rc = lins_archive_assemble(ctx, n_specs, specs.data(), infos.data())) return rc;
+  if (v.n() == 0) return LINS_OK;
+  // ---- assemble ----
+  if (int rc = verify_assemble(ctx, v, prm->search_num, prm->history_leaf)) return rc;
   lap(1);
-  // ---- align: one batch over every (entry, query, rank) of the entries whose assemblies have no status ----
-  std::vector<int> ran;    // positions in cand
-  std::vector<int> prob0;  // their first problem
-  std::vector<lins_loop_icp_problem> probs;
-  std::vector<double> T0;
-  for (int i = 0; i < nc; ++i) {
-    const int k = cand[i];
+  // ---- start transforms: the appearance's guess between the two maps ----
+  std::vector<double> T0(16 * v.hyps.size(), 0.0);
+  for (int i = 0; i < v.n(); ++i) {
+    const int k = v.of[i];
     lins_rendezvous_window_result& o = out[k];
     lins_rendezvous_hypothesis* h = hyp + k * per_entry;
-    int status = 0;
     for (int x = 0; x < o.n_hypotheses; ++x) {
-      const int ss = src_spec[(size_t)k * LINS_RENDEZVOUS_MAX_WINDOW + h[x].query];
-      if (h[x].rank == 0) {
-        o.source[h[x].query] = infos[ss];
-        if (!status) status = infos[ss].status;
-      }
-      h[x].target = infos[tgt_spec[k * per_entry + x]];
-      if (!status) status = h[x].target.status;
+      o.source[h[x].query] = v.infos[v.src_spec[v.hyp0[i] + x]];
+      h[x].target = v.infos[v.tgt_spec[v.hyp0[i] + x]];
     }
-    if (status) {  // (the entry's first: nothing is aligned for it)
-      o.status = status;
-      continue;
-    }
-    ran.push_back(i), prob0.push_back((int)probs.size());
-    for (int x = 0; x < o.n_hypotheses; ++x) {
-      probs.push_back(lins_loop_icp_problem{src_spec[(size_t)k * LINS_RENDEZVOUS_MAX_WINDOW + h[x].query], tgt_spec[k * per_entry + x], nullptr, nullptr, 0, 0});
-      T0.resize(T0.size() + 16, 0.0);
+    o.status = v.status[i];  // (not zero: nothing is aligned for it)
+    for (int x = 0; x < o.n_hypotheses && !o.status; ++x)
       lins_place::guess_team(frames[entries[k].slot][o.query_id[h[x].query]].pose, frames[h[x].cand.slot][h[x].cand.id].pose, h[x].cand.shift,
-                             A.store->prm.up_axis, &T0[T0.size() - 16]);
-    }
+                             A.store->prm.up_axis, &T0[16 * (size_t)(v.hyp0[i] + x)]);
   }
-  if (ran.empty()) return LINS_OK;
-  std::vector<lins_loop_icp_result> icp(probs.size());
-  if (int rc = lins_loop_icp_batch_from(ctx, (int)probs.size(), probs.data(), T0.data(), &prm->icp, icp.data())) return rc;
+  // ---- align ----
+  if (int rc = verify_align(ctx, v, T0.data(), &prm->icp)) return rc;
+  if (!v.n_ran) return LINS_OK;
   lap(2);
   // ---- consensus: one table per entry that was aligned, one launch ----
-  std::vector<int> judged;  // positions in cand
+  std::vector<int> judged;  // entries
   std::vector<lins_consensus_hyp> table;
   std::vector<int32_t> offsets(1, 0);
-  for (size_t a = 0; a < ran.size(); ++a) {
-    const int k = cand[ran[a]];
+  for (int i = 0; i < v.n(); ++i) {
+    if (v.status[i]) continue;
+    const int k = v.of[i];
     lins_rendezvous_window_result& o = out[k];
     lins_rendezvous_hypothesis* h = hyp + k * per_entry;
-    int status = 0, aligned = 0;
+    const lins_verify::IcpSummary s = lins_verify::icp_summary(&v.icp[v.hyp0[i]], o.n_hypotheses, nullptr, nullptr);
     for (int x = 0; x < o.n_hypotheses; ++x) {
-      const lins_loop_icp_result& r = h[x].icp = icp[prob0[a] + x];
-      if (r.status && !status) status = r.status;  // (a target box beyond the gridding's limit: nothing was run)
-      aligned += r.status ? 0 : 1;
+      const lins_loop_icp_result& r = h[x].icp = v.icp[v.hyp0[i] + x];
       bool finite = lins_consensus::finite64(r.fitness) && r.fitness >= 0.0;
       for (int j = 0; j < 16; ++j) finite = finite && lins_consensus::finite64(r.transform[j]);
       h[x].admissible = !r.status && finite && lins_loop::accept(r.converged, r.fitness, prm->max_fitness) ? 1 : 0;
     }
-    if (!aligned) {
-      o.status = status;
+    if (!s.ran) {
+      o.status = s.status;
       continue;
     }
     judged.push_back(k);
@@ -643,14 +554,14 @@ int lins_rendezvous_window_step(lins_ctx* ctx, int n, const lins_rendezvous_entr
   for (size_t a = 0; a < judged.size(); ++a) {
     lins_rendezvous_window_result& o = out[judged[a]];
     lins_rendezvous_hypothesis* h = hyp + judged[a] * per_entry;
-    const lins_consensus_result& v = verdict[a];
-    o.winner = v.winner, o.support = v.support, o.n_admissible = v.n_admissible;
-    std::memcpy(o.members, v.members, sizeof o.members);
-    for (int x = 0; x < o.n_hypotheses; ++x) h[x].member = (int32_t)((v.members[x >> 5] >> (x & 31)) & 1u);
-    o.outcome = v.winner < 0 ? LINS_RENDEZVOUS_REJECTED : (v.support < consensus->min_support ? LINS_RENDEZVOUS_UNCONFIRMED : LINS_RENDEZVOUS_FOUND);
+    const lins_consensus_result& w = verdict[a];
+    o.winner = w.winner, o.support = w.support, o.n_admissible = w.n_admissible;
+    std::memcpy(o.members, w.members, sizeof o.members);
+    for (int x = 0; x < o.n_hypotheses; ++x) h[x].member = (int32_t)((w.members[x >> 5] >> (x & 31)) & 1u);
+    o.outcome = w.winner < 0 ? LINS_RENDEZVOUS_REJECTED : (w.support < consensus->min_support ? LINS_RENDEZVOUS_UNCONFIRMED : LINS_RENDEZVOUS_FOUND);
     if (o.outcome != LINS_RENDEZVOUS_FOUND) continue;
-    o.target_slot = h[v.winner].cand.slot, o.target_id = h[v.winner].cand.id;
-    std::memcpy(o.X, h[v.winner].icp.transform, sizeof o.X);
+    o.target_slot = h[w.winner].cand.slot, o.target_id = h[w.winner].cand.id;
+    std::memcpy(o.X, h[w.winner].icp.transform, sizeof o.X);
   }
   lap(3);
   return LINS_OK;

@@ -153,6 +153,41 @@ def test_a_full_slot_reports_capacity_and_the_others_close(pair, ieskf, ref):
     assert lsc.frozen(res[0]) == ref["step"][0] and lsc.frozen(res[2]) == ref["step"][2]
 
 
+def test_an_assembly_status_stops_its_entry_and_the_others_close(pair, ieskf, ref):
+    """A frame of slot 0's history window — not the candidate, whose pose the search reads — stored so far away that its
+    points leave |coord| <= 1e6: the window's assembly reports LINS_E_INPUT and an empty cloud.  The entry stops there
+    with that status; its neighbours in the call are what they are alone."""
+    a, b = pair
+    prm = lsc.params(ieskf.lib())
+    closest = ref["raw"][0]["closest_id"]
+    far = closest + 1  # inside the window (H = 4), neither the candidate nor the latest frame
+    assert 0 <= closest < far < 11 and far in host.loop_window(11, closest, lsc.H)
+    fresh(b)
+    single = {s: lsc.frozen(b.loop_step(entries([s]), prm)[0]) for s in (1, 2)}
+    single_states = states(b, [1, 2])
+    fresh(a)
+    a.archive_set_poses(0, far, [(1.0e6, 0.0, 0.0, 0.0, 0.0, 0.0)])
+    before = states(a, [0])
+    res = a.loop_step(entries([0, 1, 2]), prm)
+    stats = a.loop_step_stats()
+    r = res[0]
+    print("entry 0:", {k: r[k] for k in ("outcome", "status", "latest_id", "closest_id", "latest", "history")})
+    assert (r["outcome"], r["status"], r["latest_id"], r["closest_id"]) == (NONE, -4, 11, closest)
+    assert r["latest"]["status"] == 0 and r["latest"]["n"] > 0 and (r["history"]["status"], r["history"]["n"]) == (-4, 0)
+    zero = lsc.result_zero()
+    assert all(lsc.frozen(r[k]) == lsc.frozen(zero[k]) for k in ("icp", "pose_from", "graph"))  # nothing was aligned or solved for it
+    assert (stats["candidates"], stats["aligned"], stats["closed"]) == (2, 1, 1)
+    for entry in (0, 1):  # the entry that stopped at its assembly, the entry without a candidate
+        with pytest.raises(ieskf.LinsError, match="error -1"):
+            a.loop_closed_cloud(entry)
+    assert len(a.loop_closed_cloud(2)) == res[2]["latest"]["n"] > 0
+    assert states(a, [0]) == before and a.pose_graph_count(0) == (12, 0)  # its graph is untouched
+    for s in (1, 2):
+        assert lsc.frozen(res[s]) == single[s] == ref["step"][s], s
+    assert states(a, [1, 2]) == single_states
+    fresh(a)  # (the far pose does not outlive the test)
+
+
 def test_errors_leave_the_context_usable(pkg, ieskf, pair, ref):
     a, _ = pair
     L = ieskf.lib()

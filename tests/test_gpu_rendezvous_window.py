@@ -214,6 +214,46 @@ def test_slot_2_is_rejected(results):
     assert (g["outcome"], g["status"], g["winner"], g["n_admissible"], g["members"]) == (REJECTED, 0, -1, 0, []) and g["n_hypotheses"] > 0
 
 
+def test_an_assembly_status_stops_its_entries_and_no_other(pair, results):
+    """A frame of target slot 0 that no hypothesis names and no entry asks from — its pose feeds neither the search nor a
+    guess — stored so far away that its points leave |coord| <= 1e6: every window that holds it assembles to LINS_E_INPUT
+    and an empty cloud.  The entries with such a window stop with that status, nothing aligned; the others are the
+    unspoiled run's bytes."""
+    a, _ = pair
+    got, prm = results["got"], results["prm"]
+    t = 0
+    named = {h["cand"]["id"] for s in ALL for h in got[s]["hyp"] if h["cand"]["slot"] == t} | set(got[t]["query_id"])
+
+    def holds(h, f):
+        return h["cand"]["slot"] == t and f in host.loop_window(LATEST, h["cand"]["id"], rwc.H)
+
+    far, hit = next((f, hit) for f in range(N) if f not in named
+                    for hit in [[s for s in ALL if any(holds(h, f) for h in got[s]["hyp"])]] if 0 < len(hit) < len(ALL))
+    print("far frame: slot %d frame %d; entries that reach it: %s" % (t, far, hit))
+    a.archive_set_poses(t, far, [(1.0e6, 0.0, 0.0, 0.0, 0.0, 0.0)])
+    try:
+        res = dict(zip([3, 1, 2, 0], step(a, [3, 1, 2, 0], prm)))
+    finally:
+        a.archive_set_poses(t, far, [tuple(float(v) for v in rwc.slots()[t][far][3])])
+    zero_icp = lsc.frozen(defs.LoopIcpResultC().as_dict())
+    for s in ALL:
+        g, u = res[s], got[s]
+        if s not in hit:
+            assert lsc.frozen(g) == lsc.frozen(u), s
+            continue
+        assert (g["outcome"], g["status"], g["winner"], g["support"], g["n_admissible"], g["target_slot"], g["target_id"], g["members"]) == (NONE, E_INPUT, -1, 0, 0, -1, -1, []), s
+        assert not g["X"].any() and g["n_hypotheses"] == u["n_hypotheses"] > 0
+        assert lsc.frozen([g[k] for k in ("n_queries", "query_id", "n_ranks", "source")]) == lsc.frozen([u[k] for k in ("n_queries", "query_id", "n_ranks", "source")])
+        for h, w in zip(g["hyp"], u["hyp"]):
+            assert lsc.frozen([h[k] for k in ("query", "rank", "cand")]) == lsc.frozen([w[k] for k in ("query", "rank", "cand")])
+            assert lsc.frozen(h["icp"]) == zero_icp and (h["admissible"], h["member"]) == (0, 0)  # no hypothesis was aligned
+            if holds(h, far):
+                assert (h["target"]["status"], h["target"]["n"]) == (E_INPUT, 0)
+            else:
+                assert lsc.frozen(h["target"]) == lsc.frozen(w["target"])
+    assert state(a) == results["before"]  # (the frame's pose is back)
+
+
 def test_the_step_leaves_graphs_archive_rings_and_map_poses(results):
     assert results["after"] == results["before"]
 
