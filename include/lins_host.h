@@ -421,6 +421,40 @@ int lins_host_pose_graph_linearize(lins_host_pose_graph* g, const double* poses,
 void lins_host_pose_from6(const float p[6], double T[12]);
 void lins_host_pose_to6(const double T[12], float p[6]);
 
+/* ---- the team graph on the CPU (host/team_graph.cpp) -----------------------------------------------------------------
+ * The restatement lins_team_graph_solve is checked against (include/lins_team.h has the contract; the text of the solve
+ * is csrc/pose_graph_team.h in both libraries).  The records are the device call's. */
+typedef struct lins_team_factor {
+  int32_t slot_b, id_b, slot_a, id_a;
+  double Z[12]; /* the measurement T_b^-1 T_a as a pose in the graph's axes: R row-major, then t */
+  double var;
+} lins_team_factor;
+typedef struct lins_team_member {
+  int32_t slot, reserved;
+  double root_variance[6]; /* rotation first; ignored for a group's first member */
+} lins_team_member;
+typedef struct lins_team_graph_result {
+  lins_pose_graph_result solve;
+  int32_t n_frames, n_loops, n_factors, reserved; /* of the group: frames of all members, their own loops, its factors */
+} lins_team_graph_result;
+/* out->Z = (X Tb)^-1 Ta, out->var = (double)(float)fitness, the slots and ids zero.  Tb, Ta: poses of 12 doubles in the
+ * graph's axes; X: 4 x 4 row-major f64 in the archive's axes, NULL: the identity.  LINS_E_INPUT for an X that
+ * lins_host_pose_graph_rebase refuses or a fitness that is not finite and > 0. */
+int lins_host_team_factor(const double Tb[12], const double Ta[12], const double* X, double fitness, lins_team_factor* out);
+/* ONE group: graphs[0] is the anchor; root_variance holds 6 doubles per member (member 0's are not read); a factor's
+ * slot_b / slot_a are member indices.  Refusals and what the solve leaves in every graph: lins_team_graph_solve's (the
+ * capacity asked against min(64, the sum of the graphs' max_loops)). */
+int lins_host_team_graph_solve(int n_members, lins_host_pose_graph* const* graphs, const double* root_variance, int n_factors,
+                               const lins_team_factor* factors, const lins_pose_graph_params* prm, lins_team_graph_result* out);
+/* The linearisation of what a team adds, at given absolute poses of all members back to back (sum of N_m x 12; NULL: the
+ * estimates), for the finite-difference test: per team factor its residual r_factor[6 i] and M[36 i] (the factor's rows
+ * are + M Ad(T_k) over chain a up to id_a and - M Ad(T_k) over chain b up to id_b); per non-anchor member m = 1 .. the
+ * root factor's residual r_root[6 (m - 1)], Hessian block H_root[36 (m - 1)] and gradient g_root[6 (m - 1)] with respect
+ * to the right perturbation of T_0.  Any output may be NULL. */
+int lins_host_team_graph_linearize(int n_members, lins_host_pose_graph* const* graphs, const double* root_variance, int n_factors,
+                                   const lins_team_factor* factors, const double* poses, double* r_factor, double* M, double* r_root,
+                                   double* H_root, double* g_root);
+
 /* ---- place recognition on the CPU (host/place.cpp) -----------------------------------------------------------------
  * The DEFINITION the device calls of include/lins_place.h are held to, bit for bit (the scalar text is
  * csrc/host/place_math.h in both libraries; DESIGN.md §5.3 "Place recognition").  A descriptor is LINS_PLACE_CELLS f32,

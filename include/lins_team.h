@@ -225,6 +225,83 @@ int lins_rendezvous_window_step(lins_ctx* ctx, int n, const lins_rendezvous_entr
  * the whole call (each stage ends in a synchronisation) */
 int lins_last_rendezvous_window_stats(lins_ctx* ctx, float* detect_ms, float* assemble_ms, float* align_ms, float* consensus_ms, float* total_ms);
 
+/* ---- team graph: the pose graphs of the robots that met, solved jointly ----
+ * (csrc/lins_team_graph_capi.hip, kernels csrc/team_graph_kernels.hip; the text of the solve is csrc/pose_graph_team.h in
+ * both libraries, on the scalar pieces of csrc/pose_graph.h; lins_host.h has the CPU twin lins_host_team_graph_solve;
+ * DESIGN.md section 5.3 "Team graph".)
+ *
+ * A GROUP is an ordered list of slots that share a map frame.  Its graph: every member's own graph as it stands (Z, the
+ * increments D, its loops) and the TEAM FACTORS handed into the call.  The call is stateless: the context keeps no factor.
+ *   Member 0, the anchor, keeps its prior exactly, as in lins_pose_graph_solve.
+ *   Every other member's root T_0 is an unknown with ONE factor of odometry form, E = Z^-1 T_0, Z the member's current
+ *   Z[0], under the six variances root_variance (rotation first); it retracts like an increment — an increment relative to
+ *   the identity — and starts at Z.
+ *   A team factor on ((slot_b, id_b), (slot_a, id_a)) is a loop factor in the existing form: E = Z^-1 T_b^-1 T_a, one
+ *   variance for all six components, the loop's residual and retraction.  Its two slots are two DIFFERENT members.
+ * Linearisation.  M = J_E Ad(T_a^-1), as a loop's but without the sign folded in.  The factor's row over unknown k is
+ * sigma(k) M Ad(T_k): sigma = +1 for the unknowns of chain a with index <= id_a, -1 for those of chain b with index <= id_b,
+ * the root included where it is an unknown.  A member's own loops keep their form: span (lo, hi], the sign folded into M.
+ * The Woodbury core keeps its shape, S_{l,l'} = W^-1 delta + M_l (sum_k sigma_l(k) sigma_l'(k) P_k) M_l'^T, the sum over the
+ * intersection of the two supports — at most one interval per chain, so at most two signed intervals.  ORDER of that sum:
+ * the intervals in group order; each as 7 chunk sums over consecutive unknowns (the single solve's chunks), the chunks
+ * added left to right; each total under its sign; then the totals left to right.  The right-hand side sums over a loop's
+ * own intervals in the same order.
+ * Poses: each member's by the single solve's prefix product, in blocks of 32 INSIDE the member; no block runs across two
+ * members.  The cost order (lane t adds the unknowns t + 1, t + 257 ... of the concatenated chains, lane 0 the lanes, then the
+ * loops), the accept rule and its `flat` rule, the lambda schedule and the stop reasons are lins_pose_graph_solve's, with
+ * one lins_pose_graph_params.  Loop order inside a group: the members' loops first, in member order and each member's
+ * own order, then the team factors in the caller's order.
+ * A group's result bits are a function of the group AS LISTED — member order and factor order — and depend neither on the
+ * batch, nor on the order of the groups, nor on what the context ran before.  Invariance under a permutation inside a
+ * group is not promised.
+ * GROUP OF ONE: a group of one member and no factor gives the bits of lins_pose_graph_solve of that slot — the result
+ * record, the f64 poses, the six floats.  A group without any loop or factor returns the bits it holds with 0 iterations.
+ *
+ * What a solve leaves, in the host's graph and the device's rows of every member: the solved increments and poses (as a
+ * single solve stores them), and for a non-anchor member Z[0] <- its solved root (as a rebase stores a prior; the held
+ * floats are rounded once).  A later lins_pose_graph_solve, a snapshot or a lins_pose_graph_apply_batch of the members sees
+ * a self-consistent graph; the archive, the rings and the streams follow through lins_pose_graph_apply_batch.
+ * A group whose solved poses are not finite or lie beyond the archive's bound (|x|, |y|, |z| <= 1e6) — asked of the
+ * device's solved poses before anything is stored — has solve.status LINS_E_INPUT, and none of its members changes.
+ * DEPARTURE: a member's own lins_pose_graph_solve, and so lins_loop_step, knows nothing of team factors.  A caller with team
+ * factors calls lins_team_graph_solve after the loop step.
+ *
+ * Limits: at most LINS_TEAM_GRAPH_MAX_MEMBERS members a group; the loops of a group — its members' own and its factors —
+ * at most min(64, members x max_loops of lins_pose_graph_init): LINS_E_CAPACITY beyond either.
+ * Refusals, all asked before anything is queued; a refused call changes nothing.  LINS_E_STATE before lins_pose_graph_init.
+ * LINS_E_ARG: null pointers, offsets that do not start at 0 or descend, an empty group, a slot out of range, without
+ * frames or named twice in the call, a factor naming a slot outside its group or the same member twice, a factor id out
+ * of range, parameters lins_pose_graph_solve refuses.  LINS_E_INPUT: a Z that is not finite or whose rotation is no
+ * rotation by lins_pose_graph_rebase_batch's bound, a var or a root_variance entry (of a non-anchor member) that is not
+ * finite and > 0.  n_groups = 0 is LINS_OK.
+ * Workspace: the concatenated Z / D / Dt / I / T / Tt / B / c / P / q rows of every group of the call, S, y, the loop
+ * records and the states; grow-only, allocated by the FIRST team solve — a caller who never calls it pays nothing.
+ * 1 248 bytes a frame (and 96 per 32 frames + 192 a member for the block prefixes), 672 bytes a loop and 288 L bytes of S
+ * per loop in a group of L loops.
+ * Device sequence: the members' new frames are uploaded as a solve uploads them; ONE upload of the tables (groups, members,
+ * loop records, supports, states); the gather launch (one workgroup per member: its Z and D rows into the group's rows);
+ * the begin launch and the trial launches, one workgroup of 256 lanes per GROUP, queued in fours with one "still running"
+ * word read between them, as the single solve; ONE download of the states and the poses; the check; the scatter launch (the
+ * solved D and T rows, and the non-anchor Z[0], into the members' own rows); one synchronisation each. */
+#define LINS_TEAM_GRAPH_MAX_MEMBERS 32
+/* (the records lins_team_factor, lins_team_member and lins_team_graph_result are lins_host.h's: both libraries use them) */
+
+/* Z =(X T_b)^-1 T_a from the two graphs' f64 estimates as they stand, var = (double)(float)fitness.
+ * X: 4 x 4 row-major f64, archive axes, as lins_rendezvous_result.X / a hypothesis' icp.transform; NULL: the identity (the
+ * two slots already share a frame).  Built with X BEFORE lins_team_rebase by X, the factor's residual after it is zero up
+ * to rounding.  Pure host work.  LINS_E_ARG: a slot or an id out of range, slot_b == slot_a, a null out; LINS_E_INPUT: an X
+ * lins_pose_graph_rebase_batch refuses, a fitness that is not finite and > 0 once rounded. */
+int lins_team_factor_from_alignment(lins_ctx* ctx, int slot_b, int id_b, int slot_a, int id_a, const double* X, double fitness,
+                                    lins_team_factor* out);
+
+/* n_groups groups: members[member_offsets[g] .. member_offsets[g + 1]), factors[factor_offsets[g] .. factor_offsets[g + 1]);
+ * out: n_groups records */
+int lins_team_graph_solve(lins_ctx* ctx, int n_groups, const lins_team_member* members, const int32_t* member_offsets,
+                          const lins_team_factor* factors, const int32_t* factor_offsets, const lins_pose_graph_params* prm,
+                          lins_team_graph_result* out);
+/* the last lins_team_graph_solve: HIP-event time (ms) from the gather launch to the last trial, and the trials run */
+int lins_last_team_graph_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* iterations);
+
 #ifdef __cplusplus
 }
 #endif

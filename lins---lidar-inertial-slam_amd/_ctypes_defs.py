@@ -484,6 +484,40 @@ def pose_graph_params(lib, **kw):
     return p
 
 
+# ---- the team graph (include/lins_team.h lins_team_graph_*, include/lins_host.h lins_host_team_graph_*) --------
+class TeamFactorC(C.Structure):
+    _fields_ = [("slot_b", C.c_int32), ("id_b", C.c_int32), ("slot_a", C.c_int32), ("id_a", C.c_int32), ("Z", C.c_double * 12),
+                ("var", C.c_double)]
+
+    def as_dict(self):
+        return dict(slot_b=int(self.slot_b), id_b=int(self.id_b), slot_a=int(self.slot_a), id_a=int(self.id_a),
+                    Z=np.array(self.Z[:], np.float64), var=float(self.var))
+
+
+class TeamMemberC(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("reserved", C.c_int32), ("root_variance", C.c_double * 6)]
+
+
+class TeamGraphResultC(C.Structure):
+    _fields_ = [("solve", PoseGraphResultC), ("n_frames", C.c_int32), ("n_loops", C.c_int32), ("n_factors", C.c_int32),
+                ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return dict(self.solve.as_dict(), n_frames=int(self.n_frames), n_loops=int(self.n_loops), n_factors=int(self.n_factors))
+
+
+def team_factor(f):
+    """a TeamFactorC from a TeamFactorC, a dict of its fields, or a tuple (slot_b, id_b, slot_a, id_a, Z, var)"""
+    if isinstance(f, TeamFactorC):
+        return f
+    if isinstance(f, dict):
+        f = (f["slot_b"], f["id_b"], f["slot_a"], f["id_a"], f["Z"], f["var"])
+    c = TeamFactorC(int(f[0]), int(f[1]), int(f[2]), int(f[3]))
+    c.Z[:] = [float(x) for x in np.asarray(f[4], np.float64).reshape(12)]
+    c.var = float(f[5])
+    return c
+
+
 # ---- the loop thread's step (include/lins_map.h lins_loop_step) ------------------------------------------------
 LOOP_NONE, LOOP_REPEAT, LOOP_REJECTED, LOOP_CLOSED = range(4)
 LOOP_CENTRE_STREAM = 1

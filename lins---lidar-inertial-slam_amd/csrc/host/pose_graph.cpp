@@ -5,20 +5,11 @@
 #include <cstring>
 #include <vector>
 
+#include "pose_graph_host.h"
+
 using namespace lins_pg;
 
-struct lins_host_pose_graph {
-  Graph g;
-};
-
 namespace {
-
-struct HostExec {  // a phase on the CPU: the lanes one after the other
-  template <class F>
-  void operator()(F f) const {
-    for (int t = 0; t < kThreads; ++t) f(t);
-  }
-};
 
 struct Work {  // the arrays of one problem
   std::vector<double> Z, D, Dt, I, T, Tt, Q, B, c, P, q, S, y;

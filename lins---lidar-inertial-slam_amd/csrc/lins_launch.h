@@ -12,6 +12,8 @@
 
 namespace lins_pg {
 struct Prob;  // pose_graph.h
+struct TeamProb;  // pose_graph_team.h
+struct TeamCopy;
 }
 struct lins_snapshot_segment;  // include/lins_snapshot.h
 
@@ -236,6 +238,12 @@ void launch_rendezvous_consensus(hipStream_t s, int n, const ::lins_consensus_hy
 void launch_pose_graph_begin(hipStream_t s, int n_problems, const lins_pg::Prob* probs);
 // one Levenberg-Marquardt trial of every problem still active; still_running (may be null) += the problems that go on
 void launch_pose_graph_trial(hipStream_t s, int n_problems, const lins_pg::Prob* probs, const lins_pose_graph_params& prm, int* still_running);
+
+// ---- team_graph_kernels.hip: the team graph's solve, one workgroup per group of robots (pose_graph_team.h) ----
+void launch_team_graph_begin(hipStream_t s, int n_groups, const lins_pg::TeamProb* probs);
+void launch_team_graph_trial(hipStream_t s, int n_groups, const lins_pg::TeamProb* probs, const lins_pose_graph_params& prm, int* still_running);
+// one workgroup per member: its Z and D rows into its group's rows, or (scatter) the solved rows back where recs[].store
+void launch_team_graph_copy(hipStream_t s, int n_members, const lins_pg::TeamCopy* recs, bool scatter);
 
 // ---- snapshot_kernels.hip: the device-resident pieces of a call's streams into / out of one staging buffer (include/
 // lins_snapshot.h).  tiles: the (segment, tile) entries of the segments of `unit` bytes (16 or 8); bases: the module

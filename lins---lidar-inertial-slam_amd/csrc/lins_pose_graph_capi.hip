@@ -20,6 +20,7 @@
 #include "lins_launch.h"
 #include "local_map.h"
 #include "pose_graph.h"
+#include "pose_graph_mem.h"
 #include "snapshot.h"
 
 using namespace lins;
@@ -35,42 +36,7 @@ namespace {
 // launches.  A reasoned default, not a measured one.
 constexpr int kPgGroup = 4;
 
-struct PgMem {
-  int n_slots = 0, F = 0, L = 0;
-  std::vector<Graph> g;
-  std::vector<int> up_frames, up_loops;  // what of each slot is on the device
-  DevBuf<double> d_Z, d_D, d_Dt, d_I, d_T, d_Tt, d_Q;
-  DevBuf<double> d_B, d_c, d_P, d_q, d_S, d_y;
-  DevBuf<LoopRec> d_loops;
-  DevBuf<State> d_st;
-  DevBuf<Prob> d_probs;
-  DevBuf<int> d_running;
-  PinBuf<int> h_running;
-  float ms = 0.f;
-  uint64_t iterations = 0;
-  size_t nq() const { return (size_t)F / lins_pg::kPrefixBlock + 2; }
-};
-
 void pg_release(PgMem* m) { *m = PgMem(); }
-void pg_free(void* p) { delete (PgMem*)p; }
-
-PgMem* mem_of(lins_ctx* ctx) {
-  void** slot = map_slot(ctx, kSlotGraph, pg_free);
-  if (!*slot) *slot = new PgMem();
-  return (PgMem*)*slot;
-}
-
-Prob prob_of(const PgMem* m, int slot, int idx) {
-  const size_t s = (size_t)slot, F = (size_t)m->F, L = (size_t)m->L;
-  Prob p{};
-  p.n_frames = m->g[slot].n_frames(), p.n_loops = (int)m->g[slot].loops.size(), p.slot = slot;
-  p.Z = m->d_Z + s * F * 12, p.D = m->d_D + s * F * 12, p.Dt = m->d_Dt + s * F * 12, p.I = m->d_I + s * F * 12;
-  p.T = m->d_T + s * F * 12, p.Tt = m->d_Tt + s * F * 12, p.Q = m->d_Q + s * m->nq() * 12;
-  p.B = m->d_B + s * F * 36, p.c = m->d_c + s * F * 6, p.P = m->d_P + s * F * 36, p.q = m->d_q + s * F * 6;
-  p.loops = m->d_loops + s * L, p.S = m->d_S + s * 36 * L * L, p.y = m->d_y + s * 18 * L;
-  p.st = m->d_st + idx;
-  return p;
-}
 
 }  // namespace
 

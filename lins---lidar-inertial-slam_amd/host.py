@@ -954,3 +954,66 @@ class PoseGraph:
         if rc:
             raise RuntimeError(f"lins_host_pose_graph_linearize: {rc}")
         return dict(r_odo=r[:n - 1], D=D[:n - 1], g=g[:n - 1], r_loop=rl[:nl], M=M[:nl])
+
+
+# ---- the team graph on the CPU (include/lins_host.h lins_host_team_*) ----------------------------
+TEAM_ROOT_VARIANCE = (1e-6, 1e-6, 1e-6, 1e-8, 1e-8, 1e-6)  # the odometry factor's, rotation first
+
+
+def team_factor(Tb, Ta, X=None, fitness=1.0):
+    """lins_host_team_factor: Z = (X Tb)^-1 Ta of two poses (12 doubles each; X: 4 x 4 f64 in the archive's axes, None: the
+    identity) -> a TeamFactorC with zero slots and ids, or the C return code of a refused call"""
+    from ._ctypes_defs import TeamFactorC
+
+    L, out = lib(), TeamFactorC()
+    b, a = np.ascontiguousarray(Tb, np.float64).reshape(12), np.ascontiguousarray(Ta, np.float64).reshape(12)
+    x = None if X is None else np.ascontiguousarray(X, np.float64).reshape(16)
+    L.lins_host_team_factor.argtypes, L.lins_host_team_factor.restype = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.POINTER(TeamFactorC)], C.c_int
+    rc = L.lins_host_team_factor(b.ctypes.data, a.ctypes.data, x.ctypes.data if x is not None else None, float(fitness), C.byref(out))
+    return rc if rc else out
+
+
+def _team_args(graphs, factors, root_variance):
+    from ._ctypes_defs import TeamFactorC, team_factor as rec
+
+    n = len(graphs)
+    hs = (C.c_void_p * max(n, 1))(*[g._h for g in graphs])
+    rv = np.ascontiguousarray(np.broadcast_to(np.asarray(TEAM_ROOT_VARIANCE if root_variance is None else root_variance, np.float64), (max(n, 1), 6)))
+    fac = [rec(f) for f in factors]
+    farr = (TeamFactorC * max(len(fac), 1))(*fac)
+    return n, hs, rv, len(fac), farr
+
+
+def team_graph_solve(graphs, factors=(), params=None, root_variance=None):
+    """lins_host_team_graph_solve of ONE group: graphs[0] (PoseGraph objects) is the anchor; a factor's slots are member
+    indices; root_variance: six variances, or (members, 6).  Returns the result dict, or the C return code of a refused call."""
+    from ._ctypes_defs import PoseGraphParamsC, TeamFactorC, TeamGraphResultC
+
+    L, out = lib(), TeamGraphResultC()
+    prm = params if params is not None else pose_graph_params()
+    n, hs, rv, nf, farr = _team_args(graphs, factors, root_variance)
+    L.lins_host_team_graph_solve.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(TeamFactorC), C.POINTER(PoseGraphParamsC),
+                                             C.POINTER(TeamGraphResultC)]
+    L.lins_host_team_graph_solve.restype = C.c_int
+    rc = L.lins_host_team_graph_solve(n, hs, rv.ctypes.data, nf, farr, C.byref(prm), C.byref(out))
+    return rc if rc else out.as_dict()
+
+
+def team_graph_linearize(graphs, factors=(), poses=None, root_variance=None):
+    """lins_host_team_graph_linearize at the absolute poses of all members back to back (sum N, 12) (None: the estimates) ->
+    dict r_factor (F, 6), M (F, 6, 6), r_root (members - 1, 6), H_root (members - 1, 6, 6), g_root (members - 1, 6)"""
+    from ._ctypes_defs import TeamFactorC
+
+    L = lib()
+    n, hs, rv, nf, farr = _team_args(graphs, factors, root_variance)
+    T = None if poses is None else np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12)
+    assert T is None or len(T) == sum(g.count()[0] for g in graphs)
+    k = max(n - 1, 1)
+    rf, M, rr, H, g = np.zeros((max(nf, 1), 6)), np.zeros((max(nf, 1), 6, 6)), np.zeros((k, 6)), np.zeros((k, 6, 6)), np.zeros((k, 6))
+    L.lins_host_team_graph_linearize.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(TeamFactorC)] + [C.c_void_p] * 6
+    L.lins_host_team_graph_linearize.restype = C.c_int
+    rc = L.lins_host_team_graph_linearize(n, hs, rv.ctypes.data, nf, farr, T.ctypes.data if T is not None else None, rf.ctypes.data,
+                                          M.ctypes.data, rr.ctypes.data, H.ctypes.data, g.ctypes.data)
+    if rc:
+        raise RuntimeError(f"lins_host_team_graph_linearize: {rc}")
+    return dict(r_factor=rf[:nf], M=M[:nf], r_root=rr[:n - 1], H_root=H[:n - 1], g_root=g[:n - 1])

@@ -185,6 +185,57 @@ def rebase(ctx, slots, X, streams=None):
     return L.lins_team_rebase(ctx._h, len(s), s.ctypes.data if len(s) else None, t.ctypes.data if len(s) else None, x.ctypes.data if len(s) else None)
 
 
+# ---- the team graph ----
+def factor_from_alignment(ctx, slot_b, id_b, slot_a, id_a, X=None, fitness=1.0):
+    """lins_team_factor_from_alignment: the team factor Z = (X T_b)^-1 T_a of the two graphs' estimates as they stand (X: 4 x 4
+    f64 in the archive's axes, None: the identity) -> a TeamFactorC, or the C return code of a refused call"""
+    from ._ctypes_defs import TeamFactorC
+
+    L, out = _ieskf.lib(), TeamFactorC()
+    x = None if X is None else np.ascontiguousarray(X, np.float64).reshape(16)
+    L.lins_team_factor_from_alignment.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_double, C.POINTER(TeamFactorC)]
+    rc = L.lins_team_factor_from_alignment(ctx._h, int(slot_b), int(id_b), int(slot_a), int(id_a), x.ctypes.data if x is not None else None,
+                                           float(fitness), C.byref(out))
+    return rc if rc else out
+
+
+def graph_solve(ctx, groups, params=None, root_variance=None):
+    """lins_team_graph_solve.  groups: tuples (slots, factors) — slots[0] is the anchor; factors: TeamFactorC records, dicts or
+    tuples (slot_b, id_b, slot_a, id_a, Z, var).  root_variance: six variances (rotation first) for every non-anchor member,
+    or a dict slot -> six variances; default the odometry factor's (1e-6, 1e-6, 1e-6, 1e-8, 1e-8, 1e-6).  Returns the
+    per-group result dicts, or the C return code of a refused call."""
+    from ._ctypes_defs import PoseGraphParamsC, TeamFactorC, TeamGraphResultC, TeamMemberC, pose_graph_params, team_factor
+
+    L = _ieskf.lib()
+    prm = params if params is not None else pose_graph_params(L)
+    default = (1e-6, 1e-6, 1e-6, 1e-8, 1e-8, 1e-6)
+    mem, fac, moff, foff = [], [], [0], [0]
+    for slots, factors in groups:
+        for s in slots:
+            v = root_variance.get(int(s), default) if isinstance(root_variance, dict) else (root_variance if root_variance is not None else default)
+            m = TeamMemberC(int(s), 0)
+            m.root_variance[:] = [float(x) for x in v]
+            mem.append(m)
+        fac += [team_factor(f) for f in factors]
+        moff.append(len(mem)), foff.append(len(fac))
+    n = len(groups)
+    marr, farr = (TeamMemberC * max(len(mem), 1))(*mem), (TeamFactorC * max(len(fac), 1))(*fac)
+    mo, fo = np.ascontiguousarray(moff, np.int32), np.ascontiguousarray(foff, np.int32)
+    out = (TeamGraphResultC * max(n, 1))()
+    L.lins_team_graph_solve.argtypes = [C.c_void_p, C.c_int, C.POINTER(TeamMemberC), C.c_void_p, C.POINTER(TeamFactorC), C.c_void_p,
+                                        C.POINTER(PoseGraphParamsC), C.POINTER(TeamGraphResultC)]
+    rc = L.lins_team_graph_solve(ctx._h, n, marr, mo.ctypes.data, farr, fo.ctypes.data, C.byref(prm), out)
+    return rc if rc else [out[k].as_dict() for k in range(n)]
+
+
+def graph_stats(ctx):
+    """(HIP-event ms of the last graph_solve, trials it ran over all groups)"""
+    L, ms, it = _ieskf.lib(), C.c_float(0), C.c_uint64(0)
+    L.lins_last_team_graph_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+    ctx._check(L.lins_last_team_graph_stats(ctx._h, C.byref(ms), C.byref(it)))
+    return float(ms.value), int(it.value)
+
+
 # ---- the team map ----
 def select(ctx, queries, stride=None):
     """lins_keyposes_team_select_batch.  queries: tuples (centre, radius, pose_leaf, target slots); stride: pairs an entry
