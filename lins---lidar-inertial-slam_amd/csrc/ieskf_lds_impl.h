@@ -341,65 +341,121 @@ struct Spans {  // the grid positions of a column window: [s0, e0) and, when the
   int s0, e0, s1, e1, spans;
   __device__ __forceinline__ int count() const { return (e0 - s0) + (e1 - s1); }
 };
+struct SpanCells {  // the cells a column window names: first / last cell of its first span, the ring's first cell, the unwrapped last column
+  int c0, c1, row, hi, naz;
+  bool any;  // a window at all: lo <= hi on a ring that exists
+};
+__device__ __forceinline__ SpanCells span_cells(const LCloud& c, int r, int lo, int hi) {
+  const int naz = c.naz, row = r * naz;
+  const bool any = lo <= hi && r >= 0 && r < kRingsBinned;
+  int len = hi - lo;
+  if (len >= naz - 1) lo = 0, len = naz - 1;  // at most naz columns
+  lo &= naz - 1;  // (naz is a power of two: the non-negative remainder without an integer division, ~20 instructions)
+  hi = lo + len;
+  return SpanCells{row + lo, row + (hi < naz ? hi : naz - 1), row, hi, naz, any};
+}
 __device__ __forceinline__ Spans spans_of(const LCloud& c, int r, int lo, int hi) {
   int s0 = 0, e0 = 0, s1 = 0, e1 = 0, spans = 1;  // (a window that wraps past the last column has a second span)
   if (lo <= hi) {
-    const int naz = c.naz, row = r * naz;
-    int len = hi - lo;
-    if (len >= naz - 1) lo = 0, len = naz - 1;  // at most naz columns
-    lo &= naz - 1;  // (naz is a power of two: the non-negative remainder without an integer division, ~20 instructions)
-    hi = lo + len;
-    const int c0 = row + lo, c1 = row + (hi < naz ? hi : naz - 1);
-    s0 = c0 ? (int)c.cell_end[c0 - 1] : c.base;
-    e0 = (int)c.cell_end[c1];
-    if (hi >= naz) {  // wrapped tail: columns 0 .. hi-naz
+    const SpanCells k = span_cells(c, r, lo, hi);
+    s0 = k.c0 ? (int)c.cell_end[k.c0 - 1] : c.base;
+    e0 = (int)c.cell_end[k.c1];
+    if (k.hi >= k.naz) {  // wrapped tail: columns 0 .. hi-naz
       spans = 2;
-      s1 = row ? (int)c.cell_end[row - 1] : c.base;
-      e1 = (int)c.cell_end[row + hi - naz];
+      s1 = k.row ? (int)c.cell_end[k.row - 1] : c.base;
+      e1 = (int)c.cell_end[k.row + k.hi - k.naz];
     }
   }
   return Spans{s0, e0, s1, e1, spans};
 }
 template <class F>
-__device__ __forceinline__ void scan_spans(const LdsStore& L, const LCloud& c, const Spans& w, F f) {
+__device__ __forceinline__ void scan_span(const LdsStore& L, const LCloud& c, int s, int e, F f) {  // the points of positions [s, e)
+  const int el = kHybrid ? (e < c.n_lds ? e : c.n_lds) : e;
+  // kScanBatch points per trip, all their LDS reads issued before the first is consumed (the
+  // loop is latency bound: one dependent LDS round trip per trip instead of per point); the last
+  // trip re-reads the final point for its padding lanes and masks them
 #pragma unroll 1
-  for (int k = 0; k < w.spans; ++k) {
-    const int s = k ? w.s1 : w.s0, e = k ? w.e1 : w.e0;
-    const int el = kHybrid ? (e < c.n_lds ? e : c.n_lds) : e;
-    // kScanBatch points per trip, all their LDS reads issued before the first is consumed (the
-    // loop is latency bound: one dependent LDS round trip per trip instead of per point); the last
-    // trip re-reads the final point for its padding lanes and masks them
-#pragma unroll 1
-    for (int p = s; p < el; p += kScanBatch) {
-      float x[kScanBatch], y[kScanBatch], z[kScanBatch];
-      int j[kScanBatch];
+  for (int p = s; p < el; p += kScanBatch) {
+    float x[kScanBatch], y[kScanBatch], z[kScanBatch];
+    int j[kScanBatch];
 #pragma unroll
-      for (int u = 0; u < kScanBatch; ++u) {
-        const int pu = p + u < el ? p + u : el - 1;
-        const float4 v = L.pt[pu];
-        x[u] = v.x, y[u] = v.y, z[u] = v.z, j[u] = __float_as_int(v.w);
-      }
-#pragma unroll
-      for (int u = 0; u < kScanBatch; ++u) f(x[u], y[u], z[u], j[u], p + u, p + u < el);
+    for (int u = 0; u < kScanBatch; ++u) {
+      const int pu = p + u < el ? p + u : el - 1;
+      const float4 v = L.pt[pu];
+      x[u] = v.x, y[u] = v.y, z[u] = v.z, j[u] = __float_as_int(v.w);
     }
-    if (kHybrid) {
-      // the positions past the resident ones, from the sorted global copy (L2), one record per trip (four in flight: + 2.0 %,
-      // profiles/history/kernel_notes.md #globbatch)
+#pragma unroll
+    for (int u = 0; u < kScanBatch; ++u) f(x[u], y[u], z[u], j[u], p + u, p + u < el);
+  }
+  if (kHybrid) {
+    // the positions past the resident ones, from the sorted global copy (L2), one record per trip (four in flight: + 2.0 %,
+    // profiles/history/kernel_notes.md #globbatch)
 #pragma unroll 1
-      for (int p = s > c.n_lds ? s : c.n_lds; p < e; p += kGlobBatch) {
-        float4 g[kGlobBatch];
+    for (int p = s > c.n_lds ? s : c.n_lds; p < e; p += kGlobBatch) {
+      float4 g[kGlobBatch];
 #pragma unroll
-        for (int u = 0; u < kGlobBatch; ++u) g[u] = c.gs[p + u < e ? p + u : e - 1];
+      for (int u = 0; u < kGlobBatch; ++u) g[u] = c.gs[p + u < e ? p + u : e - 1];
 #pragma unroll
-        for (int u = 0; u < kGlobBatch; ++u) f(g[u].x, g[u].y, g[u].z, __float_as_int(g[u].w), p + u, p + u < e);
-      }
+      for (int u = 0; u < kGlobBatch; ++u) f(g[u].x, g[u].y, g[u].z, __float_as_int(g[u].w), p + u, p + u < e);
     }
   }
+}
+template <class F>
+__device__ __forceinline__ void scan_spans(const LdsStore& L, const LCloud& c, const Spans& w, F f) {
+#pragma unroll 1
+  for (int k = 0; k < w.spans; ++k) scan_span(L, c, k ? w.s1 : w.s0, k ? w.e1 : w.e0, f);
 }
 
 template <class F>
 __device__ __forceinline__ void scan_cols(const LdsStore& L, const LCloud& c, int r, int lo, int hi, F f) {
   scan_spans(L, c, spans_of(c, r, lo, hi), f);
+}
+
+// ---- one trip per window's bounds (the lean core of the batch shape: ieskf_lds_lean.h, profiles/search_spans.md) -------------
+// scan_cols() reads its window's bounds — two to four cell_end words, the second pair behind a branch — and waits for
+// them before its first point: every window of a search starts with a round trip of its own.  Where several windows are
+// known at once (the three seed rings of a one-lane cold search, nn_lean) their bounds are requested together:
+// spans_read() reads all four words of a window on clamped cells and guards nothing (pt_rec above: the same means), so
+// that several requests — and whatever other table reads stand beside them — are issued back to back in front of
+// spans_issued(); spans_pack() then keeps the words under the predicates that guarded the reads in spans_of().  A
+// window's positions travel as s | e << 16 per span (positions are < 12288): two registers for a window that may wrap;
+// an empty window (lo > hi) or a ring out of range gives (0, 0).  scan_packed() is scan_spans() on such words: both run
+// scan_span() per span, and spans_of() and these helpers share span_cells()' window arithmetic.
+// Contract: spans_pack() must be given the (r, lo, hi) its words were read for by spans_read(), or an empty window (lo > hi:
+// the words are dropped); for any other window the words name the wrong cells.  Nothing checks this but the caller.
+struct PSpans {
+  unsigned w0, w1;  // [s0, e0) and, when the window wraps past the last column, [s1, e1); 0 = no points
+};
+static_assert(kGridNpMax <= 0x4000, "two positions per word");
+struct SpanWords {
+  unsigned s0, e0, s1, e1;  // the four cell_end words of a window as they were read (spans_pack decides which of them count)
+};
+__device__ __forceinline__ SpanWords spans_read(const LCloud& c, int r, int lo, int hi) {
+  const SpanCells k = span_cells(c, r, lo, hi);
+  const unsigned last = (unsigned)(kRingsBinned * k.naz - 1);  // (this cloud's last cell: what an empty window names ends there)
+  return SpanWords{c.cell_end[min((unsigned)(k.c0 - 1), last)], c.cell_end[min((unsigned)k.c1, last)],
+                   c.cell_end[min((unsigned)(k.row - 1), last)], c.cell_end[min((unsigned)(k.row + k.hi - k.naz), last)]};
+}
+__device__ __forceinline__ PSpans spans_pack(const LCloud& c, int r, int lo, int hi, const SpanWords& v) {
+  const SpanCells k = span_cells(c, r, lo, hi);
+  const unsigned s0 = k.c0 > 0 ? v.s0 : (unsigned)c.base, s1 = k.row > 0 ? v.s1 : (unsigned)c.base;
+  return PSpans{k.any ? (s0 | (v.e0 << 16)) : 0u, (k.any && k.hi >= k.naz) ? (s1 | (v.e1 << 16)) : 0u};
+}
+// Every read requested above this line is issued above it, and nothing that consumes one is scheduled in between (the
+// scheduler otherwise puts each window's selects — and their wait — right behind its reads); the compiler may not sink
+// a read into the loop that uses it either.  No wait is implied: the words are no operands of it.
+__device__ __forceinline__ void spans_issued() {
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("" ::: "memory");
+}
+template <class F>
+__device__ __forceinline__ void scan_packed(const LdsStore& L, const LCloud& c, const PSpans& w, F f) {
+#pragma unroll 1
+  for (int k = 0; k < 2; ++k) {
+    const unsigned wk = k ? w.w1 : w.w0;
+    if (k && wk == 0u) break;
+    scan_span(L, c, (int)(wk & 0xFFFFu), (int)(wk >> 16), f);
+  }
 }
 
 // How many columns either side of a0 can hold a point within sqrt(bound) of the query:

@@ -115,19 +115,32 @@ __device__ __forceinline__ Top2 nn_lean(const LdsStore& L, const LCloud& c, floa
   };
   const bool own = ring_nonempty(c, rq);
   {  // cold seed: columns a0-1..a0+1 of the query's own ring and of its two neighbours (one ring per lane when ln > 1)
-    const int rs = ln == 1 ? rq : rq + (role == 0 ? 0 : (role == 1 ? 1 : -1));
-    const bool seed = !warm && role < 3 && ring_nonempty(c, rs);
-    rcur = rs;
-    scan_cols(L, c, rs, seed ? a0 - 1 : 1, seed ? a0 + 1 : 0, f);
-    if (ln == 1) {
+    if (ln == 1) {  // the three rings' bounds in one trip, then the three point loops (own ring, rq - 1, rq + 1: the order it was)
+      // (ring_nonempty of the two neighbours on clamped rings: their ring_start words travel with the bounds)
+      // The sixteen reads are unconditional ON PURPOSE, also for a warm search, which keeps none of them (before, lo > hi
+      // guarded them all): `warm` differs from lane to lane, and a guard around the reads is a branch with its own wait in
+      // front of the point loops — what this block removes.  Hoisting `!warm` around them was not measured; the late
+      // iterations, where most one-lane searches are warm, were: not longer (profiles/search_spans.md, wave phases).
+      const int rm = rq > 0 ? rq - 1 : 0, rp = rq < kRingsBinned - 1 ? rq + 1 : kRingsBinned - 1;
+      const int m0 = c.ring_start[rm], m1 = c.ring_start[rm + 1], p0 = c.ring_start[rp], p1 = c.ring_start[rp + 1];
+      const SpanWords v0 = spans_read(c, rq, a0 - 1, a0 + 1), vm = spans_read(c, rq - 1, a0 - 1, a0 + 1), vp = spans_read(c, rq + 1, a0 - 1, a0 + 1);
+      spans_issued();
+      const bool seed = !warm && own, sdm = !warm && rm == rq - 1 && m1 > m0, sdp = !warm && rp == rq + 1 && p1 > p0;
+      const PSpans w0 = spans_pack(c, rq, seed ? a0 - 1 : 1, seed ? a0 + 1 : 0, v0);
+      const PSpans wm = spans_pack(c, rq - 1, sdm ? a0 - 1 : 1, sdm ? a0 + 1 : 0, vm);
+      const PSpans wp = spans_pack(c, rq + 1, sdp ? a0 - 1 : 1, sdp ? a0 + 1 : 0, vp);
 #pragma unroll 1
-      for (int dr = -1; dr <= 1; dr += 2) {
-        const bool sd2 = !warm && ring_nonempty(c, rq + dr);
-        rcur = rq + dr;
-        scan_cols(L, c, rq + dr, sd2 ? a0 - 1 : 1, sd2 ? a0 + 1 : 0, f);
+      for (int dr = 0; dr < 3; ++dr) {
+        rcur = rq + (dr == 0 ? 0 : (dr == 1 ? -1 : 1));
+        // (word by word: choosing among the three PSpans as whole structs puts them on the stack, 32 B of scratch)
+        scan_packed(L, c, PSpans{dr == 0 ? w0.w0 : (dr == 1 ? wm.w0 : wp.w0), dr == 0 ? w0.w1 : (dr == 1 ? wm.w1 : wp.w1)}, f);
       }
-    } else if (!warm) {  // (the lanes of a query agree on `warm`)
-      t2_merge_lanes(b, lane, ln);
+    } else {
+      const int rs = rq + (role == 0 ? 0 : (role == 1 ? 1 : -1));
+      const bool seed = !warm && role < 3 && ring_nonempty(c, rs);
+      rcur = rs;
+      scan_cols(L, c, rs, seed ? a0 - 1 : 1, seed ? a0 + 1 : 0, f);
+      if (!warm) t2_merge_lanes(b, lane, ln);  // (the lanes of a query agree on `warm`)
     }
   }
   const int cin = warm ? 0 : 2;  // first column either side that the seed has not covered
