@@ -455,6 +455,56 @@ int lins_host_team_graph_linearize(int n_members, lins_host_pose_graph* const* g
                                    const lins_team_factor* factors, const double* poses, double* r_factor, double* M, double* r_root,
                                    double* H_root, double* g_root);
 
+/* ---- pairwise-consistent team factors on the CPU (host/team_pcm.cpp): the DEFINITION of include/lins_team.h's
+ * lins_team_factors_consistent_batch --------------------------------------------------------------------------------
+ * Per pair of members, the largest set of a group's team factors that agree with each other TWO BY TWO (pairwise
+ * consistency maximisation; DESIGN.md §5.3 "Pairwise-consistent team factors"; the scalar text is csrc/host/team_pcm.h,
+ * the same inline code in both libraries).  f64, products and sums in the order written, contraction off, no libm.
+ *   record      of a factor: u < v its two members, iu, iv its frames on them; Zn = Z where slot_b is u, else inverse(Z);
+ *               X = compose(compose(Tu, Zn), inverse(Tv)), the transform from v's map frame to u's that the factor claims
+ *               (Tu, Tv: the two frames' f64 estimates); p = the translation of Tv.  X depends on the two chains' relative
+ *               poses only: it can be asked before any rebase.
+ *   consistent  l != m: the same (u, v), NOT the same (iu, iv) — two factors on one frame pair witness nothing for each
+ *               other —, sum_ij Rl[i][j] Rm[i][j] >= 1 + 2 min_cos_rotation and, for p in {p_l, p_m}, |X_l p - X_m p|^2 <=
+ *               t^2, t = max_translation + translation_per_frame (|iu_l - iu_m| + |iv_l - iv_m|); the sums as
+ *               lins_host_rendezvous_consensus forms them.  Symmetric by construction.
+ *   search      per factor s, in index order, the best clique whose smallest member is s: depth first, candidates in
+ *               ascending index order, cut where |R| + |P| cannot beat the best; its own node counter (a node is a call
+ *               of the recursive statement), stopped beyond max_nodes with the best so far.  A pair's clique is the
+ *               subproblem result of largest size, then smallest s: where nothing ran out, the maximum clique with the
+ *               lexicographically smallest ascending index list.  A caller who prefers some factors lists them first.
+ *   kept        a pair's clique is kept iff its size >= min_support; a group's kept set is the union over its pairs */
+#define LINS_TEAM_PCM_MAX_FACTORS 64
+typedef struct lins_team_pcm_params {
+  double max_translation;       /* 1.0 m (finite, >= 0) */
+  double min_cos_rotation;      /* 0.99619469809174555 = cos 5 degrees, as lins_consensus_params (not a NaN) */
+  double translation_per_frame; /* 0.0 (finite, >= 0): metres the bar grows per frame between two factors, for drift */
+  int32_t min_support;          /* 3 (>= 1) */
+  int32_t max_nodes;            /* 65536 per subproblem (>= 1) */
+} lins_team_pcm_params;
+void lins_team_pcm_default_params(lins_team_pcm_params* p); /* exported by both libraries */
+
+typedef struct lins_team_pcm_result {
+  int32_t n_factors, n_kept, n_pairs, n_pairs_kept; /* pairs: member pairs with a factor; kept: with a kept clique */
+  int32_t exact;      /* 1 iff no subproblem ran out of nodes */
+  uint32_t nodes_max; /* the largest subproblem's node counter (max_nodes + 1 where it ran out) */
+  uint32_t kept[2];   /* factor f is bit f % 32 of kept[f / 32] */
+} lins_team_pcm_result; /* 32 bytes */
+
+/* ONE group of n_factors in [0, LINS_TEAM_PCM_MAX_FACTORS] factors whose slot_b / slot_a are member indices; Tb, Ta: 12
+ * doubles per factor, the f64 estimates of frame id_b of slot_b and of frame id_a of slot_a (R row-major, t).
+ * LINS_E_ARG: a null pointer, n_factors < 0, max_translation not finite or < 0, a NaN min_cos_rotation,
+ * translation_per_frame not finite or < 0, min_support or max_nodes < 1, a factor naming one member twice, a negative slot
+ * or id.  LINS_E_INPUT: a Z lins_host_team_graph_solve refuses (an entry that is not finite, no rotation), a pose entry that is
+ * not finite, a var that is not finite and > 0 — a kept list is one the solve takes.  LINS_E_CAPACITY: more than
+ * LINS_TEAM_PCM_MAX_FACTORS factors.  A refused call writes nothing. */
+int lins_host_team_factors_consistent(int n_factors, const lins_team_factor* factors, const double* Tb, const double* Ta,
+                                      const lins_team_pcm_params* prm, lins_team_pcm_result* out);
+/* The search and the winners alone, on n in [0, 64] vertices: adj[a] bit b = a and b are consistent, pair[a] = any key of
+ * a's member pair.  Of prm min_support and max_nodes are read.  LINS_E_ARG: a null pointer, n out of range, parameters as
+ * above, a row with a bit at or beyond n or at its own index, rows that are not symmetric, an edge between two keys. */
+int lins_host_team_pcm_clique(int n, const uint64_t* adj, const int32_t* pair, const lins_team_pcm_params* prm, lins_team_pcm_result* out);
+
 /* ---- place recognition on the CPU (host/place.cpp) -----------------------------------------------------------------
  * The DEFINITION the device calls of include/lins_place.h are held to, bit for bit (the scalar text is
  * csrc/host/place_math.h in both libraries; DESIGN.md §5.3 "Place recognition").  A descriptor is LINS_PLACE_CELLS f32,

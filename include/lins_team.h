@@ -302,6 +302,41 @@ int lins_team_graph_solve(lins_ctx* ctx, int n_groups, const lins_team_member* m
 /* the last lins_team_graph_solve: HIP-event time (ms) from the gather launch to the last trial, and the trials run */
 int lins_last_team_graph_stats(lins_ctx* ctx, float* kernel_ms, uint64_t* iterations);
 
+/* ---- pairwise-consistent team factors: which factors of a group agree with each other two by two ----
+ * (csrc/lins_team_pcm_capi.hip, kernel csrc/team_pcm_kernels.hip; the rule is lins_host.h's
+ * lins_host_team_factors_consistent, the scalar text csrc/host/team_pcm.h in both libraries, which the kernel calls;
+ * DESIGN.md section 5.3 "Pairwise-consistent team factors".)
+ *
+ * lins_team_graph_solve takes every factor it is handed, and one aliased factor bends every member's history.  This call
+ * comes ahead of it: per group and per pair of members it keeps the largest set of factors whose implied frame transforms
+ * agree two by two — the consensus rule's rotation bar, and both places the robot stood within the translation bar —
+ * and drops a pair's set below min_support.  The transform a factor implies depends on the two chains' relative poses
+ * only, so the answer does not depend on the members' roots and can be asked BEFORE any lins_team_rebase.
+ * Layout: lins_team_graph_solve's — members[member_offsets[g] .. member_offsets[g + 1]), factors[factor_offsets[g] ..
+ * factor_offsets[g + 1]), out: n_groups records — with the same membership checks; root_variance is not read.  At most
+ * LINS_TEAM_PCM_MAX_FACTORS factors a group, whatever max_loops of lins_pose_graph_init is.  The poses are the members'
+ * f64 estimates in the context's host graphs.  In a record, factor f of its group is bit f % 32 of kept[f / 32].
+ * The call reads and changes no graph, archive, ring or stream.  A group's bits are those of
+ * lins_host_team_factors_consistent of the group as listed (slots replaced by member indices), `exact` and `nodes_max`
+ * included, and depend neither on the batch, nor on the order of the groups, nor on what the context ran before.
+ * Device sequence: ONE upload (the records | the offsets), one launch (one workgroup of 64 lanes per group), one download,
+ * one synchronisation; the staging is grow-only and allocated by the first call.  n_groups = 0 is LINS_OK.
+ * Refusals, all asked before anything is queued; a refused call changes nothing and writes nothing.  LINS_E_STATE before
+ * lins_pose_graph_init.  LINS_E_ARG: null pointers, parameters lins_host_team_factors_consistent refuses, offsets that do
+ * not start at 0 or descend, an empty group, a slot out of range, without frames or named twice in the call, a factor naming
+ * a slot outside its group or the same member twice, a factor id out of range.  LINS_E_INPUT: a Z or a var that
+ * lins_team_graph_solve refuses, a pose entry that is not finite.  LINS_E_CAPACITY: more than LINS_TEAM_PCM_MAX_FACTORS
+ * factors or LINS_TEAM_GRAPH_MAX_MEMBERS members in a group. */
+int lins_team_factors_consistent_batch(lins_ctx* ctx, int n_groups, const lins_team_member* members, const int32_t* member_offsets,
+                                       const lins_team_factor* factors, const int32_t* factor_offsets, const lins_team_pcm_params* prm,
+                                       lins_team_pcm_result* out);
+/* HIP-event time (ms) of the last lins_team_factors_consistent_batch launch */
+int lins_last_team_pcm_stats(lins_ctx* ctx, float* kernel_ms);
+/* test aid: the search stage alone on a given graph, through the device function the production kernel calls; arguments
+ * and refusals are lins_host_team_pcm_clique's */
+int lins_debug_team_pcm_clique(lins_ctx* ctx, int n, const uint64_t* adj, const int32_t* pair, const lins_team_pcm_params* prm,
+                               lins_team_pcm_result* out);
+
 #ifdef __cplusplus
 }
 #endif

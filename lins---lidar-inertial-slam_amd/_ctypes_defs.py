@@ -518,6 +518,39 @@ def team_factor(f):
     return c
 
 
+# ---- pairwise-consistent team factors (include/lins_host.h lins_team_pcm_*) ------------------------------------
+TEAM_PCM_MAX_FACTORS = 64
+
+
+class TeamPcmParamsC(C.Structure):
+    _fields_ = [("max_translation", C.c_double), ("min_cos_rotation", C.c_double), ("translation_per_frame", C.c_double),
+                ("min_support", C.c_int32), ("max_nodes", C.c_int32)]
+
+
+class TeamPcmResultC(C.Structure):
+    _fields_ = [("n_factors", C.c_int32), ("n_kept", C.c_int32), ("n_pairs", C.c_int32), ("n_pairs_kept", C.c_int32), ("exact", C.c_int32),
+                ("nodes_max", C.c_uint32), ("kept", C.c_uint32 * 2)]
+
+    def as_dict(self):
+        return dict(n_factors=int(self.n_factors), n_kept=int(self.n_kept), n_pairs=int(self.n_pairs), n_pairs_kept=int(self.n_pairs_kept),
+                    exact=int(self.exact), nodes_max=int(self.nodes_max),
+                    kept=[f for f in range(TEAM_PCM_MAX_FACTORS) if (int(self.kept[f >> 5]) >> (f & 31)) & 1])
+
+
+def team_pcm_params(lib, **kw):
+    """lins_team_pcm_default_params of library `lib` (max_translation 1.0, min_cos_rotation cos 5 degrees,
+    translation_per_frame 0, min_support 3, max_nodes 65536) with fields overridden by keyword"""
+    p = TeamPcmParamsC()
+    lib.lins_team_pcm_default_params.argtypes = [C.POINTER(TeamPcmParamsC)]
+    lib.lins_team_pcm_default_params.restype = None
+    lib.lins_team_pcm_default_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError(f"lins_team_pcm_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
 # ---- the loop thread's step (include/lins_map.h lins_loop_step) ------------------------------------------------
 LOOP_NONE, LOOP_REPEAT, LOOP_REJECTED, LOOP_CLOSED = range(4)
 LOOP_CENTRE_STREAM = 1

@@ -15,6 +15,9 @@ struct Prob;  // pose_graph.h
 struct TeamProb;  // pose_graph_team.h
 struct TeamCopy;
 }
+namespace lins_pcm {
+struct Rec;  // host/team_pcm.h
+}
 struct lins_snapshot_segment;  // include/lins_snapshot.h
 
 namespace lins {
@@ -232,6 +235,15 @@ void launch_team_pairs(hipStream_t s, int n_queries, const TmQuery* queries, int
 constexpr int kCsBlock = 128;
 void launch_rendezvous_consensus(hipStream_t s, int n, const ::lins_consensus_hyp* table, const int* offsets, double max_translation,
                                  double min_cos_rotation, ::lins_consensus_result* out);
+
+// ---- team_pcm_kernels.hip: which team factors of a group agree two by two (host/team_pcm.h) ----
+// one workgroup of kPcmBlock lanes per group: group g's records are recs[offsets[g] .. offsets[g + 1]), at most kPcmBlock
+// of them, checked by the caller; its record goes to out + g
+constexpr int kPcmBlock = 64;
+void launch_team_pcm(hipStream_t s, int n_groups, const lins_pcm::Rec* recs, const int* offsets, const ::lins_team_pcm_params& prm,
+                     ::lins_team_pcm_result* out);
+// the search and the winners alone, one workgroup: n <= kPcmBlock rows and pair keys that lins_pcm::graph_check took
+void launch_team_pcm_clique(hipStream_t s, int n, const uint64_t* adj, const int* key, const ::lins_team_pcm_params& prm, ::lins_team_pcm_result* out);
 
 // ---- pose_graph_kernels.hip: the pose graph's solve, one workgroup per problem (pose_graph.h) ----
 // the poses and the cost of every problem as it stands (the first launch of a solve)

@@ -1,6 +1,7 @@
-// pose_graph_mem.h — what a context holds of its pose graphs, for the two files that work on it: lins_pose_graph_capi.hip
-// (the graphs, the single solve, the rebase, the write-back) and lins_team_graph_capi.hip (the team solve over groups of
-// them, with a workspace of its own that the first team solve allocates).
+// pose_graph_mem.h — what a context holds of its pose graphs, for the files that work on it: lins_pose_graph_capi.hip
+// (the graphs, the single solve, the rebase, the write-back), lins_team_graph_capi.hip (the team solve over groups of
+// them, with a workspace of its own that the first team solve allocates) and lins_team_pcm_capi.hip (which team factors
+// agree: it reads the graphs' estimates and owns a staging of its own).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +30,14 @@ struct TeamWs {
   uint64_t iterations = 0;
 };
 
+// The staging of lins_team_factors_consistent_batch (lins_team_pcm_capi.hip): grow-only, allocated by its first call.
+struct PcmWs {
+  DevBuf<char> d_up, d_down;  // (bytes) the records | the offsets; the results
+  PinBuf<char> h_up, h_down;
+  Event ev[2];  // around the launch
+  float kernel_ms = 0.f;
+};
+
 struct PgMem {
   int n_slots = 0, F = 0, L = 0;
   std::vector<lins_pg::Graph> g;
@@ -43,6 +52,7 @@ struct PgMem {
   float ms = 0.f;
   uint64_t iterations = 0;
   TeamWs team;
+  PcmWs pcm;
   size_t nq() const { return (size_t)F / lins_pg::kPrefixBlock + 2; }
 };
 

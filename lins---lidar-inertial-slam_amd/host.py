@@ -1017,3 +1017,63 @@ def team_graph_linearize(graphs, factors=(), poses=None, root_variance=None):
     if rc:
         raise RuntimeError(f"lins_host_team_graph_linearize: {rc}")
     return dict(r_factor=rf[:nf], M=M[:nf], r_root=rr[:n - 1], H_root=H[:n - 1], g_root=g[:n - 1])
+
+
+# ---- pairwise-consistent team factors on the CPU (include/lins_host.h lins_host_team_factors_consistent) ----------
+def team_pcm_params(**kw):
+    from ._ctypes_defs import team_pcm_params as rec
+
+    return rec(lib(), **kw)
+
+
+def team_factors_consistent(factors, Tb, Ta, n_factors=None, out=None, **kw):
+    """lins_host_team_factors_consistent of ONE group: factors whose slots are member indices (TeamFactorC records, dicts or
+    tuples), Tb / Ta (n, 12): the f64 estimates of every factor's two frames.  kw: fields of lins_team_pcm_params over the
+    defaults.  n_factors: the count to pass instead of len(factors); out: a TeamPcmResultC to write into (for the
+    refusals).  Returns dict(n_factors, n_kept, n_pairs, n_pairs_kept, exact, nodes_max, kept: the kept factors' indices),
+    or the C return code (a negative int) of a refused call."""
+    from ._ctypes_defs import TeamFactorC, TeamPcmParamsC, TeamPcmResultC, team_factor as rec
+
+    L = lib()
+    fac = [rec(f) for f in factors]
+    n = len(fac) if n_factors is None else int(n_factors)
+    farr = (TeamFactorC * max(len(fac), 1))(*fac)
+    b = np.ascontiguousarray(Tb, np.float64).reshape(-1, 12) if len(fac) else np.zeros((1, 12))
+    a = np.ascontiguousarray(Ta, np.float64).reshape(-1, 12) if len(fac) else np.zeros((1, 12))
+    assert len(a) >= len(fac) and len(b) >= len(fac)
+    prm = team_pcm_params(**kw)
+    res = out if out is not None else TeamPcmResultC()
+    L.lins_host_team_factors_consistent.argtypes = [C.c_int, C.POINTER(TeamFactorC), C.c_void_p, C.c_void_p, C.POINTER(TeamPcmParamsC),
+                                                    C.POINTER(TeamPcmResultC)]
+    L.lins_host_team_factors_consistent.restype = C.c_int
+    rc = L.lins_host_team_factors_consistent(n, farr, b.ctypes.data, a.ctypes.data, C.byref(prm), C.byref(res))
+    return rc if rc else res.as_dict()
+
+
+def team_factors_consistent_graphs(graphs, factors, **kw):
+    """team_factors_consistent with the poses taken from PoseGraph objects: graphs[m] is member m"""
+    from ._ctypes_defs import team_factor as rec
+
+    fac = [rec(f) for f in factors]
+    T = [g.poses_f64() for g in graphs]
+    Tb = np.array([T[f.slot_b][f.id_b] for f in fac]).reshape(-1, 12)
+    Ta = np.array([T[f.slot_a][f.id_a] for f in fac]).reshape(-1, 12)
+    return team_factors_consistent(fac, Tb, Ta, **kw)
+
+
+def team_pcm_clique(adj, pair=None, out=None, **kw):
+    """lins_host_team_pcm_clique: the search and the winners alone.  adj: n 64-bit rows (bit b of row a: a and b are
+    consistent); pair: n keys (default: one pair) -> the result dict, or the C return code of a refused call"""
+    from ._ctypes_defs import TeamPcmParamsC, TeamPcmResultC
+
+    L = lib()
+    rows = np.ascontiguousarray(adj, np.uint64)
+    n = len(rows)
+    keys = np.ascontiguousarray(pair if pair is not None else np.zeros(n), np.int32)
+    assert len(keys) == n
+    prm = team_pcm_params(**kw)
+    res = out if out is not None else TeamPcmResultC()
+    L.lins_host_team_pcm_clique.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(TeamPcmParamsC), C.POINTER(TeamPcmResultC)]
+    L.lins_host_team_pcm_clique.restype = C.c_int
+    rc = L.lins_host_team_pcm_clique(n, rows.ctypes.data if n else None, keys.ctypes.data if n else None, C.byref(prm), C.byref(res))
+    return rc if rc else res.as_dict()

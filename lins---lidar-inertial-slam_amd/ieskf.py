@@ -75,6 +75,8 @@ TEAM_EXPORTS = [
 ]
 # the team graph's calls (include/lins_team.h lins_team_graph_*; team.py wraps them); lib() resolves every one of them
 TEAM_GRAPH_EXPORTS = ["lins_team_factor_from_alignment", "lins_team_graph_solve", "lins_last_team_graph_stats"]
+# the pairwise-consistent team factors (include/lins_team.h; team.py wraps them); lib() resolves every one of them
+TEAM_PCM_EXPORTS = ["lins_team_pcm_default_params", "lins_team_factors_consistent_batch", "lins_last_team_pcm_stats"]
 # the team map's calls (include/lins_map.h; team.py wraps them); lib() resolves every one of them
 TEAM_MAP_EXPORTS = [
     "lins_keyposes_team_select_batch", "lins_last_keyposes_team_stats", "lins_local_map_build_team",
@@ -148,7 +150,7 @@ def lib():
                 if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                     continue  # (an older build under A/B timing)
                 getattr(L, name).restype = C.c_int
-        for name in LIFECYCLE_EXPORTS + SNAPSHOT_EXPORTS + PLACE_EXPORTS + TEAM_EXPORTS + TEAM_MAP_EXPORTS + TEAM_GRAPH_EXPORTS:
+        for name in LIFECYCLE_EXPORTS + SNAPSHOT_EXPORTS + PLACE_EXPORTS + TEAM_EXPORTS + TEAM_MAP_EXPORTS + TEAM_GRAPH_EXPORTS + TEAM_PCM_EXPORTS:
             if os.environ.get("LINS_IESKF_LIB") and not hasattr(L, name):
                 continue  # (an older build under A/B timing)
             getattr(L, name).restype = None if name.endswith("_default_params") else C.c_int

@@ -236,6 +236,72 @@ def graph_stats(ctx):
     return float(ms.value), int(it.value)
 
 
+# ---- pairwise-consistent team factors ----
+def factors_consistent(ctx, groups, member_offsets=None, factor_offsets=None, out=None, **kw):
+    """lins_team_factors_consistent_batch.  groups: tuples (slots, factors) as graph_solve's; kw: fields of
+    lins_team_pcm_params over the defaults (max_translation=, min_cos_rotation=, translation_per_frame=, min_support=,
+    max_nodes=).  member_offsets / factor_offsets: the n + 1 offsets to pass instead of the groups' own, out: a
+    TeamPcmResultC array to write into (for the refusals).  Returns per group dict(n_factors, n_kept, n_pairs, n_pairs_kept,
+    exact, nodes_max, kept: the indices of the kept factors inside the group), or the C return code of a refused call."""
+    from ._ctypes_defs import TeamFactorC, TeamMemberC, TeamPcmParamsC, TeamPcmResultC, team_factor, team_pcm_params
+
+    L = _ieskf.lib()
+    mem, fac, moff, foff = [], [], [0], [0]
+    for slots, factors in groups:
+        mem += [TeamMemberC(int(s), 0) for s in slots]
+        fac += [team_factor(f) for f in factors]
+        moff.append(len(mem)), foff.append(len(fac))
+    n = len(groups)
+    marr, farr = (TeamMemberC * max(len(mem), 1))(*mem), (TeamFactorC * max(len(fac), 1))(*fac)
+    mo = np.ascontiguousarray(moff if member_offsets is None else member_offsets, np.int32)
+    fo = np.ascontiguousarray(foff if factor_offsets is None else factor_offsets, np.int32)
+    prm = team_pcm_params(L, **kw)
+    res = out if out is not None else (TeamPcmResultC * max(n, 1))()
+    L.lins_team_factors_consistent_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(TeamMemberC), C.c_void_p, C.POINTER(TeamFactorC), C.c_void_p,
+                                                     C.POINTER(TeamPcmParamsC), C.POINTER(TeamPcmResultC)]
+    rc = L.lins_team_factors_consistent_batch(ctx._h, n, marr, mo.ctypes.data, farr, fo.ctypes.data, C.byref(prm), res)
+    return rc if rc else [res[k].as_dict() for k in range(n)]
+
+
+def keep_factors(factors, factor_offsets, results):
+    """the factors that factors_consistent kept, compacted in the caller's order: (factors, factor_offsets) ready for
+    lins_team_graph_solve.  factors: the call's factors back to back; factor_offsets: its n + 1 offsets; results: its
+    per-group dicts (or TeamPcmResultC records)."""
+    kept, off = [], [0]
+    for g, r in enumerate(results):
+        idx = r["kept"] if isinstance(r, dict) else r.as_dict()["kept"]
+        first, count = int(factor_offsets[g]), int(factor_offsets[g + 1]) - int(factor_offsets[g])
+        assert all(0 <= i < count for i in idx)
+        kept += [factors[first + i] for i in sorted(idx)]
+        off.append(len(kept))
+    return kept, np.ascontiguousarray(off, np.int32)
+
+
+def pcm_stats(ctx):
+    """HIP-event ms of the last factors_consistent launch"""
+    L, ms = _ieskf.lib(), C.c_float(0)
+    L.lins_last_team_pcm_stats.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    ctx._check(L.lins_last_team_pcm_stats(ctx._h, C.byref(ms)))
+    return ms.value
+
+
+def debug_pcm_clique(ctx, adj, pair=None, out=None, **kw):
+    """lins_debug_team_pcm_clique: the device's search stage alone on given rows, the twin of host.team_pcm_clique"""
+    from ._ctypes_defs import TeamPcmParamsC, TeamPcmResultC, team_pcm_params
+
+    L = _ieskf.lib()
+    rows = np.ascontiguousarray(adj, np.uint64)
+    n = len(rows)
+    keys = np.ascontiguousarray(pair if pair is not None else np.zeros(n), np.int32)
+    assert len(keys) == n
+    prm = team_pcm_params(L, **kw)
+    res = out if out is not None else TeamPcmResultC()
+    L.lins_debug_team_pcm_clique.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(TeamPcmParamsC), C.POINTER(TeamPcmResultC)]
+    L.lins_debug_team_pcm_clique.restype = C.c_int
+    rc = L.lins_debug_team_pcm_clique(ctx._h, n, rows.ctypes.data if n else None, keys.ctypes.data if n else None, C.byref(prm), C.byref(res))
+    return rc if rc else res.as_dict()
+
+
 # ---- the team map ----
 def select(ctx, queries, stride=None):
     """lins_keyposes_team_select_batch.  queries: tuples (centre, radius, pose_leaf, target slots); stride: pairs an entry
